@@ -49,7 +49,74 @@ def parse():
                     "morph triangles, the per-t isosurface stream of 64 times in one call)")
     ap.add_argument("--streams", type=int, default=0, help="extractions in flight: consecutive steps alternate between this many contexts / HIP streams "
                                                            "(0 = auto: 2; 3 from 4 ranks on, where a rank's slab is thin and every step waits for a halo plane)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the Level-0 mesh of the last timed step (rank 0) to DIR/*.npy: a fixed, seeded sample "
+                         "of at most %d vertices and %d triangles, in an order that does not depend on the order the device emitted them"
+                         % (DUMP_ROWS, DUMP_ROWS))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_ROWS = 1 << 20          # rows per sampled array of --dump-outputs: 44 MB in all at most
+DUMP_SEED = 0x5EED0B0E
+
+
+def _mix64(x):
+    "splitmix64 finaliser of a uint64 array"
+    import numpy as np
+    x = x ^ (x >> np.uint64(30))
+    x = x * np.uint64(0xBF58476D1CE4E5B9)
+    x = x ^ (x >> np.uint64(27))
+    x = x * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def _sample_mask(h, n):
+    "rows whose seeded hash falls below a threshold: about 0.95 * DUMP_ROWS of n rows (all of them if n is small)"
+    import numpy as np
+    if n <= DUMP_ROWS:
+        return np.ones(n, dtype=bool)
+    return h < np.uint64(int(0.95 * DUMP_ROWS / n * 2.0 ** 64))
+
+
+def dump_outputs(ctx, outdir):
+    """--dump-outputs: the Level-0 mesh the last timed step left on `ctx` (what cx_level0_download gives its caller), as
+    float arrays that two builds can compare file for file.  Vertices and triangles are sampled by a seeded hash of their
+    content (the edge id; the triangle's three edge ids) and sorted, so the files do not depend on the order in which the
+    device emitted the mesh.  Triangles are written as the edge ids of their corners, starting at the smallest (winding kept).
+      counts.npy             float64 (4,): n_cells, n_vertices, n_triangles, n_border_voxels
+      vertex_edge_ids.npy    float64 (V,): edge ids of the sampled vertices, ascending
+      vertex_xyz.npy         float32 (V, 3): their grid coordinates
+      triangle_edge_ids.npy  float64 (T, 3): the sampled triangles, rows ascending
+    -> {name: shape}"""
+    import numpy as np
+    counts = ctx.counts()
+    xyz, keys, tris = ctx.download_level0(counts)
+    seed = np.uint64(DUMP_SEED)
+    k64 = keys.astype(np.uint64)
+    pick = np.flatnonzero(_sample_mask(_mix64(k64 ^ seed), len(k64)))
+    pick = pick[np.argsort(keys[pick], kind="stable")][:DUMP_ROWS]
+    v_ids, v_xyz = keys[pick].astype(np.float64), np.ascontiguousarray(xyz[pick], dtype=np.float32)
+    del k64, pick
+    tk = keys[tris]                                          # (T, 3) uint32: corners as edge ids
+    h = seed
+    for c in range(3):                                       # symmetric in the corners: the same triangle whatever corner comes first
+        h = h + _mix64(tk[:, c].astype(np.uint64) ^ seed)
+    sel = tk[_sample_mask(_mix64(h), len(tk))]
+    del tk, h
+    r = np.argmin(sel, axis=1)
+    sel = np.take_along_axis(sel, (r[:, None] + np.arange(3)[None, :]) % 3, axis=1)
+    sel = sel[np.lexsort((sel[:, 2], sel[:, 1], sel[:, 0]))][:DUMP_ROWS]
+    arrays = {"counts": np.array([counts[k] for k in ("n_cells", "n_vertices", "n_triangles", "n_border_voxels")], dtype=np.float64),
+              "vertex_edge_ids": v_ids, "vertex_xyz": v_xyz, "triangle_edge_ids": sel.astype(np.float64)}
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def launch_ranks(args):
@@ -506,6 +573,10 @@ def main():
     elapsed, timing, final = run_job(args, torch, dist, ctxs, streams, job, flags, overlap_halo, c_halo=c_halo)
     if watchdog is not None:
         watchdog.cancel()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the contexts: the last timed step's mesh is still on the context that extracted it
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(ctxs[(args.warmup + args.steps - 1) % nstreams], args.dump_outputs)}
     if os.environ.get("BENCH_NO_EVENTS") == "1":      # measurement of what the per-kernel events cost: the same region without them
         el2, _, _ = run_job(args, torch, dist, ctxs, streams, job, flags, overlap_halo, timing=False, c_halo=c_halo)
         if rank == 0:
@@ -702,6 +773,8 @@ def main():
                 "ms_per_step": single[0] / args.steps * 1e3, "value": job.total_samples * args.steps / single[0] / 1e6,
                 "level0_ms": s_sum, "achieved": s_ach, "frac": s_ach / HBM_PEAK_GBS, "kernels": s_kernels,
                 "note": "the same steps on one stream: 4N / sum of the Level-0 kernel durations of one extraction"}
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if weak_line is not None:
             out["weak"] = weak_line
         if projection is not None:

@@ -10,6 +10,9 @@ def test_library_exports_header_symbols():
     from contourist_amd import _ffi, build
     path = build.build()
     assert os.path.exists(path)
+    # through _ffi.load() first: it puts torch's HIP runtime in place before the library binds one.  A bare dlopen first would
+    # bind ROCm's copy, and the process would hold two HIP runtimes: every later test in it that opens a device would fail.
+    L = _ffi.load()
     lib = ctypes.CDLL(path)
     header = open(os.path.join(ROOT, "include", "contourist_hip.h")).read()
     declared = set(re.findall(r"\b(cx_[a-z0-9_]+)\s*\(", header))
@@ -17,7 +20,6 @@ def test_library_exports_header_symbols():
     assert declared == set(_ffi.SYMBOLS), declared ^ set(_ffi.SYMBOLS)
     for name in declared:
         assert hasattr(lib, name), name
-    L = _ffi.load()
     assert b"gfx950" in L.cx_version()
 
 
