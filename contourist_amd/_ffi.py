@@ -29,6 +29,7 @@ SYMBOLS = [
     "cx_extract3d", "cx_extract3d_async", "cx_counts_get", "cx_extract3d_levels", "cx_levels_select", "cx_level0_path", "cx_level0_download", "cx_level0_device_ptrs", "cx_level0_device_records", "cx_level0_download_records",
     "cx_postprocess3d", "cx_postprocess3d_ex", "cx_level0_points_f64", "cx_postprocess3d_mesh", "cx_select_seeded3d", "cx_select_seeded3d_ex", "cx_seeded_masks_download", "cx_set_reference_corner", "cx_level1_download", "cx_level1_device_ptrs", "cx_level1_download_keys", "cx_postprocess3d_shard_begin", "cx_postprocess3d_shard_boundary", "cx_postprocess3d_shard_candidates", "cx_postprocess3d_shard_finish", "cx_level1_write", "cx_surface_geometry",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
+    "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
     "cx_timing_enable", "cx_timing_read", "cx_measure_read_bandwidth", "cx_debug_stamps", "cx_version",
 ]
@@ -158,6 +159,10 @@ def load():
         "cx_morph_eval_many_download": [vp, ctypes.c_int32, vp, vp],
         "cx_morph_eval_many_device_ptrs": [vp, ctypes.c_int32, vp, vp],
         "cx_morph_eval_many_download_all": [vp, vp, vp],
+        "cx_slab4d_begin": [vp, vp],
+        "cx_slab4d_append": [vp, i64, i64, vp],
+        "cx_slab4d_finish": [vp, ctypes.c_int32, vp],
+        "cx_slab4d_download_keys": [vp, vp],
         "cx_contour2d_extract": [vp, vp, ctypes.c_int, i64, i64, vp, ctypes.c_int32, vp, i64, u32, vp, ctypes.POINTER(CxCounts2D)],
         "cx_contour2d_download": [vp, vp, vp, vp],
         "cx_timing_enable": [vp, ctypes.c_int],
@@ -560,6 +565,33 @@ class Context(object):
         tets = np.empty((int(counts["n_tetrahedra"]), 4), dtype=np.int32)
         self._check(self.lib.cx_level1_4d_download(self.handle, pts.ctypes.data, tets.ctypes.data))
         return pts, tets
+
+    # -- a 4-D volume of more than one extraction, slab by slab (cx_slab4d_*) --------------------------------------------
+    def slab4d_begin(self, whole_shape):
+        "start the assembly of a volume of shape whole_shape (n0, n1, n2, n3), marched slab by slab along axis 0"
+        shape = np.ascontiguousarray([int(n) for n in whole_shape], dtype=np.int64)
+        assert shape.shape == (4,)
+        self._check(self.lib.cx_slab4d_begin(self.handle, shape.ctypes.data))
+
+    def slab4d_append(self, i0, owned_planes):
+        """append the slab just marched (extract4d with set_origin4d(i0, 0, 0, 0)): planes i0 .. i0 + owned_planes of the whole volume,
+        the bound array holding one more (the halo) unless it is the last slab"""
+        out = np.zeros(8, dtype=np.int64)
+        self._check(self.lib.cx_slab4d_append(self.handle, int(i0), int(owned_planes), out.ctypes.data))
+        return dict(n_vertices=int(out[0]), n_tetrahedra=int(out[1]), slab_vertices=int(out[2]), slab_tetrahedra=int(out[3]),
+                    pending=int(out[4]), n_slabs=int(out[5]))
+
+    def slab4d_finish(self, nbins=100):
+        "the post-steps of postprocess4d on the assembly; returns what postprocess4d returns (download_level1_4d, morph_triangles follow)"
+        out = np.zeros(8, dtype=np.int64)
+        self._check(self.lib.cx_slab4d_finish(self.handle, int(nbins), out.ctypes.data))
+        return dict(n_vertices=int(out[0]), n_tetrahedra=int(out[1]), n_after_drop=int(out[2]), n_after_tiny=int(out[3]))
+
+    def slab4d_keys(self, counts):
+        "global edge id (int64) of every assembled vertex, in the order of the points"
+        keys = np.empty(int(counts["n_vertices"]), dtype=np.int64)
+        self._check(self.lib.cx_slab4d_download_keys(self.handle, keys.ctypes.data))
+        return keys
 
     def morph_triangles(self):
         "-> (points4d (V,4) float64, segments (S,2) int32 low t -> high t, triangles (T,3) int32 oriented)"

@@ -24,6 +24,7 @@ void cx_state4_free(cx_ctx* ctx) {
     cx_release(S->verts, S->vcap); cx_release(S->vkeys, S->vkeys_cap); cx_release(S->cells, S->ccap); cx_release(S->tets, S->tcap);
     cx_release(S->hash_xyz, S->hash_cap); cx_release(S->signbits, S->signbits_cap); cx_release(S->tet_keep, S->keep_cap);
     cx_release(S->queue, S->qcap); cx_release(S->rounds, S->rounds_cap);
+    cx_slab4_free(S->slab);
     delete S;
     ctx->s4 = nullptr;
 }
@@ -173,6 +174,7 @@ static int settle4(cx_ctx* ctx, cx_state4* S, double value, cx_counts* out) {
     if (c.n_cells <= S->ccap && c.n_vertices <= S->vcap && c.n_triangles <= S->tcap) {
         S->extracted = true;
         S->post_valid = false;
+        S->post_assembled = false;
         S->keep_valid = false;
         S->value = value;
         return 0;

@@ -139,6 +139,29 @@ int cx_grow(cx_ctx* ctx, T*& ptr, C& cap, size_t need) {
     cap = (C)need;
     return CX_OK;
 }
+// The same for a buffer that is appended to (the slab assembly of cx_slab4d.hip): the first `used` elements move into the new buffer,
+// which gets room for half as many again as before when that is more than `need` (a volume of many slabs grows it a few times, not
+// once per slab).  Pointers into the old buffer are dead after the call: kernels get pointers taken after the last grow.
+template <typename T>
+int cx_grow_keep(cx_ctx* ctx, T*& ptr, size_t& cap, size_t used, size_t need) {
+    if (cap >= need && ptr) return CX_OK;
+    if (need == 0) return CX_OK;
+    const size_t want = need > cap + cap / 2 ? need : cap + cap / 2;
+    void* fresh = nullptr;
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess) e = hipMalloc(&fresh, want * sizeof(T));
+    if (e == hipSuccess && ptr && used) e = hipMemcpyAsync(fresh, ptr, used * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        if (fresh) (void)hipFree(fresh);
+        ctx->err = std::string("device buffer (") + std::to_string(want * sizeof(T)) + " bytes): " + hipGetErrorString(e);
+        return (e == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;
+    }
+    if (ptr) (void)hipFree(ptr);
+    ptr = static_cast<T*>(fresh);
+    cap = want;
+    return CX_OK;
+}
 template <typename T, typename C>
 void cx_release(T*& ptr, C& cap) {
     if (ptr) (void)hipFree(ptr);

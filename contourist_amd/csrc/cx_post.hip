@@ -2215,16 +2215,47 @@ extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double*
 extern "C" int cx_postprocess4d(cx_ctx* ctx, int32_t nbins, int64_t* out_counts) {
     return cx_postprocess4d_points(ctx, nbins, nullptr, out_counts);
 }
-extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double* points_xyzt, int64_t* out_counts) {
-    if (!ctx || nbins <= 0) return CX_ERR_INVALID;
-    cx_state4* G = ctx->s4;
-    if (!G || !G->extracted) { ctx->err = "cx_postprocess4d: no valid 4-D extraction"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
-    cx_post_state* S;
-    int rc = cxp_state(ctx, &S);
-    if (rc) return rc;
-    const uint32_t nv = (uint32_t)G->counts.n_vertices, nt = (uint32_t)G->counts.n_triangles;
+// drop_instant, the seeded selection's mask (keep, or null), the tiny collapse and the compaction of the survivors into S->tri_out, on the
+// points and priorities already in S->pts / S->prio (nv, nt > 0).  counts[2], [3]: tetrahedra after drop_instant / the tiny collapse
+static int cxp_post4_tets(cx_ctx* ctx, cx_post_state* S, const int32_t* tets, uint32_t nv, uint32_t nt, const double corner[4], const uint8_t* keep,
+                          int64_t* counts, uint32_t* nt2_out) {
+    int rc;
     hipStream_t st = ctx->stream;
+    double* pts = (double*)S->pts.p;
+    uint32_t* prio = (uint32_t*)S->prio.p;
+    uint8_t* moved = (uint8_t*)S->rep.p;
+    uint8_t* alive = (uint8_t*)S->alive.p;
+    u64* parent = (u64*)S->parent.p;
+    uint32_t* misc = (uint32_t*)S->misc.p;
+    hipLaunchKernelGGL(cxp_k_drop_instant, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1e-7);
+    // cx_select_seeded4d: only the tetrahedra of the selected components exist
+    if (keep) hipLaunchKernelGGL(cxp_k_and_mask, dim3(cxp_blocks(nt)), dim3(256), 0, st, alive, keep, nt);
+    CXP_HIP(ctx, hipMemsetAsync(misc + 4, 0, 2 * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cxp_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 4);
+    hipLaunchKernelGGL(cxp_k_iota64, dim3(cxp_blocks(nv)), dim3(256), 0, st, parent, nv);
+    CXP_HIP(ctx, hipMemsetAsync(moved, 0, nv, st));
+    hipLaunchKernelGGL(cxp_k_tiny4, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1.0 / corner[0], 1.0 / corner[1],
+                       1.0 / corner[2], 1.0 / corner[3], 1e-3, parent, prio, moved);
+    hipLaunchKernelGGL(cxp_k_move4, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, parent, moved, nv);
+    hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cxp_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 5);
+    uint32_t* tflag = (uint32_t*)S->flags.p;
+    uint32_t* tnew = (uint32_t*)S->scan.p;
+    hipLaunchKernelGGL(cxp_k_alive_u32, dim3(cxp_blocks(nt)), dim3(256), 0, st, alive, nt, tflag);
+    if ((rc = cxp_scan(ctx, S, tflag, tnew, nt, misc + 2))) return rc;
+    uint32_t h[3];
+    CXP_HIP(ctx, hipMemcpyAsync(h, misc + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CXP_HIP(ctx, hipMemcpyAsync(h + 2, misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CXP_HIP(ctx, hipStreamSynchronize(st));
+    counts[2] = h[0]; counts[3] = h[1];
+    const uint32_t nt2 = h[2];
+    if ((rc = cxp_reserve(ctx, S->tri_out, (size_t)(nt2 + 1) * 4 * sizeof(int32_t)))) return rc;
+    hipLaunchKernelGGL(cxp_k_compact_tets, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, tnew, nt, (int32_t*)S->tri_out.p);
+    CXP_HIP(ctx, hipGetLastError());
+    *nt2_out = nt2;
+    return CX_OK;
+}
+static int cxp_reserve4(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt) {
+    int rc;
     if ((rc = cxp_reserve(ctx, S->pts, (size_t)(nv + 1) * 4 * sizeof(double)))) return rc;
     if ((rc = cxp_reserve(ctx, S->prio, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
     if ((rc = cxp_reserve(ctx, S->rep, (size_t)nv + 16))) return rc;
@@ -2232,14 +2263,25 @@ extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double*
     if ((rc = cxp_reserve(ctx, S->parent, (size_t)(nv + 1) * sizeof(u64)))) return rc;
     if ((rc = cxp_reserve(ctx, S->flags, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
     if ((rc = cxp_reserve(ctx, S->scan, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
+    return CX_OK;
+}
+extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double* points_xyzt, int64_t* out_counts) {
+    if (!ctx || nbins <= 0) return CX_ERR_INVALID;
+    cx_state4* G = ctx->s4;
+    if (!G || !G->extracted) { ctx->err = "cx_postprocess4d: no valid 4-D extraction"; return CX_ERR_STATE; }
+    if (G->slab && G->slab->open) { ctx->err = "cx_postprocess4d: a slab assembly is open (cx_slab4d_finish post-processes it)"; return CX_ERR_STATE; }
+    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    cx_post_state* S;
+    int rc = cxp_state(ctx, &S);
+    if (rc) return rc;
+    const uint32_t nv = (uint32_t)G->counts.n_vertices, nt = (uint32_t)G->counts.n_triangles;
+    hipStream_t st = ctx->stream;
+    if ((rc = cxp_reserve4(ctx, S, nv, nt))) return rc;
     double* pts = (double*)S->pts.p;
     uint32_t* prio = (uint32_t*)S->prio.p;
-    uint8_t* moved = (uint8_t*)S->rep.p;
-    uint8_t* alive = (uint8_t*)S->alive.p;
-    u64* parent = (u64*)S->parent.p;
-    uint32_t* misc = (uint32_t*)S->misc.p;
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t nt2 = 0;
+    G->post_assembled = false;
     if (nv && nt) {
         const uint32_t n1 = (uint32_t)G->n[1], n2 = (uint32_t)G->n[2], n3 = (uint32_t)G->n[3];
         // an array with a rim of samples around the reference's grid (negative origin, cx_set_origin4d): the reference's own
@@ -2257,34 +2299,53 @@ extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double*
         } else
         hipLaunchKernelGGL(cxp_k_vertices4_f64, dim3(cxp_blocks(nv)), dim3(256), 0, st, G->grid, n1, n2, n3, cx_fdiv_make(n1 * n2 * n3),
                            cx_fdiv_make(n2 * n3), cx_fdiv_make(n3), G->value, G->vkeys, nv, min_interval, pts, prio, org[0], org[1], org[2], org[3]);
-        hipLaunchKernelGGL(cxp_k_drop_instant, dim3(cxp_blocks(nt)), dim3(256), 0, st, G->tets, alive, nt, pts, 1e-7);
-        // cx_select_seeded4d: only the tetrahedra of the selected components exist
-        if (G->keep_valid) hipLaunchKernelGGL(cxp_k_and_mask, dim3(cxp_blocks(nt)), dim3(256), 0, st, alive, (const uint8_t*)G->tet_keep, nt);
-        CXP_HIP(ctx, hipMemsetAsync(misc + 4, 0, 2 * sizeof(uint32_t), st));
-        hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cxp_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 4);
-        hipLaunchKernelGGL(cxp_k_iota64, dim3(cxp_blocks(nv)), dim3(256), 0, st, parent, nv);
-        CXP_HIP(ctx, hipMemsetAsync(moved, 0, nv, st));
-        hipLaunchKernelGGL(cxp_k_tiny4, dim3(cxp_blocks(nt)), dim3(256), 0, st, G->tets, alive, nt, pts, 1.0 / corner[0], 1.0 / corner[1],
-                           1.0 / corner[2], 1.0 / corner[3], 1e-3, parent, prio, moved);
-        hipLaunchKernelGGL(cxp_k_move4, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, parent, moved, nv);
-        hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cxp_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 5);
-        uint32_t* tflag = (uint32_t*)S->flags.p;
-        uint32_t* tnew = (uint32_t*)S->scan.p;
-        hipLaunchKernelGGL(cxp_k_alive_u32, dim3(cxp_blocks(nt)), dim3(256), 0, st, alive, nt, tflag);
-        if ((rc = cxp_scan(ctx, S, tflag, tnew, nt, misc + 2))) return rc;
-        uint32_t h[3];
-        CXP_HIP(ctx, hipMemcpyAsync(h, misc + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CXP_HIP(ctx, hipMemcpyAsync(h + 2, misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CXP_HIP(ctx, hipStreamSynchronize(st));
-        counts[2] = h[0]; counts[3] = h[1];
-        nt2 = h[2];
-        if ((rc = cxp_reserve(ctx, S->tri_out, (size_t)(nt2 + 1) * 4 * sizeof(int32_t)))) return rc;
-        hipLaunchKernelGGL(cxp_k_compact_tets, dim3(cxp_blocks(nt)), dim3(256), 0, st, G->tets, alive, tnew, nt, (int32_t*)S->tri_out.p);
-        CXP_HIP(ctx, hipGetLastError());
+        if ((rc = cxp_post4_tets(ctx, S, G->tets, nv, nt, corner, G->keep_valid ? (const uint8_t*)G->tet_keep : nullptr, counts, &nt2))) return rc;
     }
     S->nv_out = nv; S->nt_out = nt2;
     counts[0] = nv; counts[1] = nt2;
     G->post_valid = true;
+    if (out_counts) memcpy(out_counts, counts, sizeof(counts));
+    return CX_OK;
+}
+
+// ---- the same post-steps on a slab assembly (cx_slab4d.hip): the points were interpolated per slab in the whole volume's lattice, the
+// priority of a vertex is its index (the assembly is in ascending global edge id, the order the edge ids give a single extraction)
+__global__ void cxp_k_bin_times_iota(double* pts, uint32_t nv, double min_interval, uint32_t* prio) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const double t = pts[(size_t)v * 4 + 3];
+    pts[(size_t)v * 4 + 3] = (double)(long long)(t / min_interval) * min_interval;
+    prio[v] = v;
+}
+int cx_slab4_check(cx_ctx* ctx, cx_slab4* A);
+extern "C" int cx_slab4d_finish(cx_ctx* ctx, int32_t nbins, int64_t* out_counts) {
+    if (!ctx || nbins <= 0) return CX_ERR_INVALID;
+    cx_state4* G = ctx->s4;
+    cx_slab4* A = G ? G->slab : nullptr;
+    if (!A || !A->open) { ctx->err = "cx_slab4d_finish: no assembly open (cx_slab4d_begin)"; return CX_ERR_STATE; }
+    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc;
+    if ((rc = cx_slab4_check(ctx, A))) return rc;
+    cx_post_state* S;
+    if ((rc = cxp_state(ctx, &S))) return rc;
+    const uint32_t nv = A->nv, nt = A->nt;
+    hipStream_t st = ctx->stream;
+    if ((rc = cxp_reserve4(ctx, S, nv, nt))) return rc;
+    int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t nt2 = 0;
+    if (nv && nt) {
+        double corner[4];
+        for (int a = 0; a < 4; a++) corner[a] = (double)(A->whole[a] - 1);
+        const double min_interval = corner[3] * (1.0 / (double)nbins);
+        CXP_HIP(ctx, hipMemcpyAsync(S->pts.p, A->pts, (size_t)nv * 4 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(cxp_k_bin_times_iota, dim3(cxp_blocks(nv)), dim3(256), 0, st, (double*)S->pts.p, nv, min_interval, (uint32_t*)S->prio.p);
+        if ((rc = cxp_post4_tets(ctx, S, A->tets, nv, nt, corner, nullptr, counts, &nt2))) return rc;
+    }
+    S->nv_out = nv; S->nt_out = nt2;
+    counts[0] = nv; counts[1] = nt2;
+    A->open = false;
+    G->post_valid = true;
+    G->post_assembled = true;
     if (out_counts) memcpy(out_counts, counts, sizeof(counts));
     return CX_OK;
 }
@@ -2789,7 +2850,8 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
         G4.value = G->value;
         // the march's table already emits every tetrahedron in that order (tools/gen_tables.py orient_tet: exact, and valid
         // where samples EQUAL the isovalue and the determinant below vanishes); CX_TETS_ORIENT=1 (debug) recomputes it from the data
-        if (cx_debug_knob("CX_TETS_ORIENT", 0))
+        // (not on a slab assembly: its tetrahedra come from several grids, G->grid is only the last slab's)
+        if (!G->post_assembled && cx_debug_knob("CX_TETS_ORIENT", 0))
             hipLaunchKernelGGL(cxp_k_tets_orient, dim3(cxp_blocks(nt)), dim3(256), 0, st, (int32_t*)S->tri_out.p, nt, prio, G4);
         hipLaunchKernelGGL(cxp_k_morph_count, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, nt, pts, prio, mm, cnt);
         if ((rc = cxp_scan(ctx, S, cnt, off, nt, misc + 1))) return rc;

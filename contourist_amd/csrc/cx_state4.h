@@ -41,6 +41,40 @@ void cx_launch_emit_tets(const cx_params4& P, hipStream_t s);
 void cx_launch_hash_xyz(uint64_t* table, uint32_t n0, uint32_t n1, uint32_t n2, const uint32_t org[4], hipStream_t s);
 const uint64_t* cx_pent_lut_device();
 
+// Assembly of a volume marched slab by slab along axis 0 (cx_slab4d_begin / _append / _finish; cx_slab4d.hip, cx_post.hip).  Slab
+// i0 .. i1 is marched with origin (i0,0,0,0) and, unless it is the last, with plane i1 as a halo.  Its OWNED vertices (lower lattice
+// point below the halo) are appended in ascending edge id, so the whole assembly is in ascending GLOBAL edge id; tetrahedra are
+// appended with assembly indices, a reference to a halo vertex is held as -(1 + h) until the next append resolves entry h of `pend`.
+// Every assembly buffer is grown by cx_slab4_grow (which keeps its contents); kernels get pointers taken after the last grow.
+struct cx_slab4 {
+    bool open = false;              // between cx_slab4d_begin and cx_slab4d_finish
+    int64_t whole[4] = {0, 0, 0, 0};
+    int64_t next_i0 = 0;            // plane the next append starts at
+    int64_t nslabs = 0;
+    double value = 0.0;             // isovalue of the first slab (every slab must use it)
+    uint32_t nv = 0, nt = 0;        // assembled vertices / tetrahedra
+    uint32_t npend = 0;             // halo vertices of the last slab, resolved by the next append
+    uint32_t pend_t0 = 0;           // first tetrahedron of the last slab (the only ones that may hold pending references)
+    uint64_t* keys = nullptr;       // [nv] global edge id ((linear index in the whole volume << 4) | direction)
+    size_t keys_cap = 0;
+    double* pts = nullptr;          // [nv * 4] float64 crossing points in the whole volume's lattice (t not yet binned)
+    size_t pts_cap = 0;
+    int32_t* tets = nullptr;        // [nt * 4]
+    size_t tets_cap = 0;
+    uint32_t* pend = nullptr;       // [npend] the next slab's local edge ids of the last slab's halo vertices
+    size_t pend_cap = 0;
+    // scratch of one append: radix sort of (edge id, source) pairs, digit counts per unit, their scan, vertex map
+    uint32_t *ka = nullptr, *kb = nullptr, *va = nullptr, *vb = nullptr;
+    size_t ka_cap = 0, kb_cap = 0, va_cap = 0, vb_cap = 0;
+    uint32_t *hist = nullptr, *offs = nullptr, *sums = nullptr, *flag = nullptr, *pos = nullptr;
+    size_t hist_cap = 0, offs_cap = 0, sums_cap = 0, flag_cap = 0, pos_cap = 0;
+    int32_t *vmap = nullptr, *resolved = nullptr;
+    size_t vmap_cap = 0, resolved_cap = 0;
+    uint32_t* cnt = nullptr;        // [16] device counters
+    size_t cnt_cap = 0;
+};
+void cx_slab4_free(cx_slab4*& A);
+
 struct cx_state4 {
     const float* grid = nullptr;
     float* grid_owned = nullptr;
@@ -68,6 +102,8 @@ struct cx_state4 {
     int64_t origin[4] = {0, 0, 0, 0};
     bool extracted = false;
     bool post_valid = false;
+    bool post_assembled = false;     // the post-pass result is a slab assembly's (cx_slab4d_finish): tetrahedra already oriented, G->grid not its own
+    cx_slab4* slab = nullptr;
     bool pending = false;            // a cx_extract4d_async is enqueued, its counters not yet looked at (cx_counts4d_get)
     double pending_value = 0.0;
     uint32_t pending_flags = 0;

@@ -57,6 +57,12 @@ class GridContour4D(object):
     reference's search reaches from them (80-neighbour growth: tetrahedral.py:396-463 with OFFSETS4D,
     pentatopes.py:32-39; on the device: cx_select_seeded4d).  march() always returns the whole Level-0 mesh."""
 
+    # One extraction addresses its samples and edges with 32-bit ids, (linear index << 4) | direction: 2^28 samples at most
+    # (cx_grid4d_upload).  A larger volume -- a 256^3 series of 32 steps is 2^29 samples -- is marched slab by slab along axis 0 (each
+    # slab with one plane of its upper neighbour) and assembled on the device into ONE mesh with global edge ids (cx_slab4d_*), which
+    # then goes through the post-steps once.  Lowered by the tests to force the slab path on small volumes.
+    MAX_SAMPLES_PER_EXTRACTION = 1 << 28
+
     def __init__(self, corner, samples, value, segment_endpoints=None, linear_interpolate=True, callback=None,
                  device=None, diagonal="cpython310", context=None, voxel_range=None, origin=(0, 0, 0, 0), function=None):
         self.corner = np.array(corner, dtype=int)
@@ -102,9 +108,76 @@ class GridContour4D(object):
             self._ctx = _ffi.Context(self.device)
         return self._ctx
 
+    # -- volumes of more than one extraction ----------------------------------------------------------------------
+    def _in_slabs(self):
+        "more samples than one extraction addresses: the volume goes through the device slab by slab"
+        return int(np.prod(self.shape, dtype=np.int64)) > int(self.MAX_SAMPLES_PER_EXTRACTION)
+
+    def _slab_planes(self):
+        "planes of axis 0 per slab, so that a slab plus its halo plane stays within one extraction"
+        per_plane = int(self.shape[1]) * int(self.shape[2]) * int(self.shape[3])
+        planes = int(self.MAX_SAMPLES_PER_EXTRACTION) // per_plane - 1
+        if planes < 2:
+            raise ValueError("a plane of %d x %d x %d samples leaves no room for a slab of two planes and its halo in one extraction "
+                             "(%d samples)" % (self.shape[1], self.shape[2], self.shape[3], int(self.MAX_SAMPLES_PER_EXTRACTION)))
+        return planes
+
+    _slab_bounds = staticmethod(tetrahedral.GridContour3d._slab_bounds)
+
+    def _check_slab_scope(self):
+        "what the slab path covers (as in 3-D): exhaustive search, linear interpolation, an array without a rim"
+        if (self.end_points is not None and len(self.end_points)) or self.voxel_range is not None or not self.linear_interpolate \
+                or any(self.origin):
+            raise NotImplementedError("a 4-D volume of more than %d samples is marched in slabs: exhaustive search, linear interpolation "
+                                      "and an array without a rim only (no end points, no voxel range)" % int(self.MAX_SAMPLES_PER_EXTRACTION))
+
+    def _find_tetrahedra_in_slabs(self, nbins):
+        """the march slab by slab (origin (i0,0,0,0), one halo plane) assembled on the device (cx_slab4d_append), then the post-steps
+        on the whole assembly (cx_slab4d_finish).  Vertices in ascending global edge id, keys int64."""
+        self._check_slab_scope()
+        planes = self._slab_planes()
+        s = self.samples
+        on_device = grid_field._is_torch(s)
+        if on_device:
+            assert s.is_cuda and s.is_contiguous() and str(s.dtype) == "torch.float32", \
+                "device samples must be a contiguous float32 tensor on the GPU"
+        else:
+            s = np.ascontiguousarray(s, dtype=np.float32)
+        n0 = int(self.shape[0])
+        bounds = self._slab_bounds(n0, planes)
+        ctx = self.context()
+        totals = dict(n_cells=0, n_vertices=0, n_tetrahedra=0, n_border_voxels=0)
+        ctx.slab4d_begin(self.shape)
+        try:
+            for (i0, i1) in bounds:
+                local = s[i0:i1 + (1 if i1 < n0 else 0)]
+                ctx.set_origin4d(i0, 0, 0, 0)
+                if on_device:
+                    ctx.adopt_device_grid4d(local.data_ptr(), tuple(int(n) for n in local.shape), keepalive=s)
+                else:
+                    ctx.upload_grid4d(local)
+                counts = ctx.extract4d(self.value, self.flags)
+                ctx.slab4d_append(i0, i1 - i0)
+                for k in totals:
+                    totals[k] += int(counts[k])
+        finally:
+            ctx.set_origin4d(*self.origin)
+        post = ctx.slab4d_finish(nbins)
+        pts, tets = ctx.download_level1_4d(post)
+        keys = ctx.slab4d_keys(post)
+        self._counts = None
+        self._interp_vertices = None
+        self.post_counts = post
+        self.n_components = None
+        self._slab_counts = dict(totals, n_slabs=len(bounds), n_vertices=int(len(keys)), n_tetrahedra=int(len(tets)))
+        return dict(points4d=pts, keys=keys, tetrahedra=tets, counts=post)
+
     def march(self):
         """Level 0: the hyper-voxel march alone.  returns dict(xyzt (V,4) f32 grid coords, keys (V,) u32 edge ids,
         tetrahedra (T,4) i32, counts)"""
+        if self._in_slabs():
+            raise NotImplementedError("a 4-D volume of more than %d samples has no single Level-0 extraction: find_tetrahedra() marches "
+                                      "it in slabs" % int(self.MAX_SAMPLES_PER_EXTRACTION))
         ctx = self.context()
         ctx.set_origin4d(*self.origin)
         s = self.samples
@@ -122,7 +195,10 @@ class GridContour4D(object):
     def find_tetrahedra(self, nbins=100):
         """GridContour4D.find_tetrahedra (pentatopes.py:101-125) on the device: march, bin_times(nbins),
         drop_instant_tetrahedra, remove_tiny_simplices(1e-3).  returns dict(points4d (V,4) float64 grid
-        coordinates, keys (V,) edge ids, tetrahedra (T,4) int32, counts)"""
+        coordinates, keys (V,) edge ids, tetrahedra (T,4) int32, counts).  A volume of more than MAX_SAMPLES_PER_EXTRACTION
+        samples is marched in slabs and assembled on the device: keys are then int64 global edge ids (and self._slab_counts is set)"""
+        if self._in_slabs():
+            return self._find_tetrahedra_in_slabs(nbins)
         L = self.march()
         ctx = self.context()
         self._interp_vertices = None

@@ -344,6 +344,29 @@ int cx_morph_eval_many_device_ptrs(cx_ctx* ctx, int32_t i, void** points_xyz, vo
  * doubles), the triangles likewise (indices local to their surface) */
 int cx_morph_eval_many_download_all(cx_ctx* ctx, double* points_xyz, int32_t* triangles);
 
+/* ---- 4-D volumes of more than 2^28 samples: marched slab by slab along axis 0, assembled on the device ----------------------------
+ * One extraction addresses 2^28 samples (32-bit edge ids).  A larger volume is marched in slabs of whole planes, each with the next
+ * plane as a halo (all but the last), and assembled into ONE mesh on the device:
+ *     cx_slab4d_begin(ctx, whole_shape)                              whole_shape = {n0, n1, n2, n3} of the whole volume
+ *     per slab, in axis-0 order:  bind planes i0 .. i1 (+ halo plane i1 unless last) with cx_grid4d_upload / _adopt_device,
+ *                                 cx_set_origin4d(ctx, i0, 0, 0, 0), cx_extract4d, cx_slab4d_append(ctx, i0, i1 - i0, counts)
+ *     cx_slab4d_finish(ctx, nbins, counts)                           the post-steps of cx_postprocess4d on the assembly
+ * The append keeps the slab's OWNED vertices (lower lattice point below its halo plane) in ascending edge id, so the assembly is in
+ * ascending GLOBAL edge id ((linear index in the whole volume << 4) | direction; cx_slab4d_download_keys) and a vertex's index is its
+ * priority; points are float64 in the whole volume's lattice, bit for bit those of a single extraction.  Tetrahedra get assembly
+ * indices; a reference to a halo-plane vertex is resolved by the next slab's append.  The march's table emits every tetrahedron
+ * oriented, so the assembly is oriented as a single extraction is.  append out_counts (8 x int64): [0] assembled vertices, [1] assembled
+ * tetrahedra, [2] this slab's new vertices, [3] its tetrahedra, [4] halo vertices pending, [5] slabs.  finish out_counts as
+ * cx_postprocess4d's; afterwards cx_level1_4d_download, cx_morph_triangles (which then skips any data-driven orientation and does not
+ * read the grid, only the last slab's by then), cx_morph_eval* work as after cx_postprocess4d.
+ * CX_ERR_STATE: a slab out of order, cx_postprocess4d between begin and finish, finish with planes missing or references unresolved.
+ * A later cx_extract4d, cx_postprocess4d or cx_slab4d_begin invalidates an assembled result, as a new post-pass does a single one. */
+int cx_slab4d_begin(cx_ctx* ctx, const int64_t* whole_shape);
+int cx_slab4d_append(cx_ctx* ctx, int64_t i0, int64_t owned_planes, int64_t* out_counts);
+int cx_slab4d_finish(cx_ctx* ctx, int32_t nbins, int64_t* out_counts);
+/* the global edge id of every assembled vertex (n_vertices int64, the order of the points) */
+int cx_slab4d_download_keys(cx_ctx* ctx, int64_t* keys);
+
 /* ---- 2-D contour lines at several isovalues ------------------------------------------------------
  * Replaces triangulated.Grid2DContour (search_grid :198-212, find_initial_contour_pairs :299-320,
  * expand_contour_pairs :322-331, get_contour_sequences :226-297; triangulated.py) for one sample array and ALL
