@@ -25,7 +25,7 @@ CX_KERNEL_TILED = 0x800
 # every symbol include/contourist_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "cx_ctx_create", "cx_ctx_destroy", "cx_last_error", "cx_set_stream", "cx_synchronize",
-    "cx_grid_upload", "cx_grid_adopt_device", "cx_grid_shadow_f64", "cx_set_origin", "cx_reserve",
+    "cx_grid_upload", "cx_grid_adopt_device", "cx_grid_upload_typed", "cx_grid_adopt_device_typed", "cx_grid_info", "cx_grid_shadow_f64", "cx_set_origin", "cx_reserve",
     "cx_extract3d", "cx_extract3d_async", "cx_counts_get", "cx_extract3d_levels", "cx_levels_select", "cx_level0_path", "cx_level0_download", "cx_level0_device_ptrs", "cx_level0_device_records", "cx_level0_download_records",
     "cx_postprocess3d", "cx_postprocess3d_ex", "cx_level0_points_f64", "cx_postprocess3d_mesh", "cx_select_seeded3d", "cx_select_seeded3d_ex", "cx_seeded_masks_download", "cx_set_reference_corner", "cx_level1_download", "cx_level1_device_ptrs", "cx_level1_download_keys", "cx_postprocess3d_shard_begin", "cx_postprocess3d_shard_boundary", "cx_postprocess3d_shard_candidates", "cx_postprocess3d_shard_finish", "cx_level1_write", "cx_surface_geometry",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
@@ -33,6 +33,46 @@ SYMBOLS = [
     "cx_contour2d_extract", "cx_contour2d_download",
     "cx_timing_enable", "cx_timing_read", "cx_measure_read_bandwidth", "cx_debug_stamps", "cx_version",
 ]
+# sample types of a 3-D grid the kernels read as they are (CX_DTYPE_*): each converts to fp32 exactly.  Other types (int32, int64,
+# float64) are not exact in fp32 and are widened on the host, as every type was before.
+DTYPE_CODES = {"float32": 0, "uint8": 1, "int8": 2, "uint16": 3, "int16": 4, "float16": 5, "bfloat16": 6}
+DTYPE_NAMES = {v: k for k, v in DTYPE_CODES.items()}
+
+
+def dtype_code(dtype):
+    """CX_DTYPE_* code of a numpy dtype, a torch dtype or a name ("int16", torch.bfloat16, np.uint8, ...); ValueError if the
+    kernels do not read that type"""
+    name = str(dtype)
+    if name.startswith("torch."):
+        name = name[len("torch."):]
+    else:
+        try:
+            name = np.dtype(dtype).name
+        except TypeError:
+            pass
+    if name not in DTYPE_CODES:
+        raise ValueError("sample type %s is not one the 3-D kernels read (supported: %s)" % (dtype, ", ".join(DTYPE_CODES)))
+    return DTYPE_CODES[name]
+
+
+def native_array(array):
+    """a numpy sample array of a type the kernels read, contiguous and in the machine's byte order (a big-endian '>i2' volume, as
+    np.fromfile or FITS files give, is byte-swapped here; its raw bytes would be other numbers to the kernels)"""
+    a = np.asarray(array)
+    if not a.dtype.isnative:
+        a = a.astype(a.dtype.newbyteorder("="))
+    return np.ascontiguousarray(a)
+
+
+def native_dtype(dtype):
+    "True if a 3-D grid of this numpy / torch dtype is marched as it is (no fp32 copy)"
+    try:
+        dtype_code(dtype)
+        return True
+    except ValueError:
+        return False
+
+
 CX_MESH_OF_THE_MARCH = 8      # cx_postprocess3d_mesh flags bit 3: the triangles are ones the march emitted (at most two per edge before merges)
 CX2_ALL_CHAINS = 1
 CX2_NO_DEDUPE = 2
@@ -99,6 +139,9 @@ def load():
         "cx_synchronize": [vp],
         "cx_grid_upload": [vp, vp, i64, i64, i64],
         "cx_grid_adopt_device": [vp, vp, i64, i64, i64],
+        "cx_grid_upload_typed": [vp, vp, ctypes.c_int32, i64, i64, i64],
+        "cx_grid_adopt_device_typed": [vp, vp, ctypes.c_int32, i64, i64, i64],
+        "cx_grid_info": [vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)],
         "cx_grid_shadow_f64": [vp, vp, i64, i64, i64],
         "cx_set_origin": [vp, i64, i64, i64],
         "cx_reserve": [vp, i64, i64, i64],
@@ -227,11 +270,34 @@ class Context(object):
         self.shape = tuple(int(n) for n in a.shape)
         self._keep = None
 
-    def adopt_device_grid(self, device_ptr, shape, keepalive=None):
+    def upload_grid_native(self, array):
+        """the samples in their own type when the kernels read it (uint8, int8, uint16, int16, float16: n*sizeof(T) bytes on
+        the device, no fp32 copy); any other type is widened to fp32 as upload_grid does"""
+        a = np.asarray(array)
+        assert a.ndim == 3, "3-D sample array expected"
+        if not native_dtype(a.dtype) or dtype_code(a.dtype) == 0:
+            return self.upload_grid(a)
+        a = native_array(a)
+        self._check(self.lib.cx_grid_upload_typed(self.handle, a.ctypes.data, dtype_code(a.dtype), *a.shape))
+        self.shape = tuple(int(n) for n in a.shape)
+        self._keep = None
+
+    def adopt_device_grid(self, device_ptr, shape, keepalive=None, dtype="float32"):
+        "samples already on the device (contiguous, of `dtype`: float32 or a type of DTYPE_CODES), not copied"
         assert len(shape) == 3
-        self._check(self.lib.cx_grid_adopt_device(self.handle, ctypes.c_void_p(int(device_ptr)), *[int(n) for n in shape]))
+        code = dtype_code(dtype)
+        if code == 0:
+            self._check(self.lib.cx_grid_adopt_device(self.handle, ctypes.c_void_p(int(device_ptr)), *[int(n) for n in shape]))
+        else:
+            self._check(self.lib.cx_grid_adopt_device_typed(self.handle, ctypes.c_void_p(int(device_ptr)), code, *[int(n) for n in shape]))
         self.shape = tuple(int(n) for n in shape)
         self._keep = keepalive
+
+    def grid_info(self):
+        "dict(dtype=name of the bound grid's sample type, device_bytes=what the context holds for it: 0 for an adopted grid)"
+        dt, nb = ctypes.c_int32(), ctypes.c_int64()
+        self._check(self.lib.cx_grid_info(self.handle, ctypes.byref(dt), ctypes.byref(nb)))
+        return dict(dtype=DTYPE_NAMES[int(dt.value)], device_bytes=int(nb.value))
 
     def shadow_grid_f64(self, array=None):
         """float64 originals of the bound samples (None drops them): Level 1 interpolates the crossings on these, as the

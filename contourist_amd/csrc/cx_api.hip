@@ -129,30 +129,46 @@ static int set_grid_dims(cx_ctx* ctx, int64_t n0, int64_t n1, int64_t n2) {
     return CX_OK;
 }
 
-extern "C" int cx_grid_upload(cx_ctx* ctx, const float* host, int64_t n0, int64_t n1, int64_t n2) {
+extern "C" int cx_grid_upload_typed(cx_ctx* ctx, const void* host, int32_t dtype, int64_t n0, int64_t n1, int64_t n2) {
     if (!ctx || !host) return CX_ERR_INVALID;
+    if (!cx_dtype_valid(dtype)) return fail(ctx, CX_ERR_INVALID, ("cx_grid_upload_typed: unknown sample type " + std::to_string(dtype)).c_str());
     CX_HIP(ctx, hipSetDevice(ctx->device));
     int rc = set_grid_dims(ctx, n0, n1, n2);
     if (rc) return rc;
-    const size_t bytes = (size_t)(n0 * n1 * n2) * sizeof(float);
-    {
-        size_t have = ctx->grid_owned_bytes / sizeof(float);
-        rc = cx_grow(ctx, ctx->grid_owned, have, (size_t)(n0 * n1 * n2));
-        ctx->grid_owned_bytes = have * sizeof(float);
-        if (rc) return rc;
-    }
+    ctx->grid = {nullptr, CX_DTYPE_F32};
+    const size_t bytes = (size_t)(n0 * n1 * n2) * cx_dtype_size(dtype);
+    rc = cx_grow(ctx, ctx->grid_owned, ctx->grid_owned_bytes, bytes);   // bytes: a grid of another type reuses the buffer
+    if (rc) return rc;
     CX_HIP(ctx, hipMemcpyAsync(ctx->grid_owned, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->grid = ctx->grid_owned;
+    ctx->grid = {ctx->grid_owned, dtype};
+    return CX_OK;
+}
+
+extern "C" int cx_grid_upload(cx_ctx* ctx, const float* host, int64_t n0, int64_t n1, int64_t n2) {
+    return cx_grid_upload_typed(ctx, host, CX_DTYPE_F32, n0, n1, n2);
+}
+
+extern "C" int cx_grid_adopt_device_typed(cx_ctx* ctx, const void* device_ptr, int32_t dtype, int64_t n0, int64_t n1, int64_t n2) {
+    if (!ctx || !device_ptr) return CX_ERR_INVALID;
+    if (!cx_dtype_valid(dtype)) return fail(ctx, CX_ERR_INVALID, ("cx_grid_adopt_device_typed: unknown sample type " + std::to_string(dtype)).c_str());
+    CX_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = set_grid_dims(ctx, n0, n1, n2);
+    if (rc) return rc;
+    ctx->grid = {device_ptr, dtype};
     return CX_OK;
 }
 
 extern "C" int cx_grid_adopt_device(cx_ctx* ctx, const void* device_ptr, int64_t n0, int64_t n1, int64_t n2) {
-    if (!ctx || !device_ptr) return CX_ERR_INVALID;
-    CX_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = set_grid_dims(ctx, n0, n1, n2);
-    if (rc) return rc;
-    ctx->grid = (const float*)device_ptr;
+    return cx_grid_adopt_device_typed(ctx, device_ptr, CX_DTYPE_F32, n0, n1, n2);
+}
+
+extern "C" int cx_grid_info(cx_ctx* ctx, int32_t* dtype, int64_t* device_bytes) {
+    if (!ctx) return CX_ERR_INVALID;
+    if (!ctx->grid.p) return fail(ctx, CX_ERR_STATE, "no grid: call cx_grid_upload or cx_grid_adopt_device first");
+    if (dtype) *dtype = ctx->grid.dtype;
+    if (device_bytes)
+        *device_bytes = ctx->grid.p == ctx->grid_owned ? ctx->n0 * ctx->n1 * ctx->n2 * (int64_t)cx_dtype_size(ctx->grid.dtype) : 0;
     return CX_OK;
 }
 
@@ -165,7 +181,7 @@ extern "C" int cx_grid_shadow_f64(cx_ctx* ctx, const double* host, int64_t n0, i
     ctx->grid64_valid = false;
     ctx->post_valid = false;
     if (!host) return CX_OK;
-    if (!ctx->grid || n0 != ctx->n0 || n1 != ctx->n1 || n2 != ctx->n2)
+    if (!ctx->grid.p || n0 != ctx->n0 || n1 != ctx->n1 || n2 != ctx->n2)   // of any sample type
         return fail(ctx, CX_ERR_STATE, "cx_grid_shadow_f64: bind the fp32 grid of the same dimensions first");
     CX_HIP(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)(n0 * n1 * n2);
@@ -252,7 +268,7 @@ void cx_fill_value_params(cx_params& P, double value) {
 }
 
 static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
-    if (!ctx->grid) return fail(ctx, CX_ERR_STATE, "no grid: call cx_grid_upload or cx_grid_adopt_device first");
+    if (!ctx->grid.p) return fail(ctx, CX_ERR_STATE, "no grid: call cx_grid_upload or cx_grid_adopt_device first");
     if (!(value == value)) return fail(ctx, CX_ERR_INVALID, "isovalue is NaN");
     // the public flags are the documented ones; the ablation bits (CX_DBG_*) give partial meshes and are only honoured
     // in a process started with CX_DEBUG=1 (tools/)
@@ -275,12 +291,14 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
     const bool staged = !(flags & CX_KERNEL_GENERIC) && cx_fast_classify_supported_dims(ctx->n2, ctx->grid);
     // fused emit kernel (no per-cell table, no cell records) only on request: measured slower than the staged kernels
     // (DESIGN.md section 4); an extraction that meets the tolerance path is sent through the staged kernels by cx_counts_get
-    const bool fused = staged && (flags & CX_KERNEL_FUSED) && !(flags & CX_KERNEL_STAGED);
+    // (grids of a narrow sample type: the fused and tile emit kernels are fp32 only, the staged kernels serve those requests)
+    const bool typed = ctx->grid.dtype != CX_DTYPE_F32;
+    const bool fused = staged && !typed && (flags & CX_KERNEL_FUSED) && !(flags & CX_KERNEL_STAGED);
     // tile emit (cx_tile3d.h): vertex records and triangles tile by tile, the hand-over between them in LDS
     // On request (CX_KERNEL_TILED; CX_DEBUG=1 CX_TILED=1 makes it the default of a tools/ process): measured 4 % faster than the staged
     // kernels with one extraction in flight, equal with two, 0.35 GB less traffic -- and a smooth sheet lying flat in a half tile
     // (a quarter of its cells active) is beyond its LDS words, which sends the whole extraction through the staged kernels
-    const bool tiled = staged && !fused && !(flags & CX_KERNEL_STAGED) && ((flags & CX_KERNEL_TILED) || cx_debug_knob("CX_TILED", 0u));
+    const bool tiled = staged && !typed && !fused && !(flags & CX_KERNEL_STAGED) && ((flags & CX_KERNEL_TILED) || cx_debug_knob("CX_TILED", 0u));
     if (!staged) {
         // the per-cell table of the generic emit path (one 8-byte entry per sample): only when that path runs
         const int rc = cx_grow(ctx, ctx->celltab, ctx->tables_for, (size_t)N + 64u);
@@ -346,7 +364,7 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
         // own loads, goes from 0.131 to 0.176 ms (~125 instructions per step that queued cells, at three waves per SIMD).  So it is
         // built, tested (tests/test_gpu_level0.py::test_fraction_stream) and OFF; CX_DEBUG=1 CX_TQ=1 turns it on.
         P.tq = nullptr; P.tlimit = 0;
-        if (!fused && cx_debug_knob("CX_TQ", 0u)) {
+        if (!fused && !typed && cx_debug_knob("CX_TQ", 0u)) {   // (an fp32 A/B switch: not instantiated for narrow types)
             if ((rc = cx_grow(ctx, ctx->tq, ctx->tq_cap, need))) return rc;
             P.tq = ctx->tq; P.tlimit = T.wcap;
         }

@@ -66,7 +66,8 @@ __device__ __forceinline__ bool cx_near_b(double f, double v) { return fabs(v - 
 // Is the crossing lattice edge (q, q+d) used by at least one emitted triangle?  Only reached when
 // both end points are within the reference's np.allclose tolerances of the isovalue, where the
 // reference may skip whole voxels (border_voxel) or single tetrahedra (tetrahedral.py:576).
-static __device__ __forceinline__ bool cx_edge_used_slow(const float* A, uint32_t n0, uint32_t n1, uint32_t n2,
+template <int DT>
+static __device__ __forceinline__ bool cx_edge_used_slow(const cx_grid_ref& A, uint32_t n0, uint32_t n1, uint32_t n2,
                                                       double value, double tol_value, uint32_t i, uint32_t j,
                                                       uint32_t k, uint32_t d) {
     for (uint32_t o = 0; o < 8; o++) {
@@ -77,7 +78,7 @@ static __device__ __forceinline__ bool cx_edge_used_slow(const float* A, uint32_
         if (pi + 1 >= n0 || pj + 1 >= n1 || pk + 1 >= n2) continue;
         uint32_t near_a = 0, all_b = 1;
         for (uint32_t c = 0; c < 8; c++) {
-            const double f = (double)A[((size_t)(pi + ((c >> 2) & 1u)) * n1 + (pj + ((c >> 1) & 1u))) * n2 + (pk + (c & 1u))];
+            const double f = (double)cx_sample<DT>(A, ((size_t)(pi + ((c >> 2) & 1u)) * n1 + (pj + ((c >> 1) & 1u))) * n2 + (pk + (c & 1u)));
             if (fabs(f - value) <= tol_value) near_a |= 1u << c;
             if (!cx_near_b(f, value)) all_b = 0;
         }
@@ -105,22 +106,34 @@ struct cx_cell_info {
 struct __attribute__((packed, aligned(4))) cx_f2 {
     float x, y;
 };
+// the same pair of a narrow sample type: the compiler picks the loads its alignment (one sample) allows
+template <typename T>
+struct __attribute__((packed, aligned(sizeof(T)))) cx_t2 {
+    T x, y;
+};
+// the pair a kernel loads for sample type DT (fp32: cx_f2, as it always was)
+template <int DT>
+using cx_pair = typename std::conditional<DT == CX_DTYPE_F32, cx_f2, cx_t2<typename cx_dt<DT>::bits>>::type;
+template <int DT>
 __device__ __forceinline__ uint32_t cx_load_corners(const cx_params& P, uint32_t lin, uint32_t i, uint32_t j,
                                                     uint32_t k, float f[8]) {
-    const float* __restrict__ A = P.grid;
+    typedef typename cx_dt<DT>::bits B;
+    const B* __restrict__ A = reinterpret_cast<const B*>(cx_grid_data<DT>(P.grid));
     const uint32_t plane = P.n1 * P.n2;
     const bool vi = (i + 1 < P.n0), vj = (j + 1 < P.n1), vk = (k + 1 < P.n2);
     const uint32_t oi = vi ? plane : 0u, oj = vj ? P.n2 : 0u;
     // at the array edge in k read the pair (k-1, k) instead and repeat k
     const uint32_t base = vk ? lin : lin - 1u;
-    const cx_f2 p0 = *reinterpret_cast<const cx_f2*>(A + base);
-    const cx_f2 p1 = *reinterpret_cast<const cx_f2*>(A + base + oj);
-    const cx_f2 p2 = *reinterpret_cast<const cx_f2*>(A + base + oi);
-    const cx_f2 p3 = *reinterpret_cast<const cx_f2*>(A + base + oi + oj);
-    f[0] = vk ? p0.x : p0.y; f[1] = p0.y;
-    f[2] = vk ? p1.x : p1.y; f[3] = p1.y;
-    f[4] = vk ? p2.x : p2.y; f[5] = p2.y;
-    f[6] = vk ? p3.x : p3.y; f[7] = p3.y;
+    const cx_pair<DT> p0 = *reinterpret_cast<const cx_pair<DT>*>(A + base);
+    const cx_pair<DT> p1 = *reinterpret_cast<const cx_pair<DT>*>(A + base + oj);
+    const cx_pair<DT> p2 = *reinterpret_cast<const cx_pair<DT>*>(A + base + oi);
+    const cx_pair<DT> p3 = *reinterpret_cast<const cx_pair<DT>*>(A + base + oi + oj);
+    const float x0 = cx_dt<DT>::cvt(p0.x), y0 = cx_dt<DT>::cvt(p0.y), x1 = cx_dt<DT>::cvt(p1.x), y1 = cx_dt<DT>::cvt(p1.y);
+    const float x2 = cx_dt<DT>::cvt(p2.x), y2 = cx_dt<DT>::cvt(p2.y), x3 = cx_dt<DT>::cvt(p3.x), y3 = cx_dt<DT>::cvt(p3.y);
+    f[0] = vk ? x0 : y0; f[1] = y0;
+    f[2] = vk ? x1 : y1; f[3] = y1;
+    f[4] = vk ? x2 : y2; f[5] = y2;
+    f[6] = vk ? x3 : y3; f[7] = y3;
     uint32_t vm = 1u | (vk ? 2u : 0u) | (vj ? 4u : 0u) | ((vj && vk) ? 8u : 0u);
     vm |= vi ? (vm << 4) : 0u;
     return vm;
@@ -134,6 +147,7 @@ __device__ __forceinline__ uint32_t cx_sign_mask(const cx_params& P, const float
 }
 
 // classification of one ACTIVE cell (sign change among its valid corners)
+template <int DT>
 __device__ __forceinline__ cx_cell_info cx_classify_cell(const cx_params& P, const float f[8], uint32_t vm,
                                                          uint32_t sm, uint32_t i, uint32_t j, uint32_t k) {
     cx_cell_info R;
@@ -186,7 +200,7 @@ __device__ __forceinline__ cx_cell_info cx_classify_cell(const cx_params& P, con
         for (uint32_t d = 1; d < 8; d++) {
             if (!((R.emask >> d) & 1u)) continue;
             const bool suspicious = (((near_a >> d) & near_a & 1u) | ((nb >> d) & nb & 1u)) != 0u;
-            if (suspicious && !cx_edge_used_slow(P.grid, P.n0, P.n1, P.n2, P.value, P.tol_value, i, j, k, d))
+            if (suspicious && !cx_edge_used_slow<DT>(P.grid, P.n0, P.n1, P.n2, P.value, P.tol_value, i, j, k, d))
                 R.emask &= ~(1u << d);
         }
     }

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/contourist_hip.h"
 #include "cx_tables.h"
 
@@ -46,9 +48,76 @@ __device__ __forceinline__ uint32_t cx_div(uint32_t n, const cx_fdiv& f) {
 // fp32 grid coordinates get them expanded on request (cx_k_expand_verts: cx_level0_download / cx_level0_device_ptrs).
 typedef uint2 cx_vrec;
 
+// ---- the samples of a 3-D grid: a pointer that carries its type (CX_DTYPE_*, include/contourist_hip.h) --------------------------
+// Kernels read them only through cx_grid_data<DT>: a kernel that has not been ported to a type cannot read the buffer as fp32 by
+// accident (a uint8 grid read as floats runs 4 x past its end).  Every type converts to fp32 exactly; a kernel loads the narrow
+// type, converts it in registers (cx_dt<DT>::cvt) and runs the fp32 arithmetic unchanged.
+struct cx_grid_ref {
+    const void* p;
+    int32_t dtype;
+};
+template <int DT> struct cx_dt;
+// cvt: the loaded value (narrow types: its bits, zero-extended) as fp32.  raw / placeholder: what a kernel that converts later
+// (cx_vround_front -> cx_vround_pin) keeps in an fp32 register meanwhile -- the bits, and the bits of the small integer n (debug ablations)
+template <> struct cx_dt<CX_DTYPE_F32> {
+    typedef float T; typedef float bits;
+    static __device__ __forceinline__ float cvt(float v) { return v; }
+    static __device__ __forceinline__ float raw(float v) { return v; }
+    static __device__ __forceinline__ float placeholder(uint32_t n) { return (float)n; }
+};
+template <int DT, typename TT, typename B>
+struct cx_dt_narrow {
+    typedef TT T; typedef B bits;
+    static __device__ __forceinline__ float raw(uint32_t v) { return __uint_as_float(v); }
+};
+template <int DT, typename TT>
+struct cx_dt_int : cx_dt_narrow<DT, TT, typename std::make_unsigned<TT>::type> {
+    static __device__ __forceinline__ float cvt(uint32_t v) {
+        return (float)(TT)(typename std::make_unsigned<TT>::type)v;   // zero- or sign-extended, then v_cvt_f32_{u,i}32
+    }
+    static __device__ __forceinline__ float placeholder(uint32_t n) { return __uint_as_float(n); }
+};
+template <> struct cx_dt<CX_DTYPE_U8> : cx_dt_int<CX_DTYPE_U8, uint8_t> {};
+template <> struct cx_dt<CX_DTYPE_I8> : cx_dt_int<CX_DTYPE_I8, int8_t> {};
+template <> struct cx_dt<CX_DTYPE_U16> : cx_dt_int<CX_DTYPE_U16, uint16_t> {};
+template <> struct cx_dt<CX_DTYPE_I16> : cx_dt_int<CX_DTYPE_I16, int16_t> {};
+template <> struct cx_dt<CX_DTYPE_F16> : cx_dt_narrow<CX_DTYPE_F16, uint16_t, uint16_t> {
+    static __device__ __forceinline__ float cvt(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)v); }
+    static __device__ __forceinline__ float placeholder(uint32_t n) { return __uint_as_float(__builtin_bit_cast(uint16_t, (_Float16)n)); }
+};
+template <> struct cx_dt<CX_DTYPE_BF16> : cx_dt_narrow<CX_DTYPE_BF16, uint16_t, uint16_t> {
+    static __device__ __forceinline__ float cvt(uint32_t v) { return __uint_as_float(v << 16); }
+    static __device__ __forceinline__ float placeholder(uint32_t n) { return __uint_as_float(__float_as_uint((float)n) >> 16); }
+};
+template <int DT>
+__device__ __forceinline__ const typename cx_dt<DT>::T* cx_grid_data(const cx_grid_ref& g) {
+    return static_cast<const typename cx_dt<DT>::T*>(g.p);
+}
+// sample i as fp32
+template <int DT>
+__device__ __forceinline__ float cx_sample(const cx_grid_ref& g, size_t i) {
+    if constexpr (DT == CX_DTYPE_F32) return cx_grid_data<DT>(g)[i];
+    else return cx_dt<DT>::cvt((uint32_t)(typename cx_dt<DT>::bits)cx_grid_data<DT>(g)[i]);
+}
+static inline size_t cx_dtype_size(int32_t dt) {
+    return dt == CX_DTYPE_F32 ? 4u : (dt == CX_DTYPE_U8 || dt == CX_DTYPE_I8) ? 1u : 2u;
+}
+static inline bool cx_dtype_valid(int32_t dt) { return dt >= CX_DTYPE_F32 && dt <= CX_DTYPE_BF16; }
+// one instantiation per sample type: F(DT) is called with DT a compile-time constant (host side: the launchers)
+#define CX_DISPATCH_DTYPE(dt, F)                                   \
+    switch (dt) {                                                  \
+        case CX_DTYPE_U8: F(CX_DTYPE_U8); break;                   \
+        case CX_DTYPE_I8: F(CX_DTYPE_I8); break;                   \
+        case CX_DTYPE_U16: F(CX_DTYPE_U16); break;                 \
+        case CX_DTYPE_I16: F(CX_DTYPE_I16); break;                 \
+        case CX_DTYPE_F16: F(CX_DTYPE_F16); break;                 \
+        case CX_DTYPE_BF16: F(CX_DTYPE_BF16); break;               \
+        default: F(CX_DTYPE_F32); break;                           \
+    }
+
 // ---- parameters of one extraction ---------------------------------------------------------------
 struct cx_params {
-    const float* grid;     // n0*n1*n2 fp32 samples
+    cx_grid_ref grid;      // n0*n1*n2 samples (CX_DTYPE_*)
     uint32_t n0, n1, n2;
     uint32_t nsamples;     // n0*n1*n2  (<= 2^29)
     cx_fdiv div_plane;     // / (n1*n2)
@@ -174,7 +243,7 @@ extern __device__ __constant__ uint8_t cx_d_voxel_ntri[256];
 // kernel launchers (cx_march3d.hip)
 void cx_launch_classify_generic(const cx_params& P, hipStream_t s);
 bool cx_fast_classify_supported(const cx_params& P);
-bool cx_fast_classify_supported_dims(int64_t n2, const float* grid);
+bool cx_fast_classify_supported_dims(int64_t n2, const cx_grid_ref& grid);
 cx_task cx_fast_task(uint32_t n0, uint32_t n1, uint32_t n2);
 void cx_launch_stream(const cx_params& P, const cx_task& T, hipStream_t s);
 void cx_launch_scan_waves(const cx_params& P, const cx_task& T, hipStream_t s);

@@ -15,8 +15,8 @@ struct cx_ctx {
     hipStream_t own_stream = nullptr;  // stream created by the context
     std::string err;
     // sampled field
-    const float* grid = nullptr;
-    float* grid_owned = nullptr;
+    cx_grid_ref grid = {nullptr, CX_DTYPE_F32};
+    uint8_t* grid_owned = nullptr;     // the uploaded samples, any type (bytes)
     size_t grid_owned_bytes = 0;
     int64_t n0 = 0, n1 = 0, n2 = 0;
     double* grid64 = nullptr;          // float64 originals of the samples (cx_grid_shadow_f64): Level 1 interpolates on these

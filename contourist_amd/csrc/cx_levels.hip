@@ -168,7 +168,7 @@ extern "C" int cx_levels_select(cx_ctx* ctx, int32_t index) {
 
 extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nlevels, uint32_t flags, cx_counts* out_counts) {
     if (!ctx || !values || nlevels < 1 || nlevels > 64) return CX_ERR_INVALID;
-    if (!ctx->grid) { ctx->err = "no grid: call cx_grid_upload or cx_grid_adopt_device first"; return CX_ERR_STATE; }
+    if (!ctx->grid.p) { ctx->err = "no grid: call cx_grid_upload or cx_grid_adopt_device first"; return CX_ERR_STATE; }
     if ((flags & ~(uint32_t)(CX_DIAG_CPYTHON310)) != 0u) { ctx->err = "cx_extract3d_levels: only the diagonal flag is accepted"; return CX_ERR_INVALID; }
     for (int l = 0; l < nlevels; l++)
         if (!(values[l] == values[l])) { ctx->err = "isovalue is NaN"; return CX_ERR_INVALID; }

@@ -66,7 +66,7 @@ struct cx_run {
 // advances as vertex records and table entries (RECORDS: and cell records) are written.
 #define CX_VSTAGE 256u   // vertex records a wave stages in LDS per batch of 64 cells (typical: ~200)
 #define CX_VSTAGE_LDS 384u   // float4 slots per wave in the vertex stage's LDS (fast path: 2 x 448 slot words + 64 x 9 corner samples)
-template <bool RECORDS, typename LinOf>
+template <bool RECORDS, int DT, typename LinOf>
 __device__ __forceinline__ void cx_process_queue(const cx_params& P, LinOf lin_of, uint32_t n, uint32_t lane,
                                                  bool emit, cx_run& run, cx_vrec* vstage, uint64_t* info = nullptr) {
     const uint32_t plane = P.n1 * P.n2;
@@ -79,13 +79,13 @@ __device__ __forceinline__ void cx_process_queue(const cx_params& P, LinOf lin_o
         const uint32_t j = cx_div(r, P.div_row);
         const uint32_t k = r - j * P.n2;
         float f[8];
-        const uint32_t vm = cx_load_corners(P, lin, i, j, k, f);
+        const uint32_t vm = cx_load_corners<DT>(P, lin, i, j, k, f);
         const uint32_t sm = cx_sign_mask(P, f);
         const uint32_t smv = sm & vm;
         const bool active = have && smv != 0u && smv != vm;
         cx_cell_info R;
         R.sm = sm; R.emask = 0; R.ntri = 0; R.tetskip = 0; R.border = 0;
-        if (active) R = cx_classify_cell(P, f, vm, sm, i, j, k);
+        if (active) R = cx_classify_cell<DT>(P, f, vm, sm, i, j, k);
         const uint32_t nv = __popc(R.emask);
         const bool rec = active && (nv != 0u || R.ntri != 0u);
         uint32_t vtot, ttot;
@@ -211,6 +211,10 @@ struct cx_vround {
     uint32_t e_next;                   // entries of the following round
 };
 #define CX_CORNER_ROW 9u               // dwords per cell in the LDS corner table (8 + 1: bank spread)
+// A narrow sample type (DT != CX_DTYPE_F32) leaves the front half with its raw bits in R.f: they are converted to fp32 in
+// cx_vround_pin, after the loads are complete, so that the gathers stay in flight meanwhile.  A (k, k+1) pair may start at any
+// sample: it is one packed 2 x sizeof(T) load aligned to one sample (cx_t2), whose instructions the compiler picks for that alignment.
+template <int DT>
 __device__ __forceinline__ void cx_vround_front(const cx_params& P, const cx_fast_geom& G, const uint32_t* q, uint32_t n, uint32_t b0,
                                                 uint32_t lane, uint32_t e, const cx_run& base, uint32_t* slot,
                                                 const uint8_t* ntri_lut, cx_vround& R) {
@@ -233,20 +237,21 @@ __device__ __forceinline__ void cx_vround_front(const cx_params& P, const cx_fas
     R.vk = (vm >> 1) & 1u;
     if (P.flags & CX_DBG_NO_VLOADS) {
 #pragma unroll
-        for (int c = 0; c < 8; c++) R.f[c] = (float)(c + 1);
+        for (int c = 0; c < 8; c++) R.f[c] = cx_dt<DT>::placeholder(c + 1);   // (cx_vround_pin converts them to c + 1)
         R.vk = 1u;
     } else {
-        const float* __restrict__ A = P.grid;
         const uint32_t lin = have ? R.lin : 0u;
         const uint32_t oi = (have && (vm & 0x10u)) ? P.n1 * P.n2 : 0u, oj = (have && (vm & 4u)) ? P.n2 : 0u;
         // at the array edge in k read the pair (k-1, k) instead and repeat k (as cx_load_corners does)
         const uint32_t base = (R.vk || !have) ? lin : lin - 1u;
-        const cx_f2 p0 = *reinterpret_cast<const cx_f2*>(A + base);
-        const cx_f2 p1 = *reinterpret_cast<const cx_f2*>(A + base + oj);
-        const cx_f2 p2 = *reinterpret_cast<const cx_f2*>(A + base + oi);
-        const cx_f2 p3 = *reinterpret_cast<const cx_f2*>(A + base + oi + oj);
-        R.f[0] = p0.x; R.f[1] = p0.y; R.f[2] = p1.x; R.f[3] = p1.y;
-        R.f[4] = p2.x; R.f[5] = p2.y; R.f[6] = p3.x; R.f[7] = p3.y;
+        typedef typename cx_dt<DT>::bits B;
+        const B* __restrict__ A = reinterpret_cast<const B*>(cx_grid_data<DT>(P.grid));
+        const cx_pair<DT> p0 = *reinterpret_cast<const cx_pair<DT>*>(A + base);
+        const cx_pair<DT> p1 = *reinterpret_cast<const cx_pair<DT>*>(A + base + oj);
+        const cx_pair<DT> p2 = *reinterpret_cast<const cx_pair<DT>*>(A + base + oi);
+        const cx_pair<DT> p3 = *reinterpret_cast<const cx_pair<DT>*>(A + base + oi + oj);
+        R.f[0] = cx_dt<DT>::raw(p0.x); R.f[1] = cx_dt<DT>::raw(p0.y); R.f[2] = cx_dt<DT>::raw(p1.x); R.f[3] = cx_dt<DT>::raw(p1.y);
+        R.f[4] = cx_dt<DT>::raw(p2.x); R.f[5] = cx_dt<DT>::raw(p2.y); R.f[6] = cx_dt<DT>::raw(p3.x); R.f[7] = cx_dt<DT>::raw(p3.y);
         if (!have) { vm = 0; R.vk = 1u; }
     }
     R.real_voxel = (have && vm == 0xFFu) ? 1u : 0u;
@@ -266,10 +271,15 @@ __device__ __forceinline__ void cx_vround_front(const cx_params& P, const cx_fas
     __builtin_amdgcn_wave_barrier();
 }
 // the loads issued by the front half have to be complete here
+template <int DT>
 __device__ __forceinline__ void cx_vround_pin(cx_vround& R) {
 #pragma unroll
     for (uint32_t c = 0; c < 8; c++) asm volatile("" : "+v"(R.f[c]) :: "memory");
     asm volatile("" : "+v"(R.e_next) :: "memory");
+    if constexpr (DT != CX_DTYPE_F32) {
+#pragma unroll
+        for (uint32_t c = 0; c < 8; c++) R.f[c] = cx_dt<DT>::cvt(__float_as_uint(R.f[c]));
+    }
 }
 __device__ __forceinline__ cx_vrec cx_vertex_record(const cx_params& P, const cx_fast_geom& G, uint32_t e2, uint32_t d, float f0, float f1) {
     const uint32_t lin2 = cx_entry_lin(P, G, e2);
@@ -287,14 +297,15 @@ __device__ __forceinline__ cx_vrec cx_vertex_record(const cx_params& P, const cx
 // LDS per wave: two slot tables of 448 words (double buffered) and the corner table of 64 x CX_CORNER_ROW words.
 // `first`: the cell the walk starts at (a multiple of 64; `run` holds what precedes it), `n`: where it ends -- a wave takes a
 // range of a batch's rounds (cx_k_emit_vertices)
+template <int DT>
 __device__ __forceinline__ void cx_emit_queue_fast(const cx_params& P, const cx_fast_geom& G, const uint32_t* q, uint32_t first, uint32_t n,
                                                    uint32_t lane, cx_run run, uint32_t* slot2, const uint8_t* ntri_lut, uint64_t* info, unsigned long long* tacc = nullptr) {
     float* corners = reinterpret_cast<float*>(slot2 + 2u * 448u);
     cx_vround Ra, Rb;
     uint32_t e0 = (first + lane < n) ? q[first + lane] : 0u;
     asm volatile("" : "+v"(e0) :: "memory");
-    cx_vround_front(P, G, q, n, first, lane, e0, run, slot2, ntri_lut, Ra);
-    cx_vround_pin(Ra);
+    cx_vround_front<DT>(P, G, q, n, first, lane, e0, run, slot2, ntri_lut, Ra);
+    cx_vround_pin<DT>(Ra);
     uint32_t par = 0;
 #ifdef CX_S3_STAMPS
 #define CX_S3_T(k) { const unsigned long long tn = __builtin_amdgcn_s_memrealtime(); tacc[k] += tn - tprev; tprev = tn; }
@@ -307,7 +318,7 @@ __device__ __forceinline__ void cx_emit_queue_fast(const cx_params& P, const cx_
         if (more) {
             cx_run nb = Ra.base;
             nb.v += Ra.vtot; nb.t += Ra.ttot; nb.c += Ra.ctot;
-            cx_vround_front(P, G, q, n, b0 + 64u, lane, Ra.e_next, nb, slot2 + (par ^ 1u) * 448u, ntri_lut, Rb);
+            cx_vround_front<DT>(P, G, q, n, b0 + 64u, lane, Ra.e_next, nb, slot2 + (par ^ 1u) * 448u, ntri_lut, Rb);
         }
         CX_S3_T(0)
         // back half of round b0: the corner samples of the 64 cells go to LDS ...
@@ -330,7 +341,7 @@ __device__ __forceinline__ void cx_emit_queue_fast(const cx_params& P, const cx_
         }
         CX_S3_T(1)
 #if CX_PIN_BEFORE_STORES
-        if (more) cx_vround_pin(Rb);
+        if (more) cx_vround_pin<DT>(Rb);
 #endif
         CX_S3_T(2)
         // ... then the stores
@@ -363,7 +374,7 @@ __device__ __forceinline__ void cx_emit_queue_fast(const cx_params& P, const cx_
         }
         __builtin_amdgcn_wave_barrier();
 #if !CX_PIN_BEFORE_STORES
-        if (more) cx_vround_pin(Rb);   // the next round's samples are waited for AFTER this round's stores went out (see CX_PIN_BEFORE_STORES)
+        if (more) cx_vround_pin<DT>(Rb);   // the next round's samples are waited for AFTER this round's stores went out (see CX_PIN_BEFORE_STORES)
 #endif
         CX_S3_T(3)
         if (more) Ra = Rb;
@@ -566,6 +577,7 @@ __device__ __forceinline__ void cx_cross_words(uint32_t A, uint32_t B, const cx_
 // generic classify kernel (any shape / alignment): one lane per cell, wave-private LDS queue, the
 // workgroup reserves output space with ONE atomic per counter, then emits (per-cell path).
 // =================================================================================================
+template <int DT>
 __global__ __launch_bounds__(256) void cx_k_classify_generic(const cx_params P, const uint32_t cells_per_block) {
     __shared__ uint32_t s_queue[4][CX_QCAP];
     __shared__ cx_vrec s_vstage[4][CX_VSTAGE];
@@ -592,7 +604,7 @@ __global__ __launch_bounds__(256) void cx_k_classify_generic(const cx_params P, 
             const uint32_t j = cx_div(r, P.div_row);
             const uint32_t k = r - j * P.n2;
             float f[8];
-            const uint32_t vm = cx_load_corners(P, linc, i, j, k, f);
+            const uint32_t vm = cx_load_corners<DT>(P, linc, i, j, k, f);
             const uint32_t sm = cx_sign_mask(P, f);
             const uint32_t smv = sm & vm;
             const bool active = in && smv != 0u && smv != vm;
@@ -618,7 +630,7 @@ __global__ __launch_bounds__(256) void cx_k_classify_generic(const cx_params P, 
         cx_run run = {0, 0, 0, 0};
         auto lin_of = [&](uint32_t x) { return q[x]; };
         if (__ballot(dnear <= P.near_abs) != 0ULL) {   // wave-uniform: a sample inside the tolerance screen, count exactly
-            cx_process_queue<true>(P, lin_of, qn, lane, false, run, s_vstage[wave]);
+            cx_process_queue<true, DT>(P, lin_of, qn, lane, false, run, s_vstage[wave]);
         } else {
             run.v = cx_wave_sum(acc.v); run.t = cx_wave_sum(acc.t);
             run.c = cx_wave_sum(acc.c); run.b = cx_wave_sum(acc.b);
@@ -662,7 +674,7 @@ __global__ __launch_bounds__(256) void cx_k_classify_generic(const cx_params P, 
             run.t = __builtin_amdgcn_readfirstlane(base.t);
             run.c = __builtin_amdgcn_readfirstlane(base.c);
         }
-        cx_process_queue<true>(P, lin_of, qn, lane, true, run, s_vstage[wave]);
+        cx_process_queue<true, DT>(P, lin_of, qn, lane, true, run, s_vstage[wave]);
         qn = 0;
         if (final_round) break;
     }
@@ -710,7 +722,27 @@ static_assert(CX_SQ >= 512u, "half a wave's lanes queue up to 512 cells per step
 // ALIGNED: n2 % 4 == 0 and a 16-byte aligned grid (rows start on 16-byte boundaries, every lane holds 4 samples
 // of one row).  Otherwise the 16-byte loads are only 4-byte aligned and the lane that holds the end of a row
 // loads the row's last 4 samples and shifts them into place, repeating the last one (a clamped corner).
-template <bool ALIGNED>
+// DT: the sample type.  A narrow type keeps the same lane layout: a lane loads its 4 samples as ONE 4 x sizeof(T) load (aligned to
+// 4 x sizeof(T) when ALIGNED, else to one sample: cx_row4) and the halo sample as its raw bits; they are converted to fp32 where the
+// fp32 kernel reads them (plane_bits), so that the planes requested ahead stay in flight.  Everything after that is the fp32 code.
+template <int DT> struct cx_row4 { typedef float4 v; typedef float h; };   // DT == CX_DTYPE_F32: the loads as they were
+template <> struct cx_row4<CX_DTYPE_U8> { typedef uint32_t v; typedef uint32_t h; };
+template <> struct cx_row4<CX_DTYPE_I8> { typedef uint32_t v; typedef uint32_t h; };
+template <> struct cx_row4<CX_DTYPE_U16> { typedef cx_v2u v; typedef uint32_t h; };
+template <> struct cx_row4<CX_DTYPE_I16> { typedef cx_v2u v; typedef uint32_t h; };
+template <> struct cx_row4<CX_DTYPE_F16> { typedef cx_v2u v; typedef uint32_t h; };
+template <> struct cx_row4<CX_DTYPE_BF16> { typedef cx_v2u v; typedef uint32_t h; };
+template <typename V, size_t AL>
+struct __attribute__((packed, aligned(AL))) cx_row4_ua { V v; };
+template <int DT>
+__device__ __forceinline__ void cx_row4_unpack(const typename cx_row4<DT>::v& w, float& x, float& y, float& z, float& t) {
+    if constexpr (sizeof(typename cx_dt<DT>::T) == 1) {
+        x = cx_dt<DT>::cvt(w); y = cx_dt<DT>::cvt(w >> 8); z = cx_dt<DT>::cvt(w >> 16); t = cx_dt<DT>::cvt(w >> 24);
+    } else {
+        x = cx_dt<DT>::cvt(w.x); y = cx_dt<DT>::cvt(w.x >> 16); z = cx_dt<DT>::cvt(w.y); t = cx_dt<DT>::cvt(w.y >> 16);
+    }
+}
+template <bool ALIGNED, int DT>
 __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task& T, const uint32_t b) {
     __shared__ uint32_t s_q[4][CX_SQ];
     __shared__ uint32_t s_br[4][CX_SBR][5];
@@ -747,7 +779,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
     uint32_t p = tile.p;
     uint32_t* __restrict__ gq = P.queue + (size_t)w * T.wcap;
     cx_brec* __restrict__ brec = P.brec + (size_t)w * T.bcap;
-    const float* __restrict__ A = P.grid;
+    const typename cx_dt<DT>::bits* __restrict__ A = reinterpret_cast<const typename cx_dt<DT>::bits*>(cx_grid_data<DT>(P.grid));
     cx_cnt acc = {0, 0, 0, 0};   // per-lane counts of the cells queued since the last batch record (b: all)
     uint32_t qn = 0, qstart = 0, nb = 0;   // wave-uniform: queued cells, start of the open batch, closed batches
     uint32_t rv = 0, rt = 0, rc = 0;       // wave-uniform: vertices / triangles / records of the closed batches
@@ -847,8 +879,8 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
 
         // one sample plane of this lane: RJ+1 rows x 4 consecutive k-samples, plus the sample right of the segment
         struct plane_raw {
-            float4 v[CX_RJ + 1];
-            float hv[CX_RJ + 1];
+            typename cx_row4<DT>::v v[CX_RJ + 1];
+            typename cx_row4<DT>::h hv[CX_RJ + 1];
         };
         const uint32_t plane_last = min(ib, P.n0 - 1u);
         auto load_plane = [&](uint32_t pp, plane_raw& R) {
@@ -857,6 +889,11 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
             for (int r = 0; r <= CX_RJ; r++) {
                 const uint32_t jr = min(j0 + (uint32_t)r, P.n1 - 1u);   // rows beyond the array repeat the last row
                 const uint32_t rowofs = (pc * P.n1 + jr) * P.n2;
+                if constexpr (DT != CX_DTYPE_F32) {
+                    typedef typename cx_row4<DT>::v V;
+                    R.v[r] = reinterpret_cast<const cx_row4_ua<V, ALIGNED ? sizeof(V) : sizeof(*A)>*>(A + rowofs + kofs_c)->v;
+                    R.hv[r] = A[rowofs + (halo_in ? k0 + 256u : 0u)];                // raw bits, wave-uniform address
+                } else {
 #if CX_NT_GRID   // A/B: streaming loads of the grid (do not keep it in L2 / Infinity Cache)
                 {
                     const cx_v4f t4 = __builtin_nontemporal_load(reinterpret_cast<const cx_v4f*>(A + rowofs + kofs_c));
@@ -866,6 +903,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
                 R.v[r] = *reinterpret_cast<const float4*>(A + rowofs + kofs_c);      // lanes right of the array re-read its last 4 samples
 #endif
                 R.hv[r] = A[rowofs + (halo_in ? k0 + 256u : 0u)];                    // wave-uniform address
+                }
             }
         };
         // sign bits of a loaded plane.  f < vcmp  <=>  sign bit of (f - vcmp)  (f == vcmp gives +0 -- also for f = -0.0 at isovalue 0:
@@ -885,8 +923,14 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
             uint32_t own = 0, halo = 0;
 #pragma unroll
             for (int r = CX_RJ; r >= 0; r--) {
-                float vx = R.v[r].x, vy = R.v[r].y, vz = R.v[r].z;
-                const float vw = R.v[r].w;
+                float vx, vy, vz, vw_, hv;
+                if constexpr (DT == CX_DTYPE_F32) {
+                    vx = R.v[r].x; vy = R.v[r].y; vz = R.v[r].z; vw_ = R.v[r].w; hv = R.hv[r];
+                } else {
+                    cx_row4_unpack<DT>(R.v[r], vx, vy, vz, vw_);
+                    hv = cx_dt<DT>::cvt(R.hv[r]);
+                }
+                const float vw = vw_;
                 if (!ALIGNED) {   // lane at the end of the row: samples kofs.. of (n2-4 .. n2-1), the last one repeated
                     vx = (kshift == 1u) ? vy : ((kshift == 2u) ? vz : ((kshift == 3u) ? vw : vx));
                     vy = (kshift == 0u) ? vy : ((kshift == 1u) ? vz : vw);
@@ -894,10 +938,10 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
                 }
                 if (stage_ring) {   // the lane's four samples of row r, in place; the sample right of the segment behind them
                     *reinterpret_cast<float4*>(&ring[slot][r][4u * lane]) = make_float4(vx, vy, vz, vw);
-                    if (lane == 0u) ring[slot][r][256] = R.hv[r];
+                    if (lane == 0u) ring[slot][r][256] = hv;
                 }
                 const float dx = vx - P.vcmp, dy = vy - P.vcmp, dz = vz - P.vcmp, dw = vw - P.vcmp;
-                const float dh = R.hv[r] - P.vcmp;
+                const float dh = hv - P.vcmp;
 #if CX_S1_SHIFT_OR      // A/B: a shift and a shift-or per sample
                 own |= (__float_as_uint(dx) >> 31) << (CX_ROWBITS * r + 0);
                 own |= (__float_as_uint(dy) >> 31) << (CX_ROWBITS * r + 1);
@@ -1112,7 +1156,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
         // fence) and hand the whole queue over as ONE batch that takes the per-cell path downstream.
         __threadfence();
         cx_run ex = {0, 0, 0, 0, 0};
-        cx_process_queue<false>(P, [&](uint32_t x) { return cx_entry_lin(P, G, __builtin_nontemporal_load(gq + x)); }, qn, lane, false, ex, nullptr);
+        cx_process_queue<false, DT>(P, [&](uint32_t x) { return cx_entry_lin(P, G, __builtin_nontemporal_load(gq + x)); }, qn, lane, false, ex, nullptr);
         // The tolerance rules only ever REMOVE crossings and triangles from what the signs give.  Equal totals therefore
         // mean equal masks in every cell: the wave stays on the common path (its batches, its numbering), only the border
         // voxel count is the exact one.  Otherwise: ONE batch that takes the per-cell path downstream.
@@ -1151,9 +1195,9 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
         if (sum) atomicAdd(cs + threadIdx.x, sum);      // (slot 5: number of waves on the tolerance path; non-zero = flag; slot 6: rounds; slot 7: waves whose queue slice overflowed)
     }
 }
-template <bool ALIGNED>
+template <bool ALIGNED, int DT>
 __global__ __launch_bounds__(256, CX_K1_MIN_WAVES) void cx_k_stream(const cx_params P, const cx_task T) {
-    cx_stream_tile<ALIGNED>(P, T, cx_task_of_block(T));
+    cx_stream_tile<ALIGNED, DT>(P, T, cx_task_of_block(T));
 }
 // Several isovalues of ONE grid: the same pass, with workgroups numbered (tile, level), the level running fastest
 // inside an XCD's sequence: the nlevels workgroups that stream one tile run next to each other on one XCD, so the tile comes
@@ -1169,11 +1213,11 @@ __global__ __launch_bounds__(256, CX_K1_MIN_WAVES) void cx_k_stream(const cx_par
 struct cx_params_pack {
     cx_params p[CX_LEVELS_PER_LAUNCH];
 };
-template <bool ALIGNED>
+template <bool ALIGNED, int DT>
 __global__ __launch_bounds__(256, CX_K1_MIN_WAVES) void cx_k_stream_levels(const cx_params_pack LP, const cx_task T, const uint32_t nlevels) {
     const uint32_t seq = blockIdx.x >> 3;                   // position in this XCD's sequence of workgroups
     const uint32_t tile_seq = seq / nlevels, level = seq - tile_seq * nlevels;
-    cx_stream_tile<ALIGNED>(LP.p[level], T, (blockIdx.x & 7u) * T.chunk + tile_seq);
+    cx_stream_tile<ALIGNED, DT>(LP.p[level], T, (blockIdx.x & 7u) * T.chunk + tile_seq);
 }
 
 // ---- S2 in one launch: workgroup g owns the streaming waves [256 g, 256 g + 256).  It sums the totals of ALL waves before its
@@ -1324,7 +1368,7 @@ __device__ __forceinline__ void cx_skip_rounds(const cx_params& P, const cx_fast
 #ifndef CX_S3_MIN_WAVES
 #define CX_S3_MIN_WAVES 1
 #endif
-template <bool TQ>     // TQ: the interpolation fractions come from the stream kernel's stream (P.tq); else the samples are gathered here
+template <bool TQ, int DT>     // TQ: the interpolation fractions come from the stream kernel's stream (P.tq); else the samples are gathered here
 __global__ __launch_bounds__(256, CX_S3_MIN_WAVES) void cx_k_emit_vertices(const cx_params P, const cx_task T) {
 #ifdef CX_OCC_PAD   // experiment: fewer workgroups per CU (what does the time do with the occupancy?)
     __shared__ uint32_t s_pad[CX_OCC_PAD / 4];
@@ -1366,16 +1410,16 @@ __global__ __launch_bounds__(256, CX_S3_MIN_WAVES) void cx_k_emit_vertices(const
             if (r0) cx_skip_rounds(P, G, q, r0, lane, s_ntri, run);
 #ifdef CX_S3_STAMPS
             nrounds += r1 - r0;
-            cx_emit_queue_fast(P, G, q, r0 * 64u, min(D.n, r1 * 64u), lane, run, reinterpret_cast<uint32_t*>(s_vstage[wave]), s_ntri, info, tacc);
+            cx_emit_queue_fast<DT>(P, G, q, r0 * 64u, min(D.n, r1 * 64u), lane, run, reinterpret_cast<uint32_t*>(s_vstage[wave]), s_ntri, info, tacc);
 #else
             if (TQ)        // the fractions come from the stream kernel (the pointer is the wave's region minus its first vertex: indexed by GLOBAL vertex)
                 cx_emit_queue_t(P, G, q, r0 * 64u, min(D.n, r1 * 64u), lane, run, reinterpret_cast<uint32_t*>(s_vstage[wave]), s_ntri, info,
                                 reinterpret_cast<const uint32_t*>(P.tq) + ((size_t)D.w * T.wcap) - __builtin_amdgcn_readfirstlane(P.wbase[D.w].v));
             else
-                cx_emit_queue_fast(P, G, q, r0 * 64u, min(D.n, r1 * 64u), lane, run, reinterpret_cast<uint32_t*>(s_vstage[wave]), s_ntri, info);
+                cx_emit_queue_fast<DT>(P, G, q, r0 * 64u, min(D.n, r1 * 64u), lane, run, reinterpret_cast<uint32_t*>(s_vstage[wave]), s_ntri, info);
 #endif
         } else if (r0 == 0u) {
-            cx_process_queue<true>(P, [&](uint32_t x) { return cx_entry_lin(P, G, q[x]); }, D.n, lane, true, run, reinterpret_cast<cx_vrec*>(s_vstage[wave]), info);
+            cx_process_queue<true, DT>(P, [&](uint32_t x) { return cx_entry_lin(P, G, q[x]); }, D.n, lane, true, run, reinterpret_cast<cx_vrec*>(s_vstage[wave]), info);
         }
         if (D.rbase + nrb >= hi || fn >= nbatches) break;
         f = fn;
@@ -2414,7 +2458,7 @@ __device__ __forceinline__ void cx_mesh_pin1(cx_mstage1& S) {
 __device__ __forceinline__ void cx_mesh_stage2(const cx_params& P, const cx_task& T, const cx_fast_geom& G, const cx_mstage1& S,
                                                uint32_t n, uint32_t b0, uint32_t lane, uint32_t vbase, uint32_t tbase, uint32_t* slot,
                                                const uint8_t* ntri_lut, const uint32_t* qbt, cx_mround& R) {
-    const float* __restrict__ A = P.grid;
+    const float* __restrict__ A = cx_grid_data<CX_DTYPE_F32>(P.grid);   // fp32 grids only: enqueue_extract sends typed ones through the staged kernels
     const uint32_t plane = P.n1 * P.n2;
     const uint32_t idx = b0 + lane;
     const bool have = idx < n;
@@ -2538,7 +2582,7 @@ __global__ __launch_bounds__(256, CX_EM_MIN_WAVES) void cx_k_emit_mesh(const cx_
     cx_tri_lds_init(L.tri);
     L.ntri[threadIdx.x] = cx_d_voxel_ntri[threadIdx.x];
     __syncthreads();
-    const float* __restrict__ A = P.grid;
+    const float* __restrict__ A = cx_grid_data<CX_DTYPE_F32>(P.grid);   // fp32 grids only (as cx_mesh_stage2)
     const uint32_t plane = P.n1 * P.n2;
     const uint32_t lane = cx_lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2625,12 +2669,17 @@ __global__ __launch_bounds__(256, CX_EM_MIN_WAVES) void cx_k_emit_mesh(const cx_
 #include "cx_tile3d.h"
 
 // ---- launchers --------------------------------------------------------------------------------------
+// a lane loads 4 samples of one row: fp32 grids need 4-byte aligned samples, narrow types take any address
 bool cx_fast_classify_supported(const cx_params& P) {
-    return P.n2 >= 4u && ((reinterpret_cast<uintptr_t>(P.grid) & 3u) == 0u);   // a lane loads 4 samples of one row
+    return cx_fast_classify_supported_dims(P.n2, P.grid);
 }
 
-bool cx_fast_classify_supported_dims(int64_t n2, const float* grid) {
-    return n2 >= 4 && ((reinterpret_cast<uintptr_t>(grid) & 3u) == 0u);
+bool cx_fast_classify_supported_dims(int64_t n2, const cx_grid_ref& grid) {
+    return n2 >= 4 && (grid.dtype != CX_DTYPE_F32 || (reinterpret_cast<uintptr_t>(grid.p) & 3u) == 0u);
+}
+// the aligned stream kernel: n2 % 4 == 0 and every lane's 4 samples on a 4 x sizeof(T) boundary
+static bool cx_stream_aligned(const cx_params& P) {
+    return (P.n2 % 4u == 0u) && ((reinterpret_cast<uintptr_t>(P.grid.p) & (4u * cx_dtype_size(P.grid.dtype) - 1u)) == 0u);
 }
 
 cx_task cx_fast_task(uint32_t n0, uint32_t n1, uint32_t n2) {
@@ -2661,21 +2710,27 @@ cx_task cx_fast_task(uint32_t n0, uint32_t n1, uint32_t n2) {
 }
 
 void cx_launch_stream(const cx_params& P, const cx_task& T, hipStream_t s) {
-    const bool aligned = (P.n2 % 4u == 0u) && ((reinterpret_cast<uintptr_t>(P.grid) & 15u) == 0u);
+    const bool aligned = cx_stream_aligned(P);
     const uint32_t ring = P.tq ? (uint32_t)(4u * 2u * (CX_RJ + 1u) * CX_PLW * sizeof(float)) : 0u;   // the staged sample planes (cx_stream_tile)
-    if (aligned) hipLaunchKernelGGL(cx_k_stream<true>, dim3(T.chunk * 8u), dim3(256), ring, s, P, T);
-    else hipLaunchKernelGGL(cx_k_stream<false>, dim3(T.chunk * 8u), dim3(256), ring, s, P, T);
+#define CX_LAUNCH(DT)                                                                                       \
+    if (aligned) hipLaunchKernelGGL((cx_k_stream<true, DT>), dim3(T.chunk * 8u), dim3(256), ring, s, P, T);  \
+    else hipLaunchKernelGGL((cx_k_stream<false, DT>), dim3(T.chunk * 8u), dim3(256), ring, s, P, T);
+    CX_DISPATCH_DTYPE(P.grid.dtype, CX_LAUNCH)
+#undef CX_LAUNCH
 }
 
 void cx_launch_stream_levels(const cx_params* host_params, const cx_task& T, uint32_t nlevels, hipStream_t s) {
     const cx_params& P0 = host_params[0];
-    const bool aligned = (P0.n2 % 4u == 0u) && ((reinterpret_cast<uintptr_t>(P0.grid) & 15u) == 0u);
+    const bool aligned = cx_stream_aligned(P0);
     for (uint32_t l0 = 0; l0 < nlevels; l0 += CX_LEVELS_PER_LAUNCH) {      // more than 8 levels: another pass over the samples per 8
         const uint32_t n = std::min(CX_LEVELS_PER_LAUNCH, nlevels - l0);
         cx_params_pack pack;
         for (uint32_t k = 0; k < CX_LEVELS_PER_LAUNCH; k++) pack.p[k] = host_params[l0 + std::min(k, n - 1u)];
-        if (aligned) hipLaunchKernelGGL(cx_k_stream_levels<true>, dim3(T.chunk * 8u * n), dim3(256), 0, s, pack, T, n);
-        else hipLaunchKernelGGL(cx_k_stream_levels<false>, dim3(T.chunk * 8u * n), dim3(256), 0, s, pack, T, n);
+#define CX_LAUNCH(DT)                                                                                                    \
+        if (aligned) hipLaunchKernelGGL((cx_k_stream_levels<true, DT>), dim3(T.chunk * 8u * n), dim3(256), 0, s, pack, T, n);   \
+        else hipLaunchKernelGGL((cx_k_stream_levels<false, DT>), dim3(T.chunk * 8u * n), dim3(256), 0, s, pack, T, n);
+        CX_DISPATCH_DTYPE(P0.grid.dtype, CX_LAUNCH)
+#undef CX_LAUNCH
     }
 }
 void cx_launch_scan_levels(const cx_params* device_params, const cx_task& T, uint32_t nlevels, hipStream_t s) {
@@ -2703,7 +2758,7 @@ static uint32_t cx_vertex_grid(const cx_params& P) {
     static const uint32_t resident = [] {
         int per_cu = 0, dev = 0;
         hipDeviceProp_t prop;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cx_k_emit_vertices<true>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cx_k_emit_vertices<true, CX_DTYPE_F32>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1) return 256u * (uint32_t)per_cu;
         return (uint32_t)prop.multiProcessorCount * (uint32_t)per_cu;
     }();
@@ -2713,8 +2768,13 @@ static uint32_t cx_vertex_grid(const cx_params& P) {
 }
 uint32_t cx_vertex_stage_waves(const cx_params& P) { return 4u * cx_vertex_grid(P); }
 void cx_launch_emit_vertices(const cx_params& P, const cx_task& T, hipStream_t s) {
-    if (P.tq) hipLaunchKernelGGL(cx_k_emit_vertices<true>, dim3(P.nvw / 4u), dim3(256), 0, s, P, T);
-    else hipLaunchKernelGGL(cx_k_emit_vertices<false>, dim3(P.nvw / 4u), dim3(256), 0, s, P, T);
+    // the stream of fractions (P.tq, an A/B switch of fp32 grids) is not instantiated for narrow types: enqueue_extract leaves it off
+    if (P.tq) hipLaunchKernelGGL((cx_k_emit_vertices<true, CX_DTYPE_F32>), dim3(P.nvw / 4u), dim3(256), 0, s, P, T);
+    else {
+#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_emit_vertices<false, DT>), dim3(P.nvw / 4u), dim3(256), 0, s, P, T);
+        CX_DISPATCH_DTYPE(P.grid.dtype, CX_LAUNCH)
+#undef CX_LAUNCH
+    }
 }
 
 
@@ -2724,7 +2784,9 @@ void cx_launch_classify_generic(const cx_params& P, hipStream_t s) {
     cpb = (cpb + 255u) & ~255u;
     if (cpb < 16384u) cpb = 16384u;
     const uint32_t blocks = (P.nsamples + cpb - 1u) / cpb;
-    hipLaunchKernelGGL(cx_k_classify_generic, dim3(blocks), dim3(256), 0, s, P, cpb);
+#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_classify_generic<DT>), dim3(blocks), dim3(256), 0, s, P, cpb);
+    CX_DISPATCH_DTYPE(P.grid.dtype, CX_LAUNCH)
+#undef CX_LAUNCH
 }
 
 void cx_launch_emit_triangles(const cx_params& P, const uint64_t* hash_xy, hipStream_t s) {

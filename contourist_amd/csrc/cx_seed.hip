@@ -28,7 +28,7 @@
     } while (0)
 
 struct cxs_grid {
-    const float* A;
+    cx_grid_ref A;      // read by cxs_f / cxs_border_voxel only, through their sample type DT
     uint32_t n0, n1, n2;
     double value;
     int lo[3], hi[3];   // in_range box of the breadth-first growth: lo <= voxel < hi (default 0 .. n-1)
@@ -164,13 +164,14 @@ __global__ void cxs_k_flatten(uint32_t* parent, uint32_t n) {
 }
 
 // ---- seeds: sequential, as the reference runs them (one thread; end point lists are short)
+template <int DT>
 __device__ bool cxs_border_voxel(const cxs_grid& G, int i, int j, int k, bool& inside) {
     inside = i >= 0 && j >= 0 && k >= 0 && i + 1 < (int)G.n0 && j + 1 < (int)G.n1 && k + 1 < (int)G.n2;
     if (!inside) return false;
     double lo = 1e300, hi = -1e300;
     bool allclose = true;
     for (int c = 0; c < 8; c++) {
-        const double f = (double)G.A[((size_t)(i + ((c >> 2) & 1)) * G.n1 + (size_t)(j + ((c >> 1) & 1))) * G.n2 + (size_t)(k + (c & 1))];
+        const double f = (double)cx_sample<DT>(G.A, ((size_t)(i + ((c >> 2) & 1)) * G.n1 + (size_t)(j + ((c >> 1) & 1))) * G.n2 + (size_t)(k + (c & 1)));
         lo = fmin(lo, f); hi = fmax(hi, f);
         if (!(fabs(G.value - f) <= 1e-8 + 1e-5 * fabs(f))) allclose = false;
     }
@@ -187,10 +188,12 @@ __device__ bool cxs_visit(unsigned long long* table, unsigned long long mask, lo
         h++;
     }
 }
+template <int DT>
 __device__ __forceinline__ double cxs_f(const cxs_grid& G, const int p[3]) {
-    return (double)G.A[((size_t)p[0] * G.n1 + (size_t)p[1]) * G.n2 + (size_t)p[2]];
+    return (double)cx_sample<DT>(G.A, ((size_t)p[0] * G.n1 + (size_t)p[1]) * G.n2 + (size_t)p[2]);
 }
 // out[0] = number of seed voxels, out[1] = number of end point pairs that do not straddle the isovalue (error)
+template <int DT>
 __global__ void cxs_k_seeds(cxs_grid G, const int32_t* ep, uint32_t n, unsigned long long* visited, unsigned long long vmask,
                             uint32_t* seeds, uint32_t* out) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
@@ -203,7 +206,7 @@ __global__ void cxs_k_seeds(cxs_grid G, const int32_t* ep, uint32_t n, unsigned 
             if (lowp[a] < 0 || highp[a] < 0 || lowp[a] >= lim || highp[a] >= lim) okp = false;
         }
         if (!okp) { bad++; continue; }
-        double lowv = cxs_f(G, lowp), highv = cxs_f(G, highp);
+        double lowv = cxs_f<DT>(G, lowp), highv = cxs_f<DT>(G, highp);
         if (lowv > G.value || highv < G.value) {
             for (int a = 0; a < 3; a++) { const int t = lowp[a]; lowp[a] = highp[a]; highp[a] = t; }
             const double t = lowv; lowv = highv; highv = t;
@@ -215,14 +218,14 @@ __global__ void cxs_k_seeds(cxs_grid G, const int32_t* ep, uint32_t n, unsigned 
                 const int sum = lowp[a] + highp[a];
                 mid[a] = (sum >= 0) ? sum / 2 : -((-sum + 1) / 2);
             }
-            if (cxs_f(G, mid) < G.value) { for (int a = 0; a < 3; a++) lowp[a] = mid[a]; }
+            if (cxs_f<DT>(G, mid) < G.value) { for (int a = 0; a < 3; a++) lowp[a] = mid[a]; }
             else { for (int a = 0; a < 3; a++) highp[a] = mid[a]; }
         }
         for (int which = 0; which < 2; which++) {
             const int* p = which ? highp : lowp;
             if (!cxs_visit(visited, vmask, p[0], p[1], p[2])) continue;
             bool inside;
-            if (cxs_border_voxel(G, p[0], p[1], p[2], inside)) {
+            if (cxs_border_voxel<DT>(G, p[0], p[1], p[2], inside)) {
                 seeds[ns++] = ((uint32_t)p[0] * G.n1 + (uint32_t)p[1]) * G.n2 + (uint32_t)p[2];
                 continue;
             }
@@ -233,7 +236,7 @@ __global__ void cxs_k_seeds(cxs_grid G, const int32_t* ep, uint32_t n, unsigned 
                         if (di == 0 && dj == 0 && dk == 0) continue;
                         const int q0 = p[0] + di, q1 = p[1] + dj, q2 = p[2] + dk;
                         if (!cxs_visit(visited, vmask, q0, q1, q2)) continue;
-                        if (cxs_border_voxel(G, q0, q1, q2, inside)) {
+                        if (cxs_border_voxel<DT>(G, q0, q1, q2, inside)) {
                             seeds[ns++] = ((uint32_t)q0 * G.n1 + (uint32_t)q1) * G.n2 + (uint32_t)q2;
                             found = true;
                         }
@@ -248,6 +251,7 @@ __global__ void cxs_k_seeds(cxs_grid G, const int32_t* ep, uint32_t n, unsigned 
 // many end point pairs (coarse crossing search, skip > 1): one thread per pair, no shared `visited` set -- each end
 // point yields its own voxel or its first border neighbour.  (The reference's shared set only changes which of
 // several adjacent candidate voxels gets picked when pairs collide.)  Slots 2s, 2s+1; 0xFFFFFFFF = none.
+template <int DT>
 __global__ void cxs_k_seeds_parallel(cxs_grid G, const int32_t* ep, uint32_t n, uint32_t* seeds, uint32_t* out) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
@@ -257,7 +261,7 @@ __global__ void cxs_k_seeds_parallel(cxs_grid G, const int32_t* ep, uint32_t n, 
         const int lim = (int)(a == 0 ? G.n0 : (a == 1 ? G.n1 : G.n2));
         if (lowp[a] < 0 || highp[a] < 0 || lowp[a] >= lim || highp[a] >= lim) { atomicAdd(&out[1], 1u); return; }
     }
-    double lowv = cxs_f(G, lowp), highv = cxs_f(G, highp);
+    double lowv = cxs_f<DT>(G, lowp), highv = cxs_f<DT>(G, highp);
     if (lowv > G.value || highv < G.value) {
         for (int a = 0; a < 3; a++) { const int t = lowp[a]; lowp[a] = highp[a]; highp[a] = t; }
         const double t = lowv; lowv = highv; highv = t;
@@ -269,13 +273,13 @@ __global__ void cxs_k_seeds_parallel(cxs_grid G, const int32_t* ep, uint32_t n, 
             const int sum = lowp[a] + highp[a];
             mid[a] = (sum >= 0) ? sum / 2 : -((-sum + 1) / 2);
         }
-        if (cxs_f(G, mid) < G.value) { for (int a = 0; a < 3; a++) lowp[a] = mid[a]; }
+        if (cxs_f<DT>(G, mid) < G.value) { for (int a = 0; a < 3; a++) lowp[a] = mid[a]; }
         else { for (int a = 0; a < 3; a++) highp[a] = mid[a]; }
     }
     for (int which = 0; which < 2; which++) {
         const int* p = which ? highp : lowp;
         bool inside;
-        if (cxs_border_voxel(G, p[0], p[1], p[2], inside)) {
+        if (cxs_border_voxel<DT>(G, p[0], p[1], p[2], inside)) {
             seeds[2 * s + which] = ((uint32_t)p[0] * G.n1 + (uint32_t)p[1]) * G.n2 + (uint32_t)p[2];
             continue;
         }
@@ -284,7 +288,7 @@ __global__ void cxs_k_seeds_parallel(cxs_grid G, const int32_t* ep, uint32_t n, 
             for (int dj = -1; dj <= 1 && !found; dj++)
                 for (int dk = -1; dk <= 1 && !found; dk++) {
                     if (di == 0 && dj == 0 && dk == 0) continue;
-                    if (cxs_border_voxel(G, p[0] + di, p[1] + dj, p[2] + dk, inside)) {
+                    if (cxs_border_voxel<DT>(G, p[0] + di, p[1] + dj, p[2] + dk, inside)) {
                         seeds[2 * s + which] = ((uint32_t)(p[0] + di) * G.n1 + (uint32_t)(p[1] + dj)) * G.n2 + (uint32_t)(p[2] + dk);
                         found = true;
                     }
@@ -462,10 +466,14 @@ extern "C" int cx_select_seeded3d_ex(cx_ctx* ctx, const int32_t* endpoints_ijk, 
             hipLaunchKernelGGL(cxs_k_union_block, dim3((ncells + CXS_UB - 1u) / CXS_UB), dim3(256), 0, st, ctx->cells, ncells, vmap, parent, G, (const uint32_t*)abits);
             hipLaunchKernelGGL(cxs_k_union_far, dim3(blocks), dim3(256), 0, st, ctx->cells, ncells, vmap, parent, G, (const uint32_t*)abits);
             hipLaunchKernelGGL(cxs_k_flatten, dim3(blocks), dim3(256), 0, st, parent, ncells);
-            if (n <= CXS_SEQUENTIAL_MAX)   // sequential, with the reference's shared visited set
-                hipLaunchKernelGGL(cxs_k_seeds, dim3(1), dim3(64), 0, st, G, ep, (uint32_t)n, visited, vsize - 1ULL, seeds, out);
-            else
-                hipLaunchKernelGGL(cxs_k_seeds_parallel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, G, ep, (uint32_t)n, seeds, out);
+            // (the two kernels that read samples are instantiated per sample type)
+#define CX_LAUNCH(DT)                                                                                                                  \
+            if (n <= CXS_SEQUENTIAL_MAX)   /* sequential, with the reference's shared visited set */                                 \
+                hipLaunchKernelGGL((cxs_k_seeds<DT>), dim3(1), dim3(64), 0, st, G, ep, (uint32_t)n, visited, vsize - 1ULL, seeds, out); \
+            else                                                                                                                       \
+                hipLaunchKernelGGL((cxs_k_seeds_parallel<DT>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, G, ep, (uint32_t)n, seeds, out);
+            CX_DISPATCH_DTYPE(G.A.dtype, CX_LAUNCH)
+#undef CX_LAUNCH
             hipLaunchKernelGGL(cxs_k_mark, dim3((uint32_t)((2 * n + 255) / 256) + 1u), dim3(256), 0, st, ctx->cells, ncells, vmap, parent, seeds, out, flag, flag + ncells + 64, G);
             hipLaunchKernelGGL(cxs_k_keep, dim3(blocks), dim3(256), 0, st, ctx->cells, ncells, parent, flag, flag + ncells + 64, tri_keep, ctx->tris, vkeep, out, G, all_in_range);
             hipLaunchKernelGGL(cxs_k_keep_sum, dim3(1), dim3(CXS_PARTIALS), 0, st, out);

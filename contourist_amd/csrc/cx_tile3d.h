@@ -197,15 +197,15 @@ __global__ __launch_bounds__(256, CX_TILE_MIN_WAVES) void cx_k_tile_emit(const c
         uint32_t carry = half ? (q[first - 1u] >> 15) : 0xFFFFFFFFu;       // (plane step, lane) of the entry before the wave's first
         asm volatile("" : "+v"(e0), "+v"(carry) :: "memory");
         carry = __builtin_amdgcn_readfirstlane(carry);
-        cx_vround_front(P, G, q, end, first, lane, e0, run0, slot2, SH.ntri, Ra);
-        cx_vround_pin(Ra);
+        cx_vround_front<CX_DTYPE_F32>(P, G, q, end, first, lane, e0, run0, slot2, SH.ntri, Ra);
+        cx_vround_pin<CX_DTYPE_F32>(Ra);
         uint32_t par = 0;
         for (uint32_t b0 = first; b0 < end; b0 += 64u) {
             const bool more = b0 + 64u < end;   // wave-uniform
             if (more) {
                 cx_run nb = Ra.base;
                 nb.v += Ra.vtot; nb.t += Ra.ttot; nb.c += Ra.ctot;
-                cx_vround_front(P, G, q, end, b0 + 64u, lane, Ra.e_next, nb, slot2 + (par ^ 1u) * 448u, SH.ntri, Rb);
+                cx_vround_front<CX_DTYPE_F32>(P, G, q, end, b0 + 64u, lane, Ra.e_next, nb, slot2 + (par ^ 1u) * 448u, SH.ntri, Rb);
             }
 #pragma unroll
             for (uint32_t c = 0; c < 8; c++) corners[lane * CX_CORNER_ROW + c] = ((c & 1u) || Ra.vk) ? Ra.f[c] : Ra.f[c + 1u];
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256, CX_TILE_MIN_WAVES) void cx_k_tile_emit(const c
                 nbnd += (uint32_t)__popcll(__ballot(have && Ra.ntri != 0u && (jhi || khi)));
             }
             __builtin_amdgcn_wave_barrier();
-            if (more) cx_vround_pin(Rb);   // the next round's samples are waited for AFTER this round's stores went out
+            if (more) cx_vround_pin<CX_DTYPE_F32>(Rb);   // the next round's samples are waited for AFTER this round's stores went out
             if (more) Ra = Rb;
             par ^= 1u;
         }

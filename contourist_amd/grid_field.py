@@ -75,7 +75,13 @@ class FunctionGrid(object):
         self.cache = {}
         self.grid_dimensions = np.array(shape, dtype=int) - 1
         assert np.all(self.grid_dimensions >= 1)
-        self._dense = samples if _is_torch(samples) else np.ascontiguousarray(samples, dtype=np.float32)
+        if _is_torch(samples):
+            self._dense = samples
+        elif dim == 3 and _ffi_native_dtype(np.asarray(samples).dtype):
+            # 8- and 16-bit samples stay as they are: the 3-D kernels read them (each converts to fp32 exactly)
+            self._dense = _ffi_native_array(samples)
+        else:
+            self._dense = np.ascontiguousarray(samples, dtype=np.float32)
         self.array_backed = True      # f cannot be evaluated outside the samples
         dense = self._dense
 
@@ -192,7 +198,8 @@ class FunctionGrid(object):
         return out
 
     def dense_samples(self, margin=0):
-        """fp32 samples at grid vertices 0..grid_dimensions inclusive (numpy array or CUDA/HIP tensor).
+        """samples at grid vertices 0..grid_dimensions inclusive (numpy array or CUDA/HIP tensor): fp32, or a 3-D sample array
+        of a type the kernels read as it is (from_array keeps uint8 / int8 / uint16 / int16 / float16 arrays in their type).
         margin > 0 (callable f only): vertices -margin .. grid_dimensions+margin, the lattice the reference reaches
         when a seed voxel lies on the rim of the grid (tetrahedral.py:396-441 does not range-check seed voxels)."""
         if margin:
@@ -228,8 +235,21 @@ class FunctionGrid(object):
     def dense_samples_host(self):
         d = self.dense_samples()
         if _is_torch(d):
-            return d.detach().cpu().numpy()
+            d = d.detach().cpu()
+            if str(d.dtype) == "torch.bfloat16":    # no numpy type: fp32 holds every value exactly
+                d = d.float()
+            return d.numpy()
         return d
+
+
+def _ffi_native_array(samples):
+    from . import _ffi
+    return _ffi.native_array(samples)
+
+
+def _ffi_native_dtype(dtype):
+    from . import _ffi
+    return _ffi.native_dtype(dtype)
 
 
 def _is_torch(x):

@@ -100,11 +100,11 @@ class GridContour3d(object):
         ctx = self.context()
         s = self.samples
         if grid_field._is_torch(s):
-            assert s.is_cuda and s.is_contiguous() and str(s.dtype) == "torch.float32", \
-                "device samples must be a contiguous float32 tensor on the GPU"
-            ctx.adopt_device_grid(s.data_ptr(), self.shape, keepalive=s)
+            assert s.is_cuda and s.is_contiguous() and _ffi.native_dtype(s.dtype), \
+                "device samples must be a contiguous tensor on the GPU of a supported dtype (%s)" % ", ".join(_ffi.DTYPE_CODES)
+            ctx.adopt_device_grid(s.data_ptr(), self.shape, keepalive=s, dtype=s.dtype)
         else:
-            ctx.upload_grid(s)
+            ctx.upload_grid_native(s)
         ctx.shadow_grid_f64(self.samples64)
 
     def _in_slabs(self):
@@ -147,10 +147,11 @@ class GridContour3d(object):
         s, s64 = self.samples, self.samples64
         on_device = grid_field._is_torch(s)
         if on_device:
-            assert s.is_cuda and s.is_contiguous() and str(s.dtype) == "torch.float32", \
-                "device samples must be a contiguous float32 tensor on the GPU"
-        else:
-            s = np.ascontiguousarray(s, dtype=np.float32)
+            assert s.is_cuda and s.is_contiguous() and _ffi.native_dtype(s.dtype), \
+                "device samples must be a contiguous tensor on the GPU of a supported dtype (%s)" % ", ".join(_ffi.DTYPE_CODES)
+        else:   # slabs of a supported type are uploaded in that type
+            s = np.asarray(s)
+            s = _ffi.native_array(s) if _ffi.native_dtype(s.dtype) else np.ascontiguousarray(s, dtype=np.float32)
         n0 = int(self.shape[0])
         planes = self._slab_planes()
         parts = []
@@ -161,9 +162,9 @@ class GridContour3d(object):
             local = s[i0:i1 + (1 if has_halo else 0)]
             ctx.set_origin(i0, 0, 0)
             if on_device:
-                ctx.adopt_device_grid(local.data_ptr(), tuple(int(n) for n in local.shape), keepalive=s)
+                ctx.adopt_device_grid(local.data_ptr(), tuple(int(n) for n in local.shape), keepalive=s, dtype=s.dtype)
             else:
-                ctx.upload_grid(local)
+                ctx.upload_grid_native(local)
             ctx.shadow_grid_f64(None if s64 is None else s64[i0:i1 + (1 if has_halo else 0)])
             counts = ctx.extract3d(self.value, self.flags)
             _xyz32, keys, tris = ctx.download_level0(counts)
@@ -333,7 +334,7 @@ class GridContour3d(object):
         "{((i,j,k) low, (i,j,k) high): grid xyz} as the reference keeps it -- host side, for inspection only"
         L = self.level0()
         lo, hi = unpack_edge_ids(L["keys"], self.shape)
-        S = np.asarray(self.samples if not grid_field._is_torch(self.samples) else self.samples.cpu().numpy())
+        S = np.asarray(self.samples if not grid_field._is_torch(self.samples) else self.samples.cpu().float().numpy())
         swap = S[tuple(lo.T)] > S[tuple(hi.T)]
         a = np.where(swap[:, None], hi, lo)
         b = np.where(swap[:, None], lo, hi)
@@ -646,9 +647,11 @@ class MultiLevelIsosurfaces(object):
                 yield (v, self.grid.from_grid_coordinates(grid_points) if len(grid_points) else np.zeros((0, 3)), triangles)
             return
         if grid_field._is_torch(samples):
-            ctx.adopt_device_grid(samples.data_ptr(), shape, keepalive=samples)
+            assert samples.is_cuda and samples.is_contiguous() and _ffi.native_dtype(samples.dtype), \
+                "device samples must be a contiguous tensor on the GPU of a supported dtype (%s)" % ", ".join(_ffi.DTYPE_CODES)
+            ctx.adopt_device_grid(samples.data_ptr(), shape, keepalive=samples, dtype=samples.dtype)
         else:
-            ctx.upload_grid(samples)
+            ctx.upload_grid_native(samples)
         ctx.set_origin(0, 0, 0)
         ctx.set_reference_corner((0, 0, 0))
         self.counts = ctx.extract3d_levels(self.values, self.flags)

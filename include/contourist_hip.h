@@ -77,6 +77,29 @@ int cx_grid_adopt_device(cx_ctx* ctx, const void* device_ptr, int64_t n0, int64_
  * (surface_geometry.py:30-48) fall on the reference's side of it.  The march itself stays on fp32. */
 int cx_grid_shadow_f64(cx_ctx* ctx, const double* host, int64_t n0, int64_t n1, int64_t n2);
 
+/* Sample types of a 3-D grid.  Every one converts to fp32 exactly: the kernels load the narrow type, convert it to fp32 in
+ * registers and run the fp32 march unchanged, so a grid of type T gives bit for bit the result of the same call on its fp32
+ * copy.  cx_grid_upload / cx_grid_adopt_device bind CX_DTYPE_F32. */
+#define CX_DTYPE_F32 0
+#define CX_DTYPE_U8 1
+#define CX_DTYPE_I8 2
+#define CX_DTYPE_U16 3
+#define CX_DTYPE_I16 4
+#define CX_DTYPE_F16 5
+#define CX_DTYPE_BF16 6
+/* n0*n1*n2 samples of type `dtype` (a CX_DTYPE_*; CX_ERR_INVALID otherwise), copied into a buffer of the context of
+ * n0*n1*n2*sizeof(T) bytes: no fp32 copy is made or held. */
+int cx_grid_upload_typed(cx_ctx* ctx, const void* host, int32_t dtype, int64_t n0, int64_t n1, int64_t n2);
+/* the same for samples already on the device (not copied; they must outlive their use).  Any alignment: rows of a multiple of
+ * 4 samples on a 4*sizeof(T)-byte boundary take the aligned stream kernel. */
+int cx_grid_adopt_device_typed(cx_ctx* ctx, const void* device_ptr, int32_t dtype, int64_t n0, int64_t n1, int64_t n2);
+/* the bound grid's sample type, and the device bytes the context holds for it: 0 for an adopted grid, n*sizeof(T) otherwise.
+ * CX_ERR_STATE without a grid.  Either pointer may be NULL.
+ * What a typed grid (dtype != CX_DTYPE_F32) runs through: cx_extract3d* (CX_KERNEL_FUSED and CX_KERNEL_TILED are served by the
+ * staged kernels: cx_level0_path reports 1), cx_extract3d_levels, cx_postprocess3d*, cx_level0_points_f64 and the seeded
+ * selection.  cx_grid_shadow_f64 accepts any type.  The 4-D, 2-D and slab-step entry points have grids of their own (fp32). */
+int cx_grid_info(cx_ctx* ctx, int32_t* dtype, int64_t* device_bytes);
+
 /* the grid is a sub-block of a larger volume starting at lattice point (o0,o1,o2) (slab partitions).
  * Only CX_DIAG_CPYTHON310 depends on it: the reference's set order hashes ABSOLUTE lattice
  * coordinates (tetrahedral.py:567-575), so slabs must hash global coordinates to agree with the
@@ -118,7 +141,8 @@ int cx_counts_get(cx_ctx* ctx, cx_counts* out);
 int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nlevels, uint32_t flags, cx_counts* out_counts);
 int cx_levels_select(cx_ctx* ctx, int32_t index);
 /* which kernels produced the last extraction: 0 generic classify + triangle stage, 1 staged pipeline (stream, scan, vertex
- * stage, triangle stage), 2 stream, scan + fused emit kernel -- for measurement (bench.py names its kernels by it) */
+ * stage, triangle stage), 2 stream, scan + fused emit kernel, 3 tile emit -- for measurement (bench.py names its kernels by
+ * it).  A grid of a type other than CX_DTYPE_F32 never takes 2 or 3: those requests run the staged pipeline (1). */
 int cx_level0_path(cx_ctx* ctx, int* path);
 /* copy the Level-0 mesh to host: verts = n_vertices*4 floats, tris = n_triangles*3 int32 */
 int cx_level0_download(cx_ctx* ctx, float* verts_xyzk, int32_t* tris);
