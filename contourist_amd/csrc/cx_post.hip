@@ -3259,7 +3259,9 @@ __global__ __launch_bounds__(256) void cxp_k_me_visible(const cxp_me_desc* D, ui
     if (x < d.tn) {
         const size_t q = (size_t)d.tf + x;
         const double2 r = *reinterpret_cast<const double2*>(ttime + q * 2);
-        vis = r.x <= d.t && d.t <= r.y;
+        // [start, end): the viewer's active set (misc/morph_triangles.js:117-147, `triangle_max_t > min_t`).  Closed at the end, a surface
+        // on a vertex time held both the slices that end there and those that start there.
+        vis = r.x <= d.t && d.t < r.y;
         if (vis) {
             const uint32_t a = (uint32_t)tris[q * 3] - d.sf, b = (uint32_t)tris[q * 3 + 1] - d.sf, c = (uint32_t)tris[q * 3 + 2] - d.sf;
             if (a < d.sn && b < d.sn && c < d.sn) {

@@ -34,12 +34,12 @@ class MorphTriangles(object):
     def triangles_at(self, t):
         """(points (P,3), triangles (Q,3)) of the surface at time t: the consumer-side evaluation of
         misc/morph_triangles.js:26-140 (lerp along each segment; a triangle is visible while t is inside all
-        three of its segments' intervals)."""
+        three of its segments' intervals [t_low, t_high), i.e. on [tr_min, tr_max) as in the viewer)."""
         P, S, T = self.points4d, self.segment_point_indices, self.triangle_segment_indices
         if len(T) == 0:
             return np.zeros((0, 3)), np.zeros((0, 3), dtype=np.int64)
         lo, hi = P[S[:, 0], 3], P[S[:, 1], 3]
-        inside = (lo <= t) & (t <= hi)
+        inside = (lo <= t) & (t < hi)
         vis = inside[T].all(axis=1)
         lam = np.where(hi > lo, (t - lo) / np.where(hi > lo, hi - lo, 1.0), 0.0)
         pos = P[S[:, 0], :3] + lam[:, None] * (P[S[:, 1], :3] - P[S[:, 0], :3])

@@ -111,3 +111,73 @@ def canonical(segment_ids, points, faces):
         rot = [f[(r + k) % 3] for k in range(3)]
         out.append(tuple((int(segment_ids[k]),) + tuple(float(x) for x in points[k]) for k in rot))
     return sorted(out)
+
+
+# ---- the same in numpy, for millions of triangles (tests/test_oracle4d_np.py holds it to the loops above) --------------------------
+def triangle_intervals_np(points4d, segments, triangles):
+    """triangle_intervals without the loop: per triangle its segments are read in order, and the first one without a positive time
+    extent decides -- t_low > t_high raises ValueError, t_low == t_high leaves the triangle invalid"""
+    P = np.asarray(points4d, dtype=np.float64)
+    S = np.asarray(segments, dtype=np.int64).reshape(-1, 2)
+    T = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+    t_low, t_high = P[S[T, 0], 3].reshape(-1, 3), P[S[T, 1], 3].reshape(-1, 3)
+    rising = t_low < t_high
+    first_flat = np.argmin(np.concatenate([rising, np.zeros((len(T), 1), bool)], axis=1), axis=1)   # 3: none
+    bad = first_flat < 3
+    if bad.any():
+        r = np.nonzero(bad)[0]
+        if (t_low[r, first_flat[r]] > t_high[r, first_flat[r]]).any():
+            raise ValueError("segment in triangle has negative time dimension.")
+    lo = t_low.max(axis=1, initial=-np.inf)
+    hi = t_high.min(axis=1, initial=np.inf)
+    valid = ~bad & (lo < hi)
+    return np.where(valid, lo, 0.0), np.where(valid, hi, 0.0), valid
+
+
+class SurfaceStream(object):
+    """the viewer's surfaces of one set of morph triangles at many times: the triangle intervals and their order by (tr_min, index)
+    are computed once, each surface_at(t) is then what surface_at(points4d, segments, triangles, t) returns, arrays equal element
+    for element (points bit for bit: the same double operations in the same order as interpolate_points_3d)"""
+
+    def __init__(self, points4d, segments, triangles, min_value=None, max_value=None):
+        self.P = np.asarray(points4d, dtype=np.float64)
+        self.S = np.asarray(segments, dtype=np.int64).reshape(-1, 2)
+        self.T = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+        if min_value is None:
+            min_value = float(self.P[:, 3].min())
+        if max_value is None:
+            max_value = float(self.P[:, 3].max())
+        self.epsilon = (max_value - min_value) * 1.0 * 1e-7
+        tr_min, tr_max, valid = triangle_intervals_np(self.P, self.S, self.T)
+        idx = np.nonzero(valid)[0]
+        self.order = idx[np.argsort(tr_min[idx], kind="stable")]        # sorted((tr_min[i], i) for valid i)
+        self.start = tr_min[self.order]
+        self.end = tr_max[self.order]
+
+    def surface_at(self, t):
+        n = np.searchsorted(self.start, t, side="right")               # the scan stops at the first tr_min > t
+        active = self.order[:n][self.end[:n] > t]
+        flat = self.T[active].reshape(-1)
+        uniq, first, where = np.unique(flat, return_index=True, return_inverse=True)
+        by_use = np.argsort(first, kind="stable")
+        seg_ids = uniq[by_use]                                          # numbered by first use
+        number = np.empty(len(by_use), dtype=np.int64)
+        number[by_use] = np.arange(len(by_use))
+        faces = number[where.reshape(-1)].reshape(-1, 3)
+        early, late = self.P[self.S[seg_ids, 0]], self.P[self.S[seg_ids, 1]]
+        eps = self.epsilon
+        diff = late[:, 3] - early[:, 3]
+        ratio = np.full(len(seg_ids), 0.5)
+        big = diff > eps
+        ratio[big] = (t - early[big, 3]) * 1.0 / diff[big]
+        points = early[:, :3] + ratio[:, None] * (late[:, :3] - early[:, :3])
+        before = ratio + eps < 0
+        after = ~before & (ratio - eps > 1)
+        points[before] = early[before, :3]
+        points[after] = late[after, :3]
+        return dict(active=active, segment_ids=seg_ids, points=points.reshape(-1, 3), faces=faces.astype(np.int64).reshape(-1, 3))
+
+
+def surface_at_np(points4d, segments, triangles, t, min_value=None, max_value=None):
+    "surface_at in numpy (one time; SurfaceStream for many)"
+    return SurfaceStream(points4d, segments, triangles, min_value, max_value).surface_at(t)

@@ -113,6 +113,81 @@ def collect_morph_triangles(keys, xyzt, tets, epsilon=1e-7):
     return dict(keys=keys, points4d=V, segments=segments, triangles=triangles)
 
 
+# the six vertex pairs of a tetrahedron a < b < c < d, in the order collect_morph_triangles visits them
+_TET_PAIRS = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
+
+
+def collect_morph_triangles_np(keys, xyzt, tets, epsilon=1e-7, chunk=1 << 21):
+    """collect_morph_triangles in numpy, for meshes of tens of millions of tetrahedra: the same rules, the same dict, arrays equal
+    element for element (tests/test_oracle4d_np.py holds it to the loop version).  Tetrahedra are sliced `chunk` at a time; a
+    triangle is a sorted triple of pair codes i * V + j (i < j vertex indices), de-duplicated over all chunks at the end."""
+    keys = np.asarray(keys, dtype=np.int64)
+    order = np.argsort(keys, kind="stable")
+    inv = np.empty(len(keys), dtype=np.int64)
+    inv[order] = np.arange(len(keys))
+    keys = keys[order]
+    V = np.asarray(xyzt, dtype=np.float64)[order]
+    tets = np.asarray(tets, dtype=np.int64).reshape(-1, 4)
+    tvals = V[:, 3]
+    nv = np.int64(len(keys))
+    found = []
+    for c0 in range(0, len(tets), chunk):
+        S = np.sort(inv[tets[c0:c0 + chunk]], axis=1)                 # a < b < c < d
+        T = tvals[S]                                                   # their times, in vertex order
+        ts = np.sort(T, axis=1)                                        # the four times sorted on their own
+        lo = np.stack([np.minimum(T[:, p], T[:, q]) for p, q in _TET_PAIRS], axis=1)
+        hi = np.stack([np.maximum(T[:, p], T[:, q]) for p, q in _TET_PAIRS], axis=1)
+        code = np.stack([S[:, p] * nv + S[:, q] for p, q in _TET_PAIRS], axis=1)
+        for g in range(3):
+            prev, cur = ts[:, g], ts[:, g + 1]
+            gap = (cur - prev) > 1e-4
+            mid = (0.5 * (cur + prev))[:, None]
+            span = ~((mid + 1e-5 < lo) | (mid - 1e-5 > hi)) & gap[:, None]
+            nspan = span.sum(axis=1)
+            # three spanning pairs: one triangle of them
+            r3 = np.nonzero(nspan == 3)[0]
+            if len(r3):
+                found.append(code[r3][span[r3]].reshape(-1, 3))
+            # four: pair1 = the first spanning pair, pair2 = the LAST spanning pair after it that shares no vertex with it;
+            # one triangle {pair1, pair2, p} for each of the two other spanning pairs p
+            r4 = np.nonzero(nspan == 4)[0]
+            if len(r4):
+                sp, cd, sv = span[r4], code[r4], S[r4]
+                k1 = np.argmax(sp, axis=1)
+                rows = np.arange(len(r4))
+                i1 = sv[rows, np.array([p for p, _ in _TET_PAIRS])[k1]]
+                j1 = sv[rows, np.array([q for _, q in _TET_PAIRS])[k1]]
+                k2 = np.full(len(r4), -1, dtype=np.int64)
+                for k, (p, q) in enumerate(_TET_PAIRS):
+                    ik, jk = sv[:, p], sv[:, q]
+                    disjoint = (ik != i1) & (ik != j1) & (jk != i1) & (jk != j1)
+                    k2 = np.where(sp[:, k] & (k > k1) & disjoint, k, k2)
+                if (k2 < 0).any():
+                    raise ValueError("four spanning pairs without a disjoint one")
+                rest = sp.copy()
+                rest[rows, k1] = False
+                rest[rows, k2] = False
+                others = cd[rest].reshape(-1, 2)
+                c1, c2 = cd[rows, k1], cd[rows, k2]
+                found.append(np.stack([c1, c2, others[:, 0]], axis=1))
+                found.append(np.stack([c1, c2, others[:, 1]], axis=1))
+    tri = np.sort(np.concatenate(found), axis=1) if found else np.zeros((0, 3), np.int64)
+    if len(tri):
+        tri = tri[np.lexsort(tri.T[::-1])]
+        tri = tri[np.concatenate([[True], (tri[1:] != tri[:-1]).any(axis=1)])]        # a set of triangles
+    t_eps = epsilon * (tvals.max() - tvals.min()) if len(tvals) else 0.0
+    pi, pj = tri // nv, tri % nv
+    tri = tri[(np.abs(tvals[pi] - tvals[pj]) > t_eps).all(axis=1)]
+    seg_codes = np.unique(tri)                                          # sorted (i, j) pairs
+    i, j = seg_codes // nv, seg_codes % nv
+    flip = tvals[i] > tvals[j]
+    segments = np.stack([np.where(flip, j, i), np.where(flip, i, j)], axis=1).astype(np.int64).reshape(-1, 2)
+    triangles = np.sort(np.searchsorted(seg_codes, tri), axis=1).astype(np.int64).reshape(-1, 3)
+    if len(triangles):
+        triangles = triangles[np.lexsort(triangles.T[::-1])]
+    return dict(keys=keys, points4d=V, segments=segments, triangles=triangles)
+
+
 def orient_morph_triangles(M, shuffle=None):
     """MorphTriangles.orient_triangles (morph_geometry.py:49-89): SurfaceGeometry.orient_triangles on the
     3-D midpoints of the segments, propagating only between triangles whose time ranges overlap.

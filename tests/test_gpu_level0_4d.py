@@ -537,7 +537,8 @@ def test_post_steps_and_morph_triangles_against_the_oracle_at_mid_size():
     """26 x 24 x 22 x 12 samples, two moving blobs + noise (277 k tetrahedra, 525 k morph triangles -- the reference's own run would take
     hours: the oracle's restatement stands in, pinned by the small fixtures above): bin_times / drop_instant / tiny collapse (B3),
     the slicing into morph triangles (B4: segments with direction, triangles as sets of segments) and the time-compatible windings
-    (B5: every triangle the oracle's flood fill orients agrees) -- pentatopes.py:162-189, 314-368, morph_geometry.py:145-237"""
+    (B5: every triangle the oracle's flood fill orients agrees) -- pentatopes.py:162-189, 314-368, morph_geometry.py:145-237; the numpy
+    oracles equal the loop ones here, and the device's surfaces equal the viewer oracle's (B6)"""
     from contourist_amd import pentatopes
     from oracle import level0_4d, postpass4d
     shape = (26, 24, 22, 12)
@@ -566,6 +567,9 @@ def test_post_steps_and_morph_triangles_against_the_oracle_at_mid_size():
     want = level0_4d.canonical4(ko, W["xyzt"], W["tets"])[2]
     assert np.array_equal(got, want)
     M = postpass4d.collect_morph_triangles(ko, W["xyzt"], W["tets"])
+    N = postpass4d.collect_morph_triangles_np(ko, W["xyzt"], W["tets"], chunk=50000)       # the numpy oracle: the same, exactly
+    for k in M:
+        assert M[k].dtype == N[k].dtype and np.array_equal(M[k], N[k]), k
     seg_d = np.asarray(MT.segment_point_indices, dtype=np.int64)
     seg_o = np.asarray(M["segments"], dtype=np.int64)
     # segments with direction: pairs of edge ids
@@ -579,6 +583,20 @@ def test_post_steps_and_morph_triangles_against_the_oracle_at_mid_size():
     assert common == len(ot) and agree == common, (common, agree, len(ot))
     bad_d, seen_d = postpass4d.forced_pair_violations(kh, MT.segment_point_indices, MT.triangle_segment_indices, MT.points4d)
     assert seen_d > 0 and bad_d == 0, (bad_d, seen_d)
+    # B6: the device's surfaces against the viewer oracle on the device's morph triangles -- generic times, vertex times, both ends;
+    # the numpy viewer oracle against the loop one at two of them
+    from oracle import morph_eval
+    from test_gpu_config4_back_half import check_surfaces
+    P, S, T = MT.points4d, MT.segment_point_indices, MT.triangle_segment_indices
+    lo, hi = float(MT.min_value), float(MT.max_value)
+    vt = np.unique(P[:, 3])
+    times = [lo + f * (hi - lo) for f in (0.137, 0.419, 0.677)] + [float(vt[2]), float(vt[len(vt) // 2]), lo, hi]
+    stream = morph_eval.SurfaceStream(P, S, T)
+    assert check_surfaces(stream, times, maker.triangles_at_many(times)) > 10000
+    for t in (times[1], times[4]):
+        Wl, Wn = morph_eval.surface_at(P, S, T, t), stream.surface_at(t)
+        assert np.array_equal(Wl["active"], Wn["active"]) and np.array_equal(Wl["faces"], Wn["faces"])
+        assert np.array_equal(Wl["points"].view(np.uint64), Wn["points"].view(np.uint64))
 
 
 def _blob_field(shape, seed):
@@ -726,7 +744,8 @@ def test_per_t_stream_argument_errors():
 
 def test_per_t_stream_at_mid_size_equals_the_host_evaluation():
     """64 x 64 x 64 x 32 (two moving blobs, ~1.5 M morph triangles): the per-t stream of 40 times in one call -- windows of many blocks,
-    offsets across blocks and across times -- against MorphTriangles.triangles_at on the host for every time, and the single calls"""
+    offsets across blocks and across times -- against MorphTriangles.triangles_at on the host for every time, and the single calls;
+    then the post steps and morph triangles against the oracle chain (B3, B4) and every surface against the viewer oracle (B6)"""
     torch = pytest.importorskip("torch")
     from contourist_amd import _ffi, morph_geometry
     dev = torch.device("cuda", 0)
@@ -742,9 +761,12 @@ def test_per_t_stream_at_mid_size_equals_the_host_evaluation():
     ctx = _ffi.Context(0)
     try:
         ctx.adopt_device_grid4d(A.data_ptr(), shape, keepalive=A)
-        ctx.extract4d(0.5, 1)
-        ctx.postprocess4d(100)
-        pts, segs, tris, _ = ctx.morph_triangles()
+        c = ctx.extract4d(0.5, 1)
+        _, keys, _ = ctx.download_level0_4d(c)
+        post = ctx.postprocess4d(100)
+        points_post, tets_post = ctx.download_level1_4d(post)
+        morph = ctx.morph_triangles()
+        pts, segs, tris, _ = morph
         assert len(tris) > 500000
         MT = morph_geometry.MorphTriangles(pts, segs, tris)
         tmin, tmax = float(pts[:, 3].min()), float(pts[:, 3].max())
@@ -762,6 +784,11 @@ def test_per_t_stream_at_mid_size_equals_the_host_evaluation():
         for i in (0, 7, 21):
             p1, t1 = ctx.morph_eval(float(times[i]))
             assert np.array_equal(t1, many[i][1]) and np.array_equal(p1, many[i][0])
+        # B3 / B4 against the oracle chain (C oracle's Level 0, post steps, numpy slicing); B6 against the viewer oracle
+        from oracle import morph_eval
+        from test_gpu_config4_back_half import check_post_and_morph, check_surfaces
+        check_post_and_morph(keys, np.ascontiguousarray(A.cpu().numpy()), 0.5, points_post, tets_post, post, morph)
+        assert check_surfaces(morph_eval.SurfaceStream(pts, segs, tris), times, many) == total
     finally:
         ctx.close()
 
