@@ -14,7 +14,9 @@ if os.environ.get("CX_DEBUG") == "1" and os.environ.get("CX_LIB_PATH"):   # A/B 
     LIB_PATH = os.environ["CX_LIB_PATH"]
 
 CX_OK = 0
+CX_ERR_INVALID = -1
 CX_ERR_CAPACITY = -5
+CX_ERR_UNSUPPORTED = -6
 CX_DIAG_CANONICAL = 0
 CX_DIAG_CPYTHON310 = 1
 CX_KERNEL_GENERIC = 0x100
@@ -28,6 +30,7 @@ SYMBOLS = [
     "cx_grid_upload", "cx_grid_adopt_device", "cx_grid_upload_typed", "cx_grid_adopt_device_typed", "cx_grid_info", "cx_grid_shadow_f64", "cx_set_origin", "cx_reserve",
     "cx_extract3d", "cx_extract3d_async", "cx_counts_get", "cx_extract3d_levels", "cx_levels_select", "cx_level0_path", "cx_level0_download", "cx_level0_device_ptrs", "cx_level0_device_records", "cx_level0_download_records",
     "cx_postprocess3d", "cx_postprocess3d_ex", "cx_level0_points_f64", "cx_postprocess3d_mesh", "cx_select_seeded3d", "cx_select_seeded3d_ex", "cx_seeded_masks_download", "cx_set_reference_corner", "cx_level1_download", "cx_level1_device_ptrs", "cx_level1_download_keys", "cx_postprocess3d_shard_begin", "cx_postprocess3d_shard_boundary", "cx_postprocess3d_shard_candidates", "cx_postprocess3d_shard_finish", "cx_level1_write", "cx_surface_geometry",
+    "cx_level0_normals", "cx_level0_normals_download", "cx_level1_normals", "cx_level1_normals_download", "cx_level0_sample_grid", "cx_level1_sample_grid",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -172,6 +175,12 @@ def load():
         "cx_postprocess3d_shard_finish": [vp, vp, vp, i64, vp],
         "cx_level1_write": [vp, ctypes.c_int, ctypes.c_char_p, vp, vp],
         "cx_surface_geometry": [vp, vp, ctypes.POINTER(i64), vp, ctypes.POINTER(i64), ctypes.c_int],
+        "cx_level0_normals": [vp, vp, ctypes.POINTER(vp)],
+        "cx_level0_normals_download": [vp, vp, vp],
+        "cx_level1_normals": [vp, vp, ctypes.POINTER(vp)],
+        "cx_level1_normals_download": [vp, vp, vp],
+        "cx_level0_sample_grid": [vp, vp, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(vp), vp],
+        "cx_level1_sample_grid": [vp, vp, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(vp), vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -494,16 +503,113 @@ class Context(object):
 
     def write_level1(self, path, fmt="ply", mins=None, delta=None):
         """the Level-1 mesh of the last post-pass as a binary file written straight from the device buffers (no numpy arrays):
-        fmt "ply" (float64 positions, int32 faces) or "gltf_bin" (float32 positions + uint32 indices); mins / delta: world
+        fmt "ply" (float64 positions, int32 faces), "gltf_bin" (float32 positions + uint32 indices), "ply_normals" (double nx ny nz
+        after x y z) or "gltf_bin_normals" (float32 positions, float32 normals, uint32 indices); mins / delta: world
         coordinates = grid * delta + mins.  -> dict(n_vertices, n_triangles, bytes, min, max)"""
         md = None
         if mins is not None or delta is not None:
             md = np.ascontiguousarray(np.concatenate([np.asarray(mins if mins is not None else [0, 0, 0], dtype=np.float64).reshape(3),
                                                       np.asarray(delta if delta is not None else [1, 1, 1], dtype=np.float64).reshape(3)]))
         info = np.zeros(9, dtype=np.float64)
-        self._check(self.lib.cx_level1_write(self.handle, {"ply": 0, "gltf_bin": 1}[fmt], os.fsencode(path),
+        self._check_attr(self.lib.cx_level1_write(self.handle, {"ply": 0, "gltf_bin": 1, "ply_normals": 2, "gltf_bin_normals": 3}[fmt], os.fsencode(path),
                                              None if md is None else md.ctypes.data, info.ctypes.data))
         return dict(n_vertices=int(info[0]), n_triangles=int(info[1]), bytes=int(info[2]), min=info[3:6].copy(), max=info[6:9].copy())
+
+    # ---- vertex attributes (cx_attr.hip): normals from the field's gradient, a second grid sampled at the vertices ----------
+    def _check_attr(self, rc):
+        "CX_ERR_UNSUPPORTED of the attribute calls is a NotImplementedError with the library's plain message"
+        if rc == CX_ERR_UNSUPPORTED:
+            raise NotImplementedError(self.lib.cx_last_error(self.handle).decode("utf-8", "replace"))
+        self._check(rc)
+
+    @staticmethod
+    def _delta3(delta):
+        return None if delta is None else np.ascontiguousarray(np.asarray(delta, dtype=np.float64).reshape(3))
+
+    def _device_view(self, ptr, shape, typestr, torch_dtype):
+        "a torch tensor that owns a copy of `shape` elements at device address `ptr` (an empty one for ptr == 0)"
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not ptr or not shape[0]:
+            return torch.zeros(shape, dtype=torch_dtype, device=dev)
+
+        class _View(object):
+            def __init__(self, ptr, shape, typestr):
+                self.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
+        self.synchronize()
+        return torch.as_tensor(_View(ptr, shape, typestr), device=dev).clone()
+
+    def level0_normals(self, counts, delta=None, device=False):
+        """(V,4) float32 {nx, ny, nz, |g|} per vertex record of the current extraction, in the order of download_level0
+        (delta: world spacing per axis; device=True: a torch tensor on the GPU)"""
+        nv = int(counts["n_vertices"])
+        d3 = self._delta3(delta)
+        dp = None if d3 is None else d3.ctypes.data
+        if device:
+            import torch
+            p = ctypes.c_void_p()
+            self._check_attr(self.lib.cx_level0_normals(self.handle, dp, ctypes.byref(p)))
+            return self._device_view(p.value or 0, (nv, 4), "<f4", torch.float32)
+        out = np.zeros((nv, 4), dtype=np.float32)
+        self._check_attr(self.lib.cx_level0_normals_download(self.handle, dp, out.ctypes.data))
+        return out
+
+    def level1_normals(self, counts, delta=None, device=False):
+        """(V,3) float64 unit normals of the Level-1 vertices in the order of download_level1, agreeing with the winding of
+        their triangles (delta: world spacing per axis; device=True: a torch tensor on the GPU)"""
+        nv = int(counts["n_vertices"])
+        d3 = self._delta3(delta)
+        dp = None if d3 is None else d3.ctypes.data
+        if device:
+            import torch
+            p = ctypes.c_void_p()
+            self._check_attr(self.lib.cx_level1_normals(self.handle, dp, ctypes.byref(p)))
+            return self._device_view(p.value or 0, (nv, 3), "<f8", torch.float64)
+        out = np.zeros((nv, 3), dtype=np.float64)
+        self._check_attr(self.lib.cx_level1_normals_download(self.handle, dp, out.ctypes.data))
+        return out
+
+    def _second_grid(self, field):
+        "(pointer, CX_DTYPE code, on_device, keepalive) of a second grid of the bound grid's shape, in its own type when the kernels read it"
+        if hasattr(field, "data_ptr"):     # a torch tensor
+            assert tuple(int(n) for n in field.shape) == tuple(self.shape), (tuple(field.shape), self.shape)
+            t = field if native_dtype(field.dtype) else field.float()
+            t = t.contiguous()
+            if t.is_cuda:
+                return t.data_ptr(), dtype_code(t.dtype), 1, t
+            field = t.numpy() if str(t.dtype) != "torch.bfloat16" else t.float().numpy()
+        a = np.asarray(field)
+        assert tuple(a.shape) == tuple(self.shape), (a.shape, self.shape)
+        a = native_array(a) if native_dtype(a.dtype) else np.ascontiguousarray(a, dtype=np.float32)
+        return a.ctypes.data, dtype_code(a.dtype), 0, a
+
+    def level0_sample(self, counts, field, device=False):
+        "(V,) float32: `field` (an array or device tensor of the bound grid's shape) at the Level-0 vertices, B(q) + t (B(q+d) - B(q))"
+        nv = int(counts["n_vertices"])
+        ptr, code, on_dev, keep = self._second_grid(field)
+        p = ctypes.c_void_p()
+        if device:
+            import torch
+            self._check_attr(self.lib.cx_level0_sample_grid(self.handle, ctypes.c_void_p(ptr), code, on_dev, ctypes.byref(p), None))
+            return self._device_view(p.value or 0, (nv,), "<f4", torch.float32)
+        out = np.zeros(nv, dtype=np.float32)
+        self._check_attr(self.lib.cx_level0_sample_grid(self.handle, ctypes.c_void_p(ptr), code, on_dev, ctypes.byref(p), out.ctypes.data))
+        del keep
+        return out
+
+    def level1_sample(self, counts, field, device=False):
+        "(V,) float64: `field` at the Level-1 vertices, B(low) + ratio (B(high) - B(low)), in the order of download_level1"
+        nv = int(counts["n_vertices"])
+        ptr, code, on_dev, keep = self._second_grid(field)
+        p = ctypes.c_void_p()
+        if device:
+            import torch
+            self._check_attr(self.lib.cx_level1_sample_grid(self.handle, ctypes.c_void_p(ptr), code, on_dev, ctypes.byref(p), None))
+            return self._device_view(p.value or 0, (nv,), "<f8", torch.float64)
+        out = np.zeros(nv, dtype=np.float64)
+        self._check_attr(self.lib.cx_level1_sample_grid(self.handle, ctypes.c_void_p(ptr), code, on_dev, ctypes.byref(p), out.ctypes.data))
+        del keep
+        return out
 
     def surface_geometry(self, points, triangles, do_clean):
         pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3).copy()

@@ -1,0 +1,363 @@
+// cx_attr.hip -- vertex attributes of the 3-D isosurface: normals from the field's gradient and a second grid sampled at the
+// vertices (include/contourist_hip.h, "vertex attributes").
+//
+// A vertex is a crossing of the lattice edge a -> b at fraction r.  The gradient G of the resident sample array at a lattice point
+// follows numpy.gradient with its defaults: (f[p+e] - f[p-e]) / 2 inside, the one-sided first difference on the rim of the marched
+// array.  Both are ONE difference of two samples times 0.5 or 1: the neighbour indices are clamped to the array and the scale
+// follows from how many of them moved.  g = G(a) + r (G(b) - G(a)), divided per axis by the world spacing when one is handed
+// over, n = s g / |g| and (0,0,0) when |g| == 0.
+//   Level 0: a = q, b = q + d, r = the record's fp32 fraction, fp32, s = +1, float4 {nx, ny, nz, |g|} per vertex record.
+//   Level 1: a / b / r = low point / high point / ratio exactly as cxp_k_vertices_f64 (cx_post.hip) computes them, float64,
+//            s = -1 where the orientation step reversed the vertex's component.
+// No atomics, no adjacency: every lane owns one vertex and writes one record.
+#include <cmath>
+#include <string>
+
+#include "cx_ctx.h"
+
+#define CXA_HIP(ctx, call)                                                                       \
+    do {                                                                                         \
+        hipError_t e__ = (call);                                                                 \
+        if (e__ != hipSuccess) {                                                                 \
+            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
+            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
+        }                                                                                        \
+    } while (0)
+
+typedef float cxa_v4f __attribute__((ext_vector_type(4)));
+
+struct cxa_dims {
+    uint32_t n0, n1, n2, plane;
+    cx_fdiv dplane, drow;
+};
+
+// offsets (in samples) to the clamped lower / upper neighbour of coordinate c on an axis of n samples with the given stride, and the
+// scale of the difference: 0.5 when both neighbours exist, 1 on the rim (n >= 2, so one of them always does)
+__device__ __forceinline__ void cxa_axis(uint32_t c, uint32_t n, uint32_t stride, uint32_t& lo, uint32_t& hi, bool& both) {
+    lo = c ? stride : 0u;
+    hi = (c + 1u < n) ? stride : 0u;
+    both = lo != 0u && hi != 0u;
+}
+
+// fp32 gradient at lattice point (i, j, k) = sample `lin`: six loads, three in the point's own plane (the k neighbours share its
+// 128-byte line or the next one, the j neighbours lie one row away); one rounding per component (the difference; the scale is exact)
+template <int DT>
+__device__ __forceinline__ void cxa_grad32(const cx_grid_ref& A, const cxa_dims& D, uint32_t lin, uint32_t i, uint32_t j, uint32_t k, float& gx,
+                                           float& gy, float& gz) {
+    uint32_t lo, hi;
+    bool both;
+    cxa_axis(k, D.n2, 1u, lo, hi, both);
+    gz = (cx_sample<DT>(A, lin + hi) - cx_sample<DT>(A, lin - lo)) * (both ? 0.5f : 1.0f);
+    cxa_axis(j, D.n1, D.n2, lo, hi, both);
+    gy = (cx_sample<DT>(A, lin + hi) - cx_sample<DT>(A, lin - lo)) * (both ? 0.5f : 1.0f);
+    cxa_axis(i, D.n0, D.plane, lo, hi, both);
+    gx = (cx_sample<DT>(A, lin + hi) - cx_sample<DT>(A, lin - lo)) * (both ? 0.5f : 1.0f);
+}
+
+// ---- Level 0: one lane per vertex record, in record order (the 64 vertices of a wave sit in neighbouring cells, so the rows their
+// twelve samples come from are a handful of lines shared by the whole wave).  Output: one nontemporal 16-byte store per lane.
+template <int DT, bool WORLD>
+__global__ __launch_bounds__(256) void cx_k_vertex_normals(const cx_grid_ref A, const cx_vrec* __restrict__ recs, cxa_v4f* __restrict__ out, uint32_t nv,
+                                                           cxa_dims D, float d0, float d1, float d2) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= nv) return;
+    const cx_vrec rec = recs[v];
+    const uint32_t lin = rec.x >> 3, d = rec.x & 7u;
+    const float t = __uint_as_float(rec.y);
+    const uint32_t i = cx_div(lin, D.dplane);
+    const uint32_t rem = lin - i * D.plane;
+    const uint32_t j = cx_div(rem, D.drow);
+    const uint32_t k = rem - j * D.n2;
+    const uint32_t di = (d >> 2) & 1u, dj = (d >> 1) & 1u, dk = d & 1u;
+    cxa_v4f o = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (i + di < D.n0 && j + dj < D.n1 && k + dk < D.n2) {      // (always, for a record of the march: nothing is read outside the array)
+        float ax, ay, az, bx, by, bz;
+        cxa_grad32<DT>(A, D, lin, i, j, k, ax, ay, az);
+        cxa_grad32<DT>(A, D, lin + di * D.plane + dj * D.n2 + dk, i + di, j + dj, k + dk, bx, by, bz);
+        float gx = fmaf(t, bx - ax, ax), gy = fmaf(t, by - ay, ay), gz = fmaf(t, bz - az, az);
+        if (WORLD) { gx /= d0; gy /= d1; gz /= d2; }
+        // scaled by a power of two (exact) so that the squares neither overflow nor vanish
+        const float m = fmaxf(fabsf(gx), fmaxf(fabsf(gy), fabsf(gz)));
+        if (m > 0.0f && m <= 3.0e38f) {
+            int e;
+            (void)frexpf(m, &e);
+            const float sx = ldexpf(gx, -e), sy = ldexpf(gy, -e), sz = ldexpf(gz, -e);
+            const float len = sqrtf(sx * sx + sy * sy + sz * sz);
+            const float inv = 1.0f / len;
+            o = cxa_v4f{sx * inv, sy * inv, sz * inv, ldexpf(len, e)};
+        }
+    }
+    __builtin_nontemporal_store(o, out + v);
+}
+
+// a second grid B at the same places: B(q) + t (B(q + d) - B(q)), two samples per vertex
+template <int DTB>
+__global__ __launch_bounds__(256) void cx_k_vertex_sample(const cx_grid_ref B, const cx_vrec* __restrict__ recs, float* __restrict__ out, uint32_t nv,
+                                                          uint32_t n2, uint32_t plane, uint32_t nsamples) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= nv) return;
+    const cx_vrec rec = recs[v];
+    const uint32_t lin = rec.x >> 3, d = rec.x & 7u;
+    const uint32_t lin2 = lin + ((d & 4u) ? plane : 0u) + ((d & 2u) ? n2 : 0u) + (d & 1u);
+    float r = 0.0f;
+    if (lin2 < nsamples) {
+        const float b0 = cx_sample<DTB>(B, lin), b1 = cx_sample<DTB>(B, lin2);
+        r = fmaf(__uint_as_float(rec.y), b1 - b0, b0);
+    }
+    __builtin_nontemporal_store(r, out + v);
+}
+
+// ---- Level 1: float64, one lane per Level-1 vertex, driven by the key array.  Not hot: clarity over tricks.
+// The edge of every vertex once: {sample index of the low point a, of the high point b, ratio} as cxp_k_vertices_f64 has them
+struct cxa_edge1 {
+    uint32_t a, b;
+    double r;
+};
+template <int DT>
+__device__ __forceinline__ double cxa_sample64(const cx_grid_ref& A, const double* __restrict__ A64, uint32_t lin) {
+    return A64 ? A64[lin] : (double)cx_sample<DT>(A, lin);
+}
+template <int DT>
+__global__ void cx_k_level1_edges(const cx_grid_ref A, const double* __restrict__ A64, const uint32_t* __restrict__ keys, uint32_t nv, uint32_t n2,
+                                  uint32_t plane, uint32_t nsamples, double value, cxa_edge1* __restrict__ out) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const uint32_t key = keys[v];
+    const uint32_t lin = key >> 3, d = key & 7u;
+    const uint32_t lin2 = lin + ((d & 4u) ? plane : 0u) + ((d & 2u) ? n2 : 0u) + (d & 1u);
+    cxa_edge1 e = {0u, 0u, 0.5};
+    if (lin2 < nsamples) {
+        const double f0 = cxa_sample64<DT>(A, A64, lin), f1 = cxa_sample64<DT>(A, A64, lin2);
+        const bool owner_low = !(f0 > f1);             // the reference swaps when flow > fhigh
+        const double flow = owner_low ? f0 : f1, fhigh = owner_low ? f1 : f0;
+        const double den = 1.0 * (fhigh - flow);
+        if (!(fabs(den) <= 1e-8)) e.r = (value - flow) / den;
+        e.a = owner_low ? lin : lin2;
+        e.b = owner_low ? lin2 : lin;
+    }
+    out[v] = e;
+}
+template <int DT>
+__device__ __forceinline__ void cxa_grad64(const cx_grid_ref& A, const double* __restrict__ A64, const cxa_dims& D, uint32_t lin, double g[3]) {
+    const uint32_t i = cx_div(lin, D.dplane);
+    const uint32_t rem = lin - i * D.plane;
+    const uint32_t j = cx_div(rem, D.drow);
+    const uint32_t k = rem - j * D.n2;
+    uint32_t lo, hi;
+    bool both;
+    cxa_axis(i, D.n0, D.plane, lo, hi, both);
+    g[0] = (cxa_sample64<DT>(A, A64, lin + hi) - cxa_sample64<DT>(A, A64, lin - lo)) * (both ? 0.5 : 1.0);
+    cxa_axis(j, D.n1, D.n2, lo, hi, both);
+    g[1] = (cxa_sample64<DT>(A, A64, lin + hi) - cxa_sample64<DT>(A, A64, lin - lo)) * (both ? 0.5 : 1.0);
+    cxa_axis(k, D.n2, 1u, lo, hi, both);
+    g[2] = (cxa_sample64<DT>(A, A64, lin + hi) - cxa_sample64<DT>(A, A64, lin - lo)) * (both ? 0.5 : 1.0);
+}
+template <int DT>
+__global__ void cx_k_level1_normals(const cx_grid_ref A, const double* __restrict__ A64, const cxa_edge1* __restrict__ edges,
+                                    const uint8_t* __restrict__ vflip, uint32_t nv, cxa_dims D, int world, double d0, double d1, double d2,
+                                    double* __restrict__ out) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const cxa_edge1 e = edges[v];
+    double ga[3], gb[3], g[3];
+    cxa_grad64<DT>(A, A64, D, e.a, ga);
+    cxa_grad64<DT>(A, A64, D, e.b, gb);
+#pragma unroll
+    for (int a = 0; a < 3; a++) g[a] = ga[a] + e.r * (gb[a] - ga[a]);
+    if (world) { g[0] /= d0; g[1] /= d1; g[2] /= d2; }
+    const double m = fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2])));
+    double n[3] = {0.0, 0.0, 0.0};
+    if (m > 0.0 && m <= 1.7e308) {
+        int ex;
+        (void)frexp(m, &ex);
+        const double sx = ldexp(g[0], -ex), sy = ldexp(g[1], -ex), sz = ldexp(g[2], -ex);
+        const double len = sqrt(sx * sx + sy * sy + sz * sz);
+        const double s = vflip[v] ? -1.0 : 1.0;
+        n[0] = s * sx / len; n[1] = s * sy / len; n[2] = s * sz / len;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; a++) out[(size_t)v * 3 + a] = n[a];
+}
+template <int DTB>
+__global__ void cx_k_level1_sample(const cx_grid_ref B, const cxa_edge1* __restrict__ edges, uint32_t nv, double* __restrict__ out) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const cxa_edge1 e = edges[v];
+    const double b0 = (double)cx_sample<DTB>(B, e.a), b1 = (double)cx_sample<DTB>(B, e.b);
+    out[v] = b0 + e.r * (b1 - b0);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------------
+static int cxa_fail(cx_ctx* ctx, int code, const char* msg) {
+    ctx->err = msg;
+    return code;
+}
+static cxa_dims cxa_dims_of(const cx_ctx* ctx) {
+    cxa_dims D;
+    D.n0 = (uint32_t)ctx->n0; D.n1 = (uint32_t)ctx->n1; D.n2 = (uint32_t)ctx->n2;
+    D.plane = D.n1 * D.n2;
+    D.dplane = cx_fdiv_make(D.plane);
+    D.drow = cx_fdiv_make(D.n2);
+    return D;
+}
+static bool cxa_delta_ok(const double* delta3) {
+    if (!delta3) return true;
+    for (int a = 0; a < 3; a++)
+        if (!(delta3[a] > 0.0) || !std::isfinite(delta3[a])) return false;
+    return true;
+}
+static inline dim3 cxa_grid(uint32_t n) { return dim3((n + 255u) / 256u); }
+
+void cx_attr_free(cx_ctx* ctx) {
+    cx_release(ctx->attr_n0, ctx->attr_n0_cap);
+    cx_release(ctx->attr_n1, ctx->attr_n1_cap);
+    cx_release(ctx->attr_v0, ctx->attr_v0_cap);
+    cx_release(ctx->attr_v1, ctx->attr_v1_cap);
+    cx_release(ctx->attr_e1, ctx->attr_e1_cap);
+    cx_release(ctx->attr_grid, ctx->attr_grid_cap);
+}
+
+// the second grid as the kernels read it: the caller's device pointer, or a copy of the host array in a buffer of the context
+static int cxa_second_grid(cx_ctx* ctx, const char* who, const void* grid, int32_t dtype, int on_device, cx_grid_ref* out) {
+    if (!grid || !cx_dtype_valid(dtype)) { ctx->err = std::string(who) + ": a grid of a CX_DTYPE_* sample type is needed"; return CX_ERR_INVALID; }
+    if (on_device) { *out = {grid, dtype}; return CX_OK; }
+    const size_t bytes = (size_t)(ctx->n0 * ctx->n1 * ctx->n2) * cx_dtype_size(dtype);
+    const int rc = cx_grow(ctx, ctx->attr_grid, ctx->attr_grid_cap, bytes);
+    if (rc) return rc;
+    CXA_HIP(ctx, hipMemcpyAsync(ctx->attr_grid, grid, bytes, hipMemcpyHostToDevice, ctx->stream));
+    CXA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the caller's array may go away when this returns
+    *out = {ctx->attr_grid, dtype};
+    return CX_OK;
+}
+
+// Level 0: the current extraction and its vertex count (one synchronisation the first time the counts are asked for)
+static int cxa_level0(cx_ctx* ctx, const char* who, uint32_t* nv) {
+    if (!ctx->extracted || !ctx->grid.p) { ctx->err = std::string(who) + ": no valid extraction"; return CX_ERR_INVALID; }
+    CXA_HIP(ctx, hipSetDevice(ctx->device));
+    cx_counts c;
+    const int rc = cx_counts_get(ctx, &c);
+    if (rc) return rc;
+    *nv = (uint32_t)c.n_vertices;
+    return CX_OK;
+}
+
+extern "C" int cx_level0_normals(cx_ctx* ctx, const double* delta3, void** normals_dev) {
+    if (!ctx) return CX_ERR_INVALID;
+    if (!cxa_delta_ok(delta3)) return cxa_fail(ctx, CX_ERR_INVALID, "cx_level0_normals: the spacing must be positive and finite");
+    uint32_t nv = 0;
+    int rc = cxa_level0(ctx, "cx_level0_normals", &nv);
+    if (rc) return rc;
+    if (normals_dev) *normals_dev = nullptr;
+    if (!nv) return CX_OK;
+    if (ctx->attr_n0_cap < nv && (rc = cx_grow(ctx, ctx->attr_n0, ctx->attr_n0_cap, (size_t)nv + nv / 16u + 64u))) return rc;
+    const cxa_dims D = cxa_dims_of(ctx);
+    const float d0 = delta3 ? (float)delta3[0] : 1.0f, d1 = delta3 ? (float)delta3[1] : 1.0f, d2 = delta3 ? (float)delta3[2] : 1.0f;
+    cxa_v4f* out = reinterpret_cast<cxa_v4f*>(ctx->attr_n0);
+#define CX_LAUNCH(DT)                                                                                                                          \
+    if (delta3) hipLaunchKernelGGL((cx_k_vertex_normals<DT, true>), cxa_grid(nv), dim3(256), 0, ctx->stream, ctx->grid, ctx->verts, out, nv, D, d0, d1, d2); \
+    else hipLaunchKernelGGL((cx_k_vertex_normals<DT, false>), cxa_grid(nv), dim3(256), 0, ctx->stream, ctx->grid, ctx->verts, out, nv, D, d0, d1, d2);
+    CX_DISPATCH_DTYPE(ctx->grid.dtype, CX_LAUNCH)
+#undef CX_LAUNCH
+    CXA_HIP(ctx, hipGetLastError());
+    if (normals_dev) *normals_dev = ctx->attr_n0;
+    return CX_OK;
+}
+
+extern "C" int cx_level0_normals_download(cx_ctx* ctx, const double* delta3, float* normals_xyzg) {
+    if (!ctx || !normals_xyzg) return CX_ERR_INVALID;
+    void* dev = nullptr;
+    const int rc = cx_level0_normals(ctx, delta3, &dev);
+    if (rc || !dev) return rc;
+    return cx_copy_to_host1(ctx, normals_xyzg, dev, (size_t)ctx->counts.n_vertices * sizeof(float4));
+}
+
+extern "C" int cx_level0_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtype, int on_device, void** values_dev, float* values_host) {
+    if (!ctx) return CX_ERR_INVALID;
+    uint32_t nv = 0;
+    int rc = cxa_level0(ctx, "cx_level0_sample_grid", &nv);
+    if (rc) return rc;
+    cx_grid_ref B;
+    if ((rc = cxa_second_grid(ctx, "cx_level0_sample_grid", grid, dtype, on_device, &B))) return rc;
+    if (values_dev) *values_dev = nullptr;
+    if (!nv) return CX_OK;
+    if (ctx->attr_v0_cap < nv && (rc = cx_grow(ctx, ctx->attr_v0, ctx->attr_v0_cap, (size_t)nv + nv / 16u + 64u))) return rc;
+    const uint32_t n2 = (uint32_t)ctx->n2, plane = (uint32_t)(ctx->n1 * ctx->n2), ns = (uint32_t)(ctx->n0 * ctx->n1 * ctx->n2);
+#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_vertex_sample<DT>), cxa_grid(nv), dim3(256), 0, ctx->stream, B, ctx->verts, ctx->attr_v0, nv, n2, plane, ns);
+    CX_DISPATCH_DTYPE(dtype, CX_LAUNCH)
+#undef CX_LAUNCH
+    CXA_HIP(ctx, hipGetLastError());
+    if (values_dev) *values_dev = ctx->attr_v0;
+    if (values_host) return cx_copy_to_host1(ctx, values_host, ctx->attr_v0, (size_t)nv * sizeof(float));
+    return CX_OK;
+}
+
+// Level 1: the view of the post-pass and the edge {a, b, ratio} of every output vertex in ctx->attr_e1
+static int cxa_level1(cx_ctx* ctx, const char* who, cx_level1_view* V) {
+    CXA_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = cx_level1_attr_view(ctx, who, V);
+    if (rc) return rc;
+    if (!ctx->extracted || !ctx->grid.p) { ctx->err = std::string(who) + ": no valid extraction"; return CX_ERR_INVALID; }
+    if (!V->nv) return CX_OK;
+    if (ctx->attr_e1_cap < (size_t)V->nv * sizeof(cxa_edge1) &&
+        (rc = cx_grow(ctx, ctx->attr_e1, ctx->attr_e1_cap, ((size_t)V->nv + V->nv / 16u + 64u) * sizeof(cxa_edge1)))) return rc;
+    const uint32_t n2 = (uint32_t)ctx->n2, plane = (uint32_t)(ctx->n1 * ctx->n2), ns = (uint32_t)(ctx->n0 * ctx->n1 * ctx->n2);
+    const double* A64 = ctx->grid64_valid ? ctx->grid64 : nullptr;
+    cxa_edge1* edges = reinterpret_cast<cxa_edge1*>(ctx->attr_e1);
+#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_edges<DT>), cxa_grid(V->nv), dim3(256), 0, ctx->stream, ctx->grid, A64, V->keys, V->nv, n2, plane, ns, ctx->last.value, edges);
+    CX_DISPATCH_DTYPE(ctx->grid.dtype, CX_LAUNCH)
+#undef CX_LAUNCH
+    CXA_HIP(ctx, hipGetLastError());
+    return CX_OK;
+}
+
+extern "C" int cx_level1_normals(cx_ctx* ctx, const double* delta3, void** normals_dev) {
+    if (!ctx) return CX_ERR_INVALID;
+    if (!cxa_delta_ok(delta3)) return cxa_fail(ctx, CX_ERR_INVALID, "cx_level1_normals: the spacing must be positive and finite");
+    cx_level1_view V;
+    int rc = cxa_level1(ctx, "cx_level1_normals", &V);
+    if (rc) return rc;
+    if (normals_dev) *normals_dev = nullptr;
+    if (!V.nv) return CX_OK;
+    if (ctx->attr_n1_cap < (size_t)V.nv * 3u && (rc = cx_grow(ctx, ctx->attr_n1, ctx->attr_n1_cap, ((size_t)V.nv + V.nv / 16u + 64u) * 3u))) return rc;
+    const cxa_dims D = cxa_dims_of(ctx);
+    const double* A64 = ctx->grid64_valid ? ctx->grid64 : nullptr;
+    const cxa_edge1* edges = reinterpret_cast<const cxa_edge1*>(ctx->attr_e1);
+    const double d0 = delta3 ? delta3[0] : 1.0, d1 = delta3 ? delta3[1] : 1.0, d2 = delta3 ? delta3[2] : 1.0;
+#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_normals<DT>), cxa_grid(V.nv), dim3(256), 0, ctx->stream, ctx->grid, A64, edges, V.vflip, V.nv, D, delta3 ? 1 : 0, d0, d1, d2, ctx->attr_n1);
+    CX_DISPATCH_DTYPE(ctx->grid.dtype, CX_LAUNCH)
+#undef CX_LAUNCH
+    CXA_HIP(ctx, hipGetLastError());
+    if (normals_dev) *normals_dev = ctx->attr_n1;
+    return CX_OK;
+}
+
+extern "C" int cx_level1_normals_download(cx_ctx* ctx, const double* delta3, double* normals_xyz) {
+    if (!ctx || !normals_xyz) return CX_ERR_INVALID;
+    void* dev = nullptr;
+    const int rc = cx_level1_normals(ctx, delta3, &dev);
+    if (rc || !dev) return rc;
+    cx_level1_view V;
+    const int rv = cx_level1_attr_view(ctx, "cx_level1_normals_download", &V);
+    if (rv) return rv;
+    return cx_copy_to_host1(ctx, normals_xyz, dev, (size_t)V.nv * 3u * sizeof(double));
+}
+
+extern "C" int cx_level1_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtype, int on_device, void** values_dev, double* values_host) {
+    if (!ctx) return CX_ERR_INVALID;
+    cx_level1_view V;
+    int rc = cxa_level1(ctx, "cx_level1_sample_grid", &V);
+    if (rc) return rc;
+    cx_grid_ref B;
+    if ((rc = cxa_second_grid(ctx, "cx_level1_sample_grid", grid, dtype, on_device, &B))) return rc;
+    if (values_dev) *values_dev = nullptr;
+    if (!V.nv) return CX_OK;
+    if (ctx->attr_v1_cap < V.nv && (rc = cx_grow(ctx, ctx->attr_v1, ctx->attr_v1_cap, (size_t)V.nv + V.nv / 16u + 64u))) return rc;
+    const cxa_edge1* edges = reinterpret_cast<const cxa_edge1*>(ctx->attr_e1);
+#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_sample<DT>), cxa_grid(V.nv), dim3(256), 0, ctx->stream, B, edges, V.nv, ctx->attr_v1);
+    CX_DISPATCH_DTYPE(dtype, CX_LAUNCH)
+#undef CX_LAUNCH
+    CXA_HIP(ctx, hipGetLastError());
+    if (values_dev) *values_dev = ctx->attr_v1;
+    if (values_host) return cx_copy_to_host1(ctx, values_host, ctx->attr_v1, (size_t)V.nv * sizeof(double));
+    return CX_OK;
+}

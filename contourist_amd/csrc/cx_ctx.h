@@ -99,6 +99,20 @@ struct cx_ctx {
     size_t seed_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int seed_mode = 0;      // how the last seeded selection (3-D or 4-D) ran its end points: 0 sequential (the reference's shared visited set), 1 one thread per pair
     bool keep_valid = false;
+    // vertex attributes (cx_attr.hip), kept between calls: Level-0 normals float4 {nx, ny, nz, |g|}, Level-1 normals double[3], sampled
+    // values (fp32 at Level 0, float64 at Level 1) and the device copy of a second grid handed over from the host
+    float4* attr_n0 = nullptr;
+    size_t attr_n0_cap = 0;
+    double* attr_n1 = nullptr;
+    size_t attr_n1_cap = 0;
+    float* attr_v0 = nullptr;
+    size_t attr_v0_cap = 0;
+    double* attr_v1 = nullptr;
+    size_t attr_v1_cap = 0;
+    uint8_t* attr_e1 = nullptr;        // Level 1: per output vertex {sample index of the low point, of the high point, ratio} (16 bytes)
+    size_t attr_e1_cap = 0;
+    uint8_t* attr_grid = nullptr;
+    size_t attr_grid_cap = 0;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -186,6 +200,17 @@ void cx_levels_invalidate(cx_ctx* ctx);
 void cx_post_free(cx_ctx* ctx);
 int cx_scan_u32(cx_ctx* ctx, const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* sums_tmp, uint32_t* total_dev,
                 unsigned long long* total64_dev = nullptr);   // total64: the total without the wrap at 2^32
+// what cx_attr.hip reads of the Level-1 state: the edge id of every output vertex and one byte per vertex, 1 = the orientation step
+// reversed the triangles of its component.  CX_ERR_INVALID without a post-pass, CX_ERR_UNSUPPORTED when the keys are not edge ids
+// of the resident array (cx_postprocess3d_mesh, cx_postprocess3d_shard_*).  `who` names the caller in the error text.
+struct cx_level1_view {
+    const uint32_t* keys;
+    const uint8_t* vflip;
+    uint32_t nv;
+};
+int cx_level1_attr_view(cx_ctx* ctx, const char* who, cx_level1_view* out);
+// cx_attr.hip
+void cx_attr_free(cx_ctx* ctx);
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);
 // cx_contour2d.hip

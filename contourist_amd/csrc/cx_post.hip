@@ -47,6 +47,12 @@ struct cx_post_state {
     cxp_dev keys_out, keys_tmp, told, cls, bnd;   // edge ids of the output vertices; sharded Level 1 (cx_postprocess3d_shard_*)
     cxp_dev ever;                                 // vertices something was ever merged into: u8[nv] before | u8[nv2] after the compaction
     bool keys_valid = false;
+    // vertex attributes (cx_attr.hip).  keys_edge: keys_out holds edge ids of the resident array (cx_postprocess3d*, not a caller's mesh
+    // and not a shard).  orient_live: S->parent / S->comp still hold the component roots and flips of the orientation step for the
+    // orient_nt triangles of tri_out; vflip: per output vertex, 1 = its component's triangles were reversed (filled on first request)
+    cxp_dev vflip;
+    bool keys_edge = false, orient_live = false, vflip_valid = false;
+    uint32_t orient_nt = 0;
     struct {
         bool open = false;            // between cx_postprocess3d_shard_begin and _finish
         uint32_t nv2 = 0, nt2 = 0;    // mesh of own + first-halo-layer triangles the labels refer to
@@ -83,7 +89,7 @@ void cx_post_free(cx_ctx* ctx) {
     cx_post_state* S = ctx->post;
     cxp_dev* all[] = {&S->pts, &S->prio, &S->rep, &S->tri, &S->alive, &S->parent, &S->parent2, &S->tkeys, &S->tvals,
                       &S->flags, &S->scan, &S->blocksums, &S->pts_out, &S->tri_out, &S->comp, &S->misc,
-                      &S->keys_out, &S->keys_tmp, &S->told, &S->cls, &S->bnd, &S->ever,
+                      &S->keys_out, &S->keys_tmp, &S->told, &S->cls, &S->bnd, &S->ever, &S->vflip,
                       &S->mpairs, &S->msegs, &S->mtris, &S->mmid, &S->mtime, &S->mnext, &S->msegs2, &S->mtris2, &S->mtime2,
                       &S->meflags, &S->metflag, &S->menew, &S->mecnt, &S->medesc, &S->me_pts, &S->me_tri};
     for (cxp_dev* d : all)
@@ -1227,6 +1233,7 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
     uint32_t* misc = (uint32_t*)S->misc.p;   // [0] changed flag, [1..] counters
     hipStream_t st = ctx->stream;
     S->keys_valid = false;
+    S->keys_edge = false; S->orient_live = false; S->vflip_valid = false;
     S->shard.open = false;
     if (do_clean && nt) {
         u64* parent2 = (u64*)S->parent2.p;
@@ -1395,6 +1402,7 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
         if (!shard) {
             hipLaunchKernelGGL(cxp_k_orient, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, nt2, parent, cbest, misc + 3);
             CXP_HIP(ctx, hipMemcpyAsync(&ncomp, misc + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            S->orient_live = true; S->orient_nt = nt2;
         }
         CXP_HIP(ctx, hipStreamSynchronize(st));
     } else if (shard) {
@@ -1726,6 +1734,7 @@ extern "C" int cx_postprocess3d_ex(cx_ctx* ctx, uint32_t flags, double smooth, i
         if (ctx->corner_ref[a] > 0) corner[a] = (double)ctx->corner_ref[a];
     if ((rc = cxp_run3d(ctx, S, nv, nt, corner, vkeep, !(flags & 1u), smooth, true, counts, true))) return rc;   // the march winds every triangle low -> high
     ctx->post_valid = true;
+    S->keys_edge = true;
     if (out_counts) memcpy(out_counts, counts, sizeof(counts));
     return CX_OK;
 }
@@ -1940,6 +1949,46 @@ extern "C" int cx_level1_device_ptrs(cx_ctx* ctx, void** points_xyz, void** tris
     return CX_OK;
 }
 
+// ---- what the vertex attributes (cx_attr.hip) need from the Level-1 state ------------------------------------------------------------
+// One byte per output vertex: the flip of the component its triangles belong to (cflip of the component's root, cxp_k_comp_decide).
+// Every triangle of a component stores the same value, so the result does not depend on the launch order for a vertex whose
+// triangles all lie in one component; plain byte stores, no atomics.
+__global__ void cxp_k_vertex_flip(const int32_t* __restrict__ tri, uint32_t nt, const u64* __restrict__ parent, const u64* __restrict__ cflip,
+                                  uint8_t* __restrict__ vflip) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nt) return;
+    const uint8_t f = (uint8_t)(cflip[(uint32_t)parent[t]] & 1u);
+    if (!f) return;                       // (the bytes start at zero)
+#pragma unroll
+    for (int k = 0; k < 3; k++) vflip[(uint32_t)tri[(size_t)t * 3 + k]] = 1;
+}
+int cx_level1_attr_view(cx_ctx* ctx, const char* who, cx_level1_view* out) {
+    if (!ctx->post || !ctx->post_valid || !ctx->post->keys_valid) { ctx->err = std::string(who) + ": no Level-1 mesh (run cx_postprocess3d first)"; return CX_ERR_INVALID; }
+    cx_post_state* S = ctx->post;
+    if (!S->keys_edge) {
+        ctx->err = std::string(who) + ": the Level-1 vertices are not edge crossings of the resident array (a mesh handed to cx_postprocess3d_mesh, or a shard)";
+        return CX_ERR_UNSUPPORTED;
+    }
+    const uint32_t nv = (uint32_t)S->nv_out, nt = (uint32_t)S->nt_out;
+    if (nv && !S->vflip_valid) {
+        if (nt && (!S->orient_live || S->orient_nt != nt)) { ctx->err = std::string(who) + ": the orientation tables of the post-pass are gone (run cx_postprocess3d again)"; return CX_ERR_STATE; }
+        int rc;
+        if ((rc = cxp_reserve(ctx, S->vflip, (size_t)nv + 16))) return rc;
+        CXP_HIP(ctx, hipMemsetAsync(S->vflip.p, 0, nv, ctx->stream));
+        if (nt) {
+            const u64* parent = (const u64*)S->parent.p;
+            const u64* cflip = (const u64*)S->comp.p + nt;    // (cbest of cxp_clean_orient)
+            hipLaunchKernelGGL(cxp_k_vertex_flip, dim3(cxp_blocks(nt)), dim3(256), 0, ctx->stream, (const int32_t*)S->tri_out.p, nt, parent, cflip, (uint8_t*)S->vflip.p);
+            CXP_HIP(ctx, hipGetLastError());
+        }
+        S->vflip_valid = true;
+    }
+    out->keys = (const uint32_t*)S->keys_out.p;
+    out->vflip = (const uint8_t*)S->vflip.p;
+    out->nv = nv;
+    return CX_OK;
+}
+
 // ---- binary mesh files straight from the Level-1 device buffers (what every caller of the reference does next,
 // html_demo.py:118-161, without the detour through Python arrays).  The file's records are laid out ON THE DEVICE, a chunk at a
 // time (world coordinates = grid * delta + mins, rounded as numpy rounds them: no fused multiply-add), and streamed through two
@@ -1959,6 +2008,26 @@ __global__ void cxw_k_points(const double* __restrict__ pts, uint32_t first, uin
         o[0] = x; o[1] = y; o[2] = z;
     }
 }
+// the same with the unit normal behind the position (CX_FILE_PLY_NORMALS: six doubles per vertex), and the normals alone as float32
+// (the second section of CX_FILE_GLTF_BIN_NORMALS)
+__global__ void cxw_k_points_normals(const double* __restrict__ pts, const double* __restrict__ nrm, uint32_t first, uint32_t n, double m0, double m1,
+                                     double m2, double d0, double d1, double d2, double* out) {
+#pragma clang fp contract(off)
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* p = pts + (size_t)(first + i) * 3;
+    const double* q = nrm + (size_t)(first + i) * 3;
+    double* o = out + (size_t)i * 6;
+    o[0] = p[0] * d0 + m0; o[1] = p[1] * d1 + m1; o[2] = p[2] * d2 + m2;
+    o[3] = q[0]; o[4] = q[1]; o[5] = q[2];
+}
+__global__ void cxw_k_normals_f32(const double* __restrict__ nrm, uint32_t first, uint32_t n, float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* q = nrm + (size_t)(first + i) * 3;
+    // (the rounded components of a float64 unit vector are 1 +- 1e-7 long)
+    out[(size_t)i * 3] = (float)q[0]; out[(size_t)i * 3 + 1] = (float)q[1]; out[(size_t)i * 3 + 2] = (float)q[2];
+}
 // PLY faces: uchar 3 + three little-endian int32 = 13 bytes per triangle
 __global__ void cxw_k_faces13(const int32_t* __restrict__ tri, uint32_t first, uint32_t n, uint8_t* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1972,16 +2041,26 @@ __global__ void cxw_k_faces13(const int32_t* __restrict__ tri, uint32_t first, u
 }
 #include <cstdio>
 extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const double* mins_delta, double* out_info) {
-    if (!ctx || !path || (format != CX_FILE_PLY && format != CX_FILE_GLTF_BIN)) return CX_ERR_INVALID;
+    if (!ctx || !path || (format != CX_FILE_PLY && format != CX_FILE_GLTF_BIN && format != CX_FILE_PLY_NORMALS && format != CX_FILE_GLTF_BIN_NORMALS)) return CX_ERR_INVALID;
     if (!ctx->post || !ctx->post_valid) { ctx->err = "cx_level1_write: run cx_postprocess3d first"; return CX_ERR_STATE; }
     CXP_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
+    // the formats with normals: the unit normals of cx_level1_normals (world normals when a spacing is handed over), laid out like the positions
+    const bool with_normals = format == CX_FILE_PLY_NORMALS || format == CX_FILE_GLTF_BIN_NORMALS;
+    const double* nrm = nullptr;
+    if (with_normals) {
+        void* nd = nullptr;
+        const int rcn = cx_level1_normals(ctx, mins_delta ? mins_delta + 3 : nullptr, &nd);
+        if (rcn) return rcn;
+        nrm = (const double*)nd;
+        format = format == CX_FILE_PLY_NORMALS ? CX_FILE_PLY : CX_FILE_GLTF_BIN;
+    }
     hipStream_t st = ctx->stream;
     const uint32_t nv = (uint32_t)S->nv_out, nt = (uint32_t)S->nt_out;
     double m[3] = {0, 0, 0}, d[3] = {1, 1, 1};
     if (mins_delta) for (int a = 0; a < 3; a++) { m[a] = mins_delta[a]; d[a] = mins_delta[3 + a]; }
     const uint32_t CHUNK = 1u << 20;                       // elements per chunk
-    const size_t stage_bytes = (size_t)CHUNK * 24u;         // the widest record: 3 doubles
+    const size_t stage_bytes = (size_t)CHUNK * (with_normals ? 48u : 24u);   // the widest record: 3 doubles (6 with normals)
     uint8_t* dstage = nullptr;
     uint8_t* hstage[2] = {nullptr, nullptr};
     FILE* f = fopen(path, "wb");
@@ -1999,16 +2078,21 @@ extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const 
             char header[512];
             const int hl = snprintf(header, sizeof(header),
                                     "ply\nformat binary_little_endian 1.0\ncomment contourist_amd isosurface\nelement vertex %u\n"
-                                    "property double x\nproperty double y\nproperty double z\n"
-                                    "element face %u\nproperty list uchar int vertex_indices\nend_header\n", nv, nt);
+                                    "property double x\nproperty double y\nproperty double z\n%s"
+                                    "element face %u\nproperty list uchar int vertex_indices\nend_header\n", nv,
+                                    with_normals ? "property double nx\nproperty double ny\nproperty double nz\n" : "", nt);
             if (fwrite(header, 1, (size_t)hl, f) != (size_t)hl) { rc = CX_ERR_INVALID; ctx->err = "cx_level1_write: write failed"; break; }
             written += (size_t)hl;
         }
         // section 0: points, section 1: faces / indices.  Chunk c of a section is prepared on the device into half c & 1 of
         // dstage and copied to hstage[c & 1]; the previous chunk is written to the file meanwhile.
-        for (int section = 0; section < 2 && rc == CX_OK; section++) {
-            const uint32_t count = section == 0 ? nv : nt;
-            const size_t rec = section == 0 ? (format == CX_FILE_PLY ? 24u : 12u) : (format == CX_FILE_PLY ? 13u : 12u);
+        // (glTF with normals: a section 2 of float32 normals between the two; PLY with normals: six doubles per vertex in section 0)
+        const int order3[3] = {0, 2, 1}, order2[3] = {0, 1, 1};
+        const bool three = with_normals && format != CX_FILE_PLY;
+        for (int si = 0; si < (three ? 3 : 2) && rc == CX_OK; si++) {
+            const int section = three ? order3[si] : order2[si];
+            const uint32_t count = section == 1 ? nt : nv;
+            const size_t rec = section == 0 ? (format == CX_FILE_PLY ? (with_normals ? 48u : 24u) : 12u) : (section == 2 ? 12u : (format == CX_FILE_PLY ? 13u : 12u));
             size_t pending_bytes = 0;
             int pending = -1;
             for (uint32_t first = 0, c = 0; rc == CX_OK; first += CHUNK, c++) {
@@ -2017,9 +2101,14 @@ extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const 
                 const int half = (int)(c & 1u);
                 if (more) {
                     uint8_t* dst = dstage + (size_t)half * stage_bytes;
-                    if (section == 0)
+                    if (section == 0 && with_normals && format == CX_FILE_PLY)
+                        hipLaunchKernelGGL(cxw_k_points_normals, dim3(cxp_blocks(n)), dim3(256), 0, st, (const double*)S->pts_out.p, nrm, first, n, m[0], m[1], m[2],
+                                           d[0], d[1], d[2], (double*)dst);
+                    else if (section == 0)
                         hipLaunchKernelGGL(cxw_k_points, dim3(cxp_blocks(n)), dim3(256), 0, st, (const double*)S->pts_out.p, first, n, m[0], m[1], m[2],
                                            d[0], d[1], d[2], format == CX_FILE_PLY ? 0 : 1, (void*)dst);
+                    else if (section == 2)
+                        hipLaunchKernelGGL(cxw_k_normals_f32, dim3(cxp_blocks(n)), dim3(256), 0, st, nrm, first, n, (float*)dst);
                     else if (format == CX_FILE_PLY)
                         hipLaunchKernelGGL(cxw_k_faces13, dim3(cxp_blocks(n)), dim3(256), 0, st, (const int32_t*)S->tri_out.p, first, n, dst);
                     const void* src = (section == 1 && format != CX_FILE_PLY) ? (const void*)((const int32_t*)S->tri_out.p + (size_t)first * 3) : (const void*)dst;
@@ -2040,8 +2129,9 @@ extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const 
                             for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], (double)q[3 * i + a]); hi[a] = std::max(hi[a], (double)q[3 * i + a]); }
                     } else {
                         const double* q = reinterpret_cast<const double*>(hstage[half]);
+                        const size_t stride = with_normals ? 6u : 3u;
                         for (uint32_t i = 0; i < n; i++)
-                            for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], q[3 * i + a]); hi[a] = std::max(hi[a], q[3 * i + a]); }
+                            for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], q[stride * i + a]); hi[a] = std::max(hi[a], q[stride * i + a]); }
                     }
                 }
                 pending = half;
@@ -2233,6 +2323,7 @@ static int cxp_post4_tets(cx_ctx* ctx, cx_post_state* S, const int32_t* tets, ui
     uint8_t* moved = (uint8_t*)S->rep.p;
     uint8_t* alive = (uint8_t*)S->alive.p;
     u64* parent = (u64*)S->parent.p;
+    S->orient_live = false;   // (the 3-D orientation's tables lived here)
     uint32_t* misc = (uint32_t*)S->misc.p;
     hipLaunchKernelGGL(cxp_k_drop_instant, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1e-7);
     // cx_select_seeded4d: only the tetrahedra of the selected components exist
@@ -2916,6 +3007,7 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             u64* ekeys = (u64*)S->tkeys.p;
             u64* eheads = (u64*)S->tvals.p;
             u64* parent = (u64*)S->parent.p;
+            S->orient_live = false;   // (the 3-D orientation's tables lived here)
             uint32_t* next = (uint32_t*)S->mnext.p;
             u64* cmaxx = (u64*)S->comp.p;
             u64* cbest = cmaxx + ntri;
@@ -3162,6 +3254,7 @@ static int cxp_morph_sort_by_start(cx_ctx* ctx, cx_post_state* S, uint32_t nseg,
     if ((rc = cxp_reserve(ctx, S->mtime2, ((size_t)(nseg + 1) * 2 + (size_t)(ntri + 1) * 2) * sizeof(double)))) return rc;
     if ((rc = cxp_reserve(ctx, S->parent, ((size_t)nseg + ntri + 64) * sizeof(uint32_t)))) return rc;
     uint32_t* rank_s = (uint32_t*)S->parent.p;
+    S->orient_live = false;   // (the 3-D orientation's tables lived here)
     uint32_t* rank_t = rank_s + nseg + 16;
     const int32_t* segs = (const int32_t*)S->msegs.p;
     const int32_t* tris = (const int32_t*)S->mtris.p;

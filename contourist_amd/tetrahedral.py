@@ -255,10 +255,45 @@ class GridContour3d(object):
             self._post = ctx.postprocess3d(0 if clean else 1, self.smooth or 0.0) if self.linear_interpolate else self._postprocess_refined(ctx, clean)
         return ctx
 
+    # -- vertex attributes: normals from the field's gradient, a second grid sampled at the vertices -------------
+    def _attr_checks(self):
+        if not self.linear_interpolate:
+            raise NotImplementedError("vertex normals and sampled values need linear_interpolate=True: refined points are not "
+                                      "crossings {edge, fraction} of the resident sample array")
+        if self._in_slabs():
+            raise NotImplementedError("vertex normals and sampled values of a volume marched in slabs are not available: the "
+                                      "assembled mesh's vertices are not edge crossings of one resident array")
+
+    def level0_normals(self, device=False):
+        "(V,4) float32 {nx, ny, nz, |g|} next to level0(): the unit gradient direction and the gradient's length per vertex record"
+        counts = self.march()
+        return self.context().level0_normals(counts, None, device)
+
+    def level0_values(self, field, device=False):
+        "(V,) float32: `field` (array or device tensor of the grid's shape, marched in its own type) at the vertices of level0()"
+        counts = self.march()
+        return self.context().level0_sample(counts, field, device)
+
+    def vertex_normals(self, clean=True, device=False, delta=None):
+        """(V,3) float64 unit normals in grid coordinates; row i belongs to row i of get_points_and_triangles()[0] and agrees with
+        the winding of its triangles.  delta: world spacing per axis (the world normal is g / delta, normalised)."""
+        self._attr_checks()
+        ctx = self._ensure_post(clean)
+        return ctx.level1_normals(self._post, delta, device)
+
+    def vertex_values(self, field, clean=True, device=False):
+        "(V,) float64: `field` (array or device tensor of the grid's shape, any supported dtype) at the vertices of get_points_and_triangles()"
+        self._attr_checks()
+        ctx = self._ensure_post(clean)
+        return ctx.level1_sample(self._post, field, device)
+
     def write_mesh(self, path, fmt="ply", mins=None, delta=None, clean=True):
         """the welded, cleaned, oriented mesh as a binary file written STRAIGHT FROM THE DEVICE BUFFERS (cx_level1_write: no
         (points, triangles) arrays on the host) -- the step every caller of the reference takes next (html_demo.py:118-161).
-        fmt "ply" | "gltf_bin"; mins / delta: world = grid * delta + mins.  Faces in device order (the Python API sorts rows)."""
+        fmt "ply" | "gltf_bin" | "ply_normals" | "gltf_bin_normals"; mins / delta: world = grid * delta + mins.  Faces in device order
+        (the Python API sorts rows)."""
+        if fmt.endswith("_normals"):
+            self._attr_checks()
         ctx = self._ensure_post(clean)
         return ctx.write_level1(path, fmt, mins, delta)
 
@@ -504,10 +539,31 @@ class Delta3DContour(object):
 
     def write_mesh(self, path, fmt="ply"):
         "binary mesh file in WORLD coordinates straight from the device buffers (GridContour3d.write_mesh)"
-        if fmt == "gltf":
+        if fmt in ("gltf", "gltf_normals"):
             from . import mesh_io
-            return mesh_io.write_gltf_device(self, path)
+            return mesh_io.write_gltf_device(self, path, normals=fmt == "gltf_normals")
         return self.contour_maker.write_mesh(path, fmt, self.grid.mins, self.grid.delta)
+
+    def vertex_normals(self, clean=True, device=False):
+        """(V,3) float64 unit normals in WORLD coordinates (the gradient per axis divided by delta, normalised); row i belongs
+        to row i of get_points_and_triangles()[0]"""
+        return self.contour_maker.vertex_normals(clean, device, delta=self.grid.delta)
+
+    def vertex_values(self, field, clean=True, device=False):
+        """(V,) float64: a second field at the vertices.  `field`: an array or device tensor of the grid's shape
+        (grid_dimensions + 1), or -- for a grid made from a callable -- a callable g(x, y, z) in world coordinates, sampled
+        by the host on the same lattice as the function (its rim included)."""
+        maker = self.contour_maker
+        m = int(getattr(self, "_grid_shift", 0))
+        if callable(field):
+            if getattr(self.grid, "array_backed", False):
+                raise ValueError("a callable field needs a grid made from a callable")
+            second = grid_field.FunctionGrid(self.grid.mins, self.grid.maxes, self.grid.delta, field)
+            field = second.dense_samples(margin=m) if m else second.dense_samples()
+        elif m:
+            raise NotImplementedError("the sample array carries a rim of %d lattice steps around the grid: hand the second field "
+                                      "over as a callable" % m)
+        return maker.vertex_values(field, clean, device)
 
     def search_for_endpoints(self, skip=1):
         """Reference: crossing search over every skip-th lattice point + new contour maker (tetrahedral.py:74-81,
@@ -617,6 +673,29 @@ class TriangulatedIsosurfaces(Delta3DContour):
         Delta3DContour.__init__(self, grid, value, segment_endpoints, linear_interpolate=linear_interpolate)
 
 
+class LevelResult(tuple):
+    """(value, points, triangles) of one level of MultiLevelIsosurfaces.levels(), with the vertex attributes of that level:
+    vertex_normals() / vertex_values(field).  They read the level's mesh on the device, so they work until the
+    generator moves on to the next level."""
+
+    def _bind(self, owner, index, post, delta):
+        self._owner, self._index, self._post, self._delta = owner, index, post, delta
+        return self
+
+    def _ctx(self):
+        if self._owner._current != self._index:
+            raise RuntimeError("level %d is no longer the current level of the context: ask for its attributes before advancing levels()" % self._index)
+        return self._owner._ctx
+
+    def vertex_normals(self, device=False):
+        "(V,3) float64 unit normals in world coordinates, row i for points[i]"
+        return self._ctx().level1_normals(self._post, self._delta, device)
+
+    def vertex_values(self, field, device=False):
+        "(V,) float64: a second grid of the samples' shape at the vertices"
+        return self._ctx().level1_sample(self._post, field, device)
+
+
 class MultiLevelIsosurfaces(object):
     """Several isovalues of ONE field (BASELINE.json config 5; the reference has this only in 2-D,
     contourist/multiple_2d_contour.py:17-75).  The dense samples are bound to the device once and ALL levels are
@@ -634,6 +713,7 @@ class MultiLevelIsosurfaces(object):
         self.flags = {"cpython310": _ffi.CX_DIAG_CPYTHON310, "canonical": _ffi.CX_DIAG_CANONICAL}[diagonal]
         self._ctx = _ffi.Context(self.device)
         self.counts = None
+        self._current = None
 
     def levels(self, clean=True):
         samples = self.grid.dense_samples()
@@ -641,10 +721,13 @@ class MultiLevelIsosurfaces(object):
         shape = tuple(int(n) for n in samples.shape)
         ctx = self._ctx
         if shape[2] < 4:          # rows shorter than 4 samples take the shape-agnostic kernel: one level at a time
-            for v in self.values:
+            for n, v in enumerate(self.values):
                 maker = GridContour3d(corner, samples, v, None, context=ctx)
                 grid_points, triangles = maker.get_points_and_triangles(clean)
-                yield (v, self.grid.from_grid_coordinates(grid_points) if len(grid_points) else np.zeros((0, 3)), triangles)
+                self._current = n
+                yield LevelResult((v, self.grid.from_grid_coordinates(grid_points) if len(grid_points) else np.zeros((0, 3)),
+                                   triangles))._bind(self, n, maker._post, self.grid.delta)
+            self._current = None
             return
         if grid_field._is_torch(samples):
             assert samples.is_cuda and samples.is_contiguous() and _ffi.native_dtype(samples.dtype), \
@@ -661,7 +744,9 @@ class MultiLevelIsosurfaces(object):
             grid_points, triangles = ctx.download_level1(post)
             geometry = surface_geometry.SurfaceGeometry._from_device(grid_points, triangles, ctx)   # sorted rows, as the reference returns them
             points = self.grid.from_grid_coordinates(geometry.vertices) if len(grid_points) else np.zeros((0, 3))
-            yield (v, points, geometry.oriented_triangles)
+            self._current = n
+            yield LevelResult((v, points, geometry.oriented_triangles))._bind(self, n, post, self.grid.delta)
+        self._current = None
 
 
 def rim_crossing_segments(S, gd, v, shell=2):

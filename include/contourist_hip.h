@@ -283,7 +283,41 @@ int cx_postprocess3d_shard_finish(cx_ctx* ctx, const uint32_t* labels, const uin
  * positions as written (glTF accessor bounds; PLY: not computed).  Face order is the device's (the Python API sorts the rows). */
 #define CX_FILE_PLY 0
 #define CX_FILE_GLTF_BIN 1
+/* the same with the unit normals of cx_level1_normals (world normals, delta = mins_delta[3..5], when mins_delta is given):
+ * CX_FILE_PLY_NORMALS: double nx ny nz after x y z in every vertex record (contourist_amd.mesh_io.write_ply with normals, byte for
+ * byte); CX_FILE_GLTF_BIN_NORMALS: float32 positions, float32 normals, uint32 indices.  out_info as for the other two. */
+#define CX_FILE_PLY_NORMALS 2
+#define CX_FILE_GLTF_BIN_NORMALS 3
 int cx_level1_write(cx_ctx* ctx, int format, const char* path, const double* mins_delta, double* out_info);
+
+/* ---- vertex attributes: normals from the field's gradient, and a second grid sampled at the vertices -------------------------------
+ * What every consumer of the reference computes right after get_points_and_triangles (html_demo.py:91-92 asks three.js for
+ * computeFaceNormals / computeVertexNormals).  A vertex is a crossing of the lattice edge a -> b at fraction r; the resident sample
+ * array gives the gradient G at both ends by the rule of numpy.gradient with its defaults (central difference inside, the one-sided
+ * first difference on the rim of the marched array, unit spacing), and
+ *     g = G(a) + r * (G(b) - G(a));   g_axis /= delta3[axis] when delta3 != NULL (world spacing);   n = s * g / |g|, (0,0,0) when |g| == 0.
+ * Level 0: a = the owning lattice point q, b = q + d, r = the fp32 fraction of the vertex record, fp32 arithmetic, s = +1 (the march
+ * winds its triangles from f < value to f >= value: the gradient's side).  One float4 {nx, ny, nz, |g|} per vertex record, |g| the
+ * length before normalisation.
+ * Level 1: the vertices of cx_level1_download in its order, identified by cx_level1_download_keys; a, b, r = the low point, the high
+ * point and the ratio of the float64 interpolation (on the float64 originals of cx_grid_shadow_f64 when bound; ratio 0.5 where the
+ * two samples are within 1e-8), float64 throughout, three doubles per vertex.  s = -1 for the vertices of a component whose
+ * triangles the orientation step reversed, +1 otherwise: a Level-1 normal agrees with the winding of its triangles.
+ * A second grid B of the marched array's shape, of any CX_DTYPE_*, is sampled at the same places: B(a) + r * (B(b) - B(a)), fp32 at
+ * Level 0, float64 at Level 1.  grid: host pointer (copied into a buffer of the context), or device pointer when on_device != 0.
+ * values_dev / values_host: either may be NULL.
+ * The kernels are enqueued on the context's stream; the device buffers belong to the context, are reused between calls and are valid
+ * until the next call of the same function, extraction or post-pass.  CX_ERR_INVALID without an extraction (Level 0) or a post-pass
+ * (Level 1).  CX_ERR_UNSUPPORTED where the Level-1 vertices are not edge crossings of the resident array: after
+ * cx_postprocess3d_mesh (refined points, volumes assembled from slabs or ranks) and after cx_postprocess3d_shard_finish (the flips
+ * come from other ranks and the rim planes belong to neighbours).  After cx_levels_select they act on the selected level; after a
+ * seeded selection Level 0 covers every vertex record and Level 1 what the selection kept. */
+int cx_level0_normals(cx_ctx* ctx, const double* delta3, void** normals_dev);
+int cx_level0_normals_download(cx_ctx* ctx, const double* delta3, float* normals_xyzg);
+int cx_level1_normals(cx_ctx* ctx, const double* delta3, void** normals_dev);
+int cx_level1_normals_download(cx_ctx* ctx, const double* delta3, double* normals_xyz);
+int cx_level0_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtype, int on_device, void** values_dev, float* values_host);
+int cx_level1_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtype, int on_device, void** values_dev, double* values_host);
 
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
