@@ -15,6 +15,7 @@ if os.environ.get("CX_DEBUG") == "1" and os.environ.get("CX_LIB_PATH"):   # A/B 
 
 CX_OK = 0
 CX_ERR_INVALID = -1
+CX_ERR_STATE = -4
 CX_ERR_CAPACITY = -5
 CX_ERR_UNSUPPORTED = -6
 CX_DIAG_CANONICAL = 0
@@ -24,6 +25,20 @@ CX_KERNEL_STAGED = 0x200
 CX_KERNEL_FUSED = 0x400
 CX_KERNEL_TILED = 0x800
 
+
+class cx_component(ctypes.Structure):
+    "one record of cx_level1_components (include/contourist_hip.h): 128 bytes"
+    _fields_ = [("triangles", ctypes.c_int64), ("vertices", ctypes.c_int64), ("area", ctypes.c_double), ("volume", ctypes.c_double),
+                ("centroid", ctypes.c_double * 3), ("bbox_lo", ctypes.c_double * 3), ("bbox_hi", ctypes.c_double * 3),
+                ("flipped", ctypes.c_int32), ("closed", ctypes.c_int32), ("first_triangle", ctypes.c_int64),
+                ("reserved", ctypes.c_double * 1)]
+
+
+# the same record as a numpy structured type (what Context.level1_components returns)
+COMPONENT_DTYPE = np.dtype([("triangles", "<i8"), ("vertices", "<i8"), ("area", "<f8"), ("volume", "<f8"), ("centroid", "<f8", (3,)),
+                            ("bbox_lo", "<f8", (3,)), ("bbox_hi", "<f8", (3,)), ("flipped", "<i4"), ("closed", "<i4"),
+                            ("first_triangle", "<i8"), ("reserved", "<f8", (1,))])
+
 # every symbol include/contourist_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "cx_ctx_create", "cx_ctx_destroy", "cx_last_error", "cx_set_stream", "cx_synchronize",
@@ -31,6 +46,7 @@ SYMBOLS = [
     "cx_extract3d", "cx_extract3d_async", "cx_counts_get", "cx_extract3d_levels", "cx_levels_select", "cx_level0_path", "cx_level0_download", "cx_level0_device_ptrs", "cx_level0_device_records", "cx_level0_download_records",
     "cx_postprocess3d", "cx_postprocess3d_ex", "cx_level0_points_f64", "cx_postprocess3d_mesh", "cx_select_seeded3d", "cx_select_seeded3d_ex", "cx_seeded_masks_download", "cx_set_reference_corner", "cx_level1_download", "cx_level1_device_ptrs", "cx_level1_download_keys", "cx_postprocess3d_shard_begin", "cx_postprocess3d_shard_boundary", "cx_postprocess3d_shard_candidates", "cx_postprocess3d_shard_finish", "cx_level1_write", "cx_surface_geometry",
     "cx_level0_normals", "cx_level0_normals_download", "cx_level1_normals", "cx_level1_normals_download", "cx_level0_sample_grid", "cx_level1_sample_grid",
+    "cx_level1_components", "cx_level1_components_download", "cx_level1_component_labels", "cx_level1_component_labels_download", "cx_level1_keep_components",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -181,6 +197,11 @@ def load():
         "cx_level1_normals_download": [vp, vp, vp],
         "cx_level0_sample_grid": [vp, vp, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(vp), vp],
         "cx_level1_sample_grid": [vp, vp, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(vp), vp],
+        "cx_level1_components": [vp, vp, ctypes.POINTER(i64), ctypes.POINTER(vp), vp],
+        "cx_level1_components_download": [vp, vp, vp],
+        "cx_level1_component_labels": [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)],
+        "cx_level1_component_labels_download": [vp, vp, vp],
+        "cx_level1_keep_components": [vp, vp, vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -610,6 +631,52 @@ class Context(object):
         self._check_attr(self.lib.cx_level1_sample_grid(self.handle, ctypes.c_void_p(ptr), code, on_dev, ctypes.byref(p), out.ctypes.data))
         del keep
         return out
+
+    # ---- components of the Level-1 mesh (cx_comp.hip): labels, per-component measures, filtering ------------------------------
+    @staticmethod
+    def _mins_delta(mins, delta):
+        if mins is None and delta is None:
+            return None
+        return np.ascontiguousarray(np.concatenate([np.asarray(mins if mins is not None else [0, 0, 0], dtype=np.float64).reshape(3),
+                                                    np.asarray(delta if delta is not None else [1, 1, 1], dtype=np.float64).reshape(3)]))
+
+    def level1_components(self, mins=None, delta=None, info=False):
+        """the components of the Level-1 mesh as a numpy structured array (COMPONENT_DTYPE: triangles, vertices, area, volume,
+        centroid, bbox_lo, bbox_hi, flipped, closed, first_triangle), in world coordinates grid * delta + mins when either is given.
+        info=True: (table, origin (3,), q): the point the volumes are taken about and the exponent of the sums' grid 2^-q"""
+        md = self._mins_delta(mins, delta)
+        mp = None if md is None else md.ctypes.data
+        nc, oq = ctypes.c_int64(0), np.zeros(4, dtype=np.float64)
+        self._check_attr(self.lib.cx_level1_components(self.handle, mp, ctypes.byref(nc), None, oq.ctypes.data))
+        table = np.zeros(int(nc.value), dtype=COMPONENT_DTYPE)
+        if len(table):
+            self._check_attr(self.lib.cx_level1_components_download(self.handle, mp, table.ctypes.data))
+        return (table, oq[:3].copy(), int(oq[3])) if info else table
+
+    def level1_component_labels(self, device=False):
+        """(triangle labels int32 (T,), vertex labels int32 (V,)) of the Level-1 mesh in device order (a vertex: the smallest id
+        among its triangles' components, -1 when unused); device=True: torch tensors on the GPU"""
+        _pp, _tp, nv, nt = self.level1_device_ptrs()
+        if device:
+            import torch
+            tp, vp = ctypes.c_void_p(), ctypes.c_void_p()
+            self._check_attr(self.lib.cx_level1_component_labels(self.handle, ctypes.byref(tp), ctypes.byref(vp)))
+            return (self._device_view(tp.value or 0, (nt,), "<i4", torch.int32), self._device_view(vp.value or 0, (nv,), "<i4", torch.int32))
+        tl, vl = np.zeros(nt, dtype=np.int32), np.zeros(nv, dtype=np.int32)
+        self._check_attr(self.lib.cx_level1_component_labels_download(self.handle, tl.ctypes.data, vl.ctypes.data))
+        return tl, vl
+
+    def level1_keep_components(self, mask):
+        """drop the components whose entry of `mask` (one per component) is false; every reader of the Level-1 mesh serves the
+        filtered mesh afterwards -> dict(n_vertices, n_triangles, n_components)"""
+        keep = np.ascontiguousarray(np.asarray(mask).astype(bool), dtype=np.uint8).reshape(-1)
+        nc = ctypes.c_int64(0)
+        self._check_attr(self.lib.cx_level1_components(self.handle, None, ctypes.byref(nc), None, None))
+        if len(keep) != int(nc.value):
+            raise ValueError("the mask has %d entries, the mesh has %d components" % (len(keep), int(nc.value)))
+        out = np.zeros(8, dtype=np.int64)
+        self._check_attr(self.lib.cx_level1_keep_components(self.handle, keep.ctypes.data if len(keep) else None, out.ctypes.data))
+        return dict(n_vertices=int(out[0]), n_triangles=int(out[1]), n_components=int(out[4]))
 
     def surface_geometry(self, points, triangles, do_clean):
         pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3).copy()

@@ -113,6 +113,8 @@ struct cx_ctx {
     size_t attr_e1_cap = 0;
     uint8_t* attr_grid = nullptr;
     size_t attr_grid_cap = 0;
+    // components of the Level-1 mesh (cx_comp.hip): labels, accumulators and the table, kept between calls
+    struct cx_comp_state* comp = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -209,8 +211,34 @@ struct cx_level1_view {
     uint32_t nv;
 };
 int cx_level1_attr_view(cx_ctx* ctx, const char* who, cx_level1_view* out);
+// what cx_comp.hip reads of the Level-1 state: the tables of the orientation step (parent word = (parity << 32) | root triangle, the
+// root's flip in cflip[root]), the output mesh, the grid box of the post-pass and the generation of the mesh.  CX_ERR_INVALID without a
+// post-pass, CX_ERR_UNSUPPORTED for a shard, CX_ERR_STATE when the tables are gone.  The scratch buffers take a filtered copy of the
+// mesh (room for the whole of it); cx_level1_comp_commit makes that copy the Level-1 mesh.
+struct cx_level1_comp_view {
+    const unsigned long long* parent;
+    const unsigned long long* cflip;
+    const int32_t* tri;
+    const double* pts;
+    const uint32_t* keys;
+    uint32_t nv, nt;
+    double corner[3];
+    uint64_t gen;
+};
+struct cx_level1_comp_scratch {
+    double* pts;
+    int32_t* tri;
+    uint32_t* keys;
+    unsigned long long* parent;
+    unsigned long long* cflip;
+};
+int cx_level1_comp_view_get(cx_ctx* ctx, const char* who, cx_level1_comp_view* out);
+int cx_level1_comp_scratch_get(cx_ctx* ctx, cx_level1_comp_scratch* out);
+int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new);
 // cx_attr.hip
 void cx_attr_free(cx_ctx* ctx);
+// cx_comp.hip
+void cx_comp_free(cx_ctx* ctx);
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);
 // cx_contour2d.hip

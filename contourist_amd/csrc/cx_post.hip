@@ -53,6 +53,12 @@ struct cx_post_state {
     cxp_dev vflip;
     bool keys_edge = false, orient_live = false, vflip_valid = false;
     uint32_t orient_nt = 0;
+    // components (cx_comp.hip).  shard_mesh: the mesh came out of cx_postprocess3d_shard_finish (its components reach other ranks);
+    // corner: the grid box the 3-D post-pass worked in; gen: counts the meshes this state has held (every post-pass and every
+    // cx_level1_keep_components make a new one): what cx_comp.hip caches belongs to one value of it
+    bool shard_mesh = false;
+    double corner[3] = {1.0, 1.0, 1.0};
+    uint64_t gen = 0;
     struct {
         bool open = false;            // between cx_postprocess3d_shard_begin and _finish
         uint32_t nv2 = 0, nt2 = 0;    // mesh of own + first-halo-layer triangles the labels refer to
@@ -1234,6 +1240,7 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
     hipStream_t st = ctx->stream;
     S->keys_valid = false;
     S->keys_edge = false; S->orient_live = false; S->vflip_valid = false;
+    S->shard_mesh = false; S->gen++; S->orient_nt = 0;
     S->shard.open = false;
     if (do_clean && nt) {
         u64* parent2 = (u64*)S->parent2.p;
@@ -1478,6 +1485,7 @@ static int cxp_shard_finish(cx_ctx* ctx, cx_post_state* S, const uint32_t* label
     }
     S->nv_out = nv3; S->nt_out = nt3;
     S->keys_valid = true;
+    S->shard_mesh = true; S->gen++;
     CXP_HIP(ctx, hipGetLastError());
     if (out_counts) { out_counts[0] = nv3; out_counts[1] = nt3; out_counts[4] = ncomp; }
     return CX_OK;
@@ -1622,6 +1630,7 @@ static int cxp_run3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, co
     uint8_t* alive = (uint8_t*)S->alive.p;
     uint32_t* misc = (uint32_t*)S->misc.p;
     uint8_t* ever = nullptr;      // the march's own crossings: which vertices weld or clean-up merge something into
+    for (int a = 0; a < 3; a++) S->corner[a] = corner[a];
     // (march_mesh: a mesh the march emitted, handed back by the caller -- slabs assembled on the host, refined points --: an edge lies on
     // at most two triangles until something is merged into one of its ends, which is all the block linking needs; the weld shortcut needs
     // the crossings' own geometry and stays with edge_crossings)
@@ -1989,6 +1998,72 @@ int cx_level1_attr_view(cx_ctx* ctx, const char* who, cx_level1_view* out) {
     return CX_OK;
 }
 
+// ---- what the components (cx_comp.hip) need from the Level-1 state --------------------------------------------------------------------
+// The tables of the orientation step as they stand after cxp_k_orient: parent[t] = (parity << 32) | root, flattened, the root being the
+// smallest triangle index of the component (every union keeps the smaller root); cflip[root] = the root's flip.  Nothing here needs
+// edge ids, so the meshes of cx_postprocess3d_mesh are served too; a shard's components reach other ranks: CX_ERR_UNSUPPORTED.
+int cx_level1_comp_view_get(cx_ctx* ctx, const char* who, cx_level1_comp_view* out) {
+    if (!ctx->post || !ctx->post_valid || !ctx->post->keys_valid) { ctx->err = std::string(who) + ": no Level-1 mesh (run cx_postprocess3d first)"; return CX_ERR_INVALID; }
+    cx_post_state* S = ctx->post;
+    if (S->shard_mesh || S->shard.open) {
+        ctx->err = std::string(who) + ": the components of a sharded Level-1 mesh reach other ranks (cx_postprocess3d_shard_*): not available";
+        return CX_ERR_UNSUPPORTED;
+    }
+    const uint32_t nv = (uint32_t)S->nv_out, nt = (uint32_t)S->nt_out;
+    if ((nt && (!S->orient_live || S->orient_nt != nt)) || (!nt && S->orient_nt && !S->orient_live)) {
+        ctx->err = std::string(who) + ": the orientation tables of the post-pass are gone (a 4-D pass used their memory, or the post-pass ran without the orientation step): run cx_postprocess3d again";
+        return CX_ERR_STATE;
+    }
+    out->parent = (const u64*)S->parent.p;
+    out->cflip = nt ? (const u64*)S->comp.p + nt : nullptr;    // (cbest of cxp_clean_orient)
+    out->tri = (const int32_t*)S->tri_out.p;
+    out->pts = (const double*)S->pts_out.p;
+    out->keys = (const uint32_t*)S->keys_out.p;
+    out->nv = nv; out->nt = nt;
+    for (int a = 0; a < 3; a++) out->corner[a] = S->corner[a];
+    out->gen = S->gen;
+    return CX_OK;
+}
+// room for a filtered copy of the mesh and its tables in buffers the post-pass is done with (the march's points and triangles, the key
+// scratch, the edge table), as cxp_shard_finish uses them: nothing is allocated once they have their size
+int cx_level1_comp_scratch_get(cx_ctx* ctx, cx_level1_comp_scratch* out) {
+    cx_post_state* S = ctx->post;
+    const size_t nv = (size_t)S->nv_out, nt = (size_t)S->nt_out;
+    int rc;
+    if ((rc = cxp_reserve(ctx, S->pts, (nv + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = cxp_reserve(ctx, S->tri, (nt + 1) * 3 * sizeof(int32_t)))) return rc;
+    if ((rc = cxp_reserve(ctx, S->keys_tmp, (nv + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = cxp_reserve(ctx, S->tkeys, (nt + 1) * 2 * sizeof(u64)))) return rc;
+    out->pts = (double*)S->pts.p;
+    out->tri = (int32_t*)S->tri.p;
+    out->keys = (uint32_t*)S->keys_tmp.p;
+    out->parent = (u64*)S->tkeys.p;
+    out->cflip = out->parent + nt + 1;
+    return CX_OK;
+}
+// the filtered copy becomes the Level-1 mesh: every reader of the state (download, device pointers, keys, files, normals) serves it
+int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new) {
+    cx_post_state* S = ctx->post;
+    hipStream_t st = ctx->stream;
+    const size_t nt_old = (size_t)S->nt_out;
+    const u64* parent_new = (const u64*)S->tkeys.p;
+    if (nv_new) {
+        CXP_HIP(ctx, hipMemcpyAsync(S->pts_out.p, S->pts.p, (size_t)nv_new * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        CXP_HIP(ctx, hipMemcpyAsync(S->keys_out.p, S->keys_tmp.p, (size_t)nv_new * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    }
+    if (nt_new) {
+        CXP_HIP(ctx, hipMemcpyAsync(S->tri_out.p, S->tri.p, (size_t)nt_new * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        CXP_HIP(ctx, hipMemcpyAsync(S->parent.p, parent_new, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
+        CXP_HIP(ctx, hipMemcpyAsync((u64*)S->comp.p + nt_new, parent_new + nt_old + 1, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
+    }
+    CXP_HIP(ctx, hipStreamSynchronize(st));
+    S->nv_out = nv_new; S->nt_out = nt_new;
+    S->orient_nt = nt_new;
+    S->vflip_valid = false;      // (written again from the tables on the next request)
+    S->gen++;
+    return CX_OK;
+}
+
 // ---- binary mesh files straight from the Level-1 device buffers (what every caller of the reference does next,
 // html_demo.py:118-161, without the detour through Python arrays).  The file's records are laid out ON THE DEVICE, a chunk at a
 // time (world coordinates = grid * delta + mins, rounded as numpy rounds them: no fused multiply-add), and streamed through two
@@ -2323,7 +2398,7 @@ static int cxp_post4_tets(cx_ctx* ctx, cx_post_state* S, const int32_t* tets, ui
     uint8_t* moved = (uint8_t*)S->rep.p;
     uint8_t* alive = (uint8_t*)S->alive.p;
     u64* parent = (u64*)S->parent.p;
-    S->orient_live = false;   // (the 3-D orientation's tables lived here)
+    S->orient_live = false; S->gen++;   // (the 3-D orientation's tables lived here: what cx_comp.hip cached of them is stale)
     uint32_t* misc = (uint32_t*)S->misc.p;
     hipLaunchKernelGGL(cxp_k_drop_instant, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1e-7);
     // cx_select_seeded4d: only the tetrahedra of the selected components exist
@@ -3007,7 +3082,7 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             u64* ekeys = (u64*)S->tkeys.p;
             u64* eheads = (u64*)S->tvals.p;
             u64* parent = (u64*)S->parent.p;
-            S->orient_live = false;   // (the 3-D orientation's tables lived here)
+            S->orient_live = false; S->gen++;   // (the 3-D orientation's tables lived here: what cx_comp.hip cached of them is stale)
             uint32_t* next = (uint32_t*)S->mnext.p;
             u64* cmaxx = (u64*)S->comp.p;
             u64* cbest = cmaxx + ntri;
@@ -3254,7 +3329,7 @@ static int cxp_morph_sort_by_start(cx_ctx* ctx, cx_post_state* S, uint32_t nseg,
     if ((rc = cxp_reserve(ctx, S->mtime2, ((size_t)(nseg + 1) * 2 + (size_t)(ntri + 1) * 2) * sizeof(double)))) return rc;
     if ((rc = cxp_reserve(ctx, S->parent, ((size_t)nseg + ntri + 64) * sizeof(uint32_t)))) return rc;
     uint32_t* rank_s = (uint32_t*)S->parent.p;
-    S->orient_live = false;   // (the 3-D orientation's tables lived here)
+    S->orient_live = false; S->gen++;   // (the 3-D orientation's tables lived here: what cx_comp.hip cached of them is stale)
     uint32_t* rank_t = rank_s + nseg + 16;
     const int32_t* segs = (const int32_t*)S->msegs.p;
     const int32_t* tris = (const int32_t*)S->mtris.p;

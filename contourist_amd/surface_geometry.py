@@ -68,8 +68,48 @@ class SurfaceGeometry(object):
         return self.oriented_triangles
 
 
-def _sorted_rows(tris):
+def row_order(tris):
+    """the permutation that sorts the rows of a (T,3) triangle array as the host API returns them: sort_rows(tris) ==
+    tris[row_order(tris)].  Whatever belongs to the triangles in device order (component labels) is permuted with it."""
+    tris = np.asarray(tris).reshape(-1, 3)
+    if len(tris) == 0:
+        return np.zeros(0, dtype=np.intp)
+    return np.lexsort((tris[:, 2], tris[:, 1], tris[:, 0]))
+
+
+def sort_rows(tris):
     tris = np.asarray(tris).reshape(-1, 3)
     if len(tris) == 0:
         return tris
-    return tris[np.lexsort((tris[:, 2], tris[:, 1], tris[:, 0]))]
+    return tris[row_order(tris)]
+
+
+_sorted_rows = sort_rows
+
+
+def select_components(table, mask=None, largest=None, min_triangles=None, min_area=None, closed=None):
+    """boolean keep mask over the rows of a component table (fields triangles, area, closed).  The selectors combine with AND:
+    mask (one entry per component), largest=k (the k components with the most triangles, ties by id), min_triangles,
+    min_area, closed (True: closed ones only, False: open ones only)."""
+    n = len(table)
+    keep = np.ones(n, dtype=bool)
+    if mask is not None:
+        m = np.asarray(mask).astype(bool).reshape(-1)
+        if len(m) != n:
+            raise ValueError("the mask has %d entries, the mesh has %d components" % (len(m), n))
+        keep &= m
+    if largest is not None:
+        k = int(largest)
+        if k < 0:
+            raise ValueError("largest must not be negative")
+        rank = np.lexsort((np.arange(n), -np.asarray(table["triangles"], dtype=np.int64)))     # most triangles first, ties by id
+        top = np.zeros(n, dtype=bool)
+        top[rank[:k]] = True
+        keep &= top
+    if min_triangles is not None:
+        keep &= np.asarray(table["triangles"]) >= int(min_triangles)
+    if min_area is not None:
+        keep &= np.asarray(table["area"]) >= float(min_area)
+    if closed is not None:
+        keep &= (np.asarray(table["closed"]) != 0) == bool(closed)
+    return keep

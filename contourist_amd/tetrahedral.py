@@ -287,6 +287,41 @@ class GridContour3d(object):
         ctx = self._ensure_post(clean)
         return ctx.level1_sample(self._post, field, device)
 
+    # -- components of the welded mesh: labels, per-component measures, filtering ----------------------------------
+    def components(self, clean=True, mins=None, delta=None, device=False):
+        """the connected components of get_points_and_triangles() as a numpy structured array (_ffi.COMPONENT_DTYPE: triangles,
+        vertices, area, volume, centroid, bbox_lo, bbox_hi, flipped, closed, first_triangle), measured on the device; component
+        c is row c.  mins / delta: world = grid * delta + mins (grid coordinates without them).
+        device=True: (table, triangle labels, vertex labels), the labels as torch tensors on the GPU in device order."""
+        ctx = self._ensure_post(clean)
+        table = ctx.level1_components(mins, delta)
+        if device:
+            return (table,) + tuple(ctx.level1_component_labels(device=True))
+        return table
+
+    def component_labels(self, clean=True, device=False):
+        """(triangle labels (T,), vertex labels (V,)) int32: the component id of every triangle, and per vertex the smallest id
+        among its triangles' components (-1 for a vertex no triangle uses).  Host: triangle labels in the order of the sorted
+        rows get_points_and_triangles() returns; device=True: torch tensors in device order, next to
+        get_points_and_triangles(device=True)."""
+        ctx = self._ensure_post(clean)
+        if device:
+            return ctx.level1_component_labels(device=True)
+        tl, vl = ctx.level1_component_labels()
+        _pts, tris = ctx.download_level1(self._post)
+        return tl[surface_geometry.row_order(tris)], vl
+
+    def keep_components(self, mask=None, largest=None, min_triangles=None, min_area=None, closed=None, clean=True):
+        """drop components of the mesh ON THE DEVICE: mask (one entry per component), largest=k (most triangles, ties by id),
+        min_triangles, min_area (grid coordinates), closed; the selectors combine with AND.  Afterwards
+        get_points_and_triangles(), vertex_normals(), vertex_values(), write_mesh(), components() give the filtered mesh
+        (until the next march).  -> dict(n_vertices, n_triangles, n_components)"""
+        ctx = self._ensure_post(clean)
+        keep = surface_geometry.select_components(ctx.level1_components(), mask, largest, min_triangles, min_area, closed)
+        counts = ctx.level1_keep_components(keep)
+        self._post = dict(self._post, **counts)
+        return counts
+
     def write_mesh(self, path, fmt="ply", mins=None, delta=None, clean=True):
         """the welded, cleaned, oriented mesh as a binary file written STRAIGHT FROM THE DEVICE BUFFERS (cx_level1_write: no
         (points, triangles) arrays on the host) -- the step every caller of the reference takes next (html_demo.py:118-161).
@@ -544,6 +579,22 @@ class Delta3DContour(object):
             return mesh_io.write_gltf_device(self, path, normals=fmt == "gltf_normals")
         return self.contour_maker.write_mesh(path, fmt, self.grid.mins, self.grid.delta)
 
+    def components(self, clean=True, device=False):
+        "GridContour3d.components in WORLD coordinates (areas, volumes, centroids and boxes of the grid's mins and delta)"
+        return self.contour_maker.components(clean, self.grid.mins, self.grid.delta, device)
+
+    def component_labels(self, clean=True, device=False):
+        "GridContour3d.component_labels of this isosurface"
+        return self.contour_maker.component_labels(clean, device)
+
+    def keep_components(self, mask=None, largest=None, min_triangles=None, min_area=None, closed=None, clean=True):
+        "GridContour3d.keep_components; min_area in WORLD units"
+        maker = self.contour_maker
+        if min_area is not None:
+            keep = surface_geometry.select_components(self.components(clean), mask, largest, min_triangles, min_area, closed)
+            return maker.keep_components(mask=keep, clean=clean)
+        return maker.keep_components(mask, largest, min_triangles, None, closed, clean)
+
     def vertex_normals(self, clean=True, device=False):
         """(V,3) float64 unit normals in WORLD coordinates (the gradient per axis divided by delta, normalised); row i belongs
         to row i of get_points_and_triangles()[0]"""
@@ -678,8 +729,9 @@ class LevelResult(tuple):
     vertex_normals() / vertex_values(field).  They read the level's mesh on the device, so they work until the
     generator moves on to the next level."""
 
-    def _bind(self, owner, index, post, delta):
+    def _bind(self, owner, index, post, delta, mins=None):
         self._owner, self._index, self._post, self._delta = owner, index, post, delta
+        self._mins = (0.0, 0.0, 0.0) if mins is None else mins
         return self
 
     def _ctx(self):
@@ -694,6 +746,37 @@ class LevelResult(tuple):
     def vertex_values(self, field, device=False):
         "(V,) float64: a second grid of the samples' shape at the vertices"
         return self._ctx().level1_sample(self._post, field, device)
+
+    def components(self, device=False):
+        "the level's components in world coordinates (GridContour3d.components); device=True: with the labels as device tensors"
+        ctx = self._ctx()
+        table = ctx.level1_components(self._mins, self._delta)
+        return (table,) + tuple(ctx.level1_component_labels(device=True)) if device else table
+
+    def component_labels(self, device=False):
+        "(triangle labels in the order of the level's sorted triangle rows, vertex labels); device=True: tensors in device order"
+        ctx = self._ctx()
+        if device:
+            return ctx.level1_component_labels(device=True)
+        tl, vl = ctx.level1_component_labels()
+        _pts, tris = ctx.download_level1(self._post)
+        return tl[surface_geometry.row_order(tris)], vl
+
+    def keep_components(self, mask=None, largest=None, min_triangles=None, min_area=None, closed=None):
+        """drop components of the level's mesh on the device (GridContour3d.keep_components, min_area in world units); the tuple's
+        own points and triangles are the unfiltered ones: mesh() downloads the filtered mesh"""
+        ctx = self._ctx()
+        keep = surface_geometry.select_components(ctx.level1_components(self._mins, self._delta), mask, largest, min_triangles, min_area, closed)
+        counts = ctx.level1_keep_components(keep)
+        self._post = dict(self._post, **counts)
+        return counts
+
+    def mesh(self):
+        "(world points, sorted triangle rows) of the level's mesh as it stands on the device (after keep_components: the filtered one)"
+        ctx = self._ctx()
+        pts, tris = ctx.download_level1(self._post)
+        delta, mins = np.asarray(self._delta, dtype=np.float64), np.asarray(self._mins, dtype=np.float64)
+        return (pts * delta + mins if len(pts) else np.zeros((0, 3))), surface_geometry.sort_rows(tris)
 
 
 class MultiLevelIsosurfaces(object):
@@ -726,7 +809,7 @@ class MultiLevelIsosurfaces(object):
                 grid_points, triangles = maker.get_points_and_triangles(clean)
                 self._current = n
                 yield LevelResult((v, self.grid.from_grid_coordinates(grid_points) if len(grid_points) else np.zeros((0, 3)),
-                                   triangles))._bind(self, n, maker._post, self.grid.delta)
+                                   triangles))._bind(self, n, maker._post, self.grid.delta, self.grid.mins)
             self._current = None
             return
         if grid_field._is_torch(samples):
@@ -745,7 +828,7 @@ class MultiLevelIsosurfaces(object):
             geometry = surface_geometry.SurfaceGeometry._from_device(grid_points, triangles, ctx)   # sorted rows, as the reference returns them
             points = self.grid.from_grid_coordinates(geometry.vertices) if len(grid_points) else np.zeros((0, 3))
             self._current = n
-            yield LevelResult((v, points, geometry.oriented_triangles))._bind(self, n, post, self.grid.delta)
+            yield LevelResult((v, points, geometry.oriented_triangles))._bind(self, n, post, self.grid.delta, self.grid.mins)
         self._current = None
 
 

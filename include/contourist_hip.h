@@ -319,6 +319,64 @@ int cx_level1_normals_download(cx_ctx* ctx, const double* delta3, double* normal
 int cx_level0_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtype, int on_device, void** values_dev, float* values_host);
 int cx_level1_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtype, int on_device, void** values_dev, double* values_host);
 
+/* ---- components of the Level-1 mesh: labels, per-component measures, filtering -------------------------------------------------------
+ * What a caller does with an isosurface of noisy data right after extracting it: how many pieces, how big is each, is it closed, and
+ * drop the specks / keep the largest few.  The orientation step of the post-pass already finds the components (the reference orients
+ * every component on its own, surface_geometry.py:52-140); these calls read its tables, so the mesh never leaves the device.
+ * Component      = a set of the orientation step: the triangles linked through shared edges.  Their number is out_counts[4] of
+ *                  the post-pass that made the mesh.
+ * Component id   c in 0 .. nc-1: the components in ascending order of their smallest triangle index in the order of
+ *                  cx_level1_download.  It depends on the mesh only.
+ * Triangle label int32[nt]: the id of the triangle's component.  Vertex label int32[nv]: the SMALLEST id among the components of
+ *                  the triangles that use the vertex (two components may touch in a vertex without sharing an edge); -1 for a
+ *                  vertex no triangle uses.
+ * Measures, of the triangles as wound in the output (p0, p1, p2 = the rows of the triangle array), in world coordinates
+ * w = grid * delta + mins when mins_delta (six doubles, as for cx_level1_write; mapped without fused multiply-add) is given, in
+ * grid coordinates when it is NULL:
+ *   triangles, vertices   counts (vertices by vertex label)
+ *   area                  sum of |(p1-p0) x (p2-p0)| / 2
+ *   volume                sum of det[p0-o, p1-o, p2-o] / 6, o = the centre of the WHOLE mesh's grid box (corner / 2, mapped like the
+ *                         points; one o for all components, returned in origin3_and_q[0..2]).  Signed: positive for a closed
+ *                         component wound outward, negative for one wound inward (the reference winds the outermost of nested
+ *                         shells outward and every component by its own max-x rule).  For an open component it depends on o.
+ *   centroid[3]           area-weighted mean of the triangle centroids ((0,0,0) for zero area)
+ *   bbox_lo, bbox_hi      over the triangles' vertices
+ *   flipped               1 = the orientation step reversed the component's root triangle (the s of cx_level1_normals)
+ *   closed                1 = every undirected edge of the component is used by an even number of its triangles.  Decided from
+ *                         the XOR of a 64-bit hash of the edges {min, max} of all its triangles: a false "closed" needs a 64-bit
+ *                         hash collision; "open" is never wrong.
+ *   first_triangle        the component's smallest triangle index
+ * Reproducible: every triangle's term of the three sums (area, volume, centroid moments) is rounded once to a multiple of 2^-q' with
+ * q' >= q = origin3_and_q[3], chosen from the grid box alone, and the integers are added exactly; a record is the same bit for bit in
+ * every call, in every context, and whatever other components the mesh holds (cx_level1_keep_components leaves the kept records
+ * unchanged).  |sum - exact sum of the terms| <= triangles * 2^-(q+1).  The grid is chosen for vertices that lie within the diagonal of
+ * the grid box of its centre.  A term past that bound (a caller's mesh that does not fit the corner it was handed over with, a wrong
+ * cx_set_reference_corner) is clamped and the record says so: reserved[0] == 1.0 means its three sums are not exact; 0.0 otherwise.
+ * The table and the labels live in buffers of the context, are made on the first request and kept until the next post-pass or
+ * cx_level1_keep_components; table_dev / the label pointers are valid until then (kernels are enqueued on the context's stream).
+ * cx_level1_keep_components: keep[c] != 0 keeps component c (nc bytes on the host).  Triangles, vertices and keys keep their relative
+ * order, components are renumbered in order; afterwards every reader of the Level-1 mesh -- cx_level1_download, _device_ptrs,
+ * _download_keys, cx_level1_write, cx_level1_normals, cx_level1_sample_grid and these calls -- serves the filtered mesh.
+ * (cx_surface_geometry works on arrays of the caller and is not affected.)  All ones leaves everything as it is; all zeros gives
+ * an empty mesh.  out_counts: [0] vertices, [1] triangles, [4] components.  The sign of cx_level1_normals is read from the tables of the
+ * FILTERED mesh: a vertex shared by two components with different flips (they touch in it without sharing an edge) takes the flip of a
+ * component that is still there, which can differ from its sign before the filter; every other kept vertex keeps its normal bit for bit.
+ * CX_ERR_INVALID without a Level-1 mesh; CX_ERR_UNSUPPORTED after cx_postprocess3d_shard_* (a shard's components reach other ranks);
+ * CX_ERR_STATE when the tables of the orientation step are gone (a 4-D pass on the same context used their memory).  Meshes of
+ * cx_postprocess3d_mesh are served: nothing here needs edge ids. */
+typedef struct cx_component {            /* 128 bytes, plain data */
+    int64_t triangles, vertices;
+    double  area, volume, centroid[3], bbox_lo[3], bbox_hi[3];
+    int32_t flipped, closed;
+    int64_t first_triangle;              /* smallest triangle index (device order) */
+    double  reserved[1];                 /* [0]: 1.0 when a term was past the bound of the sums' grid (see above), else 0.0 */
+} cx_component;
+int cx_level1_components(cx_ctx* ctx, const double* mins_delta, int64_t* n_components, void** table_dev, double* origin3_and_q);
+int cx_level1_components_download(cx_ctx* ctx, const double* mins_delta, cx_component* out);
+int cx_level1_component_labels(cx_ctx* ctx, void** tri_labels_dev, void** vert_labels_dev);
+int cx_level1_component_labels_download(cx_ctx* ctx, int32_t* tri_labels, int32_t* vert_labels);
+int cx_level1_keep_components(cx_ctx* ctx, const uint8_t* keep, int64_t* out_counts);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
