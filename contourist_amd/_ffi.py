@@ -47,6 +47,7 @@ SYMBOLS = [
     "cx_postprocess3d", "cx_postprocess3d_ex", "cx_level0_points_f64", "cx_postprocess3d_mesh", "cx_select_seeded3d", "cx_select_seeded3d_ex", "cx_seeded_masks_download", "cx_set_reference_corner", "cx_level1_download", "cx_level1_device_ptrs", "cx_level1_download_keys", "cx_postprocess3d_shard_begin", "cx_postprocess3d_shard_boundary", "cx_postprocess3d_shard_candidates", "cx_postprocess3d_shard_finish", "cx_level1_write", "cx_surface_geometry",
     "cx_level0_normals", "cx_level0_normals_download", "cx_level1_normals", "cx_level1_normals_download", "cx_level0_sample_grid", "cx_level1_sample_grid",
     "cx_level1_components", "cx_level1_components_download", "cx_level1_component_labels", "cx_level1_component_labels_download", "cx_level1_keep_components",
+    "cx_level1_simplify", "cx_level1_simplify_map", "cx_level1_simplify_map_download",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -93,6 +94,11 @@ def native_dtype(dtype):
 
 
 CX_MESH_OF_THE_MARCH = 8      # cx_postprocess3d_mesh flags bit 3: the triangles are ones the march emitted (at most two per edge before merges)
+CX_SIMPLIFY_NO_CLEAN = 1
+CX_SIMPLIFY_ACROSS_COMPONENTS = 2
+CX_SIMPLIFY_COUNT_ONLY = 4
+CX_SIMPLIFY_NORMALS = 8
+SIMPLIFY_KEYS = ("n_vertices", "n_triangles", "n_components", "n_clusters", "cell", "clamped")
 CX2_ALL_CHAINS = 1
 CX2_NO_DEDUPE = 2
 CX2_SEARCH_SEEDS = 4
@@ -202,6 +208,9 @@ def load():
         "cx_level1_component_labels": [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)],
         "cx_level1_component_labels_download": [vp, vp, vp],
         "cx_level1_keep_components": [vp, vp, vp],
+        "cx_level1_simplify": [vp, vp, ctypes.c_uint32, vp, vp],
+        "cx_level1_simplify_map": [vp, ctypes.POINTER(vp)],
+        "cx_level1_simplify_map_download": [vp, vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -677,6 +686,29 @@ class Context(object):
         out = np.zeros(8, dtype=np.int64)
         self._check_attr(self.lib.cx_level1_keep_components(self.handle, keep.ctypes.data if len(keep) else None, out.ctypes.data))
         return dict(n_vertices=int(out[0]), n_triangles=int(out[1]), n_components=int(out[4]))
+
+    # ---- simplification of the Level-1 mesh by vertex clustering (cx_simplify.hip) ----------------------------------------------
+    def level1_simplify(self, cell, flags=0):
+        """cx_level1_simplify with `cell` (a scalar or three, grid units) -> dict(n_vertices, n_triangles, n_components, n_clusters,
+        cell, clamped, n_distinct, q); with CX_SIMPLIFY_COUNT_ONLY only n_clusters and n_distinct (triangles with three distinct
+        indices after the remap) are filled and the mesh stays as it is"""
+        c3 = np.ascontiguousarray(np.broadcast_to(np.asarray(cell, dtype=np.float64), (3,)))
+        out, q = np.zeros(8, dtype=np.int64), ctypes.c_double(0.0)
+        self._check_attr(self.lib.cx_level1_simplify(self.handle, c3.ctypes.data, int(flags), out.ctypes.data, ctypes.byref(q)))
+        return dict(n_vertices=int(out[0]), n_triangles=int(out[1]), n_components=int(out[4]), n_clusters=int(out[6]),
+                    cell=tuple(float(c) for c in c3), clamped=int(out[5]), n_distinct=int(out[7]), q=int(q.value))
+
+    def level1_simplify_map(self, n_old, device=False):
+        "(n_old,) int32: the new index of every vertex of the mesh before the last simplification, -1 where it went away"
+        n_old = int(n_old)
+        if device:
+            import torch
+            p = ctypes.c_void_p()
+            self._check_attr(self.lib.cx_level1_simplify_map(self.handle, ctypes.byref(p)))
+            return self._device_view(p.value or 0, (n_old,), "<i4", torch.int32)
+        out = np.zeros(n_old, dtype=np.int32)
+        self._check_attr(self.lib.cx_level1_simplify_map_download(self.handle, out.ctypes.data if n_old else None))
+        return out
 
     def surface_geometry(self, points, triangles, do_clean):
         pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3).copy()

@@ -310,9 +310,44 @@ static int cxa_level1(cx_ctx* ctx, const char* who, cx_level1_view* V) {
     return CX_OK;
 }
 
+// the normals a simplified mesh carries (cx_level1_simplify with CX_SIMPLIFY_NORMALS): N as it stands, or normalize(N / delta)
+__global__ void cx_k_carried_normals(const double* __restrict__ N, uint32_t nv, int scaled, double d0, double d1, double d2, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    double x = N[(size_t)v * 3], y = N[(size_t)v * 3 + 1], z = N[(size_t)v * 3 + 2];
+    if (scaled) {
+        x = x / d0; y = y / d1; z = z / d2;
+        const double len = sqrt(x * x + y * y + z * z);
+        if (len > 0.0) { x = x / len; y = y / len; z = z / len; }
+    }
+    out[(size_t)v * 3] = x; out[(size_t)v * 3 + 1] = y; out[(size_t)v * 3 + 2] = z;
+}
+// 0: not a simplified mesh; 1: served (or failed: *rc); the normals are in ctx->attr_n1
+static int cxa_carried(cx_ctx* ctx, const double* delta3, void** normals_dev, uint32_t* nv_out, int* rc) {
+    const double* N = nullptr;
+    uint32_t nv = 0;
+    const int mode = cx_level1_carried_normals(ctx, &N, &nv);
+    if (!mode) return 0;
+    *rc = CX_OK;
+    if (mode == 2) { *rc = cxa_fail(ctx, CX_ERR_UNSUPPORTED, "cx_level1_normals: the mesh was simplified without CX_SIMPLIFY_NORMALS: it carries no normals"); return 1; }
+    if (normals_dev) *normals_dev = nullptr;
+    if (nv_out) *nv_out = nv;
+    if (!nv) return 1;
+    if (hipSetDevice(ctx->device) != hipSuccess) { *rc = cxa_fail(ctx, CX_ERR_HIP, "cx_level1_normals: hipSetDevice"); return 1; }
+    if (ctx->attr_n1_cap < (size_t)nv * 3u && (*rc = cx_grow(ctx, ctx->attr_n1, ctx->attr_n1_cap, ((size_t)nv + nv / 16u + 64u) * 3u))) return 1;
+    hipLaunchKernelGGL(cx_k_carried_normals, cxa_grid(nv), dim3(256), 0, ctx->stream, N, nv, delta3 ? 1 : 0, delta3 ? delta3[0] : 1.0, delta3 ? delta3[1] : 1.0,
+                       delta3 ? delta3[2] : 1.0, ctx->attr_n1);
+    if (hipGetLastError() != hipSuccess) { *rc = cxa_fail(ctx, CX_ERR_HIP, "cx_level1_normals: launch of the carried normals failed"); return 1; }
+    if (normals_dev) *normals_dev = ctx->attr_n1;
+    return 1;
+}
+
 extern "C" int cx_level1_normals(cx_ctx* ctx, const double* delta3, void** normals_dev) {
     if (!ctx) return CX_ERR_INVALID;
     if (!cxa_delta_ok(delta3)) return cxa_fail(ctx, CX_ERR_INVALID, "cx_level1_normals: the spacing must be positive and finite");
+    int rcc = CX_OK;
+    if (cxa_carried(ctx, delta3, normals_dev, nullptr, &rcc)) return rcc;
     cx_level1_view V;
     int rc = cxa_level1(ctx, "cx_level1_normals", &V);
     if (rc) return rc;
@@ -336,6 +371,9 @@ extern "C" int cx_level1_normals_download(cx_ctx* ctx, const double* delta3, dou
     void* dev = nullptr;
     const int rc = cx_level1_normals(ctx, delta3, &dev);
     if (rc || !dev) return rc;
+    const double* carried = nullptr;
+    uint32_t nvc = 0;
+    if (cx_level1_carried_normals(ctx, &carried, &nvc) == 1) return cx_copy_to_host1(ctx, normals_xyz, dev, (size_t)nvc * 3u * sizeof(double));
     cx_level1_view V;
     const int rv = cx_level1_attr_view(ctx, "cx_level1_normals_download", &V);
     if (rv) return rv;

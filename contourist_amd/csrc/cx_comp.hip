@@ -560,7 +560,7 @@ extern "C" int cx_level1_keep_components(cx_ctx* ctx, const uint8_t* keep, int64
         } else
             nv2 = 0;
         CXC_HIP(ctx, hipGetLastError());
-        if ((rc = cx_level1_comp_commit(ctx, nv2, nt2))) return rc;
+        if ((rc = cx_level1_comp_commit(ctx, nv2, nt2, C->vuse, C->vnew))) return rc;
         C->gen_labels = ~0ULL; C->gen_table = ~0ULL;
     }
     if (out_counts) { out_counts[0] = nv2; out_counts[1] = nt2; out_counts[4] = kept; }

@@ -115,6 +115,8 @@ struct cx_ctx {
     size_t attr_grid_cap = 0;
     // components of the Level-1 mesh (cx_comp.hip): labels, accumulators and the table, kept between calls
     struct cx_comp_state* comp = nullptr;
+    // vertex clustering of the Level-1 mesh (cx_simplify.hip): cluster table, accumulators, scans, kept between calls
+    struct cx_simplify_state* simp = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -234,11 +236,33 @@ struct cx_level1_comp_scratch {
 };
 int cx_level1_comp_view_get(cx_ctx* ctx, const char* who, cx_level1_comp_view* out);
 int cx_level1_comp_scratch_get(cx_ctx* ctx, cx_level1_comp_scratch* out);
-int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new);
+// (vuse / vnew: which vertices stay and their new indices, for what travels with the vertices -- the carried normals of a simplified mesh)
+int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new, const uint32_t* vuse, const uint32_t* vnew);
+// what cx_simplify.hip writes for the shared tail of the post-pass (clean, compaction, orientation), in buffers the post-pass starts
+// from: the clusters' points, prio = first member, the remapped triangles, tprio3 = {old triangle index} x 3, alive bytes; map: one
+// int32 per vertex of the mesh before (the cluster id; the tail turns it into the new vertex index); nrm_new: the clusters' normals;
+// nrm_src: the carried normals of the mesh before when it is a simplified one itself
+struct cx_level1_simplify_io {
+    double* pts;
+    uint32_t* prio;
+    int32_t* tri;
+    uint32_t* tprio3;
+    uint8_t* alive;
+    int32_t* map;
+    double* nrm_new;
+    const double* nrm_src;
+    bool simplified;
+};
+int cx_level1_simplify_bufs(cx_ctx* ctx, bool normals, bool dry_run, cx_level1_simplify_io* out);   // dry_run: map is scratch, the last map stays
+int cx_level1_simplify_tail(cx_ctx* ctx, uint32_t nv_old, uint32_t ncl, uint32_t nt, bool do_clean, bool normals, int64_t* counts);
+int cx_level1_carried_normals(cx_ctx* ctx, const double** nrm, uint32_t* nv);
+int cx_level1_simplify_map_get(cx_ctx* ctx, const int32_t** map, uint32_t* n);
 // cx_attr.hip
 void cx_attr_free(cx_ctx* ctx);
 // cx_comp.hip
 void cx_comp_free(cx_ctx* ctx);
+// cx_simplify.hip
+void cx_simplify_free(cx_ctx* ctx);
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);
 // cx_contour2d.hip

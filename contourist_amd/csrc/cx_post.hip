@@ -59,6 +59,13 @@ struct cx_post_state {
     bool shard_mesh = false;
     double corner[3] = {1.0, 1.0, 1.0};
     uint64_t gen = 0;
+    // simplification (cx_simplify.hip).  simplified: the mesh came out of cx_level1_simplify (its keys are vertex indices of the mesh
+    // before); carried: nrm[nrm_cur] holds one unit normal per vertex of it, carried over from the members of its clusters;
+    // smap: new index of every vertex of the mesh before the last simplification
+    cxp_dev nrm[2], nrm_tmp, smap;
+    int nrm_cur = 0;
+    bool simplified = false, carried = false, smap_valid = false;
+    uint32_t smap_n = 0;
     struct {
         bool open = false;            // between cx_postprocess3d_shard_begin and _finish
         uint32_t nv2 = 0, nt2 = 0;    // mesh of own + first-halo-layer triangles the labels refer to
@@ -96,6 +103,7 @@ void cx_post_free(cx_ctx* ctx) {
     cxp_dev* all[] = {&S->pts, &S->prio, &S->rep, &S->tri, &S->alive, &S->parent, &S->parent2, &S->tkeys, &S->tvals,
                       &S->flags, &S->scan, &S->blocksums, &S->pts_out, &S->tri_out, &S->comp, &S->misc,
                       &S->keys_out, &S->keys_tmp, &S->told, &S->cls, &S->bnd, &S->ever, &S->vflip,
+                      &S->nrm[0], &S->nrm[1], &S->nrm_tmp, &S->smap,
                       &S->mpairs, &S->msegs, &S->mtris, &S->mmid, &S->mtime, &S->mnext, &S->msegs2, &S->mtris2, &S->mtime2,
                       &S->meflags, &S->metflag, &S->menew, &S->mecnt, &S->medesc, &S->me_pts, &S->me_tri};
     for (cxp_dev* d : all)
@@ -1242,6 +1250,7 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
     S->keys_edge = false; S->orient_live = false; S->vflip_valid = false;
     S->shard_mesh = false; S->gen++; S->orient_nt = 0;
     S->shard.open = false;
+    S->simplified = false; S->carried = false; S->smap_valid = false;
     if (do_clean && nt) {
         u64* parent2 = (u64*)S->parent2.p;
         hipLaunchKernelGGL(cxp_k_iota64, dim3(cxp_blocks(nv)), dim3(256), 0, st, parent2, nv);
@@ -1975,7 +1984,8 @@ int cx_level1_attr_view(cx_ctx* ctx, const char* who, cx_level1_view* out) {
     if (!ctx->post || !ctx->post_valid || !ctx->post->keys_valid) { ctx->err = std::string(who) + ": no Level-1 mesh (run cx_postprocess3d first)"; return CX_ERR_INVALID; }
     cx_post_state* S = ctx->post;
     if (!S->keys_edge) {
-        ctx->err = std::string(who) + ": the Level-1 vertices are not edge crossings of the resident array (a mesh handed to cx_postprocess3d_mesh, or a shard)";
+        ctx->err = std::string(who) + (S->simplified ? ": the vertices of a simplified mesh (cx_level1_simplify) are cluster means, not edge crossings of the resident array"
+                                                     : ": the Level-1 vertices are not edge crossings of the resident array (a mesh handed to cx_postprocess3d_mesh, or a shard)");
         return CX_ERR_UNSUPPORTED;
     }
     const uint32_t nv = (uint32_t)S->nv_out, nt = (uint32_t)S->nt_out;
@@ -2002,6 +2012,16 @@ int cx_level1_attr_view(cx_ctx* ctx, const char* who, cx_level1_view* out) {
 // The tables of the orientation step as they stand after cxp_k_orient: parent[t] = (parity << 32) | root, flattened, the root being the
 // smallest triangle index of the component (every union keeps the smaller root); cflip[root] = the root's flip.  Nothing here needs
 // edge ids, so the meshes of cx_postprocess3d_mesh are served too; a shard's components reach other ranks: CX_ERR_UNSUPPORTED.
+// carried normals (cx_simplify.hip) of the vertices that stay, in their order: vnew[v] = new index (0xFFFFFFFF or use[v] == 0: gone)
+__global__ void cxp_k_carry_normals(const double* __restrict__ in, const uint32_t* __restrict__ use, const uint32_t* __restrict__ vnew, uint32_t n,
+                                    double* __restrict__ out) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n || (use && !use[v])) return;
+    const uint32_t j = vnew[v];
+    if (j == 0xFFFFFFFFu) return;
+#pragma unroll
+    for (int a = 0; a < 3; a++) out[(size_t)j * 3 + a] = in[(size_t)v * 3 + a];
+}
 int cx_level1_comp_view_get(cx_ctx* ctx, const char* who, cx_level1_comp_view* out) {
     if (!ctx->post || !ctx->post_valid || !ctx->post->keys_valid) { ctx->err = std::string(who) + ": no Level-1 mesh (run cx_postprocess3d first)"; return CX_ERR_INVALID; }
     cx_post_state* S = ctx->post;
@@ -2042,9 +2062,17 @@ int cx_level1_comp_scratch_get(cx_ctx* ctx, cx_level1_comp_scratch* out) {
     return CX_OK;
 }
 // the filtered copy becomes the Level-1 mesh: every reader of the state (download, device pointers, keys, files, normals) serves it
-int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new) {
+int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new, const uint32_t* vuse, const uint32_t* vnew) {
     cx_post_state* S = ctx->post;
     hipStream_t st = ctx->stream;
+    S->smap_valid = false;
+    if (S->carried && nv_new && S->nv_out) {       // the carried normals of a simplified mesh follow their vertices
+        const int rcn = cxp_reserve(ctx, S->nrm[1 - S->nrm_cur], ((size_t)nv_new + 1) * 3 * sizeof(double));
+        if (rcn) return rcn;
+        hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cxp_blocks((size_t)S->nv_out)), dim3(256), 0, st, (const double*)S->nrm[S->nrm_cur].p, vuse, vnew,
+                           (uint32_t)S->nv_out, (double*)S->nrm[1 - S->nrm_cur].p);
+        S->nrm_cur = 1 - S->nrm_cur;
+    }
     const size_t nt_old = (size_t)S->nt_out;
     const u64* parent_new = (const u64*)S->tkeys.p;
     if (nv_new) {
@@ -2061,6 +2089,97 @@ int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new) {
     S->orient_nt = nt_new;
     S->vflip_valid = false;      // (written again from the tables on the next request)
     S->gen++;
+    return CX_OK;
+}
+
+// ---- what the simplification (cx_simplify.hip) needs from the Level-1 state ------------------------------------------------------------
+// The clusters' points, priorities (= first member, ascending with the cluster id), remapped triangles with their priorities (the old
+// triangle index, three times) and alive bytes go into the buffers the post-pass starts from; cx_level1_simplify_tail then drops
+// triangles that became the same vertex set and runs the shared tail (clean, compaction, orientation with the windings taken as
+// coherent) on them, exactly the kernels cxp_run3d ends with.  Nothing is uploaded; nothing is allocated once the buffers have their size.
+int cx_level1_simplify_bufs(cx_ctx* ctx, bool normals, bool dry_run, cx_level1_simplify_io* out) {
+    cx_post_state* S = ctx->post;
+    const size_t nv = (size_t)S->nv_out, nt = (size_t)S->nt_out;
+    int rc;
+    // (as cxp_reserve3d, without S->parent: it holds the tables of the orientation step the mesh still needs if the call fails)
+    if ((rc = cxp_reserve(ctx, S->pts, (nv + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = cxp_reserve(ctx, S->prio, (nv + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = cxp_reserve(ctx, S->tri, (nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;
+    if ((rc = cxp_reserve(ctx, S->alive, nt + 16))) return rc;
+    if ((rc = cxp_reserve(ctx, S->parent2, (nv + 1) * sizeof(u64)))) return rc;
+    // (a dry run leaves the map of the last simplification alone: its cluster ids go into the weld's scratch)
+    if ((rc = cxp_reserve(ctx, dry_run ? S->rep : S->smap, (nv + 16) * sizeof(int32_t)))) return rc;
+    if (normals && (rc = cxp_reserve(ctx, S->nrm_tmp, (nv + 1) * 3 * sizeof(double)))) return rc;
+    out->pts = (double*)S->pts.p;
+    out->prio = (uint32_t*)S->prio.p;
+    out->tri = (int32_t*)S->tri.p;
+    out->tprio3 = (uint32_t*)(out->tri + (nt + 1) * 3);
+    out->alive = (uint8_t*)S->alive.p;
+    out->map = (int32_t*)(dry_run ? S->rep.p : S->smap.p);
+    out->nrm_new = normals ? (double*)S->nrm_tmp.p : nullptr;
+    out->nrm_src = S->carried ? (const double*)S->nrm[S->nrm_cur].p : nullptr;
+    out->simplified = S->simplified;
+    if (!dry_run) S->smap_valid = false;
+    return CX_OK;
+}
+// new index of every OLD vertex: through the cluster, the vertex the clean-up merged the cluster into (if any), the compaction
+__global__ void cxp_k_simplify_map(int32_t* map, uint32_t nv_old, uint32_t ncl, const u64* parent2, const uint32_t* vnew) {
+    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv_old) return;
+    int32_t c = map[v];
+    if (c < 0 || (uint32_t)c >= ncl) { map[v] = -1; return; }
+    if (parent2) { uint32_t par; c = (int32_t)cxp_find(parent2, (uint32_t)c, par); }
+    map[v] = (int32_t)vnew[c];       // (0xFFFFFFFF where no surviving triangle uses it)
+}
+int cx_level1_simplify_tail(cx_ctx* ctx, uint32_t nv_old, uint32_t ncl, uint32_t nt, bool do_clean, bool normals, int64_t* counts) {
+    cx_post_state* S = ctx->post;
+    hipStream_t st = ctx->stream;
+    int rc;
+    int32_t* tri = (int32_t*)S->tri.p;
+    uint32_t* tprio3 = (uint32_t*)(tri + ((size_t)S->nt_out + 1) * 3);
+    uint8_t* alive = (uint8_t*)S->alive.p;
+    const int cur = S->nrm_cur;
+    if (nt && ncl) {
+        const u64 tsz = cxp_table_size(nt);
+        if ((rc = cxp_reserve(ctx, S->tkeys, tsz * sizeof(u64)))) return rc;
+        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, (u64*)S->tkeys.p, (size_t)tsz, CXP_EMPTY);
+        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, (u64*)S->tkeys.p, tsz - 1, (const uint8_t*)nullptr);
+        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, (u64*)S->tkeys.p, tsz - 1, (const uint8_t*)nullptr);
+    }
+    // (the compaction writes the new id of every vertex in use: the others keep -1)
+    if ((rc = cxp_reserve(ctx, S->scan, ((size_t)ncl + 16) * sizeof(uint32_t)))) return rc;
+    if (ncl) CXP_HIP(ctx, hipMemsetAsync(S->scan.p, 0xFF, (size_t)ncl * sizeof(uint32_t), st));
+    if (normals && (rc = cxp_reserve(ctx, S->nrm[1 - cur], ((size_t)ncl + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = cxp_clean_orient(ctx, S, ncl, nt, do_clean, true, tprio3, counts, true))) { ctx->post_valid = false; return rc; }
+    const uint32_t* vnew = (const uint32_t*)S->scan.p;
+    if (nv_old) hipLaunchKernelGGL(cxp_k_simplify_map, dim3(cxp_blocks(nv_old)), dim3(256), 0, st, (int32_t*)S->smap.p, nv_old, ncl,
+                                   (do_clean && nt) ? (const u64*)S->parent2.p : (const u64*)nullptr, vnew);
+    if (normals && ncl && S->nv_out) {
+        hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cxp_blocks(ncl)), dim3(256), 0, st, (const double*)S->nrm_tmp.p, (const uint32_t*)nullptr, vnew, ncl,
+                           (double*)S->nrm[1 - cur].p);
+        S->nrm_cur = 1 - cur;
+    }
+    CXP_HIP(ctx, hipGetLastError());
+    CXP_HIP(ctx, hipStreamSynchronize(st));
+    S->simplified = true; S->carried = normals;
+    S->smap_valid = true; S->smap_n = nv_old;
+    return CX_OK;
+}
+// 0: the mesh is not a simplified one; 1: simplified, *nrm = its carried normals; 2: simplified without normals
+int cx_level1_carried_normals(cx_ctx* ctx, const double** nrm, uint32_t* nv) {
+    cx_post_state* S = ctx->post;
+    if (!S || !ctx->post_valid || !S->keys_valid || !S->simplified) return 0;
+    *nv = (uint32_t)S->nv_out;
+    *nrm = S->carried ? (const double*)S->nrm[S->nrm_cur].p : nullptr;
+    return S->carried ? 1 : 2;
+}
+int cx_level1_simplify_map_get(cx_ctx* ctx, const int32_t** map, uint32_t* n) {
+    cx_post_state* S = ctx->post;
+    if (!S || !ctx->post_valid || !S->simplified || !S->smap_valid) {
+        ctx->err = "cx_level1_simplify_map: no simplification since the last post-pass or filter";
+        return CX_ERR_STATE;
+    }
+    *map = (const int32_t*)S->smap.p; *n = S->smap_n;
     return CX_OK;
 }
 

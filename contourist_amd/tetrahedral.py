@@ -322,6 +322,33 @@ class GridContour3d(object):
         self._post = dict(self._post, **counts)
         return counts
 
+    # -- simplification by vertex clustering on the device (the reference's flatten=True is LP decimation: not this) -------------
+    def simplify(self, cell=None, target_triangles=None, by_component=True, clean=True, normals="auto"):
+        """reduce the mesh ON THE DEVICE by vertex clustering (cx_level1_simplify): the vertices of one cell of a lattice of `cell`
+        voxels (a scalar or three), per component unless by_component=False, become one vertex at their exact mean.
+        target_triangles=N instead of cell: the smallest scalar cell a bisection over [1, max(corner)] finds (dry runs only, at
+        most 16, down to 1/16 voxel) whose mesh has no more than N triangles; ValueError if the largest cell does not get there.
+        normals: True carries the vertex normals over (vertex_normals() serves them), False drops them, "auto" carries them where
+        vertex_normals() is available.  Afterwards get_points_and_triangles(), vertex_normals(), components(), keep_components()
+        and write_mesh() give the simplified mesh until the next march; vertex_values() raises NotImplementedError.
+        -> dict(n_vertices, n_triangles, n_components, n_clusters, cell, clamped)"""
+        if (cell is None) == (target_triangles is None):
+            raise ValueError("exactly one of cell and target_triangles is needed")
+        ctx = self._ensure_post(clean)
+        if normals == "auto":
+            try:
+                self._attr_checks()
+                normals = bool(self._post.get("carried_normals", True))
+            except NotImplementedError:
+                normals = False
+        counts = _simplify_on(ctx, cell, target_triangles, by_component, clean, bool(normals), max(int(c) for c in self.corner), self)
+        self._post = dict(self._post, carried_normals=bool(normals), **{k: counts[k] for k in ("n_vertices", "n_triangles", "n_components")})
+        return counts
+
+    def simplify_map(self, device=False):
+        "(V_before,) int32: the new index of every vertex of the mesh before the last simplify(), -1 where it went away"
+        return self.context().level1_simplify_map(getattr(self, "_simplify_n_old", 0), device)      # (none yet: the library's CX_ERR_STATE)
+
     def write_mesh(self, path, fmt="ply", mins=None, delta=None, clean=True):
         """the welded, cleaned, oriented mesh as a binary file written STRAIGHT FROM THE DEVICE BUFFERS (cx_level1_write: no
         (points, triangles) arrays on the host) -- the step every caller of the reference takes next (html_demo.py:118-161).
@@ -410,6 +437,36 @@ class GridContour3d(object):
         b = np.where(swap[:, None], lo, hi)
         return {(tuple(int(x) for x in p), tuple(int(x) for x in q)): np.array(c, dtype=float)
                 for p, q, c in zip(a, b, L["xyz"])}
+
+
+def _simplify_on(ctx, cell, target_triangles, by_component, clean, normals, max_corner, owner):
+    "simplify() of the three isosurface classes on the context that holds the mesh; owner gets _simplify_n_old and _simplify_search"
+    flags = (0 if clean else _ffi.CX_SIMPLIFY_NO_CLEAN) | (0 if by_component else _ffi.CX_SIMPLIFY_ACROSS_COMPONENTS)
+    owner._simplify_search = []          # [(cell, triangles with three distinct indices)] of the dry runs, in the order they ran
+    if target_triangles is not None:
+        n = int(target_triangles)
+
+        def dry(c):
+            got = ctx.level1_simplify(c, flags | _ffi.CX_SIMPLIFY_COUNT_ONLY)["n_distinct"]
+            owner._simplify_search.append((float(c), int(got)))
+            return got
+        lo, hi = 1.0, float(max(1, max_corner))
+        reached = dry(hi)
+        if reached > n:
+            raise ValueError("target_triangles=%d is out of reach: the largest cell (%g voxels) still leaves %d triangles" % (n, hi, reached))
+        if hi > lo and dry(lo) <= n:
+            hi = lo
+        while len(owner._simplify_search) < 16 and hi - lo >= 1.0 / 16.0:
+            mid = 0.5 * (lo + hi)
+            if dry(mid) <= n:
+                hi = mid          # (the smallest cell found so far that stays within n)
+            else:
+                lo = mid
+        cell = hi
+    n_old = ctx.level1_device_ptrs()[2]
+    counts = ctx.level1_simplify(cell, flags | (_ffi.CX_SIMPLIFY_NORMALS if normals else 0))
+    owner._simplify_n_old = int(n_old)
+    return {k: counts[k] for k in _ffi.SIMPLIFY_KEYS}
 
 
 def unpack_edge_ids(keys, shape):
@@ -595,6 +652,14 @@ class Delta3DContour(object):
             return maker.keep_components(mask=keep, clean=clean)
         return maker.keep_components(mask, largest, min_triangles, None, closed, clean)
 
+    def simplify(self, cell=None, target_triangles=None, by_component=True, clean=True, normals="auto"):
+        "GridContour3d.simplify of this isosurface: `cell` in VOXELS (grid units), a scalar or one per axis"
+        return self.contour_maker.simplify(cell, target_triangles, by_component, clean, normals)
+
+    def simplify_map(self, device=False):
+        "GridContour3d.simplify_map"
+        return self.contour_maker.simplify_map(device)
+
     def vertex_normals(self, clean=True, device=False):
         """(V,3) float64 unit normals in WORLD coordinates (the gradient per axis divided by delta, normalised); row i belongs
         to row i of get_points_and_triangles()[0]"""
@@ -771,8 +836,25 @@ class LevelResult(tuple):
         self._post = dict(self._post, **counts)
         return counts
 
+    def simplify(self, cell=None, target_triangles=None, by_component=True, clean=True, normals="auto"):
+        """GridContour3d.simplify on the level's mesh (`cell` in voxels); the tuple's own points and triangles are the unsimplified
+        ones: mesh() downloads the simplified mesh"""
+        if (cell is None) == (target_triangles is None):
+            raise ValueError("exactly one of cell and target_triangles is needed")
+        ctx = self._ctx()
+        if normals == "auto":
+            normals = bool(self._post.get("carried_normals", True))
+        corner = max(int(n) for n in self._owner.grid.grid_dimensions)
+        counts = _simplify_on(ctx, cell, target_triangles, by_component, clean, bool(normals), corner, self)
+        self._post = dict(self._post, carried_normals=bool(normals), **{k: counts[k] for k in ("n_vertices", "n_triangles", "n_components")})
+        return counts
+
+    def simplify_map(self, device=False):
+        "GridContour3d.simplify_map for the level's mesh"
+        return self._ctx().level1_simplify_map(getattr(self, "_simplify_n_old", 0), device)
+
     def mesh(self):
-        "(world points, sorted triangle rows) of the level's mesh as it stands on the device (after keep_components: the filtered one)"
+        "(world points, sorted triangle rows) of the level's mesh as it stands on the device (after keep_components or simplify: that one)"
         ctx = self._ctx()
         pts, tris = ctx.download_level1(self._post)
         delta, mins = np.asarray(self._delta, dtype=np.float64), np.asarray(self._mins, dtype=np.float64)

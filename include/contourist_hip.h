@@ -377,6 +377,62 @@ int cx_level1_component_labels(cx_ctx* ctx, void** tri_labels_dev, void** vert_l
 int cx_level1_component_labels_download(cx_ctx* ctx, int32_t* tri_labels, int32_t* vert_labels);
 int cx_level1_keep_components(cx_ctx* ctx, const uint8_t* keep, int64_t* out_counts);
 
+/* ---- simplification: vertex clustering of the Level-1 mesh on the device ---------------------------------------------------------
+ * (The reference's flatten=True is serial LP decimation, a different algorithm with different output; it stays unsupported.)
+ * Input: the current unsharded Level-1 mesh of the context -- points P (float64, grid coordinates), triangles T (device order) --
+ * and the tables of the orientation step.  Parameters: cell3, three positive finite doubles in grid units, and flags.
+ * Cluster of a vertex v:
+ *   - its cell k_a = floor(P[v][a] / cell3[a]) per axis, an IEEE division as numpy.floor(p / c) computes it.  The lattice is anchored
+ *     at grid coordinate 0; points on a sampled rim are negative, hence floor and not truncation.  The grid box has, per axis, the cells
+ *     floor(-1 / cell_a) .. floor((corner_a + 1) / cell_a); a vertex outside of it (a caller's mesh that does not fit its corner)
+ *     counts to the nearest cell of the box.
+ *   - unless CX_SIMPLIFY_ACROSS_COMPONENTS is set the cluster is the pair (cell, vertex label of cx_level1_component_labels): two
+ *     sheets that pass through one cell never fuse, and components cannot merge.
+ *   - vertices with label -1 are dropped.
+ *   - the number of cells of the grid box, per axis floor((corner_a + 1) / cell_a) - floor(-1 / cell_a) + 1, multiplied over the
+ *     axes, must be below 2^31 ((label, linear cell) is one 64-bit table key): CX_ERR_INVALID otherwise, with a message that names
+ *     the smallest admissible cell.
+ * Position of a cluster: the mean of its members, computed exactly.  Each coordinate is clamped to [-1, corner_a + 1] (a clamped
+ * coordinate is counted in out_counts[5]) and rounded once to X = llrint(x * 2^q), q = 52 - ceil(log2(max_a(corner_a) + 2)); q
+ * comes from the grid box alone and is returned in *q_out.  The integers are added exactly (64-bit inside a wave, then a two-word
+ * 128-bit accumulator per cluster); the result is double(sum), rounded once (to nearest, ties to even), / double(n), * 2^-q.
+ * Order: new vertex i is the cluster with the i-th smallest first member, the first member being the cluster's smallest old vertex
+ * index.  Surviving triangles keep their relative order and their winding.
+ * Triangles: indices are remapped; a triangle with two equal indices is dropped; of several triangles with the same vertex set the
+ * one with the smallest old index stays.  Unless CX_SIMPLIFY_NO_CLEAN (bit 0, with the meaning it has in cx_postprocess3d) is set,
+ * the reference's clean_triangles rule (surface_geometry.py:14-50) then runs on the result with the kernels of the post-pass, on
+ * the device buffers: nothing is uploaded, there is no weld and no tiny collapse.  The orientation step always runs, with the
+ * windings taken as coherent (a component is turned as a whole by the max-x rule); afterwards cx_level1_components,
+ * cx_level1_keep_components and their `flipped` work on the new mesh.  New vertices that no surviving triangle uses are compacted away.
+ * Keys: cx_level1_download_keys gives the first member's old vertex index (the convention after cx_postprocess3d_mesh).  The keys
+ * stop being edge ids: cx_level1_sample_grid answers CX_ERR_UNSUPPORTED after a simplification.
+ * Carried normals (CX_SIMPLIFY_NORMALS): allowed only where cx_level1_normals is served for the source mesh (CX_ERR_UNSUPPORTED
+ * elsewhere, the mesh untouched).  The grid-coordinate unit normals of the source (delta3 == NULL) are summed per cluster as
+ * llrint(n * 2^30) integers, added exactly in 64 bits, then normalised in float64: N = s / sqrt(s.s), (0,0,0) for a zero sum.
+ * After the call cx_level1_normals(delta3) serves N for delta3 == NULL and normalize(N / delta3) otherwise; so do
+ * cx_level1_normals_download and the two _NORMALS file formats of cx_level1_write.  The component flip is not applied again (the
+ * members' normals carry it; the orientation step's decision for the simplified mesh is reported by `flipped` as usual).
+ * Simplifying a simplified mesh carries the carried normals on; cx_level1_keep_components keeps them with their vertices.  Without
+ * the flag the normals calls answer CX_ERR_UNSUPPORTED after a simplification.
+ * out_counts (8 x int64): [0] vertices, [1] triangles, [4] components, [5] clamped coordinates, [6] clusters, [7] triangles with
+ * three distinct indices after the remap, before duplicate removal (an upper bound on [1]).  CX_SIMPLIFY_COUNT_ONLY is a dry run:
+ * the mesh is untouched and only [6] and [7] are filled.
+ * cx_level1_simplify_map: one int32 per vertex of the mesh BEFORE the call, its new index, -1 where the vertex went away (label -1,
+ * or no surviving triangle uses its cluster; a cluster the clean rule merged into another maps to that one).  Valid until the next
+ * post-pass, filter or simplification (CX_ERR_STATE then); callers use it to carry attributes of their own.
+ * Errors and state: CX_ERR_INVALID without a Level-1 mesh or with bad cells; CX_ERR_UNSUPPORTED after cx_postprocess3d_shard_*;
+ * CX_ERR_STATE when the tables of the orientation step are gone (a 4-D pass on the same context used their memory).  A call that
+ * fails leaves the mesh as it was.  A successful call starts a new generation of the post state: cached component tables and
+ * labels are rebuilt on request.  All buffers belong to the context and are reused.  Reproducible: every output array is the same
+ * bit for bit in every call and context. */
+#define CX_SIMPLIFY_NO_CLEAN           1u   /* bit 0, as cx_postprocess3d */
+#define CX_SIMPLIFY_ACROSS_COMPONENTS  2u
+#define CX_SIMPLIFY_COUNT_ONLY         4u   /* dry run: mesh untouched, only out_counts[6], [7] filled */
+#define CX_SIMPLIFY_NORMALS            8u
+int cx_level1_simplify(cx_ctx* ctx, const double* cell3, uint32_t flags, int64_t* out_counts8, double* q_out);
+int cx_level1_simplify_map(cx_ctx* ctx, void** new_index_of_old_vertex_dev);
+int cx_level1_simplify_map_download(cx_ctx* ctx, int32_t* new_index_of_old_vertex);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
