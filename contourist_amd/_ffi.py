@@ -51,7 +51,7 @@ SYMBOLS = [
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
-    "cx_timing_enable", "cx_timing_read", "cx_measure_read_bandwidth", "cx_debug_stamps", "cx_version",
+    "cx_timing_enable", "cx_timing_read", "cx_measure_read_bandwidth", "cx_device_bytes", "cx_debug_stamps", "cx_version",
 ]
 # sample types of a 3-D grid the kernels read as they are (CX_DTYPE_*): each converts to fp32 exactly.  Other types (int32, int64,
 # float64) are not exact in fp32 and are widened on the host, as every type was before.
@@ -250,6 +250,7 @@ def load():
         "cx_timing_enable": [vp, ctypes.c_int],
         "cx_timing_read": [vp, ctypes.POINTER(dbl), ctypes.POINTER(ctypes.c_int)],
         "cx_measure_read_bandwidth": [vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(dbl)],
+        "cx_device_bytes": [vp, ctypes.POINTER(i64), ctypes.POINTER(i64)],
     }
     for name, args in sigs.items():
         fn = getattr(L, name)
@@ -257,6 +258,15 @@ def load():
         fn.argtypes = args
     _lib = L
     return L
+
+
+def device_bytes(handle=None):
+    """(live bytes, hipMalloc calls so far) of the library's device buffers: of the context with this handle, or of the whole process"""
+    live, allocations = ctypes.c_int64(), ctypes.c_int64()
+    rc = load().cx_device_bytes(handle, ctypes.byref(live), ctypes.byref(allocations))
+    if rc:
+        raise CxError(rc, "cx_device_bytes")
+    return live.value, allocations.value
 
 
 class CxError(RuntimeError):

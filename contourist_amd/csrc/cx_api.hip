@@ -41,7 +41,7 @@ extern "C" int cx_ctx_create(int device_id, cx_ctx** out) {
     // same context must not disturb what a later relaunch of the 3-D vertex stage (cx_ensure_cell_records) reads on the device
     // (+ a second page: the 4-D cells kernel's (tetrahedra | border voxels) word sits 4 KB away from its (cells | vertices) word --
     // two same-line atomics per workgroup executed one after the other at the memory side, 38 us of that kernel's 63)
-    if (hipMalloc(&ctx->counters, 2048 * sizeof(uint32_t)) != hipSuccess ||
+    if (ctx->counters.grow(ctx, 2048) != CX_OK ||
         hipHostMalloc(&ctx->counters_host, 2 * CX_CNT_WORDS * sizeof(uint32_t)) != hipSuccess) {
         cx_ctx_destroy(ctx);
         return CX_ERR_NOMEM;
@@ -50,58 +50,30 @@ extern "C" int cx_ctx_create(int device_id, cx_ctx** out) {
     return CX_OK;
 }
 
-static void free_outputs(cx_ctx* ctx) {
-    cx_release(ctx->verts, ctx->vcap);
-    cx_release(ctx->verts_xyz, ctx->verts_xyz_cap);
-    cx_release(ctx->cells, ctx->ccap);
-    cx_release(ctx->tris, ctx->tcap);
-}
-
 extern "C" int cx_ctx_destroy(cx_ctx* ctx) {
     if (!ctx) return CX_OK;
     (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();
+    (void)hipDeviceSynchronize();   // in front of everything that destroys buffers
     cx_rccl_comm_free(ctx);
     cx_levels_free(ctx);
     cx_xfer_free(ctx);
     cx_post_free(ctx);
-    cx_attr_free(ctx);
     cx_comp_free(ctx);
     cx_simplify_free(ctx);
     cx_state4_free(ctx);
     cx_state2_free(ctx);
-    free_outputs(ctx);
-    cx_release(ctx->grid_owned, ctx->grid_owned_bytes);
-    cx_release(ctx->grid64, ctx->grid64_cap);
-    cx_release(ctx->celltab, ctx->tables_for);
-    cx_release(ctx->queue, ctx->queue_cap);
-    cx_release(ctx->wsum, ctx->wsum_cap);
-    cx_release(ctx->wbase, ctx->wbase_cap);
-    cx_release(ctx->tri_keep, ctx->keep_cap);
-    for (int k = 0; k < 8; k++) cx_release(ctx->seed_buf[k], ctx->seed_cap[k]);
-    cx_release(ctx->brec, ctx->brec_cap);
-    cx_release(ctx->flat, ctx->flat_cap);
-    cx_release(ctx->hash_xy, ctx->hash_xy_cap);
-    cx_release(ctx->qa, ctx->qa_cap);
-    cx_release(ctx->info, ctx->info_cap);
-    cx_release(ctx->info64, ctx->info64_cap);
-    cx_release(ctx->tq, ctx->tq_cap);
-    cx_release(ctx->chunksum, ctx->chunksum_cap);
-    cx_release(ctx->rstart, ctx->rstart_cap);
-    cx_release(ctx->kstart, ctx->kstart_cap);
-    cx_release(ctx->hbytes, ctx->hbytes_cap);
-    cx_release(ctx->fj, ctx->fj_cap);
-    cx_release(ctx->fk, ctx->fk_cap);
-    cx_release(ctx->bnd, ctx->bnd_cap);
-    cx_release(ctx->bndn, ctx->bndn_cap);
-    cx_release(ctx->torder, ctx->torder_cap);
-    if (ctx->counters) (void)hipFree(ctx->counters);
     if (ctx->counters_host) (void)hipHostFree(ctx->counters_host);
     for (auto& ev : ctx->events)
         for (int n = 0; n < 5; n++)
             if (ev.e[n]) (void)hipEventDestroy(ev.e[n]);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;   // the context's own buffers go with it
+    return CX_OK;
+}
+
+extern "C" int cx_device_bytes(cx_ctx* ctx, int64_t* live_bytes, int64_t* allocations) {
+    if (live_bytes) *live_bytes = ctx ? ctx->tally.live_bytes : cx_process_tally.live_bytes.load();
+    if (allocations) *allocations = ctx ? ctx->tally.allocations : cx_process_tally.allocations.load();
     return CX_OK;
 }
 
@@ -126,6 +98,7 @@ static int set_grid_dims(cx_ctx* ctx, int64_t n0, int64_t n1, int64_t n2) {
     if (N > (1LL << 29)) return fail(ctx, CX_ERR_UNSUPPORTED, "more than 2^29 samples in one grid: partition into slabs");
     ctx->n0 = n0; ctx->n1 = n1; ctx->n2 = n2;
     ctx->grid64_valid = false;   // the float64 originals belonged to the previous grid
+    cx_levels_unselect(ctx);     // a level selected on the previous grid gets its output buffers back: its slot would allocate new ones otherwise
     cx_levels_invalidate(ctx);
     ctx->extracted = false;
     ctx->post_valid = false;
@@ -140,7 +113,7 @@ extern "C" int cx_grid_upload_typed(cx_ctx* ctx, const void* host, int32_t dtype
     if (rc) return rc;
     ctx->grid = {nullptr, CX_DTYPE_F32};
     const size_t bytes = (size_t)(n0 * n1 * n2) * cx_dtype_size(dtype);
-    rc = cx_grow(ctx, ctx->grid_owned, ctx->grid_owned_bytes, bytes);   // bytes: a grid of another type reuses the buffer
+    rc = ctx->grid_owned.grow(ctx, bytes);   // bytes: a grid of another type reuses the buffer
     if (rc) return rc;
     CX_HIP(ctx, hipMemcpyAsync(ctx->grid_owned, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -188,7 +161,7 @@ extern "C" int cx_grid_shadow_f64(cx_ctx* ctx, const double* host, int64_t n0, i
         return fail(ctx, CX_ERR_STATE, "cx_grid_shadow_f64: bind the fp32 grid of the same dimensions first");
     CX_HIP(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)(n0 * n1 * n2);
-    int rc = cx_grow(ctx, ctx->grid64, ctx->grid64_cap, N);
+    int rc = ctx->grid64.grow(ctx, N);
     if (rc) return rc;
     CX_HIP(ctx, hipMemcpyAsync(ctx->grid64, host, N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -218,13 +191,9 @@ extern "C" int cx_reserve(cx_ctx* ctx, int64_t max_cells, int64_t max_vertices, 
         return fail(ctx, CX_ERR_UNSUPPORTED, "capacity beyond 32-bit indices");
     CX_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
-    if ((rc = cx_grow(ctx, ctx->cells, ctx->ccap, (size_t)max_cells))) return rc;
-    if ((rc = cx_grow(ctx, ctx->verts, ctx->vcap, (size_t)max_vertices))) return rc;
-    {
-        size_t t3 = (size_t)ctx->tcap * 3u;
-        if ((rc = cx_grow(ctx, ctx->tris, t3, (size_t)max_triangles * 3u))) { ctx->tcap = 0; return rc; }
-        ctx->tcap = (uint32_t)(t3 / 3u);
-    }
+    if ((rc = ctx->cells.grow(ctx, (size_t)max_cells))) return rc;
+    if ((rc = ctx->verts.grow(ctx, (size_t)max_vertices))) return rc;
+    if ((rc = ctx->tris.grow(ctx, (size_t)max_triangles * 3u))) return rc;
     ctx->extracted = false;
     ctx->post_valid = false;
     return CX_OK;
@@ -244,7 +213,7 @@ int cx_ensure_hash_xy(cx_ctx* ctx, uint32_t flags) {
         return CX_OK;
     const size_t need = (size_t)(ctx->n0 * ctx->n1);
     {
-        const int rc = cx_grow(ctx, ctx->hash_xy, ctx->hash_xy_cap, need);
+        const int rc = ctx->hash_xy.grow(ctx, need);
         if (rc) return rc;
     }
     cx_launch_hash_xy(ctx->hash_xy, (uint32_t)ctx->n0, (uint32_t)ctx->n1, (uint32_t)ctx->origin[0], (uint32_t)ctx->origin[1], ctx->stream);
@@ -304,13 +273,13 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
     const bool tiled = staged && !typed && !fused && !(flags & CX_KERNEL_STAGED) && ((flags & CX_KERNEL_TILED) || cx_debug_knob("CX_TILED", 0u));
     if (!staged) {
         // the per-cell table of the generic emit path (one 8-byte entry per sample): only when that path runs
-        const int rc = cx_grow(ctx, ctx->celltab, ctx->tables_for, (size_t)N + 64u);
+        const int rc = ctx->celltab.grow(ctx, (size_t)N + 64u);
         if (rc) return rc;
     }
     P.celltab = ctx->celltab;
     P.fused = fused ? 1u : 0u;
     P.verts = ctx->verts; P.cells = ctx->cells; P.tris = ctx->tris;
-    P.vcap = ctx->vcap; P.ccap = ctx->ccap; P.tcap = ctx->tcap;
+    P.vcap = ctx->vcap(); P.ccap = ctx->ccap(); P.tcap = ctx->tcap();
     P.counters = ctx->counters;
     P.stamps = ctx->stamps;
     ctx->last = P;
@@ -325,7 +294,7 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
         // one byte per lattice point: its slot (and alternative slot) in CPython's 8-slot set, built once per shape / origin
         if (!ctx->hbytes_valid || ctx->hbytes_n2 != ctx->n2 || ctx->hbytes_o2 != ctx->origin[2]) {
             {
-                const int rc = cx_grow(ctx, ctx->hbytes, ctx->hbytes_cap, (size_t)N + 64u);
+                const int rc = ctx->hbytes.grow(ctx, (size_t)N + 64u);
                 if (rc) return rc;
             }
             cx_launch_hash_bytes(ctx->hbytes, ctx->hash_xy, P.n0, P.n1, P.n2, P.org2, ctx->stream);
@@ -339,22 +308,22 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
         T = cx_fast_task(P.n0, P.n1, P.n2);
         const size_t nw = (size_t)T.nblocks * 4u, need = nw * T.wcap;
         int rc;
-        if ((rc = cx_grow(ctx, ctx->queue, ctx->queue_cap, need))) return rc;
-        if ((rc = cx_grow(ctx, ctx->wsum, ctx->wsum_cap, nw))) return rc;
-        if ((rc = cx_grow(ctx, ctx->wbase, ctx->wbase_cap, nw))) return rc;
-        if ((rc = cx_grow(ctx, ctx->brec, ctx->brec_cap, nw * T.bcap))) return rc;
+        if ((rc = ctx->queue.grow(ctx, need))) return rc;
+        if ((rc = ctx->wsum.grow(ctx, nw))) return rc;
+        if ((rc = ctx->wbase.grow(ctx, nw))) return rc;
+        if ((rc = ctx->brec.grow(ctx, nw * T.bcap))) return rc;
         // batches: at most one short batch per streaming wave plus one per CX_BATCH_MIN (>= 128) queued cells; queued
         // cells = cell records + array-boundary cells without vertices.  Sized from the cell capacity, so a
         // surface that fits the cell capacity fits here (cx_counts_get reports CX_ERR_CAPACITY otherwise).
         const size_t boundary = (size_t)(ctx->n0 * ctx->n1 + ctx->n0 * ctx->n2 + ctx->n1 * ctx->n2);
-        const size_t nflat = nw + (size_t)ctx->ccap / 64u + boundary / 128u + 4096u;
-        if ((rc = cx_grow(ctx, ctx->flat, ctx->flat_cap, nflat))) return rc;
-        if ((rc = cx_grow(ctx, ctx->qa, ctx->qa_cap, nw * CX_SWP * 64u + 64u))) return rc;
+        const size_t nflat = nw + (size_t)ctx->ccap() / 64u + boundary / 128u + 4096u;
+        if ((rc = ctx->flat.grow(ctx, nflat))) return rc;
+        if ((rc = ctx->qa.grow(ctx, nw * CX_SWP * 64u + 64u))) return rc;
         const size_t nchunk_words = ((nw + 255u) / 256u) * 8u;
-        if ((rc = cx_grow(ctx, ctx->chunksum, ctx->chunksum_cap, nchunk_words))) return rc;
+        if ((rc = ctx->chunksum.grow(ctx, nchunk_words))) return rc;
         CX_HIP(ctx, hipMemsetAsync(ctx->chunksum, 0, nchunk_words * sizeof(uint32_t), ctx->stream));
-        if (!fused && (rc = cx_grow(ctx, ctx->info64, ctx->info64_cap, need))) return rc;   // staged kernels: (first vertex, crossing mask) per queue entry
-        if (fused && (rc = cx_grow(ctx, ctx->info, ctx->info_cap, need))) return rc;        // fused kernel: one word per queue entry
+        if (!fused && (rc = ctx->info64.grow(ctx, need))) return rc;   // staged kernels: (first vertex, crossing mask) per queue entry
+        if (fused && (rc = ctx->info.grow(ctx, need))) return rc;        // fused kernel: one word per queue entry
         P.queue = ctx->queue; P.wsum = ctx->wsum; P.wbase = ctx->wbase; P.brec = ctx->brec;
         P.flat = ctx->flat; P.fcap = (uint32_t)nflat;
         P.qa = ctx->qa; P.info = ctx->info; P.info64 = ctx->info64; P.chunksum = ctx->chunksum;
@@ -368,7 +337,7 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
         // built, tested (tests/test_gpu_level0.py::test_fraction_stream) and OFF; CX_DEBUG=1 CX_TQ=1 turns it on.
         P.tq = nullptr; P.tlimit = 0;
         if (!fused && !typed && cx_debug_knob("CX_TQ", 0u)) {   // (an fp32 A/B switch: not instantiated for narrow types)
-            if ((rc = cx_grow(ctx, ctx->tq, ctx->tq_cap, need))) return rc;
+            if ((rc = ctx->tq.grow(ctx, need))) return rc;
             P.tq = ctx->tq; P.tlimit = T.wcap;
         }
         // the triangle stage walks the vertex stage's cell records.  The kernel that walks queue entries instead (no records: 80 MB
@@ -377,19 +346,19 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
         P.write_records = (!fused && !tiled && !cx_debug_knob("CX_K2_ENTRIES", 0u)) ? 1u : 0u;
         if (tiled) {
             P.qa = nullptr;       // nobody gathers the queue words: the stream kernel does not store them
-            if ((rc = cx_grow(ctx, ctx->fj, ctx->fj_cap, (size_t)P.n0 * (4u * T.njg) * P.n2 + 64u))) return rc;
-            if ((rc = cx_grow(ctx, ctx->fk, ctx->fk_cap, (size_t)P.n0 * P.n1 * (2u * T.nks) + 64u))) return rc;
-            if ((rc = cx_grow(ctx, ctx->bnd, ctx->bnd_cap, (size_t)T.nblocks * 2u * T.bndcap))) return rc;
-            if ((rc = cx_grow(ctx, ctx->bndn, ctx->bndn_cap, (size_t)T.nblocks * 2u))) return rc;
-            if ((rc = cx_grow(ctx, ctx->torder, ctx->torder_cap, (size_t)T.nblocks * 6u))) return rc;
+            if ((rc = ctx->fj.grow(ctx, (size_t)P.n0 * (4u * T.njg) * P.n2 + 64u))) return rc;
+            if ((rc = ctx->fk.grow(ctx, (size_t)P.n0 * P.n1 * (2u * T.nks) + 64u))) return rc;
+            if ((rc = ctx->bnd.grow(ctx, (size_t)T.nblocks * 2u * T.bndcap))) return rc;
+            if ((rc = ctx->bndn.grow(ctx, (size_t)T.nblocks * 2u))) return rc;
+            if ((rc = ctx->torder.grow(ctx, (size_t)T.nblocks * 6u))) return rc;
             P.fj = ctx->fj; P.fk = ctx->fk; P.bnd = ctx->bnd; P.bndn = ctx->bndn; P.torder = ctx->torder;
             P.tile_cap = cx_debug_knob("CX_TILE_CAP", cx_tile_cap_default());
         }
         P.nvw = cx_vertex_stage_waves(P);
-        if ((rc = cx_grow(ctx, ctx->rstart, ctx->rstart_cap, (size_t)P.nvw + 1u))) return rc;
+        if ((rc = ctx->rstart.grow(ctx, (size_t)P.nvw + 1u))) return rc;
         P.rstart = ctx->rstart;
         P.nkw = cx_triangle_stage_waves(P);
-        if ((rc = cx_grow(ctx, ctx->kstart, ctx->kstart_cap, (size_t)P.nkw + 1u))) return rc;
+        if ((rc = ctx->kstart.grow(ctx, (size_t)P.nkw + 1u))) return rc;
         P.kstart = ctx->kstart;
         ctx->last = P;
     }
@@ -457,7 +426,7 @@ extern "C" int cx_counts_get(cx_ctx* ctx, cx_counts* out) {
     out->n_triangles = ctx->counters_host[CX_CNT_TRIS];
     out->n_border_voxels = ctx->counters_host[CX_CNT_BORDER];
     ctx->counts = *out;
-    if (out->n_cells > ctx->ccap || out->n_vertices > ctx->vcap || out->n_triangles > ctx->tcap ||
+    if (out->n_cells > ctx->ccap() || out->n_vertices > ctx->vcap() || out->n_triangles > ctx->tcap() ||
         (ctx->last.flat && ctx->counters_host[CX_CNT_BATCHES] > ctx->last.fcap)) {
         ctx->extracted = false;
         return fail(ctx, CX_ERR_CAPACITY, "output buffers too small for this isosurface");
@@ -507,7 +476,7 @@ int cx_ensure_cell_records(cx_ctx* ctx) {
     cx_params P = ctx->last;
     P.flags |= CX_DBG_NO_VERTS | CX_DBG_NO_CELLTAB;
     P.write_records = 1u;
-    P.ccap = ctx->ccap; P.cells = ctx->cells;
+    P.ccap = ctx->ccap(); P.cells = ctx->cells;
     cx_launch_emit_vertices(P, ctx->last_task, ctx->stream);
     CX_HIP(ctx, hipGetLastError());
     ctx->records_valid = true;
@@ -523,8 +492,8 @@ extern "C" int cx_level0_path(cx_ctx* ctx, int* path) {
 // the vertex records of the current extraction expanded to float4 {x, y, z, bits(edge id)} in a buffer of the context
 int cx_level0_expanded(cx_ctx* ctx, float4** out) {
     const size_t nv = (size_t)ctx->counts.n_vertices;
-    if (ctx->verts_xyz_cap < nv) {
-        const int rc = cx_grow(ctx, ctx->verts_xyz, ctx->verts_xyz_cap, nv + nv / 16 + 64);
+    if (ctx->verts_xyz.cap() < nv) {
+        const int rc = ctx->verts_xyz.grow(ctx, nv + nv / 16 + 64);
         if (rc) return rc;
     }
     cx_launch_expand_verts(ctx->verts, ctx->verts_xyz, (uint32_t)nv, (uint32_t)ctx->n1, (uint32_t)ctx->n2, ctx->stream);
@@ -591,15 +560,14 @@ extern "C" int cx_debug_stamps(cx_ctx* ctx, int64_t words, unsigned long long* h
     CX_HIP(ctx, hipSetDevice(ctx->device));
     CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (host && ctx->stamps) {
-        CX_HIP(ctx, hipMemcpy(host, ctx->stamps, ctx->stamps_words * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        CX_HIP(ctx, hipMemcpy(host, ctx->stamps, ctx->stamps.bytes(), hipMemcpyDeviceToHost));
         return CX_OK;
     }
-    if (ctx->stamps) (void)hipFree(ctx->stamps);
-    ctx->stamps = nullptr; ctx->stamps_words = 0;
+    ctx->stamps.release();
     if (words > 0) {
-        CX_HIP(ctx, hipMalloc(&ctx->stamps, (size_t)words * sizeof(unsigned long long)));
-        CX_HIP(ctx, hipMemset(ctx->stamps, 0, (size_t)words * sizeof(unsigned long long)));
-        ctx->stamps_words = (size_t)words;
+        const int rc = ctx->stamps.grow(ctx, (size_t)words);
+        if (rc) return rc;
+        CX_HIP(ctx, hipMemset(ctx->stamps, 0, ctx->stamps.bytes()));
     }
     return CX_OK;
 }
@@ -621,34 +589,39 @@ __global__ __launch_bounds__(256) void cx_k_read_bw(const uint4* __restrict__ sr
     for (; i < n16; i += stride) { const uint4 v = src[i]; acc += v.x ^ v.y ^ v.z ^ v.w; }
     if (acc == 0x9E3779B9u) sink[blockIdx.x & 255u] = acc;    // (practically never: keeps the loads alive)
 }
-extern "C" int cx_measure_read_bandwidth(cx_ctx* ctx, const void* device_ptr, int64_t bytes, int reps, double* out_GBps) {
-    if (!ctx || !device_ptr || bytes < (1 << 20) || reps < 1 || !out_GBps) return ctx ? fail(ctx, CX_ERR_INVALID, "cx_measure_read_bandwidth: bad argument") : CX_ERR_INVALID;
-    CX_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->counters) return fail(ctx, CX_ERR_STATE, "context has no scratch words yet (extract once first)");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    CX_HIP(ctx, hipEventCreate(&e0));
-    CX_HIP(ctx, hipEventCreate(&e1));
-    const size_t n16 = (size_t)bytes / 16u;
-    uint32_t* sink = nullptr;
-    CX_HIP(ctx, hipMalloc(&sink, 256 * sizeof(uint32_t)));
+static int read_bandwidth(cx_ctx* ctx, const void* device_ptr, size_t n16, int reps, hipEvent_t e0, hipEvent_t e1, uint32_t* sink, double* out_GBps) {
     hipLaunchKernelGGL(cx_k_read_bw, dim3(256 * 8), dim3(256), 0, ctx->stream, static_cast<const uint4*>(device_ptr), n16, sink);   // warm
+    CX_HIP(ctx, hipGetLastError());
     double best = 0.0;
     const uint32_t grids[3] = {256u * 8u, 256u * 16u, 256u * 32u};     // workgroups: 8, 16, 32 per CU's worth (the best one counts)
     for (int r = 0; r < reps; r++)
         for (uint32_t g : grids) {
             CX_HIP(ctx, hipEventRecord(e0, ctx->stream));
             hipLaunchKernelGGL(cx_k_read_bw, dim3(g), dim3(256), 0, ctx->stream, static_cast<const uint4*>(device_ptr), n16, sink);
+            CX_HIP(ctx, hipGetLastError());
             CX_HIP(ctx, hipEventRecord(e1, ctx->stream));
             CX_HIP(ctx, hipEventSynchronize(e1));
             float ms = 0.f;
             CX_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
             if (ms > 0.f) best = fmax(best, (double)n16 * 16.0 / (ms * 1e-3) / 1e9);
         }
-    (void)hipFree(sink);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
     *out_GBps = best;
     return CX_OK;
+}
+extern "C" int cx_measure_read_bandwidth(cx_ctx* ctx, const void* device_ptr, int64_t bytes, int reps, double* out_GBps) {
+    if (!ctx || !device_ptr || bytes < (1 << 20) || reps < 1 || !out_GBps) return ctx ? fail(ctx, CX_ERR_INVALID, "cx_measure_read_bandwidth: bad argument") : CX_ERR_INVALID;
+    CX_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->counters) return fail(ctx, CX_ERR_STATE, "context has no scratch words yet (extract once first)");
+    // one way out for the sink and the two events, whatever fails in between
+    cx_buf<uint32_t> sink;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = sink.grow(ctx, 256);
+    if (!rc && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = fail(ctx, CX_ERR_HIP, "cx_measure_read_bandwidth: hipEventCreate failed");
+    if (!rc) rc = read_bandwidth(ctx, device_ptr, (size_t)bytes / 16u, reps, e0, e1, sink, out_GBps);
+    if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing enqueued here outlives the sink
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return rc;
 }
 
 extern "C" int cx_timing_enable(cx_ctx* ctx, int on) {

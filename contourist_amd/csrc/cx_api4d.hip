@@ -20,10 +20,6 @@
 void cx_state4_free(cx_ctx* ctx) {
     cx_state4* S = ctx->s4;
     if (!S) return;
-    cx_release(S->grid_owned, S->grid_owned_bytes); cx_release(S->items, S->items_cap); cx_release(S->info, S->info_cap);
-    cx_release(S->verts, S->vcap); cx_release(S->vkeys, S->vkeys_cap); cx_release(S->cells, S->ccap); cx_release(S->tets, S->tcap);
-    cx_release(S->hash_xyz, S->hash_cap); cx_release(S->signbits, S->signbits_cap); cx_release(S->tet_keep, S->keep_cap);
-    cx_release(S->queue, S->qcap); cx_release(S->rounds, S->rounds_cap);
     cx_slab4_free(S->slab);
     delete S;
     ctx->s4 = nullptr;
@@ -54,12 +50,7 @@ extern "C" int cx_grid4d_upload(cx_ctx* ctx, const float* host, int64_t n0, int6
     if (rc) return rc;
     if ((rc = set_dims4(ctx, S, n0, n1, n2, n3))) return rc;
     const size_t bytes = (size_t)(n0 * n1 * n2 * n3) * sizeof(float);
-    {
-        size_t have = S->grid_owned_bytes / sizeof(float);
-        rc = cx_grow(ctx, S->grid_owned, have, bytes / sizeof(float));
-        S->grid_owned_bytes = have * sizeof(float);
-        if (rc) return rc;
-    }
+    if ((rc = S->grid_owned.grow(ctx, bytes / sizeof(float)))) return rc;
     CX4_HIP(ctx, hipMemcpyAsync(S->grid_owned, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     CX4_HIP(ctx, hipStreamSynchronize(ctx->stream));
     S->grid = S->grid_owned;
@@ -80,17 +71,13 @@ extern "C" int cx_grid4d_adopt_device(cx_ctx* ctx, const void* device_ptr, int64
 static int reserve4(cx_ctx* ctx, cx_state4* S, int64_t nc, int64_t nv, int64_t nt, int64_t nq) {
     if (nq > 0xFFFFFFF0LL || nc > 0xFFFFFFF0LL || nv > 0xFFFFFFF0LL || nt > 0x7FFFFFF0LL) { ctx->err = "capacity beyond 32-bit indices"; return CX_ERR_UNSUPPORTED; }
     int rc;
-    if ((rc = cx_grow(ctx, S->queue, S->qcap, (size_t)nq))) return rc;
-    if ((rc = cx_grow(ctx, S->rounds, S->rounds_cap, (size_t)S->qcap / 64 + 8))) return rc;
-    if ((rc = cx_grow(ctx, S->info, S->info_cap, (size_t)S->qcap + 64u))) return rc;
-    if ((rc = cx_grow(ctx, S->cells, S->ccap, (size_t)nc))) return rc;
-    if ((rc = cx_grow(ctx, S->verts, S->vcap, (size_t)nv))) return rc;
-    if ((rc = cx_grow(ctx, S->vkeys, S->vkeys_cap, (size_t)S->vcap))) return rc;
-    {
-        size_t t4 = (size_t)S->tcap * 4u;
-        if ((rc = cx_grow(ctx, S->tets, t4, (size_t)nt * 4u))) { S->tcap = 0; return rc; }
-        S->tcap = (uint32_t)(t4 / 4u);
-    }
+    if ((rc = S->queue.grow(ctx, (size_t)nq))) return rc;
+    if ((rc = S->rounds.grow(ctx, (size_t)S->qcap() / 64 + 8))) return rc;
+    if ((rc = S->info.grow(ctx, (size_t)S->qcap() + 64u))) return rc;
+    if ((rc = S->cells.grow(ctx, (size_t)nc))) return rc;
+    if ((rc = S->verts.grow(ctx, (size_t)nv))) return rc;
+    if ((rc = S->vkeys.grow(ctx, (size_t)S->vcap()))) return rc;
+    if ((rc = S->tets.grow(ctx, (size_t)nt * 4u))) return rc;
     return CX_OK;
 }
 
@@ -118,8 +105,8 @@ static int enqueue4(cx_ctx* ctx, cx_state4* S, double value, uint32_t flags) {
     P.flags = flags;
     for (int d = 0; d < 4; d++) P.org[d] = (uint32_t)S->origin[d];
     P.info = S->info; P.verts = S->verts; P.vkeys = S->vkeys; P.cells = S->cells; P.tets = S->tets;
-    P.vcap = S->vcap; P.ccap = S->ccap; P.tcap = S->tcap;
-    P.queue = S->queue; P.qcap = S->qcap; P.rounds = S->rounds;
+    P.vcap = S->vcap(); P.ccap = S->ccap(); P.tcap = S->tcap();
+    P.queue = S->queue; P.qcap = S->qcap(); P.rounds = S->rounds;
     P.counters = ctx->counters + CX_CNT_WORDS;   // the 4-D march's own block (cx_ctx_create)
     P.counters_tb = reinterpret_cast<unsigned long long*>(ctx->counters + 1024);
     P.lut = cx_pent_lut_device();
@@ -128,7 +115,7 @@ static int enqueue4(cx_ctx* ctx, cx_state4* S, double value, uint32_t flags) {
         const int64_t key[7] = {S->n[0], S->n[1], S->n[2], S->origin[0], S->origin[1], S->origin[2], 1};
         if (memcmp(key, S->hash_key, sizeof(key)) != 0) {
             const size_t need = (size_t)(S->n[0] * S->n[1] * S->n[2]);
-            if ((rc = cx_grow(ctx, S->hash_xyz, S->hash_cap, need))) return rc;
+            if ((rc = S->hash_xyz.grow(ctx, need))) return rc;
             cx_launch_hash_xyz(S->hash_xyz, P.n0, P.n1, P.n2, P.org, ctx->stream);
             memcpy(S->hash_key, key, sizeof(key));
         }
@@ -141,9 +128,9 @@ static int enqueue4(cx_ctx* ctx, cx_state4* S, double value, uint32_t flags) {
     P.div_r1 = cx_fdiv_make(P.n2);
     {
         const size_t need = (size_t)P.nrows * P.nw3 + 64u;
-        if ((rc = cx_grow(ctx, S->signbits, S->signbits_cap, need))) return rc;
+        if ((rc = S->signbits.grow(ctx, need))) return rc;
         P.signbits = S->signbits;
-        if ((rc = cx_grow(ctx, S->items, S->items_cap, need))) return rc;
+        if ((rc = S->items.grow(ctx, need))) return rc;
         P.items = S->items;
     }
     CX4_HIP(ctx, hipMemsetAsync(ctx->counters + CX_CNT_WORDS, 0, CX_CNT_WORDS * sizeof(uint32_t), ctx->stream));
@@ -167,11 +154,11 @@ static int settle4(cx_ctx* ctx, cx_state4* S, double value, cx_counts* out) {
     S->counts = c;
     if (out) *out = c;
     const uint32_t nq = ctx->counters_host[CX_CNT_WORDS + CX4_CNT_QUEUE];
-    if (nq > S->qcap) {   // nothing was classified: only the queue length is known
+    if (nq > S->qcap()) {   // nothing was classified: only the queue length is known
         if ((rc = reserve4(ctx, S, 0, 0, 0, (int64_t)nq + nq / 20 + 1024))) return rc;
         return 1;
     }
-    if (c.n_cells <= S->ccap && c.n_vertices <= S->vcap && c.n_triangles <= S->tcap) {
+    if (c.n_cells <= S->ccap() && c.n_vertices <= S->vcap() && c.n_triangles <= S->tcap()) {
         S->extracted = true;
         S->post_valid = false;
         S->post_assembled = false;

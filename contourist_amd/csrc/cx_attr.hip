@@ -208,21 +208,12 @@ static bool cxa_delta_ok(const double* delta3) {
 }
 static inline dim3 cxa_grid(uint32_t n) { return dim3((n + 255u) / 256u); }
 
-void cx_attr_free(cx_ctx* ctx) {
-    cx_release(ctx->attr_n0, ctx->attr_n0_cap);
-    cx_release(ctx->attr_n1, ctx->attr_n1_cap);
-    cx_release(ctx->attr_v0, ctx->attr_v0_cap);
-    cx_release(ctx->attr_v1, ctx->attr_v1_cap);
-    cx_release(ctx->attr_e1, ctx->attr_e1_cap);
-    cx_release(ctx->attr_grid, ctx->attr_grid_cap);
-}
-
 // the second grid as the kernels read it: the caller's device pointer, or a copy of the host array in a buffer of the context
 static int cxa_second_grid(cx_ctx* ctx, const char* who, const void* grid, int32_t dtype, int on_device, cx_grid_ref* out) {
     if (!grid || !cx_dtype_valid(dtype)) { ctx->err = std::string(who) + ": a grid of a CX_DTYPE_* sample type is needed"; return CX_ERR_INVALID; }
     if (on_device) { *out = {grid, dtype}; return CX_OK; }
     const size_t bytes = (size_t)(ctx->n0 * ctx->n1 * ctx->n2) * cx_dtype_size(dtype);
-    const int rc = cx_grow(ctx, ctx->attr_grid, ctx->attr_grid_cap, bytes);
+    const int rc = ctx->attr_grid.grow(ctx, bytes);
     if (rc) return rc;
     CXA_HIP(ctx, hipMemcpyAsync(ctx->attr_grid, grid, bytes, hipMemcpyHostToDevice, ctx->stream));
     CXA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the caller's array may go away when this returns
@@ -249,10 +240,10 @@ extern "C" int cx_level0_normals(cx_ctx* ctx, const double* delta3, void** norma
     if (rc) return rc;
     if (normals_dev) *normals_dev = nullptr;
     if (!nv) return CX_OK;
-    if (ctx->attr_n0_cap < nv && (rc = cx_grow(ctx, ctx->attr_n0, ctx->attr_n0_cap, (size_t)nv + nv / 16u + 64u))) return rc;
+    if (ctx->attr_n0.cap() < nv && (rc = ctx->attr_n0.grow(ctx, (size_t)nv + nv / 16u + 64u))) return rc;
     const cxa_dims D = cxa_dims_of(ctx);
     const float d0 = delta3 ? (float)delta3[0] : 1.0f, d1 = delta3 ? (float)delta3[1] : 1.0f, d2 = delta3 ? (float)delta3[2] : 1.0f;
-    cxa_v4f* out = reinterpret_cast<cxa_v4f*>(ctx->attr_n0);
+    cxa_v4f* out = ctx->attr_n0.as<cxa_v4f>();
 #define CX_LAUNCH(DT)                                                                                                                          \
     if (delta3) hipLaunchKernelGGL((cx_k_vertex_normals<DT, true>), cxa_grid(nv), dim3(256), 0, ctx->stream, ctx->grid, ctx->verts, out, nv, D, d0, d1, d2); \
     else hipLaunchKernelGGL((cx_k_vertex_normals<DT, false>), cxa_grid(nv), dim3(256), 0, ctx->stream, ctx->grid, ctx->verts, out, nv, D, d0, d1, d2);
@@ -280,7 +271,7 @@ extern "C" int cx_level0_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtyp
     if ((rc = cxa_second_grid(ctx, "cx_level0_sample_grid", grid, dtype, on_device, &B))) return rc;
     if (values_dev) *values_dev = nullptr;
     if (!nv) return CX_OK;
-    if (ctx->attr_v0_cap < nv && (rc = cx_grow(ctx, ctx->attr_v0, ctx->attr_v0_cap, (size_t)nv + nv / 16u + 64u))) return rc;
+    if (ctx->attr_v0.cap() < nv && (rc = ctx->attr_v0.grow(ctx, (size_t)nv + nv / 16u + 64u))) return rc;
     const uint32_t n2 = (uint32_t)ctx->n2, plane = (uint32_t)(ctx->n1 * ctx->n2), ns = (uint32_t)(ctx->n0 * ctx->n1 * ctx->n2);
 #define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_vertex_sample<DT>), cxa_grid(nv), dim3(256), 0, ctx->stream, B, ctx->verts, ctx->attr_v0, nv, n2, plane, ns);
     CX_DISPATCH_DTYPE(dtype, CX_LAUNCH)
@@ -298,11 +289,11 @@ static int cxa_level1(cx_ctx* ctx, const char* who, cx_level1_view* V) {
     if (rc) return rc;
     if (!ctx->extracted || !ctx->grid.p) { ctx->err = std::string(who) + ": no valid extraction"; return CX_ERR_INVALID; }
     if (!V->nv) return CX_OK;
-    if (ctx->attr_e1_cap < (size_t)V->nv * sizeof(cxa_edge1) &&
-        (rc = cx_grow(ctx, ctx->attr_e1, ctx->attr_e1_cap, ((size_t)V->nv + V->nv / 16u + 64u) * sizeof(cxa_edge1)))) return rc;
+    if (ctx->attr_e1.cap() < (size_t)V->nv * sizeof(cxa_edge1) &&
+        (rc = ctx->attr_e1.grow(ctx, ((size_t)V->nv + V->nv / 16u + 64u) * sizeof(cxa_edge1)))) return rc;
     const uint32_t n2 = (uint32_t)ctx->n2, plane = (uint32_t)(ctx->n1 * ctx->n2), ns = (uint32_t)(ctx->n0 * ctx->n1 * ctx->n2);
     const double* A64 = ctx->grid64_valid ? ctx->grid64 : nullptr;
-    cxa_edge1* edges = reinterpret_cast<cxa_edge1*>(ctx->attr_e1);
+    cxa_edge1* edges = ctx->attr_e1.as<cxa_edge1>();
 #define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_edges<DT>), cxa_grid(V->nv), dim3(256), 0, ctx->stream, ctx->grid, A64, V->keys, V->nv, n2, plane, ns, ctx->last.value, edges);
     CX_DISPATCH_DTYPE(ctx->grid.dtype, CX_LAUNCH)
 #undef CX_LAUNCH
@@ -335,7 +326,7 @@ static int cxa_carried(cx_ctx* ctx, const double* delta3, void** normals_dev, ui
     if (nv_out) *nv_out = nv;
     if (!nv) return 1;
     if (hipSetDevice(ctx->device) != hipSuccess) { *rc = cxa_fail(ctx, CX_ERR_HIP, "cx_level1_normals: hipSetDevice"); return 1; }
-    if (ctx->attr_n1_cap < (size_t)nv * 3u && (*rc = cx_grow(ctx, ctx->attr_n1, ctx->attr_n1_cap, ((size_t)nv + nv / 16u + 64u) * 3u))) return 1;
+    if (ctx->attr_n1.cap() < (size_t)nv * 3u && (*rc = ctx->attr_n1.grow(ctx, ((size_t)nv + nv / 16u + 64u) * 3u))) return 1;
     hipLaunchKernelGGL(cx_k_carried_normals, cxa_grid(nv), dim3(256), 0, ctx->stream, N, nv, delta3 ? 1 : 0, delta3 ? delta3[0] : 1.0, delta3 ? delta3[1] : 1.0,
                        delta3 ? delta3[2] : 1.0, ctx->attr_n1);
     if (hipGetLastError() != hipSuccess) { *rc = cxa_fail(ctx, CX_ERR_HIP, "cx_level1_normals: launch of the carried normals failed"); return 1; }
@@ -353,10 +344,10 @@ extern "C" int cx_level1_normals(cx_ctx* ctx, const double* delta3, void** norma
     if (rc) return rc;
     if (normals_dev) *normals_dev = nullptr;
     if (!V.nv) return CX_OK;
-    if (ctx->attr_n1_cap < (size_t)V.nv * 3u && (rc = cx_grow(ctx, ctx->attr_n1, ctx->attr_n1_cap, ((size_t)V.nv + V.nv / 16u + 64u) * 3u))) return rc;
+    if (ctx->attr_n1.cap() < (size_t)V.nv * 3u && (rc = ctx->attr_n1.grow(ctx, ((size_t)V.nv + V.nv / 16u + 64u) * 3u))) return rc;
     const cxa_dims D = cxa_dims_of(ctx);
     const double* A64 = ctx->grid64_valid ? ctx->grid64 : nullptr;
-    const cxa_edge1* edges = reinterpret_cast<const cxa_edge1*>(ctx->attr_e1);
+    const cxa_edge1* edges = ctx->attr_e1.as<cxa_edge1>();
     const double d0 = delta3 ? delta3[0] : 1.0, d1 = delta3 ? delta3[1] : 1.0, d2 = delta3 ? delta3[2] : 1.0;
 #define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_normals<DT>), cxa_grid(V.nv), dim3(256), 0, ctx->stream, ctx->grid, A64, edges, V.vflip, V.nv, D, delta3 ? 1 : 0, d0, d1, d2, ctx->attr_n1);
     CX_DISPATCH_DTYPE(ctx->grid.dtype, CX_LAUNCH)
@@ -389,8 +380,8 @@ extern "C" int cx_level1_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtyp
     if ((rc = cxa_second_grid(ctx, "cx_level1_sample_grid", grid, dtype, on_device, &B))) return rc;
     if (values_dev) *values_dev = nullptr;
     if (!V.nv) return CX_OK;
-    if (ctx->attr_v1_cap < V.nv && (rc = cx_grow(ctx, ctx->attr_v1, ctx->attr_v1_cap, (size_t)V.nv + V.nv / 16u + 64u))) return rc;
-    const cxa_edge1* edges = reinterpret_cast<const cxa_edge1*>(ctx->attr_e1);
+    if (ctx->attr_v1.cap() < V.nv && (rc = ctx->attr_v1.grow(ctx, (size_t)V.nv + V.nv / 16u + 64u))) return rc;
+    const cxa_edge1* edges = ctx->attr_e1.as<cxa_edge1>();
 #define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_sample<DT>), cxa_grid(V.nv), dim3(256), 0, ctx->stream, B, edges, V.nv, ctx->attr_v1);
     CX_DISPATCH_DTYPE(dtype, CX_LAUNCH)
 #undef CX_LAUNCH

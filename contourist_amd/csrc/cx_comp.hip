@@ -51,28 +51,24 @@ struct cx_comp_state {
     double table_md[6] = {0, 0, 0, 1, 1, 1};
     double origin_q[4] = {0, 0, 0, 0};
     uint32_t nc = 0, nv = 0, nt = 0;
-    uint32_t* tlab = nullptr;  size_t tlab_cap = 0;     // flags of the roots first, then the triangle labels (int32)
-    uint32_t* tidx = nullptr;  size_t tidx_cap = 0;     // exclusive scan of the root flags
-    uint32_t* vlab = nullptr;  size_t vlab_cap = 0;     // vertex labels (int32)
-    uint32_t* sums = nullptr;  size_t sums_cap = 0;     // block sums of the scans
-    uint32_t* first = nullptr; size_t first_cap = 0;    // root triangle of every component
-    u64* acc = nullptr;        size_t acc_cap = 0;
-    cx_component* table = nullptr; size_t table_cap = 0;
-    uint32_t* misc = nullptr;  size_t misc_cap = 0;     // totals of the scans
+    cx_buf<uint32_t> tlab;                              // flags of the roots first, then the triangle labels (int32)
+    cx_buf<uint32_t> tidx;                              // exclusive scan of the root flags
+    cx_buf<uint32_t> vlab;                              // vertex labels (int32)
+    cx_buf<uint32_t> sums;                              // block sums of the scans
+    cx_buf<uint32_t> first;                             // root triangle of every component
+    cx_buf<u64> acc;
+    cx_buf<cx_component> table;
+    cx_buf<uint32_t> misc;                              // totals of the scans
     // filtering
-    uint32_t* tnew = nullptr;  size_t tnew_cap = 0;
-    uint32_t* vuse = nullptr;  size_t vuse_cap = 0;
-    uint32_t* vnew = nullptr;  size_t vnew_cap = 0;
-    uint8_t* keep = nullptr;   size_t keep_cap = 0;
+    cx_buf<uint32_t> tnew;
+    cx_buf<uint32_t> vuse;
+    cx_buf<uint32_t> vnew;
+    cx_buf<uint8_t> keep;
 };
 
 void cx_comp_free(cx_ctx* ctx) {
     cx_comp_state* C = ctx->comp;
     if (!C) return;
-    cx_release(C->tlab, C->tlab_cap); cx_release(C->tidx, C->tidx_cap); cx_release(C->vlab, C->vlab_cap);
-    cx_release(C->sums, C->sums_cap); cx_release(C->first, C->first_cap); cx_release(C->acc, C->acc_cap);
-    cx_release(C->table, C->table_cap); cx_release(C->misc, C->misc_cap); cx_release(C->tnew, C->tnew_cap);
-    cx_release(C->vuse, C->vuse_cap); cx_release(C->vnew, C->vnew_cap); cx_release(C->keep, C->keep_cap);
     delete C;
     ctx->comp = nullptr;
 }
@@ -391,7 +387,7 @@ static int cxc_state(cx_ctx* ctx, cx_comp_state** out) {
     if (!ctx->comp) ctx->comp = new (std::nothrow) cx_comp_state();
     if (!ctx->comp) return CX_ERR_NOMEM;
     *out = ctx->comp;
-    return cx_grow(ctx, ctx->comp->misc, ctx->comp->misc_cap, 16);
+    return ctx->comp->misc.grow(ctx, 16);
 }
 
 // labels of the current mesh (cached per generation of the mesh)
@@ -407,19 +403,19 @@ static int cxc_labels(cx_ctx* ctx, const char* who, cx_level1_comp_view* V, cx_c
     const uint32_t nv = V->nv, nt = V->nt;
     hipStream_t st = ctx->stream;
     uint32_t nc = 0;
-    if ((rc = cx_grow(ctx, C->vlab, C->vlab_cap, (size_t)nv + 16))) return rc;
+    if ((rc = C->vlab.grow(ctx, (size_t)nv + 16))) return rc;
     if (nv) hipLaunchKernelGGL(cxc_k_fill32, cxc_grid(nv), dim3(256), 0, st, C->vlab, nv, nt ? 0x7FFFFFFFu : 0xFFFFFFFFu);
     if (nt) {
-        if ((rc = cx_grow(ctx, C->tlab, C->tlab_cap, (size_t)nt + 16))) return rc;
-        if ((rc = cx_grow(ctx, C->tidx, C->tidx_cap, (size_t)nt + 16))) return rc;
-        if ((rc = cx_grow(ctx, C->sums, C->sums_cap, (size_t)nt / 1024 + 16))) return rc;
+        if ((rc = C->tlab.grow(ctx, (size_t)nt + 16))) return rc;
+        if ((rc = C->tidx.grow(ctx, (size_t)nt + 16))) return rc;
+        if ((rc = C->sums.grow(ctx, (size_t)nt / 1024 + 16))) return rc;
         hipLaunchKernelGGL(cxc_k_roots, cxc_grid(nt), dim3(256), 0, st, V->parent, nt, C->tlab);
         if ((rc = cx_scan_u32(ctx, C->tlab, C->tidx, nt, C->sums, C->misc))) return rc;
         CXC_HIP(ctx, hipMemcpyAsync(&nc, C->misc, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         CXC_HIP(ctx, hipStreamSynchronize(st));
-        if ((rc = cx_grow(ctx, C->first, C->first_cap, (size_t)nc + 16))) return rc;
-        hipLaunchKernelGGL(cxc_k_labels, cxc_grid(nt), dim3(256), 0, st, V->parent, C->tidx, V->tri, nt, nv, (int32_t*)C->tlab, (int32_t*)C->vlab, C->first);
-        hipLaunchKernelGGL(cxc_k_labels_unused, cxc_grid(nv), dim3(256), 0, st, (int32_t*)C->vlab, nv);
+        if ((rc = C->first.grow(ctx, (size_t)nc + 16))) return rc;
+        hipLaunchKernelGGL(cxc_k_labels, cxc_grid(nt), dim3(256), 0, st, V->parent, C->tidx, V->tri, nt, nv, C->tlab.as<int32_t>(), C->vlab.as<int32_t>(), C->first);
+        hipLaunchKernelGGL(cxc_k_labels_unused, cxc_grid(nv), dim3(256), 0, st, C->vlab.as<int32_t>(), nv);
     }
     CXC_HIP(ctx, hipGetLastError());
     C->nc = nc; C->nv = nv; C->nt = nt;
@@ -472,11 +468,11 @@ extern "C" int cx_level1_components(cx_ctx* ctx, const double* mins_delta, int64
         C->origin_q[3] = (double)std::min(qa, std::min(qv, qm));
         if (nc) {
             hipStream_t st = ctx->stream;
-            if ((rc = cx_grow(ctx, C->acc, C->acc_cap, (size_t)nc * CXC_WORDS + 16))) return rc;
-            if ((rc = cx_grow(ctx, C->table, C->table_cap, (size_t)nc + 1))) return rc;
+            if ((rc = C->acc.grow(ctx, (size_t)nc * CXC_WORDS + 16))) return rc;
+            if ((rc = C->table.grow(ctx, (size_t)nc + 1))) return rc;
             hipLaunchKernelGGL(cxc_k_acc_init, cxc_grid((size_t)nc * CXC_WORDS), dim3(256), 0, st, C->acc, nc);
-            hipLaunchKernelGGL(cxc_k_measure, cxc_grid(V.nt), dim3(256), 0, st, V.tri, V.pts, (const int32_t*)C->tlab, V.nt, V.nv, M, C->acc);
-            hipLaunchKernelGGL(cxc_k_vertex_count, cxc_grid(V.nv), dim3(256), 0, st, (const int32_t*)C->vlab, V.nv, nc, C->acc);
+            hipLaunchKernelGGL(cxc_k_measure, cxc_grid(V.nt), dim3(256), 0, st, V.tri, V.pts, C->tlab.as<const int32_t>(), V.nt, V.nv, M, C->acc);
+            hipLaunchKernelGGL(cxc_k_vertex_count, cxc_grid(V.nv), dim3(256), 0, st, C->vlab.as<const int32_t>(), V.nv, nc, C->acc);
             hipLaunchKernelGGL(cxc_k_finish, cxc_grid(nc), dim3(256), 0, st, (const u64*)C->acc, (const uint32_t*)C->first, V.cflip, nc, M, qa, qv, qm, C->table);
             CXC_HIP(ctx, hipGetLastError());
         }
@@ -506,8 +502,8 @@ extern "C" int cx_level1_component_labels(cx_ctx* ctx, void** tri_labels_dev, vo
     cx_comp_state* C = nullptr;
     const int rc = cxc_labels(ctx, "cx_level1_component_labels", &V, &C);
     if (rc) return rc;
-    if (tri_labels_dev) *tri_labels_dev = V.nt ? (void*)C->tlab : nullptr;
-    if (vert_labels_dev) *vert_labels_dev = V.nv ? (void*)C->vlab : nullptr;
+    if (tri_labels_dev) *tri_labels_dev = V.nt ? C->tlab.get() : nullptr;
+    if (vert_labels_dev) *vert_labels_dev = V.nv ? C->vlab.get() : nullptr;
     return CX_OK;
 }
 
@@ -537,15 +533,15 @@ extern "C" int cx_level1_keep_components(cx_ctx* ctx, const uint8_t* keep, int64
         hipStream_t st = ctx->stream;
         cx_level1_comp_scratch X;
         if ((rc = cx_level1_comp_scratch_get(ctx, &X))) return rc;
-        if ((rc = cx_grow(ctx, C->keep, C->keep_cap, (size_t)nc + 16))) return rc;
-        if ((rc = cx_grow(ctx, C->tnew, C->tnew_cap, (size_t)nt + 16))) return rc;
-        if ((rc = cx_grow(ctx, C->vuse, C->vuse_cap, (size_t)nv + 16))) return rc;
-        if ((rc = cx_grow(ctx, C->vnew, C->vnew_cap, (size_t)nv + 16))) return rc;
-        if ((rc = cx_grow(ctx, C->sums, C->sums_cap, (size_t)std::max(nt, nv) / 1024 + 16))) return rc;
+        if ((rc = C->keep.grow(ctx, (size_t)nc + 16))) return rc;
+        if ((rc = C->tnew.grow(ctx, (size_t)nt + 16))) return rc;
+        if ((rc = C->vuse.grow(ctx, (size_t)nv + 16))) return rc;
+        if ((rc = C->vnew.grow(ctx, (size_t)nv + 16))) return rc;
+        if ((rc = C->sums.grow(ctx, (size_t)std::max(nt, nv) / 1024 + 16))) return rc;
         uint32_t* tflag = C->tidx;     // (the scan of the root flags has done its work once the labels stand)
         CXC_HIP(ctx, hipMemcpyAsync(C->keep, keep, nc, hipMemcpyHostToDevice, st));
         CXC_HIP(ctx, hipMemsetAsync(C->vuse, 0, (size_t)nv * sizeof(uint32_t), st));
-        hipLaunchKernelGGL(cxc_k_keep_flags, cxc_grid(nt), dim3(256), 0, st, (const int32_t*)C->tlab, (const uint8_t*)C->keep, V.tri, nt, nv, tflag, C->vuse);
+        hipLaunchKernelGGL(cxc_k_keep_flags, cxc_grid(nt), dim3(256), 0, st, C->tlab.as<const int32_t>(), C->keep.get(), V.tri, nt, nv, tflag, C->vuse);
         if ((rc = cx_scan_u32(ctx, tflag, C->tnew, nt, C->sums, C->misc + 1))) return rc;
         if ((rc = cx_scan_u32(ctx, C->vuse, C->vnew, nv, C->sums, C->misc + 2))) return rc;
         uint32_t h[2] = {0, 0};

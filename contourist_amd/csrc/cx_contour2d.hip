@@ -35,41 +35,22 @@
 #define C2_NIL 0xFFFFFFFFu
 typedef unsigned long long c2_u64;
 
-struct c2_buf {
-    void* p = nullptr;
-    size_t cap = 0;
-};
 struct cx_state2 {
-    c2_buf grid, values, cnt, base, sums, pts, keys, succ, pred, parent, mark, rmark, rep, rank, cyc, jst[2], alist, len, hflag, cidx,
+    cx_buf<uint8_t> grid, values, cnt, base, sums, pts, keys, succ, pred, parent, mark, rmark, rep, rank, cyc, jst[2], alist, len, hflag, cidx,
         chead, clen, coff, opts, okeys, ochain, keep, fidx, fpts, fkeys, chains, scal, seeds;
     cx_counts2d counts = {0, 0, 0, 0};
     bool valid = false;
 };
 
-static int c2_reserve(cx_ctx* ctx, c2_buf& b, size_t bytes) {
-    if (bytes <= b.cap && b.p) return CX_OK;
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    const size_t want = bytes + bytes / 8 + 256;
-    hipError_t e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
-        ctx->err = std::string("hipMalloc(2-D contour buffers): ") + hipGetErrorString(e);
-        b.p = nullptr;
-        return CX_ERR_NOMEM;
-    }
-    b.cap = want;
-    return CX_OK;
+// Room for `bytes` in a buffer of the 2-D path.  Its slack policy: an eighth more and 256 bytes, so that a slightly larger grid or
+// a few more levels reuse the buffers.
+static int c2_room(cx_ctx* ctx, cx_buf<uint8_t>& b, size_t bytes) {
+    if (bytes <= b.cap() && b) return CX_OK;
+    return b.grow(ctx, bytes + bytes / 8 + 256);
 }
 void cx_state2_free(cx_ctx* ctx) {
     if (!ctx->s2) return;
     cx_state2* S = ctx->s2;
-    c2_buf* all[] = {&S->grid, &S->values, &S->cnt, &S->base, &S->sums, &S->pts, &S->keys, &S->succ, &S->pred, &S->parent,
-                     &S->mark, &S->rmark, &S->rep, &S->rank, &S->cyc, &S->jst[0], &S->jst[1], &S->alist, &S->len, &S->hflag, &S->cidx, &S->chead,
-                     &S->clen, &S->coff, &S->opts, &S->okeys, &S->ochain, &S->keep, &S->fidx, &S->fpts, &S->fkeys, &S->chains, &S->scal,
-                     &S->seeds};
-    for (c2_buf* b : all)
-        if (b->p) (void)hipFree(b->p);
     delete S;
     ctx->s2 = nullptr;
 }
@@ -554,25 +535,25 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
     int rc;
     const float* A = samples;
     if (!on_device) {
-        if ((rc = c2_reserve(ctx, S->grid, N * sizeof(float)))) return rc;
-        C2_HIP(ctx, hipMemcpyAsync(S->grid.p, samples, N * sizeof(float), hipMemcpyHostToDevice, st));
-        A = (const float*)S->grid.p;
+        if ((rc = c2_room(ctx, S->grid, N * sizeof(float)))) return rc;
+        C2_HIP(ctx, hipMemcpyAsync(S->grid.get(), samples, N * sizeof(float), hipMemcpyHostToDevice, st));
+        A = S->grid.as<const float>();
     }
-    if ((rc = c2_reserve(ctx, S->values, (size_t)nvalues * sizeof(double)))) return rc;
-    C2_HIP(ctx, hipMemcpyAsync(S->values.p, values, (size_t)nvalues * sizeof(double), hipMemcpyHostToDevice, st));
+    if ((rc = c2_room(ctx, S->values, (size_t)nvalues * sizeof(double)))) return rc;
+    C2_HIP(ctx, hipMemcpyAsync(S->values.get(), values, (size_t)nvalues * sizeof(double), hipMemcpyHostToDevice, st));
     double scal_host[4] = {0.0, 0.0, 1.0, 1.0};
     if (mins_delta) memcpy(scal_host, mins_delta, sizeof(scal_host));
-    if ((rc = c2_reserve(ctx, S->scal, 64))) return rc;
-    C2_HIP(ctx, hipMemcpyAsync(S->scal.p, scal_host, sizeof(scal_host), hipMemcpyHostToDevice, st));
-    uint32_t* scratch = (uint32_t*)((char*)S->scal.p + 32);   // [0] scan total, [1] changed flag, [2] tie flag, [4..5] 64-bit total
+    if ((rc = c2_room(ctx, S->scal, 64))) return rc;
+    C2_HIP(ctx, hipMemcpyAsync(S->scal.get(), scal_host, sizeof(scal_host), hipMemcpyHostToDevice, st));
+    uint32_t* scratch = (uint32_t*)(S->scal.as<char>() + 32);   // [0] scan total, [1] changed flag, [2] tie flag, [4..5] 64-bit total
     C2_HIP(ctx, hipMemsetAsync(scratch, 0, 24, st));
     const size_t E = 3 * N;
-    if ((rc = c2_reserve(ctx, S->cnt, E * 4)) || (rc = c2_reserve(ctx, S->base, (E + 1) * 4)) || (rc = c2_reserve(ctx, S->sums, (E / 1024 + 4) * 4)))
+    if ((rc = c2_room(ctx, S->cnt, E * 4)) || (rc = c2_room(ctx, S->base, (E + 1) * 4)) || (rc = c2_room(ctx, S->sums, (E / 1024 + 4) * 4)))
         return rc;
-    c2_grid G{A, (uint32_t)n, (uint32_t)m, (const double*)S->values.p, (uint32_t)nvalues, (const uint32_t*)S->base.p};
-    hipLaunchKernelGGL(c2_k_count, dim3(c2_blocks(N)), dim3(256), 0, st, G, (uint32_t*)S->cnt.p, scratch + 2);
+    c2_grid G{A, (uint32_t)n, (uint32_t)m, S->values.as<const double>(), (uint32_t)nvalues, S->base.as<const uint32_t>()};
+    hipLaunchKernelGGL(c2_k_count, dim3(c2_blocks(N)), dim3(256), 0, st, G, S->cnt.as<uint32_t>(), scratch + 2);
     // (the scan also returns the total in 64 bits: a 32-bit total cannot show an overflow)
-    cx_scan_u32(ctx, (const uint32_t*)S->cnt.p, (uint32_t*)S->base.p, (uint32_t)E, (uint32_t*)S->sums.p, scratch, (unsigned long long*)(scratch + 4));
+    cx_scan_u32(ctx, S->cnt.as<const uint32_t>(), S->base.as<uint32_t>(), (uint32_t)E, S->sums.as<uint32_t>(), scratch, (unsigned long long*)(scratch + 4));
     uint32_t head6[6] = {0, 0, 0, 0, 0, 0};
     C2_HIP(ctx, hipMemcpyAsync(head6, scratch, 24, hipMemcpyDeviceToHost, st));
     C2_HIP(ctx, hipStreamSynchronize(st));
@@ -590,26 +571,26 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
         return CX_OK;
     }
     const size_t V = nv;
-    c2_buf* u32s[] = {&S->succ, &S->pred, &S->parent, &S->mark, &S->rmark, &S->rep, &S->rank, &S->cyc, &S->len, &S->hflag, &S->cidx, &S->ochain, &S->keep,
+    cx_buf<uint8_t>* u32s[] = {&S->succ, &S->pred, &S->parent, &S->mark, &S->rmark, &S->rep, &S->rank, &S->cyc, &S->len, &S->hflag, &S->cidx, &S->ochain, &S->keep,
                       &S->fidx};
-    for (c2_buf* b : u32s)
-        if ((rc = c2_reserve(ctx, *b, (V + 1) * 4))) return rc;
-    if ((rc = c2_reserve(ctx, S->pts, V * 16)) || (rc = c2_reserve(ctx, S->keys, V * 8)) || (rc = c2_reserve(ctx, S->opts, V * 16)) ||
-        (rc = c2_reserve(ctx, S->okeys, V * 8)) || (rc = c2_reserve(ctx, S->fpts, V * 16)) || (rc = c2_reserve(ctx, S->fkeys, V * 8)))
+    for (cx_buf<uint8_t>* b : u32s)
+        if ((rc = c2_room(ctx, *b, (V + 1) * 4))) return rc;
+    if ((rc = c2_room(ctx, S->pts, V * 16)) || (rc = c2_room(ctx, S->keys, V * 8)) || (rc = c2_room(ctx, S->opts, V * 16)) ||
+        (rc = c2_room(ctx, S->okeys, V * 8)) || (rc = c2_room(ctx, S->fpts, V * 16)) || (rc = c2_room(ctx, S->fkeys, V * 8)))
         return rc;
-    if (S->sums.cap < (V / 1024 + 4) * 4 && (rc = c2_reserve(ctx, S->sums, (V / 1024 + 4) * 4))) return rc;
-    double2* pts = (double2*)S->pts.p;
-    c2_u64* keys = (c2_u64*)S->keys.p;
-    uint32_t *succ = (uint32_t*)S->succ.p, *pred = (uint32_t*)S->pred.p, *parent = (uint32_t*)S->parent.p, *rep = (uint32_t*)S->rep.p;
-    uint32_t *mark = (uint32_t*)S->mark.p, *rmark = (uint32_t*)S->rmark.p, *rank = (uint32_t*)S->rank.p, *cyc = (uint32_t*)S->cyc.p, *len = (uint32_t*)S->len.p;
-    uint32_t *hflag = (uint32_t*)S->hflag.p, *cidx = (uint32_t*)S->cidx.p;
+    if (S->sums.cap() < (V / 1024 + 4) * 4 && (rc = c2_room(ctx, S->sums, (V / 1024 + 4) * 4))) return rc;
+    double2* pts = S->pts.as<double2>();
+    c2_u64* keys = S->keys.as<c2_u64>();
+    uint32_t *succ = S->succ.as<uint32_t>(), *pred = S->pred.as<uint32_t>(), *parent = S->parent.as<uint32_t>(), *rep = S->rep.as<uint32_t>();
+    uint32_t *mark = S->mark.as<uint32_t>(), *rmark = S->rmark.as<uint32_t>(), *rank = S->rank.as<uint32_t>(), *cyc = S->cyc.as<uint32_t>(), *len = S->len.as<uint32_t>();
+    uint32_t *hflag = S->hflag.as<uint32_t>(), *cidx = S->cidx.as<uint32_t>();
     const uint32_t gb = c2_blocks(V);
-    hipLaunchKernelGGL(c2_k_emit, dim3((uint32_t)((E + C2_EPB - 1) / C2_EPB)), dim3(256), 0, st, G, (const uint32_t*)S->cnt.p, pts, keys, succ, pred);
+    hipLaunchKernelGGL(c2_k_emit, dim3((uint32_t)((E + C2_EPB - 1) / C2_EPB)), dim3(256), 0, st, G, S->cnt.as<const uint32_t>(), pts, keys, succ, pred);
     const int all = (flags & CX2_ALL_CHAINS) ? 1 : 0;
     // chains: first element, rank, length
-    if ((rc = c2_reserve(ctx, S->jst[0], V * 16)) || (rc = c2_reserve(ctx, S->jst[1], V * 16))) return rc;
+    if ((rc = c2_room(ctx, S->jst[0], V * 16)) || (rc = c2_room(ctx, S->jst[1], V * 16))) return rc;
     int cur = 0;
-    hipLaunchKernelGGL(c2_k_jump_init, dim3(gb), dim3(256), 0, st, pred, nv, (uint4*)S->jst[0].p);
+    hipLaunchKernelGGL(c2_k_jump_init, dim3(gb), dim3(256), 0, st, pred, nv, S->jst[0].as<uint4>());
     uint32_t nlist = 0;           // 0: rounds over all elements
     const uint32_t* list = nullptr;
     for (int round = 0;; round++) {
@@ -619,10 +600,10 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
         }
         C2_HIP(ctx, hipMemsetAsync(scratch + 1, 0, 4, st));
         if (nlist)
-            hipLaunchKernelGGL(c2_k_jump_listed, dim3(c2_blocks(nlist)), dim3(256), 0, st, (const uint4*)S->jst[cur].p, (uint4*)S->jst[1 - cur].p, list,
+            hipLaunchKernelGGL(c2_k_jump_listed, dim3(c2_blocks(nlist)), dim3(256), 0, st, S->jst[cur].as<const uint4>(), S->jst[1 - cur].as<uint4>(), list,
                                nlist, scratch + 1);
         else
-            hipLaunchKernelGGL(c2_k_jump, dim3(gb), dim3(256), 0, st, (const uint4*)S->jst[cur].p, (uint4*)S->jst[1 - cur].p, nv, scratch + 1);
+            hipLaunchKernelGGL(c2_k_jump, dim3(gb), dim3(256), 0, st, S->jst[cur].as<const uint4>(), S->jst[1 - cur].as<uint4>(), nv, scratch + 1);
         cur = 1 - cur;
         uint32_t changed = 0;
         C2_HIP(ctx, hipMemcpyAsync(&changed, scratch + 1, 4, hipMemcpyDeviceToHost, st));
@@ -631,17 +612,17 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
         if (round == C2_FULL_ROUNDS && nv > (1u << 20)) {
             // the list of elements that were unfinished BEFORE this round (buffer 1 - cur): whatever finished earlier has
             // just been copied, i.e. is the same in both buffers, and can be left alone from now on
-            if ((rc = c2_reserve(ctx, S->alist, V * 4))) return rc;
-            hipLaunchKernelGGL(c2_k_jump_flags, dim3(gb), dim3(256), 0, st, (const uint4*)S->jst[1 - cur].p, nv, hflag);
-            cx_scan_u32(ctx, hflag, cidx, nv, (uint32_t*)S->sums.p, scratch);
-            hipLaunchKernelGGL(c2_k_jump_list, dim3(gb), dim3(256), 0, st, hflag, cidx, nv, (uint32_t*)S->alist.p);
+            if ((rc = c2_room(ctx, S->alist, V * 4))) return rc;
+            hipLaunchKernelGGL(c2_k_jump_flags, dim3(gb), dim3(256), 0, st, S->jst[1 - cur].as<const uint4>(), nv, hflag);
+            cx_scan_u32(ctx, hflag, cidx, nv, S->sums.as<uint32_t>(), scratch);
+            hipLaunchKernelGGL(c2_k_jump_list, dim3(gb), dim3(256), 0, st, hflag, cidx, nv, S->alist.as<uint32_t>());
             C2_HIP(ctx, hipMemcpyAsync(&nlist, scratch, 4, hipMemcpyDeviceToHost, st));
             C2_HIP(ctx, hipStreamSynchronize(st));
-            list = (const uint32_t*)S->alist.p;
+            list = S->alist.as<const uint32_t>();
             if (nlist == 0) break;   // (cannot happen while `changed` is set; defensive)
         }
     }
-    hipLaunchKernelGGL(c2_k_chain_finish, dim3(gb), dim3(256), 0, st, (const uint4*)S->jst[cur].p, succ, nv, rep, rank, len, cyc, parent);
+    hipLaunchKernelGGL(c2_k_chain_finish, dim3(gb), dim3(256), 0, st, S->jst[cur].as<const uint4>(), succ, nv, rep, rank, len, cyc, parent);
     // growth groups of chains and their seeds
     if (!all) {
         const bool search = nseeds <= 0 || (flags & CX2_SEARCH_SEEDS);
@@ -650,15 +631,15 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
         hipLaunchKernelGGL(c2_k_group, dim3(gb), dim3(256), 0, st, G, keys, rep, nv, search ? 1 : 0, parent, mark);
         if (search && ties) hipLaunchKernelGGL(c2_k_seed_ties, dim3(c2_blocks(N)), dim3(256), 0, st, G, rep, mark);
         if (nseeds > 0) {
-            if ((rc = c2_reserve(ctx, S->seeds, (size_t)nseeds * 16))) return rc;
-            C2_HIP(ctx, hipMemcpyAsync(S->seeds.p, seeds, (size_t)nseeds * 16, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(c2_k_seed_points, dim3(c2_blocks((size_t)nseeds)), dim3(256), 0, st, G, (const int32_t*)S->seeds.p, (uint32_t)nseeds,
+            if ((rc = c2_room(ctx, S->seeds, (size_t)nseeds * 16))) return rc;
+            C2_HIP(ctx, hipMemcpyAsync(S->seeds.get(), seeds, (size_t)nseeds * 16, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(c2_k_seed_points, dim3(c2_blocks((size_t)nseeds)), dim3(256), 0, st, G, S->seeds.as<const int32_t>(), (uint32_t)nseeds,
                                rep, mark);
         }
         hipLaunchKernelGGL(c2_k_mark_roots, dim3(gb), dim3(256), 0, st, rep, mark, nv, parent, rmark);
     }
     hipLaunchKernelGGL(c2_k_head_flags, dim3(gb), dim3(256), 0, st, rep, parent, rmark, all, nv, hflag);
-    cx_scan_u32(ctx, hflag, cidx, nv, (uint32_t*)S->sums.p, scratch);
+    cx_scan_u32(ctx, hflag, cidx, nv, S->sums.as<uint32_t>(), scratch);
     uint32_t nchains = 0;
     C2_HIP(ctx, hipMemcpyAsync(&nchains, scratch, 4, hipMemcpyDeviceToHost, st));
     C2_HIP(ctx, hipStreamSynchronize(st));
@@ -667,12 +648,12 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
         if (out) *out = S->counts;
         return CX_OK;
     }
-    if ((rc = c2_reserve(ctx, S->chead, (size_t)nchains * 4)) || (rc = c2_reserve(ctx, S->clen, (size_t)nchains * 4)) ||
-        (rc = c2_reserve(ctx, S->coff, ((size_t)nchains + 1) * 4)) || (rc = c2_reserve(ctx, S->chains, (size_t)nchains * sizeof(cx_chain2d))))
+    if ((rc = c2_room(ctx, S->chead, (size_t)nchains * 4)) || (rc = c2_room(ctx, S->clen, (size_t)nchains * 4)) ||
+        (rc = c2_room(ctx, S->coff, ((size_t)nchains + 1) * 4)) || (rc = c2_room(ctx, S->chains, (size_t)nchains * sizeof(cx_chain2d))))
         return rc;
-    uint32_t *chead = (uint32_t*)S->chead.p, *clen = (uint32_t*)S->clen.p, *coff = (uint32_t*)S->coff.p;
+    uint32_t *chead = S->chead.as<uint32_t>(), *clen = S->clen.as<uint32_t>(), *coff = S->coff.as<uint32_t>();
     hipLaunchKernelGGL(c2_k_chain_table, dim3(gb), dim3(256), 0, st, hflag, cidx, len, nv, chead, clen);
-    cx_scan_u32(ctx, clen, coff, nchains, (uint32_t*)S->sums.p, scratch);
+    cx_scan_u32(ctx, clen, coff, nchains, S->sums.as<uint32_t>(), scratch);
     uint32_t nsel = 0;
     C2_HIP(ctx, hipMemcpyAsync(&nsel, scratch, 4, hipMemcpyDeviceToHost, st));
     C2_HIP(ctx, hipStreamSynchronize(st));
@@ -680,19 +661,19 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
         ctx->err = "cx_contour2d_extract: inconsistent chain lengths";
         return CX_ERR_HIP;
     }
-    double2* opts = (double2*)S->opts.p;
-    c2_u64* okeys = (c2_u64*)S->okeys.p;
-    uint32_t *ochain = (uint32_t*)S->ochain.p, *keep = (uint32_t*)S->keep.p, *fidx = (uint32_t*)S->fidx.p;
+    double2* opts = S->opts.as<double2>();
+    c2_u64* okeys = S->okeys.as<c2_u64>();
+    uint32_t *ochain = S->ochain.as<uint32_t>(), *keep = S->keep.as<uint32_t>(), *fidx = S->fidx.as<uint32_t>();
     hipLaunchKernelGGL(c2_k_place, dim3(gb), dim3(256), 0, st, pts, keys, rep, hflag, cidx, coff, rank, nv, opts, okeys, ochain);
     hipLaunchKernelGGL(c2_k_keep, dim3(c2_blocks(nsel)), dim3(256), 0, st, opts, ochain, coff, nsel, (flags & CX2_NO_DEDUPE) ? 0 : 1, keep);
-    cx_scan_u32(ctx, keep, fidx, nsel, (uint32_t*)S->sums.p, scratch);
+    cx_scan_u32(ctx, keep, fidx, nsel, S->sums.as<uint32_t>(), scratch);
     uint32_t nfinal = 0;
     C2_HIP(ctx, hipMemcpyAsync(&nfinal, scratch, 4, hipMemcpyDeviceToHost, st));
     C2_HIP(ctx, hipStreamSynchronize(st));
-    hipLaunchKernelGGL(c2_k_final_points, dim3(c2_blocks(nsel)), dim3(256), 0, st, opts, okeys, keep, fidx, nsel, (const double*)S->scal.p,
-                       (double2*)S->fpts.p, (c2_u64*)S->fkeys.p);
+    hipLaunchKernelGGL(c2_k_final_points, dim3(c2_blocks(nsel)), dim3(256), 0, st, opts, okeys, keep, fidx, nsel, S->scal.as<const double>(),
+                       S->fpts.as<double2>(), S->fkeys.as<c2_u64>());
     hipLaunchKernelGGL(c2_k_final_chains, dim3(c2_blocks(nchains)), dim3(256), 0, st, opts, okeys, keep, fidx, coff, clen, chead, cyc, nchains, nfinal,
-                       (cx_chain2d*)S->chains.p);
+                       S->chains.as<cx_chain2d>());
     C2_HIP(ctx, hipGetLastError());
     C2_HIP(ctx, hipStreamSynchronize(st));
     S->counts = cx_counts2d{nfinal, nchains, nv, (uint32_t)nvalues};
@@ -711,9 +692,9 @@ extern "C" int cx_contour2d_download(cx_ctx* ctx, double* points_xy, int64_t* ke
     }
     C2_HIP(ctx, hipSetDevice(ctx->device));
     const size_t np = S->counts.n_points, nc = S->counts.n_chains;
-    if (points_xy && np) C2_HIP(ctx, hipMemcpyAsync(points_xy, S->fpts.p, np * 16, hipMemcpyDeviceToHost, ctx->stream));
-    if (keys && np) C2_HIP(ctx, hipMemcpyAsync(keys, S->fkeys.p, np * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (chains && nc) C2_HIP(ctx, hipMemcpyAsync(chains, S->chains.p, nc * sizeof(cx_chain2d), hipMemcpyDeviceToHost, ctx->stream));
+    if (points_xy && np) C2_HIP(ctx, hipMemcpyAsync(points_xy, S->fpts.get(), np * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (keys && np) C2_HIP(ctx, hipMemcpyAsync(keys, S->fkeys.get(), np * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (chains && nc) C2_HIP(ctx, hipMemcpyAsync(chains, S->chains.get(), nc * sizeof(cx_chain2d), hipMemcpyDeviceToHost, ctx->stream));
     C2_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CX_OK;
 }

@@ -1,6 +1,9 @@
 // cx_ctx.h -- the context object behind the C ABI (host side only).
 #pragma once
+#include <atomic>
 #include <string>
+#include <type_traits>
+#include <utility>
 
 #include "cx_common.h"
 
@@ -8,67 +11,96 @@ struct cx_post_state;  // Level-1 buffers (cx_post.hip)
 struct cx_state4;       // 4-D march state (cx_api4d.hip)
 struct cx_state2;       // 2-D contour lines (cx_contour2d.hip)
 struct cx_levels_state; // several isovalues of one grid (cx_levels.hip)
+struct cx_ctx;
+
+// Device memory in use by one context (cx_ctx::tally) and by the whole process (cx_process_tally): bytes held by cx_bufs now and
+// hipMalloc calls made so far.  Read through cx_device_bytes.
+struct cx_tally { int64_t live_bytes = 0, allocations = 0; };
+struct cx_process_tally_t { std::atomic<int64_t> live_bytes{0}, allocations{0}; };
+inline cx_process_tally_t cx_process_tally;
+
+// The one owner of growable device memory.  Capacity in elements of T.  Reads as a T* wherever a
+// pointer is handed on; pointers taken from it are dead after the next grow.  Never give one static storage duration: its hipFree
+// would run after the runtime has gone.
+template <typename T>
+class cx_buf {
+public:
+    cx_buf() = default;
+    cx_buf(const cx_buf&) = delete;
+    cx_buf& operator=(const cx_buf&) = delete;
+    cx_buf(cx_buf&& o) noexcept : p_(o.p_), cap_(o.cap_), tally_(o.tally_) { o.p_ = nullptr; o.cap_ = 0; }
+    cx_buf& operator=(cx_buf&& o) noexcept {
+        if (this != &o) { release(); p_ = o.p_; cap_ = o.cap_; tally_ = o.tally_; o.p_ = nullptr; o.cap_ = 0; }
+        return *this;
+    }
+    ~cx_buf() { release(); }
+
+    operator T*() const { return p_; }
+    T* get() const { return p_; }
+    size_t cap() const { return cap_; }
+    size_t bytes() const { return cap_ * sizeof(T); }
+    template <typename U> U* as() const { return reinterpret_cast<U*>(p_); }   // a byte buffer read as another type
+
+    int grow(cx_ctx* ctx, size_t need);
+    int grow_keep(cx_ctx* ctx, size_t used, size_t need);
+    void release() {
+        if (p_) (void)hipFree(p_);
+        forget();
+    }
+
+private:
+    hipError_t alloc(cx_ctx* ctx, size_t n);
+    static int fail(cx_ctx* ctx, size_t bytes, hipError_t e);
+    void forget() {
+        if (p_) { tally_->live_bytes -= (int64_t)bytes(); cx_process_tally.live_bytes -= (int64_t)bytes(); }
+        p_ = nullptr; cap_ = 0;
+    }
+    T* p_ = nullptr;
+    size_t cap_ = 0;
+    cx_tally* tally_ = nullptr;   // of the context that allocated p_ (outlives its buffers)
+};
+static_assert(!std::is_copy_constructible<cx_buf<uint8_t>>::value && !std::is_copy_assignable<cx_buf<uint8_t>>::value, "cx_buf owns its memory");
+static_assert(std::is_nothrow_move_constructible<cx_buf<uint8_t>>::value && std::is_nothrow_move_assignable<cx_buf<uint8_t>>::value, "cx_buf moves");
 
 struct cx_ctx {
+    cx_tally tally;                 // first: the buffers below count themselves out of it when the context goes
     int device = 0;
     hipStream_t stream = nullptr;      // stream in use
     hipStream_t own_stream = nullptr;  // stream created by the context
     std::string err;
     // sampled field
     cx_grid_ref grid = {nullptr, CX_DTYPE_F32};
-    uint8_t* grid_owned = nullptr;     // the uploaded samples, any type (bytes)
-    size_t grid_owned_bytes = 0;
+    cx_buf<uint8_t> grid_owned;     // the uploaded samples, any type (bytes)
     int64_t n0 = 0, n1 = 0, n2 = 0;
-    double* grid64 = nullptr;          // float64 originals of the samples (cx_grid_shadow_f64): Level 1 interpolates on these
-    size_t grid64_cap = 0;
+    cx_buf<double> grid64;          // float64 originals of the samples (cx_grid_shadow_f64): Level 1 interpolates on these
     bool grid64_valid = false;
     // side tables of the march
-    uint64_t* celltab = nullptr;
-    size_t tables_for = 0;
-    uint32_t* queue = nullptr;         // staged pipeline: per-wave queues, totals and offsets
-    size_t queue_cap = 0;
-    cx_wsum* wsum = nullptr;
-    size_t wsum_cap = 0;
-    cx_wbase* wbase = nullptr;
-    size_t wbase_cap = 0;
-    cx_brec* brec = nullptr;
-    size_t brec_cap = 0;
-    cx_bdesc* flat = nullptr;
-    size_t flat_cap = 0;
-    uint32_t* qa = nullptr;            // fused emit: queue positions / active cells per plane step and lane of the streaming waves
-    size_t qa_cap = 0;
-    uint32_t* info = nullptr;          // fused emit: per queue entry, first vertex of the cell in its wave | crossing mask
-    size_t info_cap = 0;
-    float* tq = nullptr;               // staged kernels: the stream kernel's interpolation fractions, one region per streaming wave (cx_params::tq)
-    size_t tq_cap = 0;
-    uint64_t* info64 = nullptr;        // staged kernels: per queue entry, (crossing mask << 32) | first vertex
-    size_t info64_cap = 0;
-    uint32_t* chunksum = nullptr;      // totals of every 256 streaming waves (cx_params::chunksum)
-    size_t chunksum_cap = 0;
-    uint32_t* rstart = nullptr;        // vertex stage: first batch of every wave's share of the rounds (cx_params::rstart)
-    size_t rstart_cap = 0;
-    uint32_t* kstart = nullptr;        // the same for the triangle stage (cx_params::kstart)
-    size_t kstart_cap = 0;
-    uint64_t* fj = nullptr;            // tile emit path: face words (cx_params::fj, fk), boundary records and their counts per tile
-    size_t fj_cap = 0;
-    uint64_t* fk = nullptr;
-    size_t fk_cap = 0;
-    uint4* bnd = nullptr;
-    size_t bnd_cap = 0;
-    uint32_t* bndn = nullptr;
-    size_t bndn_cap = 0;
-    uint32_t* torder = nullptr;
-    size_t torder_cap = 0;
-    uint8_t* hbytes = nullptr;         // fused emit: CPython set-order code per lattice point (valid for hash_xy's shape and origin)
-    size_t hbytes_cap = 0;
+    cx_buf<uint64_t> celltab;
+    cx_buf<uint32_t> queue;         // staged pipeline: per-wave queues, totals and offsets
+    cx_buf<cx_wsum> wsum;
+    cx_buf<cx_wbase> wbase;
+    cx_buf<cx_brec> brec;
+    cx_buf<cx_bdesc> flat;
+    cx_buf<uint32_t> qa;            // fused emit: queue positions / active cells per plane step and lane of the streaming waves
+    cx_buf<uint32_t> info;          // fused emit: per queue entry, first vertex of the cell in its wave | crossing mask
+    cx_buf<float> tq;               // staged kernels: the stream kernel's interpolation fractions, one region per streaming wave (cx_params::tq)
+    cx_buf<uint64_t> info64;        // staged kernels: per queue entry, (crossing mask << 32) | first vertex
+    cx_buf<uint32_t> chunksum;      // totals of every 256 streaming waves (cx_params::chunksum)
+    cx_buf<uint32_t> rstart;        // vertex stage: first batch of every wave's share of the rounds (cx_params::rstart)
+    cx_buf<uint32_t> kstart;        // the same for the triangle stage (cx_params::kstart)
+    cx_buf<uint64_t> fj;            // tile emit path: face words (cx_params::fj, fk), boundary records and their counts per tile
+    cx_buf<uint64_t> fk;
+    cx_buf<uint4> bnd;
+    cx_buf<uint32_t> bndn;
+    cx_buf<uint32_t> torder;
+    cx_buf<uint8_t> hbytes;         // fused emit: CPython set-order code per lattice point (valid for hash_xy's shape and origin)
     bool hbytes_valid = false;
     int64_t hbytes_n2 = 0, hbytes_o2 = 0;
     cx_task last_task = {};
     uint32_t last_flags = 0;
     int path = 0;                      // kernels of the last extraction: 0 generic, 1 staged, 2 fused, 3 tile emit
     bool records_valid = false;        // ctx->cells holds the cell records of the last extraction
-    uint64_t* hash_xy = nullptr;       // CPython tuple-hash prefix per (i,j), for CX_DIAG_CPYTHON310
-    size_t hash_xy_cap = 0;
+    cx_buf<uint64_t> hash_xy;       // CPython tuple-hash prefix per (i,j), for CX_DIAG_CPYTHON310
     int64_t hash_xy_n0 = 0, hash_xy_n1 = 0, hash_xy_o0 = -1, hash_xy_o1 = -1;
     int64_t origin[3] = {0, 0, 0};
     int64_t corner_ref[3] = {0, 0, 0};   // > 0: the reference's corner for the Level-1 scales (cx_set_reference_corner)
@@ -78,41 +110,35 @@ struct cx_ctx {
     cx_levels_state* lv = nullptr;
     int lv_current = -1;               // level of cx_extract3d_levels whose mesh the context's output buffers hold (-1: none)
     // Level-0 outputs
-    cx_vrec* verts = nullptr;          // 8-byte vertex records {edge id, fp32 fraction}
-    float4* verts_xyz = nullptr;       // {x, y, z, bits(edge id)} expanded from the records on request (cx_level0_expanded)
-    size_t verts_xyz_cap = 0;
-    uint4* cells = nullptr;
-    int32_t* tris = nullptr;
-    uint32_t vcap = 0, ccap = 0, tcap = 0;
-    uint32_t* counters = nullptr;
+    cx_buf<cx_vrec> verts;          // 8-byte vertex records {edge id, fp32 fraction}
+    cx_buf<float4> verts_xyz;       // {x, y, z, bits(edge id)} expanded from the records on request (cx_level0_expanded)
+    cx_buf<uint4> cells;
+    cx_buf<int32_t> tris;           // three per triangle
+    // the capacities as the kernels and the ABI count them (cx_params, cx_counts)
+    uint32_t vcap() const { return (uint32_t)verts.cap(); }
+    uint32_t ccap() const { return (uint32_t)cells.cap(); }
+    uint32_t tcap() const { return (uint32_t)(tris.cap() / 3u); }
+    cx_buf<uint32_t> counters;
     uint32_t* counters_host = nullptr;
     bool extracted = false;
     bool counts_fetched = false;       // ctx->counts holds the counters of the last 3-D extraction (cx_counts_get)
     cx_counts counts = {0, 0, 0, 0};
     cx_params last;
     // seeded selection (cx_select_seeded3d): triangle mask followed by vertex mask, valid until the next extraction
-    uint8_t* tri_keep = nullptr;
-    size_t keep_cap = 0;
+    cx_buf<uint8_t> tri_keep;
     // scratch of cx_select_seeded3d_ex (bytes), kept between calls: map per sample, union-find, bitmap, flags, seeds, counters, end
     // points, visited set -- a selection allocated and freed them every time (0.8 of 2.9 ms on the 512^3 bench field)
-    uint8_t* seed_buf[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t seed_cap[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    cx_buf<uint8_t> seed_buf[8];
     int seed_mode = 0;      // how the last seeded selection (3-D or 4-D) ran its end points: 0 sequential (the reference's shared visited set), 1 one thread per pair
     bool keep_valid = false;
     // vertex attributes (cx_attr.hip), kept between calls: Level-0 normals float4 {nx, ny, nz, |g|}, Level-1 normals double[3], sampled
     // values (fp32 at Level 0, float64 at Level 1) and the device copy of a second grid handed over from the host
-    float4* attr_n0 = nullptr;
-    size_t attr_n0_cap = 0;
-    double* attr_n1 = nullptr;
-    size_t attr_n1_cap = 0;
-    float* attr_v0 = nullptr;
-    size_t attr_v0_cap = 0;
-    double* attr_v1 = nullptr;
-    size_t attr_v1_cap = 0;
-    uint8_t* attr_e1 = nullptr;        // Level 1: per output vertex {sample index of the low point, of the high point, ratio} (16 bytes)
-    size_t attr_e1_cap = 0;
-    uint8_t* attr_grid = nullptr;
-    size_t attr_grid_cap = 0;
+    cx_buf<float4> attr_n0;
+    cx_buf<double> attr_n1;
+    cx_buf<float> attr_v0;
+    cx_buf<double> attr_v1;
+    cx_buf<uint8_t> attr_e1;        // Level 1: per output vertex {sample index of the low point, of the high point, ratio} (16 bytes)
+    cx_buf<uint8_t> attr_grid;
     // components of the Level-1 mesh (cx_comp.hip): labels, accumulators and the table, kept between calls
     struct cx_comp_state* comp = nullptr;
     // vertex clustering of the Level-1 mesh (cx_simplify.hip): cluster table, accumulators, scans, kept between calls
@@ -120,8 +146,7 @@ struct cx_ctx {
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
-    unsigned long long* stamps = nullptr;   // diagnostic stamps (cx_debug_stamps)
-    size_t stamps_words = 0;
+    cx_buf<unsigned long long> stamps;   // diagnostic stamps (cx_debug_stamps)
     // the context's own RCCL communicator (cx_rccl_comm_init, cx_halo.hip), or null
     void* rccl_comm = nullptr;
     bool rccl_owned = true;              // false: the communicator belongs to another context of this rank (cx_rccl_comm_share)
@@ -136,54 +161,49 @@ struct cx_ctx {
     evset events[256];
 };
 
-// THE place where a device buffer of a context is freed and allocated again.  A buffer is a (pointer, capacity) pair that always
-// travels together through this function: a regrow branch cannot free a neighbour's pointer or leave a capacity describing a
-// buffer that is gone (rounds 1 and 2 each had a stray hipFree in a hand-written regrow block).  Waits for the context's stream
-// first (kernels enqueued on it may still use the old buffer).  `need` in elements; grows to exactly `need`.
-template <typename T, typename C>
-int cx_grow(cx_ctx* ctx, T*& ptr, C& cap, size_t need) {
-    if ((size_t)cap >= need && ptr) return CX_OK;
+template <typename T>
+int cx_buf<T>::fail(cx_ctx* ctx, size_t bytes, hipError_t e) {
+    ctx->err = std::string("device buffer (") + std::to_string(bytes) + " bytes): " + hipGetErrorString(e);
+    return (e == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;
+}
+template <typename T>
+hipError_t cx_buf<T>::alloc(cx_ctx* ctx, size_t n) {
+    void* fresh = nullptr;
+    const hipError_t e = hipMalloc(&fresh, n * sizeof(T));
+    if (e != hipSuccess) return e;
+    p_ = static_cast<T*>(fresh); cap_ = n; tally_ = &ctx->tally;
+    tally_->live_bytes += (int64_t)bytes(); tally_->allocations++;
+    cx_process_tally.live_bytes += (int64_t)bytes(); cx_process_tally.allocations++;
+    return hipSuccess;
+}
+// Room for `need` elements, contents not kept: waits for the context's stream first (kernels enqueued on it may still use the old
+// buffer), frees, allocates exactly `need`.
+template <typename T>
+int cx_buf<T>::grow(cx_ctx* ctx, size_t need) {
+    if (cap_ >= need && p_) return CX_OK;
     if (need == 0) return CX_OK;
     hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && ptr) e = hipFree(ptr);
-    ptr = nullptr; cap = 0;
-    void* fresh = nullptr;
-    if (e == hipSuccess) e = hipMalloc(&fresh, need * sizeof(T));
-    if (e != hipSuccess) {
-        ctx->err = std::string("device buffer (") + std::to_string(need * sizeof(T)) + " bytes): " + hipGetErrorString(e);
-        return (e == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;
-    }
-    ptr = static_cast<T*>(fresh);
-    cap = (C)need;
-    return CX_OK;
+    if (e == hipSuccess && p_) e = hipFree(p_);
+    forget();
+    if (e == hipSuccess) e = alloc(ctx, need);
+    return e == hipSuccess ? CX_OK : fail(ctx, need * sizeof(T), e);
 }
 // The same for a buffer that is appended to (the slab assembly of cx_slab4d.hip): the first `used` elements move into the new buffer,
 // which gets room for half as many again as before when that is more than `need` (a volume of many slabs grows it a few times, not
-// once per slab).  Pointers into the old buffer are dead after the call: kernels get pointers taken after the last grow.
+// once per slab).
 template <typename T>
-int cx_grow_keep(cx_ctx* ctx, T*& ptr, size_t& cap, size_t used, size_t need) {
-    if (cap >= need && ptr) return CX_OK;
+int cx_buf<T>::grow_keep(cx_ctx* ctx, size_t used, size_t need) {
+    if (cap_ >= need && p_) return CX_OK;
     if (need == 0) return CX_OK;
-    const size_t want = need > cap + cap / 2 ? need : cap + cap / 2;
-    void* fresh = nullptr;
+    const size_t want = need > cap_ + cap_ / 2 ? need : cap_ + cap_ / 2;
+    cx_buf fresh;
     hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMalloc(&fresh, want * sizeof(T));
-    if (e == hipSuccess && ptr && used) e = hipMemcpyAsync(fresh, ptr, used * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess) e = fresh.alloc(ctx, want);
+    if (e == hipSuccess && p_ && used) e = hipMemcpyAsync(fresh.p_, p_, used * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        if (fresh) (void)hipFree(fresh);
-        ctx->err = std::string("device buffer (") + std::to_string(want * sizeof(T)) + " bytes): " + hipGetErrorString(e);
-        return (e == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;
-    }
-    if (ptr) (void)hipFree(ptr);
-    ptr = static_cast<T*>(fresh);
-    cap = want;
+    if (e != hipSuccess) return fail(ctx, want * sizeof(T), e);
+    *this = std::move(fresh);
     return CX_OK;
-}
-template <typename T, typename C>
-void cx_release(T*& ptr, C& cap) {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr; cap = 0;
 }
 
 // cx_api.hip
@@ -200,6 +220,7 @@ void cx_xfer_free(cx_ctx* ctx);
 // cx_levels.hip
 void cx_levels_free(cx_ctx* ctx);
 void cx_levels_invalidate(cx_ctx* ctx);
+void cx_levels_unselect(cx_ctx* ctx);
 // cx_post.hip
 void cx_post_free(cx_ctx* ctx);
 int cx_scan_u32(cx_ctx* ctx, const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* sums_tmp, uint32_t* total_dev,
@@ -257,8 +278,6 @@ int cx_level1_simplify_bufs(cx_ctx* ctx, bool normals, bool dry_run, cx_level1_s
 int cx_level1_simplify_tail(cx_ctx* ctx, uint32_t nv_old, uint32_t ncl, uint32_t nt, bool do_clean, bool normals, int64_t* counts);
 int cx_level1_carried_normals(cx_ctx* ctx, const double** nrm, uint32_t* nv);
 int cx_level1_simplify_map_get(cx_ctx* ctx, const int32_t** map, uint32_t* n);
-// cx_attr.hip
-void cx_attr_free(cx_ctx* ctx);
 // cx_comp.hip
 void cx_comp_free(cx_ctx* ctx);
 // cx_simplify.hip

@@ -29,29 +29,26 @@ struct cx_level_slot {
     cx_params P;                       // parameters of the level (valid after cx_extract3d_levels)
     cx_counts counts = {0, 0, 0, 0};
     // per-level side tables of the staged pipeline
-    uint32_t* queue = nullptr;
-    size_t queue_cap = 0;
-    cx_wsum* wsum = nullptr;
-    size_t wsum_cap = 0;
-    cx_wbase* wbase = nullptr;
-    size_t wbase_cap = 0;
-    cx_brec* brec = nullptr;
-    size_t brec_cap = 0;
-    cx_bdesc* flat = nullptr;
-    size_t flat_cap = 0;
-    uint32_t* qa = nullptr;
-    size_t qa_cap = 0;
+    cx_buf<uint32_t> queue;
+    cx_buf<cx_wsum> wsum;
+    cx_buf<cx_wbase> wbase;
+    cx_buf<cx_brec> brec;
+    cx_buf<cx_bdesc> flat;
+    cx_buf<uint32_t> qa;
     uint32_t* counters = nullptr;      // a slice of cx_levels_state::counters_all (not owned)
     uint32_t* chunksum = nullptr;      // a slice of cx_levels_state::chunk_all (not owned)
-    uint32_t* rstart = nullptr;        // vertex stage: first batch of every wave's share of the rounds
-    size_t rstart_cap = 0;
-    uint32_t* kstart = nullptr;        // triangle stage: the same
-    size_t kstart_cap = 0;
+    cx_buf<uint32_t> rstart;           // vertex stage: first batch of every wave's share of the rounds
+    cx_buf<uint32_t> kstart;           // triangle stage: the same
     // Level-0 outputs of the level (swapped with the context's while the level is selected)
-    cx_vrec* verts = nullptr;
-    uint4* cells = nullptr;
-    int32_t* tris = nullptr;
-    uint32_t vcap = 0, ccap = 0, tcap = 0;
+    cx_buf<cx_vrec> verts;
+    cx_buf<uint4> cells;
+    cx_buf<int32_t> tris;              // three per triangle
+    // the level's output buffers and their capacities as the kernels count them
+    void outputs_to(cx_params& Q) const {
+        Q.verts = verts; Q.cells = cells; Q.tris = tris;
+        Q.vcap = (uint32_t)verts.cap(); Q.ccap = (uint32_t)cells.cap(); Q.tcap = (uint32_t)(tris.cap() / 3u);
+    }
+    void swap_outputs(cx_ctx* ctx) { std::swap(ctx->verts, verts); std::swap(ctx->cells, cells); std::swap(ctx->tris, tris); }
 };
 
 #ifndef CXL_SIDES
@@ -60,16 +57,13 @@ struct cx_level_slot {
 struct cx_levels_state {
     std::vector<cx_level_slot> slots;
     int nvalid = 0;                    // levels of the last cx_extract3d_levels
-    cx_params* dparams = nullptr;      // device copy of the levels' parameters
-    size_t dparams_cap = 0;
+    cx_buf<cx_params> dparams;         // device copy of the levels' parameters
     uint32_t* hcounters = nullptr;     // pinned: CX_CNT_WORDS per level
     size_t hcounters_cap = 0;
     // the levels' counters and chunk totals side by side: ONE memset and ONE copy back per call (a memset and a copy per level were
     // 16 small stream operations in front of and behind the scans: ~0.1 ms of a 2.3 ms call)
-    uint32_t* counters_all = nullptr;
-    size_t counters_all_cap = 0;
-    uint32_t* chunk_all = nullptr;
-    size_t chunk_all_cap = 0;
+    cx_buf<uint32_t> counters_all;
+    cx_buf<uint32_t> chunk_all;
     cx_params* hparams = nullptr;      // pinned staging of the levels' parameters (the upload needs no wait)
     size_t hparams_cap = 0;
     cx_task T;
@@ -79,42 +73,29 @@ struct cx_levels_state {
     // the emit stages of the levels run on CXL_SIDES + 1 streams (the context's and these), level l on stream l % (CXL_SIDES + 1)
     hipStream_t side[CXL_SIDES] = {};
     hipEvent_t ev_fork = nullptr, ev_join[CXL_SIDES] = {};
-    uint64_t* info_side[CXL_SIDES] = {};       // info words of the levels in flight on the side streams (unpooled queues)
-    size_t info_side_cap[CXL_SIDES] = {};
+    cx_buf<uint64_t> info_side[CXL_SIDES];     // info words of the levels in flight on the side streams (unpooled queues)
     // ONE pool of queue entries for all levels (every level a slice of every streaming wave's region); false after a call
     // whose surface overflowed a slice: that grid then gets full-size regions per level, as in round 2
     bool pooled = true;
-    uint32_t* qpool = nullptr;
-    size_t qpool_cap = 0;
+    cx_buf<uint32_t> qpool;
     int64_t pooled_off_for[3] = {0, 0, 0};   // the grid shape `pooled == false` was decided for
 };
 
-static void free_slot(cx_level_slot& S) {
-    void* all[] = {S.queue, S.wsum, S.wbase, S.brec, S.flat, S.qa, S.rstart, S.kstart, S.verts, S.cells, S.tris};
-    for (void* p : all)
-        if (p) (void)hipFree(p);
-    S = cx_level_slot();
+// the buffers of the selected level sit in the context (and the context's own in that slot): back to where they belong
+void cx_levels_unselect(cx_ctx* ctx) {
+    cx_levels_state* L = ctx->lv;
+    if (!L || ctx->lv_current < 0 || ctx->lv_current >= (int)L->slots.size()) { ctx->lv_current = -1; return; }
+    cx_level_slot& S = L->slots[ctx->lv_current];
+    S.swap_outputs(ctx);
+    ctx->lv_current = -1;
 }
 
 void cx_levels_free(cx_ctx* ctx) {
     cx_levels_state* L = ctx->lv;
     if (!L) return;
-    // the buffers of the selected level sit in the context (and the context's own in that slot): give them back first so that
-    // both sides free what they own
-    if (ctx->lv_current >= 0 && ctx->lv_current < (int)L->slots.size()) {
-        cx_level_slot& S = L->slots[ctx->lv_current];
-        std::swap(ctx->verts, S.verts); std::swap(ctx->cells, S.cells); std::swap(ctx->tris, S.tris);
-        std::swap(ctx->vcap, S.vcap); std::swap(ctx->ccap, S.ccap); std::swap(ctx->tcap, S.tcap);
-        ctx->lv_current = -1;
-    }
-    for (auto& S : L->slots) free_slot(S);
-    cx_release(L->dparams, L->dparams_cap);
+    cx_levels_unselect(ctx);
     if (L->hcounters) (void)hipHostFree(L->hcounters);
     if (L->hparams) (void)hipHostFree(L->hparams);
-    cx_release(L->counters_all, L->counters_all_cap);
-    cx_release(L->chunk_all, L->chunk_all_cap);
-    for (int k = 0; k < CXL_SIDES; k++) cx_release(L->info_side[k], L->info_side_cap[k]);
-    cx_release(L->qpool, L->qpool_cap);
     for (int k = 0; k < CXL_SIDES; k++) {
         if (L->side[k]) (void)hipStreamDestroy(L->side[k]);
         if (L->ev_join[k]) (void)hipEventDestroy(L->ev_join[k]);
@@ -124,21 +105,9 @@ void cx_levels_free(cx_ctx* ctx) {
     ctx->lv = nullptr;
 }
 
-template <typename Tp, typename C>
-static int grow(cx_ctx* ctx, Tp*& ptr, C& cap, size_t need) { return cx_grow(ctx, ptr, cap, need); }
-
 // a single-level extraction is about to overwrite the context's output buffers: the levels are gone
 void cx_levels_invalidate(cx_ctx* ctx) {
     if (ctx->lv) ctx->lv->nvalid = 0;
-    ctx->lv_current = -1;
-}
-
-static void unselect(cx_ctx* ctx) {
-    cx_levels_state* L = ctx->lv;
-    if (!L || ctx->lv_current < 0 || ctx->lv_current >= (int)L->slots.size()) { ctx->lv_current = -1; return; }
-    cx_level_slot& S = L->slots[ctx->lv_current];
-    std::swap(ctx->verts, S.verts); std::swap(ctx->cells, S.cells); std::swap(ctx->tris, S.tris);
-    std::swap(ctx->vcap, S.vcap); std::swap(ctx->ccap, S.ccap); std::swap(ctx->tcap, S.tcap);
     ctx->lv_current = -1;
 }
 
@@ -148,10 +117,9 @@ extern "C" int cx_levels_select(cx_ctx* ctx, int32_t index) {
     if (!L || index < 0 || index >= L->nvalid) { ctx->err = "cx_levels_select: no such level (call cx_extract3d_levels first)"; return CX_ERR_STATE; }
     CXL_HIP(ctx, hipSetDevice(ctx->device));
     CXL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    unselect(ctx);
+    cx_levels_unselect(ctx);
     cx_level_slot& S = L->slots[index];
-    std::swap(ctx->verts, S.verts); std::swap(ctx->cells, S.cells); std::swap(ctx->tris, S.tris);
-    std::swap(ctx->vcap, S.vcap); std::swap(ctx->ccap, S.ccap); std::swap(ctx->tcap, S.tcap);
+    S.swap_outputs(ctx);
     ctx->lv_current = index;
     ctx->last = S.P;
     ctx->last_task = L->T;
@@ -179,7 +147,7 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
     }
     if (!ctx->lv) ctx->lv = new cx_levels_state();
     cx_levels_state* L = ctx->lv;
-    unselect(ctx);
+    cx_levels_unselect(ctx);
     L->nvalid = 0;
     // nothing is selected from here on: an error return below must not leave the context describing a level that is gone
     ctx->extracted = false; ctx->counts_fetched = false; ctx->post_valid = false; ctx->keep_valid = false;
@@ -207,25 +175,25 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
     // the pool is only tried with up to 3 levels (2 levels: 2.5 GB held instead of 3.7), more levels take full-size regions at once.
     bool pooled = L->pooled && sub >= 64u && (nlevels <= 3 || cx_debug_knob("CX_LEVELS_SLICE", 0u)) && !cx_debug_knob("CX_LEVELS_NO_POOL", 0u);
     if (pooled) {
-        if ((rc = grow(ctx, L->qpool, L->qpool_cap, need))) return rc;
-        for (auto& S : L->slots) cx_release(S.queue, S.queue_cap);      // full-size regions of an earlier call
-        for (int k = 0; k < CXL_SIDES; k++) cx_release(L->info_side[k], L->info_side_cap[k]);
+        if ((rc = L->qpool.grow(ctx, need))) return rc;
+        for (auto& S : L->slots) S.queue.release();      // full-size regions of an earlier call
+        for (int k = 0; k < CXL_SIDES; k++) L->info_side[k].release();
     } else {
-        cx_release(L->qpool, L->qpool_cap);
+        L->qpool.release();
     }
     const size_t chunk_words = (((nw + 255u) / 256u) * 8u + 63u) & ~(size_t)63u;      // per level, a multiple of 256 bytes
-    if ((rc = grow(ctx, L->counters_all, L->counters_all_cap, (size_t)nlevels * CX_CNT_WORDS))) return rc;
-    if ((rc = grow(ctx, L->chunk_all, L->chunk_all_cap, (size_t)nlevels * chunk_words))) return rc;
+    if ((rc = L->counters_all.grow(ctx, (size_t)nlevels * CX_CNT_WORDS))) return rc;
+    if ((rc = L->chunk_all.grow(ctx, (size_t)nlevels * chunk_words))) return rc;
     CXL_HIP(ctx, hipMemsetAsync(L->chunk_all, 0, (size_t)nlevels * chunk_words * sizeof(uint32_t), ctx->stream));
     for (int l = 0; l < nlevels; l++) {
         cx_level_slot& S = L->slots[l];
         S.value = values[l];
-        if (!pooled && (rc = grow(ctx, S.queue, S.queue_cap, need))) return rc;
-        if ((rc = grow(ctx, S.wsum, S.wsum_cap, nw))) return rc;
-        if ((rc = grow(ctx, S.wbase, S.wbase_cap, nw))) return rc;
-        if ((rc = grow(ctx, S.brec, S.brec_cap, nw * T.bcap))) return rc;
-        if ((rc = grow(ctx, S.flat, S.flat_cap, nflat))) return rc;
-        if ((rc = grow(ctx, S.qa, S.qa_cap, nw * CX_SWP * 64u + 64u))) return rc;
+        if (!pooled && (rc = S.queue.grow(ctx, need))) return rc;
+        if ((rc = S.wsum.grow(ctx, nw))) return rc;
+        if ((rc = S.wbase.grow(ctx, nw))) return rc;
+        if ((rc = S.brec.grow(ctx, nw * T.bcap))) return rc;
+        if ((rc = S.flat.grow(ctx, nflat))) return rc;
+        if ((rc = S.qa.grow(ctx, nw * CX_SWP * 64u + 64u))) return rc;
         S.counters = L->counters_all + (size_t)l * CX_CNT_WORDS;
         S.chunksum = L->chunk_all + (size_t)l * chunk_words;
         cx_params& P = S.P;
@@ -247,17 +215,16 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
         P.qa = S.qa;
         P.chunksum = S.chunksum;
         P.nvw = cx_vertex_stage_waves(P);
-        if ((rc = grow(ctx, S.rstart, S.rstart_cap, (size_t)P.nvw + 1u))) return rc;
+        if ((rc = S.rstart.grow(ctx, (size_t)P.nvw + 1u))) return rc;
         P.rstart = S.rstart;
         P.nkw = cx_triangle_stage_waves(P);
-        if ((rc = grow(ctx, S.kstart, S.kstart_cap, (size_t)P.nkw + 1u))) return rc;
+        if ((rc = S.kstart.grow(ctx, (size_t)P.nkw + 1u))) return rc;
         P.kstart = S.kstart;
-        P.verts = S.verts; P.cells = S.cells; P.tris = S.tris;
-        P.vcap = S.vcap; P.ccap = S.ccap; P.tcap = S.tcap;
+        S.outputs_to(P);
     }
     // the staged kernels' word per queue entry is shared: the levels' vertex and triangle stages run one level after the other
-    if ((rc = grow(ctx, ctx->info64, ctx->info64_cap, need))) return rc;
-    if ((rc = grow(ctx, L->dparams, L->dparams_cap, (size_t)nlevels))) return rc;
+    if ((rc = ctx->info64.grow(ctx, need))) return rc;
+    if ((rc = L->dparams.grow(ctx, (size_t)nlevels))) return rc;
     if (L->hcounters_cap < (size_t)nlevels) {
         if (L->hcounters) (void)hipHostFree(L->hcounters);
         L->hcounters = nullptr; L->hcounters_cap = 0;
@@ -274,8 +241,7 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
         cx_params* hp = L->hparams;       // pinned: the copy below is asynchronous and nothing has to wait for it (every call ends synchronised)
         for (int l = 0; l < nlevels; l++) {
             cx_level_slot& S = L->slots[l];
-            S.P.verts = S.verts; S.P.cells = S.cells; S.P.tris = S.tris;
-            S.P.vcap = S.vcap; S.P.ccap = S.ccap; S.P.tcap = S.tcap;
+            S.outputs_to(S.P);
             S.P.info64 = pooled ? ctx->info64 + (size_t)l * sub : ctx->info64;
             hp[l] = S.P;
         }
@@ -305,17 +271,10 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
                 ctx->err = "capacity beyond 32-bit indices";
                 return CX_ERR_UNSUPPORTED;
             }
-            size_t c = S.ccap, v = S.vcap, t = S.tcap;
-            if ((rc = grow(ctx, S.cells, c, (size_t)S.counts.n_cells + 64u))) return rc;
-            if ((rc = grow(ctx, S.verts, v, (size_t)S.counts.n_vertices + 64u))) return rc;
-            {
-                size_t t3 = (size_t)S.tcap * 3u;
-                if ((rc = grow(ctx, S.tris, t3, ((size_t)S.counts.n_triangles + 64u) * 3u))) return rc;
-                t = t3 / 3u;
-            }
-            S.ccap = (uint32_t)c; S.vcap = (uint32_t)v; S.tcap = (uint32_t)t;
-            S.P.verts = S.verts; S.P.cells = S.cells; S.P.tris = S.tris;
-            S.P.vcap = S.vcap; S.P.ccap = S.ccap; S.P.tcap = S.tcap;
+            if ((rc = S.cells.grow(ctx, (size_t)S.counts.n_cells + 64u))) return rc;
+            if ((rc = S.verts.grow(ctx, (size_t)S.counts.n_vertices + 64u))) return rc;
+            if ((rc = S.tris.grow(ctx, ((size_t)S.counts.n_triangles + 64u) * 3u))) return rc;
+            S.outputs_to(S.P);
             S.P.info64 = pooled ? ctx->info64 + (size_t)l * sub : ctx->info64;
         }
         // vertex and triangle stages, several levels side by side: level l on stream l % nstr (0 = the context's stream), the side
@@ -335,7 +294,7 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
             for (int k = 0; k + 1 < nstr; k++) {
                 if (!L->side[k]) CXL_HIP(ctx, hipStreamCreateWithFlags(&L->side[k], hipStreamNonBlocking));
                 if (!L->ev_join[k]) CXL_HIP(ctx, hipEventCreateWithFlags(&L->ev_join[k], hipEventDisableTiming));
-                if (!pooled && (rc = grow(ctx, L->info_side[k], L->info_side_cap[k], ctx->info64_cap))) return rc;   // pooled: every level has its own slice of the info words
+                if (!pooled && (rc = L->info_side[k].grow(ctx, ctx->info64.cap()))) return rc;   // pooled: every level has its own slice of the info words
             }
             CXL_HIP(ctx, hipEventRecord(L->ev_fork, ctx->stream));
             for (int k = 0; k + 1 < nstr; k++) CXL_HIP(ctx, hipStreamWaitEvent(L->side[k], L->ev_fork, 0));

@@ -37,20 +37,15 @@ typedef unsigned long long u64;
 #define CXP_EMPTY 0xFFFFFFFFFFFFFFFFULL
 #define CXP_NONE 0xFFFFFFFFu
 
-struct cxp_dev {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
 struct cx_post_state {
-    cxp_dev pts, prio, rep, tri, alive, parent, parent2, tkeys, tvals, flags, scan, blocksums, pts_out, tri_out, comp, misc;
-    cxp_dev keys_out, keys_tmp, told, cls, bnd;   // edge ids of the output vertices; sharded Level 1 (cx_postprocess3d_shard_*)
-    cxp_dev ever;                                 // vertices something was ever merged into: u8[nv] before | u8[nv2] after the compaction
+    cx_buf<uint8_t> pts, prio, rep, tri, alive, parent, parent2, tkeys, tvals, flags, scan, blocksums, pts_out, tri_out, comp, misc;
+    cx_buf<uint8_t> keys_out, keys_tmp, told, cls, bnd;   // edge ids of the output vertices; sharded Level 1 (cx_postprocess3d_shard_*)
+    cx_buf<uint8_t> ever;                                 // vertices something was ever merged into: u8[nv] before | u8[nv2] after the compaction
     bool keys_valid = false;
     // vertex attributes (cx_attr.hip).  keys_edge: keys_out holds edge ids of the resident array (cx_postprocess3d*, not a caller's mesh
     // and not a shard).  orient_live: S->parent / S->comp still hold the component roots and flips of the orientation step for the
     // orient_nt triangles of tri_out; vflip: per output vertex, 1 = its component's triangles were reversed (filled on first request)
-    cxp_dev vflip;
+    cx_buf<uint8_t> vflip;
     bool keys_edge = false, orient_live = false, vflip_valid = false;
     uint32_t orient_nt = 0;
     // components (cx_comp.hip).  shard_mesh: the mesh came out of cx_postprocess3d_shard_finish (its components reach other ranks);
@@ -62,7 +57,7 @@ struct cx_post_state {
     // simplification (cx_simplify.hip).  simplified: the mesh came out of cx_level1_simplify (its keys are vertex indices of the mesh
     // before); carried: nrm[nrm_cur] holds one unit normal per vertex of it, carried over from the members of its clusters;
     // smap: new index of every vertex of the mesh before the last simplification
-    cxp_dev nrm[2], nrm_tmp, smap;
+    cx_buf<uint8_t> nrm[2], nrm_tmp, smap;
     int nrm_cur = 0;
     bool simplified = false, carried = false, smap_valid = false;
     uint32_t smap_n = 0;
@@ -72,11 +67,11 @@ struct cx_post_state {
         uint32_t nt_in = 0;           // triangles the post-pass started from (layout of S->cls)
         uint32_t n1 = 0, n4 = 0, ncand = 0;   // own triangles next to the lower neighbour, copies of the upper neighbour's, open components
     } shard;
-    cxp_dev mpairs, msegs, mtris, mmid, mtime, mnext;   // morph triangles (4-D)
+    cx_buf<uint8_t> mpairs, msegs, mtris, mmid, mtime, mnext;   // morph triangles (4-D)
     // The morph triangles and their segments are kept SORTED by the bin of their start time (cxp_morph_sort_by_start, the last step of
     // cx_morph_triangles): the triangles that exist at a time t are then a window of ids, and so are their segments.
-    cxp_dev msegs2, mtris2, mtime2;                     // the other halves of the double buffers the sort writes into
-    cxp_dev meflags, metflag, menew, mecnt, medesc, me_pts, me_tri;   // cx_morph_eval_many: segment flag bytes (ALL zero between two calls) / triangle flag bytes / new point ids / block counts of the windows, per-time descriptors, outputs
+    cx_buf<uint8_t> msegs2, mtris2, mtime2;                     // the other halves of the double buffers the sort writes into
+    cx_buf<uint8_t> meflags, metflag, menew, mecnt, medesc, me_pts, me_tri;   // cx_morph_eval_many: segment flag bytes (ALL zero between two calls) / triangle flag bytes / new point ids / block counts of the windows, per-time descriptors, outputs
     void* me_pinned = nullptr;                          // 48 KB of pinned host memory: descriptors up (36 KB), totals back (12 KB) without staging copies
     bool meflags_clean = false;                         // the segment flag bytes are all zero (the kernels that consume a flag clear it)
     uint32_t mbin_t[257] = {0}, mbin_s[257] = {0};      // first triangle / segment of every start-time bin (CXP_SB_BINS + 1 entries)
@@ -88,26 +83,9 @@ struct cx_post_state {
     int64_t ms_out = 0, mt_out = 0;
 };
 
-static int cxp_reserve(cx_ctx* ctx, cxp_dev& d, size_t bytes) {
-    if (d.bytes >= bytes) return CX_OK;
-    if (d.p) (void)hipFree(d.p);
-    d.p = nullptr; d.bytes = 0;
-    CXP_HIP(ctx, hipMalloc(&d.p, bytes));
-    d.bytes = bytes;
-    return CX_OK;
-}
-
 void cx_post_free(cx_ctx* ctx) {
     if (!ctx->post) return;
     cx_post_state* S = ctx->post;
-    cxp_dev* all[] = {&S->pts, &S->prio, &S->rep, &S->tri, &S->alive, &S->parent, &S->parent2, &S->tkeys, &S->tvals,
-                      &S->flags, &S->scan, &S->blocksums, &S->pts_out, &S->tri_out, &S->comp, &S->misc,
-                      &S->keys_out, &S->keys_tmp, &S->told, &S->cls, &S->bnd, &S->ever, &S->vflip,
-                      &S->nrm[0], &S->nrm[1], &S->nrm_tmp, &S->smap,
-                      &S->mpairs, &S->msegs, &S->mtris, &S->mmid, &S->mtime, &S->mnext, &S->msegs2, &S->mtris2, &S->mtime2,
-                      &S->meflags, &S->metflag, &S->menew, &S->mecnt, &S->medesc, &S->me_pts, &S->me_tri};
-    for (cxp_dev* d : all)
-        if (d->p) (void)hipFree(d->p);
     if (S->me_pinned) (void)hipHostFree(S->me_pinned);
     delete S;
     ctx->post = nullptr;
@@ -1203,9 +1181,9 @@ static inline u64 cxp_edge_table_size(size_t n) {
 
 static int cxp_scan(cx_ctx* ctx, cx_post_state* S, const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* total_dev) {
     const uint32_t nb = cxp_blocks(n, CXP_SCAN_BLOCK);
-    int rc = cxp_reserve(ctx, S->blocksums, (size_t)(nb + 1) * sizeof(uint32_t));
+    int rc = S->blocksums.grow(ctx, (size_t)(nb + 1) * sizeof(uint32_t));
     if (rc) return rc;
-    uint32_t* sums = (uint32_t*)S->blocksums.p;
+    uint32_t* sums = S->blocksums.as<uint32_t>();
     hipLaunchKernelGGL(cxp_k_scan_blocks, dim3(nb ? nb : 1), dim3(256), 0, ctx->stream, in, out, sums, n);
     hipLaunchKernelGGL(cxp_k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums, nb, total_dev, (unsigned long long*)nullptr);
     hipLaunchKernelGGL(cxp_k_scan_add, dim3(cxp_blocks(n)), dim3(256), 0, ctx->stream, out, sums, n);
@@ -1240,11 +1218,11 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
                             uint32_t* tprio3, int64_t* out_counts, bool coherent, uint8_t* involved = nullptr, const cxp_shard* shard = nullptr,
                             uint8_t* ever = nullptr) {   // ever != nullptr: the march's own mesh (cxp_k_edges_block); u8[nv] flags, room for nv more behind them
     int rc;
-    double* pts = (double*)S->pts.p;
-    uint32_t* prio = (uint32_t*)S->prio.p;
-    int32_t* tri = (int32_t*)S->tri.p;
-    uint8_t* alive = (uint8_t*)S->alive.p;
-    uint32_t* misc = (uint32_t*)S->misc.p;   // [0] changed flag, [1..] counters
+    double* pts = S->pts.as<double>();
+    uint32_t* prio = S->prio.as<uint32_t>();
+    int32_t* tri = S->tri.as<int32_t>();
+    uint8_t* alive = S->alive.as<uint8_t>();
+    uint32_t* misc = S->misc.as<uint32_t>();   // [0] changed flag, [1..] counters
     hipStream_t st = ctx->stream;
     S->keys_valid = false;
     S->keys_edge = false; S->orient_live = false; S->vflip_valid = false;
@@ -1252,37 +1230,37 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
     S->shard.open = false;
     S->simplified = false; S->carried = false; S->smap_valid = false;
     if (do_clean && nt) {
-        u64* parent2 = (u64*)S->parent2.p;
+        u64* parent2 = S->parent2.as<u64>();
         hipLaunchKernelGGL(cxp_k_iota64, dim3(cxp_blocks(nv)), dim3(256), 0, st, parent2, nv);
         hipLaunchKernelGGL(cxp_k_degenerate, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, pts, parent2, prio);
         if (involved) CXP_HIP(ctx, hipMemsetAsync(involved, 0, nv, st));
         hipLaunchKernelGGL(cxp_k_remap, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, (const uint32_t*)nullptr, parent2, involved, ever);
         // (with the filter only triangles next to a merge enter the table: 5/4 of the bound is plenty and half as much to clear)
         const u64 tsz = involved ? cxp_edge_table_size(nt) : cxp_table_size(nt);
-        if ((rc = cxp_reserve(ctx, S->tkeys, tsz * sizeof(u64)))) return rc;
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, (u64*)S->tkeys.p, (size_t)tsz, CXP_EMPTY);
-        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, (u64*)S->tkeys.p, tsz - 1, (const uint8_t*)involved);
-        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, (u64*)S->tkeys.p, tsz - 1, (const uint8_t*)involved);
+        if ((rc = S->tkeys.grow(ctx, tsz * sizeof(u64)))) return rc;
+        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXP_EMPTY);
+        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
+        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
     }
     // ---- sharded: the second layer of the neighbours' cells has done its work (weld, tiny collapse and clean-up above saw it)
     uint8_t* cls = nullptr;
     uint32_t* told = nullptr;
     if (shard) {
-        if ((rc = cxp_reserve(ctx, S->cls, 3 * (size_t)nt + 64))) return rc;
-        if ((rc = cxp_reserve(ctx, S->told, ((size_t)nt + 16) * sizeof(uint32_t)))) return rc;
-        cls = (uint8_t*)S->cls.p;
-        told = (uint32_t*)S->told.p;
+        if ((rc = S->cls.grow(ctx, 3 * (size_t)nt + 64))) return rc;
+        if ((rc = S->told.grow(ctx, ((size_t)nt + 16) * sizeof(uint32_t)))) return rc;
+        cls = S->cls.as<uint8_t>();
+        told = S->told.as<uint32_t>();
         CXP_HIP(ctx, hipMemsetAsync(misc + 6, 0, 2 * sizeof(uint32_t), st));
         if (nt) hipLaunchKernelGGL(cxp_k_shard_classify, dim3(cxp_blocks(nt)), dim3(256), 0, st, tprio3, alive, nt, *shard, cx_fdiv_make(shard->plane), cls, misc + 6);
     }
     // ---- compaction of used vertices and living triangles (byte flags, per-block counts, the scan redone inside the two consumers)
-    if ((rc = cxp_reserve(ctx, S->flags, (size_t)(nv + nt + 16) * sizeof(uint32_t)))) return rc;      // (also: the list of possible start triangles below)
-    if ((rc = cxp_reserve(ctx, S->scan, (size_t)(nv + 16) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->flags.grow(ctx, (size_t)(nv + nt + 16) * sizeof(uint32_t)))) return rc;      // (also: the list of possible start triangles below)
+    if ((rc = S->scan.grow(ctx, (size_t)(nv + 16) * sizeof(uint32_t)))) return rc;
     const uint32_t nbv = cxp_blocks(nv, CXP_SCAN_BLOCK), nbt = cxp_blocks(nt, CXP_SCAN_BLOCK);
-    if ((rc = cxp_reserve(ctx, S->blocksums, (size_t)(nbv + nbt + 16) * sizeof(uint32_t)))) return rc;
-    uint8_t* used = (uint8_t*)S->flags.p;
-    uint32_t* vnew = (uint32_t*)S->scan.p;
-    uint32_t* voff = (uint32_t*)S->blocksums.p;
+    if ((rc = S->blocksums.grow(ctx, (size_t)(nbv + nbt + 16) * sizeof(uint32_t)))) return rc;
+    uint8_t* used = S->flags.as<uint8_t>();
+    uint32_t* vnew = S->scan.as<uint32_t>();
+    uint32_t* voff = S->blocksums.as<uint32_t>();
     uint32_t* toff = voff + nbv + 8;
     uint32_t nv2 = 0, nt2 = 0;
     if (nt) {
@@ -1296,12 +1274,12 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
         CXP_HIP(ctx, hipStreamSynchronize(st));
         nv2 = h[0]; nt2 = h[1];
     }
-    if ((rc = cxp_reserve(ctx, S->pts_out, (size_t)(nv2 + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->tri_out, (size_t)(nt2 + 1) * 3 * sizeof(int32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->keys_out, (size_t)(nv2 + 1) * sizeof(uint32_t)))) return rc;
-    double* pts2 = (double*)S->pts_out.p;
-    int32_t* tri2 = (int32_t*)S->tri_out.p;
-    uint32_t* keys2 = (uint32_t*)S->keys_out.p;
+    if ((rc = S->pts_out.grow(ctx, (size_t)(nv2 + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = S->tri_out.grow(ctx, (size_t)(nt2 + 1) * 3 * sizeof(int32_t)))) return rc;
+    if ((rc = S->keys_out.grow(ctx, (size_t)(nv2 + 1) * sizeof(uint32_t)))) return rc;
+    double* pts2 = S->pts_out.as<double>();
+    int32_t* tri2 = S->tri_out.as<int32_t>();
+    uint32_t* keys2 = S->keys_out.as<uint32_t>();
     if (nt2) {
         hipLaunchKernelGGL(cxp_k_compact_pts_fused, dim3(nbv), dim3(256), 0, st, (const double*)pts, (const uint8_t*)used, (const uint32_t*)voff, nv, vnew, pts2,
                            (const uint32_t*)prio, keys2, (const uint8_t*)ever, ever ? ever + nv : nullptr);
@@ -1332,17 +1310,17 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
             if (cx_debug_knob("CX_EDGE_TABLE_TINY", 0)) esz = 1024;     // tests: force the repeat
             if (esz > esz_full) esz = esz_full;
         }
-        if ((rc = cxp_reserve(ctx, S->parent, (size_t)nt2 * sizeof(u64)))) return rc;
-        if ((rc = cxp_reserve(ctx, S->comp, (size_t)nt2 * (3 * sizeof(u64) + sizeof(uint32_t))))) return rc;
-        u64* parent = (u64*)S->parent.p;
-        u64* cmaxx = (u64*)S->comp.p;
+        if ((rc = S->parent.grow(ctx, (size_t)nt2 * sizeof(u64)))) return rc;
+        if ((rc = S->comp.grow(ctx, (size_t)nt2 * (3 * sizeof(u64) + sizeof(uint32_t))))) return rc;
+        u64* parent = S->parent.as<u64>();
+        u64* cmaxx = S->comp.as<u64>();
         u64* cbest = cmaxx + nt2;
         u64* cmaxv = cbest + nt2;
         uint32_t* cstart = (uint32_t*)(cmaxv + nt2);
-        uint32_t* others = (uint32_t*)S->comp.p;   // 12 of the 28 bytes per triangle that the component tables take below
+        uint32_t* others = S->comp.as<uint32_t>();   // 12 of the 28 bytes per triangle that the component tables take below
         for (;;) {
-            if ((rc = cxp_reserve(ctx, S->tkeys, 2 * esz * sizeof(u64)))) return rc;
-            u64* etab = (u64*)S->tkeys.p;
+            if ((rc = S->tkeys.grow(ctx, 2 * esz * sizeof(u64)))) return rc;
+            u64* etab = S->tkeys.as<u64>();
             // (measured and dropped: clearing the table on a second stream while weld / tiny collapse / clean-up run -- no gain, the fill
             // takes from them what it saves)
             hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, etab, (size_t)(2 * esz), CXP_EMPTY);
@@ -1376,7 +1354,7 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
         const uint8_t* own = cls2;
         hipLaunchKernelGGL(cxp_k_comp_maxx, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, nt2, pts2, parent, cmaxx, own);
         // (the scan / flag arrays of the compaction are free by now: the list of possible start triangles goes there)
-        uint32_t* clist = (uint32_t*)S->flags.p;
+        uint32_t* clist = S->flags.as<uint32_t>();
         const uint32_t* cn = misc + 11;
         const dim3 lgrid(std::min(cxp_blocks(nt2), 1024u));
         CXP_HIP(ctx, hipMemsetAsync(misc + 11, 0, sizeof(uint32_t), st));
@@ -1392,8 +1370,8 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
             CXP_HIP(ctx, hipStreamSynchronize(st));
             const size_t n1 = hb[0], n4 = hb[1], nb = n1 + n4;
             // layout of S->bnd: hash1 u64[n1] | hash4 u64[n4] | candidates cxp_cand[nb] | label1 u32[n1] | label4 u32[n4]
-            if ((rc = cxp_reserve(ctx, S->bnd, (nb + 2) * (sizeof(u64) + sizeof(cxp_cand) + sizeof(uint32_t)) + 64))) return rc;
-            u64* hash1 = (u64*)S->bnd.p;
+            if ((rc = S->bnd.grow(ctx, (nb + 2) * (sizeof(u64) + sizeof(cxp_cand) + sizeof(uint32_t)) + 64))) return rc;
+            u64* hash1 = S->bnd.as<u64>();
             u64* hash4 = hash1 + n1;
             cxp_cand* cand = (cxp_cand*)(hash4 + n4);
             uint32_t* label1 = (uint32_t*)(cand + nb);
@@ -1437,18 +1415,18 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
 static int cxp_shard_finish(cx_ctx* ctx, cx_post_state* S, const uint32_t* labels, const uint8_t* flips, uint32_t n, int64_t* out_counts) {
     int rc;
     hipStream_t st = ctx->stream;
-    uint32_t* misc = (uint32_t*)S->misc.p;
+    uint32_t* misc = S->misc.as<uint32_t>();
     const uint32_t nv2 = S->shard.nv2, nt2 = S->shard.nt2;
     S->shard.open = false;
     uint32_t ncomp = 0, nv3 = 0, nt3 = 0;
     if (nt2) {
-        u64* parent = (u64*)S->parent.p;
-        u64* cflip = (u64*)S->comp.p + nt2;
-        int32_t* tri2 = (int32_t*)S->tri_out.p;
-        const uint8_t* cls2 = (const uint8_t*)S->cls.p + S->shard.nt_in;
+        u64* parent = S->parent.as<u64>();
+        u64* cflip = S->comp.as<u64>() + nt2;
+        int32_t* tri2 = S->tri_out.as<int32_t>();
+        const uint8_t* cls2 = S->cls.as<const uint8_t>() + S->shard.nt_in;
         if (n) {
-            if ((rc = cxp_reserve(ctx, S->keys_tmp, std::max((size_t)n * 5 + 64, (size_t)(nv2 + 1) * sizeof(uint32_t))))) return rc;
-            uint32_t* dl = (uint32_t*)S->keys_tmp.p;
+            if ((rc = S->keys_tmp.grow(ctx, std::max((size_t)n * 5 + 64, (size_t)(nv2 + 1) * sizeof(uint32_t))))) return rc;
+            uint32_t* dl = S->keys_tmp.as<uint32_t>();
             uint8_t* df = (uint8_t*)(dl + n);
             CXP_HIP(ctx, hipMemcpyAsync(dl, labels, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
             CXP_HIP(ctx, hipMemcpyAsync(df, flips, (size_t)n, hipMemcpyHostToDevice, st));
@@ -1457,12 +1435,12 @@ static int cxp_shard_finish(cx_ctx* ctx, cx_post_state* S, const uint32_t* label
         CXP_HIP(ctx, hipMemsetAsync(misc + 3, 0, sizeof(uint32_t), st));
         hipLaunchKernelGGL(cxp_k_orient, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, nt2, parent, cflip, misc + 3);
         // own triangles and the vertices they use (the same ordered compaction as in cxp_clean_orient)
-        uint8_t* alive = (uint8_t*)S->alive.p;
-        uint8_t* used = (uint8_t*)S->flags.p;
-        uint32_t* vnew = (uint32_t*)S->scan.p;
+        uint8_t* alive = S->alive.as<uint8_t>();
+        uint8_t* used = S->flags.as<uint8_t>();
+        uint32_t* vnew = S->scan.as<uint32_t>();
         const uint32_t nbv = cxp_blocks(nv2, CXP_SCAN_BLOCK), nbt = cxp_blocks(nt2, CXP_SCAN_BLOCK);
-        if ((rc = cxp_reserve(ctx, S->blocksums, (size_t)(nbv + nbt + 16) * sizeof(uint32_t)))) return rc;
-        uint32_t* voff = (uint32_t*)S->blocksums.p;
+        if ((rc = S->blocksums.grow(ctx, (size_t)(nbv + nbt + 16) * sizeof(uint32_t)))) return rc;
+        uint32_t* voff = S->blocksums.as<uint32_t>();
         uint32_t* toff = voff + nbv + 8;
         hipLaunchKernelGGL(cxp_k_shard_own_alive, dim3(cxp_blocks(nt2)), dim3(256), 0, st, cls2, nt2, alive);
         CXP_HIP(ctx, hipMemsetAsync(used, 0, (size_t)nv2, st));
@@ -1475,20 +1453,20 @@ static int cxp_shard_finish(cx_ctx* ctx, cx_post_state* S, const uint32_t* label
         CXP_HIP(ctx, hipStreamSynchronize(st));
         nv3 = h[0]; nt3 = h[1]; ncomp = h[2];
         // the march's own buffers are free by now: they take the final mesh on its way back into the output buffers
-        if ((rc = cxp_reserve(ctx, S->pts, (size_t)(nv3 + 1) * 3 * sizeof(double)))) return rc;
-        if ((rc = cxp_reserve(ctx, S->tri, (size_t)(nt3 + 1) * 3 * sizeof(int32_t)))) return rc;
-        if ((rc = cxp_reserve(ctx, S->keys_tmp, (size_t)(nv3 + 1) * sizeof(uint32_t)))) return rc;
+        if ((rc = S->pts.grow(ctx, (size_t)(nv3 + 1) * 3 * sizeof(double)))) return rc;
+        if ((rc = S->tri.grow(ctx, (size_t)(nt3 + 1) * 3 * sizeof(int32_t)))) return rc;
+        if ((rc = S->keys_tmp.grow(ctx, (size_t)(nv3 + 1) * sizeof(uint32_t)))) return rc;
         if (nt3) {
-            hipLaunchKernelGGL(cxp_k_compact_pts_fused, dim3(nbv), dim3(256), 0, st, (const double*)S->pts_out.p, (const uint8_t*)used, (const uint32_t*)voff, nv2, vnew,
-                               (double*)S->pts.p, (const uint32_t*)S->keys_out.p, (uint32_t*)S->keys_tmp.p, (const uint8_t*)nullptr, (uint8_t*)nullptr);
+            hipLaunchKernelGGL(cxp_k_compact_pts_fused, dim3(nbv), dim3(256), 0, st, S->pts_out.as<const double>(), (const uint8_t*)used, (const uint32_t*)voff, nv2, vnew,
+                               S->pts.as<double>(), S->keys_out.as<const uint32_t>(), S->keys_tmp.as<uint32_t>(), (const uint8_t*)nullptr, (uint8_t*)nullptr);
             hipLaunchKernelGGL(cxp_k_compact_tri_fused, dim3(nbt), dim3(256), 0, st, (const int32_t*)tri2, (const uint8_t*)alive, (const uint32_t*)toff,
-                               (const uint32_t*)vnew, nt2, (int32_t*)S->tri.p, (uint32_t*)nullptr);
+                               (const uint32_t*)vnew, nt2, S->tri.as<int32_t>(), (uint32_t*)nullptr);
         }
         // back into the output buffers (every buffer keeps its size from call to call: nothing is reallocated for the next volume)
         if (nt3) {
-            CXP_HIP(ctx, hipMemcpyAsync(S->pts_out.p, S->pts.p, (size_t)nv3 * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
-            CXP_HIP(ctx, hipMemcpyAsync(S->tri_out.p, S->tri.p, (size_t)nt3 * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-            CXP_HIP(ctx, hipMemcpyAsync(S->keys_out.p, S->keys_tmp.p, (size_t)nv3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+            CXP_HIP(ctx, hipMemcpyAsync(S->pts_out.get(), S->pts.get(), (size_t)nv3 * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+            CXP_HIP(ctx, hipMemcpyAsync(S->tri_out.get(), S->tri.get(), (size_t)nt3 * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+            CXP_HIP(ctx, hipMemcpyAsync(S->keys_out.get(), S->keys_tmp.get(), (size_t)nv3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         }
         CXP_HIP(ctx, hipStreamSynchronize(st));
     }
@@ -1507,7 +1485,7 @@ static int cxp_state(cx_ctx* ctx, cx_post_state** out) {
     // every post-pass rewrites the points the morph triangles of an earlier cx_morph_triangles index: those are gone (their segments would
     // point into the new points: cx_morph_eval on them read out of bounds)
     ctx->post->ms_out = 0; ctx->post->mt_out = 0; ctx->post->msorted = false; ctx->post->me_off.clear();
-    return cxp_reserve(ctx, ctx->post->misc, 512 * sizeof(uint32_t));      // (words 32..288: bin starts of the start-time sort)
+    return ctx->post->misc.grow(ctx, 512 * sizeof(uint32_t));      // (words 32..288: bin starts of the start-time sort)
 }
 
 // ---- smooth_interpolations(factor) (tetrahedral.py:329-351): every vertex that is part of a triangle moves by
@@ -1614,13 +1592,13 @@ extern "C" int cx_postprocess3d(cx_ctx* ctx, uint32_t flags, int64_t* out_counts
 // buffers of the 3-D post-pass for nv vertices and nt triangles
 static int cxp_reserve3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt) {
     int rc;
-    if ((rc = cxp_reserve(ctx, S->pts, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->prio, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->rep, (size_t)(nv + 1) * (sizeof(uint32_t) + 1)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->tri, (size_t)(nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;   // triangles + priority triples
-    if ((rc = cxp_reserve(ctx, S->alive, (size_t)nt + 16))) return rc;
-    if ((rc = cxp_reserve(ctx, S->parent, (size_t)(nv + 1) * sizeof(u64)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->parent2, (size_t)(nv + 1) * sizeof(u64)))) return rc;
+    if ((rc = S->pts.grow(ctx, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = S->prio.grow(ctx, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->rep.grow(ctx, (size_t)(nv + 1) * (sizeof(uint32_t) + 1)))) return rc;
+    if ((rc = S->tri.grow(ctx, (size_t)(nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;   // triangles + priority triples
+    if ((rc = S->alive.grow(ctx, (size_t)nt + 16))) return rc;
+    if ((rc = S->parent.grow(ctx, (size_t)(nv + 1) * sizeof(u64)))) return rc;
+    if ((rc = S->parent2.grow(ctx, (size_t)(nv + 1) * sizeof(u64)))) return rc;
     return CX_OK;
 }
 // weld -> (smooth) -> tiny collapse -> clean -> orient on S->pts / S->prio / S->tri / S->alive (A6..A10)
@@ -1630,22 +1608,22 @@ static int cxp_run3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, co
                      double smooth, bool coherent, int64_t* counts, bool edge_crossings = false, const cxp_shard* shard = nullptr, bool march_mesh = false) {
     int rc;
     hipStream_t st = ctx->stream;
-    double* pts = (double*)S->pts.p;
-    uint32_t* prio = (uint32_t*)S->prio.p;
-    uint32_t* rep = (uint32_t*)S->rep.p;
+    double* pts = S->pts.as<double>();
+    uint32_t* prio = S->prio.as<uint32_t>();
+    uint32_t* rep = S->rep.as<uint32_t>();
     uint8_t* moved = (uint8_t*)(rep + nv + 1);
-    int32_t* tri = (int32_t*)S->tri.p;
+    int32_t* tri = S->tri.as<int32_t>();
     uint32_t* tprio3 = (uint32_t*)(tri + (size_t)(nt + 1) * 3);
-    uint8_t* alive = (uint8_t*)S->alive.p;
-    uint32_t* misc = (uint32_t*)S->misc.p;
+    uint8_t* alive = S->alive.as<uint8_t>();
+    uint32_t* misc = S->misc.as<uint32_t>();
     uint8_t* ever = nullptr;      // the march's own crossings: which vertices weld or clean-up merge something into
     for (int a = 0; a < 3; a++) S->corner[a] = corner[a];
     // (march_mesh: a mesh the march emitted, handed back by the caller -- slabs assembled on the host, refined points --: an edge lies on
     // at most two triangles until something is merged into one of its ends, which is all the block linking needs; the weld shortcut needs
     // the crossings' own geometry and stays with edge_crossings)
     if (nv && nt && (edge_crossings || march_mesh) && coherent) {
-        if ((rc = cxp_reserve(ctx, S->ever, 2 * (size_t)nv + 64))) return rc;
-        ever = (uint8_t*)S->ever.p;
+        if ((rc = S->ever.grow(ctx, 2 * (size_t)nv + 64))) return rc;
+        ever = S->ever.as<uint8_t>();
         CXP_HIP(ctx, hipMemsetAsync(ever, 0, nv, st));
     }
     if (nv && nt) {
@@ -1660,44 +1638,44 @@ static int cxp_run3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, co
         }
         // (W.thr > 0: four of five crossings are alone in their bucket and skip the table -- 5/4 of the bound instead of twice it)
         const u64 wsz = W.thr > 0.0 ? cxp_edge_table_size(nv) : cxp_table_size(nv);
-        if ((rc = cxp_reserve(ctx, S->tkeys, std::max(wsz, cxp_table_size(nt)) * sizeof(u64)))) return rc;
-        if ((rc = cxp_reserve(ctx, S->tvals, wsz * sizeof(u64)))) return rc;
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, (u64*)S->tkeys.p, (size_t)wsz, CXP_EMPTY);
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, (u64*)S->tvals.p, (size_t)wsz, (u64)0);
-        hipLaunchKernelGGL(cxp_k_weld_insert, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, prio, nv, W, (u64*)S->tkeys.p, (u64*)S->tvals.p, wsz - 1, vkeep);
-        hipLaunchKernelGGL(cxp_k_weld_lookup, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, nv, W, (u64*)S->tkeys.p, (u64*)S->tvals.p, wsz - 1, rep, vkeep, prio);
+        if ((rc = S->tkeys.grow(ctx, std::max(wsz, cxp_table_size(nt)) * sizeof(u64)))) return rc;
+        if ((rc = S->tvals.grow(ctx, wsz * sizeof(u64)))) return rc;
+        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)wsz, CXP_EMPTY);
+        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tvals.as<u64>(), (size_t)wsz, (u64)0);
+        hipLaunchKernelGGL(cxp_k_weld_insert, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, prio, nv, W, S->tkeys.as<u64>(), S->tvals.as<u64>(), wsz - 1, vkeep);
+        hipLaunchKernelGGL(cxp_k_weld_lookup, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, nv, W, S->tkeys.as<u64>(), S->tvals.as<u64>(), wsz - 1, rep, vkeep, prio);
         // meshes of the march hold no triangle twice: only triangles with a vertex something was welded into can have a twin
         // (`moved` is free until the tiny collapse: it carries the flags)
         uint8_t* involved = (coherent && !cx_debug_knob("CX_DEDUPE_ALL", 0)) ? moved : nullptr;
         if (involved) CXP_HIP(ctx, hipMemsetAsync(involved, 0, nv, st));
         hipLaunchKernelGGL(cxp_k_remap, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, rep, (const u64*)nullptr, involved, ever);
         const u64 tsz = involved ? cxp_edge_table_size(nt) : cxp_table_size(nt);
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, (u64*)S->tkeys.p, (size_t)tsz, CXP_EMPTY);
-        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, (u64*)S->tkeys.p, tsz - 1, (const uint8_t*)involved);
-        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, (u64*)S->tkeys.p, tsz - 1, (const uint8_t*)involved);
+        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXP_EMPTY);
+        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
+        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
         CXP_HIP(ctx, hipMemsetAsync(misc + 4, 0, 2 * sizeof(uint32_t), st));
         hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cxp_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 4);
         if (smooth > 0.0) {
             // ---- smooth_interpolations (tetrahedral.py:547-550), between the weld and the tiny collapse
             const u64 esz = cxp_table_size((size_t)nt * 3);
-            if ((rc = cxp_reserve(ctx, S->tkeys, esz * sizeof(u64)))) return rc;
-            if ((rc = cxp_reserve(ctx, S->pts_out, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
-            if ((rc = cxp_reserve(ctx, S->flags, (size_t)(nv + nt + 16) * sizeof(uint32_t)))) return rc;
-            double* sum = (double*)S->pts_out.p;
-            uint32_t* cnt = (uint32_t*)S->flags.p;
+            if ((rc = S->tkeys.grow(ctx, esz * sizeof(u64)))) return rc;
+            if ((rc = S->pts_out.grow(ctx, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
+            if ((rc = S->flags.grow(ctx, (size_t)(nv + nt + 16) * sizeof(uint32_t)))) return rc;
+            double* sum = S->pts_out.as<double>();
+            uint32_t* cnt = S->flags.as<uint32_t>();
             CXP_HIP(ctx, hipMemsetAsync(sum, 0, (size_t)nv * 3 * sizeof(double), st));
             CXP_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)nv * sizeof(uint32_t), st));
-            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, (u64*)S->tkeys.p, (size_t)esz, CXP_EMPTY);
+            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)esz, CXP_EMPTY);
             if (cx_debug_knob("CX_SMOOTH_TWO_STEP", 0)) {
-                hipLaunchKernelGGL(cxp_k_unique_edges, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, (u64*)S->tkeys.p, esz - 1);
-                hipLaunchKernelGGL(cxp_k_smooth_accumulate, dim3(cxp_blocks(esz)), dim3(256), 0, st, (const u64*)S->tkeys.p, (size_t)esz, pts, sum, cnt);
+                hipLaunchKernelGGL(cxp_k_unique_edges, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), esz - 1);
+                hipLaunchKernelGGL(cxp_k_smooth_accumulate, dim3(cxp_blocks(esz)), dim3(256), 0, st, S->tkeys.as<const u64>(), (size_t)esz, pts, sum, cnt);
             } else {
-                hipLaunchKernelGGL(cxp_k_smooth_edges, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, (u64*)S->tkeys.p, esz - 1, (const double*)pts, sum, cnt);
+                hipLaunchKernelGGL(cxp_k_smooth_edges, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), esz - 1, (const double*)pts, sum, cnt);
             }
             hipLaunchKernelGGL(cxp_k_smooth_apply, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, sum, cnt, nv, smooth);
         }
         // ---- tiny collapse (tetrahedral.py:353-375), epsilon = 1e-4, scaled by 1/corner
-        u64* parent = (u64*)S->parent.p;
+        u64* parent = S->parent.as<u64>();
         hipLaunchKernelGGL(cxp_k_iota64, dim3(cxp_blocks(nv)), dim3(256), 0, st, parent, nv);
         CXP_HIP(ctx, hipMemsetAsync(moved, 0, nv, st));
         hipLaunchKernelGGL(cxp_k_tiny, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, pts, 1.0 / corner[0], 1.0 / corner[1],
@@ -1735,14 +1713,14 @@ extern "C" int cx_postprocess3d_ex(cx_ctx* ctx, uint32_t flags, double smooth, i
     if (ctx->origin[0] < 0 || ctx->origin[1] < 0 || ctx->origin[2] < 0)
         for (int a = 0; a < 3; a++) org.o[a] = (double)ctx->origin[a];
     if (nv && nt) {
-        cxp_launch_vertices_f64(dim3(cxp_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64 : nullptr, P.n1, P.n2,
-                           P.div_plane, P.div_row, P.value, ctx->verts, nv, (double*)S->pts.p, (uint32_t*)S->prio.p, org);
-        CXP_HIP(ctx, hipMemcpyAsync(S->tri.p, ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        cxp_launch_vertices_f64(dim3(cxp_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
+                           P.div_plane, P.div_row, P.value, ctx->verts.get(), nv, S->pts.as<double>(), S->prio.as<uint32_t>(), org);
+        CXP_HIP(ctx, hipMemcpyAsync(S->tri.get(), ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
         if (ctx->keep_valid) {   // cx_select_seeded3d: only the triangles (and vertices) of the selected components exist
-            CXP_HIP(ctx, hipMemcpyAsync(S->alive.p, ctx->tri_keep, nt, hipMemcpyDeviceToDevice, st));
+            CXP_HIP(ctx, hipMemcpyAsync(S->alive.get(), ctx->tri_keep, nt, hipMemcpyDeviceToDevice, st));
             vkeep = ctx->tri_keep + nt;
         } else {
-            CXP_HIP(ctx, hipMemsetAsync(S->alive.p, 1, nt, st));
+            CXP_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
         }
     }
     // the reference's `corner` (voxels per axis); a sample array with a margin around the reference's grid
@@ -1786,10 +1764,10 @@ extern "C" int cx_postprocess3d_shard_begin(cx_ctx* ctx, uint32_t flags, int64_t
     // volume computes, so that the weld buckets truncate identically
     const cxp_origin3 org{{(double)ctx->origin[0], (double)ctx->origin[1], (double)ctx->origin[2]}};
     if (nv && nt) {
-        cxp_launch_vertices_f64(dim3(cxp_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64 : nullptr, P.n1, P.n2,
-                           P.div_plane, P.div_row, P.value, ctx->verts, nv, (double*)S->pts.p, (uint32_t*)S->prio.p, org);
-        CXP_HIP(ctx, hipMemcpyAsync(S->tri.p, ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        CXP_HIP(ctx, hipMemsetAsync(S->alive.p, 1, nt, st));
+        cxp_launch_vertices_f64(dim3(cxp_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
+                           P.div_plane, P.div_row, P.value, ctx->verts.get(), nv, S->pts.as<double>(), S->prio.as<uint32_t>(), org);
+        CXP_HIP(ctx, hipMemcpyAsync(S->tri.get(), ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        CXP_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
     }
     double corner[3] = {(double)(P.n0 - 1), (double)(P.n1 - 1), (double)(P.n2 - 1)};
     for (int a = 0; a < 3; a++)
@@ -1818,7 +1796,7 @@ extern "C" int cx_postprocess3d_shard_boundary(cx_ctx* ctx, int which, uint64_t*
     const size_t n = which == 1 ? n1 : n4;
     if (!n) return CX_OK;
     if (!hash || !label) return CX_ERR_INVALID;
-    const u64* hash1 = (const u64*)S->bnd.p;
+    const u64* hash1 = S->bnd.as<const u64>();
     const cxp_cand* cand = (const cxp_cand*)(hash1 + nb);
     const uint32_t* label1 = (const uint32_t*)(cand + nb);
     CXP_HIP(ctx, hipMemcpyAsync(hash, which == 1 ? hash1 : hash1 + n1, n * sizeof(u64), hipMemcpyDefault, ctx->stream));
@@ -1840,7 +1818,7 @@ extern "C" int cx_postprocess3d_shard_candidates(cx_ctx* ctx, uint32_t* cand_lab
     const size_t nb = (size_t)S->shard.n1 + S->shard.n4, nc = S->shard.ncand;
     if (!nc) return CX_OK;
     if (!cand_label || !cand_x || !cand_vertex_key || !cand_nx || !cand_negative || !cand_has) return CX_ERR_INVALID;
-    const cxp_cand* cand = (const cxp_cand*)((const u64*)S->bnd.p + nb);
+    const cxp_cand* cand = (const cxp_cand*)(S->bnd.as<const u64>() + nb);
     std::vector<cxp_cand> h(nc);
     CXP_HIP(ctx, hipMemcpyAsync(h.data(), cand, nc * sizeof(cxp_cand), hipMemcpyDeviceToHost, ctx->stream));
     CXP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1877,7 +1855,7 @@ extern "C" int cx_level1_download_keys(cx_ctx* ctx, uint32_t* keys) {
     CXP_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     if (!S->nv_out) return CX_OK;
-    return cx_copy_to_host1(ctx, keys, S->keys_out.p, (size_t)S->nv_out * sizeof(uint32_t));
+    return cx_copy_to_host1(ctx, keys, S->keys_out.get(), (size_t)S->nv_out * sizeof(uint32_t));
 }
 
 // float64 coordinates of the Level-0 vertices exactly as the reference interpolates them (tetrahedral.py:471-487) in the
@@ -1892,13 +1870,13 @@ extern "C" int cx_level0_points_f64(cx_ctx* ctx, double* points_xyz) {
     if (rc) return rc;
     const uint32_t nv = (uint32_t)ctx->counts.n_vertices;
     if (!nv) return CX_OK;
-    if ((rc = cxp_reserve(ctx, S->pts, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->prio, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->pts.grow(ctx, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = S->prio.grow(ctx, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
     const cx_params& P = ctx->last;
     const cxp_origin3 org{{(double)ctx->origin[0], (double)ctx->origin[1], (double)ctx->origin[2]}};
-    cxp_launch_vertices_f64(dim3(cxp_blocks(nv)), ctx->stream, P.grid, ctx->grid64_valid ? ctx->grid64 : nullptr, P.n1, P.n2,
-                       P.div_plane, P.div_row, P.value, ctx->verts, nv, (double*)S->pts.p, (uint32_t*)S->prio.p, org);
-    if ((rc = cx_copy_to_host1(ctx, points_xyz, S->pts.p, (size_t)nv * 3 * sizeof(double)))) return rc;
+    cxp_launch_vertices_f64(dim3(cxp_blocks(nv)), ctx->stream, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
+                       P.div_plane, P.div_row, P.value, ctx->verts.get(), nv, S->pts.as<double>(), S->prio.as<uint32_t>(), org);
+    if ((rc = cx_copy_to_host1(ctx, points_xyz, S->pts.get(), (size_t)nv * 3 * sizeof(double)))) return rc;
     ctx->post_valid = false;   // the post-pass buffers no longer hold a Level-1 mesh
     return CX_OK;
 }
@@ -1928,10 +1906,10 @@ extern "C" int cx_postprocess3d_mesh(cx_ctx* ctx, const double* points_xyz, int6
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if ((rc = cxp_reserve3d(ctx, S, nv, nt))) return rc;
     if (nv && nt) {
-        CXP_HIP(ctx, hipMemcpyAsync(S->pts.p, points_xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-        CXP_HIP(ctx, hipMemcpyAsync(S->tri.p, tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        CXP_HIP(ctx, hipMemsetAsync(S->alive.p, 1, nt, st));
-        hipLaunchKernelGGL(cxp_k_iota_prio, dim3(cxp_blocks(nv)), dim3(256), 0, st, (uint32_t*)S->prio.p, nv);
+        CXP_HIP(ctx, hipMemcpyAsync(S->pts.get(), points_xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        CXP_HIP(ctx, hipMemcpyAsync(S->tri.get(), tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        CXP_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
+        hipLaunchKernelGGL(cxp_k_iota_prio, dim3(cxp_blocks(nv)), dim3(256), 0, st, S->prio.as<uint32_t>(), nv);
     }
     const double corner[3] = {(double)corner3[0], (double)corner3[1], (double)corner3[2]};
     if ((rc = cxp_run3d(ctx, S, nv, nt, corner, nullptr, !(flags & 1u), smooth, !(flags & 4u), counts, false, nullptr, (flags & 8u) != 0u))) return rc;
@@ -1946,7 +1924,7 @@ extern "C" int cx_level1_download(cx_ctx* ctx, double* points_xyz, int32_t* tris
     CXP_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     void* d[2] = {(points_xyz && S->nv_out) ? (void*)points_xyz : nullptr, (tris && S->nt_out) ? (void*)tris : nullptr};
-    const void* sp[2] = {S->pts_out.p, S->tri_out.p};
+    const void* sp[2] = {S->pts_out.get(), S->tri_out.get()};
     const size_t nb[2] = {(size_t)S->nv_out * 3 * sizeof(double), (size_t)S->nt_out * 3 * sizeof(int32_t)};
     return cx_copy_to_host(ctx, 2, d, sp, nb);   // pinned, double-buffered, several host threads (cx_xfer.hip)
 }
@@ -1960,8 +1938,8 @@ extern "C" int cx_level1_device_ptrs(cx_ctx* ctx, void** points_xyz, void** tris
     CXP_HIP(ctx, hipSetDevice(ctx->device));
     CXP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     cx_post_state* S = ctx->post;
-    if (points_xyz) *points_xyz = S->nv_out ? S->pts_out.p : nullptr;
-    if (tris) *tris = S->nt_out ? S->tri_out.p : nullptr;
+    if (points_xyz) *points_xyz = S->nv_out ? S->pts_out.get() : nullptr;
+    if (tris) *tris = S->nt_out ? S->tri_out.get() : nullptr;
     if (n_vertices) *n_vertices = (int64_t)S->nv_out;
     if (n_triangles) *n_triangles = (int64_t)S->nt_out;
     return CX_OK;
@@ -1992,18 +1970,18 @@ int cx_level1_attr_view(cx_ctx* ctx, const char* who, cx_level1_view* out) {
     if (nv && !S->vflip_valid) {
         if (nt && (!S->orient_live || S->orient_nt != nt)) { ctx->err = std::string(who) + ": the orientation tables of the post-pass are gone (run cx_postprocess3d again)"; return CX_ERR_STATE; }
         int rc;
-        if ((rc = cxp_reserve(ctx, S->vflip, (size_t)nv + 16))) return rc;
-        CXP_HIP(ctx, hipMemsetAsync(S->vflip.p, 0, nv, ctx->stream));
+        if ((rc = S->vflip.grow(ctx, (size_t)nv + 16))) return rc;
+        CXP_HIP(ctx, hipMemsetAsync(S->vflip.get(), 0, nv, ctx->stream));
         if (nt) {
-            const u64* parent = (const u64*)S->parent.p;
-            const u64* cflip = (const u64*)S->comp.p + nt;    // (cbest of cxp_clean_orient)
-            hipLaunchKernelGGL(cxp_k_vertex_flip, dim3(cxp_blocks(nt)), dim3(256), 0, ctx->stream, (const int32_t*)S->tri_out.p, nt, parent, cflip, (uint8_t*)S->vflip.p);
+            const u64* parent = S->parent.as<const u64>();
+            const u64* cflip = S->comp.as<const u64>() + nt;    // (cbest of cxp_clean_orient)
+            hipLaunchKernelGGL(cxp_k_vertex_flip, dim3(cxp_blocks(nt)), dim3(256), 0, ctx->stream, S->tri_out.as<const int32_t>(), nt, parent, cflip, S->vflip.as<uint8_t>());
             CXP_HIP(ctx, hipGetLastError());
         }
         S->vflip_valid = true;
     }
-    out->keys = (const uint32_t*)S->keys_out.p;
-    out->vflip = (const uint8_t*)S->vflip.p;
+    out->keys = S->keys_out.as<const uint32_t>();
+    out->vflip = S->vflip.as<const uint8_t>();
     out->nv = nv;
     return CX_OK;
 }
@@ -2034,11 +2012,11 @@ int cx_level1_comp_view_get(cx_ctx* ctx, const char* who, cx_level1_comp_view* o
         ctx->err = std::string(who) + ": the orientation tables of the post-pass are gone (a 4-D pass used their memory, or the post-pass ran without the orientation step): run cx_postprocess3d again";
         return CX_ERR_STATE;
     }
-    out->parent = (const u64*)S->parent.p;
-    out->cflip = nt ? (const u64*)S->comp.p + nt : nullptr;    // (cbest of cxp_clean_orient)
-    out->tri = (const int32_t*)S->tri_out.p;
-    out->pts = (const double*)S->pts_out.p;
-    out->keys = (const uint32_t*)S->keys_out.p;
+    out->parent = S->parent.as<const u64>();
+    out->cflip = nt ? S->comp.as<const u64>() + nt : nullptr;    // (cbest of cxp_clean_orient)
+    out->tri = S->tri_out.as<const int32_t>();
+    out->pts = S->pts_out.as<const double>();
+    out->keys = S->keys_out.as<const uint32_t>();
     out->nv = nv; out->nt = nt;
     for (int a = 0; a < 3; a++) out->corner[a] = S->corner[a];
     out->gen = S->gen;
@@ -2050,14 +2028,14 @@ int cx_level1_comp_scratch_get(cx_ctx* ctx, cx_level1_comp_scratch* out) {
     cx_post_state* S = ctx->post;
     const size_t nv = (size_t)S->nv_out, nt = (size_t)S->nt_out;
     int rc;
-    if ((rc = cxp_reserve(ctx, S->pts, (nv + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->tri, (nt + 1) * 3 * sizeof(int32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->keys_tmp, (nv + 1) * sizeof(uint32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->tkeys, (nt + 1) * 2 * sizeof(u64)))) return rc;
-    out->pts = (double*)S->pts.p;
-    out->tri = (int32_t*)S->tri.p;
-    out->keys = (uint32_t*)S->keys_tmp.p;
-    out->parent = (u64*)S->tkeys.p;
+    if ((rc = S->pts.grow(ctx, (nv + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = S->tri.grow(ctx, (nt + 1) * 3 * sizeof(int32_t)))) return rc;
+    if ((rc = S->keys_tmp.grow(ctx, (nv + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->tkeys.grow(ctx, (nt + 1) * 2 * sizeof(u64)))) return rc;
+    out->pts = S->pts.as<double>();
+    out->tri = S->tri.as<int32_t>();
+    out->keys = S->keys_tmp.as<uint32_t>();
+    out->parent = S->tkeys.as<u64>();
     out->cflip = out->parent + nt + 1;
     return CX_OK;
 }
@@ -2067,22 +2045,22 @@ int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new, const u
     hipStream_t st = ctx->stream;
     S->smap_valid = false;
     if (S->carried && nv_new && S->nv_out) {       // the carried normals of a simplified mesh follow their vertices
-        const int rcn = cxp_reserve(ctx, S->nrm[1 - S->nrm_cur], ((size_t)nv_new + 1) * 3 * sizeof(double));
+        const int rcn = S->nrm[1 - S->nrm_cur].grow(ctx, ((size_t)nv_new + 1) * 3 * sizeof(double));
         if (rcn) return rcn;
-        hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cxp_blocks((size_t)S->nv_out)), dim3(256), 0, st, (const double*)S->nrm[S->nrm_cur].p, vuse, vnew,
-                           (uint32_t)S->nv_out, (double*)S->nrm[1 - S->nrm_cur].p);
+        hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cxp_blocks((size_t)S->nv_out)), dim3(256), 0, st, S->nrm[S->nrm_cur].as<const double>(), vuse, vnew,
+                           (uint32_t)S->nv_out, S->nrm[1 - S->nrm_cur].as<double>());
         S->nrm_cur = 1 - S->nrm_cur;
     }
     const size_t nt_old = (size_t)S->nt_out;
-    const u64* parent_new = (const u64*)S->tkeys.p;
+    const u64* parent_new = S->tkeys.as<const u64>();
     if (nv_new) {
-        CXP_HIP(ctx, hipMemcpyAsync(S->pts_out.p, S->pts.p, (size_t)nv_new * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        CXP_HIP(ctx, hipMemcpyAsync(S->keys_out.p, S->keys_tmp.p, (size_t)nv_new * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        CXP_HIP(ctx, hipMemcpyAsync(S->pts_out.get(), S->pts.get(), (size_t)nv_new * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        CXP_HIP(ctx, hipMemcpyAsync(S->keys_out.get(), S->keys_tmp.get(), (size_t)nv_new * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     }
     if (nt_new) {
-        CXP_HIP(ctx, hipMemcpyAsync(S->tri_out.p, S->tri.p, (size_t)nt_new * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        CXP_HIP(ctx, hipMemcpyAsync(S->parent.p, parent_new, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
-        CXP_HIP(ctx, hipMemcpyAsync((u64*)S->comp.p + nt_new, parent_new + nt_old + 1, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
+        CXP_HIP(ctx, hipMemcpyAsync(S->tri_out.get(), S->tri.get(), (size_t)nt_new * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        CXP_HIP(ctx, hipMemcpyAsync(S->parent.get(), parent_new, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
+        CXP_HIP(ctx, hipMemcpyAsync(S->comp.as<u64>() + nt_new, parent_new + nt_old + 1, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
     }
     CXP_HIP(ctx, hipStreamSynchronize(st));
     S->nv_out = nv_new; S->nt_out = nt_new;
@@ -2102,22 +2080,22 @@ int cx_level1_simplify_bufs(cx_ctx* ctx, bool normals, bool dry_run, cx_level1_s
     const size_t nv = (size_t)S->nv_out, nt = (size_t)S->nt_out;
     int rc;
     // (as cxp_reserve3d, without S->parent: it holds the tables of the orientation step the mesh still needs if the call fails)
-    if ((rc = cxp_reserve(ctx, S->pts, (nv + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->prio, (nv + 1) * sizeof(uint32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->tri, (nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;
-    if ((rc = cxp_reserve(ctx, S->alive, nt + 16))) return rc;
-    if ((rc = cxp_reserve(ctx, S->parent2, (nv + 1) * sizeof(u64)))) return rc;
+    if ((rc = S->pts.grow(ctx, (nv + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = S->prio.grow(ctx, (nv + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->tri.grow(ctx, (nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;
+    if ((rc = S->alive.grow(ctx, nt + 16))) return rc;
+    if ((rc = S->parent2.grow(ctx, (nv + 1) * sizeof(u64)))) return rc;
     // (a dry run leaves the map of the last simplification alone: its cluster ids go into the weld's scratch)
-    if ((rc = cxp_reserve(ctx, dry_run ? S->rep : S->smap, (nv + 16) * sizeof(int32_t)))) return rc;
-    if (normals && (rc = cxp_reserve(ctx, S->nrm_tmp, (nv + 1) * 3 * sizeof(double)))) return rc;
-    out->pts = (double*)S->pts.p;
-    out->prio = (uint32_t*)S->prio.p;
-    out->tri = (int32_t*)S->tri.p;
+    if ((rc = (dry_run ? S->rep : S->smap).grow(ctx, (nv + 16) * sizeof(int32_t)))) return rc;
+    if (normals && (rc = S->nrm_tmp.grow(ctx, (nv + 1) * 3 * sizeof(double)))) return rc;
+    out->pts = S->pts.as<double>();
+    out->prio = S->prio.as<uint32_t>();
+    out->tri = S->tri.as<int32_t>();
     out->tprio3 = (uint32_t*)(out->tri + (nt + 1) * 3);
-    out->alive = (uint8_t*)S->alive.p;
-    out->map = (int32_t*)(dry_run ? S->rep.p : S->smap.p);
-    out->nrm_new = normals ? (double*)S->nrm_tmp.p : nullptr;
-    out->nrm_src = S->carried ? (const double*)S->nrm[S->nrm_cur].p : nullptr;
+    out->alive = S->alive.as<uint8_t>();
+    out->map = (dry_run ? S->rep : S->smap).as<int32_t>();
+    out->nrm_new = normals ? S->nrm_tmp.as<double>() : nullptr;
+    out->nrm_src = S->carried ? S->nrm[S->nrm_cur].as<const double>() : nullptr;
     out->simplified = S->simplified;
     if (!dry_run) S->smap_valid = false;
     return CX_OK;
@@ -2135,28 +2113,28 @@ int cx_level1_simplify_tail(cx_ctx* ctx, uint32_t nv_old, uint32_t ncl, uint32_t
     cx_post_state* S = ctx->post;
     hipStream_t st = ctx->stream;
     int rc;
-    int32_t* tri = (int32_t*)S->tri.p;
+    int32_t* tri = S->tri.as<int32_t>();
     uint32_t* tprio3 = (uint32_t*)(tri + ((size_t)S->nt_out + 1) * 3);
-    uint8_t* alive = (uint8_t*)S->alive.p;
+    uint8_t* alive = S->alive.as<uint8_t>();
     const int cur = S->nrm_cur;
     if (nt && ncl) {
         const u64 tsz = cxp_table_size(nt);
-        if ((rc = cxp_reserve(ctx, S->tkeys, tsz * sizeof(u64)))) return rc;
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, (u64*)S->tkeys.p, (size_t)tsz, CXP_EMPTY);
-        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, (u64*)S->tkeys.p, tsz - 1, (const uint8_t*)nullptr);
-        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, (u64*)S->tkeys.p, tsz - 1, (const uint8_t*)nullptr);
+        if ((rc = S->tkeys.grow(ctx, tsz * sizeof(u64)))) return rc;
+        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXP_EMPTY);
+        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)nullptr);
+        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)nullptr);
     }
     // (the compaction writes the new id of every vertex in use: the others keep -1)
-    if ((rc = cxp_reserve(ctx, S->scan, ((size_t)ncl + 16) * sizeof(uint32_t)))) return rc;
-    if (ncl) CXP_HIP(ctx, hipMemsetAsync(S->scan.p, 0xFF, (size_t)ncl * sizeof(uint32_t), st));
-    if (normals && (rc = cxp_reserve(ctx, S->nrm[1 - cur], ((size_t)ncl + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = S->scan.grow(ctx, ((size_t)ncl + 16) * sizeof(uint32_t)))) return rc;
+    if (ncl) CXP_HIP(ctx, hipMemsetAsync(S->scan.get(), 0xFF, (size_t)ncl * sizeof(uint32_t), st));
+    if (normals && (rc = S->nrm[1 - cur].grow(ctx, ((size_t)ncl + 1) * 3 * sizeof(double)))) return rc;
     if ((rc = cxp_clean_orient(ctx, S, ncl, nt, do_clean, true, tprio3, counts, true))) { ctx->post_valid = false; return rc; }
-    const uint32_t* vnew = (const uint32_t*)S->scan.p;
-    if (nv_old) hipLaunchKernelGGL(cxp_k_simplify_map, dim3(cxp_blocks(nv_old)), dim3(256), 0, st, (int32_t*)S->smap.p, nv_old, ncl,
-                                   (do_clean && nt) ? (const u64*)S->parent2.p : (const u64*)nullptr, vnew);
+    const uint32_t* vnew = S->scan.as<const uint32_t>();
+    if (nv_old) hipLaunchKernelGGL(cxp_k_simplify_map, dim3(cxp_blocks(nv_old)), dim3(256), 0, st, S->smap.as<int32_t>(), nv_old, ncl,
+                                   (do_clean && nt) ? S->parent2.as<const u64>() : (const u64*)nullptr, vnew);
     if (normals && ncl && S->nv_out) {
-        hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cxp_blocks(ncl)), dim3(256), 0, st, (const double*)S->nrm_tmp.p, (const uint32_t*)nullptr, vnew, ncl,
-                           (double*)S->nrm[1 - cur].p);
+        hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cxp_blocks(ncl)), dim3(256), 0, st, S->nrm_tmp.as<const double>(), (const uint32_t*)nullptr, vnew, ncl,
+                           S->nrm[1 - cur].as<double>());
         S->nrm_cur = 1 - cur;
     }
     CXP_HIP(ctx, hipGetLastError());
@@ -2170,7 +2148,7 @@ int cx_level1_carried_normals(cx_ctx* ctx, const double** nrm, uint32_t* nv) {
     cx_post_state* S = ctx->post;
     if (!S || !ctx->post_valid || !S->keys_valid || !S->simplified) return 0;
     *nv = (uint32_t)S->nv_out;
-    *nrm = S->carried ? (const double*)S->nrm[S->nrm_cur].p : nullptr;
+    *nrm = S->carried ? S->nrm[S->nrm_cur].as<const double>() : nullptr;
     return S->carried ? 1 : 2;
 }
 int cx_level1_simplify_map_get(cx_ctx* ctx, const int32_t** map, uint32_t* n) {
@@ -2179,7 +2157,7 @@ int cx_level1_simplify_map_get(cx_ctx* ctx, const int32_t** map, uint32_t* n) {
         ctx->err = "cx_level1_simplify_map: no simplification since the last post-pass or filter";
         return CX_ERR_STATE;
     }
-    *map = (const int32_t*)S->smap.p; *n = S->smap_n;
+    *map = S->smap.as<const int32_t>(); *n = S->smap_n;
     return CX_OK;
 }
 
@@ -2255,7 +2233,7 @@ extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const 
     if (mins_delta) for (int a = 0; a < 3; a++) { m[a] = mins_delta[a]; d[a] = mins_delta[3 + a]; }
     const uint32_t CHUNK = 1u << 20;                       // elements per chunk
     const size_t stage_bytes = (size_t)CHUNK * (with_normals ? 48u : 24u);   // the widest record: 3 doubles (6 with normals)
-    uint8_t* dstage = nullptr;
+    cx_buf<uint8_t> dstage;
     uint8_t* hstage[2] = {nullptr, nullptr};
     FILE* f = fopen(path, "wb");
     if (!f) { ctx->err = std::string("cx_level1_write: cannot open ") + path; return CX_ERR_INVALID; }
@@ -2265,7 +2243,7 @@ extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const 
     do {
         hipError_t e;
 #define CXW_TRY(call) if ((e = (call)) != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e); rc = (e == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP; break; }
-        CXW_TRY(hipMalloc(&dstage, 2 * stage_bytes));
+        if ((rc = dstage.grow(ctx, 2 * stage_bytes))) break;
         CXW_TRY(hipHostMalloc(&hstage[0], stage_bytes));
         CXW_TRY(hipHostMalloc(&hstage[1], stage_bytes));
         if (format == CX_FILE_PLY) {
@@ -2296,16 +2274,16 @@ extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const 
                 if (more) {
                     uint8_t* dst = dstage + (size_t)half * stage_bytes;
                     if (section == 0 && with_normals && format == CX_FILE_PLY)
-                        hipLaunchKernelGGL(cxw_k_points_normals, dim3(cxp_blocks(n)), dim3(256), 0, st, (const double*)S->pts_out.p, nrm, first, n, m[0], m[1], m[2],
+                        hipLaunchKernelGGL(cxw_k_points_normals, dim3(cxp_blocks(n)), dim3(256), 0, st, S->pts_out.as<const double>(), nrm, first, n, m[0], m[1], m[2],
                                            d[0], d[1], d[2], (double*)dst);
                     else if (section == 0)
-                        hipLaunchKernelGGL(cxw_k_points, dim3(cxp_blocks(n)), dim3(256), 0, st, (const double*)S->pts_out.p, first, n, m[0], m[1], m[2],
+                        hipLaunchKernelGGL(cxw_k_points, dim3(cxp_blocks(n)), dim3(256), 0, st, S->pts_out.as<const double>(), first, n, m[0], m[1], m[2],
                                            d[0], d[1], d[2], format == CX_FILE_PLY ? 0 : 1, (void*)dst);
                     else if (section == 2)
                         hipLaunchKernelGGL(cxw_k_normals_f32, dim3(cxp_blocks(n)), dim3(256), 0, st, nrm, first, n, (float*)dst);
                     else if (format == CX_FILE_PLY)
-                        hipLaunchKernelGGL(cxw_k_faces13, dim3(cxp_blocks(n)), dim3(256), 0, st, (const int32_t*)S->tri_out.p, first, n, dst);
-                    const void* src = (section == 1 && format != CX_FILE_PLY) ? (const void*)((const int32_t*)S->tri_out.p + (size_t)first * 3) : (const void*)dst;
+                        hipLaunchKernelGGL(cxw_k_faces13, dim3(cxp_blocks(n)), dim3(256), 0, st, S->tri_out.as<const int32_t>(), first, n, dst);
+                    const void* src = (section == 1 && format != CX_FILE_PLY) ? (const void*)(S->tri_out.as<const int32_t>() + (size_t)first * 3) : (const void*)dst;
                     e = hipMemcpyAsync(hstage[half], src, (size_t)n * rec, hipMemcpyDeviceToHost, st);
                     if (e != hipSuccess) { ctx->err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); rc = CX_ERR_HIP; break; }
                 }
@@ -2337,7 +2315,6 @@ extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const 
     // a short write may only surface when the buffered bytes are flushed (disk full): check both, and leave no partial file
     if (fflush(f) != 0 && rc == CX_OK) { rc = CX_ERR_INVALID; ctx->err = "cx_level1_write: write failed (flush)"; }
     if (fclose(f) != 0 && rc == CX_OK) { rc = CX_ERR_INVALID; ctx->err = "cx_level1_write: write failed (close)"; }
-    if (dstage) (void)hipFree(dstage);
     for (int k = 0; k < 2; k++)
         if (hstage[k]) (void)hipHostFree(hstage[k]);
     if (rc) { (void)remove(path); return rc; }
@@ -2360,27 +2337,27 @@ extern "C" int cx_surface_geometry(cx_ctx* ctx, double* points_xyz, int64_t* nv_
     for (int64_t n = 0; n < (int64_t)nt * 3; n++)
         if (tris[n] < 0 || tris[n] >= (int64_t)nv) { ctx->err = "cx_surface_geometry: triangle index out of range"; return CX_ERR_INVALID; }
     hipStream_t st = ctx->stream;
-    if ((rc = cxp_reserve(ctx, S->pts, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->prio, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->tri, (size_t)(nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;
-    if ((rc = cxp_reserve(ctx, S->alive, (size_t)nt + 16))) return rc;
-    if ((rc = cxp_reserve(ctx, S->parent2, (size_t)(nv + 1) * sizeof(u64)))) return rc;
-    int32_t* tri = (int32_t*)S->tri.p;
+    if ((rc = S->pts.grow(ctx, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = S->prio.grow(ctx, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->tri.grow(ctx, (size_t)(nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;
+    if ((rc = S->alive.grow(ctx, (size_t)nt + 16))) return rc;
+    if ((rc = S->parent2.grow(ctx, (size_t)(nv + 1) * sizeof(u64)))) return rc;
+    int32_t* tri = S->tri.as<int32_t>();
     uint32_t* tprio3 = (uint32_t*)(tri + (size_t)(nt + 1) * 3);
-    if (nv) CXP_HIP(ctx, hipMemcpyAsync(S->pts.p, points_xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (nv) CXP_HIP(ctx, hipMemcpyAsync(S->pts.get(), points_xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     if (nt) CXP_HIP(ctx, hipMemcpyAsync(tri, tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (nv) hipLaunchKernelGGL(cxp_k_iota_prio, dim3(cxp_blocks(nv)), dim3(256), 0, st, (uint32_t*)S->prio.p, nv);
+    if (nv) hipLaunchKernelGGL(cxp_k_iota_prio, dim3(cxp_blocks(nv)), dim3(256), 0, st, S->prio.as<uint32_t>(), nv);
     if (nt) {
-        CXP_HIP(ctx, hipMemsetAsync(S->alive.p, 1, nt, st));
-        hipLaunchKernelGGL(cxp_k_tri_prio, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, (const uint32_t*)S->prio.p, nt, tprio3);
+        CXP_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
+        hipLaunchKernelGGL(cxp_k_tri_prio, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, S->prio.as<const uint32_t>(), nt, tprio3);
         // a caller's triangle may repeat a vertex: such rows are not triangles (surface_geometry.py:63)
-        hipLaunchKernelGGL(cxp_k_remap, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, (uint8_t*)S->alive.p, nt, (const uint32_t*)S->prio.p,
+        hipLaunchKernelGGL(cxp_k_remap, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, S->alive.as<uint8_t>(), nt, S->prio.as<const uint32_t>(),
                            (const u64*)nullptr);
     }
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if ((rc = cxp_clean_orient(ctx, S, nv, nt, mode != 0, mode != 2, tprio3, counts, false))) return rc;   // caller's windings: arbitrary
-    if (S->nv_out) CXP_HIP(ctx, hipMemcpyAsync(points_xyz, S->pts_out.p, (size_t)S->nv_out * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (S->nt_out) CXP_HIP(ctx, hipMemcpyAsync(tris, S->tri_out.p, (size_t)S->nt_out * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    if (S->nv_out) CXP_HIP(ctx, hipMemcpyAsync(points_xyz, S->pts_out.get(), (size_t)S->nv_out * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (S->nt_out) CXP_HIP(ctx, hipMemcpyAsync(tris, S->tri_out.get(), (size_t)S->nt_out * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     CXP_HIP(ctx, hipStreamSynchronize(st));
     *nv_io = S->nv_out; *nt_io = S->nt_out;
     ctx->post_valid = false;
@@ -2512,13 +2489,13 @@ static int cxp_post4_tets(cx_ctx* ctx, cx_post_state* S, const int32_t* tets, ui
                           int64_t* counts, uint32_t* nt2_out) {
     int rc;
     hipStream_t st = ctx->stream;
-    double* pts = (double*)S->pts.p;
-    uint32_t* prio = (uint32_t*)S->prio.p;
-    uint8_t* moved = (uint8_t*)S->rep.p;
-    uint8_t* alive = (uint8_t*)S->alive.p;
-    u64* parent = (u64*)S->parent.p;
+    double* pts = S->pts.as<double>();
+    uint32_t* prio = S->prio.as<uint32_t>();
+    uint8_t* moved = S->rep.as<uint8_t>();
+    uint8_t* alive = S->alive.as<uint8_t>();
+    u64* parent = S->parent.as<u64>();
     S->orient_live = false; S->gen++;   // (the 3-D orientation's tables lived here: what cx_comp.hip cached of them is stale)
-    uint32_t* misc = (uint32_t*)S->misc.p;
+    uint32_t* misc = S->misc.as<uint32_t>();
     hipLaunchKernelGGL(cxp_k_drop_instant, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1e-7);
     // cx_select_seeded4d: only the tetrahedra of the selected components exist
     if (keep) hipLaunchKernelGGL(cxp_k_and_mask, dim3(cxp_blocks(nt)), dim3(256), 0, st, alive, keep, nt);
@@ -2530,8 +2507,8 @@ static int cxp_post4_tets(cx_ctx* ctx, cx_post_state* S, const int32_t* tets, ui
                        1.0 / corner[2], 1.0 / corner[3], 1e-3, parent, prio, moved);
     hipLaunchKernelGGL(cxp_k_move4, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, parent, moved, nv);
     hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cxp_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 5);
-    uint32_t* tflag = (uint32_t*)S->flags.p;
-    uint32_t* tnew = (uint32_t*)S->scan.p;
+    uint32_t* tflag = S->flags.as<uint32_t>();
+    uint32_t* tnew = S->scan.as<uint32_t>();
     hipLaunchKernelGGL(cxp_k_alive_u32, dim3(cxp_blocks(nt)), dim3(256), 0, st, alive, nt, tflag);
     if ((rc = cxp_scan(ctx, S, tflag, tnew, nt, misc + 2))) return rc;
     uint32_t h[3];
@@ -2540,21 +2517,21 @@ static int cxp_post4_tets(cx_ctx* ctx, cx_post_state* S, const int32_t* tets, ui
     CXP_HIP(ctx, hipStreamSynchronize(st));
     counts[2] = h[0]; counts[3] = h[1];
     const uint32_t nt2 = h[2];
-    if ((rc = cxp_reserve(ctx, S->tri_out, (size_t)(nt2 + 1) * 4 * sizeof(int32_t)))) return rc;
-    hipLaunchKernelGGL(cxp_k_compact_tets, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, tnew, nt, (int32_t*)S->tri_out.p);
+    if ((rc = S->tri_out.grow(ctx, (size_t)(nt2 + 1) * 4 * sizeof(int32_t)))) return rc;
+    hipLaunchKernelGGL(cxp_k_compact_tets, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, tnew, nt, S->tri_out.as<int32_t>());
     CXP_HIP(ctx, hipGetLastError());
     *nt2_out = nt2;
     return CX_OK;
 }
 static int cxp_reserve4(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt) {
     int rc;
-    if ((rc = cxp_reserve(ctx, S->pts, (size_t)(nv + 1) * 4 * sizeof(double)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->prio, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->rep, (size_t)nv + 16))) return rc;
-    if ((rc = cxp_reserve(ctx, S->alive, (size_t)nt + 16))) return rc;
-    if ((rc = cxp_reserve(ctx, S->parent, (size_t)(nv + 1) * sizeof(u64)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->flags, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->scan, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->pts.grow(ctx, (size_t)(nv + 1) * 4 * sizeof(double)))) return rc;
+    if ((rc = S->prio.grow(ctx, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->rep.grow(ctx, (size_t)nv + 16))) return rc;
+    if ((rc = S->alive.grow(ctx, (size_t)nt + 16))) return rc;
+    if ((rc = S->parent.grow(ctx, (size_t)(nv + 1) * sizeof(u64)))) return rc;
+    if ((rc = S->flags.grow(ctx, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->scan.grow(ctx, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
     return CX_OK;
 }
 extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double* points_xyzt, int64_t* out_counts) {
@@ -2569,8 +2546,8 @@ extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double*
     const uint32_t nv = (uint32_t)G->counts.n_vertices, nt = (uint32_t)G->counts.n_triangles;
     hipStream_t st = ctx->stream;
     if ((rc = cxp_reserve4(ctx, S, nv, nt))) return rc;
-    double* pts = (double*)S->pts.p;
-    uint32_t* prio = (uint32_t*)S->prio.p;
+    double* pts = S->pts.as<double>();
+    uint32_t* prio = S->prio.as<uint32_t>();
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t nt2 = 0;
     G->post_assembled = false;
@@ -2629,8 +2606,8 @@ extern "C" int cx_slab4d_finish(cx_ctx* ctx, int32_t nbins, int64_t* out_counts)
         double corner[4];
         for (int a = 0; a < 4; a++) corner[a] = (double)(A->whole[a] - 1);
         const double min_interval = corner[3] * (1.0 / (double)nbins);
-        CXP_HIP(ctx, hipMemcpyAsync(S->pts.p, A->pts, (size_t)nv * 4 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(cxp_k_bin_times_iota, dim3(cxp_blocks(nv)), dim3(256), 0, st, (double*)S->pts.p, nv, min_interval, (uint32_t*)S->prio.p);
+        CXP_HIP(ctx, hipMemcpyAsync(S->pts.get(), A->pts, (size_t)nv * 4 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(cxp_k_bin_times_iota, dim3(cxp_blocks(nv)), dim3(256), 0, st, S->pts.as<double>(), nv, min_interval, S->prio.as<uint32_t>());
         if ((rc = cxp_post4_tets(ctx, S, A->tets, nv, nt, corner, nullptr, counts, &nt2))) return rc;
     }
     S->nv_out = nv; S->nt_out = nt2;
@@ -2649,7 +2626,7 @@ extern "C" int cx_level1_4d_download(cx_ctx* ctx, double* points_xyzt, int32_t* 
     CXP_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     void* d[2] = {(points_xyzt && S->nv_out) ? (void*)points_xyzt : nullptr, (tets && S->nt_out) ? (void*)tets : nullptr};
-    const void* sp[2] = {S->pts.p, S->tri_out.p};
+    const void* sp[2] = {S->pts.get(), S->tri_out.get()};
     const size_t nb[2] = {(size_t)S->nv_out * 4 * sizeof(double), (size_t)S->nt_out * 4 * sizeof(int32_t)};
     return cx_copy_to_host(ctx, 2, d, sp, nb);
 }
@@ -3119,10 +3096,10 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
     cx_post_state* S = ctx->post;
     hipStream_t st = ctx->stream;
     const uint32_t nv = (uint32_t)S->nv_out, nt = (uint32_t)S->nt_out;   // vertices / surviving tetrahedra
-    const double* pts = (const double*)S->pts.p;
-    const uint32_t* prio = (const uint32_t*)S->prio.p;
-    const int32_t* tets = (const int32_t*)S->tri_out.p;
-    uint32_t* misc = (uint32_t*)S->misc.p;
+    const double* pts = S->pts.as<const double>();
+    const uint32_t* prio = S->prio.as<const uint32_t>();
+    const int32_t* tets = S->tri_out.as<const int32_t>();
+    uint32_t* misc = S->misc.as<uint32_t>();
     u64* mm = (u64*)(misc + 16);
     int rc;
     int64_t counts[8] = {nv, 0, 0, 0, 0, 0, 0, 0};
@@ -3132,10 +3109,10 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
         const u64 init[2] = {~0ULL, 0ULL};
         CXP_HIP(ctx, hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(cxp_k_minmax_t, dim3(std::min(cxp_blocks(nv), 2048u)), dim3(256), 0, st, pts, nv, mm);
-        if ((rc = cxp_reserve(ctx, S->flags, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
-        if ((rc = cxp_reserve(ctx, S->scan, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
-        uint32_t* cnt = (uint32_t*)S->flags.p;
-        uint32_t* off = (uint32_t*)S->scan.p;
+        if ((rc = S->flags.grow(ctx, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
+        if ((rc = S->scan.grow(ctx, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
+        uint32_t* cnt = S->flags.as<uint32_t>();
+        uint32_t* off = S->scan.as<uint32_t>();
         cxp_grid4 G4;
         G4.A = G->grid;
         for (int k = 0; k < 4; k++) G4.n[k] = (int)G->n[k];
@@ -3144,7 +3121,7 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
         // where samples EQUAL the isovalue and the determinant below vanishes); CX_TETS_ORIENT=1 (debug) recomputes it from the data
         // (not on a slab assembly: its tetrahedra come from several grids, G->grid is only the last slab's)
         if (!G->post_assembled && cx_debug_knob("CX_TETS_ORIENT", 0))
-            hipLaunchKernelGGL(cxp_k_tets_orient, dim3(cxp_blocks(nt)), dim3(256), 0, st, (int32_t*)S->tri_out.p, nt, prio, G4);
+            hipLaunchKernelGGL(cxp_k_tets_orient, dim3(cxp_blocks(nt)), dim3(256), 0, st, S->tri_out.as<int32_t>(), nt, prio, G4);
         hipLaunchKernelGGL(cxp_k_morph_count, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, nt, pts, prio, mm, cnt);
         if ((rc = cxp_scan(ctx, S, cnt, off, nt, misc + 1))) return rc;
         uint32_t ntri = 0;
@@ -3154,21 +3131,21 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
         CXP_HIP(ctx, hipStreamSynchronize(st));
         S->me_off.clear();
         if (ntri) {
-            if ((rc = cxp_reserve(ctx, S->mpairs, (size_t)ntri * 3 * sizeof(u64)))) return rc;
-            u64* pairs = (u64*)S->mpairs.p;
+            if ((rc = S->mpairs.grow(ctx, (size_t)ntri * 3 * sizeof(u64)))) return rc;
+            u64* pairs = S->mpairs.as<u64>();
             hipLaunchKernelGGL(cxp_k_morph_emit, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, nt, pts, prio, mm, off, pairs);
             // ---- segments
             const size_t np = (size_t)ntri * 3;
             // (n keys of which a third or less are distinct -- every segment shows up in several triangles: the edge-table rule, 5/4 of the
             // bound, keeps the load below 0.8 in the worst case and near 0.25 here with half the slots to clear, flag and scan)
             const u64 ssz = cxp_edge_table_size(np);
-            if ((rc = cxp_reserve(ctx, S->tkeys, ssz * sizeof(u64)))) return rc;
+            if ((rc = S->tkeys.grow(ctx, ssz * sizeof(u64)))) return rc;
             const uint32_t nob = cxp_blocks(ssz, CXP_OCC_BLOCK);
-            if ((rc = cxp_reserve(ctx, S->flags, (size_t)(nob + 16) * sizeof(uint32_t)))) return rc;
-            if ((rc = cxp_reserve(ctx, S->scan, (size_t)(ssz + 16) * sizeof(uint32_t)))) return rc;
-            u64* skeys = (u64*)S->tkeys.p;
-            uint32_t* boff = (uint32_t*)S->flags.p;        // occupied slots per block of 4 096, then their exclusive scan
-            uint32_t* sid = (uint32_t*)S->scan.p;          // segment id per slot, written for occupied slots only
+            if ((rc = S->flags.grow(ctx, (size_t)(nob + 16) * sizeof(uint32_t)))) return rc;
+            if ((rc = S->scan.grow(ctx, (size_t)(ssz + 16) * sizeof(uint32_t)))) return rc;
+            u64* skeys = S->tkeys.as<u64>();
+            uint32_t* boff = S->flags.as<uint32_t>();        // occupied slots per block of 4 096, then their exclusive scan
+            uint32_t* sid = S->scan.as<uint32_t>();          // segment id per slot, written for occupied slots only
             hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, skeys, (size_t)ssz, CXP_EMPTY);
             const u64 smult = std::max<u64>(1, ssz / std::max<u64>(1, (u64)nv));
             hipLaunchKernelGGL(cxp_k_seg_insert, dim3(cxp_blocks(np, CXP_SEG_KEYS)), dim3(256), 0, st, pairs, np, skeys, ssz - 1, smult);
@@ -3177,15 +3154,15 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             uint32_t nseg = 0;
             CXP_HIP(ctx, hipMemcpyAsync(&nseg, misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             CXP_HIP(ctx, hipStreamSynchronize(st));
-            if ((rc = cxp_reserve(ctx, S->msegs, (size_t)(nseg + 1) * 2 * sizeof(int32_t)))) return rc;
-            if ((rc = cxp_reserve(ctx, S->mmid, (size_t)(nseg + 1) * 3 * sizeof(double)))) return rc;
-            if ((rc = cxp_reserve(ctx, S->mtime, ((size_t)(nseg + 1) * 2 + (size_t)(ntri + 1) * 2) * sizeof(double)))) return rc;
-            if ((rc = cxp_reserve(ctx, S->mtris, (size_t)(ntri + 1) * 3 * sizeof(int32_t)))) return rc;
-            int32_t* segs = (int32_t*)S->msegs.p;
-            double* mid = (double*)S->mmid.p;
-            double* stime = (double*)S->mtime.p;
+            if ((rc = S->msegs.grow(ctx, (size_t)(nseg + 1) * 2 * sizeof(int32_t)))) return rc;
+            if ((rc = S->mmid.grow(ctx, (size_t)(nseg + 1) * 3 * sizeof(double)))) return rc;
+            if ((rc = S->mtime.grow(ctx, ((size_t)(nseg + 1) * 2 + (size_t)(ntri + 1) * 2) * sizeof(double)))) return rc;
+            if ((rc = S->mtris.grow(ctx, (size_t)(ntri + 1) * 3 * sizeof(int32_t)))) return rc;
+            int32_t* segs = S->msegs.as<int32_t>();
+            double* mid = S->mmid.as<double>();
+            double* stime = S->mtime.as<double>();
             double* ttime = stime + (size_t)(nseg + 1) * 2;
-            int32_t* tris = (int32_t*)S->mtris.p;
+            int32_t* tris = S->mtris.as<int32_t>();
             hipLaunchKernelGGL(cxp_k_seg_write4, dim3(nob), dim3(256), 0, st, (const u64*)skeys, (size_t)ssz, (const uint32_t*)boff, (const uint32_t*)(misc + 2), nob,
                                pts, sid, segs, mid, stime);
             hipLaunchKernelGGL(cxp_k_tri_segments, dim3(cxp_blocks(ntri)), dim3(256), 0, st, pairs, ntri, skeys, sid, ssz - 1, smult, stime, mm, tris, ttime);
@@ -3193,17 +3170,17 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             // ---- orientation on the segment midpoints, time-compatible neighbours only
             const u64 esz = cxp_edge_table_size((size_t)ntri * 3);
             const u64 emult4 = std::max<u64>(1, esz / std::max<u64>(1, (u64)nseg));
-            if ((rc = cxp_reserve(ctx, S->tkeys, esz * sizeof(u64)))) return rc;
-            if ((rc = cxp_reserve(ctx, S->tvals, esz * sizeof(u64)))) return rc;
-            if ((rc = cxp_reserve(ctx, S->parent, (size_t)ntri * sizeof(u64)))) return rc;
-            if ((rc = cxp_reserve(ctx, S->mnext, (size_t)ntri * 3 * sizeof(uint32_t)))) return rc;
-            if ((rc = cxp_reserve(ctx, S->comp, (size_t)ntri * (3 * sizeof(u64) + sizeof(uint32_t))))) return rc;
-            u64* ekeys = (u64*)S->tkeys.p;
-            u64* eheads = (u64*)S->tvals.p;
-            u64* parent = (u64*)S->parent.p;
+            if ((rc = S->tkeys.grow(ctx, esz * sizeof(u64)))) return rc;
+            if ((rc = S->tvals.grow(ctx, esz * sizeof(u64)))) return rc;
+            if ((rc = S->parent.grow(ctx, (size_t)ntri * sizeof(u64)))) return rc;
+            if ((rc = S->mnext.grow(ctx, (size_t)ntri * 3 * sizeof(uint32_t)))) return rc;
+            if ((rc = S->comp.grow(ctx, (size_t)ntri * (3 * sizeof(u64) + sizeof(uint32_t))))) return rc;
+            u64* ekeys = S->tkeys.as<u64>();
+            u64* eheads = S->tvals.as<u64>();
+            u64* parent = S->parent.as<u64>();
             S->orient_live = false; S->gen++;   // (the 3-D orientation's tables lived here: what cx_comp.hip cached of them is stale)
-            uint32_t* next = (uint32_t*)S->mnext.p;
-            u64* cmaxx = (u64*)S->comp.p;
+            uint32_t* next = S->mnext.as<uint32_t>();
+            u64* cmaxx = S->comp.as<u64>();
             u64* cbest = cmaxx + ntri;
             u64* cmaxv = cbest + ntri;
             uint32_t* cstart = (uint32_t*)(cmaxv + ntri);
@@ -3220,7 +3197,7 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             hipLaunchKernelGGL(cxp_k_comp_maxx, dim3(cxp_blocks(ntri)), dim3(256), 0, st, tris, ntri, mid, parent, cmaxx, nocls);
             // the four kernels that pick a component's start triangle visit the list of triangles AT the component's largest x
             // (cxp_k_comp_list; the list sits where the edge lists' `next` words were: free by now)
-            uint32_t* clist = (uint32_t*)S->mnext.p;
+            uint32_t* clist = S->mnext.as<uint32_t>();
             const uint32_t* cn = misc + 11;
             const dim3 lgrid(std::min(cxp_blocks(ntri), 1024u));
             CXP_HIP(ctx, hipMemsetAsync(misc + 11, 0, sizeof(uint32_t), st));
@@ -3257,7 +3234,7 @@ extern "C" int cx_morph_download(cx_ctx* ctx, double* points_xyzt, int32_t* segm
     cx_post_state* S = ctx->post;
     void* d[3] = {(points_xyzt && S->nv_out) ? (void*)points_xyzt : nullptr, (segments && S->ms_out) ? (void*)segments : nullptr,
                   (triangles && S->mt_out) ? (void*)triangles : nullptr};
-    const void* sp[3] = {S->pts.p, S->msegs.p, S->mtris.p};
+    const void* sp[3] = {S->pts.get(), S->msegs.get(), S->mtris.get()};
     const size_t nb[3] = {(size_t)S->nv_out * 4 * sizeof(double), (size_t)S->ms_out * 2 * sizeof(int32_t), (size_t)S->mt_out * 3 * sizeof(int32_t)};
     return cx_copy_to_host(ctx, 3, d, sp, nb);
 }
@@ -3412,13 +3389,13 @@ static int cxp_sb_ranks(cx_ctx* ctx, cx_post_state* S, const double* range, uint
     const uint32_t nunits = cxp_blocks(n, CXP_SB_UNIT);
     const size_t cells = (size_t)CXP_SB_BINS * nunits;
     if (cells >= 0xFFFFFFFFull) { ctx->err = "cx_morph_triangles: too many morph triangles for the start-time sort"; return CX_ERR_INVALID; }
-    if ((rc = cxp_reserve(ctx, S->mnext, (size_t)n + 64))) return rc;
-    if ((rc = cxp_reserve(ctx, S->flags, (cells + 16) * sizeof(uint32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->scan, (cells + 16) * sizeof(uint32_t)))) return rc;
-    uint8_t* bins = (uint8_t*)S->mnext.p;
-    uint32_t* counts = (uint32_t*)S->flags.p;
-    uint32_t* offs = (uint32_t*)S->scan.p;
-    uint32_t* misc = (uint32_t*)S->misc.p;
+    if ((rc = S->mnext.grow(ctx, (size_t)n + 64))) return rc;
+    if ((rc = S->flags.grow(ctx, (cells + 16) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->scan.grow(ctx, (cells + 16) * sizeof(uint32_t)))) return rc;
+    uint8_t* bins = S->mnext.as<uint8_t>();
+    uint32_t* counts = S->flags.as<uint32_t>();
+    uint32_t* offs = S->scan.as<uint32_t>();
+    uint32_t* misc = S->misc.as<uint32_t>();
     u64* maxdur = (u64*)(misc + 20);
     CXP_HIP(ctx, hipMemsetAsync(counts, 0, cells * sizeof(uint32_t), st));
     CXP_HIP(ctx, hipMemsetAsync(maxdur, 0, sizeof(u64), st));
@@ -3443,26 +3420,26 @@ static int cxp_morph_sort_by_start(cx_ctx* ctx, cx_post_state* S, uint32_t nseg,
     if (!nseg || !ntri) return CX_OK;
     const double lo = cxp_host_from_orderable(mm_host[0]), hi = cxp_host_from_orderable(mm_host[1]);
     const double inv_width = (hi > lo) ? (double)CXP_SB_BINS / (hi - lo) : 0.0;
-    if ((rc = cxp_reserve(ctx, S->msegs2, (size_t)(nseg + 1) * 2 * sizeof(int32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->mtris2, (size_t)(ntri + 1) * 3 * sizeof(int32_t)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->mtime2, ((size_t)(nseg + 1) * 2 + (size_t)(ntri + 1) * 2) * sizeof(double)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->parent, ((size_t)nseg + ntri + 64) * sizeof(uint32_t)))) return rc;
-    uint32_t* rank_s = (uint32_t*)S->parent.p;
+    if ((rc = S->msegs2.grow(ctx, (size_t)(nseg + 1) * 2 * sizeof(int32_t)))) return rc;
+    if ((rc = S->mtris2.grow(ctx, (size_t)(ntri + 1) * 3 * sizeof(int32_t)))) return rc;
+    if ((rc = S->mtime2.grow(ctx, ((size_t)(nseg + 1) * 2 + (size_t)(ntri + 1) * 2) * sizeof(double)))) return rc;
+    if ((rc = S->parent.grow(ctx, ((size_t)nseg + ntri + 64) * sizeof(uint32_t)))) return rc;
+    uint32_t* rank_s = S->parent.as<uint32_t>();
     S->orient_live = false; S->gen++;   // (the 3-D orientation's tables lived here: what cx_comp.hip cached of them is stale)
     uint32_t* rank_t = rank_s + nseg + 16;
-    const int32_t* segs = (const int32_t*)S->msegs.p;
-    const int32_t* tris = (const int32_t*)S->mtris.p;
-    const double* stime = (const double*)S->mtime.p;
+    const int32_t* segs = S->msegs.as<const int32_t>();
+    const int32_t* tris = S->mtris.as<const int32_t>();
+    const double* stime = S->mtime.as<const double>();
     const double* ttime = stime + (size_t)(nseg + 1) * 2;
-    double* stime2 = (double*)S->mtime2.p;
+    double* stime2 = S->mtime2.as<double>();
     double* ttime2 = stime2 + (size_t)(nseg + 1) * 2;
     if ((rc = cxp_sb_ranks(ctx, S, stime, nseg, lo, inv_width, rank_s, S->mbin_s, &S->ms_maxdur))) return rc;
     if ((rc = cxp_sb_ranks(ctx, S, ttime, ntri, lo, inv_width, rank_t, S->mbin_t, &S->mt_maxdur))) return rc;
     // (the segment midpoints are scratch of the orientation, which is over: they stay behind)
     hipLaunchKernelGGL(cxp_k_sb_move_segs, dim3(cxp_blocks(nseg)), dim3(256), 0, st, segs, stime, (const double*)nullptr, nseg, (const uint32_t*)rank_s,
-                       (int32_t*)S->msegs2.p, stime2, (double*)nullptr);
+                       S->msegs2.as<int32_t>(), stime2, (double*)nullptr);
     hipLaunchKernelGGL(cxp_k_sb_move_tris, dim3(cxp_blocks(ntri)), dim3(256), 0, st, tris, ttime, ntri, (const uint32_t*)rank_t, (const uint32_t*)rank_s,
-                       (int32_t*)S->mtris2.p, ttime2);
+                       S->mtris2.as<int32_t>(), ttime2);
     CXP_HIP(ctx, hipStreamSynchronize(st));
     CXP_HIP(ctx, hipGetLastError());
     std::swap(S->msegs, S->msegs2);
@@ -3752,34 +3729,34 @@ extern "C" int cx_morph_eval_many(cx_ctx* ctx, const double* times, int32_t n_ti
     if (!tblocks || !sblocks) return CX_OK;       // every window is empty: every surface is
     const uint32_t ntb = (uint32_t)tblocks, nsb = (uint32_t)sblocks;
     {
-        const size_t before = S->meflags.bytes;     // (not the address: a freed block often comes back at the same one, larger)
-        if ((rc = cxp_reserve(ctx, S->meflags, (size_t)sblocks * CXP_ME_BLOCK + 256))) return rc;
-        if (S->meflags.bytes != before) S->meflags_clean = false;
+        const size_t before = S->meflags.bytes();     // (not the address: a freed block often comes back at the same one, larger)
+        if ((rc = S->meflags.grow(ctx, (size_t)sblocks * CXP_ME_BLOCK + 256))) return rc;
+        if (S->meflags.bytes() != before) S->meflags_clean = false;
     }
-    if ((rc = cxp_reserve(ctx, S->metflag, (size_t)tblocks * CXP_ME_BLOCK + 256))) return rc;
-    if ((rc = cxp_reserve(ctx, S->menew, (size_t)sblocks * CXP_ME_BLOCK * sizeof(uint32_t) + 256))) return rc;
-    if ((rc = cxp_reserve(ctx, S->mecnt, ((size_t)tblocks + sblocks + 4ull * nd + 64) * sizeof(uint32_t) + (2ull * nd + 8) * sizeof(u64)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->medesc, (size_t)(nd + 1) * sizeof(cxp_me_desc)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->me_pts, (size_t)(pts_bound + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = cxp_reserve(ctx, S->me_tri, (size_t)(tri_bound + 1) * 3 * sizeof(int32_t)))) return rc;
+    if ((rc = S->metflag.grow(ctx, (size_t)tblocks * CXP_ME_BLOCK + 256))) return rc;
+    if ((rc = S->menew.grow(ctx, (size_t)sblocks * CXP_ME_BLOCK * sizeof(uint32_t) + 256))) return rc;
+    if ((rc = S->mecnt.grow(ctx, ((size_t)tblocks + sblocks + 4ull * nd + 64) * sizeof(uint32_t) + (2ull * nd + 8) * sizeof(u64)))) return rc;
+    if ((rc = S->medesc.grow(ctx, (size_t)(nd + 1) * sizeof(cxp_me_desc)))) return rc;
+    if ((rc = S->me_pts.grow(ctx, (size_t)(pts_bound + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = S->me_tri.grow(ctx, (size_t)(tri_bound + 1) * 3 * sizeof(int32_t)))) return rc;
     // (the segment flags are a buffer of their own, ALL of it zero between two calls: the next call's windows may be laid out differently)
-    uint8_t* sused = (uint8_t*)S->meflags.p;
-    uint8_t* tflag = (uint8_t*)S->metflag.p;
-    uint32_t* snew = (uint32_t*)S->menew.p;
-    u64* bases = (u64*)S->mecnt.p;                                   // 2 nd + 2 words of 64 bits first (alignment)
+    uint8_t* sused = S->meflags.as<uint8_t>();
+    uint8_t* tflag = S->metflag.as<uint8_t>();
+    uint32_t* snew = S->menew.as<uint32_t>();
+    u64* bases = S->mecnt.as<u64>();                                   // 2 nd + 2 words of 64 bits first (alignment)
     uint32_t* scnt = (uint32_t*)(bases + 2ull * nd + 8);
     uint32_t* tcnt = scnt + nsb + 8;
     uint32_t* totals = tcnt + ntb + 8;
     uint32_t* err = totals + 2ull * nd;                              // (right behind the totals: one copy back for both)
-    cxp_me_desc* Dd = (cxp_me_desc*)S->medesc.p;
-    const double* P4 = (const double*)S->pts.p;
-    const int32_t* segs = (const int32_t*)S->msegs.p;
-    const int32_t* tris = (const int32_t*)S->mtris.p;
-    const double* ttime = (const double*)S->mtime.p + (size_t)(ns + 1) * 2;   // behind the segments' ranges (cx_morph_triangles)
+    cxp_me_desc* Dd = S->medesc.as<cxp_me_desc>();
+    const double* P4 = S->pts.as<const double>();
+    const int32_t* segs = S->msegs.as<const int32_t>();
+    const int32_t* tris = S->mtris.as<const int32_t>();
+    const double* ttime = S->mtime.as<const double>() + (size_t)(ns + 1) * 2;   // behind the segments' ranges (cx_morph_triangles)
     // (the segment flags count as zeroed only while the last call ran to its end; they may have moved since: a larger call reserves anew)
     const bool clean = S->meflags_clean;
     S->meflags_clean = false;
-    if (!clean) CXP_HIP(ctx, hipMemsetAsync(sused, 0, S->meflags.bytes, st));
+    if (!clean) CXP_HIP(ctx, hipMemsetAsync(sused, 0, S->meflags.bytes(), st));
     CXP_HIP(ctx, hipMemcpyAsync(Dd, D, (size_t)(nd + 1) * sizeof(cxp_me_desc), hipMemcpyHostToDevice, st));
     CXP_HIP(ctx, hipMemsetAsync(err, 0, sizeof(uint32_t), st));
     hipLaunchKernelGGL(cxp_k_me_visible, dim3(ntb * 16u), dim3(256), 0, st, (const cxp_me_desc*)Dd, nd, ttime, tris, tflag, sused, err);
@@ -3787,9 +3764,9 @@ extern "C" int cx_morph_eval_many(cx_ctx* ctx, const double* times, int32_t n_ti
     hipLaunchKernelGGL(cxp_k_me_offsets, dim3(2u * nd), dim3(256), 0, st, (const cxp_me_desc*)Dd, nd, scnt, tcnt, totals, bases);
     if (nd > 1u) hipLaunchKernelGGL(cxp_k_me_bases, dim3(1), dim3(256), 0, st, (const uint32_t*)totals, nd, bases);
     hipLaunchKernelGGL(cxp_k_me_points, dim3(nsb), dim3(256), 0, st, (const cxp_me_desc*)Dd, nd, P4, segs, sused, (const uint32_t*)scnt, (const uint32_t*)totals,
-                       (const u64*)bases, snew, (double*)S->me_pts.p);
+                       (const u64*)bases, snew, S->me_pts.as<double>());
     hipLaunchKernelGGL(cxp_k_me_tris, dim3(ntb), dim3(256), 0, st, (const cxp_me_desc*)Dd, nd, tris, (const uint8_t*)tflag, (const uint32_t*)tcnt,
-                       (const uint32_t*)totals, (const u64*)bases, (const uint32_t*)snew, (int32_t*)S->me_tri.p);
+                       (const uint32_t*)totals, (const u64*)bases, (const uint32_t*)snew, S->me_tri.as<int32_t>());
     std::vector<uint32_t> totv(pin ? 0 : (size_t)2 * nd + 1);
     uint32_t* tot = pin ? (uint32_t*)((char*)S->me_pinned + 36864) : totv.data();
     CXP_HIP(ctx, hipMemcpyAsync(tot, totals, ((size_t)2 * nd + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -3812,8 +3789,8 @@ extern "C" int cx_morph_eval_many_download(cx_ctx* ctx, int32_t i, double* point
     CXP_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t* o = &S->me_off[(size_t)i * 4];
     void* d[2] = {(points_xyz && o[1]) ? (void*)points_xyz : nullptr, (triangles && o[3]) ? (void*)triangles : nullptr};
-    const void* sp[2] = {o[1] ? (const void*)((const double*)S->me_pts.p + (size_t)o[0] * 3) : nullptr,
-                         o[3] ? (const void*)((const int32_t*)S->me_tri.p + (size_t)o[2] * 3) : nullptr};
+    const void* sp[2] = {o[1] ? (const void*)(S->me_pts.as<const double>() + (size_t)o[0] * 3) : nullptr,
+                         o[3] ? (const void*)(S->me_tri.as<const int32_t>() + (size_t)o[2] * 3) : nullptr};
     const size_t nb[2] = {(size_t)o[1] * 3 * sizeof(double), (size_t)o[3] * 3 * sizeof(int32_t)};
     return cx_copy_to_host(ctx, 2, d, sp, nb);
 }
@@ -3826,7 +3803,7 @@ extern "C" int cx_morph_eval_many_download_all(cx_ctx* ctx, double* points_xyz, 
     int64_t np_ = 0, nt_ = 0;
     for (size_t i = 0; i + 3 < S->me_off.size(); i += 4) { np_ += S->me_off[i + 1]; nt_ += S->me_off[i + 3]; }
     void* d[2] = {(points_xyz && np_) ? (void*)points_xyz : nullptr, (triangles && nt_) ? (void*)triangles : nullptr};
-    const void* sp[2] = {S->me_pts.p, S->me_tri.p};
+    const void* sp[2] = {S->me_pts.get(), S->me_tri.get()};
     const size_t nb[2] = {(size_t)np_ * 3 * sizeof(double), (size_t)nt_ * 3 * sizeof(int32_t)};
     return cx_copy_to_host(ctx, 2, d, sp, nb);
 }
@@ -3835,8 +3812,8 @@ extern "C" int cx_morph_eval_many_device_ptrs(cx_ctx* ctx, int32_t i, void** poi
     cx_post_state* S = ctx->post;
     if (i < 0 || (size_t)i * 4 >= S->me_off.size()) { ctx->err = "cx_morph_eval_many_device_ptrs: no such surface in the last call"; return CX_ERR_INVALID; }
     const int64_t* o = &S->me_off[(size_t)i * 4];
-    if (points_xyz) *points_xyz = o[1] ? (void*)((double*)S->me_pts.p + (size_t)o[0] * 3) : nullptr;
-    if (triangles) *triangles = o[3] ? (void*)((int32_t*)S->me_tri.p + (size_t)o[2] * 3) : nullptr;
+    if (points_xyz) *points_xyz = o[1] ? (void*)(S->me_pts.as<double>() + (size_t)o[0] * 3) : nullptr;
+    if (triangles) *triangles = o[3] ? (void*)(S->me_tri.as<int32_t>() + (size_t)o[2] * 3) : nullptr;
     return CX_OK;
 }
 extern "C" int cx_morph_eval(cx_ctx* ctx, double t, int64_t* out_counts) {

@@ -422,7 +422,7 @@ extern "C" int cx_select_seeded3d_ex(cx_ctx* ctx, const int32_t* endpoints_ijk, 
     }
     // persistent masks
     {
-        const int rcg = cx_grow(ctx, ctx->tri_keep, ctx->keep_cap, (size_t)nt + (size_t)nv + 64);
+        const int rcg = ctx->tri_keep.grow(ctx, (size_t)nt + (size_t)nv + 64);
         if (rcg) return rcg;
     }
     uint8_t* tri_keep = ctx->tri_keep;
@@ -443,8 +443,8 @@ extern "C" int cx_select_seeded3d_ex(cx_ctx* ctx, const int32_t* endpoints_ijk, 
     do {
         hipError_t e;
 #define CXS_TRY(call) if ((e = (call)) != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e); rc = (e == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP; break; }
-        // (scratch kept in the context between calls: cx_grow only ever grows)
-#define CXS_GRAB(slot, ptr, bytes) { if ((rc = cx_grow(ctx, ctx->seed_buf[slot], ctx->seed_cap[slot], (size_t)(bytes)))) break; ptr = reinterpret_cast<decltype(ptr)>(ctx->seed_buf[slot]); }
+        // (scratch kept in the context between calls: cx_buf::grow only ever grows)
+#define CXS_GRAB(slot, ptr, bytes) { if ((rc = ctx->seed_buf[slot].grow(ctx, (size_t)(bytes)))) break; ptr = ctx->seed_buf[slot].as<std::remove_pointer_t<decltype(ptr)>>(); }
         CXS_GRAB(0, vmap, ((size_t)P.nsamples + 64) * sizeof(uint32_t));
         CXS_GRAB(1, parent, ((size_t)ncells + 64) * sizeof(uint32_t));
         CXS_GRAB(2, abits, ((size_t)P.nsamples / 32 + 64) * sizeof(uint32_t));

@@ -403,7 +403,7 @@ extern "C" int cx_select_seeded4d_ex(cx_ctx* ctx, const int32_t* endpoints_ijkl,
     }
     G.value = S4->value;
     {
-        const int rcg = cx_grow(ctx, S4->tet_keep, S4->keep_cap, (size_t)nt + 64);
+        const int rcg = S4->tet_keep.grow(ctx, (size_t)nt + 64);
         if (rcg) return rcg;
     }
     S4->keep_valid = false;
@@ -421,8 +421,8 @@ extern "C" int cx_select_seeded4d_ex(cx_ctx* ctx, const int32_t* endpoints_ijkl,
     do {
         hipError_t e;
 #define CXS4_TRY(call) if ((e = (call)) != hipSuccess) { ctx->err = std::string(#call) + ": " + hipGetErrorString(e); rc = (e == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP; break; }
-        // (scratch kept in the context between calls, shared with cx_select_seeded3d_ex: cx_grow only ever grows)
-#define CXS4_GRAB(slot, ptr, bytes) { if ((rc = cx_grow(ctx, ctx->seed_buf[slot], ctx->seed_cap[slot], (size_t)(bytes)))) break; ptr = reinterpret_cast<decltype(ptr)>(ctx->seed_buf[slot]); }
+        // (scratch kept in the context between calls, shared with cx_select_seeded3d_ex: cx_buf::grow only ever grows)
+#define CXS4_GRAB(slot, ptr, bytes) { if ((rc = ctx->seed_buf[slot].grow(ctx, (size_t)(bytes)))) break; ptr = ctx->seed_buf[slot].as<std::remove_pointer_t<decltype(ptr)>>(); }
         CXS4_GRAB(0, vmap, (nsamples + 64) * sizeof(uint32_t));
         CXS4_GRAB(1, parent, ((size_t)ncells + 64) * sizeof(uint32_t));
         CXS4_GRAB(3, flag, 2 * ((size_t)ncells + 64));   // flag | seedkeep

@@ -41,22 +41,19 @@ extern "C" int cx_level1_component_labels(cx_ctx* ctx, void** tri_labels_dev, vo
 extern "C" int cx_level1_normals(cx_ctx* ctx, const double* delta3, void** normals_dev);
 
 struct cx_simplify_state {
-    u64* tkeys = nullptr;      size_t tkeys_cap = 0;     // cluster table: keys
-    uint32_t* tfirst = nullptr; size_t tfirst_cap = 0;   // per slot: the smallest member
-    uint32_t* vslot = nullptr; size_t vslot_cap = 0;     // per vertex: its slot (CXS_NONE: dropped)
-    uint32_t* flag = nullptr;  size_t flag_cap = 0;      // first-member flags
-    uint32_t* idx = nullptr;   size_t idx_cap = 0;       // their exclusive scan
-    uint32_t* sums = nullptr;  size_t sums_cap = 0;      // block sums of the scan
-    u64* acc = nullptr;        size_t acc_cap = 0;
-    uint32_t* misc = nullptr;  size_t misc_cap = 0;      // [0] clusters, [1] triangles with three distinct indices, [2] clamped coordinates
+    cx_buf<u64> tkeys;                                   // cluster table: keys
+    cx_buf<uint32_t> tfirst;                             // per slot: the smallest member
+    cx_buf<uint32_t> vslot;                              // per vertex: its slot (CXS_NONE: dropped)
+    cx_buf<uint32_t> flag;                               // first-member flags
+    cx_buf<uint32_t> idx;                                // their exclusive scan
+    cx_buf<uint32_t> sums;                               // block sums of the scan
+    cx_buf<u64> acc;
+    cx_buf<uint32_t> misc;                               // [0] clusters, [1] triangles with three distinct indices, [2] clamped coordinates
 };
 
 void cx_simplify_free(cx_ctx* ctx) {
     cx_simplify_state* Z = ctx->simp;
     if (!Z) return;
-    cx_release(Z->tkeys, Z->tkeys_cap); cx_release(Z->tfirst, Z->tfirst_cap); cx_release(Z->vslot, Z->vslot_cap);
-    cx_release(Z->flag, Z->flag_cap); cx_release(Z->idx, Z->idx_cap); cx_release(Z->sums, Z->sums_cap);
-    cx_release(Z->acc, Z->acc_cap); cx_release(Z->misc, Z->misc_cap);
     delete Z;
     ctx->simp = nullptr;
 }
@@ -363,13 +360,13 @@ extern "C" int cx_level1_simplify(cx_ctx* ctx, const double* cell3, uint32_t fla
     if ((rc = cx_level1_component_labels(ctx, &tl, &vl))) return rc;
     if ((rc = cx_level1_simplify_bufs(ctx, want_normals, count_only, &B))) return rc;
     const u64 tsz = cxs_table_size(nv);
-    if ((rc = cx_grow(ctx, Z->misc, Z->misc_cap, 16))) return rc;
-    if ((rc = cx_grow(ctx, Z->tkeys, Z->tkeys_cap, (size_t)tsz))) return rc;
-    if ((rc = cx_grow(ctx, Z->tfirst, Z->tfirst_cap, (size_t)tsz))) return rc;
-    if ((rc = cx_grow(ctx, Z->vslot, Z->vslot_cap, (size_t)nv + 16))) return rc;
-    if ((rc = cx_grow(ctx, Z->flag, Z->flag_cap, (size_t)nv + 16))) return rc;
-    if ((rc = cx_grow(ctx, Z->idx, Z->idx_cap, (size_t)nv + 16))) return rc;
-    if ((rc = cx_grow(ctx, Z->sums, Z->sums_cap, (size_t)nv / 1024 + 16))) return rc;
+    if ((rc = Z->misc.grow(ctx, 16))) return rc;
+    if ((rc = Z->tkeys.grow(ctx, (size_t)tsz))) return rc;
+    if ((rc = Z->tfirst.grow(ctx, (size_t)tsz))) return rc;
+    if ((rc = Z->vslot.grow(ctx, (size_t)nv + 16))) return rc;
+    if ((rc = Z->flag.grow(ctx, (size_t)nv + 16))) return rc;
+    if ((rc = Z->idx.grow(ctx, (size_t)nv + 16))) return rc;
+    if ((rc = Z->sums.grow(ctx, (size_t)nv / 1024 + 16))) return rc;
     CXS_HIP(ctx, hipMemsetAsync(Z->misc, 0, 16 * sizeof(uint32_t), st));
     uint32_t ncl = 0, n3 = 0, nclamp = 0;
     if (nv) {
@@ -392,7 +389,7 @@ extern "C" int cx_level1_simplify(cx_ctx* ctx, const double* cell3, uint32_t fla
         return CX_OK;
     }
     if (ncl) {
-        if ((rc = cx_grow(ctx, Z->acc, Z->acc_cap, (size_t)ncl * CXS_WORDS + 16))) return rc;
+        if ((rc = Z->acc.grow(ctx, (size_t)ncl * CXS_WORDS + 16))) return rc;
         CXS_HIP(ctx, hipMemsetAsync(Z->acc, 0, (size_t)ncl * CXS_WORDS * sizeof(u64), st));
         hipLaunchKernelGGL(cxs_k_accumulate, cxs_grid(nv), dim3(256), 0, st, V.pts, want_normals ? nsrc : (const double*)nullptr, (const int32_t*)B.map, nv, P, Z->acc,
                            Z->misc + 2);

@@ -36,11 +36,6 @@
 
 void cx_slab4_free(cx_slab4*& A) {
     if (!A) return;
-    cx_release(A->keys, A->keys_cap); cx_release(A->pts, A->pts_cap); cx_release(A->tets, A->tets_cap); cx_release(A->pend, A->pend_cap);
-    cx_release(A->ka, A->ka_cap); cx_release(A->kb, A->kb_cap); cx_release(A->va, A->va_cap); cx_release(A->vb, A->vb_cap);
-    cx_release(A->hist, A->hist_cap); cx_release(A->offs, A->offs_cap); cx_release(A->sums, A->sums_cap);
-    cx_release(A->flag, A->flag_cap); cx_release(A->pos, A->pos_cap);
-    cx_release(A->vmap, A->vmap_cap); cx_release(A->resolved, A->resolved_cap); cx_release(A->cnt, A->cnt_cap);
     delete A;
     A = nullptr;
 }
@@ -265,22 +260,22 @@ extern "C" int cx_slab4d_append(cx_ctx* ctx, int64_t i0, int64_t owned_planes, i
     const size_t cells = (size_t)CXS_BINS * nunits;
     int rc;
     // every reserve first (the assembly keeps its contents), pointers after
-    if ((rc = cx_grow_keep(ctx, A->keys, A->keys_cap, A->nv, (size_t)A->nv + m + 1))) return rc;
-    if ((rc = cx_grow_keep(ctx, A->pts, A->pts_cap, (size_t)A->nv * 4, ((size_t)A->nv + m + 1) * 4))) return rc;
-    if ((rc = cx_grow_keep(ctx, A->tets, A->tets_cap, (size_t)A->nt * 4, ((size_t)A->nt + ntl + 1) * 4))) return rc;
-    if ((rc = cx_grow_keep(ctx, A->pend, A->pend_cap, np, (size_t)m + 1))) return rc;
-    if ((rc = cx_grow(ctx, A->ka, A->ka_cap, (size_t)m + 64))) return rc;
-    if ((rc = cx_grow(ctx, A->kb, A->kb_cap, (size_t)m + 64))) return rc;
-    if ((rc = cx_grow(ctx, A->va, A->va_cap, (size_t)m + 64))) return rc;
-    if ((rc = cx_grow(ctx, A->vb, A->vb_cap, (size_t)m + 64))) return rc;
-    if ((rc = cx_grow(ctx, A->flag, A->flag_cap, (size_t)m + 64))) return rc;
-    if ((rc = cx_grow(ctx, A->pos, A->pos_cap, (size_t)m + 64))) return rc;
-    if ((rc = cx_grow(ctx, A->hist, A->hist_cap, cells + 64))) return rc;
-    if ((rc = cx_grow(ctx, A->offs, A->offs_cap, cells + 64))) return rc;
-    if ((rc = cx_grow(ctx, A->sums, A->sums_cap, std::max(cells, (size_t)m) / 1024 + 64))) return rc;
-    if ((rc = cx_grow(ctx, A->vmap, A->vmap_cap, (size_t)nvl + 1))) return rc;
-    if ((rc = cx_grow(ctx, A->resolved, A->resolved_cap, (size_t)np + 1))) return rc;
-    if ((rc = cx_grow(ctx, A->cnt, A->cnt_cap, (size_t)16))) return rc;
+    if ((rc = A->keys.grow_keep(ctx, A->nv, (size_t)A->nv + m + 1))) return rc;
+    if ((rc = A->pts.grow_keep(ctx, (size_t)A->nv * 4, ((size_t)A->nv + m + 1) * 4))) return rc;
+    if ((rc = A->tets.grow_keep(ctx, (size_t)A->nt * 4, ((size_t)A->nt + ntl + 1) * 4))) return rc;
+    if ((rc = A->pend.grow_keep(ctx, np, (size_t)m + 1))) return rc;
+    if ((rc = A->ka.grow(ctx, (size_t)m + 64))) return rc;
+    if ((rc = A->kb.grow(ctx, (size_t)m + 64))) return rc;
+    if ((rc = A->va.grow(ctx, (size_t)m + 64))) return rc;
+    if ((rc = A->vb.grow(ctx, (size_t)m + 64))) return rc;
+    if ((rc = A->flag.grow(ctx, (size_t)m + 64))) return rc;
+    if ((rc = A->pos.grow(ctx, (size_t)m + 64))) return rc;
+    if ((rc = A->hist.grow(ctx, cells + 64))) return rc;
+    if ((rc = A->offs.grow(ctx, cells + 64))) return rc;
+    if ((rc = A->sums.grow(ctx, std::max(cells, (size_t)m) / 1024 + 64))) return rc;
+    if ((rc = A->vmap.grow(ctx, (size_t)nvl + 1))) return rc;
+    if ((rc = A->resolved.grow(ctx, (size_t)np + 1))) return rc;
+    if ((rc = A->cnt.grow(ctx, (size_t)16))) return rc;
     hipStream_t st = ctx->stream;
     uint32_t h[2] = {0, 0};
     CXS_HIP(ctx, hipMemsetAsync(A->cnt, 0, 16 * sizeof(uint32_t), st));
@@ -348,7 +343,7 @@ int cx_slab4_check(cx_ctx* ctx, cx_slab4* A) {
     }
     if (!A->nt) return CX_OK;
     int rc;
-    if ((rc = cx_grow(ctx, A->cnt, A->cnt_cap, (size_t)16))) return rc;
+    if ((rc = A->cnt.grow(ctx, (size_t)16))) return rc;
     uint32_t bad = 0;
     const size_t n = (size_t)A->nt * 4;
     CXS_HIP(ctx, hipMemsetAsync(A->cnt + 4, 0, sizeof(uint32_t), ctx->stream));

@@ -45,7 +45,7 @@ const uint64_t* cx_pent_lut_device();
 // i0 .. i1 is marched with origin (i0,0,0,0) and, unless it is the last, with plane i1 as a halo.  Its OWNED vertices (lower lattice
 // point below the halo) are appended in ascending edge id, so the whole assembly is in ascending GLOBAL edge id; tetrahedra are
 // appended with assembly indices, a reference to a halo vertex is held as -(1 + h) until the next append resolves entry h of `pend`.
-// Every assembly buffer is grown by cx_slab4_grow (which keeps its contents); kernels get pointers taken after the last grow.
+// The four assembly buffers grow by cx_buf::grow_keep (which keeps their contents); kernels get pointers taken after the last grow.
 struct cx_slab4 {
     bool open = false;              // between cx_slab4d_begin and cx_slab4d_finish
     int64_t whole[4] = {0, 0, 0, 0};
@@ -55,49 +55,37 @@ struct cx_slab4 {
     uint32_t nv = 0, nt = 0;        // assembled vertices / tetrahedra
     uint32_t npend = 0;             // halo vertices of the last slab, resolved by the next append
     uint32_t pend_t0 = 0;           // first tetrahedron of the last slab (the only ones that may hold pending references)
-    uint64_t* keys = nullptr;       // [nv] global edge id ((linear index in the whole volume << 4) | direction)
-    size_t keys_cap = 0;
-    double* pts = nullptr;          // [nv * 4] float64 crossing points in the whole volume's lattice (t not yet binned)
-    size_t pts_cap = 0;
-    int32_t* tets = nullptr;        // [nt * 4]
-    size_t tets_cap = 0;
-    uint32_t* pend = nullptr;       // [npend] the next slab's local edge ids of the last slab's halo vertices
-    size_t pend_cap = 0;
+    cx_buf<uint64_t> keys;          // [nv] global edge id ((linear index in the whole volume << 4) | direction)
+    cx_buf<double> pts;             // [nv * 4] float64 crossing points in the whole volume's lattice (t not yet binned)
+    cx_buf<int32_t> tets;           // [nt * 4]
+    cx_buf<uint32_t> pend;          // [npend] the next slab's local edge ids of the last slab's halo vertices
     // scratch of one append: radix sort of (edge id, source) pairs, digit counts per unit, their scan, vertex map
-    uint32_t *ka = nullptr, *kb = nullptr, *va = nullptr, *vb = nullptr;
-    size_t ka_cap = 0, kb_cap = 0, va_cap = 0, vb_cap = 0;
-    uint32_t *hist = nullptr, *offs = nullptr, *sums = nullptr, *flag = nullptr, *pos = nullptr;
-    size_t hist_cap = 0, offs_cap = 0, sums_cap = 0, flag_cap = 0, pos_cap = 0;
-    int32_t *vmap = nullptr, *resolved = nullptr;
-    size_t vmap_cap = 0, resolved_cap = 0;
-    uint32_t* cnt = nullptr;        // [16] device counters
-    size_t cnt_cap = 0;
+    cx_buf<uint32_t> ka, kb, va, vb;
+    cx_buf<uint32_t> hist, offs, sums, flag, pos;
+    cx_buf<int32_t> vmap, resolved;
+    cx_buf<uint32_t> cnt;           // [16] device counters
 };
 void cx_slab4_free(cx_slab4*& A);
 
 struct cx_state4 {
-    const float* grid = nullptr;
-    float* grid_owned = nullptr;
-    size_t grid_owned_bytes = 0;
+    const float* grid = nullptr;     // the samples in use: grid_owned or an adopted array (not owned)
+    cx_buf<float> grid_owned;
     int64_t n[4] = {0, 0, 0, 0};
-    uint2* items = nullptr;
-    size_t items_cap = 0;
-    uint64_t* info = nullptr;
-    size_t info_cap = 0;
-    float4* verts = nullptr;
-    uint32_t* vkeys = nullptr;
-    size_t vkeys_cap = 0;
-    uint4* cells = nullptr;
-    int32_t* tets = nullptr;
-    uint32_t vcap = 0, ccap = 0, tcap = 0;
-    uint64_t* hash_xyz = nullptr;
-    size_t hash_cap = 0;
-    uint32_t* queue = nullptr;
-    uint4* rounds = nullptr;
-    size_t rounds_cap = 0;
-    uint32_t qcap = 0;
-    uint32_t* signbits = nullptr;
-    size_t signbits_cap = 0;
+    cx_buf<uint2> items;
+    cx_buf<uint64_t> info;
+    cx_buf<float4> verts;
+    cx_buf<uint32_t> vkeys;          // one per vertex of `verts`
+    cx_buf<uint4> cells;
+    cx_buf<int32_t> tets;            // four per tetrahedron
+    cx_buf<uint64_t> hash_xyz;
+    cx_buf<uint32_t> queue;
+    cx_buf<uint4> rounds;
+    cx_buf<uint32_t> signbits;
+    // the capacities as the kernels and the ABI count them (cx_params4, cx_counts)
+    uint32_t vcap() const { return (uint32_t)verts.cap(); }
+    uint32_t ccap() const { return (uint32_t)cells.cap(); }
+    uint32_t tcap() const { return (uint32_t)(tets.cap() / 4u); }
+    uint32_t qcap() const { return (uint32_t)queue.cap(); }
     int64_t hash_key[7] = {-1, -1, -1, -1, -1, -1, -1};
     int64_t origin[4] = {0, 0, 0, 0};
     bool extracted = false;
@@ -110,8 +98,6 @@ struct cx_state4 {
     double value = 0.0;
     cx_counts counts = {0, 0, 0, 0};
     // seeded selection (cx_select_seeded4d): mask over the Level-0 tetrahedra, valid until the next extraction
-    uint8_t* tet_keep = nullptr;
-    size_t keep_cap = 0;
+    cx_buf<uint8_t> tet_keep;
     bool keep_valid = false;
 };
-

@@ -588,6 +588,11 @@ int cx_timing_read(cx_ctx* ctx, double ms[8], int* n);
  * the stream kernel against ("also report measured stream-read BW on the box").  No counterpart in the reference. */
 int cx_measure_read_bandwidth(cx_ctx* ctx, const void* device_ptr, int64_t bytes, int reps, double* out_GBps);
 
+/* Device memory held in the library's growable buffers: bytes live now and hipMalloc calls made so far, of this context or -- with
+ * ctx == NULL -- of the whole process (what is left after cx_ctx_destroy).  Either output may be NULL.  Buffers only ever grow, so
+ * `allocations` standing still across a call says that the call allocated nothing.  No counterpart in the reference. */
+int cx_device_bytes(cx_ctx* ctx, int64_t* live_bytes, int64_t* allocations);
+
 /* diagnostics: per-wave s_memtime stamps of the stream kernel (4 words per wave: [0] start, [1] end; [2..3]
  * unused).  words > 0 allocates, host != NULL copies out, 0/NULL frees. */
 int cx_debug_stamps(cx_ctx* ctx, int64_t words, unsigned long long* host);

@@ -455,8 +455,8 @@ def test_bit_identical():
 # ---- 8. full size ------------------------------------------------------------------------------------------------------------
 def test_bench_field_at_full_size():
     """the 512^3 bench field, cell 4, with normals: cluster and distinct-triangle counts against the restatement's clustering stage
-    (vectorised numpy), positions on a 1/64 sample of the clusters with Python integers.  The context exposes no allocation counter:
-    the clause about hipMalloc on a second call is not checked here."""
+    (vectorised numpy), positions on a 1/64 sample of the clusters with Python integers.  (That a second call allocates nothing is checked at small
+    size, tests/test_gpu_buffers.py.)"""
     torch = pytest.importorskip("torch")
     from contourist_amd import _ffi, synthetic
     dev = torch.device("cuda", 0)
