@@ -39,6 +39,22 @@ COMPONENT_DTYPE = np.dtype([("triangles", "<i8"), ("vertices", "<i8"), ("area", 
                             ("bbox_lo", "<f8", (3,)), ("bbox_hi", "<f8", (3,)), ("flipped", "<i4"), ("closed", "<i4"),
                             ("first_triangle", "<i8"), ("reserved", "<f8", (1,))])
 
+class cx_topology(ctypes.Structure):
+    "one record of cx_level1_topology (include/contourist_hip.h): 64 bytes"
+    _fields_ = [("triangles", ctypes.c_int64), ("vertices", ctypes.c_int64), ("edges", ctypes.c_int64), ("boundary_edges", ctypes.c_int64),
+                ("nonmanifold_edges", ctypes.c_int64), ("euler", ctypes.c_int64), ("boundary_loops", ctypes.c_int32), ("genus", ctypes.c_int32),
+                ("nonsimple_loops", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class cx_loop(ctypes.Structure):
+    "one record of cx_level1_boundary_loops: 16 bytes"
+    _fields_ = [("component", ctypes.c_int32), ("simple", ctypes.c_int32), ("first", ctypes.c_uint32), ("count", ctypes.c_uint32)]
+
+
+TOPOLOGY_DTYPE = np.dtype([("triangles", "<i8"), ("vertices", "<i8"), ("edges", "<i8"), ("boundary_edges", "<i8"), ("nonmanifold_edges", "<i8"),
+                           ("euler", "<i8"), ("boundary_loops", "<i4"), ("genus", "<i4"), ("nonsimple_loops", "<i4"), ("reserved", "<i4")])
+LOOP_DTYPE = np.dtype([("component", "<i4"), ("simple", "<i4"), ("first", "<u4"), ("count", "<u4")])
+
 # every symbol include/contourist_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "cx_ctx_create", "cx_ctx_destroy", "cx_last_error", "cx_set_stream", "cx_synchronize",
@@ -47,6 +63,7 @@ SYMBOLS = [
     "cx_postprocess3d", "cx_postprocess3d_ex", "cx_level0_points_f64", "cx_postprocess3d_mesh", "cx_select_seeded3d", "cx_select_seeded3d_ex", "cx_seeded_masks_download", "cx_set_reference_corner", "cx_level1_download", "cx_level1_device_ptrs", "cx_level1_download_keys", "cx_postprocess3d_shard_begin", "cx_postprocess3d_shard_boundary", "cx_postprocess3d_shard_candidates", "cx_postprocess3d_shard_finish", "cx_level1_write", "cx_surface_geometry",
     "cx_level0_normals", "cx_level0_normals_download", "cx_level1_normals", "cx_level1_normals_download", "cx_level0_sample_grid", "cx_level1_sample_grid",
     "cx_level1_components", "cx_level1_components_download", "cx_level1_component_labels", "cx_level1_component_labels_download", "cx_level1_keep_components",
+    "cx_level1_topology", "cx_level1_topology_download", "cx_level1_boundary_loops", "cx_level1_boundary_loops_download",
     "cx_level1_simplify", "cx_level1_simplify_map", "cx_level1_simplify_map_download",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
@@ -208,6 +225,10 @@ def load():
         "cx_level1_component_labels": [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)],
         "cx_level1_component_labels_download": [vp, vp, vp],
         "cx_level1_keep_components": [vp, vp, vp],
+        "cx_level1_topology": [vp, ctypes.POINTER(i64), ctypes.POINTER(vp)],
+        "cx_level1_topology_download": [vp, vp],
+        "cx_level1_boundary_loops": [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp)],
+        "cx_level1_boundary_loops_download": [vp, vp, vp],
         "cx_level1_simplify": [vp, vp, ctypes.c_uint32, vp, vp],
         "cx_level1_simplify_map": [vp, ctypes.POINTER(vp)],
         "cx_level1_simplify_map_download": [vp, vp],
@@ -696,6 +717,38 @@ class Context(object):
         out = np.zeros(8, dtype=np.int64)
         self._check_attr(self.lib.cx_level1_keep_components(self.handle, keep.ctypes.data if len(keep) else None, out.ctypes.data))
         return dict(n_vertices=int(out[0]), n_triangles=int(out[1]), n_components=int(out[4]))
+
+    # ---- topology of the Level-1 mesh (cx_topo.hip): Euler number, genus, boundary loops ----------------------------------------
+    def level1_topology(self, device=False):
+        """the topology of the Level-1 mesh's components as a numpy structured array (TOPOLOGY_DTYPE: triangles, vertices, edges,
+        boundary_edges, nonmanifold_edges, euler, boundary_loops, genus, nonsimple_loops), row c = component c.
+        device=True: the records as a torch int32 tensor (nc, 16) on the GPU (64 bytes per row, the layout of cx_topology)"""
+        nc, p = ctypes.c_int64(0), ctypes.c_void_p()
+        self._check_attr(self.lib.cx_level1_topology(self.handle, ctypes.byref(nc), ctypes.byref(p)))
+        if device:
+            import torch
+            return self._device_view(p.value or 0, (int(nc.value), 16), "<i4", torch.int32)
+        table = np.zeros(int(nc.value), dtype=TOPOLOGY_DTYPE)
+        if len(table):
+            self._check_attr(self.lib.cx_level1_topology_download(self.handle, table.ctypes.data))
+        return table
+
+    def level1_boundary_loops(self, device=False):
+        """(loops, vertices): the boundary loops of the Level-1 mesh as a numpy structured array (LOOP_DTYPE: component, simple,
+        first, count) and the int32 vertex indices (device order of the points) of all loops, loop l in
+        vertices[first : first + count]: in cyclic order for a simple loop, the tails of its edges for a non-simple one.
+        device=True: torch int32 tensors on the GPU, the loops as (L, 4) rows in the layout of cx_loop"""
+        nl, nb, lp, vp = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check_attr(self.lib.cx_level1_boundary_loops(self.handle, ctypes.byref(nl), ctypes.byref(nb), ctypes.byref(lp), ctypes.byref(vp)))
+        if device:
+            import torch
+            return (self._device_view(lp.value or 0, (int(nl.value), 4), "<i4", torch.int32),
+                    self._device_view(vp.value or 0, (int(nb.value),), "<i4", torch.int32))
+        loops, verts = np.zeros(int(nl.value), dtype=LOOP_DTYPE), np.zeros(int(nb.value), dtype=np.int32)
+        if len(loops) or len(verts):
+            self._check_attr(self.lib.cx_level1_boundary_loops_download(self.handle, loops.ctypes.data if len(loops) else None,
+                                                                         verts.ctypes.data if len(verts) else None))
+        return loops, verts
 
     # ---- simplification of the Level-1 mesh by vertex clustering (cx_simplify.hip) ----------------------------------------------
     def level1_simplify(self, cell, flags=0):

@@ -59,6 +59,7 @@ extern "C" int cx_ctx_destroy(cx_ctx* ctx) {
     cx_xfer_free(ctx);
     cx_post_free(ctx);
     cx_comp_free(ctx);
+    cx_topo_free(ctx);
     cx_simplify_free(ctx);
     cx_state4_free(ctx);
     cx_state2_free(ctx);

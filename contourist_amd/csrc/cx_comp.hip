@@ -423,6 +423,15 @@ static int cxc_labels(cx_ctx* ctx, const char* who, cx_level1_comp_view* V, cx_c
     return CX_OK;
 }
 
+// what cx_topo.hip reads: the view, the labels of the current mesh (made here if need be) and the number of components
+int cx_comp_labels_get(cx_ctx* ctx, const char* who, cx_level1_comp_view* V, const int32_t** tlab, const int32_t** vlab, uint32_t* nc) {
+    cx_comp_state* C = nullptr;
+    const int rc = cxc_labels(ctx, who, V, &C);
+    if (rc) return rc;
+    *tlab = C->tlab.as<const int32_t>(); *vlab = C->vlab.as<const int32_t>(); *nc = C->nc;
+    return CX_OK;
+}
+
 static bool cxc_md_ok(const double* md) {
     if (!md) return true;
     for (int a = 0; a < 6; a++)

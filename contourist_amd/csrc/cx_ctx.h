@@ -143,6 +143,8 @@ struct cx_ctx {
     struct cx_comp_state* comp = nullptr;
     // vertex clustering of the Level-1 mesh (cx_simplify.hip): cluster table, accumulators, scans, kept between calls
     struct cx_simplify_state* simp = nullptr;
+    // topology of the Level-1 mesh (cx_topo.hip): edge-use table, boundary loops and the table, kept between calls
+    struct cx_topo_state* topo = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -280,6 +282,9 @@ int cx_level1_carried_normals(cx_ctx* ctx, const double** nrm, uint32_t* nv);
 int cx_level1_simplify_map_get(cx_ctx* ctx, const int32_t** map, uint32_t* n);
 // cx_comp.hip
 void cx_comp_free(cx_ctx* ctx);
+int cx_comp_labels_get(cx_ctx* ctx, const char* who, cx_level1_comp_view* V, const int32_t** tlab, const int32_t** vlab, uint32_t* nc);
+// cx_topo.hip
+void cx_topo_free(cx_ctx* ctx);
 // cx_simplify.hip
 void cx_simplify_free(cx_ctx* ctx);
 // cx_api4d.hip

@@ -87,10 +87,21 @@ def sort_rows(tris):
 _sorted_rows = sort_rows
 
 
-def select_components(table, mask=None, largest=None, min_triangles=None, min_area=None, closed=None):
+def _in_range(values, want):
+    "values == want for an int, lo <= values <= hi for a (lo, hi) pair"
+    values = np.asarray(values, dtype=np.int64)
+    if np.ndim(want) == 0:
+        return values == int(want)
+    lo, hi = want
+    return (values >= int(lo)) & (values <= int(hi))
+
+
+def select_components(table, mask=None, largest=None, min_triangles=None, min_area=None, closed=None, topology=None, genus=None,
+                      boundary_loops=None):
     """boolean keep mask over the rows of a component table (fields triangles, area, closed).  The selectors combine with AND:
     mask (one entry per component), largest=k (the k components with the most triangles, ties by id), min_triangles,
-    min_area, closed (True: closed ones only, False: open ones only)."""
+    min_area, closed (True: closed ones only, False: open ones only); genus and boundary_loops (an int, or an inclusive
+    (lo, hi) range) read the rows of `topology`, the table of cx_level1_topology for the same components."""
     n = len(table)
     keep = np.ones(n, dtype=bool)
     if mask is not None:
@@ -112,4 +123,11 @@ def select_components(table, mask=None, largest=None, min_triangles=None, min_ar
         keep &= np.asarray(table["area"]) >= float(min_area)
     if closed is not None:
         keep &= (np.asarray(table["closed"]) != 0) == bool(closed)
+    if genus is not None or boundary_loops is not None:
+        if topology is None or len(topology) != n:
+            raise ValueError("genus and boundary_loops need the topology table of the same %d components" % n)
+        if genus is not None:
+            keep &= _in_range(topology["genus"], genus)
+        if boundary_loops is not None:
+            keep &= _in_range(topology["boundary_loops"], boundary_loops)
     return keep

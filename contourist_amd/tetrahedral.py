@@ -311,13 +311,34 @@ class GridContour3d(object):
         _pts, tris = ctx.download_level1(self._post)
         return tl[surface_geometry.row_order(tris)], vl
 
-    def keep_components(self, mask=None, largest=None, min_triangles=None, min_area=None, closed=None, clean=True):
+    def topology(self, clean=True, device=False):
+        """the topology of the components of get_points_and_triangles() as a numpy structured array (_ffi.TOPOLOGY_DTYPE:
+        triangles, vertices, edges, boundary_edges, nonmanifold_edges, euler, boundary_loops, genus, nonsimple_loops), counted on
+        the device; row c is component c of components().  device=True: a torch int32 tensor (nc, 16) on the GPU."""
+        return self._ensure_post(clean).level1_topology(device)
+
+    def boundary_loops(self, clean=True, device=False, mins=None, delta=None):
+        """the boundary curves of the mesh, where the array's rim or a seeded range cut it open: (loops, vertices, points).
+        loops: a numpy structured array (_ffi.LOOP_DTYPE: component, simple, first, count); vertices: int32 row numbers of
+        get_points_and_triangles()[0], loop l in vertices[first : first + count], in cyclic order for a simple loop; points:
+        a list with one (count, 3) float64 array per loop (grid coordinates; world = grid * delta + mins when given).
+        device=True: (loops, vertices) as torch int32 tensors on the GPU, the loops as (L, 4) rows."""
+        ctx = self._ensure_post(clean)
+        if device:
+            return ctx.level1_boundary_loops(device=True)
+        loops, verts = ctx.level1_boundary_loops()
+        return loops, verts, _loop_points(ctx.download_level1(self._post)[0], loops, verts, mins, delta)
+
+    def keep_components(self, mask=None, largest=None, min_triangles=None, min_area=None, closed=None, clean=True, genus=None,
+                        boundary_loops=None):
         """drop components of the mesh ON THE DEVICE: mask (one entry per component), largest=k (most triangles, ties by id),
-        min_triangles, min_area (grid coordinates), closed; the selectors combine with AND.  Afterwards
+        min_triangles, min_area (grid coordinates), closed, genus and boundary_loops (an int or an inclusive (lo, hi) range, read
+        from topology()); the selectors combine with AND.  Afterwards
         get_points_and_triangles(), vertex_normals(), vertex_values(), write_mesh(), components() give the filtered mesh
         (until the next march).  -> dict(n_vertices, n_triangles, n_components)"""
         ctx = self._ensure_post(clean)
-        keep = surface_geometry.select_components(ctx.level1_components(), mask, largest, min_triangles, min_area, closed)
+        topo = ctx.level1_topology() if (genus is not None or boundary_loops is not None) else None
+        keep = surface_geometry.select_components(ctx.level1_components(), mask, largest, min_triangles, min_area, closed, topo, genus, boundary_loops)
         counts = ctx.level1_keep_components(keep)
         self._post = dict(self._post, **counts)
         return counts
@@ -644,13 +665,22 @@ class Delta3DContour(object):
         "GridContour3d.component_labels of this isosurface"
         return self.contour_maker.component_labels(clean, device)
 
-    def keep_components(self, mask=None, largest=None, min_triangles=None, min_area=None, closed=None, clean=True):
+    def topology(self, clean=True, device=False):
+        "GridContour3d.topology of this isosurface"
+        return self.contour_maker.topology(clean, device)
+
+    def boundary_loops(self, clean=True, device=False):
+        "GridContour3d.boundary_loops of this isosurface, the points in WORLD coordinates"
+        return self.contour_maker.boundary_loops(clean, device, self.grid.mins, self.grid.delta)
+
+    def keep_components(self, mask=None, largest=None, min_triangles=None, min_area=None, closed=None, clean=True, genus=None, boundary_loops=None):
         "GridContour3d.keep_components; min_area in WORLD units"
         maker = self.contour_maker
         if min_area is not None:
-            keep = surface_geometry.select_components(self.components(clean), mask, largest, min_triangles, min_area, closed)
+            topo = self.topology(clean) if (genus is not None or boundary_loops is not None) else None
+            keep = surface_geometry.select_components(self.components(clean), mask, largest, min_triangles, min_area, closed, topo, genus, boundary_loops)
             return maker.keep_components(mask=keep, clean=clean)
-        return maker.keep_components(mask, largest, min_triangles, None, closed, clean)
+        return maker.keep_components(mask, largest, min_triangles, None, closed, clean, genus, boundary_loops)
 
     def simplify(self, cell=None, target_triangles=None, by_component=True, clean=True, normals="auto"):
         "GridContour3d.simplify of this isosurface: `cell` in VOXELS (grid units), a scalar or one per axis"
@@ -789,6 +819,16 @@ class TriangulatedIsosurfaces(Delta3DContour):
         Delta3DContour.__init__(self, grid, value, segment_endpoints, linear_interpolate=linear_interpolate)
 
 
+def _loop_points(points, loops, verts, mins=None, delta=None):
+    "one (count, 3) float64 array per boundary loop: the rows of `points` its vertex indices name, mapped to grid * delta + mins"
+    P = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    if mins is not None or delta is not None:
+        d = np.ones(3) if delta is None else np.asarray(delta, dtype=np.float64)
+        m = np.zeros(3) if mins is None else np.asarray(mins, dtype=np.float64)
+        P = P * d + m if len(P) else P
+    return [P[verts[int(r["first"]):int(r["first"]) + int(r["count"])]] for r in loops]
+
+
 class LevelResult(tuple):
     """(value, points, triangles) of one level of MultiLevelIsosurfaces.levels(), with the vertex attributes of that level:
     vertex_normals() / vertex_values(field).  They read the level's mesh on the device, so they work until the
@@ -827,11 +867,25 @@ class LevelResult(tuple):
         _pts, tris = ctx.download_level1(self._post)
         return tl[surface_geometry.row_order(tris)], vl
 
-    def keep_components(self, mask=None, largest=None, min_triangles=None, min_area=None, closed=None):
+    def topology(self, device=False):
+        "the topology of the level's components (GridContour3d.topology)"
+        return self._ctx().level1_topology(device)
+
+    def boundary_loops(self, device=False):
+        "the boundary loops of the level's mesh (GridContour3d.boundary_loops), the points in world coordinates"
+        ctx = self._ctx()
+        if device:
+            return ctx.level1_boundary_loops(device=True)
+        loops, verts = ctx.level1_boundary_loops()
+        return loops, verts, _loop_points(ctx.download_level1(self._post)[0], loops, verts, self._mins, self._delta)
+
+    def keep_components(self, mask=None, largest=None, min_triangles=None, min_area=None, closed=None, genus=None, boundary_loops=None):
         """drop components of the level's mesh on the device (GridContour3d.keep_components, min_area in world units); the tuple's
         own points and triangles are the unfiltered ones: mesh() downloads the filtered mesh"""
         ctx = self._ctx()
-        keep = surface_geometry.select_components(ctx.level1_components(self._mins, self._delta), mask, largest, min_triangles, min_area, closed)
+        topo = ctx.level1_topology() if (genus is not None or boundary_loops is not None) else None
+        keep = surface_geometry.select_components(ctx.level1_components(self._mins, self._delta), mask, largest, min_triangles, min_area, closed,
+                                                  topo, genus, boundary_loops)
         counts = ctx.level1_keep_components(keep)
         self._post = dict(self._post, **counts)
         return counts

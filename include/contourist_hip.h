@@ -377,6 +377,56 @@ int cx_level1_component_labels(cx_ctx* ctx, void** tri_labels_dev, void** vert_l
 int cx_level1_component_labels_download(cx_ctx* ctx, int32_t* tri_labels, int32_t* vert_labels);
 int cx_level1_keep_components(cx_ctx* ctx, const uint8_t* keep, int64_t* out_counts);
 
+/* ---- topology of the Level-1 mesh: Euler number, genus, boundary loops -------------------------------------------------------------
+ * What a caller asks right after cx_level1_components: is this piece a blob or riddled with handles, where has the array's rim cut
+ * the surface open (the boundary curves as polylines, to cap, measure or show them), and can a simplified mesh still be trusted
+ * (edges with three or more triangles).  All integers, counted exactly: no hash decides anything here.
+ * Defined for ANY Level-1 mesh, whatever the multiplicity of its edges.  Input: the current unsharded Level-1 mesh -- triangles T in
+ * device order -- and the triangle labels of cx_level1_component_labels.
+ * Edge             an unordered pair {T[t][k], T[t][(k+1)%3]}; its multiplicity is the number of (t, k) that produce it.  All the
+ *                  triangles on one edge belong to one component (the orientation step links every pair that shares an edge).
+ * Per component c:
+ *   triangles          F
+ *   vertices           V, the number of DISTINCT vertex indices its triangles use.  A vertex two components share counts in both:
+ *                      this is NOT cx_component.vertices, which counts every vertex once, for its smallest label.
+ *   edges              E, its distinct edges
+ *   boundary_edges     edges of multiplicity 1
+ *   nonmanifold_edges  edges of multiplicity 3 or more
+ *   euler              V - E + F
+ *   boundary_loops     b, the number of its boundary loops; nonsimple_loops: those that are not simple
+ *   genus              (2 - euler - b) / 2 when that is a non-negative integer and nonmanifold_edges == 0, otherwise -1.  It is the
+ *                      genus proper only for an orientable 2-manifold with boundary: non-orientability is not detected (a Moebius
+ *                      strip gives -1 only because 2 - euler - b is odd for it), nor are vertex pinches.
+ * Boundary loop    a connected component of this graph: the nodes are the boundary edges of ONE mesh component, two nodes are linked
+ *                  when the edges share a vertex.  A loop is simple when every vertex on it lies on exactly two of its edges (an
+ *                  edge whose two ends are one vertex makes its loop non-simple).
+ * Loop ids         0 .. L-1 over the whole mesh, in ascending order of the smallest 3*t + k among the loop's edges.
+ * Loop vertices    one int32 array of length B, the total number of boundary edges, holds every loop's `count` entries from `first`
+ *                  on, the loops in id order.  A simple loop is stored as its vertices in cyclic order: it starts at T[t][k] of its
+ *                  smallest (t, k) and runs in that edge's direction, T[t][k] -> T[t][(k+1)%3].  A non-simple loop is stored as the
+ *                  tail vertices T[t][k] of its edges in ascending 3*t + k.
+ * The results live in buffers of the context, are made on the first request and cached per generation of the mesh: a new post-pass,
+ * cx_level1_keep_components and cx_level1_simplify start a new one, after which they are rebuilt on request; the device pointers are
+ * valid until then (kernels are enqueued on the context's stream).  An empty mesh has 0 components and 0 loops (null pointers).
+ * Limits: fewer than 2^30 triangles (the edge table holds 4 slots of 16 bytes per triangle -- 64 bytes per triangle -- and 3*t + k
+ * is a 32-bit word) and fewer than 2^30 boundary edges; CX_ERR_UNSUPPORTED with a message past them.
+ * CX_ERR_INVALID without a Level-1 mesh; CX_ERR_UNSUPPORTED after cx_postprocess3d_shard_*; CX_ERR_STATE when the tables of the
+ * orientation step are gone (see the components above).  Meshes of cx_postprocess3d_mesh are served.  Reproducible: every array is
+ * the same byte for byte in every call and context. */
+typedef struct cx_topology {             /* 64 bytes, plain data */
+    int64_t triangles, vertices, edges, boundary_edges, nonmanifold_edges, euler;
+    int32_t boundary_loops, genus;       /* genus -1: not defined, see above */
+    int32_t nonsimple_loops, reserved;
+} cx_topology;
+typedef struct cx_loop {                 /* 16 bytes, plain data */
+    int32_t component, simple;
+    uint32_t first, count;               /* slice of the loop-vertex array */
+} cx_loop;
+int cx_level1_topology(cx_ctx* ctx, int64_t* n_components, void** table_dev);
+int cx_level1_topology_download(cx_ctx* ctx, cx_topology* out);
+int cx_level1_boundary_loops(cx_ctx* ctx, int64_t* n_loops, int64_t* n_boundary_edges, void** loops_dev, void** vertices_dev);
+int cx_level1_boundary_loops_download(cx_ctx* ctx, cx_loop* loops, int32_t* vertices);
+
 /* ---- simplification: vertex clustering of the Level-1 mesh on the device ---------------------------------------------------------
  * (The reference's flatten=True is serial LP decimation, a different algorithm with different output; it stays unsupported.)
  * Input: the current unsharded Level-1 mesh of the context -- points P (float64, grid coordinates), triangles T (device order) --
