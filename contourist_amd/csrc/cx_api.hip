@@ -8,15 +8,6 @@
 
 #include "cx_ctx.h"
 
-#define CX_HIP(ctx, call)                                                                        \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
 static int fail(cx_ctx* ctx, int code, const char* msg) {
     if (ctx) ctx->err = msg;
     return code;

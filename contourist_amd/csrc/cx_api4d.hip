@@ -8,15 +8,6 @@
 
 #include "cx_state4.h"
 
-#define CX4_HIP(ctx, call)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
 void cx_state4_free(cx_ctx* ctx) {
     cx_state4* S = ctx->s4;
     if (!S) return;
@@ -44,22 +35,22 @@ static int set_dims4(cx_ctx* ctx, cx_state4* S, int64_t n0, int64_t n1, int64_t 
 
 extern "C" int cx_grid4d_upload(cx_ctx* ctx, const float* host, int64_t n0, int64_t n1, int64_t n2, int64_t n3) {
     if (!ctx || !host) return CX_ERR_INVALID;
-    CX4_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_state4* S;
     int rc = state4(ctx, &S);
     if (rc) return rc;
     if ((rc = set_dims4(ctx, S, n0, n1, n2, n3))) return rc;
     const size_t bytes = (size_t)(n0 * n1 * n2 * n3) * sizeof(float);
     if ((rc = S->grid_owned.grow(ctx, bytes / sizeof(float)))) return rc;
-    CX4_HIP(ctx, hipMemcpyAsync(S->grid_owned, host, bytes, hipMemcpyHostToDevice, ctx->stream));
-    CX4_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CX_HIP(ctx, hipMemcpyAsync(S->grid_owned, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     S->grid = S->grid_owned;
     return CX_OK;
 }
 
 extern "C" int cx_grid4d_adopt_device(cx_ctx* ctx, const void* device_ptr, int64_t n0, int64_t n1, int64_t n2, int64_t n3) {
     if (!ctx || !device_ptr) return CX_ERR_INVALID;
-    CX4_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_state4* S;
     int rc = state4(ctx, &S);
     if (rc) return rc;
@@ -133,19 +124,19 @@ static int enqueue4(cx_ctx* ctx, cx_state4* S, double value, uint32_t flags) {
         if ((rc = S->items.grow(ctx, need))) return rc;
         P.items = S->items;
     }
-    CX4_HIP(ctx, hipMemsetAsync(ctx->counters + CX_CNT_WORDS, 0, CX_CNT_WORDS * sizeof(uint32_t), ctx->stream));
+    CX_HIP(ctx, hipMemsetAsync(ctx->counters + CX_CNT_WORDS, 0, CX_CNT_WORDS * sizeof(uint32_t), ctx->stream));
     cx_launch_signbits4d(P, ctx->stream);
     cx_launch_classify4d(P, ctx->stream);
     cx_launch_emit_tets(P, ctx->stream);
-    CX4_HIP(ctx, hipGetLastError());
-    CX4_HIP(ctx, hipMemcpyAsync(ctx->counters_host + CX_CNT_WORDS, ctx->counters + CX_CNT_WORDS, CX_CNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    CX_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipMemcpyAsync(ctx->counters_host + CX_CNT_WORDS, ctx->counters + CX_CNT_WORDS, CX_CNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     return CX_OK;
 }
 // the counters of the attempt that was enqueued last: 0 = the extraction stands, 1 = a buffer was too small and has been grown (run
 // the attempt again), < 0: error
 static int settle4(cx_ctx* ctx, cx_state4* S, double value, cx_counts* out) {
     int rc;
-    CX4_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     cx_counts c;
     c.n_cells = ctx->counters_host[CX_CNT_WORDS + CX_CNT_CELLS];
     c.n_vertices = ctx->counters_host[CX_CNT_WORDS + CX_CNT_VERTS];
@@ -173,7 +164,7 @@ static int settle4(cx_ctx* ctx, cx_state4* S, double value, cx_counts* out) {
 }
 static int begin4(cx_ctx* ctx, cx_state4** Sout, double value) {
     if (!ctx) return CX_ERR_INVALID;
-    CX4_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_state4* S;
     int rc = state4(ctx, &S);
     if (rc) return rc;
@@ -219,7 +210,7 @@ extern "C" int cx_counts4d_get(cx_ctx* ctx, cx_counts* out) {
     if (!ctx) return CX_ERR_INVALID;
     cx_state4* S = ctx->s4;
     if (!S || !S->pending) { if (ctx) ctx->err = "cx_counts4d_get: no cx_extract4d_async in flight"; return CX_ERR_STATE; }
-    CX4_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     S->pending = false;
     const int rc = settle4(ctx, S, S->pending_value, out);
     if (rc == 0) return CX_OK;
@@ -231,14 +222,14 @@ extern "C" int cx_level0_4d_download(cx_ctx* ctx, float* verts_xyzt, uint32_t* e
     if (!ctx) return CX_ERR_INVALID;
     cx_state4* S = ctx->s4;
     if (!S || !S->extracted) { ctx->err = "no valid 4-D extraction"; return CX_ERR_STATE; }
-    CX4_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     if (verts_xyzt && S->counts.n_vertices)
-        CX4_HIP(ctx, hipMemcpyAsync(verts_xyzt, S->verts, (size_t)S->counts.n_vertices * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+        CX_HIP(ctx, hipMemcpyAsync(verts_xyzt, S->verts, (size_t)S->counts.n_vertices * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     if (edge_ids && S->counts.n_vertices)
-        CX4_HIP(ctx, hipMemcpyAsync(edge_ids, S->vkeys, (size_t)S->counts.n_vertices * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        CX_HIP(ctx, hipMemcpyAsync(edge_ids, S->vkeys, (size_t)S->counts.n_vertices * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (tets && S->counts.n_triangles)
-        CX4_HIP(ctx, hipMemcpyAsync(tets, S->tets, (size_t)S->counts.n_triangles * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    CX4_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        CX_HIP(ctx, hipMemcpyAsync(tets, S->tets, (size_t)S->counts.n_triangles * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CX_OK;
 }
 

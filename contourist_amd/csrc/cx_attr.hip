@@ -15,15 +15,6 @@
 
 #include "cx_ctx.h"
 
-#define CXA_HIP(ctx, call)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
 typedef float cxa_v4f __attribute__((ext_vector_type(4)));
 
 struct cxa_dims {
@@ -206,7 +197,6 @@ static bool cxa_delta_ok(const double* delta3) {
         if (!(delta3[a] > 0.0) || !std::isfinite(delta3[a])) return false;
     return true;
 }
-static inline dim3 cxa_grid(uint32_t n) { return dim3((n + 255u) / 256u); }
 
 // the second grid as the kernels read it: the caller's device pointer, or a copy of the host array in a buffer of the context
 static int cxa_second_grid(cx_ctx* ctx, const char* who, const void* grid, int32_t dtype, int on_device, cx_grid_ref* out) {
@@ -215,8 +205,8 @@ static int cxa_second_grid(cx_ctx* ctx, const char* who, const void* grid, int32
     const size_t bytes = (size_t)(ctx->n0 * ctx->n1 * ctx->n2) * cx_dtype_size(dtype);
     const int rc = ctx->attr_grid.grow(ctx, bytes);
     if (rc) return rc;
-    CXA_HIP(ctx, hipMemcpyAsync(ctx->attr_grid, grid, bytes, hipMemcpyHostToDevice, ctx->stream));
-    CXA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the caller's array may go away when this returns
+    CX_HIP(ctx, hipMemcpyAsync(ctx->attr_grid, grid, bytes, hipMemcpyHostToDevice, ctx->stream));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the caller's array may go away when this returns
     *out = {ctx->attr_grid, dtype};
     return CX_OK;
 }
@@ -224,7 +214,7 @@ static int cxa_second_grid(cx_ctx* ctx, const char* who, const void* grid, int32
 // Level 0: the current extraction and its vertex count (one synchronisation the first time the counts are asked for)
 static int cxa_level0(cx_ctx* ctx, const char* who, uint32_t* nv) {
     if (!ctx->extracted || !ctx->grid.p) { ctx->err = std::string(who) + ": no valid extraction"; return CX_ERR_INVALID; }
-    CXA_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_counts c;
     const int rc = cx_counts_get(ctx, &c);
     if (rc) return rc;
@@ -245,11 +235,11 @@ extern "C" int cx_level0_normals(cx_ctx* ctx, const double* delta3, void** norma
     const float d0 = delta3 ? (float)delta3[0] : 1.0f, d1 = delta3 ? (float)delta3[1] : 1.0f, d2 = delta3 ? (float)delta3[2] : 1.0f;
     cxa_v4f* out = ctx->attr_n0.as<cxa_v4f>();
 #define CX_LAUNCH(DT)                                                                                                                          \
-    if (delta3) hipLaunchKernelGGL((cx_k_vertex_normals<DT, true>), cxa_grid(nv), dim3(256), 0, ctx->stream, ctx->grid, ctx->verts, out, nv, D, d0, d1, d2); \
-    else hipLaunchKernelGGL((cx_k_vertex_normals<DT, false>), cxa_grid(nv), dim3(256), 0, ctx->stream, ctx->grid, ctx->verts, out, nv, D, d0, d1, d2);
+    if (delta3) hipLaunchKernelGGL((cx_k_vertex_normals<DT, true>), dim3(cx_blocks(nv)), dim3(256), 0, ctx->stream, ctx->grid, ctx->verts, out, nv, D, d0, d1, d2); \
+    else hipLaunchKernelGGL((cx_k_vertex_normals<DT, false>), dim3(cx_blocks(nv)), dim3(256), 0, ctx->stream, ctx->grid, ctx->verts, out, nv, D, d0, d1, d2);
     CX_DISPATCH_DTYPE(ctx->grid.dtype, CX_LAUNCH)
 #undef CX_LAUNCH
-    CXA_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipGetLastError());
     if (normals_dev) *normals_dev = ctx->attr_n0;
     return CX_OK;
 }
@@ -273,10 +263,10 @@ extern "C" int cx_level0_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtyp
     if (!nv) return CX_OK;
     if (ctx->attr_v0.cap() < nv && (rc = ctx->attr_v0.grow(ctx, (size_t)nv + nv / 16u + 64u))) return rc;
     const uint32_t n2 = (uint32_t)ctx->n2, plane = (uint32_t)(ctx->n1 * ctx->n2), ns = (uint32_t)(ctx->n0 * ctx->n1 * ctx->n2);
-#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_vertex_sample<DT>), cxa_grid(nv), dim3(256), 0, ctx->stream, B, ctx->verts, ctx->attr_v0, nv, n2, plane, ns);
+#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_vertex_sample<DT>), dim3(cx_blocks(nv)), dim3(256), 0, ctx->stream, B, ctx->verts, ctx->attr_v0, nv, n2, plane, ns);
     CX_DISPATCH_DTYPE(dtype, CX_LAUNCH)
 #undef CX_LAUNCH
-    CXA_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipGetLastError());
     if (values_dev) *values_dev = ctx->attr_v0;
     if (values_host) return cx_copy_to_host1(ctx, values_host, ctx->attr_v0, (size_t)nv * sizeof(float));
     return CX_OK;
@@ -284,7 +274,7 @@ extern "C" int cx_level0_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtyp
 
 // Level 1: the view of the post-pass and the edge {a, b, ratio} of every output vertex in ctx->attr_e1
 static int cxa_level1(cx_ctx* ctx, const char* who, cx_level1_view* V) {
-    CXA_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     int rc = cx_level1_attr_view(ctx, who, V);
     if (rc) return rc;
     if (!ctx->extracted || !ctx->grid.p) { ctx->err = std::string(who) + ": no valid extraction"; return CX_ERR_INVALID; }
@@ -294,10 +284,10 @@ static int cxa_level1(cx_ctx* ctx, const char* who, cx_level1_view* V) {
     const uint32_t n2 = (uint32_t)ctx->n2, plane = (uint32_t)(ctx->n1 * ctx->n2), ns = (uint32_t)(ctx->n0 * ctx->n1 * ctx->n2);
     const double* A64 = ctx->grid64_valid ? ctx->grid64 : nullptr;
     cxa_edge1* edges = ctx->attr_e1.as<cxa_edge1>();
-#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_edges<DT>), cxa_grid(V->nv), dim3(256), 0, ctx->stream, ctx->grid, A64, V->keys, V->nv, n2, plane, ns, ctx->last.value, edges);
+#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_edges<DT>), dim3(cx_blocks(V->nv)), dim3(256), 0, ctx->stream, ctx->grid, A64, V->keys, V->nv, n2, plane, ns, ctx->last.value, edges);
     CX_DISPATCH_DTYPE(ctx->grid.dtype, CX_LAUNCH)
 #undef CX_LAUNCH
-    CXA_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipGetLastError());
     return CX_OK;
 }
 
@@ -327,7 +317,7 @@ static int cxa_carried(cx_ctx* ctx, const double* delta3, void** normals_dev, ui
     if (!nv) return 1;
     if (hipSetDevice(ctx->device) != hipSuccess) { *rc = cxa_fail(ctx, CX_ERR_HIP, "cx_level1_normals: hipSetDevice"); return 1; }
     if (ctx->attr_n1.cap() < (size_t)nv * 3u && (*rc = ctx->attr_n1.grow(ctx, ((size_t)nv + nv / 16u + 64u) * 3u))) return 1;
-    hipLaunchKernelGGL(cx_k_carried_normals, cxa_grid(nv), dim3(256), 0, ctx->stream, N, nv, delta3 ? 1 : 0, delta3 ? delta3[0] : 1.0, delta3 ? delta3[1] : 1.0,
+    hipLaunchKernelGGL(cx_k_carried_normals, dim3(cx_blocks(nv)), dim3(256), 0, ctx->stream, N, nv, delta3 ? 1 : 0, delta3 ? delta3[0] : 1.0, delta3 ? delta3[1] : 1.0,
                        delta3 ? delta3[2] : 1.0, ctx->attr_n1);
     if (hipGetLastError() != hipSuccess) { *rc = cxa_fail(ctx, CX_ERR_HIP, "cx_level1_normals: launch of the carried normals failed"); return 1; }
     if (normals_dev) *normals_dev = ctx->attr_n1;
@@ -349,10 +339,10 @@ extern "C" int cx_level1_normals(cx_ctx* ctx, const double* delta3, void** norma
     const double* A64 = ctx->grid64_valid ? ctx->grid64 : nullptr;
     const cxa_edge1* edges = ctx->attr_e1.as<cxa_edge1>();
     const double d0 = delta3 ? delta3[0] : 1.0, d1 = delta3 ? delta3[1] : 1.0, d2 = delta3 ? delta3[2] : 1.0;
-#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_normals<DT>), cxa_grid(V.nv), dim3(256), 0, ctx->stream, ctx->grid, A64, edges, V.vflip, V.nv, D, delta3 ? 1 : 0, d0, d1, d2, ctx->attr_n1);
+#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_normals<DT>), dim3(cx_blocks(V.nv)), dim3(256), 0, ctx->stream, ctx->grid, A64, edges, V.vflip, V.nv, D, delta3 ? 1 : 0, d0, d1, d2, ctx->attr_n1);
     CX_DISPATCH_DTYPE(ctx->grid.dtype, CX_LAUNCH)
 #undef CX_LAUNCH
-    CXA_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipGetLastError());
     if (normals_dev) *normals_dev = ctx->attr_n1;
     return CX_OK;
 }
@@ -382,10 +372,10 @@ extern "C" int cx_level1_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtyp
     if (!V.nv) return CX_OK;
     if (ctx->attr_v1.cap() < V.nv && (rc = ctx->attr_v1.grow(ctx, (size_t)V.nv + V.nv / 16u + 64u))) return rc;
     const cxa_edge1* edges = ctx->attr_e1.as<cxa_edge1>();
-#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_sample<DT>), cxa_grid(V.nv), dim3(256), 0, ctx->stream, B, edges, V.nv, ctx->attr_v1);
+#define CX_LAUNCH(DT) hipLaunchKernelGGL((cx_k_level1_sample<DT>), dim3(cx_blocks(V.nv)), dim3(256), 0, ctx->stream, B, edges, V.nv, ctx->attr_v1);
     CX_DISPATCH_DTYPE(dtype, CX_LAUNCH)
 #undef CX_LAUNCH
-    CXA_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipGetLastError());
     if (values_dev) *values_dev = ctx->attr_v1;
     if (values_host) return cx_copy_to_host1(ctx, values_host, ctx->attr_v1, (size_t)V.nv * sizeof(double));
     return CX_OK;

@@ -19,17 +19,7 @@
 #include <vector>
 
 #include "cx_ctx.h"
-
-#define CXC_HIP(ctx, call)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
-typedef unsigned long long u64;
+#include "cx_dev.h"
 
 // accumulator words per component
 enum {
@@ -74,81 +64,6 @@ void cx_comp_free(cx_ctx* ctx) {
 }
 
 // ---- device helpers -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 cxc_mix(u64 x) {      // (cxp_mix of cx_post.hip)
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
-    x ^= x >> 33;
-    return x;
-}
-// total order on doubles as unsigned integers, and back
-__device__ __forceinline__ u64 cxc_orderable(double x) {
-    const u64 b = (u64)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-}
-__device__ __forceinline__ double cxc_from_orderable(u64 o) {
-    const u64 b = (o >> 63) ? (o & 0x7FFFFFFFFFFFFFFFULL) : ~o;
-    return __longlong_as_double((long long)b);
-}
-__device__ __forceinline__ u64 cxc_shfl_xor64(u64 v, int o) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
-    return ((u64)hi << 32) | lo;
-}
-// butterflies over the 64 lanes of the wave: every lane ends with the result
-__device__ __forceinline__ long long cxc_wave_add(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (long long)cxc_shfl_xor64((u64)v, o);
-    return v;
-}
-__device__ __forceinline__ u64 cxc_wave_xor(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v ^= cxc_shfl_xor64(v, o);
-    return v;
-}
-__device__ __forceinline__ u64 cxc_wave_min(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const u64 w = cxc_shfl_xor64(v, o); v = w < v ? w : v; }
-    return v;
-}
-__device__ __forceinline__ u64 cxc_wave_max(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const u64 w = cxc_shfl_xor64(v, o); v = w > v ? w : v; }
-    return v;
-}
-// signed 64-bit value into a 128-bit two's complement accumulator {low, high}: the carry out of the low word follows from the value
-// the atomic returns, so the sum is exact modulo 2^128 in any order
-__device__ __forceinline__ void cxc_add128(u64* w, long long v) {
-    if (v == 0) return;
-    const u64 lo = (u64)v;
-    u64 hi = v < 0 ? ~0ULL : 0ULL;
-    const u64 old = atomicAdd(&w[0], lo);
-    if (old + lo < old) hi += 1ULL;
-    if (hi) atomicAdd(&w[1], hi);
-}
-// monotonic minimum / maximum with a plain read first (cxp_max64 of cx_post.hip)
-__device__ __forceinline__ void cxc_max64(u64* addr, u64 v) {
-    if (__hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= v) return;
-    atomicMax(addr, v);
-}
-__device__ __forceinline__ void cxc_min64(u64* addr, u64 v) {
-    if (__hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= v) return;
-    atomicMin(addr, v);
-}
-// the 128-bit sum as a double, rounded once (the top 64 bits with a sticky bit), times 2^-q
-__device__ __forceinline__ double cxc_to_double128(u64 lo, u64 hi, int q) {
-    const bool neg = (hi >> 63) != 0ULL;
-    if (neg) { lo = ~lo + 1ULL; hi = ~hi + (lo == 0ULL ? 1ULL : 0ULL); }
-    double r;
-    if (hi == 0ULL) r = ldexp((double)lo, -q);
-    else {
-        const int s = __clzll((long long)hi);
-        u64 top = s ? ((hi << s) | (lo >> (64 - s))) : hi;
-        const u64 rest = s ? (lo << s) : lo;
-        if (rest) top |= 1ULL;
-        r = ldexp((double)top, 64 - s - q);
-    }
-    return neg ? -r : r;
-}
-
 // term * 2^q as an integer; a term past the bound the scale was chosen for (|term| 2^q <= 2^54: vertices farther from the centre of the
 // grid box than its diagonal, e.g. a caller's mesh that does not fit the corner it was handed over with) is clamped there and reported
 __device__ __forceinline__ long long cxc_fixed(double scaled, bool& over) {
@@ -207,10 +122,10 @@ __device__ __forceinline__ void cxc_lane_atomics(u64* w, long long ia, long long
                                                  u64 lo0, u64 lo1, u64 lo2, u64 hi0, u64 hi1, u64 hi2) {
     atomicAdd(&w[CXC_W_NT], 1ULL);
     atomicXor(&w[CXC_W_XOR], ex);
-    cxc_add128(&w[CXC_W_AREA], ia); cxc_add128(&w[CXC_W_VOL], iv);
-    cxc_add128(&w[CXC_W_MOM], im0); cxc_add128(&w[CXC_W_MOM + 2], im1); cxc_add128(&w[CXC_W_MOM + 4], im2);
-    cxc_min64(&w[CXC_W_LO], lo0); cxc_min64(&w[CXC_W_LO + 1], lo1); cxc_min64(&w[CXC_W_LO + 2], lo2);
-    cxc_max64(&w[CXC_W_HI], hi0); cxc_max64(&w[CXC_W_HI + 1], hi1); cxc_max64(&w[CXC_W_HI + 2], hi2);
+    cxd_add128(&w[CXC_W_AREA], ia); cxd_add128(&w[CXC_W_VOL], iv);
+    cxd_add128(&w[CXC_W_MOM], im0); cxd_add128(&w[CXC_W_MOM + 2], im1); cxd_add128(&w[CXC_W_MOM + 4], im2);
+    cxd_min64(&w[CXC_W_LO], lo0); cxd_min64(&w[CXC_W_LO + 1], lo1); cxd_min64(&w[CXC_W_LO + 2], lo2);
+    cxd_max64(&w[CXC_W_HI], hi0); cxd_max64(&w[CXC_W_HI + 1], hi1); cxd_max64(&w[CXC_W_HI + 2], hi2);
 }
 // One lane per triangle in the order of tri_out.  The lanes of a wave that share a label reduce among themselves and ONE of them
 // touches memory; nearly every wave of a real mesh holds one label (neighbouring triangles come from neighbouring cells), the others
@@ -239,9 +154,9 @@ __global__ __launch_bounds__(256) void cxc_k_measure(const int32_t* __restrict__
                     const double g = pts[(size_t)v[k] * 3 + a];
                     p[k][a] = M.world ? g * M.d[a] + M.m[a] : g;
                 }
-            lo0 = cxc_orderable(fmin(p[0][0], fmin(p[1][0], p[2][0]))); hi0 = cxc_orderable(fmax(p[0][0], fmax(p[1][0], p[2][0])));
-            lo1 = cxc_orderable(fmin(p[0][1], fmin(p[1][1], p[2][1]))); hi1 = cxc_orderable(fmax(p[0][1], fmax(p[1][1], p[2][1])));
-            lo2 = cxc_orderable(fmin(p[0][2], fmin(p[1][2], p[2][2]))); hi2 = cxc_orderable(fmax(p[0][2], fmax(p[1][2], p[2][2])));
+            lo0 = cxd_orderable(fmin(p[0][0], fmin(p[1][0], p[2][0]))); hi0 = cxd_orderable(fmax(p[0][0], fmax(p[1][0], p[2][0])));
+            lo1 = cxd_orderable(fmin(p[0][1], fmin(p[1][1], p[2][1]))); hi1 = cxd_orderable(fmax(p[0][1], fmax(p[1][1], p[2][1])));
+            lo2 = cxd_orderable(fmin(p[0][2], fmin(p[1][2], p[2][2]))); hi2 = cxd_orderable(fmax(p[0][2], fmax(p[1][2], p[2][2])));
             const double e1x = p[1][0] - p[0][0], e1y = p[1][1] - p[0][1], e1z = p[1][2] - p[0][2];
             const double e2x = p[2][0] - p[0][0], e2y = p[2][1] - p[0][1], e2z = p[2][2] - p[0][2];
             const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
@@ -258,7 +173,7 @@ __global__ __launch_bounds__(256) void cxc_k_measure(const int32_t* __restrict__
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 const uint32_t a = v[k], b = v[(k + 1) % 3];
-                ex ^= cxc_mix(((u64)(a < b ? a : b) << 32) | (u64)(a < b ? b : a));
+                ex ^= cxd_mix(((u64)(a < b ? a : b) << 32) | (u64)(a < b ? b : a));
             }
         }
     }
@@ -280,19 +195,19 @@ __global__ __launch_bounds__(256) void cxc_k_measure(const int32_t* __restrict__
             continue;
         }
         // (|term| * 2^q <= 2^54: the sum of 64 lanes stays inside 64 bits)
-        const long long sa = cxc_wave_add(mine ? ia : 0LL), sv = cxc_wave_add(mine ? iv : 0LL);
-        const long long s0 = cxc_wave_add(mine ? im0 : 0LL), s1 = cxc_wave_add(mine ? im1 : 0LL), s2 = cxc_wave_add(mine ? im2 : 0LL);
-        const u64 sx = cxc_wave_xor(mine ? ex : 0ULL);
-        const u64 l0 = cxc_wave_min(mine ? lo0 : ~0ULL), l1 = cxc_wave_min(mine ? lo1 : ~0ULL), l2 = cxc_wave_min(mine ? lo2 : ~0ULL);
-        const u64 h0 = cxc_wave_max(mine ? hi0 : 0ULL), h1 = cxc_wave_max(mine ? hi1 : 0ULL), h2 = cxc_wave_max(mine ? hi2 : 0ULL);
+        const long long sa = cxd_wave_add(mine ? ia : 0LL), sv = cxd_wave_add(mine ? iv : 0LL);
+        const long long s0 = cxd_wave_add(mine ? im0 : 0LL), s1 = cxd_wave_add(mine ? im1 : 0LL), s2 = cxd_wave_add(mine ? im2 : 0LL);
+        const u64 sx = cxd_wave_xor(mine ? ex : 0ULL);
+        const u64 l0 = cxd_wave_min(mine ? lo0 : ~0ULL), l1 = cxd_wave_min(mine ? lo1 : ~0ULL), l2 = cxd_wave_min(mine ? lo2 : ~0ULL);
+        const u64 h0 = cxd_wave_max(mine ? hi0 : 0ULL), h1 = cxd_wave_max(mine ? hi1 : 0ULL), h2 = cxd_wave_max(mine ? hi2 : 0ULL);
         if ((int)lane == leader) {
             u64* w = acc + (size_t)k * CXC_WORDS;
             atomicAdd(&w[CXC_W_NT], (u64)__popcll(grp));
             if (sx) atomicXor(&w[CXC_W_XOR], sx);
-            cxc_add128(&w[CXC_W_AREA], sa); cxc_add128(&w[CXC_W_VOL], sv);
-            cxc_add128(&w[CXC_W_MOM], s0); cxc_add128(&w[CXC_W_MOM + 2], s1); cxc_add128(&w[CXC_W_MOM + 4], s2);
-            cxc_min64(&w[CXC_W_LO], l0); cxc_min64(&w[CXC_W_LO + 1], l1); cxc_min64(&w[CXC_W_LO + 2], l2);
-            cxc_max64(&w[CXC_W_HI], h0); cxc_max64(&w[CXC_W_HI + 1], h1); cxc_max64(&w[CXC_W_HI + 2], h2);
+            cxd_add128(&w[CXC_W_AREA], sa); cxd_add128(&w[CXC_W_VOL], sv);
+            cxd_add128(&w[CXC_W_MOM], s0); cxd_add128(&w[CXC_W_MOM + 2], s1); cxd_add128(&w[CXC_W_MOM + 4], s2);
+            cxd_min64(&w[CXC_W_LO], l0); cxd_min64(&w[CXC_W_LO + 1], l1); cxd_min64(&w[CXC_W_LO + 2], l2);
+            cxd_max64(&w[CXC_W_HI], h0); cxd_max64(&w[CXC_W_HI + 1], h1); cxd_max64(&w[CXC_W_HI + 2], h2);
         }
     }
 #endif
@@ -321,14 +236,14 @@ __global__ void cxc_k_finish(const u64* __restrict__ acc, const uint32_t* __rest
     cx_component r;
     r.triangles = (int64_t)w[CXC_W_NT];
     r.vertices = (int64_t)w[CXC_W_NV];
-    r.area = cxc_to_double128(w[CXC_W_AREA], w[CXC_W_AREA + 1], qa);
-    r.volume = cxc_to_double128(w[CXC_W_VOL], w[CXC_W_VOL + 1], qv);
+    r.area = cxd_to_double128(w[CXC_W_AREA], w[CXC_W_AREA + 1], qa);
+    r.volume = cxd_to_double128(w[CXC_W_VOL], w[CXC_W_VOL + 1], qv);
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-        const double mom = cxc_to_double128(w[CXC_W_MOM + 2 * a], w[CXC_W_MOM + 2 * a + 1], qm);
+        const double mom = cxd_to_double128(w[CXC_W_MOM + 2 * a], w[CXC_W_MOM + 2 * a + 1], qm);
         r.centroid[a] = r.area > 0.0 ? M.o[a] + mom / r.area : 0.0;
-        r.bbox_lo[a] = cxc_from_orderable(w[CXC_W_LO + a]);
-        r.bbox_hi[a] = cxc_from_orderable(w[CXC_W_HI + a]);
+        r.bbox_lo[a] = cxd_from_orderable(w[CXC_W_LO + a]);
+        r.bbox_hi[a] = cxd_from_orderable(w[CXC_W_HI + a]);
     }
     const uint32_t root = first[c];
     r.flipped = (int32_t)(cflip[root] & 1ULL);
@@ -381,7 +296,6 @@ __global__ void cxc_k_keep_vert(const double* __restrict__ pts, const uint32_t* 
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static inline dim3 cxc_grid(size_t n) { return dim3((unsigned)((n + 255) / 256 ? (n + 255) / 256 : 1)); }
 
 static int cxc_state(cx_ctx* ctx, cx_comp_state** out) {
     if (!ctx->comp) ctx->comp = new (std::nothrow) cx_comp_state();
@@ -392,7 +306,7 @@ static int cxc_state(cx_ctx* ctx, cx_comp_state** out) {
 
 // labels of the current mesh (cached per generation of the mesh)
 static int cxc_labels(cx_ctx* ctx, const char* who, cx_level1_comp_view* V, cx_comp_state** Cout) {
-    CXC_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     int rc = cx_level1_comp_view_get(ctx, who, V);
     if (rc) return rc;
     cx_comp_state* C;
@@ -404,20 +318,20 @@ static int cxc_labels(cx_ctx* ctx, const char* who, cx_level1_comp_view* V, cx_c
     hipStream_t st = ctx->stream;
     uint32_t nc = 0;
     if ((rc = C->vlab.grow(ctx, (size_t)nv + 16))) return rc;
-    if (nv) hipLaunchKernelGGL(cxc_k_fill32, cxc_grid(nv), dim3(256), 0, st, C->vlab, nv, nt ? 0x7FFFFFFFu : 0xFFFFFFFFu);
+    if (nv) hipLaunchKernelGGL(cxc_k_fill32, cx_grid1(nv), dim3(256), 0, st, C->vlab, nv, nt ? 0x7FFFFFFFu : 0xFFFFFFFFu);
     if (nt) {
         if ((rc = C->tlab.grow(ctx, (size_t)nt + 16))) return rc;
         if ((rc = C->tidx.grow(ctx, (size_t)nt + 16))) return rc;
         if ((rc = C->sums.grow(ctx, (size_t)nt / 1024 + 16))) return rc;
-        hipLaunchKernelGGL(cxc_k_roots, cxc_grid(nt), dim3(256), 0, st, V->parent, nt, C->tlab);
+        hipLaunchKernelGGL(cxc_k_roots, cx_grid1(nt), dim3(256), 0, st, V->parent, nt, C->tlab);
         if ((rc = cx_scan_u32(ctx, C->tlab, C->tidx, nt, C->sums, C->misc))) return rc;
-        CXC_HIP(ctx, hipMemcpyAsync(&nc, C->misc, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CXC_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipMemcpyAsync(&nc, C->misc, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
         if ((rc = C->first.grow(ctx, (size_t)nc + 16))) return rc;
-        hipLaunchKernelGGL(cxc_k_labels, cxc_grid(nt), dim3(256), 0, st, V->parent, C->tidx, V->tri, nt, nv, C->tlab.as<int32_t>(), C->vlab.as<int32_t>(), C->first);
-        hipLaunchKernelGGL(cxc_k_labels_unused, cxc_grid(nv), dim3(256), 0, st, C->vlab.as<int32_t>(), nv);
+        hipLaunchKernelGGL(cxc_k_labels, cx_grid1(nt), dim3(256), 0, st, V->parent, C->tidx, V->tri, nt, nv, C->tlab.as<int32_t>(), C->vlab.as<int32_t>(), C->first);
+        hipLaunchKernelGGL(cxc_k_labels_unused, cx_grid1(nv), dim3(256), 0, st, C->vlab.as<int32_t>(), nv);
     }
-    CXC_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipGetLastError());
     C->nc = nc; C->nv = nv; C->nt = nt;
     C->gen_labels = V->gen;
     return CX_OK;
@@ -479,11 +393,11 @@ extern "C" int cx_level1_components(cx_ctx* ctx, const double* mins_delta, int64
             hipStream_t st = ctx->stream;
             if ((rc = C->acc.grow(ctx, (size_t)nc * CXC_WORDS + 16))) return rc;
             if ((rc = C->table.grow(ctx, (size_t)nc + 1))) return rc;
-            hipLaunchKernelGGL(cxc_k_acc_init, cxc_grid((size_t)nc * CXC_WORDS), dim3(256), 0, st, C->acc, nc);
-            hipLaunchKernelGGL(cxc_k_measure, cxc_grid(V.nt), dim3(256), 0, st, V.tri, V.pts, C->tlab.as<const int32_t>(), V.nt, V.nv, M, C->acc);
-            hipLaunchKernelGGL(cxc_k_vertex_count, cxc_grid(V.nv), dim3(256), 0, st, C->vlab.as<const int32_t>(), V.nv, nc, C->acc);
-            hipLaunchKernelGGL(cxc_k_finish, cxc_grid(nc), dim3(256), 0, st, (const u64*)C->acc, (const uint32_t*)C->first, V.cflip, nc, M, qa, qv, qm, C->table);
-            CXC_HIP(ctx, hipGetLastError());
+            hipLaunchKernelGGL(cxc_k_acc_init, cx_grid1((size_t)nc * CXC_WORDS), dim3(256), 0, st, C->acc, nc);
+            hipLaunchKernelGGL(cxc_k_measure, cx_grid1(V.nt), dim3(256), 0, st, V.tri, V.pts, C->tlab.as<const int32_t>(), V.nt, V.nv, M, C->acc);
+            hipLaunchKernelGGL(cxc_k_vertex_count, cx_grid1(V.nv), dim3(256), 0, st, C->vlab.as<const int32_t>(), V.nv, nc, C->acc);
+            hipLaunchKernelGGL(cxc_k_finish, cx_grid1(nc), dim3(256), 0, st, (const u64*)C->acc, (const uint32_t*)C->first, V.cflip, nc, M, qa, qv, qm, C->table);
+            CX_HIP(ctx, hipGetLastError());
         }
         C->table_world = world;
         if (world) memcpy(C->table_md, mins_delta, 6 * sizeof(double));
@@ -548,23 +462,23 @@ extern "C" int cx_level1_keep_components(cx_ctx* ctx, const uint8_t* keep, int64
         if ((rc = C->vnew.grow(ctx, (size_t)nv + 16))) return rc;
         if ((rc = C->sums.grow(ctx, (size_t)std::max(nt, nv) / 1024 + 16))) return rc;
         uint32_t* tflag = C->tidx;     // (the scan of the root flags has done its work once the labels stand)
-        CXC_HIP(ctx, hipMemcpyAsync(C->keep, keep, nc, hipMemcpyHostToDevice, st));
-        CXC_HIP(ctx, hipMemsetAsync(C->vuse, 0, (size_t)nv * sizeof(uint32_t), st));
-        hipLaunchKernelGGL(cxc_k_keep_flags, cxc_grid(nt), dim3(256), 0, st, C->tlab.as<const int32_t>(), C->keep.get(), V.tri, nt, nv, tflag, C->vuse);
+        CX_HIP(ctx, hipMemcpyAsync(C->keep, keep, nc, hipMemcpyHostToDevice, st));
+        CX_HIP(ctx, hipMemsetAsync(C->vuse, 0, (size_t)nv * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(cxc_k_keep_flags, cx_grid1(nt), dim3(256), 0, st, C->tlab.as<const int32_t>(), C->keep.get(), V.tri, nt, nv, tflag, C->vuse);
         if ((rc = cx_scan_u32(ctx, tflag, C->tnew, nt, C->sums, C->misc + 1))) return rc;
         if ((rc = cx_scan_u32(ctx, C->vuse, C->vnew, nv, C->sums, C->misc + 2))) return rc;
         uint32_t h[2] = {0, 0};
-        CXC_HIP(ctx, hipMemcpyAsync(h, C->misc + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CXC_HIP(ctx, hipStreamSynchronize(st));      // (also: the caller's keep bytes are on the device)
+        CX_HIP(ctx, hipMemcpyAsync(h, C->misc + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));      // (also: the caller's keep bytes are on the device)
         nt2 = h[0]; nv2 = h[1];
         if (nt2 > nt || nv2 > nv) { ctx->err = "cx_level1_keep_components: the scans do not add up"; return CX_ERR_HIP; }
         if (nt2) {
-            hipLaunchKernelGGL(cxc_k_keep_tri, cxc_grid(nt), dim3(256), 0, st, V.tri, (const uint32_t*)tflag, (const uint32_t*)C->tnew, (const uint32_t*)C->vnew,
+            hipLaunchKernelGGL(cxc_k_keep_tri, cx_grid1(nt), dim3(256), 0, st, V.tri, (const uint32_t*)tflag, (const uint32_t*)C->tnew, (const uint32_t*)C->vnew,
                                V.parent, V.cflip, nt, nv, X.tri, X.parent, X.cflip);
-            hipLaunchKernelGGL(cxc_k_keep_vert, cxc_grid(nv), dim3(256), 0, st, V.pts, V.keys, (const uint32_t*)C->vuse, (const uint32_t*)C->vnew, nv, X.pts, X.keys);
+            hipLaunchKernelGGL(cxc_k_keep_vert, cx_grid1(nv), dim3(256), 0, st, V.pts, V.keys, (const uint32_t*)C->vuse, (const uint32_t*)C->vnew, nv, X.pts, X.keys);
         } else
             nv2 = 0;
-        CXC_HIP(ctx, hipGetLastError());
+        CX_HIP(ctx, hipGetLastError());
         if ((rc = cx_level1_comp_commit(ctx, nv2, nt2, C->vuse, C->vnew))) return rc;
         C->gen_labels = ~0ULL; C->gen_table = ~0ULL;
     }

@@ -20,17 +20,9 @@
 #include <vector>
 
 #include "cx_ctx.h"
+#include "cx_dev.h"
 
 #pragma clang fp contract(off)   // low + ratio*(high-low) and grid*delta + mins round like the reference's float64
-
-#define C2_HIP(ctx, call)                                                                        \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
 
 #define C2_NIL 0xFFFFFFFFu
 typedef unsigned long long c2_u64;
@@ -221,25 +213,7 @@ __global__ __launch_bounds__(256) void c2_k_emit(c2_grid G, const uint32_t* cnt,
     }
 }
 
-// ---- lock-free union-find, root = smallest id ---------------------------------------------------------
-__device__ __forceinline__ uint32_t c2_find(uint32_t* parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == x) return x;
-        const uint32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g != p) atomicCAS(&parent[x], p, g);
-        x = p;
-    }
-}
-__device__ __forceinline__ void c2_union(uint32_t* parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = c2_find(parent, a);
-        b = c2_find(parent, b);
-        if (a == b) return;
-        const uint32_t win = min(a, b), lose = max(a, b);
-        if (atomicCAS(&parent[lose], lose, win) == lose) return;
-    }
-}
+// ---- growth groups of the seeded search: cxd_uf_find / cxd_uf_union (cx_dev.h) over whole polylines ----
 __device__ __constant__ int c2_off_i[6] = {0, 1, 1, 0, -1, -1};   // adjacent_offsets (triangulated.py:10-12)
 __device__ __constant__ int c2_off_j[6] = {1, 1, 0, -1, -1, 0};
 // the first pair around point (i,j) in the given role at level lvl (role 0: the point is the low end), or C2_NIL
@@ -283,11 +257,11 @@ __global__ void c2_k_group(c2_grid G, const c2_u64* keys, const uint32_t* rep, u
     const uint32_t me = rep[id];
     if (ra != C2_NIL && ra != id) {
         const uint32_t o = rep[ra];
-        if (o != me) c2_union(parent, me, o);
+        if (o != me) cxd_uf_union(parent, me, o);
     }
     if (rb != C2_NIL && rb != id) {
         const uint32_t o = rep[rb];
-        if (o != me) c2_union(parent, me, o);
+        if (o != me) cxd_uf_union(parent, me, o);
     }
     if (search && !((bi != i) && (bj != j)) && i + 1 < (int)G.n && j + 1 < (int)G.m) mark[me] = 1u;
 }
@@ -342,7 +316,7 @@ __global__ void c2_k_seed_points(c2_grid G, const int32_t* seeds, uint32_t nseed
 __global__ void c2_k_mark_roots(const uint32_t* rep, const uint32_t* mark, uint32_t nv, uint32_t* parent, uint32_t* rmark) {
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= nv || rep[id] != id || !mark[id]) return;
-    rmark[c2_find(parent, id)] = 1u;
+    rmark[cxd_uf_find(parent, id)] = 1u;
 }
 
 // ---- chains ----------------------------------------------------------------------------------------------
@@ -450,7 +424,7 @@ __global__ void c2_k_head_flags(const uint32_t* rep, uint32_t* parent, const uin
     const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
     if (id >= nv) return;
     uint32_t f = 0;
-    if (rep[id] == id) f = all ? 1u : (mark[c2_find(parent, id)] ? 1u : 0u);
+    if (rep[id] == id) f = all ? 1u : (mark[cxd_uf_find(parent, id)] ? 1u : 0u);
     hflag[id] = f;
 }
 __global__ void c2_k_chain_table(const uint32_t* hflag, const uint32_t* cidx, const uint32_t* len, uint32_t nv, uint32_t* chead, uint32_t* clen) {
@@ -507,8 +481,6 @@ __global__ void c2_k_final_chains(const double2* opts, const c2_u64* okeys, cons
     chains[c] = out;
 }
 
-static inline uint32_t c2_blocks(size_t n) { return (uint32_t)((n + 255) / 256); }
-
 extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_device, int64_t n, int64_t m, const double* values, int32_t nvalues,
                                     const int32_t* seeds, int64_t nseeds, uint32_t flags, const double* mins_delta, cx_counts2d* out) {
     if (!ctx) return CX_ERR_INVALID;
@@ -526,7 +498,7 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
             ctx->err = "cx_contour2d_extract: values must be finite, distinct and ascending";
             return CX_ERR_INVALID;
         }
-    C2_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->s2) ctx->s2 = new cx_state2();
     cx_state2* S = ctx->s2;
     S->valid = false;
@@ -536,27 +508,27 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
     const float* A = samples;
     if (!on_device) {
         if ((rc = c2_room(ctx, S->grid, N * sizeof(float)))) return rc;
-        C2_HIP(ctx, hipMemcpyAsync(S->grid.get(), samples, N * sizeof(float), hipMemcpyHostToDevice, st));
+        CX_HIP(ctx, hipMemcpyAsync(S->grid.get(), samples, N * sizeof(float), hipMemcpyHostToDevice, st));
         A = S->grid.as<const float>();
     }
     if ((rc = c2_room(ctx, S->values, (size_t)nvalues * sizeof(double)))) return rc;
-    C2_HIP(ctx, hipMemcpyAsync(S->values.get(), values, (size_t)nvalues * sizeof(double), hipMemcpyHostToDevice, st));
+    CX_HIP(ctx, hipMemcpyAsync(S->values.get(), values, (size_t)nvalues * sizeof(double), hipMemcpyHostToDevice, st));
     double scal_host[4] = {0.0, 0.0, 1.0, 1.0};
     if (mins_delta) memcpy(scal_host, mins_delta, sizeof(scal_host));
     if ((rc = c2_room(ctx, S->scal, 64))) return rc;
-    C2_HIP(ctx, hipMemcpyAsync(S->scal.get(), scal_host, sizeof(scal_host), hipMemcpyHostToDevice, st));
+    CX_HIP(ctx, hipMemcpyAsync(S->scal.get(), scal_host, sizeof(scal_host), hipMemcpyHostToDevice, st));
     uint32_t* scratch = (uint32_t*)(S->scal.as<char>() + 32);   // [0] scan total, [1] changed flag, [2] tie flag, [4..5] 64-bit total
-    C2_HIP(ctx, hipMemsetAsync(scratch, 0, 24, st));
+    CX_HIP(ctx, hipMemsetAsync(scratch, 0, 24, st));
     const size_t E = 3 * N;
     if ((rc = c2_room(ctx, S->cnt, E * 4)) || (rc = c2_room(ctx, S->base, (E + 1) * 4)) || (rc = c2_room(ctx, S->sums, (E / 1024 + 4) * 4)))
         return rc;
     c2_grid G{A, (uint32_t)n, (uint32_t)m, S->values.as<const double>(), (uint32_t)nvalues, S->base.as<const uint32_t>()};
-    hipLaunchKernelGGL(c2_k_count, dim3(c2_blocks(N)), dim3(256), 0, st, G, S->cnt.as<uint32_t>(), scratch + 2);
+    hipLaunchKernelGGL(c2_k_count, dim3(cx_blocks(N)), dim3(256), 0, st, G, S->cnt.as<uint32_t>(), scratch + 2);
     // (the scan also returns the total in 64 bits: a 32-bit total cannot show an overflow)
     cx_scan_u32(ctx, S->cnt.as<const uint32_t>(), S->base.as<uint32_t>(), (uint32_t)E, S->sums.as<uint32_t>(), scratch, (unsigned long long*)(scratch + 4));
     uint32_t head6[6] = {0, 0, 0, 0, 0, 0};
-    C2_HIP(ctx, hipMemcpyAsync(head6, scratch, 24, hipMemcpyDeviceToHost, st));
-    C2_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipMemcpyAsync(head6, scratch, 24, hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipStreamSynchronize(st));
     const uint32_t nv = head6[0];
     const bool ties = head6[2] != 0;
     const unsigned long long total64 = ((unsigned long long)head6[5] << 32) | head6[4];
@@ -584,7 +556,7 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
     uint32_t *succ = S->succ.as<uint32_t>(), *pred = S->pred.as<uint32_t>(), *parent = S->parent.as<uint32_t>(), *rep = S->rep.as<uint32_t>();
     uint32_t *mark = S->mark.as<uint32_t>(), *rmark = S->rmark.as<uint32_t>(), *rank = S->rank.as<uint32_t>(), *cyc = S->cyc.as<uint32_t>(), *len = S->len.as<uint32_t>();
     uint32_t *hflag = S->hflag.as<uint32_t>(), *cidx = S->cidx.as<uint32_t>();
-    const uint32_t gb = c2_blocks(V);
+    const uint32_t gb = cx_blocks(V);
     hipLaunchKernelGGL(c2_k_emit, dim3((uint32_t)((E + C2_EPB - 1) / C2_EPB)), dim3(256), 0, st, G, S->cnt.as<const uint32_t>(), pts, keys, succ, pred);
     const int all = (flags & CX2_ALL_CHAINS) ? 1 : 0;
     // chains: first element, rank, length
@@ -598,16 +570,16 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
             ctx->err = "cx_contour2d_extract: chain ranking did not converge";
             return CX_ERR_HIP;
         }
-        C2_HIP(ctx, hipMemsetAsync(scratch + 1, 0, 4, st));
+        CX_HIP(ctx, hipMemsetAsync(scratch + 1, 0, 4, st));
         if (nlist)
-            hipLaunchKernelGGL(c2_k_jump_listed, dim3(c2_blocks(nlist)), dim3(256), 0, st, S->jst[cur].as<const uint4>(), S->jst[1 - cur].as<uint4>(), list,
+            hipLaunchKernelGGL(c2_k_jump_listed, dim3(cx_blocks(nlist)), dim3(256), 0, st, S->jst[cur].as<const uint4>(), S->jst[1 - cur].as<uint4>(), list,
                                nlist, scratch + 1);
         else
             hipLaunchKernelGGL(c2_k_jump, dim3(gb), dim3(256), 0, st, S->jst[cur].as<const uint4>(), S->jst[1 - cur].as<uint4>(), nv, scratch + 1);
         cur = 1 - cur;
         uint32_t changed = 0;
-        C2_HIP(ctx, hipMemcpyAsync(&changed, scratch + 1, 4, hipMemcpyDeviceToHost, st));
-        C2_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipMemcpyAsync(&changed, scratch + 1, 4, hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
         if (!changed) break;
         if (round == C2_FULL_ROUNDS && nv > (1u << 20)) {
             // the list of elements that were unfinished BEFORE this round (buffer 1 - cur): whatever finished earlier has
@@ -616,8 +588,8 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
             hipLaunchKernelGGL(c2_k_jump_flags, dim3(gb), dim3(256), 0, st, S->jst[1 - cur].as<const uint4>(), nv, hflag);
             cx_scan_u32(ctx, hflag, cidx, nv, S->sums.as<uint32_t>(), scratch);
             hipLaunchKernelGGL(c2_k_jump_list, dim3(gb), dim3(256), 0, st, hflag, cidx, nv, S->alist.as<uint32_t>());
-            C2_HIP(ctx, hipMemcpyAsync(&nlist, scratch, 4, hipMemcpyDeviceToHost, st));
-            C2_HIP(ctx, hipStreamSynchronize(st));
+            CX_HIP(ctx, hipMemcpyAsync(&nlist, scratch, 4, hipMemcpyDeviceToHost, st));
+            CX_HIP(ctx, hipStreamSynchronize(st));
             list = S->alist.as<const uint32_t>();
             if (nlist == 0) break;   // (cannot happen while `changed` is set; defensive)
         }
@@ -626,14 +598,14 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
     // growth groups of chains and their seeds
     if (!all) {
         const bool search = nseeds <= 0 || (flags & CX2_SEARCH_SEEDS);
-        C2_HIP(ctx, hipMemsetAsync(mark, 0, V * 4, st));
-        C2_HIP(ctx, hipMemsetAsync(rmark, 0, V * 4, st));
+        CX_HIP(ctx, hipMemsetAsync(mark, 0, V * 4, st));
+        CX_HIP(ctx, hipMemsetAsync(rmark, 0, V * 4, st));
         hipLaunchKernelGGL(c2_k_group, dim3(gb), dim3(256), 0, st, G, keys, rep, nv, search ? 1 : 0, parent, mark);
-        if (search && ties) hipLaunchKernelGGL(c2_k_seed_ties, dim3(c2_blocks(N)), dim3(256), 0, st, G, rep, mark);
+        if (search && ties) hipLaunchKernelGGL(c2_k_seed_ties, dim3(cx_blocks(N)), dim3(256), 0, st, G, rep, mark);
         if (nseeds > 0) {
             if ((rc = c2_room(ctx, S->seeds, (size_t)nseeds * 16))) return rc;
-            C2_HIP(ctx, hipMemcpyAsync(S->seeds.get(), seeds, (size_t)nseeds * 16, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(c2_k_seed_points, dim3(c2_blocks((size_t)nseeds)), dim3(256), 0, st, G, S->seeds.as<const int32_t>(), (uint32_t)nseeds,
+            CX_HIP(ctx, hipMemcpyAsync(S->seeds.get(), seeds, (size_t)nseeds * 16, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(c2_k_seed_points, dim3(cx_blocks((size_t)nseeds)), dim3(256), 0, st, G, S->seeds.as<const int32_t>(), (uint32_t)nseeds,
                                rep, mark);
         }
         hipLaunchKernelGGL(c2_k_mark_roots, dim3(gb), dim3(256), 0, st, rep, mark, nv, parent, rmark);
@@ -641,8 +613,8 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
     hipLaunchKernelGGL(c2_k_head_flags, dim3(gb), dim3(256), 0, st, rep, parent, rmark, all, nv, hflag);
     cx_scan_u32(ctx, hflag, cidx, nv, S->sums.as<uint32_t>(), scratch);
     uint32_t nchains = 0;
-    C2_HIP(ctx, hipMemcpyAsync(&nchains, scratch, 4, hipMemcpyDeviceToHost, st));
-    C2_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipMemcpyAsync(&nchains, scratch, 4, hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipStreamSynchronize(st));
     if (nchains == 0) {
         S->valid = true;
         if (out) *out = S->counts;
@@ -655,8 +627,8 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
     hipLaunchKernelGGL(c2_k_chain_table, dim3(gb), dim3(256), 0, st, hflag, cidx, len, nv, chead, clen);
     cx_scan_u32(ctx, clen, coff, nchains, S->sums.as<uint32_t>(), scratch);
     uint32_t nsel = 0;
-    C2_HIP(ctx, hipMemcpyAsync(&nsel, scratch, 4, hipMemcpyDeviceToHost, st));
-    C2_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipMemcpyAsync(&nsel, scratch, 4, hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipStreamSynchronize(st));
     if (nsel == 0 || nsel > nv) {
         ctx->err = "cx_contour2d_extract: inconsistent chain lengths";
         return CX_ERR_HIP;
@@ -665,17 +637,17 @@ extern "C" int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_de
     c2_u64* okeys = S->okeys.as<c2_u64>();
     uint32_t *ochain = S->ochain.as<uint32_t>(), *keep = S->keep.as<uint32_t>(), *fidx = S->fidx.as<uint32_t>();
     hipLaunchKernelGGL(c2_k_place, dim3(gb), dim3(256), 0, st, pts, keys, rep, hflag, cidx, coff, rank, nv, opts, okeys, ochain);
-    hipLaunchKernelGGL(c2_k_keep, dim3(c2_blocks(nsel)), dim3(256), 0, st, opts, ochain, coff, nsel, (flags & CX2_NO_DEDUPE) ? 0 : 1, keep);
+    hipLaunchKernelGGL(c2_k_keep, dim3(cx_blocks(nsel)), dim3(256), 0, st, opts, ochain, coff, nsel, (flags & CX2_NO_DEDUPE) ? 0 : 1, keep);
     cx_scan_u32(ctx, keep, fidx, nsel, S->sums.as<uint32_t>(), scratch);
     uint32_t nfinal = 0;
-    C2_HIP(ctx, hipMemcpyAsync(&nfinal, scratch, 4, hipMemcpyDeviceToHost, st));
-    C2_HIP(ctx, hipStreamSynchronize(st));
-    hipLaunchKernelGGL(c2_k_final_points, dim3(c2_blocks(nsel)), dim3(256), 0, st, opts, okeys, keep, fidx, nsel, S->scal.as<const double>(),
+    CX_HIP(ctx, hipMemcpyAsync(&nfinal, scratch, 4, hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipStreamSynchronize(st));
+    hipLaunchKernelGGL(c2_k_final_points, dim3(cx_blocks(nsel)), dim3(256), 0, st, opts, okeys, keep, fidx, nsel, S->scal.as<const double>(),
                        S->fpts.as<double2>(), S->fkeys.as<c2_u64>());
-    hipLaunchKernelGGL(c2_k_final_chains, dim3(c2_blocks(nchains)), dim3(256), 0, st, opts, okeys, keep, fidx, coff, clen, chead, cyc, nchains, nfinal,
+    hipLaunchKernelGGL(c2_k_final_chains, dim3(cx_blocks(nchains)), dim3(256), 0, st, opts, okeys, keep, fidx, coff, clen, chead, cyc, nchains, nfinal,
                        S->chains.as<cx_chain2d>());
-    C2_HIP(ctx, hipGetLastError());
-    C2_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipStreamSynchronize(st));
     S->counts = cx_counts2d{nfinal, nchains, nv, (uint32_t)nvalues};
     S->valid = true;
     if (out) *out = S->counts;
@@ -690,11 +662,11 @@ extern "C" int cx_contour2d_download(cx_ctx* ctx, double* points_xy, int64_t* ke
         ctx->err = "cx_contour2d_download: no contour extraction yet";
         return CX_ERR_STATE;
     }
-    C2_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     const size_t np = S->counts.n_points, nc = S->counts.n_chains;
-    if (points_xy && np) C2_HIP(ctx, hipMemcpyAsync(points_xy, S->fpts.get(), np * 16, hipMemcpyDeviceToHost, ctx->stream));
-    if (keys && np) C2_HIP(ctx, hipMemcpyAsync(keys, S->fkeys.get(), np * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (chains && nc) C2_HIP(ctx, hipMemcpyAsync(chains, S->chains.get(), nc * sizeof(cx_chain2d), hipMemcpyDeviceToHost, ctx->stream));
-    C2_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (points_xy && np) CX_HIP(ctx, hipMemcpyAsync(points_xy, S->fpts.get(), np * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (keys && np) CX_HIP(ctx, hipMemcpyAsync(keys, S->fkeys.get(), np * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (chains && nc) CX_HIP(ctx, hipMemcpyAsync(chains, S->chains.get(), nc * sizeof(cx_chain2d), hipMemcpyDeviceToHost, ctx->stream));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CX_OK;
 }

@@ -7,6 +7,28 @@
 
 #include "cx_common.h"
 
+// A HIP call inside a function that returns a CX_* code: on failure the context keeps the call and the runtime's text, and the
+// function returns CX_ERR_NOMEM or CX_ERR_HIP.
+#define CX_HIP(ctx, call)                                                                        \
+    do {                                                                                         \
+        hipError_t e__ = (call);                                                                 \
+        if (e__ != hipSuccess) {                                                                 \
+            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
+            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
+        }                                                                                        \
+    } while (0)
+
+// launch geometry: blocks of b threads for n items (none for n = 0); cx_grid1: at 256 threads, and one block where that is none
+// (the kernel's own bound check idles it; a launch of zero blocks is an error)
+static inline uint32_t cx_blocks(size_t n, uint32_t b = 256) { return (uint32_t)((n + b - 1) / b); }
+static inline dim3 cx_grid1(size_t n) { return dim3(n ? cx_blocks(n) : 1u); }
+// slots of an open-addressing table for n keys: a power of two, at most half full
+static inline unsigned long long cx_table_size(size_t n) {
+    unsigned long long s = 1024;
+    while (s < 2 * (unsigned long long)n + 16) s <<= 1;
+    return s;
+}
+
 struct cx_post_state;  // Level-1 buffers (cx_post.hip)
 struct cx_state4;       // 4-D march state (cx_api4d.hip)
 struct cx_state2;       // 2-D contour lines (cx_contour2d.hip)

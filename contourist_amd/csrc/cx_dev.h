@@ -1,0 +1,137 @@
+// cx_dev.h -- the device primitives that more than one translation unit needs, each defined once.
+// Only __device__ __forceinline__ functions, typedefs and constants; a primitive that a second file needs moves here instead of
+// being copied.
+#pragma once
+#include "cx_common.h"
+
+typedef unsigned long long u64;
+#define CXD_EMPTY 0xFFFFFFFFFFFFFFFFULL   // a free slot of a table of 64-bit keys
+#define CXD_NONE 0xFFFFFFFFu              // no index
+
+// 64-bit mixer (the finaliser of MurmurHash3): what every hash table here derives its home slot from
+__device__ __forceinline__ u64 cxd_mix(u64 x) {
+    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
+    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
+    x ^= x >> 33;
+    return x;
+}
+// total order on doubles as unsigned integers, and back
+__device__ __forceinline__ u64 cxd_orderable(double x) {
+    const u64 b = (u64)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
+}
+__device__ __forceinline__ double cxd_from_orderable(u64 o) {
+    const u64 b = (o >> 63) ? (o & 0x7FFFFFFFFFFFFFFFULL) : ~o;
+    return __longlong_as_double((long long)b);
+}
+
+// monotonic maximum / minimum with a plain read first: once the running extreme is established almost every caller
+// sees that its value cannot move it and skips the atomic (same-address atomics serialise at ~88/us)
+__device__ __forceinline__ void cxd_max64(u64* addr, u64 v) {
+    if (__hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= v) return;
+    atomicMax(addr, v);
+}
+__device__ __forceinline__ void cxd_min64(u64* addr, u64 v) {
+    if (__hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= v) return;
+    atomicMin(addr, v);
+}
+__device__ __forceinline__ void cxd_max32(uint32_t* addr, uint32_t v) {
+    if (__hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= v) return;
+    atomicMax(addr, v);
+}
+
+// butterflies over the 64 lanes of the wave: every lane ends with the result
+__device__ __forceinline__ u64 cxd_shfl_xor64(u64 v, int o) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
+    return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ uint32_t cxd_wave_add(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
+    return v;
+}
+__device__ __forceinline__ long long cxd_wave_add(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (long long)cxd_shfl_xor64((u64)v, o);
+    return v;
+}
+__device__ __forceinline__ u64 cxd_wave_xor(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v ^= cxd_shfl_xor64(v, o);
+    return v;
+}
+__device__ __forceinline__ u64 cxd_wave_min(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const u64 w = cxd_shfl_xor64(v, o); v = w < v ? w : v; }
+    return v;
+}
+__device__ __forceinline__ u64 cxd_wave_max(u64 v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const u64 w = cxd_shfl_xor64(v, o); v = w > v ? w : v; }
+    return v;
+}
+
+// signed 64-bit value into a 128-bit two's complement accumulator {low, high}: the carry out of the low word follows from the value
+// the atomic returns, so the sum is exact modulo 2^128 in any order
+__device__ __forceinline__ void cxd_add128(u64* w, long long v) {
+    if (v == 0) return;
+    const u64 lo = (u64)v;
+    u64 hi = v < 0 ? ~0ULL : 0ULL;
+    const u64 old = atomicAdd(&w[0], lo);
+    if (old + lo < old) hi += 1ULL;
+    if (hi) atomicAdd(&w[1], hi);
+}
+// the 128-bit sum as a double, rounded once (the top 64 bits with a sticky bit), times 2^-q
+__device__ __forceinline__ double cxd_to_double128(u64 lo, u64 hi, int q) {
+    const bool neg = (hi >> 63) != 0ULL;
+    if (neg) { lo = ~lo + 1ULL; hi = ~hi + (lo == 0ULL ? 1ULL : 0ULL); }
+    double r;
+    if (hi == 0ULL) r = ldexp((double)lo, -q);
+    else {
+        const int s = __clzll((long long)hi);
+        u64 top = s ? ((hi << s) | (lo >> (64 - s))) : hi;
+        const u64 rest = s ? (lo << s) : lo;
+        if (rest) top |= 1ULL;
+        r = ldexp((double)top, 64 - s - q);
+    }
+    return neg ? -r : r;
+}
+
+// ---- lock-free union-find -------------------------------------------------------------------------------------------------------------
+// The rule for EVERY union-find in global memory here, whatever the width of its parent words (uint32_t below; the u64 words of
+// cxp_find / cxp_union and cxp_find0 / cxp_union0 in cx_post.hip; cxt_root / cxt_union in cx_topo.hip): every access to a parent word
+// inside the kernel that unites is a device-scope atomic, loads and path-shortening writes included.  The L2s of the 8 XCDs are not
+// coherent with each other inside a kernel, and a version with plain loads and plain path-halving stores showed a rare wrong winding
+// of one component (stale lines mixing with memory-side compare-and-swaps).
+//
+// Parents are ids, a root points to itself, the root of a set is its smallest id.  Path halving: on the way up a node is pointed at
+// its grandparent by compare-and-swap, so a word only ever moves to an ancestor.
+__device__ __forceinline__ uint32_t cxd_uf_find(uint32_t* parent, uint32_t x) {
+    for (;;) {
+        const uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p == x) return x;
+        const uint32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (g != p) atomicCAS(&parent[x], p, g);
+        x = p;
+    }
+}
+__device__ __forceinline__ void cxd_uf_union(uint32_t* parent, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = cxd_uf_find(parent, a);
+        b = cxd_uf_find(parent, b);
+        if (a == b) return;
+        const uint32_t win = min(a, b), lose = max(a, b);
+        if (atomicCAS(&parent[lose], lose, win) == lose) return;
+    }
+}
+// find in a forest that one workgroup keeps in LDS (the block-local step of cx_seed.hip and cx_seed4.hip): its words are the
+// workgroup's own, so plain loads see what the compare-and-swaps wrote
+__device__ __forceinline__ uint32_t cxd_uf_find_lds(uint32_t* lp, uint32_t x) {
+    for (;;) {
+        const uint32_t p = lp[x];
+        if (p == x) return x;
+        const uint32_t g = lp[p];
+        if (g != p) atomicCAS(&lp[x], p, g);
+        x = p;
+    }
+}

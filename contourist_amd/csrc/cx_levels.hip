@@ -15,15 +15,6 @@
 
 #include "cx_ctx.h"
 
-#define CXL_HIP(ctx, call)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
 struct cx_level_slot {
     double value = 0.0;
     cx_params P;                       // parameters of the level (valid after cx_extract3d_levels)
@@ -115,8 +106,8 @@ extern "C" int cx_levels_select(cx_ctx* ctx, int32_t index) {
     if (!ctx) return CX_ERR_INVALID;
     cx_levels_state* L = ctx->lv;
     if (!L || index < 0 || index >= L->nvalid) { ctx->err = "cx_levels_select: no such level (call cx_extract3d_levels first)"; return CX_ERR_STATE; }
-    CXL_HIP(ctx, hipSetDevice(ctx->device));
-    CXL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     cx_levels_unselect(ctx);
     cx_level_slot& S = L->slots[index];
     S.swap_outputs(ctx);
@@ -140,7 +131,7 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
     if ((flags & ~(uint32_t)(CX_DIAG_CPYTHON310)) != 0u) { ctx->err = "cx_extract3d_levels: only the diagonal flag is accepted"; return CX_ERR_INVALID; }
     for (int l = 0; l < nlevels; l++)
         if (!(values[l] == values[l])) { ctx->err = "isovalue is NaN"; return CX_ERR_INVALID; }
-    CXL_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     if (!cx_fast_classify_supported_dims(ctx->n2, ctx->grid)) {
         ctx->err = "cx_extract3d_levels needs rows of at least 4 samples: extract the levels one by one with cx_extract3d";
         return CX_ERR_UNSUPPORTED;
@@ -184,7 +175,7 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
     const size_t chunk_words = (((nw + 255u) / 256u) * 8u + 63u) & ~(size_t)63u;      // per level, a multiple of 256 bytes
     if ((rc = L->counters_all.grow(ctx, (size_t)nlevels * CX_CNT_WORDS))) return rc;
     if ((rc = L->chunk_all.grow(ctx, (size_t)nlevels * chunk_words))) return rc;
-    CXL_HIP(ctx, hipMemsetAsync(L->chunk_all, 0, (size_t)nlevels * chunk_words * sizeof(uint32_t), ctx->stream));
+    CX_HIP(ctx, hipMemsetAsync(L->chunk_all, 0, (size_t)nlevels * chunk_words * sizeof(uint32_t), ctx->stream));
     for (int l = 0; l < nlevels; l++) {
         cx_level_slot& S = L->slots[l];
         S.value = values[l];
@@ -228,13 +219,13 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
     if (L->hcounters_cap < (size_t)nlevels) {
         if (L->hcounters) (void)hipHostFree(L->hcounters);
         L->hcounters = nullptr; L->hcounters_cap = 0;
-        CXL_HIP(ctx, hipHostMalloc(&L->hcounters, (size_t)nlevels * CX_CNT_WORDS * sizeof(uint32_t)));
+        CX_HIP(ctx, hipHostMalloc(&L->hcounters, (size_t)nlevels * CX_CNT_WORDS * sizeof(uint32_t)));
         L->hcounters_cap = (size_t)nlevels;
     }
     if (L->hparams_cap < (size_t)nlevels) {
         if (L->hparams) (void)hipHostFree(L->hparams);
         L->hparams = nullptr; L->hparams_cap = 0;
-        CXL_HIP(ctx, hipHostMalloc(&L->hparams, (size_t)nlevels * sizeof(cx_params)));
+        CX_HIP(ctx, hipHostMalloc(&L->hparams, (size_t)nlevels * sizeof(cx_params)));
         L->hparams_cap = (size_t)nlevels;
     }
     {
@@ -245,12 +236,12 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
             S.P.info64 = pooled ? ctx->info64 + (size_t)l * sub : ctx->info64;
             hp[l] = S.P;
         }
-        CXL_HIP(ctx, hipMemcpyAsync(L->dparams, hp, (size_t)nlevels * sizeof(cx_params), hipMemcpyHostToDevice, ctx->stream));
+        CX_HIP(ctx, hipMemcpyAsync(L->dparams, hp, (size_t)nlevels * sizeof(cx_params), hipMemcpyHostToDevice, ctx->stream));
         // ONE pass over the samples for all levels, then the scans
         cx_launch_stream_levels(hp, T, (uint32_t)nlevels, ctx->stream);
         cx_launch_scan_levels(L->dparams, T, (uint32_t)nlevels, ctx->stream);
-        CXL_HIP(ctx, hipMemcpyAsync(L->hcounters, L->counters_all, (size_t)nlevels * CX_CNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        CXL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        CX_HIP(ctx, hipMemcpyAsync(L->hcounters, L->counters_all, (size_t)nlevels * CX_CNT_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         // output buffers of every level, sized by what its surface needs
         for (int l = 0; l < nlevels; l++) {
             cx_level_slot& S = L->slots[l];
@@ -290,14 +281,14 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
             if (want >= 2 && want <= CXL_SIDES + 1) nstr = std::min(nlevels, want);
         }
         if (nstr > 1) {
-            if (!L->ev_fork) CXL_HIP(ctx, hipEventCreateWithFlags(&L->ev_fork, hipEventDisableTiming));
+            if (!L->ev_fork) CX_HIP(ctx, hipEventCreateWithFlags(&L->ev_fork, hipEventDisableTiming));
             for (int k = 0; k + 1 < nstr; k++) {
-                if (!L->side[k]) CXL_HIP(ctx, hipStreamCreateWithFlags(&L->side[k], hipStreamNonBlocking));
-                if (!L->ev_join[k]) CXL_HIP(ctx, hipEventCreateWithFlags(&L->ev_join[k], hipEventDisableTiming));
+                if (!L->side[k]) CX_HIP(ctx, hipStreamCreateWithFlags(&L->side[k], hipStreamNonBlocking));
+                if (!L->ev_join[k]) CX_HIP(ctx, hipEventCreateWithFlags(&L->ev_join[k], hipEventDisableTiming));
                 if (!pooled && (rc = L->info_side[k].grow(ctx, ctx->info64.cap()))) return rc;   // pooled: every level has its own slice of the info words
             }
-            CXL_HIP(ctx, hipEventRecord(L->ev_fork, ctx->stream));
-            for (int k = 0; k + 1 < nstr; k++) CXL_HIP(ctx, hipStreamWaitEvent(L->side[k], L->ev_fork, 0));
+            CX_HIP(ctx, hipEventRecord(L->ev_fork, ctx->stream));
+            for (int k = 0; k + 1 < nstr; k++) CX_HIP(ctx, hipStreamWaitEvent(L->side[k], L->ev_fork, 0));
         }
         for (int l = 0; l < nlevels; l++) {
             cx_level_slot& S = L->slots[l];
@@ -316,10 +307,10 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
             }
         }
         for (int k = 0; k + 1 < nstr; k++) {
-            CXL_HIP(ctx, hipEventRecord(L->ev_join[k], L->side[k]));
-            CXL_HIP(ctx, hipStreamWaitEvent(ctx->stream, L->ev_join[k], 0));
+            CX_HIP(ctx, hipEventRecord(L->ev_join[k], L->side[k]));
+            CX_HIP(ctx, hipStreamWaitEvent(ctx->stream, L->ev_join[k], 0));
         }
-        CXL_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     L->nvalid = nlevels;
     if (out_counts)

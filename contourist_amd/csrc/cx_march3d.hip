@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "cx_cell.h"
+#include "cx_dev.h"
 
 __device__ __constant__ uint8_t cx_d_tet_corners[6][4] = CX_TET_CORNERS_INIT;
 __device__ __constant__ uint32_t cx_d_tet_tris[6][16][2] = CX_TET_TRIS_INIT;
@@ -504,11 +505,6 @@ __device__ __forceinline__ void cx_count_from_signs(uint32_t sm, uint32_t vm, cx
     acc.c += (nv | nt) ? 1u : 0u;
     acc.b += real_voxel ? 1u : 0u;
 }
-__device__ __forceinline__ uint32_t cx_wave_sum(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += (uint32_t)__shfl_xor((int)x, o);
-    return x;
-}
 
 // inclusive prefix sum over the wave with DPP row shifts / broadcasts (no LDS crossbar round trips)
 __device__ __forceinline__ uint32_t cx_wave_incl_scan(uint32_t x, uint32_t lane) {
@@ -632,8 +628,8 @@ __global__ __launch_bounds__(256) void cx_k_classify_generic(const cx_params P, 
         if (__ballot(dnear <= P.near_abs) != 0ULL) {   // wave-uniform: a sample inside the tolerance screen, count exactly
             cx_process_queue<true, DT>(P, lin_of, qn, lane, false, run, s_vstage[wave]);
         } else {
-            run.v = cx_wave_sum(acc.v); run.t = cx_wave_sum(acc.t);
-            run.c = cx_wave_sum(acc.c); run.b = cx_wave_sum(acc.b);
+            run.v = cxd_wave_add(acc.v); run.t = cxd_wave_add(acc.t);
+            run.c = cxd_wave_add(acc.c); run.b = cxd_wave_add(acc.b);
         }
         acc.v = acc.t = acc.c = acc.b = 0;
         dnear = 3.0e38f;
@@ -854,7 +850,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
 #if CX_S1_LAZY
         if (!P.tq) count_pending();
 #endif
-        const uint32_t bv = cx_wave_sum(acc.v), bt = cx_wave_sum(acc.t), bc = cx_wave_sum(acc.c);
+        const uint32_t bv = cxd_wave_add(acc.v), bt = cxd_wave_add(acc.t), bc = cxd_wave_add(acc.c);
         if (lane == 0) {
             s_br[wave][nbl][0] = qstart; s_br[wave][nbl][1] = qn - qstart; s_br[wave][nbl][2] = rv;
             s_br[wave][nbl][3] = rt; s_br[wave][nbl][4] = rc;
@@ -1147,7 +1143,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
     if (stamp && lane == 0) stamp[1] = __builtin_amdgcn_s_memtime();
 #endif
     cx_run run;
-    run.v = rv; run.t = rt; run.c = rc; run.b = cx_wave_sum(acc.b);
+    run.v = rv; run.t = rt; run.c = rc; run.b = cxd_wave_add(acc.b);
     const bool near = __ballot(dnear <= P.near_abs) != 0ULL && !(P.flags & CX_DBG_NO_NEAR);   // wave-uniform
     bool really_near = false;
     if (near && qn != 0u && !overflow) {
@@ -1248,12 +1244,12 @@ __device__ __forceinline__ void cx_scan_list_chunk(const cx_params& P, const cx_
 #pragma unroll
     for (int m = 0; m < 6; m++) {
         inc[m] = cx_wave_incl_scan(x[m], lane);
-        const uint32_t before = cx_wave_sum(acc[m]);
+        const uint32_t before = cxd_wave_add(acc[m]);
         if (lane == 63u) { s_own[wave][m] = inc[m]; s_part[wave][m] = before; }
     }
     {
         const uint32_t nr = (__ballot(near_any != 0u) != 0ULL) ? 1u : 0u;
-        const uint32_t ra = cx_wave_sum(rall);
+        const uint32_t ra = cxd_wave_add(rall);
         const uint32_t ov = (__ballot(over_any != 0u) != 0ULL) ? 1u : 0u;
         if (lane == 63u) { s_part[wave][6] = nr | (ov << 1); s_part[wave][7] = ra; }
     }
@@ -1355,7 +1351,7 @@ __device__ __forceinline__ void cx_skip_rounds(const cx_params& P, const cx_fast
         const uint32_t nt = (vm == 0xFFu) ? (uint32_t)ntri_lut[sm] : 0u;
         v += nv; t += nt; c += (nv | nt) ? 1u : 0u;
     }
-    run.v += cx_wave_sum(v); run.t += cx_wave_sum(t); run.c += cx_wave_sum(c);
+    run.v += cxd_wave_add(v); run.t += cxd_wave_add(t); run.c += cxd_wave_add(c);
 }
 
 // ---- S3: vertex records, (first vertex, crossing mask) words and cell records.  The ROUNDS of 64 queued cells of all batches
@@ -2218,7 +2214,7 @@ __global__ __launch_bounds__(256, CX_K2E_MIN_WAVES) void cx_k_emit_triangles_e(c
             const uint64_t* __restrict__ iw = P.info64 + S.qofs;
             uint32_t t = 0;
             for (uint32_t x = lane; x < S.at; x += 64u) t += (uint32_t)(iw[x] >> 40) & 0xFu;
-            run_t += cx_wave_sum(t);
+            run_t += cxd_wave_add(t);
         }
         if (S.at >= S.bend) {
             // the first batch of the share is on the tolerance path and belongs to the wave before: numbering is contiguous along

@@ -22,20 +22,8 @@
 #include <vector>
 
 #include "cx_ctx.h"
+#include "cx_dev.h"
 #include "cx_state4.h"
-
-#define CXP_HIP(ctx, call)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
-typedef unsigned long long u64;
-#define CXP_EMPTY 0xFFFFFFFFFFFFFFFFULL
-#define CXP_NONE 0xFFFFFFFFu
 
 struct cx_post_state {
     cx_buf<uint8_t> pts, prio, rep, tri, alive, parent, parent2, tkeys, tvals, flags, scan, blocksums, pts_out, tri_out, comp, misc;
@@ -92,29 +80,7 @@ void cx_post_free(cx_ctx* ctx) {
 }
 
 // ---- device helpers --------------------------------------------------------------------------------
-__device__ __forceinline__ u64 cxp_mix(u64 x) {
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
-    x ^= x >> 33;
-    return x;
-}
-// total order on doubles as unsigned integers
-__device__ __forceinline__ u64 cxp_orderable(double x) {
-    u64 b = (u64)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-}
-
-// monotonic maximum with a plain read first: once the running maximum is established almost every caller
-// sees that its value cannot raise it and skips the atomic (same-address atomics serialise at ~88/us)
-__device__ __forceinline__ void cxp_max64(u64* addr, u64 v) {
-    if (__hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= v) return;
-    atomicMax(addr, v);
-}
-__device__ __forceinline__ void cxp_max32(uint32_t* addr, uint32_t v) {
-    if (__hip_atomic_load(addr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= v) return;
-    atomicMax(addr, v);
-}
-// the same for a whole wave: when all its lanes share one key (component) they reduce among themselves and issue
+// monotonic maximum (cxd_max64) for a whole wave: when all its lanes share one key (component) they reduce among themselves and issue
 // ONE atomic; a wave that straddles components falls back to one call per lane.  (With values that grow along
 // the array -- vertices ordered by x -- the plain read alone does not help: every caller raises the maximum.)
 // All lanes of the wave must call it; `active` masks the idle ones.
@@ -123,7 +89,7 @@ __device__ __forceinline__ void cxp_wave_max64(u64* table, uint32_t key, u64 v, 
     if (act == 0ULL) return;
     const uint32_t k = (uint32_t)__shfl((int)key, __ffsll((long long)act) - 1);
     if (__ballot(active && key != k) != 0ULL) {   // wave-uniform
-        if (active) cxp_max64(&table[key], v);
+        if (active) cxd_max64(&table[key], v);
         return;
     }
     u64 m = active ? v : 0ULL;
@@ -133,7 +99,7 @@ __device__ __forceinline__ void cxp_wave_max64(u64* table, uint32_t key, u64 v, 
         const u64 other = ((u64)hi << 32) | lo;
         m = other > m ? other : m;
     }
-    if ((threadIdx.x & 63u) == 0u) cxp_max64(&table[k], m);
+    if ((threadIdx.x & 63u) == 0u) cxd_max64(&table[k], m);
 }
 
 // union-find over 32-bit ids; parent word = (parity << 32) | parent id.  Root = smallest priority.
@@ -150,9 +116,7 @@ __device__ __forceinline__ uint32_t cxp_find(const u64* parent, uint32_t x, uint
     return x;
 }
 // link the sets of a and b; rel = parity between a and b (0: same winding class).
-// Every access to the parent words is a device-scope atomic (loads included): the L2s of the 8 XCDs are not
-// coherent with each other inside a kernel, and a version with plain loads and plain path-halving stores showed a
-// rare wrong winding of one component (stale lines mixing with memory-side compare-and-swaps).
+// Every access to the parent words is a device-scope atomic, loads included (why: cx_dev.h, above cxd_uf_find).
 __device__ __forceinline__ void cxp_union(u64* parent, const uint32_t* prio, uint32_t a, uint32_t b, uint32_t rel) {
     for (;;) {
         uint32_t pa, pb;
@@ -169,7 +133,7 @@ __device__ __forceinline__ void cxp_union(u64* parent, const uint32_t* prio, uin
 
 // The same for forests without parities and priorities (connectivity only: the march's own meshes), with path HALVING: on the way
 // up every node is pointed at its grandparent -- with a device-scope store, which is executed where the compare-and-swaps are, so
-// the two cannot disagree (see above) -- and only ever at an ancestor.  Most unions of a large component find both sides in one
+// the two cannot disagree (cx_dev.h, above cxd_uf_find) -- and only ever at an ancestor.  Most unions of a large component find both sides in one
 // tree already; without the halving each of them walks the whole chain again (roots are the smallest ids, not the flattest trees).
 __device__ __forceinline__ uint32_t cxp_find0(u64* parent, uint32_t x) {
     for (;;) {
@@ -385,10 +349,10 @@ __global__ void cxp_k_weld_insert(const double* pts, const uint32_t* prio, uint3
     if (vkeep && !vkeep[v]) return;   // seeded selection: vertices of dropped components do not exist
     if (cxp_weld_alone(pts + (size_t)v * 3, prio[v], W)) return;
     const u64 key = cxp_weld_key(pts + (size_t)v * 3, W);
-    u64 slot = cxp_mix(key) & mask;
+    u64 slot = cxd_mix(key) & mask;
     for (;;) {
-        const u64 cur = atomicCAS(&tkeys[slot], CXP_EMPTY, key);
-        if (cur == CXP_EMPTY || cur == key) break;
+        const u64 cur = atomicCAS(&tkeys[slot], CXD_EMPTY, key);
+        if (cur == CXD_EMPTY || cur == key) break;
         slot = (slot + 1) & mask;
     }
     atomicMax(&tvals[slot], ((u64)prio[v] << 32) | (u64)v);
@@ -400,7 +364,7 @@ __global__ void cxp_k_weld_lookup(const double* pts, uint32_t nv, cxp_weld_param
     if (vkeep && !vkeep[v]) { rep[v] = v; return; }
     if (cxp_weld_alone(pts + (size_t)v * 3, prio[v], W)) { rep[v] = v; return; }
     const u64 key = cxp_weld_key(pts + (size_t)v * 3, W);
-    u64 slot = cxp_mix(key) & mask;
+    u64 slot = cxd_mix(key) & mask;
     while (tkeys[slot] != key) slot = (slot + 1) & mask;
     rep[v] = (uint32_t)tvals[slot];
 }
@@ -462,10 +426,10 @@ __global__ void cxp_k_dedupe_insert(const int32_t* tri, const uint32_t* tprio3, 
     if (involved && !(involved[tri[(size_t)t * 3]] | involved[tri[(size_t)t * 3 + 1]] | involved[tri[(size_t)t * 3 + 2]])) return;   // cannot have a twin
     const cxp_tri3 me = cxp_sorted3((uint32_t)tri[(size_t)t * 3], (uint32_t)tri[(size_t)t * 3 + 1], (uint32_t)tri[(size_t)t * 3 + 2]);
     const cxp_tri3 mp = {tprio3[(size_t)t * 3], tprio3[(size_t)t * 3 + 1], tprio3[(size_t)t * 3 + 2]};
-    u64 slot = cxp_mix(((u64)me.a << 40) ^ ((u64)me.b << 20) ^ (u64)me.c ^ ((u64)me.c << 50)) & mask;
+    u64 slot = cxd_mix(((u64)me.a << 40) ^ ((u64)me.b << 20) ^ (u64)me.c ^ ((u64)me.c << 50)) & mask;
     for (;;) {
-        u64 cur = atomicCAS(&table[slot], CXP_EMPTY, (u64)t);
-        if (cur == CXP_EMPTY) return;
+        u64 cur = atomicCAS(&table[slot], CXD_EMPTY, (u64)t);
+        if (cur == CXD_EMPTY) return;
         for (;;) {   // slot occupied by triangle `cur`: same vertex set?
             const uint32_t o = (uint32_t)cur;
             const cxp_tri3 ot = cxp_sorted3((uint32_t)tri[(size_t)o * 3], (uint32_t)tri[(size_t)o * 3 + 1], (uint32_t)tri[(size_t)o * 3 + 2]);
@@ -484,7 +448,7 @@ __global__ void cxp_k_dedupe_resolve(const int32_t* tri, uint8_t* alive, uint32_
     if (t >= nt || !alive[t]) return;
     if (involved && !(involved[tri[(size_t)t * 3]] | involved[tri[(size_t)t * 3 + 1]] | involved[tri[(size_t)t * 3 + 2]])) return;   // was not inserted
     const cxp_tri3 me = cxp_sorted3((uint32_t)tri[(size_t)t * 3], (uint32_t)tri[(size_t)t * 3 + 1], (uint32_t)tri[(size_t)t * 3 + 2]);
-    u64 slot = cxp_mix(((u64)me.a << 40) ^ ((u64)me.b << 20) ^ (u64)me.c ^ ((u64)me.c << 50)) & mask;
+    u64 slot = cxd_mix(((u64)me.a << 40) ^ ((u64)me.b << 20) ^ (u64)me.c ^ ((u64)me.c << 50)) & mask;
     for (;;) {
         const uint32_t o = (uint32_t)table[slot];
         if (o == t) return;
@@ -686,8 +650,8 @@ __device__ __forceinline__ uint32_t cxp_edge_dir(const int32_t* tri, uint32_t t,
 // (mult == 0: plain hashing -- the small first table of cxp_k_edges_block, where the edges that arrive are the ones around merged
 // vertices, clustered in space: rows per vertex ran into each other there, chains of hundreds of probes)
 __device__ __forceinline__ u64 cxp_edge_slot(uint32_t lo, uint32_t hi, u64 mask, u64 mult) {
-    if (mult == 0) return cxp_mix(((u64)lo << 32) | (u64)hi) & mask;
-    return ((u64)lo * mult + (cxp_mix((u64)hi) % mult)) & mask;
+    if (mult == 0) return cxd_mix(((u64)lo << 32) | (u64)hi) & mask;
+    return ((u64)lo * mult + (cxd_mix((u64)hi) % mult)) & mask;
 }
 __global__ void cxp_k_edges_claim(const int32_t* tri, uint32_t nt, u64* tab, u64 mask, u64 mult) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -702,8 +666,8 @@ __global__ void cxp_k_edges_claim(const int32_t* tri, uint32_t nt, u64* tab, u64
             // plain read first: the second visitor of an edge usually finds the key already there and needs no
             // read-modify-write (a stale EMPTY only costs the CAS it would have done anyway)
             u64 cur = __hip_atomic_load(&tab[2 * slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (cur == CXP_EMPTY) cur = atomicCAS(&tab[2 * slot], CXP_EMPTY, key);
-            if (cur == CXP_EMPTY) { __hip_atomic_store(&tab[2 * slot + 1], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+            if (cur == CXD_EMPTY) cur = atomicCAS(&tab[2 * slot], CXD_EMPTY, key);
+            if (cur == CXD_EMPTY) { __hip_atomic_store(&tab[2 * slot + 1], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
             if (cur == key) break;
             slot = (slot + 1) & mask;
         }
@@ -775,7 +739,7 @@ __global__ __launch_bounds__(256) void cxp_k_edges_link_local(const int32_t* tri
             u64 slot = cxp_edge_slot(lo, hi, mask, mult);
             while (tab[2 * slot] != key) slot = (slot + 1) & mask;   // every key was inserted by the claim kernel
             const uint32_t o = (uint32_t)tab[2 * slot + 1];
-            uint32_t far = CXP_NONE;
+            uint32_t far = CXD_NONE;
             if (o != t) {
                 if (o - b0 < CXP_LINK_BLOCK) {          // partner in this block (o >= b0 by unsigned wrap-around)
                     uint32_t a = t - b0, b = o - b0;
@@ -807,7 +771,7 @@ __global__ void cxp_k_edges_link_cross(uint32_t nt, const uint32_t* others, u64*
 #pragma unroll
     for (int e = 0; e < 3; e++) {
         const uint32_t o = others[(size_t)t * 3 + e];
-        if (o != CXP_NONE) cxp_union0(parent, t, o);
+        if (o != CXD_NONE) cxp_union0(parent, t, o);
     }
 }
 // ---- the same linking for the MARCH'S OWN meshes, most of it in LDS ------------------------------------------------------
@@ -835,7 +799,7 @@ __global__ __launch_bounds__(256) void cxp_k_edges_block(const int32_t* tri, uin
     __shared__ uint8_t lpair[CXP_EB_SLOTS];
     __shared__ uint32_t lp[CXP_EB];
     const uint32_t b0 = blockIdx.x * CXP_EB;
-    for (uint32_t x = threadIdx.x; x < CXP_EB_SLOTS; x += 256u) { lkey[x] = CXP_EMPTY; lpair[x] = 0; }
+    for (uint32_t x = threadIdx.x; x < CXP_EB_SLOTS; x += 256u) { lkey[x] = CXD_EMPTY; lpair[x] = 0; }
     for (uint32_t x = threadIdx.x; x < CXP_EB; x += 256u) lp[x] = x;
     uint32_t lo_[CXP_EB_PER][3], hi_[CXP_EB_PER][3];
     uint32_t flag_[CXP_EB_PER][3];
@@ -864,10 +828,10 @@ __global__ __launch_bounds__(256) void cxp_k_edges_block(const int32_t* tri, uin
 #pragma unroll
         for (int e = 0; e < 3; e++) {
             const u64 key = ((u64)lo_[i][e] << 32) | (u64)hi_[i][e];
-            uint32_t slot = (uint32_t)cxp_mix(key) & (CXP_EB_SLOTS - 1u);
+            uint32_t slot = (uint32_t)cxd_mix(key) & (CXP_EB_SLOTS - 1u);
             for (uint32_t probes = 0; probes < CXP_EB_SLOTS; probes++) {      // (always ends earlier: the table cannot fill up)
-                const u64 cur = atomicCAS((unsigned long long*)&lkey[slot], (unsigned long long)CXP_EMPTY, (unsigned long long)key);
-                if (cur == CXP_EMPTY) { lfirst[slot] = (uint16_t)lt; break; }
+                const u64 cur = atomicCAS((unsigned long long*)&lkey[slot], (unsigned long long)CXD_EMPTY, (unsigned long long)key);
+                if (cur == CXD_EMPTY) { lfirst[slot] = (uint16_t)lt; break; }
                 if (cur == key) break;
                 slot = (slot + 1u) & (CXP_EB_SLOTS - 1u);
             }
@@ -916,8 +880,8 @@ __global__ __launch_bounds__(256) void cxp_k_edges_block(const int32_t* tri, uin
                 for (uint32_t probes = 0;; probes++) {
                     if (probes >= probe_limit) { *overflow = 1u; break; }
                     u64 cur = __hip_atomic_load(&tab[2 * slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (cur == CXP_EMPTY) cur = atomicCAS(&tab[2 * slot], CXP_EMPTY, key);
-                    if (cur == CXP_EMPTY) { __hip_atomic_store(&tab[2 * slot + 1], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                    if (cur == CXD_EMPTY) cur = atomicCAS(&tab[2 * slot], CXD_EMPTY, key);
+                    if (cur == CXD_EMPTY) { __hip_atomic_store(&tab[2 * slot + 1], (u64)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
                     if (cur == key) break;
                     slot = (slot + 1) & mask;
                 }
@@ -966,7 +930,7 @@ __global__ void cxp_k_comp_maxx(const int32_t* tri, uint32_t nt, const double* p
     if (have) {
         root = (uint32_t)parent[t];
 #pragma unroll
-        for (int s = 0; s < 3; s++) m = max(m, cxp_orderable(pts[(size_t)tri[(size_t)t * 3 + s] * 3]));
+        for (int s = 0; s < 3; s++) m = max(m, cxd_orderable(pts[(size_t)tri[(size_t)t * 3 + s] * 3]));
     }
     cxp_wave_max64(cmaxx, root, m, have);
 }
@@ -980,7 +944,7 @@ __global__ void cxp_k_comp_list(const int32_t* tri, uint32_t nt, const double* p
     if (t < nt && CXP_OWN(cls, t)) {
         const u64 m = cmaxx[(uint32_t)parent[t]];
 #pragma unroll
-        for (int s = 0; s < 3; s++) hit = hit || cxp_orderable(pts[(size_t)tri[(size_t)t * 3 + s] * 3]) == m;
+        for (int s = 0; s < 3; s++) hit = hit || cxd_orderable(pts[(size_t)tri[(size_t)t * 3 + s] * 3]) == m;
     }
     const uint64_t hits = __ballot(hit);
     if (hits == 0ULL) return;
@@ -1007,7 +971,7 @@ __global__ void cxp_k_comp_maxv(const int32_t* tri, uint32_t nt, const double* p
 #pragma unroll
         for (int s = 0; s < 3; s++) {
             const uint32_t v = tri[(size_t)t * 3 + s];
-            if (cxp_orderable(pts[(size_t)v * 3]) == m) cxp_max64(&cmaxv[root], ((u64)(keys ? keys[v] : v) << 32) | (u64)v);
+            if (cxd_orderable(pts[(size_t)v * 3]) == m) cxd_max64(&cmaxv[root], ((u64)(keys ? keys[v] : v) << 32) | (u64)v);
         }
     CXP_END_FOR
 }
@@ -1026,7 +990,7 @@ __global__ void cxp_k_comp_start(const int32_t* tri, uint32_t nt, const double* 
         const uint32_t root = (uint32_t)parent[t];
         const uint32_t vm = (uint32_t)cmaxv[root];
         if ((uint32_t)tri[(size_t)t * 3] != vm && (uint32_t)tri[(size_t)t * 3 + 1] != vm && (uint32_t)tri[(size_t)t * 3 + 2] != vm) continue;
-        cxp_max64(&cbest[root], cxp_orderable(fabs(cxp_dotx(tri, t, pts))));
+        cxd_max64(&cbest[root], cxd_orderable(fabs(cxp_dotx(tri, t, pts))));
     CXP_END_FOR
 }
 __global__ void cxp_k_comp_pick(const int32_t* tri, uint32_t nt, const double* pts, const u64* parent, const u64* cmaxv,
@@ -1036,7 +1000,7 @@ __global__ void cxp_k_comp_pick(const int32_t* tri, uint32_t nt, const double* p
         const uint32_t root = (uint32_t)parent[t];
         const uint32_t vm = (uint32_t)cmaxv[root];
         if ((uint32_t)tri[(size_t)t * 3] != vm && (uint32_t)tri[(size_t)t * 3 + 1] != vm && (uint32_t)tri[(size_t)t * 3 + 2] != vm) continue;
-        if (cxp_orderable(fabs(cxp_dotx(tri, t, pts))) == cbest[root]) cxp_max32(&cstart[root], t);
+        if (cxd_orderable(fabs(cxp_dotx(tri, t, pts))) == cbest[root]) cxd_max32(&cstart[root], t);
     CXP_END_FOR
 }
 // the root's flip, so that the start triangle gets dotx > 0 (surface_geometry.py:99-103).  Decided in its own kernel,
@@ -1107,9 +1071,9 @@ __global__ void cxp_k_shard_gather_cls(const uint8_t* cls, const uint32_t* told,
 // components are one.  (The copies on the other side -- classes 2 / 3 -- would say the same again: a link between two
 // slabs' triangles is seen from both.)  Components with such a triangle are marked open.
 __device__ __forceinline__ u64 cxp_triple_hash(u64 a, u64 b, u64 c) {
-    u64 h = cxp_mix(a + 0x9E3779B97F4A7C15ULL);
-    h = cxp_mix(h ^ (b + 0xC2B2AE3D27D4EB4FULL));
-    return cxp_mix(h ^ (c + 0x165667B19E3779F9ULL));
+    u64 h = cxd_mix(a + 0x9E3779B97F4A7C15ULL);
+    h = cxd_mix(h ^ (b + 0xC2B2AE3D27D4EB4FULL));
+    return cxd_mix(h ^ (c + 0x165667B19E3779F9ULL));
 }
 __global__ void cxp_k_shard_boundary(const uint8_t* cls2, const uint32_t* told, const uint32_t* tprio3, const u64* parent, uint32_t nt2,
                                      u64 key_offset, uint32_t* counters, uint32_t cap1, uint32_t cap4, u64* hash1, uint32_t* label1,
@@ -1161,12 +1125,6 @@ __global__ void cxp_k_shard_own_alive(const uint8_t* cls2, uint32_t nt2, uint8_t
 
 
 // ---- host orchestration ----------------------------------------------------------------------------------
-static inline uint32_t cxp_blocks(size_t n, uint32_t b = 256) { return (uint32_t)((n + b - 1) / b); }
-static inline u64 cxp_table_size(size_t n) {
-    u64 s = 1024;
-    while (s < 2 * (u64)n + 16) s <<= 1;
-    return s;
-}
 // edge tables: n = 3 * triangles is an upper bound that only an open mesh without shared edges reaches; a closed
 // mesh has half as many distinct edges.  5/4 of the bound keeps the worst case below a load of 0.8 and the usual
 // case near 0.25-0.4 with half the footprint (the table is touched at random: footprint is what costs)
@@ -1180,32 +1138,32 @@ static inline u64 cxp_edge_table_size(size_t n) {
 // run into each other)
 
 static int cxp_scan(cx_ctx* ctx, cx_post_state* S, const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* total_dev) {
-    const uint32_t nb = cxp_blocks(n, CXP_SCAN_BLOCK);
+    const uint32_t nb = cx_blocks(n, CXP_SCAN_BLOCK);
     int rc = S->blocksums.grow(ctx, (size_t)(nb + 1) * sizeof(uint32_t));
     if (rc) return rc;
     uint32_t* sums = S->blocksums.as<uint32_t>();
     hipLaunchKernelGGL(cxp_k_scan_blocks, dim3(nb ? nb : 1), dim3(256), 0, ctx->stream, in, out, sums, n);
     hipLaunchKernelGGL(cxp_k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums, nb, total_dev, (unsigned long long*)nullptr);
-    hipLaunchKernelGGL(cxp_k_scan_add, dim3(cxp_blocks(n)), dim3(256), 0, ctx->stream, out, sums, n);
+    hipLaunchKernelGGL(cxp_k_scan_add, dim3(cx_blocks(n)), dim3(256), 0, ctx->stream, out, sums, n);
     return CX_OK;
 }
 
 // exclusive scan for the other translation units (cx_contour2d.hip); sums_tmp holds n/1024 + 2 words
 int cx_scan_u32(cx_ctx* ctx, const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* sums_tmp, uint32_t* total_dev, unsigned long long* total64_dev) {
-    const uint32_t nb = cxp_blocks(n, CXP_SCAN_BLOCK);
+    const uint32_t nb = cx_blocks(n, CXP_SCAN_BLOCK);
     hipLaunchKernelGGL(cxp_k_scan_blocks, dim3(nb ? nb : 1), dim3(256), 0, ctx->stream, in, out, sums_tmp, n);
     hipLaunchKernelGGL(cxp_k_scan_sums, dim3(1), dim3(1024), 0, ctx->stream, sums_tmp, nb, total_dev, total64_dev);
-    if (n) hipLaunchKernelGGL(cxp_k_scan_add, dim3(cxp_blocks(n)), dim3(256), 0, ctx->stream, out, sums_tmp, n);
+    if (n) hipLaunchKernelGGL(cxp_k_scan_add, dim3(cx_blocks(n)), dim3(256), 0, ctx->stream, out, sums_tmp, n);
     return CX_OK;
 }
 
 static int cxp_flatten(cx_ctx* ctx, u64* parent, uint32_t n, uint32_t* changed_dev) {
     for (int it = 0; it < 64; it++) {
-        CXP_HIP(ctx, hipMemsetAsync(changed_dev, 0, sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(cxp_k_jump, dim3(cxp_blocks(n)), dim3(256), 0, ctx->stream, parent, n, changed_dev);
+        CX_HIP(ctx, hipMemsetAsync(changed_dev, 0, sizeof(uint32_t), ctx->stream));
+        hipLaunchKernelGGL(cxp_k_jump, dim3(cx_blocks(n)), dim3(256), 0, ctx->stream, parent, n, changed_dev);
         uint32_t changed = 0;
-        CXP_HIP(ctx, hipMemcpyAsync(&changed, changed_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        CXP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        CX_HIP(ctx, hipMemcpyAsync(&changed, changed_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (!changed) return CX_OK;
     }
     ctx->err = "union-find did not flatten";
@@ -1231,16 +1189,16 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
     S->simplified = false; S->carried = false; S->smap_valid = false;
     if (do_clean && nt) {
         u64* parent2 = S->parent2.as<u64>();
-        hipLaunchKernelGGL(cxp_k_iota64, dim3(cxp_blocks(nv)), dim3(256), 0, st, parent2, nv);
-        hipLaunchKernelGGL(cxp_k_degenerate, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, pts, parent2, prio);
-        if (involved) CXP_HIP(ctx, hipMemsetAsync(involved, 0, nv, st));
-        hipLaunchKernelGGL(cxp_k_remap, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, (const uint32_t*)nullptr, parent2, involved, ever);
+        hipLaunchKernelGGL(cxp_k_iota64, dim3(cx_blocks(nv)), dim3(256), 0, st, parent2, nv);
+        hipLaunchKernelGGL(cxp_k_degenerate, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, pts, parent2, prio);
+        if (involved) CX_HIP(ctx, hipMemsetAsync(involved, 0, nv, st));
+        hipLaunchKernelGGL(cxp_k_remap, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, (const uint32_t*)nullptr, parent2, involved, ever);
         // (with the filter only triangles next to a merge enter the table: 5/4 of the bound is plenty and half as much to clear)
-        const u64 tsz = involved ? cxp_edge_table_size(nt) : cxp_table_size(nt);
+        const u64 tsz = involved ? cxp_edge_table_size(nt) : cx_table_size(nt);
         if ((rc = S->tkeys.grow(ctx, tsz * sizeof(u64)))) return rc;
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXP_EMPTY);
-        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
-        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
+        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXD_EMPTY);
+        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
+        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
     }
     // ---- sharded: the second layer of the neighbours' cells has done its work (weld, tiny collapse and clean-up above saw it)
     uint8_t* cls = nullptr;
@@ -1250,13 +1208,13 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
         if ((rc = S->told.grow(ctx, ((size_t)nt + 16) * sizeof(uint32_t)))) return rc;
         cls = S->cls.as<uint8_t>();
         told = S->told.as<uint32_t>();
-        CXP_HIP(ctx, hipMemsetAsync(misc + 6, 0, 2 * sizeof(uint32_t), st));
-        if (nt) hipLaunchKernelGGL(cxp_k_shard_classify, dim3(cxp_blocks(nt)), dim3(256), 0, st, tprio3, alive, nt, *shard, cx_fdiv_make(shard->plane), cls, misc + 6);
+        CX_HIP(ctx, hipMemsetAsync(misc + 6, 0, 2 * sizeof(uint32_t), st));
+        if (nt) hipLaunchKernelGGL(cxp_k_shard_classify, dim3(cx_blocks(nt)), dim3(256), 0, st, tprio3, alive, nt, *shard, cx_fdiv_make(shard->plane), cls, misc + 6);
     }
     // ---- compaction of used vertices and living triangles (byte flags, per-block counts, the scan redone inside the two consumers)
     if ((rc = S->flags.grow(ctx, (size_t)(nv + nt + 16) * sizeof(uint32_t)))) return rc;      // (also: the list of possible start triangles below)
     if ((rc = S->scan.grow(ctx, (size_t)(nv + 16) * sizeof(uint32_t)))) return rc;
-    const uint32_t nbv = cxp_blocks(nv, CXP_SCAN_BLOCK), nbt = cxp_blocks(nt, CXP_SCAN_BLOCK);
+    const uint32_t nbv = cx_blocks(nv, CXP_SCAN_BLOCK), nbt = cx_blocks(nt, CXP_SCAN_BLOCK);
     if ((rc = S->blocksums.grow(ctx, (size_t)(nbv + nbt + 16) * sizeof(uint32_t)))) return rc;
     uint8_t* used = S->flags.as<uint8_t>();
     uint32_t* vnew = S->scan.as<uint32_t>();
@@ -1264,14 +1222,14 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
     uint32_t* toff = voff + nbv + 8;
     uint32_t nv2 = 0, nt2 = 0;
     if (nt) {
-        CXP_HIP(ctx, hipMemsetAsync(used, 0, (size_t)nv, st));
-        hipLaunchKernelGGL(cxp_k_mark_used8, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, used);
+        CX_HIP(ctx, hipMemsetAsync(used, 0, (size_t)nv, st));
+        hipLaunchKernelGGL(cxp_k_mark_used8, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, used);
         hipLaunchKernelGGL(cxp_k_me_count, dim3(nbv), dim3(256), 0, st, (const uint8_t*)used, nv, voff);
         hipLaunchKernelGGL(cxp_k_me_count, dim3(nbt), dim3(256), 0, st, (const uint8_t*)alive, nt, toff);
         hipLaunchKernelGGL(cxp_k_scan_sums2, dim3(2), dim3(1024), 0, st, voff, nbv, misc + 1, toff, nbt, misc + 2);
         uint32_t h[2];
-        CXP_HIP(ctx, hipMemcpyAsync(h, misc + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CXP_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipMemcpyAsync(h, misc + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
         nv2 = h[0]; nt2 = h[1];
     }
     if ((rc = S->pts_out.grow(ctx, (size_t)(nv2 + 1) * 3 * sizeof(double)))) return rc;
@@ -1291,7 +1249,7 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
     uint8_t* cls2 = nullptr;
     if (shard) {
         cls2 = cls + nt;
-        if (nt2) hipLaunchKernelGGL(cxp_k_shard_gather_cls, dim3(cxp_blocks(nt2)), dim3(256), 0, st, cls, told, nt2, cls2);
+        if (nt2) hipLaunchKernelGGL(cxp_k_shard_gather_cls, dim3(cx_blocks(nt2)), dim3(256), 0, st, cls, told, nt2, cls2);
     }
     uint32_t ncomp = 0;
     if (do_orient && nt2) {
@@ -1323,42 +1281,42 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
             u64* etab = S->tkeys.as<u64>();
             // (measured and dropped: clearing the table on a second stream while weld / tiny collapse / clean-up run -- no gain, the fill
             // takes from them what it saves)
-            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, etab, (size_t)(2 * esz), CXP_EMPTY);
-            hipLaunchKernelGGL(cxp_k_iota64, dim3(cxp_blocks(nt2)), dim3(256), 0, st, parent, nt2);
+            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, etab, (size_t)(2 * esz), CXD_EMPTY);
+            hipLaunchKernelGGL(cxp_k_iota64, dim3(cx_blocks(nt2)), dim3(256), 0, st, parent, nt2);
             const u64 emult = (blocks && esz != esz_full) ? 0 : std::max<u64>(1, esz / std::max<u64>(1, (u64)nv2));
             if (blocks) {
-                CXP_HIP(ctx, hipMemsetAsync(misc + 12, 0, sizeof(uint32_t), st));
+                CX_HIP(ctx, hipMemsetAsync(misc + 12, 0, sizeof(uint32_t), st));
                 hipLaunchKernelGGL(cxp_k_edges_block, dim3((nt2 + CXP_EB - 1u) / CXP_EB), dim3(256), 0, st, tri2, nt2, (const uint8_t*)(ever + nv), etab, esz - 1,
                                    emult, parent, (uint8_t*)others, esz == esz_full ? 0xFFFFFFFFu : 256u, misc + 12);
                 if (esz != esz_full) {
                     uint32_t over = 0;
-                    CXP_HIP(ctx, hipMemcpyAsync(&over, misc + 12, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                    CXP_HIP(ctx, hipStreamSynchronize(st));
+                    CX_HIP(ctx, hipMemcpyAsync(&over, misc + 12, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                    CX_HIP(ctx, hipStreamSynchronize(st));
                     if (over) { esz = esz_full; continue; }
                 }
-                hipLaunchKernelGGL(cxp_k_edges_link_far, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, nt2, etab, esz - 1, emult, (const uint8_t*)others, parent);
+                hipLaunchKernelGGL(cxp_k_edges_link_far, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, nt2, etab, esz - 1, emult, (const uint8_t*)others, parent);
             } else {
-                hipLaunchKernelGGL(cxp_k_edges_claim, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, nt2, etab, esz - 1, emult);
+                hipLaunchKernelGGL(cxp_k_edges_claim, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, nt2, etab, esz - 1, emult);
                 if (coherent && !cx_debug_knob("CX_LINK_ONE_STEP", 0)) {
                     hipLaunchKernelGGL(cxp_k_edges_link_local, dim3((nt2 + CXP_LINK_BLOCK - 1u) / CXP_LINK_BLOCK), dim3(256), 0, st, tri2, nt2, etab, esz - 1,
                                        emult, parent, others);
-                    hipLaunchKernelGGL(cxp_k_edges_link_cross, dim3(cxp_blocks(nt2)), dim3(256), 0, st, nt2, others, parent);
+                    hipLaunchKernelGGL(cxp_k_edges_link_cross, dim3(cx_blocks(nt2)), dim3(256), 0, st, nt2, others, parent);
                 } else
-                    hipLaunchKernelGGL(cxp_k_edges_link, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, nt2, etab, esz - 1, emult, parent, coherent ? 1 : 0);
+                    hipLaunchKernelGGL(cxp_k_edges_link, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, nt2, etab, esz - 1, emult, parent, coherent ? 1 : 0);
             }
             break;
         }
         if ((rc = cxp_flatten(ctx, parent, nt2, misc))) return rc;
-        CXP_HIP(ctx, hipMemsetAsync(cmaxx, 0, (size_t)nt2 * (3 * sizeof(u64) + sizeof(uint32_t)), st));
-        CXP_HIP(ctx, hipMemsetAsync(misc + 3, 0, sizeof(uint32_t), st));
+        CX_HIP(ctx, hipMemsetAsync(cmaxx, 0, (size_t)nt2 * (3 * sizeof(u64) + sizeof(uint32_t)), st));
+        CX_HIP(ctx, hipMemsetAsync(misc + 3, 0, sizeof(uint32_t), st));
         const uint8_t* own = cls2;
-        hipLaunchKernelGGL(cxp_k_comp_maxx, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, nt2, pts2, parent, cmaxx, own);
+        hipLaunchKernelGGL(cxp_k_comp_maxx, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, nt2, pts2, parent, cmaxx, own);
         // (the scan / flag arrays of the compaction are free by now: the list of possible start triangles goes there)
         uint32_t* clist = S->flags.as<uint32_t>();
         const uint32_t* cn = misc + 11;
-        const dim3 lgrid(std::min(cxp_blocks(nt2), 1024u));
-        CXP_HIP(ctx, hipMemsetAsync(misc + 11, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(cxp_k_comp_list, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, nt2, pts2, parent, cmaxx, own, clist, misc + 11);
+        const dim3 lgrid(std::min(cx_blocks(nt2), 1024u));
+        CX_HIP(ctx, hipMemsetAsync(misc + 11, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(cxp_k_comp_list, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, nt2, pts2, parent, cmaxx, own, clist, misc + 11);
         hipLaunchKernelGGL(cxp_k_comp_maxv, lgrid, dim3(256), 0, st, tri2, nt2, pts2, parent, cmaxx, cmaxv, (const uint32_t*)keys2, own, (const uint32_t*)clist, cn);
         hipLaunchKernelGGL(cxp_k_comp_start, lgrid, dim3(256), 0, st, tri2, nt2, pts2, parent, cmaxv, cbest, own, (const uint32_t*)clist, cn);
         hipLaunchKernelGGL(cxp_k_comp_pick, lgrid, dim3(256), 0, st, tri2, nt2, pts2, parent, cmaxv, cbest, cstart, own, (const uint32_t*)clist, cn);
@@ -1366,8 +1324,8 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
             // what the neighbours need: the triangles at the slab boundaries with their labels (they stay on the device), and the
             // start-triangle candidate of every component that reaches a neighbour.  Sizes follow the slab boundary, not the slab.
             uint32_t hb[2] = {0, 0};
-            CXP_HIP(ctx, hipMemcpyAsync(hb, misc + 6, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            CXP_HIP(ctx, hipStreamSynchronize(st));
+            CX_HIP(ctx, hipMemcpyAsync(hb, misc + 6, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            CX_HIP(ctx, hipStreamSynchronize(st));
             const size_t n1 = hb[0], n4 = hb[1], nb = n1 + n4;
             // layout of S->bnd: hash1 u64[n1] | hash4 u64[n4] | candidates cxp_cand[nb] | label1 u32[n1] | label4 u32[n4]
             if ((rc = S->bnd.grow(ctx, (nb + 2) * (sizeof(u64) + sizeof(cxp_cand) + sizeof(uint32_t)) + 64))) return rc;
@@ -1377,33 +1335,33 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
             uint32_t* label1 = (uint32_t*)(cand + nb);
             uint32_t* label4 = label1 + n1;
             uint8_t* open = cls + 2 * (size_t)nt;
-            CXP_HIP(ctx, hipMemsetAsync(open, 0, nt2, st));
-            CXP_HIP(ctx, hipMemsetAsync(misc + 8, 0, 3 * sizeof(uint32_t), st));
+            CX_HIP(ctx, hipMemsetAsync(open, 0, nt2, st));
+            CX_HIP(ctx, hipMemsetAsync(misc + 8, 0, 3 * sizeof(uint32_t), st));
             if (nb) {
                 const u64 key_offset = ((u64)ctx->origin[0] * (u64)shard->plane) << 3;
-                hipLaunchKernelGGL(cxp_k_shard_boundary, dim3(cxp_blocks(nt2)), dim3(256), 0, st, cls2, told, tprio3, parent, nt2, key_offset, misc + 8,
+                hipLaunchKernelGGL(cxp_k_shard_boundary, dim3(cx_blocks(nt2)), dim3(256), 0, st, cls2, told, tprio3, parent, nt2, key_offset, misc + 8,
                                    (uint32_t)n1, (uint32_t)n4, hash1, label1, hash4, label4, open);
-                hipLaunchKernelGGL(cxp_k_shard_candidates, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, pts2, keys2, parent, open, nt2, cmaxx, cmaxv,
+                hipLaunchKernelGGL(cxp_k_shard_candidates, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, pts2, keys2, parent, open, nt2, cmaxx, cmaxv,
                                    cstart, misc + 10, (uint32_t)nb, cand);
             }
             uint32_t h2[3] = {0, 0, 0};
-            CXP_HIP(ctx, hipMemcpyAsync(h2, misc + 8, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            CXP_HIP(ctx, hipStreamSynchronize(st));
+            CX_HIP(ctx, hipMemcpyAsync(h2, misc + 8, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            CX_HIP(ctx, hipStreamSynchronize(st));
             if (h2[0] != n1 || h2[1] != n4 || h2[2] > nb) { ctx->err = "sharded Level 1: boundary lists do not add up"; return CX_ERR_HIP; }
             S->shard.n1 = (uint32_t)n1; S->shard.n4 = (uint32_t)n4; S->shard.ncand = h2[2];
         }
         hipLaunchKernelGGL(cxp_k_comp_decide, lgrid, dim3(256), 0, st, tri2, nt2, pts2, parent, cstart, cbest, (const uint32_t*)clist, cn);
         if (!shard) {
-            hipLaunchKernelGGL(cxp_k_orient, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, nt2, parent, cbest, misc + 3);
-            CXP_HIP(ctx, hipMemcpyAsync(&ncomp, misc + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            hipLaunchKernelGGL(cxp_k_orient, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, nt2, parent, cbest, misc + 3);
+            CX_HIP(ctx, hipMemcpyAsync(&ncomp, misc + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             S->orient_live = true; S->orient_nt = nt2;
         }
-        CXP_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
     } else if (shard) {
         S->shard.n1 = 0; S->shard.n4 = 0; S->shard.ncand = 0;
     }
     if (shard) { S->shard.open = true; S->shard.nv2 = nv2; S->shard.nt2 = nt2; S->shard.nt_in = nt; }
-    CXP_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipGetLastError());
     if (out_counts) {
         out_counts[0] = nv2; out_counts[1] = nt2; out_counts[4] = ncomp;
     }
@@ -1428,29 +1386,29 @@ static int cxp_shard_finish(cx_ctx* ctx, cx_post_state* S, const uint32_t* label
             if ((rc = S->keys_tmp.grow(ctx, std::max((size_t)n * 5 + 64, (size_t)(nv2 + 1) * sizeof(uint32_t))))) return rc;
             uint32_t* dl = S->keys_tmp.as<uint32_t>();
             uint8_t* df = (uint8_t*)(dl + n);
-            CXP_HIP(ctx, hipMemcpyAsync(dl, labels, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-            CXP_HIP(ctx, hipMemcpyAsync(df, flips, (size_t)n, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(cxp_k_shard_set_flips, dim3(cxp_blocks(n)), dim3(256), 0, st, dl, df, n, nt2, cflip);
+            CX_HIP(ctx, hipMemcpyAsync(dl, labels, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+            CX_HIP(ctx, hipMemcpyAsync(df, flips, (size_t)n, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(cxp_k_shard_set_flips, dim3(cx_blocks(n)), dim3(256), 0, st, dl, df, n, nt2, cflip);
         }
-        CXP_HIP(ctx, hipMemsetAsync(misc + 3, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(cxp_k_orient, dim3(cxp_blocks(nt2)), dim3(256), 0, st, tri2, nt2, parent, cflip, misc + 3);
+        CX_HIP(ctx, hipMemsetAsync(misc + 3, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(cxp_k_orient, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, nt2, parent, cflip, misc + 3);
         // own triangles and the vertices they use (the same ordered compaction as in cxp_clean_orient)
         uint8_t* alive = S->alive.as<uint8_t>();
         uint8_t* used = S->flags.as<uint8_t>();
         uint32_t* vnew = S->scan.as<uint32_t>();
-        const uint32_t nbv = cxp_blocks(nv2, CXP_SCAN_BLOCK), nbt = cxp_blocks(nt2, CXP_SCAN_BLOCK);
+        const uint32_t nbv = cx_blocks(nv2, CXP_SCAN_BLOCK), nbt = cx_blocks(nt2, CXP_SCAN_BLOCK);
         if ((rc = S->blocksums.grow(ctx, (size_t)(nbv + nbt + 16) * sizeof(uint32_t)))) return rc;
         uint32_t* voff = S->blocksums.as<uint32_t>();
         uint32_t* toff = voff + nbv + 8;
-        hipLaunchKernelGGL(cxp_k_shard_own_alive, dim3(cxp_blocks(nt2)), dim3(256), 0, st, cls2, nt2, alive);
-        CXP_HIP(ctx, hipMemsetAsync(used, 0, (size_t)nv2, st));
-        hipLaunchKernelGGL(cxp_k_mark_used8, dim3(cxp_blocks(nt2)), dim3(256), 0, st, (const int32_t*)tri2, (const uint8_t*)alive, nt2, used);
+        hipLaunchKernelGGL(cxp_k_shard_own_alive, dim3(cx_blocks(nt2)), dim3(256), 0, st, cls2, nt2, alive);
+        CX_HIP(ctx, hipMemsetAsync(used, 0, (size_t)nv2, st));
+        hipLaunchKernelGGL(cxp_k_mark_used8, dim3(cx_blocks(nt2)), dim3(256), 0, st, (const int32_t*)tri2, (const uint8_t*)alive, nt2, used);
         hipLaunchKernelGGL(cxp_k_me_count, dim3(nbv), dim3(256), 0, st, (const uint8_t*)used, nv2, voff);
         hipLaunchKernelGGL(cxp_k_me_count, dim3(nbt), dim3(256), 0, st, (const uint8_t*)alive, nt2, toff);
         hipLaunchKernelGGL(cxp_k_scan_sums2, dim3(2), dim3(1024), 0, st, voff, nbv, misc + 1, toff, nbt, misc + 2);
         uint32_t h[3];
-        CXP_HIP(ctx, hipMemcpyAsync(h, misc + 1, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CXP_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipMemcpyAsync(h, misc + 1, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
         nv3 = h[0]; nt3 = h[1]; ncomp = h[2];
         // the march's own buffers are free by now: they take the final mesh on its way back into the output buffers
         if ((rc = S->pts.grow(ctx, (size_t)(nv3 + 1) * 3 * sizeof(double)))) return rc;
@@ -1464,16 +1422,16 @@ static int cxp_shard_finish(cx_ctx* ctx, cx_post_state* S, const uint32_t* label
         }
         // back into the output buffers (every buffer keeps its size from call to call: nothing is reallocated for the next volume)
         if (nt3) {
-            CXP_HIP(ctx, hipMemcpyAsync(S->pts_out.get(), S->pts.get(), (size_t)nv3 * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
-            CXP_HIP(ctx, hipMemcpyAsync(S->tri_out.get(), S->tri.get(), (size_t)nt3 * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-            CXP_HIP(ctx, hipMemcpyAsync(S->keys_out.get(), S->keys_tmp.get(), (size_t)nv3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+            CX_HIP(ctx, hipMemcpyAsync(S->pts_out.get(), S->pts.get(), (size_t)nv3 * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+            CX_HIP(ctx, hipMemcpyAsync(S->tri_out.get(), S->tri.get(), (size_t)nt3 * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+            CX_HIP(ctx, hipMemcpyAsync(S->keys_out.get(), S->keys_tmp.get(), (size_t)nv3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         }
-        CXP_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
     }
     S->nv_out = nv3; S->nt_out = nt3;
     S->keys_valid = true;
     S->shard_mesh = true; S->gen++;
-    CXP_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipGetLastError());
     if (out_counts) { out_counts[0] = nv3; out_counts[1] = nt3; out_counts[4] = ncomp; }
     return CX_OK;
 }
@@ -1497,18 +1455,18 @@ __global__ void cxp_k_unique_edges(const int32_t* tri, const uint8_t* alive, uin
     for (int e = 0; e < 3; e++) {
         const uint32_t p = v[e], q = v[(e + 1) % 3];
         const u64 key = ((u64)min(p, q) << 32) | (u64)max(p, q);
-        u64 slot = cxp_mix(key) & mask;
+        u64 slot = cxd_mix(key) & mask;
         for (;;) {
             u64 cur = __hip_atomic_load(&ekeys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the second visitor of an edge needs no read-modify-write
-            if (cur == CXP_EMPTY) cur = atomicCAS(&ekeys[slot], CXP_EMPTY, key);
-            if (cur == CXP_EMPTY || cur == key) break;
+            if (cur == CXD_EMPTY) cur = atomicCAS(&ekeys[slot], CXD_EMPTY, key);
+            if (cur == CXD_EMPTY || cur == key) break;
             slot = (slot + 1) & mask;
         }
     }
 }
 __global__ void cxp_k_smooth_accumulate(const u64* ekeys, size_t n, const double* pts, double* sum, uint32_t* cnt) {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i >= n || ekeys[i] == CXP_EMPTY) return;
+    if (i >= n || ekeys[i] == CXD_EMPTY) return;
     const uint32_t a = (uint32_t)(ekeys[i] >> 32), b = (uint32_t)ekeys[i];
 #pragma unroll
     for (int c = 0; c < 3; c++) {
@@ -1529,7 +1487,7 @@ __global__ __launch_bounds__(256) void cxp_k_smooth_edges(const int32_t* tri, co
     __shared__ uint32_t lv[CXP_SM_SLOTS];
     __shared__ uint32_t lc[CXP_SM_SLOTS];
     __shared__ double ls[CXP_SM_SLOTS][3];
-    for (uint32_t x = threadIdx.x; x < CXP_SM_SLOTS; x += 256u) { lv[x] = CXP_NONE; lc[x] = 0u; ls[x][0] = 0.0; ls[x][1] = 0.0; ls[x][2] = 0.0; }
+    for (uint32_t x = threadIdx.x; x < CXP_SM_SLOTS; x += 256u) { lv[x] = CXD_NONE; lc[x] = 0u; ls[x][0] = 0.0; ls[x][1] = 0.0; ls[x][2] = 0.0; }
     __syncthreads();
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t < nt && alive[t]) {
@@ -1537,8 +1495,8 @@ __global__ __launch_bounds__(256) void cxp_k_smooth_edges(const int32_t* tri, co
         auto add = [&](uint32_t to, uint32_t from) {      // the point `from` into the sums of vertex `to`
             uint32_t slot = (to * 0x9E3779B1u) >> 22;      // 10 bits
             for (;;) {
-                const uint32_t cur = atomicCAS(&lv[slot], CXP_NONE, to);
-                if (cur == CXP_NONE || cur == to) break;
+                const uint32_t cur = atomicCAS(&lv[slot], CXD_NONE, to);
+                if (cur == CXD_NONE || cur == to) break;
                 slot = (slot + 1u) & (CXP_SM_SLOTS - 1u);  // (at most 768 vertices per workgroup: a free slot is always found)
             }
             unsafeAtomicAdd(&ls[slot][0], pts[(size_t)from * 3]);
@@ -1549,12 +1507,12 @@ __global__ __launch_bounds__(256) void cxp_k_smooth_edges(const int32_t* tri, co
         for (int e = 0; e < 3; e++) {
             const uint32_t p = v[e], q = v[(e + 1) % 3];
             const u64 key = ((u64)min(p, q) << 32) | (u64)max(p, q);
-            u64 slot = cxp_mix(key) & mask;
+            u64 slot = cxd_mix(key) & mask;
             bool mine = false;
             for (;;) {
                 u64 cur = __hip_atomic_load(&ekeys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the second visitor of an edge needs no read-modify-write
-                if (cur == CXP_EMPTY) { cur = atomicCAS(&ekeys[slot], CXP_EMPTY, key); mine = cur == CXP_EMPTY; }
-                if (cur == CXP_EMPTY || cur == key) break;
+                if (cur == CXD_EMPTY) { cur = atomicCAS(&ekeys[slot], CXD_EMPTY, key); mine = cur == CXD_EMPTY; }
+                if (cur == CXD_EMPTY || cur == key) break;
                 slot = (slot + 1) & mask;
             }
             if (mine && p != q) { add(p, q); add(q, p); }
@@ -1564,7 +1522,7 @@ __global__ __launch_bounds__(256) void cxp_k_smooth_edges(const int32_t* tri, co
     __syncthreads();
     for (uint32_t x = threadIdx.x; x < CXP_SM_SLOTS; x += 256u) {
         const uint32_t to = lv[x];
-        if (to == CXP_NONE) continue;
+        if (to == CXD_NONE) continue;
         atomicAdd(&sum[(size_t)to * 3], ls[x][0]);
         atomicAdd(&sum[(size_t)to * 3 + 1], ls[x][1]);
         atomicAdd(&sum[(size_t)to * 3 + 2], ls[x][2]);
@@ -1624,10 +1582,10 @@ static int cxp_run3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, co
     if (nv && nt && (edge_crossings || march_mesh) && coherent) {
         if ((rc = S->ever.grow(ctx, 2 * (size_t)nv + 64))) return rc;
         ever = S->ever.as<uint8_t>();
-        CXP_HIP(ctx, hipMemsetAsync(ever, 0, nv, st));
+        CX_HIP(ctx, hipMemsetAsync(ever, 0, nv, st));
     }
     if (nv && nt) {
-        hipLaunchKernelGGL(cxp_k_tri_prio, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, prio, nt, tprio3);
+        hipLaunchKernelGGL(cxp_k_tri_prio, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, prio, nt, tprio3);
         // ---- weld (tetrahedral.py:190-215): expander = int(10000 / corner)
         cxp_weld_params W;
         for (int a = 0; a < 3; a++) W.ex[a] = std::trunc((10000 * 1.0) / corner[a]);
@@ -1637,55 +1595,55 @@ static int cxp_run3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, co
             if (exmin >= 16.0) W.thr = 2.0 / exmin + 1e-9;
         }
         // (W.thr > 0: four of five crossings are alone in their bucket and skip the table -- 5/4 of the bound instead of twice it)
-        const u64 wsz = W.thr > 0.0 ? cxp_edge_table_size(nv) : cxp_table_size(nv);
-        if ((rc = S->tkeys.grow(ctx, std::max(wsz, cxp_table_size(nt)) * sizeof(u64)))) return rc;
+        const u64 wsz = W.thr > 0.0 ? cxp_edge_table_size(nv) : cx_table_size(nv);
+        if ((rc = S->tkeys.grow(ctx, std::max(wsz, cx_table_size(nt)) * sizeof(u64)))) return rc;
         if ((rc = S->tvals.grow(ctx, wsz * sizeof(u64)))) return rc;
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)wsz, CXP_EMPTY);
+        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)wsz, CXD_EMPTY);
         hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tvals.as<u64>(), (size_t)wsz, (u64)0);
-        hipLaunchKernelGGL(cxp_k_weld_insert, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, prio, nv, W, S->tkeys.as<u64>(), S->tvals.as<u64>(), wsz - 1, vkeep);
-        hipLaunchKernelGGL(cxp_k_weld_lookup, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, nv, W, S->tkeys.as<u64>(), S->tvals.as<u64>(), wsz - 1, rep, vkeep, prio);
+        hipLaunchKernelGGL(cxp_k_weld_insert, dim3(cx_blocks(nv)), dim3(256), 0, st, pts, prio, nv, W, S->tkeys.as<u64>(), S->tvals.as<u64>(), wsz - 1, vkeep);
+        hipLaunchKernelGGL(cxp_k_weld_lookup, dim3(cx_blocks(nv)), dim3(256), 0, st, pts, nv, W, S->tkeys.as<u64>(), S->tvals.as<u64>(), wsz - 1, rep, vkeep, prio);
         // meshes of the march hold no triangle twice: only triangles with a vertex something was welded into can have a twin
         // (`moved` is free until the tiny collapse: it carries the flags)
         uint8_t* involved = (coherent && !cx_debug_knob("CX_DEDUPE_ALL", 0)) ? moved : nullptr;
-        if (involved) CXP_HIP(ctx, hipMemsetAsync(involved, 0, nv, st));
-        hipLaunchKernelGGL(cxp_k_remap, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, rep, (const u64*)nullptr, involved, ever);
-        const u64 tsz = involved ? cxp_edge_table_size(nt) : cxp_table_size(nt);
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXP_EMPTY);
-        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
-        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
-        CXP_HIP(ctx, hipMemsetAsync(misc + 4, 0, 2 * sizeof(uint32_t), st));
-        hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cxp_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 4);
+        if (involved) CX_HIP(ctx, hipMemsetAsync(involved, 0, nv, st));
+        hipLaunchKernelGGL(cxp_k_remap, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, rep, (const u64*)nullptr, involved, ever);
+        const u64 tsz = involved ? cxp_edge_table_size(nt) : cx_table_size(nt);
+        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXD_EMPTY);
+        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
+        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
+        CX_HIP(ctx, hipMemsetAsync(misc + 4, 0, 2 * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cx_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 4);
         if (smooth > 0.0) {
             // ---- smooth_interpolations (tetrahedral.py:547-550), between the weld and the tiny collapse
-            const u64 esz = cxp_table_size((size_t)nt * 3);
+            const u64 esz = cx_table_size((size_t)nt * 3);
             if ((rc = S->tkeys.grow(ctx, esz * sizeof(u64)))) return rc;
             if ((rc = S->pts_out.grow(ctx, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
             if ((rc = S->flags.grow(ctx, (size_t)(nv + nt + 16) * sizeof(uint32_t)))) return rc;
             double* sum = S->pts_out.as<double>();
             uint32_t* cnt = S->flags.as<uint32_t>();
-            CXP_HIP(ctx, hipMemsetAsync(sum, 0, (size_t)nv * 3 * sizeof(double), st));
-            CXP_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)nv * sizeof(uint32_t), st));
-            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)esz, CXP_EMPTY);
+            CX_HIP(ctx, hipMemsetAsync(sum, 0, (size_t)nv * 3 * sizeof(double), st));
+            CX_HIP(ctx, hipMemsetAsync(cnt, 0, (size_t)nv * sizeof(uint32_t), st));
+            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)esz, CXD_EMPTY);
             if (cx_debug_knob("CX_SMOOTH_TWO_STEP", 0)) {
-                hipLaunchKernelGGL(cxp_k_unique_edges, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), esz - 1);
-                hipLaunchKernelGGL(cxp_k_smooth_accumulate, dim3(cxp_blocks(esz)), dim3(256), 0, st, S->tkeys.as<const u64>(), (size_t)esz, pts, sum, cnt);
+                hipLaunchKernelGGL(cxp_k_unique_edges, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), esz - 1);
+                hipLaunchKernelGGL(cxp_k_smooth_accumulate, dim3(cx_blocks(esz)), dim3(256), 0, st, S->tkeys.as<const u64>(), (size_t)esz, pts, sum, cnt);
             } else {
-                hipLaunchKernelGGL(cxp_k_smooth_edges, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), esz - 1, (const double*)pts, sum, cnt);
+                hipLaunchKernelGGL(cxp_k_smooth_edges, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), esz - 1, (const double*)pts, sum, cnt);
             }
-            hipLaunchKernelGGL(cxp_k_smooth_apply, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, sum, cnt, nv, smooth);
+            hipLaunchKernelGGL(cxp_k_smooth_apply, dim3(cx_blocks(nv)), dim3(256), 0, st, pts, sum, cnt, nv, smooth);
         }
         // ---- tiny collapse (tetrahedral.py:353-375), epsilon = 1e-4, scaled by 1/corner
         u64* parent = S->parent.as<u64>();
-        hipLaunchKernelGGL(cxp_k_iota64, dim3(cxp_blocks(nv)), dim3(256), 0, st, parent, nv);
-        CXP_HIP(ctx, hipMemsetAsync(moved, 0, nv, st));
-        hipLaunchKernelGGL(cxp_k_tiny, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, pts, 1.0 / corner[0], 1.0 / corner[1],
+        hipLaunchKernelGGL(cxp_k_iota64, dim3(cx_blocks(nv)), dim3(256), 0, st, parent, nv);
+        CX_HIP(ctx, hipMemsetAsync(moved, 0, nv, st));
+        hipLaunchKernelGGL(cxp_k_tiny, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, pts, 1.0 / corner[0], 1.0 / corner[1],
                            1.0 / corner[2], 1e-4, parent, prio, moved);
         // roots keep their own coordinates, so moving members in place is race free
-        hipLaunchKernelGGL(cxp_k_move, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, pts, parent, moved, nv);
-        hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cxp_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 5);
+        hipLaunchKernelGGL(cxp_k_move, dim3(cx_blocks(nv)), dim3(256), 0, st, pts, pts, parent, moved, nv);
+        hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cx_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 5);
         uint32_t h[2];
-        CXP_HIP(ctx, hipMemcpyAsync(h, misc + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CXP_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipMemcpyAsync(h, misc + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
         counts[2] = h[0]; counts[3] = h[1];
     }
     // (`moved` is free again after cxp_k_move)
@@ -1696,7 +1654,7 @@ static int cxp_run3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, co
 extern "C" int cx_postprocess3d_ex(cx_ctx* ctx, uint32_t flags, double smooth, int64_t* out_counts) {
     if (!ctx) return CX_ERR_INVALID;
     if (!ctx->extracted) { ctx->err = "cx_postprocess3d: no valid extraction"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S;
     int rc = cxp_state(ctx, &S);
     if (rc) return rc;
@@ -1713,14 +1671,14 @@ extern "C" int cx_postprocess3d_ex(cx_ctx* ctx, uint32_t flags, double smooth, i
     if (ctx->origin[0] < 0 || ctx->origin[1] < 0 || ctx->origin[2] < 0)
         for (int a = 0; a < 3; a++) org.o[a] = (double)ctx->origin[a];
     if (nv && nt) {
-        cxp_launch_vertices_f64(dim3(cxp_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
+        cxp_launch_vertices_f64(dim3(cx_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
                            P.div_plane, P.div_row, P.value, ctx->verts.get(), nv, S->pts.as<double>(), S->prio.as<uint32_t>(), org);
-        CXP_HIP(ctx, hipMemcpyAsync(S->tri.get(), ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        CX_HIP(ctx, hipMemcpyAsync(S->tri.get(), ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
         if (ctx->keep_valid) {   // cx_select_seeded3d: only the triangles (and vertices) of the selected components exist
-            CXP_HIP(ctx, hipMemcpyAsync(S->alive.get(), ctx->tri_keep, nt, hipMemcpyDeviceToDevice, st));
+            CX_HIP(ctx, hipMemcpyAsync(S->alive.get(), ctx->tri_keep, nt, hipMemcpyDeviceToDevice, st));
             vkeep = ctx->tri_keep + nt;
         } else {
-            CXP_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
+            CX_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
         }
     }
     // the reference's `corner` (voxels per axis); a sample array with a margin around the reference's grid
@@ -1752,7 +1710,7 @@ extern "C" int cx_postprocess3d_shard_begin(cx_ctx* ctx, uint32_t flags, int64_t
     if (own_lo < 0 || own_hi <= own_lo || own_hi > (int64_t)P.n0 - 1) { ctx->err = "cx_postprocess3d_shard_begin: own cell layers outside the local array"; return CX_ERR_INVALID; }
     if (ctx->keep_valid) { ctx->err = "cx_postprocess3d_shard_begin: not after a seeded selection"; return CX_ERR_STATE; }
     if (ctx->origin[0] < 0) { ctx->err = "cx_postprocess3d_shard_begin: the local array starts before the volume (cx_set_origin)"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S;
     int rc = cxp_state(ctx, &S);
     if (rc) return rc;
@@ -1764,10 +1722,10 @@ extern "C" int cx_postprocess3d_shard_begin(cx_ctx* ctx, uint32_t flags, int64_t
     // volume computes, so that the weld buckets truncate identically
     const cxp_origin3 org{{(double)ctx->origin[0], (double)ctx->origin[1], (double)ctx->origin[2]}};
     if (nv && nt) {
-        cxp_launch_vertices_f64(dim3(cxp_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
+        cxp_launch_vertices_f64(dim3(cx_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
                            P.div_plane, P.div_row, P.value, ctx->verts.get(), nv, S->pts.as<double>(), S->prio.as<uint32_t>(), org);
-        CXP_HIP(ctx, hipMemcpyAsync(S->tri.get(), ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        CXP_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
+        CX_HIP(ctx, hipMemcpyAsync(S->tri.get(), ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        CX_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
     }
     double corner[3] = {(double)(P.n0 - 1), (double)(P.n1 - 1), (double)(P.n2 - 1)};
     for (int a = 0; a < 3; a++)
@@ -1790,7 +1748,7 @@ extern "C" int cx_postprocess3d_shard_begin(cx_ctx* ctx, uint32_t flags, int64_t
 extern "C" int cx_postprocess3d_shard_boundary(cx_ctx* ctx, int which, uint64_t* hash, uint32_t* label) {
     if (!ctx || (which != 1 && which != 4)) return CX_ERR_INVALID;
     if (!ctx->post || !ctx->post->shard.open) { ctx->err = "cx_postprocess3d_shard_boundary: call cx_postprocess3d_shard_begin first"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     const size_t n1 = S->shard.n1, n4 = S->shard.n4, nb = n1 + n4;
     const size_t n = which == 1 ? n1 : n4;
@@ -1799,9 +1757,9 @@ extern "C" int cx_postprocess3d_shard_boundary(cx_ctx* ctx, int which, uint64_t*
     const u64* hash1 = S->bnd.as<const u64>();
     const cxp_cand* cand = (const cxp_cand*)(hash1 + nb);
     const uint32_t* label1 = (const uint32_t*)(cand + nb);
-    CXP_HIP(ctx, hipMemcpyAsync(hash, which == 1 ? hash1 : hash1 + n1, n * sizeof(u64), hipMemcpyDefault, ctx->stream));
-    CXP_HIP(ctx, hipMemcpyAsync(label, which == 1 ? label1 : label1 + n1, n * sizeof(uint32_t), hipMemcpyDefault, ctx->stream));
-    CXP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CX_HIP(ctx, hipMemcpyAsync(hash, which == 1 ? hash1 : hash1 + n1, n * sizeof(u64), hipMemcpyDefault, ctx->stream));
+    CX_HIP(ctx, hipMemcpyAsync(label, which == 1 ? label1 : label1 + n1, n * sizeof(uint32_t), hipMemcpyDefault, ctx->stream));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CX_OK;
 }
 
@@ -1813,15 +1771,15 @@ extern "C" int cx_postprocess3d_shard_candidates(cx_ctx* ctx, uint32_t* cand_lab
                                                  uint8_t* cand_negative, uint8_t* cand_has) {
     if (!ctx) return CX_ERR_INVALID;
     if (!ctx->post || !ctx->post->shard.open) { ctx->err = "cx_postprocess3d_shard_candidates: call cx_postprocess3d_shard_begin first"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     const size_t nb = (size_t)S->shard.n1 + S->shard.n4, nc = S->shard.ncand;
     if (!nc) return CX_OK;
     if (!cand_label || !cand_x || !cand_vertex_key || !cand_nx || !cand_negative || !cand_has) return CX_ERR_INVALID;
     const cxp_cand* cand = (const cxp_cand*)(S->bnd.as<const u64>() + nb);
     std::vector<cxp_cand> h(nc);
-    CXP_HIP(ctx, hipMemcpyAsync(h.data(), cand, nc * sizeof(cxp_cand), hipMemcpyDeviceToHost, ctx->stream));
-    CXP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CX_HIP(ctx, hipMemcpyAsync(h.data(), cand, nc * sizeof(cxp_cand), hipMemcpyDeviceToHost, ctx->stream));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < nc; i++) {
         cand_label[i] = h[i].label; cand_x[i] = h[i].x; cand_vertex_key[i] = h[i].vkey; cand_nx[i] = h[i].nx;
         cand_negative[i] = (uint8_t)h[i].sign; cand_has[i] = (uint8_t)h[i].has;
@@ -1837,7 +1795,7 @@ extern "C" int cx_postprocess3d_shard_finish(cx_ctx* ctx, const uint32_t* labels
     if (!ctx || n < 0 || (n && (!labels || !flips))) return CX_ERR_INVALID;
     if (!ctx->post || !ctx->post->shard.open) { ctx->err = "cx_postprocess3d_shard_finish: call cx_postprocess3d_shard_begin first"; return CX_ERR_STATE; }
     if (n > (int64_t)ctx->post->shard.nt2) { ctx->err = "cx_postprocess3d_shard_finish: more labels than triangles"; return CX_ERR_INVALID; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int rc = cxp_shard_finish(ctx, ctx->post, labels, flips, (uint32_t)n, counts);
     if (rc) return rc;
@@ -1852,7 +1810,7 @@ extern "C" int cx_postprocess3d_shard_finish(cx_ctx* ctx, const uint32_t* labels
 extern "C" int cx_level1_download_keys(cx_ctx* ctx, uint32_t* keys) {
     if (!ctx || !keys) return CX_ERR_INVALID;
     if (!ctx->post || !ctx->post_valid || !ctx->post->keys_valid) { ctx->err = "cx_level1_download_keys: run cx_postprocess3d first"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     if (!S->nv_out) return CX_OK;
     return cx_copy_to_host1(ctx, keys, S->keys_out.get(), (size_t)S->nv_out * sizeof(uint32_t));
@@ -1864,7 +1822,7 @@ extern "C" int cx_level1_download_keys(cx_ctx* ctx, uint32_t* keys) {
 extern "C" int cx_level0_points_f64(cx_ctx* ctx, double* points_xyz) {
     if (!ctx || !points_xyz) return CX_ERR_INVALID;
     if (!ctx->extracted) { ctx->err = "cx_level0_points_f64: no valid extraction"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S;
     int rc = cxp_state(ctx, &S);
     if (rc) return rc;
@@ -1874,7 +1832,7 @@ extern "C" int cx_level0_points_f64(cx_ctx* ctx, double* points_xyz) {
     if ((rc = S->prio.grow(ctx, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
     const cx_params& P = ctx->last;
     const cxp_origin3 org{{(double)ctx->origin[0], (double)ctx->origin[1], (double)ctx->origin[2]}};
-    cxp_launch_vertices_f64(dim3(cxp_blocks(nv)), ctx->stream, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
+    cxp_launch_vertices_f64(dim3(cx_blocks(nv)), ctx->stream, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
                        P.div_plane, P.div_row, P.value, ctx->verts.get(), nv, S->pts.as<double>(), S->prio.as<uint32_t>(), org);
     if ((rc = cx_copy_to_host1(ctx, points_xyz, S->pts.get(), (size_t)nv * 3 * sizeof(double)))) return rc;
     ctx->post_valid = false;   // the post-pass buffers no longer hold a Level-1 mesh
@@ -1891,7 +1849,7 @@ extern "C" int cx_postprocess3d_mesh(cx_ctx* ctx, const double* points_xyz, int6
         ctx->err = "cx_postprocess3d_mesh: corner >= 1 per axis and fewer than 2^31 vertices / triangles";
         return CX_ERR_INVALID;
     }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S;
     int rc = cxp_state(ctx, &S);
     if (rc) return rc;
@@ -1906,10 +1864,10 @@ extern "C" int cx_postprocess3d_mesh(cx_ctx* ctx, const double* points_xyz, int6
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if ((rc = cxp_reserve3d(ctx, S, nv, nt))) return rc;
     if (nv && nt) {
-        CXP_HIP(ctx, hipMemcpyAsync(S->pts.get(), points_xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-        CXP_HIP(ctx, hipMemcpyAsync(S->tri.get(), tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        CXP_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
-        hipLaunchKernelGGL(cxp_k_iota_prio, dim3(cxp_blocks(nv)), dim3(256), 0, st, S->prio.as<uint32_t>(), nv);
+        CX_HIP(ctx, hipMemcpyAsync(S->pts.get(), points_xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+        CX_HIP(ctx, hipMemcpyAsync(S->tri.get(), tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        CX_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
+        hipLaunchKernelGGL(cxp_k_iota_prio, dim3(cx_blocks(nv)), dim3(256), 0, st, S->prio.as<uint32_t>(), nv);
     }
     const double corner[3] = {(double)corner3[0], (double)corner3[1], (double)corner3[2]};
     if ((rc = cxp_run3d(ctx, S, nv, nt, corner, nullptr, !(flags & 1u), smooth, !(flags & 4u), counts, false, nullptr, (flags & 8u) != 0u))) return rc;
@@ -1921,7 +1879,7 @@ extern "C" int cx_postprocess3d_mesh(cx_ctx* ctx, const double* points_xyz, int6
 extern "C" int cx_level1_download(cx_ctx* ctx, double* points_xyz, int32_t* tris) {
     if (!ctx) return CX_ERR_INVALID;
     if (!ctx->post || !ctx->post_valid) { ctx->err = "cx_level1_download: run cx_postprocess3d first"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     void* d[2] = {(points_xyz && S->nv_out) ? (void*)points_xyz : nullptr, (tris && S->nt_out) ? (void*)tris : nullptr};
     const void* sp[2] = {S->pts_out.get(), S->tri_out.get()};
@@ -1935,8 +1893,8 @@ extern "C" int cx_level1_download(cx_ctx* ctx, double* points_xyz, int32_t* tris
 extern "C" int cx_level1_device_ptrs(cx_ctx* ctx, void** points_xyz, void** tris, int64_t* n_vertices, int64_t* n_triangles) {
     if (!ctx) return CX_ERR_INVALID;
     if (!ctx->post || !ctx->post_valid) { ctx->err = "cx_level1_device_ptrs: run cx_postprocess3d first"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
-    CXP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     cx_post_state* S = ctx->post;
     if (points_xyz) *points_xyz = S->nv_out ? S->pts_out.get() : nullptr;
     if (tris) *tris = S->nt_out ? S->tri_out.get() : nullptr;
@@ -1971,12 +1929,12 @@ int cx_level1_attr_view(cx_ctx* ctx, const char* who, cx_level1_view* out) {
         if (nt && (!S->orient_live || S->orient_nt != nt)) { ctx->err = std::string(who) + ": the orientation tables of the post-pass are gone (run cx_postprocess3d again)"; return CX_ERR_STATE; }
         int rc;
         if ((rc = S->vflip.grow(ctx, (size_t)nv + 16))) return rc;
-        CXP_HIP(ctx, hipMemsetAsync(S->vflip.get(), 0, nv, ctx->stream));
+        CX_HIP(ctx, hipMemsetAsync(S->vflip.get(), 0, nv, ctx->stream));
         if (nt) {
             const u64* parent = S->parent.as<const u64>();
             const u64* cflip = S->comp.as<const u64>() + nt;    // (cbest of cxp_clean_orient)
-            hipLaunchKernelGGL(cxp_k_vertex_flip, dim3(cxp_blocks(nt)), dim3(256), 0, ctx->stream, S->tri_out.as<const int32_t>(), nt, parent, cflip, S->vflip.as<uint8_t>());
-            CXP_HIP(ctx, hipGetLastError());
+            hipLaunchKernelGGL(cxp_k_vertex_flip, dim3(cx_blocks(nt)), dim3(256), 0, ctx->stream, S->tri_out.as<const int32_t>(), nt, parent, cflip, S->vflip.as<uint8_t>());
+            CX_HIP(ctx, hipGetLastError());
         }
         S->vflip_valid = true;
     }
@@ -2047,22 +2005,22 @@ int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new, const u
     if (S->carried && nv_new && S->nv_out) {       // the carried normals of a simplified mesh follow their vertices
         const int rcn = S->nrm[1 - S->nrm_cur].grow(ctx, ((size_t)nv_new + 1) * 3 * sizeof(double));
         if (rcn) return rcn;
-        hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cxp_blocks((size_t)S->nv_out)), dim3(256), 0, st, S->nrm[S->nrm_cur].as<const double>(), vuse, vnew,
+        hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cx_blocks((size_t)S->nv_out)), dim3(256), 0, st, S->nrm[S->nrm_cur].as<const double>(), vuse, vnew,
                            (uint32_t)S->nv_out, S->nrm[1 - S->nrm_cur].as<double>());
         S->nrm_cur = 1 - S->nrm_cur;
     }
     const size_t nt_old = (size_t)S->nt_out;
     const u64* parent_new = S->tkeys.as<const u64>();
     if (nv_new) {
-        CXP_HIP(ctx, hipMemcpyAsync(S->pts_out.get(), S->pts.get(), (size_t)nv_new * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        CXP_HIP(ctx, hipMemcpyAsync(S->keys_out.get(), S->keys_tmp.get(), (size_t)nv_new * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        CX_HIP(ctx, hipMemcpyAsync(S->pts_out.get(), S->pts.get(), (size_t)nv_new * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        CX_HIP(ctx, hipMemcpyAsync(S->keys_out.get(), S->keys_tmp.get(), (size_t)nv_new * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     }
     if (nt_new) {
-        CXP_HIP(ctx, hipMemcpyAsync(S->tri_out.get(), S->tri.get(), (size_t)nt_new * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        CXP_HIP(ctx, hipMemcpyAsync(S->parent.get(), parent_new, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
-        CXP_HIP(ctx, hipMemcpyAsync(S->comp.as<u64>() + nt_new, parent_new + nt_old + 1, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
+        CX_HIP(ctx, hipMemcpyAsync(S->tri_out.get(), S->tri.get(), (size_t)nt_new * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        CX_HIP(ctx, hipMemcpyAsync(S->parent.get(), parent_new, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
+        CX_HIP(ctx, hipMemcpyAsync(S->comp.as<u64>() + nt_new, parent_new + nt_old + 1, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
     }
-    CXP_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipStreamSynchronize(st));
     S->nv_out = nv_new; S->nt_out = nt_new;
     S->orient_nt = nt_new;
     S->vflip_valid = false;      // (written again from the tables on the next request)
@@ -2118,27 +2076,27 @@ int cx_level1_simplify_tail(cx_ctx* ctx, uint32_t nv_old, uint32_t ncl, uint32_t
     uint8_t* alive = S->alive.as<uint8_t>();
     const int cur = S->nrm_cur;
     if (nt && ncl) {
-        const u64 tsz = cxp_table_size(nt);
+        const u64 tsz = cx_table_size(nt);
         if ((rc = S->tkeys.grow(ctx, tsz * sizeof(u64)))) return rc;
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXP_EMPTY);
-        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)nullptr);
-        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)nullptr);
+        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXD_EMPTY);
+        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)nullptr);
+        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)nullptr);
     }
     // (the compaction writes the new id of every vertex in use: the others keep -1)
     if ((rc = S->scan.grow(ctx, ((size_t)ncl + 16) * sizeof(uint32_t)))) return rc;
-    if (ncl) CXP_HIP(ctx, hipMemsetAsync(S->scan.get(), 0xFF, (size_t)ncl * sizeof(uint32_t), st));
+    if (ncl) CX_HIP(ctx, hipMemsetAsync(S->scan.get(), 0xFF, (size_t)ncl * sizeof(uint32_t), st));
     if (normals && (rc = S->nrm[1 - cur].grow(ctx, ((size_t)ncl + 1) * 3 * sizeof(double)))) return rc;
     if ((rc = cxp_clean_orient(ctx, S, ncl, nt, do_clean, true, tprio3, counts, true))) { ctx->post_valid = false; return rc; }
     const uint32_t* vnew = S->scan.as<const uint32_t>();
-    if (nv_old) hipLaunchKernelGGL(cxp_k_simplify_map, dim3(cxp_blocks(nv_old)), dim3(256), 0, st, S->smap.as<int32_t>(), nv_old, ncl,
+    if (nv_old) hipLaunchKernelGGL(cxp_k_simplify_map, dim3(cx_blocks(nv_old)), dim3(256), 0, st, S->smap.as<int32_t>(), nv_old, ncl,
                                    (do_clean && nt) ? S->parent2.as<const u64>() : (const u64*)nullptr, vnew);
     if (normals && ncl && S->nv_out) {
-        hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cxp_blocks(ncl)), dim3(256), 0, st, S->nrm_tmp.as<const double>(), (const uint32_t*)nullptr, vnew, ncl,
+        hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cx_blocks(ncl)), dim3(256), 0, st, S->nrm_tmp.as<const double>(), (const uint32_t*)nullptr, vnew, ncl,
                            S->nrm[1 - cur].as<double>());
         S->nrm_cur = 1 - cur;
     }
-    CXP_HIP(ctx, hipGetLastError());
-    CXP_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipStreamSynchronize(st));
     S->simplified = true; S->carried = normals;
     S->smap_valid = true; S->smap_n = nv_old;
     return CX_OK;
@@ -2215,7 +2173,7 @@ __global__ void cxw_k_faces13(const int32_t* __restrict__ tri, uint32_t first, u
 extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const double* mins_delta, double* out_info) {
     if (!ctx || !path || (format != CX_FILE_PLY && format != CX_FILE_GLTF_BIN && format != CX_FILE_PLY_NORMALS && format != CX_FILE_GLTF_BIN_NORMALS)) return CX_ERR_INVALID;
     if (!ctx->post || !ctx->post_valid) { ctx->err = "cx_level1_write: run cx_postprocess3d first"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     // the formats with normals: the unit normals of cx_level1_normals (world normals when a spacing is handed over), laid out like the positions
     const bool with_normals = format == CX_FILE_PLY_NORMALS || format == CX_FILE_GLTF_BIN_NORMALS;
@@ -2274,15 +2232,15 @@ extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const 
                 if (more) {
                     uint8_t* dst = dstage + (size_t)half * stage_bytes;
                     if (section == 0 && with_normals && format == CX_FILE_PLY)
-                        hipLaunchKernelGGL(cxw_k_points_normals, dim3(cxp_blocks(n)), dim3(256), 0, st, S->pts_out.as<const double>(), nrm, first, n, m[0], m[1], m[2],
+                        hipLaunchKernelGGL(cxw_k_points_normals, dim3(cx_blocks(n)), dim3(256), 0, st, S->pts_out.as<const double>(), nrm, first, n, m[0], m[1], m[2],
                                            d[0], d[1], d[2], (double*)dst);
                     else if (section == 0)
-                        hipLaunchKernelGGL(cxw_k_points, dim3(cxp_blocks(n)), dim3(256), 0, st, S->pts_out.as<const double>(), first, n, m[0], m[1], m[2],
+                        hipLaunchKernelGGL(cxw_k_points, dim3(cx_blocks(n)), dim3(256), 0, st, S->pts_out.as<const double>(), first, n, m[0], m[1], m[2],
                                            d[0], d[1], d[2], format == CX_FILE_PLY ? 0 : 1, (void*)dst);
                     else if (section == 2)
-                        hipLaunchKernelGGL(cxw_k_normals_f32, dim3(cxp_blocks(n)), dim3(256), 0, st, nrm, first, n, (float*)dst);
+                        hipLaunchKernelGGL(cxw_k_normals_f32, dim3(cx_blocks(n)), dim3(256), 0, st, nrm, first, n, (float*)dst);
                     else if (format == CX_FILE_PLY)
-                        hipLaunchKernelGGL(cxw_k_faces13, dim3(cxp_blocks(n)), dim3(256), 0, st, S->tri_out.as<const int32_t>(), first, n, dst);
+                        hipLaunchKernelGGL(cxw_k_faces13, dim3(cx_blocks(n)), dim3(256), 0, st, S->tri_out.as<const int32_t>(), first, n, dst);
                     const void* src = (section == 1 && format != CX_FILE_PLY) ? (const void*)(S->tri_out.as<const int32_t>() + (size_t)first * 3) : (const void*)dst;
                     e = hipMemcpyAsync(hstage[half], src, (size_t)n * rec, hipMemcpyDeviceToHost, st);
                     if (e != hipSuccess) { ctx->err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); rc = CX_ERR_HIP; break; }
@@ -2329,7 +2287,7 @@ extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const 
 extern "C" int cx_surface_geometry(cx_ctx* ctx, double* points_xyz, int64_t* nv_io, int32_t* tris, int64_t* nt_io, int mode) {
     if (!ctx || !points_xyz || !tris || !nv_io || !nt_io || mode < 0 || mode > 2) return CX_ERR_INVALID;
     if (*nv_io < 0 || *nt_io < 0 || *nv_io > 0x7FFFFFF0LL || *nt_io > 0x7FFFFFF0LL) return CX_ERR_INVALID;
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S;
     int rc = cxp_state(ctx, &S);
     if (rc) return rc;
@@ -2344,21 +2302,21 @@ extern "C" int cx_surface_geometry(cx_ctx* ctx, double* points_xyz, int64_t* nv_
     if ((rc = S->parent2.grow(ctx, (size_t)(nv + 1) * sizeof(u64)))) return rc;
     int32_t* tri = S->tri.as<int32_t>();
     uint32_t* tprio3 = (uint32_t*)(tri + (size_t)(nt + 1) * 3);
-    if (nv) CXP_HIP(ctx, hipMemcpyAsync(S->pts.get(), points_xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    if (nt) CXP_HIP(ctx, hipMemcpyAsync(tri, tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    if (nv) hipLaunchKernelGGL(cxp_k_iota_prio, dim3(cxp_blocks(nv)), dim3(256), 0, st, S->prio.as<uint32_t>(), nv);
+    if (nv) CX_HIP(ctx, hipMemcpyAsync(S->pts.get(), points_xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (nt) CX_HIP(ctx, hipMemcpyAsync(tri, tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (nv) hipLaunchKernelGGL(cxp_k_iota_prio, dim3(cx_blocks(nv)), dim3(256), 0, st, S->prio.as<uint32_t>(), nv);
     if (nt) {
-        CXP_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
-        hipLaunchKernelGGL(cxp_k_tri_prio, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, S->prio.as<const uint32_t>(), nt, tprio3);
+        CX_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
+        hipLaunchKernelGGL(cxp_k_tri_prio, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, S->prio.as<const uint32_t>(), nt, tprio3);
         // a caller's triangle may repeat a vertex: such rows are not triangles (surface_geometry.py:63)
-        hipLaunchKernelGGL(cxp_k_remap, dim3(cxp_blocks(nt)), dim3(256), 0, st, tri, S->alive.as<uint8_t>(), nt, S->prio.as<const uint32_t>(),
+        hipLaunchKernelGGL(cxp_k_remap, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, S->alive.as<uint8_t>(), nt, S->prio.as<const uint32_t>(),
                            (const u64*)nullptr);
     }
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if ((rc = cxp_clean_orient(ctx, S, nv, nt, mode != 0, mode != 2, tprio3, counts, false))) return rc;   // caller's windings: arbitrary
-    if (S->nv_out) CXP_HIP(ctx, hipMemcpyAsync(points_xyz, S->pts_out.get(), (size_t)S->nv_out * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (S->nt_out) CXP_HIP(ctx, hipMemcpyAsync(tris, S->tri_out.get(), (size_t)S->nt_out * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    CXP_HIP(ctx, hipStreamSynchronize(st));
+    if (S->nv_out) CX_HIP(ctx, hipMemcpyAsync(points_xyz, S->pts_out.get(), (size_t)S->nv_out * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (S->nt_out) CX_HIP(ctx, hipMemcpyAsync(tris, S->tri_out.get(), (size_t)S->nt_out * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipStreamSynchronize(st));
     *nv_io = S->nv_out; *nt_io = S->nt_out;
     ctx->post_valid = false;
     return CX_OK;
@@ -2496,30 +2454,30 @@ static int cxp_post4_tets(cx_ctx* ctx, cx_post_state* S, const int32_t* tets, ui
     u64* parent = S->parent.as<u64>();
     S->orient_live = false; S->gen++;   // (the 3-D orientation's tables lived here: what cx_comp.hip cached of them is stale)
     uint32_t* misc = S->misc.as<uint32_t>();
-    hipLaunchKernelGGL(cxp_k_drop_instant, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1e-7);
+    hipLaunchKernelGGL(cxp_k_drop_instant, dim3(cx_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1e-7);
     // cx_select_seeded4d: only the tetrahedra of the selected components exist
-    if (keep) hipLaunchKernelGGL(cxp_k_and_mask, dim3(cxp_blocks(nt)), dim3(256), 0, st, alive, keep, nt);
-    CXP_HIP(ctx, hipMemsetAsync(misc + 4, 0, 2 * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cxp_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 4);
-    hipLaunchKernelGGL(cxp_k_iota64, dim3(cxp_blocks(nv)), dim3(256), 0, st, parent, nv);
-    CXP_HIP(ctx, hipMemsetAsync(moved, 0, nv, st));
-    hipLaunchKernelGGL(cxp_k_tiny4, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1.0 / corner[0], 1.0 / corner[1],
+    if (keep) hipLaunchKernelGGL(cxp_k_and_mask, dim3(cx_blocks(nt)), dim3(256), 0, st, alive, keep, nt);
+    CX_HIP(ctx, hipMemsetAsync(misc + 4, 0, 2 * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cx_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 4);
+    hipLaunchKernelGGL(cxp_k_iota64, dim3(cx_blocks(nv)), dim3(256), 0, st, parent, nv);
+    CX_HIP(ctx, hipMemsetAsync(moved, 0, nv, st));
+    hipLaunchKernelGGL(cxp_k_tiny4, dim3(cx_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1.0 / corner[0], 1.0 / corner[1],
                        1.0 / corner[2], 1.0 / corner[3], 1e-3, parent, prio, moved);
-    hipLaunchKernelGGL(cxp_k_move4, dim3(cxp_blocks(nv)), dim3(256), 0, st, pts, parent, moved, nv);
-    hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cxp_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 5);
+    hipLaunchKernelGGL(cxp_k_move4, dim3(cx_blocks(nv)), dim3(256), 0, st, pts, parent, moved, nv);
+    hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cx_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 5);
     uint32_t* tflag = S->flags.as<uint32_t>();
     uint32_t* tnew = S->scan.as<uint32_t>();
-    hipLaunchKernelGGL(cxp_k_alive_u32, dim3(cxp_blocks(nt)), dim3(256), 0, st, alive, nt, tflag);
+    hipLaunchKernelGGL(cxp_k_alive_u32, dim3(cx_blocks(nt)), dim3(256), 0, st, alive, nt, tflag);
     if ((rc = cxp_scan(ctx, S, tflag, tnew, nt, misc + 2))) return rc;
     uint32_t h[3];
-    CXP_HIP(ctx, hipMemcpyAsync(h, misc + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CXP_HIP(ctx, hipMemcpyAsync(h + 2, misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CXP_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipMemcpyAsync(h, misc + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipMemcpyAsync(h + 2, misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipStreamSynchronize(st));
     counts[2] = h[0]; counts[3] = h[1];
     const uint32_t nt2 = h[2];
     if ((rc = S->tri_out.grow(ctx, (size_t)(nt2 + 1) * 4 * sizeof(int32_t)))) return rc;
-    hipLaunchKernelGGL(cxp_k_compact_tets, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, alive, tnew, nt, S->tri_out.as<int32_t>());
-    CXP_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(cxp_k_compact_tets, dim3(cx_blocks(nt)), dim3(256), 0, st, tets, alive, tnew, nt, S->tri_out.as<int32_t>());
+    CX_HIP(ctx, hipGetLastError());
     *nt2_out = nt2;
     return CX_OK;
 }
@@ -2539,7 +2497,7 @@ extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double*
     cx_state4* G = ctx->s4;
     if (!G || !G->extracted) { ctx->err = "cx_postprocess4d: no valid 4-D extraction"; return CX_ERR_STATE; }
     if (G->slab && G->slab->open) { ctx->err = "cx_postprocess4d: a slab assembly is open (cx_slab4d_finish post-processes it)"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S;
     int rc = cxp_state(ctx, &S);
     if (rc) return rc;
@@ -2563,10 +2521,10 @@ extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double*
         }
         const double min_interval = corner[3] * (1.0 / (double)nbins);
         if (points_xyzt) {   // the caller's points (in the reference's lattice), one per Level-0 vertex
-            CXP_HIP(ctx, hipMemcpyAsync(pts, points_xyzt, (size_t)nv * 4 * sizeof(double), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(cxp_k_vertices4_given, dim3(cxp_blocks(nv)), dim3(256), 0, st, G->vkeys, nv, min_interval, pts, prio);
+            CX_HIP(ctx, hipMemcpyAsync(pts, points_xyzt, (size_t)nv * 4 * sizeof(double), hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(cxp_k_vertices4_given, dim3(cx_blocks(nv)), dim3(256), 0, st, G->vkeys, nv, min_interval, pts, prio);
         } else
-        hipLaunchKernelGGL(cxp_k_vertices4_f64, dim3(cxp_blocks(nv)), dim3(256), 0, st, G->grid, n1, n2, n3, cx_fdiv_make(n1 * n2 * n3),
+        hipLaunchKernelGGL(cxp_k_vertices4_f64, dim3(cx_blocks(nv)), dim3(256), 0, st, G->grid, n1, n2, n3, cx_fdiv_make(n1 * n2 * n3),
                            cx_fdiv_make(n2 * n3), cx_fdiv_make(n3), G->value, G->vkeys, nv, min_interval, pts, prio, org[0], org[1], org[2], org[3]);
         if ((rc = cxp_post4_tets(ctx, S, G->tets, nv, nt, corner, G->keep_valid ? (const uint8_t*)G->tet_keep : nullptr, counts, &nt2))) return rc;
     }
@@ -2592,7 +2550,7 @@ extern "C" int cx_slab4d_finish(cx_ctx* ctx, int32_t nbins, int64_t* out_counts)
     cx_state4* G = ctx->s4;
     cx_slab4* A = G ? G->slab : nullptr;
     if (!A || !A->open) { ctx->err = "cx_slab4d_finish: no assembly open (cx_slab4d_begin)"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
     if ((rc = cx_slab4_check(ctx, A))) return rc;
     cx_post_state* S;
@@ -2606,8 +2564,8 @@ extern "C" int cx_slab4d_finish(cx_ctx* ctx, int32_t nbins, int64_t* out_counts)
         double corner[4];
         for (int a = 0; a < 4; a++) corner[a] = (double)(A->whole[a] - 1);
         const double min_interval = corner[3] * (1.0 / (double)nbins);
-        CXP_HIP(ctx, hipMemcpyAsync(S->pts.get(), A->pts, (size_t)nv * 4 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(cxp_k_bin_times_iota, dim3(cxp_blocks(nv)), dim3(256), 0, st, S->pts.as<double>(), nv, min_interval, S->prio.as<uint32_t>());
+        CX_HIP(ctx, hipMemcpyAsync(S->pts.get(), A->pts, (size_t)nv * 4 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(cxp_k_bin_times_iota, dim3(cx_blocks(nv)), dim3(256), 0, st, S->pts.as<double>(), nv, min_interval, S->prio.as<uint32_t>());
         if ((rc = cxp_post4_tets(ctx, S, A->tets, nv, nt, corner, nullptr, counts, &nt2))) return rc;
     }
     S->nv_out = nv; S->nt_out = nt2;
@@ -2623,7 +2581,7 @@ extern "C" int cx_level1_4d_download(cx_ctx* ctx, double* points_xyzt, int32_t* 
     if (!ctx) return CX_ERR_INVALID;
     cx_state4* G = ctx->s4;
     if (!G || !G->post_valid || !ctx->post) { ctx->err = "cx_level1_4d_download: run cx_postprocess4d first"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     void* d[2] = {(points_xyzt && S->nv_out) ? (void*)points_xyzt : nullptr, (tets && S->nt_out) ? (void*)tets : nullptr};
     const void* sp[2] = {S->pts.get(), S->tri_out.get()};
@@ -2647,7 +2605,7 @@ extern "C" int cx_level1_4d_download(cx_ctx* ctx, double* points_xyzt, int32_t* 
 __global__ __launch_bounds__(256) void cxp_k_minmax_t(const double* pts, uint32_t nv, u64* mm) {
     u64 lo = ~0ULL, hi = 0ULL;
     for (uint32_t v = blockIdx.x * 256u + threadIdx.x; v < nv; v += gridDim.x * 256u) {
-        const u64 o = cxp_orderable(pts[(size_t)v * 4 + 3]);
+        const u64 o = cxd_orderable(pts[(size_t)v * 4 + 3]);
         lo = o < lo ? o : lo;
         hi = o > hi ? o : hi;
     }
@@ -2659,13 +2617,9 @@ __global__ __launch_bounds__(256) void cxp_k_minmax_t(const double* pts, uint32_
         hi = h2 > hi ? h2 : hi;
     }
     if ((threadIdx.x & 63u) == 0u) {
-        if (__hip_atomic_load(&mm[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > lo) atomicMin(&mm[0], lo);
-        cxp_max64(&mm[1], hi);
+        cxd_min64(&mm[0], lo);
+        cxd_max64(&mm[1], hi);
     }
-}
-__device__ __forceinline__ double cxp_from_orderable(u64 o) {
-    const u64 b = (o >> 63) ? (o & 0x7FFFFFFFFFFFFFFFULL) : ~o;
-    return __longlong_as_double((long long)b);
 }
 
 // slices of one tetrahedron: calls emit(p0, p1, p2) with vertex-index pairs packed (i << 32 | j), i before j in
@@ -2843,7 +2797,7 @@ __global__ void cxp_k_tets_orient(int32_t* tets, uint32_t nt, const uint32_t* ke
 __global__ void cxp_k_morph_count(const int32_t* tets, uint32_t nt, const double* pts, const uint32_t* prio, const u64* mm, uint32_t* counts) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt) return;
-    const double t_eps = 1e-7 * (cxp_from_orderable(mm[1]) - cxp_from_orderable(mm[0]));
+    const double t_eps = 1e-7 * (cxd_from_orderable(mm[1]) - cxd_from_orderable(mm[0]));
     counts[t] = cxp_morph_slices(tets, t, pts, prio, t_eps, [](u64, u64, u64) {});
 }
 // (Measured and dropped: the workgroup's triangles put together in LDS and written out as consecutive words -- 0.81 -> 0.83 ms: the kernel is
@@ -2852,7 +2806,7 @@ __global__ void cxp_k_morph_emit(const int32_t* tets, uint32_t nt, const double*
                                  const uint32_t* offsets, u64* pairs) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt) return;
-    const double t_eps = 1e-7 * (cxp_from_orderable(mm[1]) - cxp_from_orderable(mm[0]));
+    const double t_eps = 1e-7 * (cxd_from_orderable(mm[1]) - cxd_from_orderable(mm[0]));
     u64* out = pairs + (size_t)offsets[t] * 3;
     cxp_morph_slices(tets, t, pts, prio, t_eps, [&](u64 p0, u64 p1, u64 p2) { out[0] = p0; out[1] = p1; out[2] = p2; out += 3; });
 }
@@ -2866,23 +2820,23 @@ __global__ void cxp_k_morph_emit(const int32_t* tets, uint32_t nt, const double*
 #define CXP_SEG_SLOTS 2048u
 __global__ __launch_bounds__(256) void cxp_k_seg_insert(const u64* pairs, size_t n, u64* tkeys, u64 mask, u64 mult) {
     __shared__ u64 lset[CXP_SEG_SLOTS];
-    for (uint32_t x = threadIdx.x; x < CXP_SEG_SLOTS; x += 256u) lset[x] = CXP_EMPTY;
+    for (uint32_t x = threadIdx.x; x < CXP_SEG_SLOTS; x += 256u) lset[x] = CXD_EMPTY;
     __syncthreads();
     const size_t b0 = (size_t)blockIdx.x * CXP_SEG_KEYS;
     u64 key[4];
 #pragma unroll
     for (uint32_t k = 0; k < 4; k++) {
         const size_t i = b0 + k * 256u + threadIdx.x;
-        key[k] = (i < n) ? pairs[i] : CXP_EMPTY;
+        key[k] = (i < n) ? pairs[i] : CXD_EMPTY;
     }
 #pragma unroll
     for (uint32_t k = 0; k < 4; k++) {
-        if (key[k] == CXP_EMPTY) continue;
-        uint32_t ls = (uint32_t)cxp_mix(key[k]) & (CXP_SEG_SLOTS - 1u);
+        if (key[k] == CXD_EMPTY) continue;
+        uint32_t ls = (uint32_t)cxd_mix(key[k]) & (CXP_SEG_SLOTS - 1u);
         bool first = false;
         for (uint32_t probes = 0; probes < CXP_SEG_SLOTS; probes++) {      // (ends earlier: 1024 keys, 2048 slots)
-            const u64 cur = atomicCAS((unsigned long long*)&lset[ls], (unsigned long long)CXP_EMPTY, (unsigned long long)key[k]);
-            if (cur == CXP_EMPTY) { first = true; break; }
+            const u64 cur = atomicCAS((unsigned long long*)&lset[ls], (unsigned long long)CXD_EMPTY, (unsigned long long)key[k]);
+            if (cur == CXD_EMPTY) { first = true; break; }
             if (cur == key[k]) break;
             ls = (ls + 1u) & (CXP_SEG_SLOTS - 1u);
         }
@@ -2890,8 +2844,8 @@ __global__ __launch_bounds__(256) void cxp_k_seg_insert(const u64* pairs, size_t
         u64 slot = cxp_edge_slot((uint32_t)(key[k] >> 32), (uint32_t)key[k], mask, mult);
         for (;;) {
             u64 cur = __hip_atomic_load(&tkeys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (see cxp_k_edge_lists)
-            if (cur == CXP_EMPTY) cur = atomicCAS(&tkeys[slot], CXP_EMPTY, key[k]);
-            if (cur == CXP_EMPTY || cur == key[k]) break;
+            if (cur == CXD_EMPTY) cur = atomicCAS(&tkeys[slot], CXD_EMPTY, key[k]);
+            if (cur == CXD_EMPTY || cur == key[k]) break;
             slot = (slot + 1) & mask;
         }
     }
@@ -2908,11 +2862,11 @@ __device__ __forceinline__ uint32_t cxp_occ16(const u64* tkeys, size_t base, siz
 #pragma unroll
         for (uint32_t k = 0; k < 8; k++) {
             const ulonglong2 w = *reinterpret_cast<const ulonglong2*>(tkeys + base + 2u * k);
-            m |= (w.x != CXP_EMPTY ? 1u : 0u) << (2u * k);
-            m |= (w.y != CXP_EMPTY ? 2u : 0u) << (2u * k);
+            m |= (w.x != CXD_EMPTY ? 1u : 0u) << (2u * k);
+            m |= (w.y != CXD_EMPTY ? 2u : 0u) << (2u * k);
         }
     } else {
-        for (uint32_t k = 0; k < 16u && base + k < n; k++) m |= (tkeys[base + k] != CXP_EMPTY ? 1u : 0u) << k;
+        for (uint32_t k = 0; k < 16u && base + k < n; k++) m |= (tkeys[base + k] != CXD_EMPTY ? 1u : 0u) << k;
     }
     return m;
 }
@@ -2921,8 +2875,7 @@ __global__ __launch_bounds__(256) void cxp_k_occ_count(const u64* tkeys, size_t 
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
     uint32_t c = __popc(cxp_occ16(tkeys, (size_t)blockIdx.x * CXP_OCC_BLOCK + threadIdx.x * 16u, n));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o);
+    c = cxd_wave_add(c);
     if ((threadIdx.x & 63u) == 0 && c) atomicAdd(&s_n, c);
     __syncthreads();
     if (threadIdx.x == 0) count[blockIdx.x] = s_n;
@@ -2975,7 +2928,7 @@ __global__ void cxp_k_tri_segments(const u64* pairs, uint32_t nt, const u64* tke
                                    const u64* mm, int32_t* tris, double* ttime) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nt) return;
-    double lo = cxp_from_orderable(mm[0]), hi = cxp_from_orderable(mm[1]);
+    double lo = cxd_from_orderable(mm[0]), hi = cxd_from_orderable(mm[1]);
     // the three keys, their three probes side by side, the three ids, the six times -- and only then the stores (one edge after the
     // other with its store at the end of each round, every load of the next round waited for that store: they may alias for all the
     // compiler knows)
@@ -3013,7 +2966,7 @@ __global__ void cxp_k_tri_segments(const u64* pairs, uint32_t nt, const u64* tke
 __global__ __launch_bounds__(256) void cxp_k_edge_lists(const int32_t* tri, uint32_t nt, u64* ekeys, u64* eheads, u64 mask, u64 mult, uint32_t* next) {
     __shared__ u64 lkey[CXP_EL_SLOTS];
     __shared__ uint32_t lhead[CXP_EL_SLOTS];
-    for (uint32_t x = threadIdx.x; x < CXP_EL_SLOTS; x += 256u) { lkey[x] = CXP_EMPTY; lhead[x] = CXP_NONE; }
+    for (uint32_t x = threadIdx.x; x < CXP_EL_SLOTS; x += 256u) { lkey[x] = CXD_EMPTY; lhead[x] = CXD_NONE; }
     __syncthreads();
     const uint32_t b0 = blockIdx.x * CXP_EL;
     u64 key_[CXP_EL_PER][3];
@@ -3029,16 +2982,16 @@ __global__ __launch_bounds__(256) void cxp_k_edge_lists(const int32_t* tri, uint
             const uint32_t p = v[e], q = v[(e + 1) % 3];
             const u64 key = ((u64)min(p, q) << 32) | (u64)max(p, q);
             key_[i][e] = key;
-            uint32_t ls = (uint32_t)cxp_mix(key) & (CXP_EL_SLOTS - 1u);
+            uint32_t ls = (uint32_t)cxd_mix(key) & (CXP_EL_SLOTS - 1u);
             for (uint32_t probes = 0; probes < CXP_EL_SLOTS; probes++) {      // (ends earlier: 3 CXP_EL visits, 4 CXP_EL slots)
-                const u64 cur = atomicCAS((unsigned long long*)&lkey[ls], (unsigned long long)CXP_EMPTY, (unsigned long long)key);
-                if (cur == CXP_EMPTY || cur == key) break;
+                const u64 cur = atomicCAS((unsigned long long*)&lkey[ls], (unsigned long long)CXD_EMPTY, (unsigned long long)key);
+                if (cur == CXD_EMPTY || cur == key) break;
                 ls = (ls + 1u) & (CXP_EL_SLOTS - 1u);
             }
             slot_[i][e] = (uint16_t)ls;
             const uint32_t me = t * 3u + (uint32_t)e;
             const uint32_t prev = atomicExch(&lhead[ls], me);
-            if (prev == CXP_NONE) tails |= 1u << (3u * i + (uint32_t)e);
+            if (prev == CXD_NONE) tails |= 1u << (3u * i + (uint32_t)e);
             else next[me] = prev;
         }
     }
@@ -3055,12 +3008,12 @@ __global__ __launch_bounds__(256) void cxp_k_edge_lists(const int32_t* tri, uint
             for (;;) {
                 // device-scope read first: every visitor of an edge but the first finds the key there and needs no read-modify-write
                 u64 cur = __hip_atomic_load(&ekeys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == CXP_EMPTY) cur = atomicCAS(&ekeys[slot], CXP_EMPTY, key);
-                if (cur == CXP_EMPTY || cur == key) break;
+                if (cur == CXD_EMPTY) cur = atomicCAS(&ekeys[slot], CXD_EMPTY, key);
+                if (cur == CXD_EMPTY || cur == key) break;
                 slot = (slot + 1) & mask;
             }
             const u64 old = atomicExch(&eheads[slot], (u64)lhead[slot_[i][e]]);      // the block's chain in front of what was there
-            next[t * 3u + (uint32_t)e] = (old == CXP_EMPTY) ? CXP_NONE : (uint32_t)old;
+            next[t * 3u + (uint32_t)e] = (old == CXD_EMPTY) ? CXD_NONE : (uint32_t)old;
         }
     }
 }
@@ -3074,10 +3027,10 @@ __global__ void cxp_k_edge_union_compat(uint32_t nt, const uint32_t* next, const
     if (t >= nt) return;
     const double lo = ttime[(size_t)t * 2], hi = ttime[(size_t)t * 2 + 1];
     uint32_t it[3] = {next[t * 3u], next[t * 3u + 1u], next[t * 3u + 2u]};      // the three walks side by side
-    while (it[0] != CXP_NONE || it[1] != CXP_NONE || it[2] != CXP_NONE) {
+    while (it[0] != CXD_NONE || it[1] != CXD_NONE || it[2] != CXD_NONE) {
 #pragma unroll
         for (int e = 0; e < 3; e++) {
-            if (it[e] == CXP_NONE) continue;
+            if (it[e] == CXD_NONE) continue;
             const uint32_t o = it[e] / 3u;
             const double l2 = fmax(lo, ttime[(size_t)o * 2]), h2 = fmin(hi, ttime[(size_t)o * 2 + 1]);
             it[e] = next[it[e]];
@@ -3092,7 +3045,7 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
     if (!ctx) return CX_ERR_INVALID;
     cx_state4* G = ctx->s4;
     if (!G || !G->post_valid || !ctx->post) { ctx->err = "cx_morph_triangles: run cx_postprocess4d first"; return CX_ERR_STATE; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     hipStream_t st = ctx->stream;
     const uint32_t nv = (uint32_t)S->nv_out, nt = (uint32_t)S->nt_out;   // vertices / surviving tetrahedra
@@ -3107,8 +3060,8 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
     S->ms_out = 0; S->mt_out = 0; S->msorted = false;
     if (nv && nt) {
         const u64 init[2] = {~0ULL, 0ULL};
-        CXP_HIP(ctx, hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(cxp_k_minmax_t, dim3(std::min(cxp_blocks(nv), 2048u)), dim3(256), 0, st, pts, nv, mm);
+        CX_HIP(ctx, hipMemcpyAsync(mm, init, sizeof(init), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(cxp_k_minmax_t, dim3(std::min(cx_blocks(nv), 2048u)), dim3(256), 0, st, pts, nv, mm);
         if ((rc = S->flags.grow(ctx, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
         if ((rc = S->scan.grow(ctx, (size_t)(nt + 16) * sizeof(uint32_t)))) return rc;
         uint32_t* cnt = S->flags.as<uint32_t>();
@@ -3121,39 +3074,39 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
         // where samples EQUAL the isovalue and the determinant below vanishes); CX_TETS_ORIENT=1 (debug) recomputes it from the data
         // (not on a slab assembly: its tetrahedra come from several grids, G->grid is only the last slab's)
         if (!G->post_assembled && cx_debug_knob("CX_TETS_ORIENT", 0))
-            hipLaunchKernelGGL(cxp_k_tets_orient, dim3(cxp_blocks(nt)), dim3(256), 0, st, S->tri_out.as<int32_t>(), nt, prio, G4);
-        hipLaunchKernelGGL(cxp_k_morph_count, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, nt, pts, prio, mm, cnt);
+            hipLaunchKernelGGL(cxp_k_tets_orient, dim3(cx_blocks(nt)), dim3(256), 0, st, S->tri_out.as<int32_t>(), nt, prio, G4);
+        hipLaunchKernelGGL(cxp_k_morph_count, dim3(cx_blocks(nt)), dim3(256), 0, st, tets, nt, pts, prio, mm, cnt);
         if ((rc = cxp_scan(ctx, S, cnt, off, nt, misc + 1))) return rc;
         uint32_t ntri = 0;
         u64* h = h_mm;
-        CXP_HIP(ctx, hipMemcpyAsync(&ntri, misc + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CXP_HIP(ctx, hipMemcpyAsync(h, mm, sizeof(h_mm), hipMemcpyDeviceToHost, st));
-        CXP_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipMemcpyAsync(&ntri, misc + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipMemcpyAsync(h, mm, sizeof(h_mm), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
         S->me_off.clear();
         if (ntri) {
             if ((rc = S->mpairs.grow(ctx, (size_t)ntri * 3 * sizeof(u64)))) return rc;
             u64* pairs = S->mpairs.as<u64>();
-            hipLaunchKernelGGL(cxp_k_morph_emit, dim3(cxp_blocks(nt)), dim3(256), 0, st, tets, nt, pts, prio, mm, off, pairs);
+            hipLaunchKernelGGL(cxp_k_morph_emit, dim3(cx_blocks(nt)), dim3(256), 0, st, tets, nt, pts, prio, mm, off, pairs);
             // ---- segments
             const size_t np = (size_t)ntri * 3;
             // (n keys of which a third or less are distinct -- every segment shows up in several triangles: the edge-table rule, 5/4 of the
             // bound, keeps the load below 0.8 in the worst case and near 0.25 here with half the slots to clear, flag and scan)
             const u64 ssz = cxp_edge_table_size(np);
             if ((rc = S->tkeys.grow(ctx, ssz * sizeof(u64)))) return rc;
-            const uint32_t nob = cxp_blocks(ssz, CXP_OCC_BLOCK);
+            const uint32_t nob = cx_blocks(ssz, CXP_OCC_BLOCK);
             if ((rc = S->flags.grow(ctx, (size_t)(nob + 16) * sizeof(uint32_t)))) return rc;
             if ((rc = S->scan.grow(ctx, (size_t)(ssz + 16) * sizeof(uint32_t)))) return rc;
             u64* skeys = S->tkeys.as<u64>();
             uint32_t* boff = S->flags.as<uint32_t>();        // occupied slots per block of 4 096, then their exclusive scan
             uint32_t* sid = S->scan.as<uint32_t>();          // segment id per slot, written for occupied slots only
-            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, skeys, (size_t)ssz, CXP_EMPTY);
+            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, skeys, (size_t)ssz, CXD_EMPTY);
             const u64 smult = std::max<u64>(1, ssz / std::max<u64>(1, (u64)nv));
-            hipLaunchKernelGGL(cxp_k_seg_insert, dim3(cxp_blocks(np, CXP_SEG_KEYS)), dim3(256), 0, st, pairs, np, skeys, ssz - 1, smult);
+            hipLaunchKernelGGL(cxp_k_seg_insert, dim3(cx_blocks(np, CXP_SEG_KEYS)), dim3(256), 0, st, pairs, np, skeys, ssz - 1, smult);
             hipLaunchKernelGGL(cxp_k_occ_count, dim3(nob), dim3(256), 0, st, (const u64*)skeys, (size_t)ssz, boff);
             hipLaunchKernelGGL(cxp_k_scan_sums, dim3(1), dim3(1024), 0, st, boff, nob, misc + 2, (unsigned long long*)nullptr);
             uint32_t nseg = 0;
-            CXP_HIP(ctx, hipMemcpyAsync(&nseg, misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            CXP_HIP(ctx, hipStreamSynchronize(st));
+            CX_HIP(ctx, hipMemcpyAsync(&nseg, misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            CX_HIP(ctx, hipStreamSynchronize(st));
             if ((rc = S->msegs.grow(ctx, (size_t)(nseg + 1) * 2 * sizeof(int32_t)))) return rc;
             if ((rc = S->mmid.grow(ctx, (size_t)(nseg + 1) * 3 * sizeof(double)))) return rc;
             if ((rc = S->mtime.grow(ctx, ((size_t)(nseg + 1) * 2 + (size_t)(ntri + 1) * 2) * sizeof(double)))) return rc;
@@ -3165,8 +3118,8 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             int32_t* tris = S->mtris.as<int32_t>();
             hipLaunchKernelGGL(cxp_k_seg_write4, dim3(nob), dim3(256), 0, st, (const u64*)skeys, (size_t)ssz, (const uint32_t*)boff, (const uint32_t*)(misc + 2), nob,
                                pts, sid, segs, mid, stime);
-            hipLaunchKernelGGL(cxp_k_tri_segments, dim3(cxp_blocks(ntri)), dim3(256), 0, st, pairs, ntri, skeys, sid, ssz - 1, smult, stime, mm, tris, ttime);
-            CXP_HIP(ctx, hipStreamSynchronize(st));   // the segment table is reused below
+            hipLaunchKernelGGL(cxp_k_tri_segments, dim3(cx_blocks(ntri)), dim3(256), 0, st, pairs, ntri, skeys, sid, ssz - 1, smult, stime, mm, tris, ttime);
+            CX_HIP(ctx, hipStreamSynchronize(st));   // the segment table is reused below
             // ---- orientation on the segment midpoints, time-compatible neighbours only
             const u64 esz = cxp_edge_table_size((size_t)ntri * 3);
             const u64 emult4 = std::max<u64>(1, esz / std::max<u64>(1, (u64)nseg));
@@ -3184,33 +3137,33 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             u64* cbest = cmaxx + ntri;
             u64* cmaxv = cbest + ntri;
             uint32_t* cstart = (uint32_t*)(cmaxv + ntri);
-            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, ekeys, (size_t)esz, CXP_EMPTY);
-            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, eheads, (size_t)esz, CXP_EMPTY);
-            hipLaunchKernelGGL(cxp_k_iota64, dim3(cxp_blocks(ntri)), dim3(256), 0, st, parent, ntri);
-            hipLaunchKernelGGL(cxp_k_edge_lists, dim3(cxp_blocks(ntri, CXP_EL)), dim3(256), 0, st, tris, ntri, ekeys, eheads, esz - 1, emult4, next);
-            hipLaunchKernelGGL(cxp_k_edge_union_compat, dim3(cxp_blocks(ntri)), dim3(256), 0, st, ntri, (const uint32_t*)next, (const double*)ttime, parent);
+            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, ekeys, (size_t)esz, CXD_EMPTY);
+            hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, eheads, (size_t)esz, CXD_EMPTY);
+            hipLaunchKernelGGL(cxp_k_iota64, dim3(cx_blocks(ntri)), dim3(256), 0, st, parent, ntri);
+            hipLaunchKernelGGL(cxp_k_edge_lists, dim3(cx_blocks(ntri, CXP_EL)), dim3(256), 0, st, tris, ntri, ekeys, eheads, esz - 1, emult4, next);
+            hipLaunchKernelGGL(cxp_k_edge_union_compat, dim3(cx_blocks(ntri)), dim3(256), 0, st, ntri, (const uint32_t*)next, (const double*)ttime, parent);
             if ((rc = cxp_flatten(ctx, parent, ntri, misc))) return rc;
-            CXP_HIP(ctx, hipMemsetAsync(cmaxx, 0, (size_t)ntri * (3 * sizeof(u64) + sizeof(uint32_t)), st));
-            CXP_HIP(ctx, hipMemsetAsync(misc + 3, 0, sizeof(uint32_t), st));
+            CX_HIP(ctx, hipMemsetAsync(cmaxx, 0, (size_t)ntri * (3 * sizeof(u64) + sizeof(uint32_t)), st));
+            CX_HIP(ctx, hipMemsetAsync(misc + 3, 0, sizeof(uint32_t), st));
             const uint32_t* nokeys = nullptr;   // segment midpoints: the largest index breaks the tie
             const uint8_t* nocls = nullptr;
-            hipLaunchKernelGGL(cxp_k_comp_maxx, dim3(cxp_blocks(ntri)), dim3(256), 0, st, tris, ntri, mid, parent, cmaxx, nocls);
+            hipLaunchKernelGGL(cxp_k_comp_maxx, dim3(cx_blocks(ntri)), dim3(256), 0, st, tris, ntri, mid, parent, cmaxx, nocls);
             // the four kernels that pick a component's start triangle visit the list of triangles AT the component's largest x
             // (cxp_k_comp_list; the list sits where the edge lists' `next` words were: free by now)
             uint32_t* clist = S->mnext.as<uint32_t>();
             const uint32_t* cn = misc + 11;
-            const dim3 lgrid(std::min(cxp_blocks(ntri), 1024u));
-            CXP_HIP(ctx, hipMemsetAsync(misc + 11, 0, sizeof(uint32_t), st));
-            hipLaunchKernelGGL(cxp_k_comp_list, dim3(cxp_blocks(ntri)), dim3(256), 0, st, tris, ntri, mid, parent, cmaxx, nocls, clist, misc + 11);
+            const dim3 lgrid(std::min(cx_blocks(ntri), 1024u));
+            CX_HIP(ctx, hipMemsetAsync(misc + 11, 0, sizeof(uint32_t), st));
+            hipLaunchKernelGGL(cxp_k_comp_list, dim3(cx_blocks(ntri)), dim3(256), 0, st, tris, ntri, mid, parent, cmaxx, nocls, clist, misc + 11);
             hipLaunchKernelGGL(cxp_k_comp_maxv, lgrid, dim3(256), 0, st, tris, ntri, mid, parent, cmaxx, cmaxv, nokeys, nocls, (const uint32_t*)clist, cn);
             hipLaunchKernelGGL(cxp_k_comp_start, lgrid, dim3(256), 0, st, tris, ntri, mid, parent, cmaxv, cbest, nocls, (const uint32_t*)clist, cn);
             hipLaunchKernelGGL(cxp_k_comp_pick, lgrid, dim3(256), 0, st, tris, ntri, mid, parent, cmaxv, cbest, cstart, nocls, (const uint32_t*)clist, cn);
             hipLaunchKernelGGL(cxp_k_comp_decide, lgrid, dim3(256), 0, st, tris, ntri, mid, parent, cstart, cbest, (const uint32_t*)clist, cn);
-            hipLaunchKernelGGL(cxp_k_orient, dim3(cxp_blocks(ntri)), dim3(256), 0, st, tris, ntri, parent, cbest, misc + 3);
+            hipLaunchKernelGGL(cxp_k_orient, dim3(cx_blocks(ntri)), dim3(256), 0, st, tris, ntri, parent, cbest, misc + 3);
             uint32_t ncomp = 0;
-            CXP_HIP(ctx, hipMemcpyAsync(&ncomp, misc + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            CXP_HIP(ctx, hipStreamSynchronize(st));
-            CXP_HIP(ctx, hipGetLastError());
+            CX_HIP(ctx, hipMemcpyAsync(&ncomp, misc + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            CX_HIP(ctx, hipStreamSynchronize(st));
+            CX_HIP(ctx, hipGetLastError());
             S->ms_out = nseg; S->mt_out = ntri;
             counts[1] = nseg; counts[2] = ntri; counts[4] = ncomp;
         }
@@ -3230,7 +3183,7 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
 
 extern "C" int cx_morph_download(cx_ctx* ctx, double* points_xyzt, int32_t* segments, int32_t* triangles) {
     if (!ctx || !ctx->post) return CX_ERR_INVALID;
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     void* d[3] = {(points_xyzt && S->nv_out) ? (void*)points_xyzt : nullptr, (segments && S->ms_out) ? (void*)segments : nullptr,
                   (triangles && S->mt_out) ? (void*)triangles : nullptr};
@@ -3292,7 +3245,7 @@ __global__ __launch_bounds__(256) void cxp_k_sb_hist(const double* range, uint32
             if (h[w][x]) counts[(size_t)x * nunits + unit] = h[w][x];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) dur = fmax(dur, __shfl_xor(dur, o));
-    if (lane == 0 && dur > 0.0) cxp_max64(maxdur, cxp_orderable(dur));
+    if (lane == 0 && dur > 0.0) cxd_max64(maxdur, cxd_orderable(dur));
 }
 __global__ __launch_bounds__(256) void cxp_k_sb_rank(const uint8_t* bins, uint32_t n, const uint32_t* offs, uint32_t nunits, uint32_t* rank) {
     __shared__ uint32_t h[4][CXP_SB_BINS];
@@ -3386,7 +3339,7 @@ static int cxp_sb_ranks(cx_ctx* ctx, cx_post_state* S, const double* range, uint
                         uint32_t* starts_host, double* maxdur_host) {
     int rc;
     hipStream_t st = ctx->stream;
-    const uint32_t nunits = cxp_blocks(n, CXP_SB_UNIT);
+    const uint32_t nunits = cx_blocks(n, CXP_SB_UNIT);
     const size_t cells = (size_t)CXP_SB_BINS * nunits;
     if (cells >= 0xFFFFFFFFull) { ctx->err = "cx_morph_triangles: too many morph triangles for the start-time sort"; return CX_ERR_INVALID; }
     if ((rc = S->mnext.grow(ctx, (size_t)n + 64))) return rc;
@@ -3397,18 +3350,18 @@ static int cxp_sb_ranks(cx_ctx* ctx, cx_post_state* S, const double* range, uint
     uint32_t* offs = S->scan.as<uint32_t>();
     uint32_t* misc = S->misc.as<uint32_t>();
     u64* maxdur = (u64*)(misc + 20);
-    CXP_HIP(ctx, hipMemsetAsync(counts, 0, cells * sizeof(uint32_t), st));
-    CXP_HIP(ctx, hipMemsetAsync(maxdur, 0, sizeof(u64), st));
-    const uint32_t nblocks = cxp_blocks(nunits, 4);
+    CX_HIP(ctx, hipMemsetAsync(counts, 0, cells * sizeof(uint32_t), st));
+    CX_HIP(ctx, hipMemsetAsync(maxdur, 0, sizeof(u64), st));
+    const uint32_t nblocks = cx_blocks(nunits, 4);
     hipLaunchKernelGGL(cxp_k_sb_hist, dim3(nblocks), dim3(256), 0, st, range, n, lo, inv_width, bins, counts, nunits, maxdur);
     if ((rc = cxp_scan(ctx, S, counts, offs, (uint32_t)cells, misc + 22))) return rc;
     hipLaunchKernelGGL(cxp_k_sb_rank, dim3(nblocks), dim3(256), 0, st, (const uint8_t*)bins, n, (const uint32_t*)offs, nunits, rank);
     hipLaunchKernelGGL(cxp_k_sb_starts, dim3(1), dim3(512), 0, st, (const uint32_t*)offs, nunits, n, misc + 32);
     u64 md = 0;
-    CXP_HIP(ctx, hipMemcpyAsync(starts_host, misc + 32, (CXP_SB_BINS + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CXP_HIP(ctx, hipMemcpyAsync(&md, maxdur, sizeof(md), hipMemcpyDeviceToHost, st));
-    CXP_HIP(ctx, hipStreamSynchronize(st));
-    CXP_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipMemcpyAsync(starts_host, misc + 32, (CXP_SB_BINS + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipMemcpyAsync(&md, maxdur, sizeof(md), hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipGetLastError());
     *maxdur_host = md ? cxp_host_from_orderable(md) : 0.0;
     return CX_OK;
 }
@@ -3436,12 +3389,12 @@ static int cxp_morph_sort_by_start(cx_ctx* ctx, cx_post_state* S, uint32_t nseg,
     if ((rc = cxp_sb_ranks(ctx, S, stime, nseg, lo, inv_width, rank_s, S->mbin_s, &S->ms_maxdur))) return rc;
     if ((rc = cxp_sb_ranks(ctx, S, ttime, ntri, lo, inv_width, rank_t, S->mbin_t, &S->mt_maxdur))) return rc;
     // (the segment midpoints are scratch of the orientation, which is over: they stay behind)
-    hipLaunchKernelGGL(cxp_k_sb_move_segs, dim3(cxp_blocks(nseg)), dim3(256), 0, st, segs, stime, (const double*)nullptr, nseg, (const uint32_t*)rank_s,
+    hipLaunchKernelGGL(cxp_k_sb_move_segs, dim3(cx_blocks(nseg)), dim3(256), 0, st, segs, stime, (const double*)nullptr, nseg, (const uint32_t*)rank_s,
                        S->msegs2.as<int32_t>(), stime2, (double*)nullptr);
-    hipLaunchKernelGGL(cxp_k_sb_move_tris, dim3(cxp_blocks(ntri)), dim3(256), 0, st, tris, ttime, ntri, (const uint32_t*)rank_t, (const uint32_t*)rank_s,
+    hipLaunchKernelGGL(cxp_k_sb_move_tris, dim3(cx_blocks(ntri)), dim3(256), 0, st, tris, ttime, ntri, (const uint32_t*)rank_t, (const uint32_t*)rank_s,
                        S->mtris2.as<int32_t>(), ttime2);
-    CXP_HIP(ctx, hipStreamSynchronize(st));
-    CXP_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipGetLastError());
     std::swap(S->msegs, S->msegs2);
     std::swap(S->mtris, S->mtris2);
     std::swap(S->mtime, S->mtime2);
@@ -3677,7 +3630,7 @@ extern "C" int cx_morph_eval_many(cx_ctx* ctx, const double* times, int32_t n_ti
     if (!ctx || !ctx->post || n_times < 0 || (n_times && !times)) return CX_ERR_INVALID;
     if (n_times > CXP_ME_MAX_TIMES) { ctx->err = "cx_morph_eval_many: more than 65536 times in one call"; return CX_ERR_INVALID; }
     cx_post_state* S = ctx->post;
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint32_t ns = (uint32_t)S->ms_out, nt = (uint32_t)S->mt_out, nd = (uint32_t)n_times;
     S->me_off.assign((size_t)nd * 4, 0);
@@ -3756,9 +3709,9 @@ extern "C" int cx_morph_eval_many(cx_ctx* ctx, const double* times, int32_t n_ti
     // (the segment flags count as zeroed only while the last call ran to its end; they may have moved since: a larger call reserves anew)
     const bool clean = S->meflags_clean;
     S->meflags_clean = false;
-    if (!clean) CXP_HIP(ctx, hipMemsetAsync(sused, 0, S->meflags.bytes(), st));
-    CXP_HIP(ctx, hipMemcpyAsync(Dd, D, (size_t)(nd + 1) * sizeof(cxp_me_desc), hipMemcpyHostToDevice, st));
-    CXP_HIP(ctx, hipMemsetAsync(err, 0, sizeof(uint32_t), st));
+    if (!clean) CX_HIP(ctx, hipMemsetAsync(sused, 0, S->meflags.bytes(), st));
+    CX_HIP(ctx, hipMemcpyAsync(Dd, D, (size_t)(nd + 1) * sizeof(cxp_me_desc), hipMemcpyHostToDevice, st));
+    CX_HIP(ctx, hipMemsetAsync(err, 0, sizeof(uint32_t), st));
     hipLaunchKernelGGL(cxp_k_me_visible, dim3(ntb * 16u), dim3(256), 0, st, (const cxp_me_desc*)Dd, nd, ttime, tris, tflag, sused, err);
     hipLaunchKernelGGL(cxp_k_me_count16, dim3(nsb + ntb), dim3(256), 0, st, (const uint8_t*)sused, nsb, (const uint8_t*)tflag, scnt, tcnt);
     hipLaunchKernelGGL(cxp_k_me_offsets, dim3(2u * nd), dim3(256), 0, st, (const cxp_me_desc*)Dd, nd, scnt, tcnt, totals, bases);
@@ -3769,9 +3722,9 @@ extern "C" int cx_morph_eval_many(cx_ctx* ctx, const double* times, int32_t n_ti
                        (const uint32_t*)totals, (const u64*)bases, (const uint32_t*)snew, S->me_tri.as<int32_t>());
     std::vector<uint32_t> totv(pin ? 0 : (size_t)2 * nd + 1);
     uint32_t* tot = pin ? (uint32_t*)((char*)S->me_pinned + 36864) : totv.data();
-    CXP_HIP(ctx, hipMemcpyAsync(tot, totals, ((size_t)2 * nd + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CXP_HIP(ctx, hipStreamSynchronize(st));
-    CXP_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipMemcpyAsync(tot, totals, ((size_t)2 * nd + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipGetLastError());
     if (tot[2 * nd]) { ctx->err = "cx_morph_eval: a visible triangle uses a segment outside its time's window (internal error)"; return CX_ERR_HIP; }
     S->meflags_clean = true;
     int64_t p0 = 0, t0 = 0;
@@ -3786,7 +3739,7 @@ extern "C" int cx_morph_eval_many_download(cx_ctx* ctx, int32_t i, double* point
     if (!ctx || !ctx->post) return CX_ERR_INVALID;
     cx_post_state* S = ctx->post;
     if (i < 0 || (size_t)i * 4 >= S->me_off.size()) { ctx->err = "cx_morph_eval_many_download: no such surface in the last call"; return CX_ERR_INVALID; }
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     const int64_t* o = &S->me_off[(size_t)i * 4];
     void* d[2] = {(points_xyz && o[1]) ? (void*)points_xyz : nullptr, (triangles && o[3]) ? (void*)triangles : nullptr};
     const void* sp[2] = {o[1] ? (const void*)(S->me_pts.as<const double>() + (size_t)o[0] * 3) : nullptr,
@@ -3799,7 +3752,7 @@ extern "C" int cx_morph_eval_many_download(cx_ctx* ctx, int32_t i, double* point
 extern "C" int cx_morph_eval_many_download_all(cx_ctx* ctx, double* points_xyz, int32_t* triangles) {
     if (!ctx || !ctx->post) return CX_ERR_INVALID;
     cx_post_state* S = ctx->post;
-    CXP_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     int64_t np_ = 0, nt_ = 0;
     for (size_t i = 0; i + 3 < S->me_off.size(); i += 4) { np_ += S->me_off[i + 1]; nt_ += S->me_off[i + 3]; }
     void* d[2] = {(points_xyz && np_) ? (void*)points_xyz : nullptr, (triangles && nt_) ? (void*)triangles : nullptr};

@@ -17,15 +17,7 @@
 #include <string>
 
 #include "cx_ctx.h"
-
-#define CXS_HIP(ctx, call)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
+#include "cx_dev.h"
 
 struct cxs_grid {
     cx_grid_ref A;      // read by cxs_f / cxs_border_voxel only, through their sample type DT
@@ -39,24 +31,6 @@ __device__ __forceinline__ bool cxs_in_range(const cxs_grid& G, int i, int j, in
 
 __device__ __forceinline__ bool cxs_is_voxel_record(const uint4& c) {
     return ((c.y >> 16) & 0xFFu) != 0u;   // has triangles (only real voxels do)
-}
-__device__ __forceinline__ uint32_t cxs_find(uint32_t* parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == x) return x;
-        const uint32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g != p) atomicCAS(&parent[x], p, g);   // path halving
-        x = p;
-    }
-}
-__device__ __forceinline__ void cxs_union(uint32_t* parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = cxs_find(parent, a);
-        b = cxs_find(parent, b);
-        if (a == b) return;
-        const uint32_t win = min(a, b), lose = max(a, b);
-        if (atomicCAS(&parent[lose], lose, win) == lose) return;
-    }
 }
 
 // abits: one bit per lattice point, set for the surface voxels (cleared by the host before): the union kernel asks it first -- a
@@ -86,15 +60,6 @@ __device__ __forceinline__ uint32_t cxs_lookup(const uint4* cells, uint32_t ncel
 // device-scope union-find (cxs_k_union_far).  (One step, every pair through device-scope atomics: 4.2 ms of the 5.8 ms a selection on
 // the 512^3 bench field took -- the look-ups themselves, map and records, were not what it cost: a bitmap in front of them changed nothing.)
 #define CXS_UB 1024u
-__device__ __forceinline__ uint32_t cxs_lfind(uint32_t* lp, uint32_t x) {
-    for (;;) {
-        const uint32_t p = lp[x];
-        if (p == x) return x;
-        const uint32_t g = lp[p];
-        if (g != p) atomicCAS(&lp[x], p, g);   // path halving
-        x = p;
-    }
-}
 // calls f(neighbour's linear index) for the 13 "forward" neighbours of voxel (i, j, k) inside the range whose bit is set (the other
 // 13 are reached from the other side)
 template <typename F>
@@ -128,8 +93,8 @@ __global__ __launch_bounds__(256) void cxs_k_union_block(const uint4* cells, uin
             if (o >= CXS_UB) return;                              // another block's record: cxs_k_union_far
             uint32_t a = x, b = o;
             for (;;) {
-                a = cxs_lfind(lp, a);
-                b = cxs_lfind(lp, b);
+                a = cxd_uf_find_lds(lp, a);
+                b = cxd_uf_find_lds(lp, b);
                 if (a == b) break;
                 const uint32_t win = min(a, b), lose = max(a, b);
                 if (atomicCAS(&lp[lose], lose, win) == lose) break;
@@ -140,7 +105,7 @@ __global__ __launch_bounds__(256) void cxs_k_union_block(const uint4* cells, uin
     // the block's forest into the global parent words (nobody else touches them in this kernel); roots = smallest ids
     for (uint32_t x = threadIdx.x; x < CXS_UB; x += 256u) {
         if (b0 + x >= ncells) continue;
-        const uint32_t root = cxs_lfind(lp, x);
+        const uint32_t root = cxd_uf_find_lds(lp, x);
         if (root != x) parent[b0 + x] = b0 + root;
     }
 }
@@ -155,12 +120,12 @@ __global__ void cxs_k_union_far(const uint4* cells, uint32_t ncells, const uint3
     const uint32_t b0 = (r / CXS_UB) * CXS_UB;
     cxs_forward_neighbours(G, abits, i, j, k, [&](uint32_t nl) {
         const uint32_t o = vmap[nl];
-        if (o - b0 >= CXS_UB) cxs_union(parent, r, o);            // (pairs inside one block are united already)
+        if (o - b0 >= CXS_UB) cxd_uf_union(parent, r, o);            // (pairs inside one block are united already)
     });
 }
 __global__ void cxs_k_flatten(uint32_t* parent, uint32_t n) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n) parent[r] = cxs_find(parent, r);
+    if (r < n) parent[r] = cxd_uf_find(parent, r);
 }
 
 // ---- seeds: sequential, as the reference runs them (one thread; end point lists are short)
@@ -405,7 +370,7 @@ extern "C" int cx_select_seeded3d_ex(cx_ctx* ctx, const int32_t* endpoints_ijk, 
     if (!ctx || (n > 0 && !endpoints_ijk) || n < 0) return CX_ERR_INVALID;
     const int all_in_range = (flags & CX_SEED_ALL_IN_RANGE) ? 1 : 0;
     if (!ctx->extracted) { ctx->err = "cx_select_seeded3d: no valid extraction"; return CX_ERR_STATE; }
-    CXS_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     {
         const int rcr = cx_ensure_cell_records(ctx);   // the fused emit kernel leaves none behind
@@ -498,16 +463,16 @@ extern "C" int cx_select_seeded3d_ex(cx_ctx* ctx, const int32_t* endpoints_ijk, 
 extern "C" int cx_seeded_masks_download(cx_ctx* ctx, uint8_t* tri_keep, uint8_t* vert_keep) {
     if (!ctx) return CX_ERR_INVALID;
     if (!ctx->extracted) { ctx->err = "cx_seeded_masks_download: no valid extraction"; return CX_ERR_STATE; }
-    CXS_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nt = (size_t)ctx->counts.n_triangles, nv = (size_t)ctx->counts.n_vertices;
     if (!ctx->keep_valid) {
         if (tri_keep) memset(tri_keep, 1, nt);
         if (vert_keep) memset(vert_keep, 1, nv);
         return CX_OK;
     }
-    if (tri_keep && nt) CXS_HIP(ctx, hipMemcpyAsync(tri_keep, ctx->tri_keep, nt, hipMemcpyDeviceToHost, ctx->stream));
-    if (vert_keep && nv) CXS_HIP(ctx, hipMemcpyAsync(vert_keep, ctx->tri_keep + nt, nv, hipMemcpyDeviceToHost, ctx->stream));
-    CXS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (tri_keep && nt) CX_HIP(ctx, hipMemcpyAsync(tri_keep, ctx->tri_keep, nt, hipMemcpyDeviceToHost, ctx->stream));
+    if (vert_keep && nv) CX_HIP(ctx, hipMemcpyAsync(vert_keep, ctx->tri_keep + nt, nv, hipMemcpyDeviceToHost, ctx->stream));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CX_OK;
 }
 

@@ -19,20 +19,10 @@
 #include <cstring>
 #include <string>
 
+#include "cx_dev.h"
 #include "cx_state4.h"
 
 extern "C" int cx_select_seeded4d_ex(cx_ctx* ctx, const int32_t* endpoints_ijkl, int64_t n, const int32_t* range_lo_hi, uint32_t flags, int64_t* out_counts);
-
-#define CXS4_HIP(ctx, call)                                                                      \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
-#define CXS4_NONE 0xFFFFFFFFu
 
 struct cxs4_grid {
     const float* A;
@@ -67,24 +57,6 @@ __device__ __forceinline__ bool cxs4_is_voxel_record(const cxs4_grid& G, const u
     cxs4_unravel(G, c.x, p);
     return cxs4_voxel_inside(G, p);
 }
-__device__ __forceinline__ uint32_t cxs4_find(uint32_t* parent, uint32_t x) {
-    for (;;) {
-        const uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (p == x) return x;
-        const uint32_t g = __hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (g != p) atomicCAS(&parent[x], p, g);   // path halving
-        x = p;
-    }
-}
-__device__ __forceinline__ void cxs4_union(uint32_t* parent, uint32_t a, uint32_t b) {
-    for (;;) {
-        a = cxs4_find(parent, a);
-        b = cxs4_find(parent, b);
-        if (a == b) return;
-        const uint32_t win = min(a, b), lose = max(a, b);
-        if (atomicCAS(&parent[lose], lose, win) == lose) return;
-    }
-}
 
 __global__ void cxs4_k_map(const uint4* cells, uint32_t ncells, uint32_t* vmap, uint32_t* parent, cxs4_grid G) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -93,28 +65,19 @@ __global__ void cxs4_k_map(const uint4* cells, uint32_t ncells, uint32_t* vmap, 
     const uint4 c = cells[r];
     if (cxs4_is_voxel_record(G, c)) vmap[c.x] = r;
 }
-// record index of the hyper-voxel at p, or CXS4_NONE (the map is not cleared: entries validate themselves)
+// record index of the hyper-voxel at p, or CXD_NONE (the map is not cleared: entries validate themselves)
 __device__ __forceinline__ uint32_t cxs4_lookup(const cxs4_grid& G, const uint4* cells, uint32_t ncells, const uint32_t* vmap, const int p[4]) {
-    if (!cxs4_voxel_inside(G, p)) return CXS4_NONE;
+    if (!cxs4_voxel_inside(G, p)) return CXD_NONE;
     const uint32_t lin = cxs4_lin(G, p);
     const uint32_t r = vmap[lin];
-    if (r >= ncells) return CXS4_NONE;
+    if (r >= ncells) return CXD_NONE;
     const uint4 c = cells[r];
-    return (c.x == lin && cxs4_is_voxel_record(G, c)) ? r : CXS4_NONE;
+    return (c.x == lin && cxs4_is_voxel_record(G, c)) ? r : CXD_NONE;
 }
 // The unions in two steps, as cx_seed.hip does them for the 3-D march: a workgroup unites CXS4_UB consecutive records among themselves in
 // an LDS forest and writes it into the global parent words with plain stores (cxs4_k_union_block); only pairs that straddle two blocks
 // go through the device-scope union-find (cxs4_k_union_far).  (One step: 2.7 ms for the 0.87 M hyper-voxels of config 4.)
 #define CXS4_UB 1024u
-__device__ __forceinline__ uint32_t cxs4_lfind(uint32_t* lp, uint32_t x) {
-    for (;;) {
-        const uint32_t p = lp[x];
-        if (p == x) return x;
-        const uint32_t g = lp[p];
-        if (g != p) atomicCAS(&lp[x], p, g);   // path halving
-        x = p;
-    }
-}
 // f(record of the neighbour) for the 40 "forward" neighbours of hyper-voxel p that are surface hyper-voxels inside the range (the
 // other 40 are reached from the other side)
 template <typename F>
@@ -128,7 +91,7 @@ __device__ __forceinline__ void cxs4_forward_neighbours(const cxs4_grid& G, cons
         const int q[4] = {p[0] + o[0], p[1] + o[1], p[2] + o[2], p[3] + o[3]};
         if (!cxs4_in_range(G, q)) continue;   // in_range (tetrahedral.py:465-469)
         const uint32_t other = cxs4_lookup(G, cells, ncells, vmap, q);
-        if (other != CXS4_NONE) f(other);
+        if (other != CXD_NONE) f(other);
     }
 }
 __global__ __launch_bounds__(256) void cxs4_k_union_block(const uint4* cells, uint32_t ncells, const uint32_t* vmap, uint32_t* parent, cxs4_grid G) {
@@ -149,8 +112,8 @@ __global__ __launch_bounds__(256) void cxs4_k_union_block(const uint4* cells, ui
             if (o >= CXS4_UB) return;                             // another block's record: cxs4_k_union_far
             uint32_t a = x, b = o;
             for (;;) {
-                a = cxs4_lfind(lp, a);
-                b = cxs4_lfind(lp, b);
+                a = cxd_uf_find_lds(lp, a);
+                b = cxd_uf_find_lds(lp, b);
                 if (a == b) break;
                 const uint32_t win = min(a, b), lose = max(a, b);
                 if (atomicCAS(&lp[lose], lose, win) == lose) break;
@@ -160,7 +123,7 @@ __global__ __launch_bounds__(256) void cxs4_k_union_block(const uint4* cells, ui
     __syncthreads();
     for (uint32_t x = threadIdx.x; x < CXS4_UB; x += 256u) {
         if (b0 + x >= ncells) continue;
-        const uint32_t root = cxs4_lfind(lp, x);
+        const uint32_t root = cxd_uf_find_lds(lp, x);
         if (root != x) parent[b0 + x] = b0 + root;      // (nobody else touches these words in this kernel); roots = smallest ids
     }
 }
@@ -174,12 +137,12 @@ __global__ void cxs4_k_union_far(const uint4* cells, uint32_t ncells, const uint
     if (!cxs4_in_range(G, p)) return;
     const uint32_t b0 = (r / CXS4_UB) * CXS4_UB;
     cxs4_forward_neighbours(G, cells, ncells, vmap, p, [&](uint32_t other) {
-        if (other - b0 >= CXS4_UB) cxs4_union(parent, r, other);  // (pairs inside one block are united already)
+        if (other - b0 >= CXS4_UB) cxd_uf_union(parent, r, other);  // (pairs inside one block are united already)
     });
 }
 __global__ void cxs4_k_flatten(uint32_t* parent, uint32_t n) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < n) parent[r] = cxs4_find(parent, r);
+    if (r < n) parent[r] = cxd_uf_find(parent, r);
 }
 
 __device__ bool cxs4_border_voxel(const cxs4_grid& G, const int p[4]) {
@@ -263,11 +226,11 @@ __global__ void cxs4_k_seeds(cxs4_grid G, const int32_t* ep, uint32_t n, unsigne
 // many end point pairs (the exhaustive search on a large open surface, the coarse crossing search): one thread per pair, no
 // shared `visited` set -- each end point yields its own hyper-voxel or its first border neighbour (OFFSETS4D order).  (The
 // reference's shared set only changes which of several adjacent candidates gets picked when pairs collide.)
-// Slots 2s, 2s+1; CXS4_NONE = none.
+// Slots 2s, 2s+1; CXD_NONE = none.
 __global__ void cxs4_k_seeds_parallel(cxs4_grid G, const int32_t* ep, uint32_t n, uint32_t* seeds, uint32_t* out) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
-    seeds[2 * s] = seeds[2 * s + 1] = CXS4_NONE;
+    seeds[2 * s] = seeds[2 * s + 1] = CXD_NONE;
     if (s == 0) out[0] = 2u * n;   // slots to look at
     int lowp[4], highp[4];
     for (int a = 0; a < 4; a++) {
@@ -315,15 +278,15 @@ __global__ void cxs4_k_seeds_parallel(cxs4_grid G, const int32_t* ep, uint32_t n
 __global__ void cxs4_k_mark(const uint4* cells, uint32_t ncells, const uint32_t* vmap, const uint32_t* parent, const uint32_t* seeds,
                             const uint32_t* nseeds, uint8_t* flag, uint8_t* seedkeep, cxs4_grid G) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= nseeds[0] || seeds[s] == CXS4_NONE) return;
+    if (s >= nseeds[0] || seeds[s] == CXD_NONE) return;
     int p[4];
     cxs4_unravel(G, seeds[s], p);
     const uint32_t r = cxs4_lookup(G, cells, ncells, vmap, p);
     if (cxs4_in_range(G, p)) {
-        if (r != CXS4_NONE) flag[parent[r]] = 1;   // (a border voxel without a strict sign change has no tetrahedra and does not grow here)
+        if (r != CXD_NONE) flag[parent[r]] = 1;   // (a border voxel without a strict sign change has no tetrahedra and does not grow here)
         return;
     }
-    if (r != CXS4_NONE) seedkeep[r] = 1;
+    if (r != CXD_NONE) seedkeep[r] = 1;
     for (int code = 0; code < 81; code++) {
         if (code == 40) continue;
         int o[4], x = code;
@@ -334,7 +297,7 @@ __global__ void cxs4_k_mark(const uint4* cells, uint32_t ncells, const uint32_t*
         const int q[4] = {p[0] + o[0], p[1] + o[1], p[2] + o[2], p[3] + o[3]};
         if (!cxs4_in_range(G, q)) continue;
         const uint32_t r2 = cxs4_lookup(G, cells, ncells, vmap, q);
-        if (r2 != CXS4_NONE) flag[parent[r2]] = 1;
+        if (r2 != CXD_NONE) flag[parent[r2]] = 1;
     }
 }
 #define CXS4_PARTIAL0 32u       // out[32 + 32 p]: partial sums p = 0 .. CXS4_PARTIALS - 1 of the tetrahedra kept
@@ -359,7 +322,7 @@ __global__ void cxs4_k_keep(const uint4* cells, uint32_t ncells, const uint32_t*
             for (int a = 0; a < 4; a++) b[a] = min(b[a], p[a]);
         }
         const uint32_t r = cxs4_lookup(G, cells, ncells, vmap, b);
-        k = (r != CXS4_NONE && ((cxs4_in_range(G, b) && (all_in_range || flag[parent[r]] != 0)) || seedkeep[r] != 0)) ? 1 : 0;
+        k = (r != CXD_NONE && ((cxs4_in_range(G, b) && (all_in_range || flag[parent[r]] != 0)) || seedkeep[r] != 0)) ? 1 : 0;
         keep[t] = k;
     }
     const uint32_t nk = (uint32_t)__popcll(__ballot(k != 0));
@@ -390,7 +353,7 @@ extern "C" int cx_select_seeded4d_ex(cx_ctx* ctx, const int32_t* endpoints_ijkl,
     if (!ctx || (n > 0 && !endpoints_ijkl) || n < 0) return CX_ERR_INVALID;
     cx_state4* S4 = ctx->s4;
     if (!S4 || !S4->extracted) { ctx->err = "cx_select_seeded4d: no valid 4-D extraction"; return CX_ERR_STATE; }
-    CXS4_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint32_t ncells = (uint32_t)S4->counts.n_cells, nt = (uint32_t)S4->counts.n_triangles;
     cxs4_grid G;
@@ -471,9 +434,9 @@ extern "C" int cx_seeded4d_mask_download(cx_ctx* ctx, uint8_t* tet_keep) {
     if (!ctx || !tet_keep) return CX_ERR_INVALID;
     cx_state4* S4 = ctx->s4;
     if (!S4 || !S4->extracted || !S4->keep_valid) { ctx->err = "cx_seeded4d_mask_download: run cx_select_seeded4d first"; return CX_ERR_STATE; }
-    CXS4_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     if (S4->counts.n_triangles)
-        CXS4_HIP(ctx, hipMemcpyAsync(tet_keep, S4->tet_keep, (size_t)S4->counts.n_triangles, hipMemcpyDeviceToHost, ctx->stream));
-    CXS4_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        CX_HIP(ctx, hipMemcpyAsync(tet_keep, S4->tet_keep, (size_t)S4->counts.n_triangles, hipMemcpyDeviceToHost, ctx->stream));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CX_OK;
 }

@@ -20,19 +20,8 @@
 #include <string>
 
 #include "cx_ctx.h"
+#include "cx_dev.h"
 
-#define CXS_HIP(ctx, call)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
-typedef unsigned long long u64;
-#define CXS_EMPTY 0xFFFFFFFFFFFFFFFFULL
-#define CXS_NONE 0xFFFFFFFFu
 #define CXS_SMALL_GROUP 4
 // accumulator words per cluster: members, three 128-bit coordinate sums {low, high}, three 64-bit normal sums
 enum { CXS_W_N = 0, CXS_W_POS = 1, CXS_W_NRM = 7, CXS_WORDS = 10 };
@@ -43,7 +32,7 @@ extern "C" int cx_level1_normals(cx_ctx* ctx, const double* delta3, void** norma
 struct cx_simplify_state {
     cx_buf<u64> tkeys;                                   // cluster table: keys
     cx_buf<uint32_t> tfirst;                             // per slot: the smallest member
-    cx_buf<uint32_t> vslot;                              // per vertex: its slot (CXS_NONE: dropped)
+    cx_buf<uint32_t> vslot;                              // per vertex: its slot (CXD_NONE: dropped)
     cx_buf<uint32_t> flag;                               // first-member flags
     cx_buf<uint32_t> idx;                                // their exclusive scan
     cx_buf<uint32_t> sums;                               // block sums of the scan
@@ -69,47 +58,9 @@ struct cxs_params {
 };
 
 // ---- device helpers -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 cxs_mix(u64 x) {      // (cxp_mix of cx_post.hip)
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
-    x ^= x >> 33;
-    return x;
-}
 __device__ __forceinline__ u64 cxs_shfl64(u64 v, int lane) {
     const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane), hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane);
     return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ long long cxs_wave_add(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)(u64)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)((u64)v >> 32), o);
-        v += (long long)(((u64)hi << 32) | lo);
-    }
-    return v;
-}
-// signed 64-bit value into a 128-bit two's complement accumulator {low, high} (cxc_add128 of cx_comp.hip)
-__device__ __forceinline__ void cxs_add128(u64* w, long long v) {
-    if (v == 0) return;
-    const u64 lo = (u64)v;
-    u64 hi = v < 0 ? ~0ULL : 0ULL;
-    const u64 old = atomicAdd(&w[0], lo);
-    if (old + lo < old) hi += 1ULL;
-    if (hi) atomicAdd(&w[1], hi);
-}
-// the 128-bit sum as a double, rounded once: the top 64 bits with a sticky bit (cxc_to_double128 of cx_comp.hip, q = 0)
-__device__ __forceinline__ double cxs_to_double128(u64 lo, u64 hi) {
-    const bool neg = (hi >> 63) != 0ULL;
-    if (neg) { lo = ~lo + 1ULL; hi = ~hi + (lo == 0ULL ? 1ULL : 0ULL); }
-    double r;
-    if (hi == 0ULL) r = (double)lo;
-    else {
-        const int s = __clzll((long long)hi);
-        u64 top = s ? ((hi << s) | (lo >> (64 - s))) : hi;
-        const u64 rest = s ? (lo << s) : lo;
-        if (rest) top |= 1ULL;
-        r = ldexp((double)top, 64 - s);
-    }
-    return neg ? -r : r;
 }
 // cell of a coordinate: floor(p / c), an IEEE division; a point outside the grid box counts to the box's nearest cell
 __device__ __forceinline__ long long cxs_cell(double p, double c, long long kmin, long long kn) {
@@ -127,7 +78,7 @@ __device__ __forceinline__ u64 cxs_key(const double* __restrict__ p, int32_t lab
 
 // ---- clusters -----------------------------------------------------------------------------------------------------------------------
 __global__ void cxs_k_table_init(u64* __restrict__ tkeys, uint32_t* __restrict__ tfirst, size_t n) {
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) { tkeys[i] = CXS_EMPTY; tfirst[i] = CXS_NONE; }
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) { tkeys[i] = CXD_EMPTY; tfirst[i] = CXD_NONE; }
 }
 // One lane per vertex.  The lanes of a wave that share a key are served by ONE probe sequence and one minimum (the leader is the
 // group's lowest lane, so its vertex is the group's smallest).
@@ -138,7 +89,7 @@ __global__ __launch_bounds__(256) void cxs_k_cluster(const double* __restrict__ 
     const bool active = v < nv && label >= 0;
     const u64 key = active ? cxs_key(pts + (size_t)v * 3, label, P) : 0ULL;
     const uint32_t lane = threadIdx.x & 63u;
-    uint32_t myslot = CXS_NONE;
+    uint32_t myslot = CXD_NONE;
     uint64_t rem = __ballot(active);
     while (rem != 0ULL) {                                   // wave-uniform
         const int leader = __ffsll((long long)rem) - 1;
@@ -147,11 +98,11 @@ __global__ __launch_bounds__(256) void cxs_k_cluster(const double* __restrict__ 
         rem &= ~__ballot(mine);
         uint32_t slot = 0;
         if ((int)lane == leader) {
-            u64 s = cxs_mix(k) & mask;
+            u64 s = cxd_mix(k) & mask;
             for (;;) {
                 u64 cur = __hip_atomic_load(&tkeys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (cur == CXS_EMPTY) cur = atomicCAS(&tkeys[s], CXS_EMPTY, k);
-                if (cur == CXS_EMPTY || cur == k) break;
+                if (cur == CXD_EMPTY) cur = atomicCAS(&tkeys[s], CXD_EMPTY, k);
+                if (cur == CXD_EMPTY || cur == k) break;
                 s = (s + 1) & mask;
             }
             slot = (uint32_t)s;
@@ -166,14 +117,14 @@ __global__ void cxs_k_first_flags(const uint32_t* __restrict__ vslot, const uint
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= nv) return;
     const uint32_t s = vslot[v];
-    flag[v] = (s != CXS_NONE && tfirst[s] == v) ? 1u : 0u;
+    flag[v] = (s != CXD_NONE && tfirst[s] == v) ? 1u : 0u;
 }
 __global__ void cxs_k_map(const uint32_t* __restrict__ vslot, const uint32_t* __restrict__ tfirst, const uint32_t* __restrict__ idx, uint32_t nv,
                           int32_t* __restrict__ map, uint32_t* __restrict__ prio) {
     const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= nv) return;
     const uint32_t s = vslot[v];
-    if (s == CXS_NONE) { map[v] = -1; return; }
+    if (s == CXD_NONE) { map[v] = -1; return; }
     const uint32_t f = tfirst[s];
     const uint32_t id = idx[f];
     map[v] = (int32_t)id;
@@ -200,7 +151,7 @@ __global__ __launch_bounds__(256) void cxs_k_remap_tri(const int32_t* __restrict
 // ---- exact means --------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void cxs_lane_atomics(u64* w, u64 n, long long x0, long long x1, long long x2, bool nrm, long long n0, long long n1, long long n2) {
     atomicAdd(&w[CXS_W_N], n);
-    cxs_add128(&w[CXS_W_POS], x0); cxs_add128(&w[CXS_W_POS + 2], x1); cxs_add128(&w[CXS_W_POS + 4], x2);
+    cxd_add128(&w[CXS_W_POS], x0); cxd_add128(&w[CXS_W_POS + 2], x1); cxd_add128(&w[CXS_W_POS + 4], x2);
     if (nrm) {
         if (n0) atomicAdd(&w[CXS_W_NRM], (u64)n0);
         if (n1) atomicAdd(&w[CXS_W_NRM + 1], (u64)n1);
@@ -250,9 +201,9 @@ __global__ __launch_bounds__(256) void cxs_k_accumulate(const double* __restrict
             if (mine) cxs_lane_atomics(acc + (size_t)k * CXS_WORDS, 1ULL, X[0], X[1], X[2], nrm != nullptr, N[0], N[1], N[2]);
             continue;
         }
-        const long long s0 = cxs_wave_add(mine ? X[0] : 0LL), s1 = cxs_wave_add(mine ? X[1] : 0LL), s2 = cxs_wave_add(mine ? X[2] : 0LL);
+        const long long s0 = cxd_wave_add(mine ? X[0] : 0LL), s1 = cxd_wave_add(mine ? X[1] : 0LL), s2 = cxd_wave_add(mine ? X[2] : 0LL);
         long long m0 = 0, m1 = 0, m2 = 0;
-        if (nrm) { m0 = cxs_wave_add(mine ? N[0] : 0LL); m1 = cxs_wave_add(mine ? N[1] : 0LL); m2 = cxs_wave_add(mine ? N[2] : 0LL); }   // (nrm: uniform)
+        if (nrm) { m0 = cxd_wave_add(mine ? N[0] : 0LL); m1 = cxd_wave_add(mine ? N[1] : 0LL); m2 = cxd_wave_add(mine ? N[2] : 0LL); }   // (nrm: uniform)
         if ((int)lane == leader) cxs_lane_atomics(acc + (size_t)k * CXS_WORDS, (u64)__popcll(grp), s0, s1, s2, nrm != nullptr, m0, m1, m2);
     }
 #endif
@@ -266,7 +217,7 @@ __global__ void cxs_k_finish(const u64* __restrict__ acc, uint32_t ncl, cxs_para
     const double n = (double)w[CXS_W_N];
     const double inv = ldexp(1.0, -P.q);
 #pragma unroll
-    for (int a = 0; a < 3; a++) pts2[(size_t)c * 3 + a] = (cxs_to_double128(w[CXS_W_POS + 2 * a], w[CXS_W_POS + 2 * a + 1]) / n) * inv;
+    for (int a = 0; a < 3; a++) pts2[(size_t)c * 3 + a] = (cxd_to_double128(w[CXS_W_POS + 2 * a], w[CXS_W_POS + 2 * a + 1], 0) / n) * inv;
     if (nrm2) {
         const double x = (double)(long long)w[CXS_W_NRM], y = (double)(long long)w[CXS_W_NRM + 1], z = (double)(long long)w[CXS_W_NRM + 2];
         const double len = sqrt(x * x + y * y + z * z);
@@ -277,12 +228,6 @@ __global__ void cxs_k_finish(const u64* __restrict__ acc, uint32_t ncl, cxs_para
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static inline dim3 cxs_grid(size_t n) { return dim3((unsigned)((n + 255) / 256 ? (n + 255) / 256 : 1)); }
-static inline u64 cxs_table_size(size_t n) {      // (cxp_table_size of cx_post.hip)
-    u64 s = 1024;
-    while (s < 2 * (u64)n + 16) s <<= 1;
-    return s;
-}
 // cells of the grid box for `cell3`; false when the product reaches 2^31
 static bool cxs_cells(const double corner[3], const double cell3[3], long long kmin[3], long long kn[3]) {
     double prod = 1.0;
@@ -299,7 +244,7 @@ static bool cxs_cells(const double corner[3], const double cell3[3], long long k
 extern "C" int cx_level1_simplify(cx_ctx* ctx, const double* cell3, uint32_t flags, int64_t* out_counts, double* q_out) {
     if (!ctx) return CX_ERR_INVALID;
     cx_level1_comp_view V;
-    CXS_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     int rc = cx_level1_comp_view_get(ctx, "cx_level1_simplify", &V);
     if (rc) return rc;
     if (!cell3 || (flags & ~15u)) { ctx->err = "cx_level1_simplify: three cell sizes and flags of CX_SIMPLIFY_* are needed"; return CX_ERR_INVALID; }
@@ -359,7 +304,7 @@ extern "C" int cx_level1_simplify(cx_ctx* ctx, const double* cell3, uint32_t fla
     void *tl = nullptr, *vl = nullptr;
     if ((rc = cx_level1_component_labels(ctx, &tl, &vl))) return rc;
     if ((rc = cx_level1_simplify_bufs(ctx, want_normals, count_only, &B))) return rc;
-    const u64 tsz = cxs_table_size(nv);
+    const u64 tsz = cx_table_size(nv);
     if ((rc = Z->misc.grow(ctx, 16))) return rc;
     if ((rc = Z->tkeys.grow(ctx, (size_t)tsz))) return rc;
     if ((rc = Z->tfirst.grow(ctx, (size_t)tsz))) return rc;
@@ -367,22 +312,22 @@ extern "C" int cx_level1_simplify(cx_ctx* ctx, const double* cell3, uint32_t fla
     if ((rc = Z->flag.grow(ctx, (size_t)nv + 16))) return rc;
     if ((rc = Z->idx.grow(ctx, (size_t)nv + 16))) return rc;
     if ((rc = Z->sums.grow(ctx, (size_t)nv / 1024 + 16))) return rc;
-    CXS_HIP(ctx, hipMemsetAsync(Z->misc, 0, 16 * sizeof(uint32_t), st));
+    CX_HIP(ctx, hipMemsetAsync(Z->misc, 0, 16 * sizeof(uint32_t), st));
     uint32_t ncl = 0, n3 = 0, nclamp = 0;
     if (nv) {
         hipLaunchKernelGGL(cxs_k_table_init, dim3(2048), dim3(256), 0, st, Z->tkeys, Z->tfirst, (size_t)tsz);
-        hipLaunchKernelGGL(cxs_k_cluster, cxs_grid(nv), dim3(256), 0, st, V.pts, (const int32_t*)vl, nv, P, Z->tkeys, Z->tfirst, tsz - 1, Z->vslot);
-        hipLaunchKernelGGL(cxs_k_first_flags, cxs_grid(nv), dim3(256), 0, st, (const uint32_t*)Z->vslot, (const uint32_t*)Z->tfirst, nv, Z->flag);
+        hipLaunchKernelGGL(cxs_k_cluster, cx_grid1(nv), dim3(256), 0, st, V.pts, (const int32_t*)vl, nv, P, Z->tkeys, Z->tfirst, tsz - 1, Z->vslot);
+        hipLaunchKernelGGL(cxs_k_first_flags, cx_grid1(nv), dim3(256), 0, st, (const uint32_t*)Z->vslot, (const uint32_t*)Z->tfirst, nv, Z->flag);
         if ((rc = cx_scan_u32(ctx, Z->flag, Z->idx, nv, Z->sums, Z->misc))) return rc;
-        hipLaunchKernelGGL(cxs_k_map, cxs_grid(nv), dim3(256), 0, st, (const uint32_t*)Z->vslot, (const uint32_t*)Z->tfirst, (const uint32_t*)Z->idx, nv, B.map, B.prio);
-        if (nt) hipLaunchKernelGGL(cxs_k_remap_tri, cxs_grid(nt), dim3(256), 0, st, V.tri, (const int32_t*)B.map, nt, nv, B.tri, B.tprio3, B.alive, Z->misc + 1);
+        hipLaunchKernelGGL(cxs_k_map, cx_grid1(nv), dim3(256), 0, st, (const uint32_t*)Z->vslot, (const uint32_t*)Z->tfirst, (const uint32_t*)Z->idx, nv, B.map, B.prio);
+        if (nt) hipLaunchKernelGGL(cxs_k_remap_tri, cx_grid1(nt), dim3(256), 0, st, V.tri, (const int32_t*)B.map, nt, nv, B.tri, B.tprio3, B.alive, Z->misc + 1);
         uint32_t h[2] = {0, 0};
-        CXS_HIP(ctx, hipMemcpyAsync(h, Z->misc, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CXS_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipMemcpyAsync(h, Z->misc, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
         ncl = h[0]; n3 = h[1];
         if (ncl > nv || n3 > nt) { ctx->err = "cx_level1_simplify: the scans do not add up"; return CX_ERR_HIP; }
     }
-    CXS_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipGetLastError());
     if (q_out) *q_out = (double)P.q;
     if (count_only) {
         if (out_counts) { out_counts[6] = ncl; out_counts[7] = n3; }
@@ -390,12 +335,12 @@ extern "C" int cx_level1_simplify(cx_ctx* ctx, const double* cell3, uint32_t fla
     }
     if (ncl) {
         if ((rc = Z->acc.grow(ctx, (size_t)ncl * CXS_WORDS + 16))) return rc;
-        CXS_HIP(ctx, hipMemsetAsync(Z->acc, 0, (size_t)ncl * CXS_WORDS * sizeof(u64), st));
-        hipLaunchKernelGGL(cxs_k_accumulate, cxs_grid(nv), dim3(256), 0, st, V.pts, want_normals ? nsrc : (const double*)nullptr, (const int32_t*)B.map, nv, P, Z->acc,
+        CX_HIP(ctx, hipMemsetAsync(Z->acc, 0, (size_t)ncl * CXS_WORDS * sizeof(u64), st));
+        hipLaunchKernelGGL(cxs_k_accumulate, cx_grid1(nv), dim3(256), 0, st, V.pts, want_normals ? nsrc : (const double*)nullptr, (const int32_t*)B.map, nv, P, Z->acc,
                            Z->misc + 2);
-        hipLaunchKernelGGL(cxs_k_finish, cxs_grid(ncl), dim3(256), 0, st, (const u64*)Z->acc, ncl, P, B.pts, want_normals ? B.nrm_new : (double*)nullptr);
-        CXS_HIP(ctx, hipMemcpyAsync(&nclamp, Z->misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CXS_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(cxs_k_finish, cx_grid1(ncl), dim3(256), 0, st, (const u64*)Z->acc, ncl, P, B.pts, want_normals ? B.nrm_new : (double*)nullptr);
+        CX_HIP(ctx, hipMemcpyAsync(&nclamp, Z->misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipGetLastError());
     }
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if ((rc = cx_level1_simplify_tail(ctx, nv, ncl, nt, !(flags & 1u), want_normals, counts))) return rc;      // (synchronises the stream)
@@ -421,6 +366,6 @@ extern "C" int cx_level1_simplify_map_download(cx_ctx* ctx, int32_t* new_index_o
     const int rc = cx_level1_simplify_map_get(ctx, &map, &n);
     if (rc || !n) return rc;
     if (!new_index_of_old_vertex) return CX_ERR_INVALID;
-    CXS_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     return cx_copy_to_host1(ctx, new_index_of_old_vertex, map, (size_t)n * sizeof(int32_t));
 }

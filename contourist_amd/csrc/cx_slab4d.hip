@@ -22,15 +22,6 @@
 
 #include "cx_state4.h"
 
-#define CXS_HIP(ctx, call)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
 #define CXS_BINS 256u
 #define CXS_UNIT 1024u        // pairs per wave and pass
 
@@ -40,7 +31,6 @@ void cx_slab4_free(cx_slab4*& A) {
     A = nullptr;
 }
 
-static inline uint32_t cxs_blocks(size_t n, uint32_t b = 256) { return (uint32_t)((n + b - 1) / b); }
 
 // ---- kernels ---------------------------------------------------------------------------------------
 // (edge id, source) pairs: the slab's own vertices (source = vertex index), then the previous slab's halo vertices (source = nv + h)
@@ -206,7 +196,7 @@ extern "C" int cx_slab4d_begin(cx_ctx* ctx, const int64_t* whole_shape) {
         ctx->err = "cx_slab4d_begin: a plane of more than 2^27 samples leaves no room for two planes per slab in one extraction";
         return CX_ERR_UNSUPPORTED;
     }
-    CXS_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->s4) ctx->s4 = new (std::nothrow) cx_state4();
     if (!ctx->s4) return CX_ERR_NOMEM;
     cx_state4* G = ctx->s4;
@@ -246,7 +236,7 @@ extern "C" int cx_slab4d_append(cx_ctx* ctx, int64_t i0, int64_t owned_planes, i
         return CX_ERR_INVALID;
     }
     if (A->nslabs && !(G->value == A->value)) { ctx->err = "cx_slab4d_append: every slab is marched at the same isovalue"; return CX_ERR_INVALID; }
-    CXS_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     const uint32_t nvl = (uint32_t)G->counts.n_vertices, ntl = (uint32_t)G->counts.n_triangles, np = A->npend;
     const uint64_t m64 = (uint64_t)nvl + np;
     if ((uint64_t)A->nv + m64 >= (1ULL << 31) || (uint64_t)A->nt + ntl >= (1ULL << 31)) {
@@ -256,7 +246,7 @@ extern "C" int cx_slab4d_append(cx_ctx* ctx, int64_t i0, int64_t owned_planes, i
     const uint32_t m = (uint32_t)m64;
     const uint32_t n1 = (uint32_t)G->n[1], n2 = (uint32_t)G->n[2], n3 = (uint32_t)G->n[3];
     const uint64_t plane = (uint64_t)n1 * n2 * n3;
-    const uint32_t nunits = cxs_blocks(m, CXS_UNIT);
+    const uint32_t nunits = cx_blocks(m, CXS_UNIT);
     const size_t cells = (size_t)CXS_BINS * nunits;
     int rc;
     // every reserve first (the assembly keeps its contents), pointers after
@@ -278,24 +268,24 @@ extern "C" int cx_slab4d_append(cx_ctx* ctx, int64_t i0, int64_t owned_planes, i
     if ((rc = A->cnt.grow(ctx, (size_t)16))) return rc;
     hipStream_t st = ctx->stream;
     uint32_t h[2] = {0, 0};
-    CXS_HIP(ctx, hipMemsetAsync(A->cnt, 0, 16 * sizeof(uint32_t), st));
+    CX_HIP(ctx, hipMemsetAsync(A->cnt, 0, 16 * sizeof(uint32_t), st));
     if (m) {
         uint32_t *k = A->ka, *v = A->va, *k2 = A->kb, *v2 = A->vb;
-        hipLaunchKernelGGL(cxs_k_pairs, dim3(cxs_blocks(m)), dim3(256), 0, st, (const uint32_t*)G->vkeys, nvl, (const uint32_t*)A->pend, np, k, v);
+        hipLaunchKernelGGL(cxs_k_pairs, dim3(cx_blocks(m)), dim3(256), 0, st, (const uint32_t*)G->vkeys, nvl, (const uint32_t*)A->pend, np, k, v);
         // as many 8-bit digits as the slab's edge ids have bits
         const uint64_t maxkey = (uint64_t)n0 * plane * 16u - 1u;
         int bits = 0;
         while (bits < 32 && (maxkey >> bits)) bits++;
         for (int shift = 0; shift < bits; shift += 8) {
-            hipLaunchKernelGGL(cxs_k_hist, dim3(cxs_blocks(nunits, 4)), dim3(256), 0, st, (const uint32_t*)k, m, (uint32_t)shift, nunits, A->hist);
+            hipLaunchKernelGGL(cxs_k_hist, dim3(cx_blocks(nunits, 4)), dim3(256), 0, st, (const uint32_t*)k, m, (uint32_t)shift, nunits, A->hist);
             if ((rc = cx_scan_u32(ctx, A->hist, A->offs, (uint32_t)cells, A->sums, A->cnt + 2))) return rc;
-            hipLaunchKernelGGL(cxs_k_scatter, dim3(cxs_blocks(nunits, 4)), dim3(256), 0, st, (const uint32_t*)k, (const uint32_t*)v, m, (uint32_t)shift,
+            hipLaunchKernelGGL(cxs_k_scatter, dim3(cx_blocks(nunits, 4)), dim3(256), 0, st, (const uint32_t*)k, (const uint32_t*)v, m, (uint32_t)shift,
                                (const uint32_t*)A->offs, nunits, k2, v2);
             std::swap(k, k2);
             std::swap(v, v2);
         }
         const uint64_t bound = (uint64_t)owned_planes * plane * 16u;
-        hipLaunchKernelGGL(cxs_k_mark, dim3(cxs_blocks(m)), dim3(256), 0, st, (const uint32_t*)k, m, bound, A->flag, A->cnt);
+        hipLaunchKernelGGL(cxs_k_mark, dim3(cx_blocks(m)), dim3(256), 0, st, (const uint32_t*)k, m, bound, A->flag, A->cnt);
         if ((rc = cx_scan_u32(ctx, A->flag, A->pos, m, A->sums, A->cnt + 1))) return rc;
         cxs_place P;
         P.A = G->grid; P.n1 = n1; P.n2 = n2; P.n3 = n3;
@@ -303,19 +293,19 @@ extern "C" int cx_slab4d_append(cx_ctx* ctx, int64_t i0, int64_t owned_planes, i
         P.value = G->value; P.i0 = (int)i0;
         P.gofs = (uint64_t)i0 * plane * 16u;
         P.bound = bound; P.nv = nvl; P.base = A->nv;
-        hipLaunchKernelGGL(cxs_k_place, dim3(cxs_blocks(m)), dim3(256), 0, st, (const uint32_t*)k, (const uint32_t*)v, (const uint32_t*)A->flag,
+        hipLaunchKernelGGL(cxs_k_place, dim3(cx_blocks(m)), dim3(256), 0, st, (const uint32_t*)k, (const uint32_t*)v, (const uint32_t*)A->flag,
                            (const uint32_t*)A->pos, m, (const uint32_t*)A->cnt, P, A->keys, A->pts, A->vmap, A->resolved, A->pend);
-        CXS_HIP(ctx, hipMemcpyAsync(h, A->cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipMemcpyAsync(h, A->cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     // the previous slab's references to its halo plane, then this slab's tetrahedra
     const size_t prev = (size_t)(A->nt - A->pend_t0) * 4;
     if (np && prev)
-        hipLaunchKernelGGL(cxs_k_resolve, dim3(cxs_blocks(prev)), dim3(256), 0, st, A->tets + (size_t)A->pend_t0 * 4, prev, (const int32_t*)A->resolved);
+        hipLaunchKernelGGL(cxs_k_resolve, dim3(cx_blocks(prev)), dim3(256), 0, st, A->tets + (size_t)A->pend_t0 * 4, prev, (const int32_t*)A->resolved);
     if (ntl)
-        hipLaunchKernelGGL(cxs_k_tets, dim3(cxs_blocks((size_t)ntl * 4)), dim3(256), 0, st, (const int32_t*)G->tets, (size_t)ntl * 4,
+        hipLaunchKernelGGL(cxs_k_tets, dim3(cx_blocks((size_t)ntl * 4)), dim3(256), 0, st, (const int32_t*)G->tets, (size_t)ntl * 4,
                            (const int32_t*)A->vmap, A->tets + (size_t)A->nt * 4);
-    CXS_HIP(ctx, hipGetLastError());
-    CXS_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipStreamSynchronize(st));
     const uint32_t hs = h[0], nnew = h[1];
     A->pend_t0 = A->nt;
     A->nt += ntl;
@@ -346,10 +336,10 @@ int cx_slab4_check(cx_ctx* ctx, cx_slab4* A) {
     if ((rc = A->cnt.grow(ctx, (size_t)16))) return rc;
     uint32_t bad = 0;
     const size_t n = (size_t)A->nt * 4;
-    CXS_HIP(ctx, hipMemsetAsync(A->cnt + 4, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(cxs_k_bad_refs, dim3(cxs_blocks(n)), dim3(256), 0, ctx->stream, (const int32_t*)A->tets, n, (int32_t)A->nv, A->cnt + 4);
-    CXS_HIP(ctx, hipMemcpyAsync(&bad, A->cnt + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    CXS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CX_HIP(ctx, hipMemsetAsync(A->cnt + 4, 0, sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(cxs_k_bad_refs, dim3(cx_blocks(n)), dim3(256), 0, ctx->stream, (const int32_t*)A->tets, n, (int32_t)A->nv, A->cnt + 4);
+    CX_HIP(ctx, hipMemcpyAsync(&bad, A->cnt + 4, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (bad) {
         ctx->err = "cx_slab4d_finish: " + std::to_string(bad) + " tetrahedron corners refer to no assembled vertex";
         return CX_ERR_STATE;
@@ -361,7 +351,7 @@ extern "C" int cx_slab4d_download_keys(cx_ctx* ctx, int64_t* keys) {
     if (!ctx || !keys) return CX_ERR_INVALID;
     cx_state4* G = ctx->s4;
     if (!G || !G->post_valid || !G->post_assembled || !G->slab) { ctx->err = "cx_slab4d_download_keys: run cx_slab4d_finish first"; return CX_ERR_STATE; }
-    CXS_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     if (!G->slab->nv) return CX_OK;
     return cx_copy_to_host1(ctx, keys, G->slab->keys, (size_t)G->slab->nv * sizeof(uint64_t));
 }

@@ -22,20 +22,8 @@
 #include <string>
 
 #include "cx_ctx.h"
+#include "cx_dev.h"
 
-#define CXT_HIP(ctx, call)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
-typedef unsigned long long u64;
-
-#define CXT_EMPTY 0xFFFFFFFFFFFFFFFFULL
-#define CXT_NONE 0xFFFFFFFFu
 #define CXT_END 0xFFFFFFFFu
 
 // accumulator words per component
@@ -72,47 +60,37 @@ void cx_topo_free(cx_ctx* ctx) {
 }
 
 // ---- device helpers -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u64 cxt_mix(u64 x) {      // (cxp_mix of cx_post.hip)
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL;
-    x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL;
-    x ^= x >> 33;
-    return x;
-}
 // home slot in a table of cap < 2^32 slots (any size, not a power of two)
-__device__ __forceinline__ uint32_t cxt_home(u64 key, uint32_t cap) { return (uint32_t)(((cxt_mix(key) >> 32) * (u64)cap) >> 32); }
-// slot of key, claimed if it was not there (fresh: this lane claimed it); CXT_NONE when the table is full
+__device__ __forceinline__ uint32_t cxt_home(u64 key, uint32_t cap) { return (uint32_t)(((cxd_mix(key) >> 32) * (u64)cap) >> 32); }
+// slot of key, claimed if it was not there (fresh: this lane claimed it); CXD_NONE when the table is full
 __device__ __forceinline__ uint32_t cxt_insert(u64* keys, uint32_t cap, u64 key, bool& fresh) {
     uint32_t s = cxt_home(key, cap);
     fresh = false;
     for (uint32_t probe = 0; probe < cap; probe++) {
         u64 cur = __hip_atomic_load(&keys[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == CXT_EMPTY) {
-            cur = atomicCAS(&keys[s], CXT_EMPTY, key);
-            if (cur == CXT_EMPTY) { fresh = true; return s; }
+        if (cur == CXD_EMPTY) {
+            cur = atomicCAS(&keys[s], CXD_EMPTY, key);
+            if (cur == CXD_EMPTY) { fresh = true; return s; }
         }
         if (cur == key) return s;
         s = s + 1u == cap ? 0u : s + 1u;
     }
-    return CXT_NONE;
+    return CXD_NONE;
 }
-// slot of a key of a finished table; CXT_NONE when it is not there
+// slot of a key of a finished table; CXD_NONE when it is not there
 __device__ __forceinline__ uint32_t cxt_find(const u64* __restrict__ keys, uint32_t cap, u64 key) {
     uint32_t s = cxt_home(key, cap);
     for (uint32_t probe = 0; probe < cap; probe++) {
         const u64 cur = keys[s];
         if (cur == key) return s;
-        if (cur == CXT_EMPTY) return CXT_NONE;
+        if (cur == CXD_EMPTY) return CXD_NONE;
         s = s + 1u == cap ? 0u : s + 1u;
     }
-    return CXT_NONE;
+    return CXD_NONE;
 }
 __device__ __forceinline__ u64 cxt_edge_key(uint32_t a, uint32_t b) { return ((u64)(a < b ? a : b) << 32) | (u64)(a < b ? b : a); }
-__device__ __forceinline__ uint32_t cxt_wave_add(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o);
-    return v;
-}
-// union-find over list indices: a root points to itself, parents are smaller than their children, so a set's root is its smallest member
+// union-find over list indices: a root points to itself, parents are smaller than their children, so a set's root is its smallest member.
+// No path halving; every access to a parent word is a device-scope atomic (why: cx_dev.h, above cxd_uf_find)
 __device__ __forceinline__ uint32_t cxt_root(uint32_t* parent, uint32_t x) {
     for (;;) {
         const uint32_t p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -144,7 +122,7 @@ __global__ __launch_bounds__(256) void cxt_k_edges_insert(const int32_t* __restr
     for (int k = 0; k < 3; k++) {
         bool fresh;
         const uint32_t s = cxt_insert(keys, cap, cxt_edge_key(v[k], v[(k + 1) % 3]), fresh);
-        if (s == CXT_NONE) { atomicOr(&misc[CXT_M_FAIL], 1u); continue; }
+        if (s == CXD_NONE) { atomicOr(&misc[CXT_M_FAIL], 1u); continue; }
         if (fresh) rep[s] = t * 3u + (uint32_t)k;
         atomicAdd(&cnt[s], 1u);
         mismatch += vlab[v[k]] != c ? 1u : 0u;
@@ -172,7 +150,7 @@ __global__ __launch_bounds__(256) void cxt_k_edges_count(const int32_t* __restri
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 const uint32_t s = cxt_find(keys, cap, cxt_edge_key(v[k], v[(k + 1) % 3]));
-                if (s == CXT_NONE) { atomicOr(&misc[CXT_M_FAIL], 2u); continue; }
+                if (s == CXD_NONE) { atomicOr(&misc[CXT_M_FAIL], 2u); continue; }
                 const uint32_t uses = cnt[s];
                 const bool first = rep[s] == t * 3u + (uint32_t)k;
                 if (first) packed += 1u << 8;
@@ -191,7 +169,7 @@ __global__ __launch_bounds__(256) void cxt_k_edges_count(const int32_t* __restri
         const bool mine = active && label == k;
         const uint64_t grp = __ballot(mine);
         rem &= ~grp;
-        const uint32_t sum = cxt_wave_add(mine ? packed : 0u);
+        const uint32_t sum = cxd_wave_add(mine ? packed : 0u);
         if ((int)lane == leader) {
             u64* w = acc + (size_t)k * CXT_WORDS;
             atomicAdd(&w[CXT_W_F], (u64)(sum & 255u));
@@ -234,7 +212,7 @@ __global__ __launch_bounds__(256) void cxt_k_vertices_shared(const int32_t* __re
         if (vlab[v[k]] == c) continue;
         bool fresh;
         const uint32_t s = cxt_insert(keys, cap, ((u64)(uint32_t)c << 32) | (u64)v[k], fresh);
-        if (s == CXT_NONE) { atomicOr(&misc[CXT_M_FAIL], 4u); continue; }
+        if (s == CXD_NONE) { atomicOr(&misc[CXT_M_FAIL], 4u); continue; }
         if (fresh) atomicAdd(&acc[(size_t)c * CXT_WORDS + CXT_W_V], 1ULL);
     }
 }
@@ -267,7 +245,7 @@ __global__ void cxt_k_loop_insert(const uint32_t* __restrict__ bl, const int32_t
     for (int end = 0; end < 2; end++) {
         bool fresh;
         const uint32_t s = cxt_insert(vkeys, vcap, ((u64)c << 32) | (u64)(end ? b : a), fresh);
-        if (s == CXT_NONE) { atomicOr(&misc[CXT_M_FAIL], 8u); continue; }
+        if (s == CXD_NONE) { atomicOr(&misc[CXT_M_FAIL], 8u); continue; }
         atomicMin(&vmin[s], i);
         atomicMax(&vmax[s], i);
         atomicAdd(&vdeg[s], 1u);
@@ -281,7 +259,7 @@ __global__ void cxt_k_loop_link(const uint32_t* __restrict__ ea, const uint32_t*
 #pragma unroll
     for (int end = 0; end < 2; end++) {
         const uint32_t s = cxt_find(vkeys, vcap, ((u64)ec[i] << 32) | (u64)(end ? eb[i] : ea[i]));
-        if (s == CXT_NONE) continue;
+        if (s == CXD_NONE) continue;
         const uint32_t j = vmin[s];
         if (j < nb && j != i) cxt_union(parent, i, j);
     }
@@ -312,7 +290,7 @@ __global__ void cxt_k_loop_edges(const uint32_t* __restrict__ ea, const uint32_t
                                  uint32_t* lcount, cx_loop* loops, uint32_t* __restrict__ nxt, uint32_t* __restrict__ rnk) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nb) return;
-    const uint32_t r = root[i], l = r < nb ? lidx[r] : CXT_NONE;
+    const uint32_t r = root[i], l = r < nb ? lidx[r] : CXD_NONE;
     eloop[i] = l;
     if (l >= nl) { nxt[2 * (size_t)i] = CXT_END; nxt[2 * (size_t)i + 1] = CXT_END; rnk[2 * (size_t)i] = 0; rnk[2 * (size_t)i + 1] = 0; return; }
     atomicAdd(&lcount[l], 1u);
@@ -323,7 +301,7 @@ __global__ void cxt_k_loop_edges(const uint32_t* __restrict__ ea, const uint32_t
         const uint32_t far = dir ? a : b;
         const uint32_t s = cxt_find(vkeys, vcap, ((u64)c << 32) | (u64)far);
         uint32_t to = 2u * i + (uint32_t)dir;          // (to itself: a walk that gets nowhere)
-        if (s == CXT_NONE || vdeg[s] != 2u) simple = false;
+        if (s == CXD_NONE || vdeg[s] != 2u) simple = false;
         else {
             const uint32_t j = vmin[s] == i ? vmax[s] : vmin[s];
             if (j < nb) to = 2u * j + (ea[j] == far ? 0u : 1u);
@@ -379,7 +357,7 @@ __global__ __launch_bounds__(64) void cxt_k_nonsimple(const uint32_t* __restrict
     const uint32_t lane = threadIdx.x & 63u;
     for (u64 base = 0; base < (u64)nb; base += 64ULL) {      // wave-uniform
         const u64 i = base + lane;
-        uint32_t l = CXT_NONE;
+        uint32_t l = CXD_NONE;
         bool active = i < (u64)nb;
         if (active) { l = eloop[i]; active = l < nl && loops[l].simple == 0; }
         uint64_t rem = __ballot(active);
@@ -421,7 +399,6 @@ __global__ void cxt_k_finish(const u64* __restrict__ acc, uint32_t nc, cx_topolo
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static inline dim3 cxt_grid(size_t n) { return dim3((unsigned)((n + 255) / 256 ? (n + 255) / 256 : 1)); }
 
 static int cxt_fail_check(cx_ctx* ctx, const uint32_t* h) {
     if (!h[CXT_M_FAIL]) return CX_OK;
@@ -453,21 +430,21 @@ static int cxt_loops(cx_ctx* ctx, cx_topo_state* T, const cx_level1_comp_view& V
         if ((rc = T->nxt[b].grow(ctx, 2 * (size_t)nb + 16))) return rc;
         if ((rc = T->rnk[b].grow(ctx, 2 * (size_t)nb + 16))) return rc;
     }
-    CXT_HIP(ctx, hipMemsetAsync(T->vkeys, 0xFF, (size_t)vcap * sizeof(u64), st));
-    CXT_HIP(ctx, hipMemsetAsync(T->vmin, 0xFF, (size_t)vcap * sizeof(uint32_t), st));
-    CXT_HIP(ctx, hipMemsetAsync(T->vmax, 0, (size_t)vcap * sizeof(uint32_t), st));
-    CXT_HIP(ctx, hipMemsetAsync(T->vdeg, 0, (size_t)vcap * sizeof(uint32_t), st));
-    CXT_HIP(ctx, hipMemsetAsync(T->lverts, 0, (size_t)nb * sizeof(int32_t), st));
-    hipLaunchKernelGGL(cxt_k_compact, cxt_grid(nt), dim3(256), 0, st, T->bmask.get(), (const uint32_t*)T->bpos, nt, nb, T->bl);
-    hipLaunchKernelGGL(cxt_k_loop_insert, cxt_grid(nb), dim3(256), 0, st, (const uint32_t*)T->bl, V.tri, tlab, nb, T->ea, T->eb, T->ec, T->parent,
+    CX_HIP(ctx, hipMemsetAsync(T->vkeys, 0xFF, (size_t)vcap * sizeof(u64), st));
+    CX_HIP(ctx, hipMemsetAsync(T->vmin, 0xFF, (size_t)vcap * sizeof(uint32_t), st));
+    CX_HIP(ctx, hipMemsetAsync(T->vmax, 0, (size_t)vcap * sizeof(uint32_t), st));
+    CX_HIP(ctx, hipMemsetAsync(T->vdeg, 0, (size_t)vcap * sizeof(uint32_t), st));
+    CX_HIP(ctx, hipMemsetAsync(T->lverts, 0, (size_t)nb * sizeof(int32_t), st));
+    hipLaunchKernelGGL(cxt_k_compact, cx_grid1(nt), dim3(256), 0, st, T->bmask.get(), (const uint32_t*)T->bpos, nt, nb, T->bl);
+    hipLaunchKernelGGL(cxt_k_loop_insert, cx_grid1(nb), dim3(256), 0, st, (const uint32_t*)T->bl, V.tri, tlab, nb, T->ea, T->eb, T->ec, T->parent,
                        T->vkeys, T->vmin, T->vmax, T->vdeg, vcap, T->misc);
-    hipLaunchKernelGGL(cxt_k_loop_link, cxt_grid(nb), dim3(256), 0, st, (const uint32_t*)T->ea, (const uint32_t*)T->eb, (const uint32_t*)T->ec, nb,
+    hipLaunchKernelGGL(cxt_k_loop_link, cx_grid1(nb), dim3(256), 0, st, (const uint32_t*)T->ea, (const uint32_t*)T->eb, (const uint32_t*)T->ec, nb,
                        (const u64*)T->vkeys, (const uint32_t*)T->vmin, vcap, T->parent);
-    hipLaunchKernelGGL(cxt_k_loop_roots, cxt_grid(nb), dim3(256), 0, st, T->parent, nb, T->root, T->isroot);
+    hipLaunchKernelGGL(cxt_k_loop_roots, cx_grid1(nb), dim3(256), 0, st, T->parent, nb, T->root, T->isroot);
     if ((rc = cx_scan_u32(ctx, T->isroot, T->lidx, nb, T->sums, T->misc + CXT_M_L))) return rc;
     uint32_t h[CXT_M_WORDS];
-    CXT_HIP(ctx, hipMemcpyAsync(h, T->misc, sizeof(h), hipMemcpyDeviceToHost, st));
-    CXT_HIP(ctx, hipStreamSynchronize(st));
+    CX_HIP(ctx, hipMemcpyAsync(h, T->misc, sizeof(h), hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipStreamSynchronize(st));
     if ((rc = cxt_fail_check(ctx, h))) return rc;
     const uint32_t nl = h[CXT_M_L];
     if (nl == 0 || nl > nb) { ctx->err = "cx_level1_boundary_loops: the loops do not add up"; return CX_ERR_HIP; }
@@ -475,33 +452,33 @@ static int cxt_loops(cx_ctx* ctx, cx_topo_state* T, const cx_level1_comp_view& V
     if ((rc = T->lcount.grow(ctx, (size_t)nl + 16))) return rc;
     if ((rc = T->lfirst.grow(ctx, (size_t)nl + 16))) return rc;
     if ((rc = T->cursor.grow(ctx, (size_t)nl + 16))) return rc;
-    CXT_HIP(ctx, hipMemsetAsync(T->lcount, 0, (size_t)nl * sizeof(uint32_t), st));
-    CXT_HIP(ctx, hipMemsetAsync(T->cursor, 0, (size_t)nl * sizeof(uint32_t), st));
-    hipLaunchKernelGGL(cxt_k_loop_init, cxt_grid(nb), dim3(256), 0, st, (const uint32_t*)T->isroot, (const uint32_t*)T->lidx, (const uint32_t*)T->ec, nb, nl, T->loops);
-    hipLaunchKernelGGL(cxt_k_loop_edges, cxt_grid(nb), dim3(256), 0, st, (const uint32_t*)T->ea, (const uint32_t*)T->eb, (const uint32_t*)T->ec,
+    CX_HIP(ctx, hipMemsetAsync(T->lcount, 0, (size_t)nl * sizeof(uint32_t), st));
+    CX_HIP(ctx, hipMemsetAsync(T->cursor, 0, (size_t)nl * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(cxt_k_loop_init, cx_grid1(nb), dim3(256), 0, st, (const uint32_t*)T->isroot, (const uint32_t*)T->lidx, (const uint32_t*)T->ec, nb, nl, T->loops);
+    hipLaunchKernelGGL(cxt_k_loop_edges, cx_grid1(nb), dim3(256), 0, st, (const uint32_t*)T->ea, (const uint32_t*)T->eb, (const uint32_t*)T->ec,
                        (const uint32_t*)T->root, (const uint32_t*)T->lidx, nb, nl, (const u64*)T->vkeys, (const uint32_t*)T->vmin, (const uint32_t*)T->vmax,
                        (const uint32_t*)T->vdeg, vcap, T->eloop, T->lcount, T->loops, T->nxt[0], T->rnk[0]);
     if ((rc = cx_scan_u32(ctx, T->lcount, T->lfirst, nl, T->sums, T->misc + CXT_M_SCRATCH))) return rc;
-    hipLaunchKernelGGL(cxt_k_loop_finish, cxt_grid(nl), dim3(256), 0, st, (const uint32_t*)T->lcount, (const uint32_t*)T->lfirst, nl, nc, T->loops, T->acc, T->misc);
+    hipLaunchKernelGGL(cxt_k_loop_finish, cx_grid1(nl), dim3(256), 0, st, (const uint32_t*)T->lcount, (const uint32_t*)T->lfirst, nl, nc, T->loops, T->acc, T->misc);
     // the longest walk has nb steps: after r rounds a dart has looked 2^r steps ahead
     int rounds = 0;
     while (rounds < 32 && (1ULL << rounds) < (u64)nb) rounds++;
     int cur = 0;
     for (int r = 0; r < rounds; r++, cur ^= 1)
-        hipLaunchKernelGGL(cxt_k_double, cxt_grid(2 * (size_t)nb), dim3(256), 0, st, (const uint32_t*)T->nxt[cur], (const uint32_t*)T->rnk[cur], 2u * nb,
+        hipLaunchKernelGGL(cxt_k_double, cx_grid1(2 * (size_t)nb), dim3(256), 0, st, (const uint32_t*)T->nxt[cur], (const uint32_t*)T->rnk[cur], 2u * nb,
                            T->nxt[cur ^ 1], T->rnk[cur ^ 1]);
-    hipLaunchKernelGGL(cxt_k_scatter, cxt_grid(2 * (size_t)nb), dim3(256), 0, st, (const uint32_t*)T->nxt[cur], (const uint32_t*)T->rnk[cur], (const uint32_t*)T->eloop,
+    hipLaunchKernelGGL(cxt_k_scatter, cx_grid1(2 * (size_t)nb), dim3(256), 0, st, (const uint32_t*)T->nxt[cur], (const uint32_t*)T->rnk[cur], (const uint32_t*)T->eloop,
                        (const uint32_t*)T->ea, (const uint32_t*)T->eb, (const cx_loop*)T->loops, nb, nl, T->lverts);
     hipLaunchKernelGGL(cxt_k_nonsimple, dim3(1), dim3(64), 0, st, (const uint32_t*)T->eloop, (const uint32_t*)T->ea, (const cx_loop*)T->loops, nb, nl, T->cursor,
                        (const uint32_t*)T->misc, T->lverts);
-    CXT_HIP(ctx, hipGetLastError());
+    CX_HIP(ctx, hipGetLastError());
     *nl_out = nl;
     return CX_OK;
 }
 
 // table and loops of the current mesh (cached per generation of the mesh)
 static int cxt_build(cx_ctx* ctx, const char* who, cx_topo_state** Tout) {
-    CXT_HIP(ctx, hipSetDevice(ctx->device));
+    CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_level1_comp_view V;
     const int32_t *tlab = nullptr, *vlab = nullptr;
     uint32_t nc = 0;
@@ -533,18 +510,18 @@ static int cxt_build(cx_ctx* ctx, const char* who, cx_topo_state** Tout) {
         if ((rc = T->sums.grow(ctx, 3 * (size_t)nt / 1024 + 16))) return rc;
         if ((rc = T->acc.grow(ctx, (size_t)nc * CXT_WORDS + 16))) return rc;
         if ((rc = T->table.grow(ctx, (size_t)nc + 1))) return rc;
-        CXT_HIP(ctx, hipMemsetAsync(T->misc, 0, CXT_M_WORDS * sizeof(uint32_t), st));
-        CXT_HIP(ctx, hipMemsetAsync(T->ekeys, 0xFF, (size_t)cap * sizeof(u64), st));
-        CXT_HIP(ctx, hipMemsetAsync(T->ecnt, 0, (size_t)cap * sizeof(uint32_t), st));
-        CXT_HIP(ctx, hipMemsetAsync(T->acc, 0, (size_t)nc * CXT_WORDS * sizeof(u64), st));
-        hipLaunchKernelGGL(cxt_k_edges_insert, cxt_grid(nt), dim3(256), 0, st, V.tri, tlab, vlab, nt, nv, T->ekeys, T->ecnt, T->erep, cap, T->misc);
-        hipLaunchKernelGGL(cxt_k_edges_count, cxt_grid(nt), dim3(256), 0, st, V.tri, tlab, nt, nv, nc, (const u64*)T->ekeys, (const uint32_t*)T->ecnt,
+        CX_HIP(ctx, hipMemsetAsync(T->misc, 0, CXT_M_WORDS * sizeof(uint32_t), st));
+        CX_HIP(ctx, hipMemsetAsync(T->ekeys, 0xFF, (size_t)cap * sizeof(u64), st));
+        CX_HIP(ctx, hipMemsetAsync(T->ecnt, 0, (size_t)cap * sizeof(uint32_t), st));
+        CX_HIP(ctx, hipMemsetAsync(T->acc, 0, (size_t)nc * CXT_WORDS * sizeof(u64), st));
+        hipLaunchKernelGGL(cxt_k_edges_insert, cx_grid1(nt), dim3(256), 0, st, V.tri, tlab, vlab, nt, nv, T->ekeys, T->ecnt, T->erep, cap, T->misc);
+        hipLaunchKernelGGL(cxt_k_edges_count, cx_grid1(nt), dim3(256), 0, st, V.tri, tlab, nt, nv, nc, (const u64*)T->ekeys, (const uint32_t*)T->ecnt,
                            (const uint32_t*)T->erep, cap, T->bmask, T->bcnt, T->acc, T->misc);
-        hipLaunchKernelGGL(cxt_k_vertices, cxt_grid(nv), dim3(256), 0, st, vlab, nv, nc, T->acc);
+        hipLaunchKernelGGL(cxt_k_vertices, cx_grid1(nv), dim3(256), 0, st, vlab, nv, nc, T->acc);
         if ((rc = cx_scan_u32(ctx, T->bcnt, T->bpos, nt, T->sums, T->misc + CXT_M_B))) return rc;
         uint32_t h[CXT_M_WORDS];
-        CXT_HIP(ctx, hipMemcpyAsync(h, T->misc, sizeof(h), hipMemcpyDeviceToHost, st));
-        CXT_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipMemcpyAsync(h, T->misc, sizeof(h), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
         if ((rc = cxt_fail_check(ctx, h))) return rc;
         nb = h[CXT_M_B];
         if (nb > 3u * nt) { ctx->err = std::string(who) + ": the boundary edges do not add up"; return CX_ERR_HIP; }
@@ -552,18 +529,18 @@ static int cxt_build(cx_ctx* ctx, const char* who, cx_topo_state** Tout) {
         if (shared) {
             const uint32_t mcap = 2u * std::min(shared, 3u * nt) + 64u;
             if ((rc = T->mkeys.grow(ctx, mcap))) return rc;
-            CXT_HIP(ctx, hipMemsetAsync(T->mkeys, 0xFF, (size_t)mcap * sizeof(u64), st));
-            hipLaunchKernelGGL(cxt_k_vertices_shared, cxt_grid(nt), dim3(256), 0, st, V.tri, tlab, vlab, nt, nv, nc, T->mkeys, mcap, T->acc, T->misc);
+            CX_HIP(ctx, hipMemsetAsync(T->mkeys, 0xFF, (size_t)mcap * sizeof(u64), st));
+            hipLaunchKernelGGL(cxt_k_vertices_shared, cx_grid1(nt), dim3(256), 0, st, V.tri, tlab, vlab, nt, nv, nc, T->mkeys, mcap, T->acc, T->misc);
         }
         if (nb >= (1u << 30)) {
             ctx->err = std::string(who) + ": " + std::to_string(nb) + " boundary edges; the loops (two darts per edge, 4 table slots per edge) take fewer than 2^30";
             return CX_ERR_UNSUPPORTED;
         }
         if (nb && (rc = cxt_loops(ctx, T, V, tlab, nc, nb, &nl))) return rc;
-        hipLaunchKernelGGL(cxt_k_finish, cxt_grid(nc), dim3(256), 0, st, (const u64*)T->acc, nc, T->table);
-        CXT_HIP(ctx, hipMemcpyAsync(h, T->misc, sizeof(h), hipMemcpyDeviceToHost, st));
-        CXT_HIP(ctx, hipStreamSynchronize(st));
-        CXT_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(cxt_k_finish, cx_grid1(nc), dim3(256), 0, st, (const u64*)T->acc, nc, T->table);
+        CX_HIP(ctx, hipMemcpyAsync(h, T->misc, sizeof(h), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
+        CX_HIP(ctx, hipGetLastError());
         if ((rc = cxt_fail_check(ctx, h))) return rc;
     }
     T->nc = (nt && nc) ? nc : 0; T->nb = nb; T->nl = nl;

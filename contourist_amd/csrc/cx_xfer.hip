@@ -17,15 +17,6 @@
 
 #include "cx_ctx.h"
 
-#define CXX_HIP(ctx, call)                                                                       \
-    do {                                                                                         \
-        hipError_t e__ = (call);                                                                 \
-        if (e__ != hipSuccess) {                                                                 \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e__);                     \
-            return (e__ == hipErrorOutOfMemory) ? CX_ERR_NOMEM : CX_ERR_HIP;                      \
-        }                                                                                        \
-    } while (0)
-
 static const size_t CX_XFER_CHUNK = (size_t)32 << 20;   // bytes per staging buffer
 
 void cx_xfer_free(cx_ctx* ctx) {
@@ -54,16 +45,16 @@ static int xfer_threads() {
 int cx_copy_to_host(cx_ctx* ctx, int nparts, void* const* dst, const void* const* src, const size_t* bytes) {
     size_t total = 0;
     for (int p = 0; p < nparts; p++) total += (dst[p] && src[p]) ? bytes[p] : 0;
-    if (total == 0) { CXX_HIP(ctx, hipStreamSynchronize(ctx->stream)); return CX_OK; }
+    if (total == 0) { CX_HIP(ctx, hipStreamSynchronize(ctx->stream)); return CX_OK; }
     if (total < ((size_t)4 << 20)) {   // small: the runtime's own path
         for (int p = 0; p < nparts; p++)
-            if (dst[p] && src[p] && bytes[p]) CXX_HIP(ctx, hipMemcpyAsync(dst[p], src[p], bytes[p], hipMemcpyDeviceToHost, ctx->stream));
-        CXX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (dst[p] && src[p] && bytes[p]) CX_HIP(ctx, hipMemcpyAsync(dst[p], src[p], bytes[p], hipMemcpyDeviceToHost, ctx->stream));
+        CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return CX_OK;
     }
     for (int b = 0; b < 2; b++) {
-        if (!ctx->xfer_stage[b]) CXX_HIP(ctx, hipHostMalloc(&ctx->xfer_stage[b], CX_XFER_CHUNK));
-        if (!ctx->xfer_ev[b]) CXX_HIP(ctx, hipEventCreateWithFlags(&ctx->xfer_ev[b], hipEventDisableTiming));
+        if (!ctx->xfer_stage[b]) CX_HIP(ctx, hipHostMalloc(&ctx->xfer_stage[b], CX_XFER_CHUNK));
+        if (!ctx->xfer_ev[b]) CX_HIP(ctx, hipEventCreateWithFlags(&ctx->xfer_ev[b], hipEventDisableTiming));
     }
     struct piece { char* dst; const char* src; size_t n; };
     std::vector<piece> pieces;
