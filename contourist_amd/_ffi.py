@@ -62,6 +62,7 @@ SYMBOLS = [
     "cx_extract3d", "cx_extract3d_async", "cx_counts_get", "cx_extract3d_levels", "cx_levels_select", "cx_level0_path", "cx_level0_download", "cx_level0_device_ptrs", "cx_level0_device_records", "cx_level0_download_records",
     "cx_postprocess3d", "cx_postprocess3d_ex", "cx_level0_points_f64", "cx_postprocess3d_mesh", "cx_select_seeded3d", "cx_select_seeded3d_ex", "cx_seeded_masks_download", "cx_set_reference_corner", "cx_level1_download", "cx_level1_device_ptrs", "cx_level1_download_keys", "cx_postprocess3d_shard_begin", "cx_postprocess3d_shard_boundary", "cx_postprocess3d_shard_candidates", "cx_postprocess3d_shard_finish", "cx_level1_write", "cx_surface_geometry",
     "cx_level0_normals", "cx_level0_normals_download", "cx_level1_normals", "cx_level1_normals_download", "cx_level0_sample_grid", "cx_level1_sample_grid",
+    "cx_level0_curvature", "cx_level0_curvature_download", "cx_level1_curvature", "cx_level1_curvature_download",
     "cx_level1_components", "cx_level1_components_download", "cx_level1_component_labels", "cx_level1_component_labels_download", "cx_level1_keep_components",
     "cx_level1_topology", "cx_level1_topology_download", "cx_level1_boundary_loops", "cx_level1_boundary_loops_download",
     "cx_level1_simplify", "cx_level1_simplify_map", "cx_level1_simplify_map_download",
@@ -218,6 +219,10 @@ def load():
         "cx_level0_normals_download": [vp, vp, vp],
         "cx_level1_normals": [vp, vp, ctypes.POINTER(vp)],
         "cx_level1_normals_download": [vp, vp, vp],
+        "cx_level0_curvature": [vp, vp, ctypes.POINTER(vp)],
+        "cx_level0_curvature_download": [vp, vp, vp],
+        "cx_level1_curvature": [vp, vp, ctypes.POINTER(vp)],
+        "cx_level1_curvature_download": [vp, vp, vp],
         "cx_level0_sample_grid": [vp, vp, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(vp), vp],
         "cx_level1_sample_grid": [vp, vp, ctypes.c_int32, ctypes.c_int, ctypes.POINTER(vp), vp],
         "cx_level1_components": [vp, vp, ctypes.POINTER(i64), ctypes.POINTER(vp), vp],
@@ -628,6 +633,36 @@ class Context(object):
             return self._device_view(p.value or 0, (nv, 3), "<f8", torch.float64)
         out = np.zeros((nv, 3), dtype=np.float64)
         self._check_attr(self.lib.cx_level1_normals_download(self.handle, dp, out.ctypes.data))
+        return out
+
+    def level0_curvature(self, counts, delta=None, device=False):
+        """(V,4) float32 {mean, gauss, k1, k2} per vertex record of the current extraction, in the order of download_level0
+        (delta: world spacing per axis; device=True: a torch tensor on the GPU)"""
+        nv = int(counts["n_vertices"])
+        d3 = self._delta3(delta)
+        dp = None if d3 is None else d3.ctypes.data
+        if device:
+            import torch
+            p = ctypes.c_void_p()
+            self._check_attr(self.lib.cx_level0_curvature(self.handle, dp, ctypes.byref(p)))
+            return self._device_view(p.value or 0, (nv, 4), "<f4", torch.float32)
+        out = np.zeros((nv, 4), dtype=np.float32)
+        self._check_attr(self.lib.cx_level0_curvature_download(self.handle, dp, out.ctypes.data))
+        return out
+
+    def level1_curvature(self, counts, delta=None, device=False):
+        """(V,4) float64 {mean, gauss, k1, k2} of the Level-1 vertices in the order of download_level1, signed like
+        level1_normals (delta: world spacing per axis; device=True: a torch tensor on the GPU)"""
+        nv = int(counts["n_vertices"])
+        d3 = self._delta3(delta)
+        dp = None if d3 is None else d3.ctypes.data
+        if device:
+            import torch
+            p = ctypes.c_void_p()
+            self._check_attr(self.lib.cx_level1_curvature(self.handle, dp, ctypes.byref(p)))
+            return self._device_view(p.value or 0, (nv, 4), "<f8", torch.float64)
+        out = np.zeros((nv, 4), dtype=np.float64)
+        self._check_attr(self.lib.cx_level1_curvature_download(self.handle, dp, out.ctypes.data))
         return out
 
     def _second_grid(self, field):

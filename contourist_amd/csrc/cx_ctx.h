@@ -161,6 +161,8 @@ struct cx_ctx {
     cx_buf<double> attr_v1;
     cx_buf<uint8_t> attr_e1;        // Level 1: per output vertex {sample index of the low point, of the high point, ratio} (16 bytes)
     cx_buf<uint8_t> attr_grid;
+    cx_buf<float4> attr_c0;         // curvature: Level 0 float4 {mean, gauss, k1, k2}, Level 1 double[4] in the same order
+    cx_buf<double> attr_c1;
     // components of the Level-1 mesh (cx_comp.hip): labels, accumulators and the table, kept between calls
     struct cx_comp_state* comp = nullptr;
     // vertex clustering of the Level-1 mesh (cx_simplify.hip): cluster table, accumulators, scans, kept between calls

@@ -281,6 +281,19 @@ class GridContour3d(object):
         ctx = self._ensure_post(clean)
         return ctx.level1_normals(self._post, delta, device)
 
+    def level0_curvature(self, device=False):
+        "(V,4) float32 {mean, gauss, k1, k2} next to level0(): mean, Gaussian and principal curvatures per vertex record (grid units)"
+        counts = self.march()
+        return self.context().level0_curvature(counts, None, device)
+
+    def vertex_curvature(self, clean=True, device=False, delta=None):
+        """(V,4) float64 {mean, gauss, k1, k2} in grid units (1/voxel, 1/voxel^2); row i belongs to row i of
+        get_points_and_triangles()[0] and is signed like vertex_normals(): a sphere whose normals point outwards has mean > 0.
+        delta: world spacing per axis (curvature in world units).  Not available after simplify()."""
+        self._attr_checks()
+        ctx = self._ensure_post(clean)
+        return ctx.level1_curvature(self._post, delta, device)
+
     def vertex_values(self, field, clean=True, device=False):
         "(V,) float64: `field` (array or device tensor of the grid's shape, any supported dtype) at the vertices of get_points_and_triangles()"
         self._attr_checks()
@@ -695,6 +708,11 @@ class Delta3DContour(object):
         to row i of get_points_and_triangles()[0]"""
         return self.contour_maker.vertex_normals(clean, device, delta=self.grid.delta)
 
+    def vertex_curvature(self, clean=True, device=False):
+        """(V,4) float64 {mean, gauss, k1, k2} in WORLD units (the grid's delta is passed on); row i belongs to row i of
+        get_points_and_triangles()[0], signed like vertex_normals()"""
+        return self.contour_maker.vertex_curvature(clean, device, delta=self.grid.delta)
+
     def vertex_values(self, field, clean=True, device=False):
         """(V,) float64: a second field at the vertices.  `field`: an array or device tensor of the grid's shape
         (grid_dimensions + 1), or -- for a grid made from a callable -- a callable g(x, y, z) in world coordinates, sampled
@@ -831,7 +849,7 @@ def _loop_points(points, loops, verts, mins=None, delta=None):
 
 class LevelResult(tuple):
     """(value, points, triangles) of one level of MultiLevelIsosurfaces.levels(), with the vertex attributes of that level:
-    vertex_normals() / vertex_values(field).  They read the level's mesh on the device, so they work until the
+    vertex_normals() / vertex_curvature() / vertex_values(field).  They read the level's mesh on the device, so they work until the
     generator moves on to the next level."""
 
     def _bind(self, owner, index, post, delta, mins=None):
@@ -847,6 +865,10 @@ class LevelResult(tuple):
     def vertex_normals(self, device=False):
         "(V,3) float64 unit normals in world coordinates, row i for points[i]"
         return self._ctx().level1_normals(self._post, self._delta, device)
+
+    def vertex_curvature(self, device=False):
+        "(V,4) float64 {mean, gauss, k1, k2} in world units, row i for points[i], signed like vertex_normals()"
+        return self._ctx().level1_curvature(self._post, self._delta, device)
 
     def vertex_values(self, field, device=False):
         "(V,) float64: a second grid of the samples' shape at the vertices"

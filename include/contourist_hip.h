@@ -319,6 +319,34 @@ int cx_level1_normals_download(cx_ctx* ctx, const double* delta3, double* normal
 int cx_level0_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtype, int on_device, void** values_dev, float* values_host);
 int cx_level1_sample_grid(cx_ctx* ctx, const void* grid, int32_t dtype, int on_device, void** values_dev, double* values_host);
 
+/* Curvature at the same vertices: how strongly the isosurface bends.  For an isosurface it is a closed formula in the field's
+ * gradient and Hessian at the crossing, so it needs no mesh adjacency.  f is the resident sample array, p a lattice point.
+ * Gradient G(p): the rule of the normals above (numpy.gradient with its defaults).
+ * Hessian H(p): second differences at the centre c = clamp(p, 1, n-2) on every axis -- a rim point takes the Hessian of its
+ * nearest interior point -- in this order of evaluation (the error bound of the tests rests on it):
+ *     H_aa = (f[c+e_a] - f[c]) - (f[c] - f[c-e_a])
+ *     H_ab = ((f[c+e_a+e_b] - f[c+e_a-e_b]) - (f[c-e_a+e_b] - f[c-e_a-e_b])) * 0.25   for a < b, H symmetric
+ * 19 samples per lattice point; inside the array the 6 axis neighbours are the gradient's samples too.
+ * At a vertex on the edge a -> b at fraction r (a, b, r per level exactly as the normals take them):
+ *     g = G(a) + r (G(b) - G(a)),  H = H(a) + r (H(b) - H(a));   with delta3: g_i /= delta_i, H_ij /= delta_i delta_j;   n = g / |g|
+ *     mean  = (tr H - n'Hn) / (2 |g|)
+ *     gauss = n' adj(H) n / |g|^2
+ *     k1, k2 = mean +- sqrt(max(mean^2 - gauss, 0)),  k1 >= k2
+ * g is scaled by a power of two before it is squared, as for the normals; |g| == 0 gives four zeros.  Sign: a sphere whose field
+ * grows outwards has mean = +1/R and gauss = 1/R^2.
+ * Level 0: fp32, s = +1, one float4 {mean, gauss, k1, k2} per vertex record in record order.
+ * Level 1: float64 (on the float64 shadow samples when bound), double[4] {mean, gauss, k1, k2} per vertex of cx_level1_download.
+ * For a vertex whose component the orientation step reversed, mean, k1 and k2 change sign and k1, k2 swap, so that k1 >= k2 still
+ * holds; gauss is unchanged.  Curvature then agrees with cx_level1_normals and the winding.
+ * Stream, buffer lifetime, delta3 and the error codes are those of the normals (CX_ERR_INVALID without an extraction or a post-pass,
+ * CX_ERR_UNSUPPORTED after cx_postprocess3d_mesh and the sharded post-pass; the selected level after cx_levels_select, the filtered
+ * mesh after cx_level1_keep_components).  Also CX_ERR_UNSUPPORTED: an axis with fewer than 3 samples, and a mesh that came through
+ * cx_level1_simplify (its vertices are cluster means, not crossings, and no curvature is carried over). */
+int cx_level0_curvature(cx_ctx* ctx, const double* delta3, void** curv_dev);
+int cx_level0_curvature_download(cx_ctx* ctx, const double* delta3, float* curv_mgk1k2);
+int cx_level1_curvature(cx_ctx* ctx, const double* delta3, void** curv_dev);
+int cx_level1_curvature_download(cx_ctx* ctx, const double* delta3, double* curv_mgk1k2);
+
 /* ---- components of the Level-1 mesh: labels, per-component measures, filtering -------------------------------------------------------
  * What a caller does with an isosurface of noisy data right after extracting it: how many pieces, how big is each, is it closed, and
  * drop the specks / keep the largest few.  The orientation step of the post-pass already finds the components (the reference orients
