@@ -444,7 +444,8 @@ class Context(object):
     def select_seeded(self, endpoints, voxel_range=None, all_in_range=False, parallel=False):
         """restrict the next post-passes to the components reached from `endpoints` (n x 2 x 3 lattice points);
         voxel_range = (lo[3], hi[3]) in_range box of the growth (default: the whole array);
-        -> dict(seed_voxels, groups_kept, triangles_kept)"""
+        -> dict(seed_voxels, groups_kept, triangles_kept); groups_kept: the connected groups of surface voxels inside the box that
+        are kept (a seed voxel outside the box is no group; with all_in_range: every group of the box)"""
         ep = np.ascontiguousarray(np.asarray(endpoints, dtype=np.int64).reshape(-1, 6), dtype=np.int32)
         out = np.zeros(4, dtype=np.int64)
         box = None

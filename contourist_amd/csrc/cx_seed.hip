@@ -321,7 +321,9 @@ __global__ __launch_bounds__(256) void cxs_k_keep(const uint4* cells, uint32_t n
             keep = (inr && (all_in_range || flag[parent[r]] != 0)) || seedkeep[r] != 0;
             // (counted per workgroup and added to one of 128 partial sums, each in a cache line of its own: one device-scope add per
             // kept voxel on ONE address -- same-address atomics execute one after the other -- was most of this kernel's 0.75 ms)
-            if (keep && parent[r] == r) atomicAdd(&s_groups, 1u);   // groups kept
+            // groups kept: the in-range groups reached (all of them with all_in_range); a group's root is one of its own, in-range
+            // records, and a seed voxel outside the box is kept but is no group
+            if (inr && parent[r] == r && (all_in_range || flag[r] != 0)) atomicAdd(&s_groups, 1u);
             if (keep) atomicAdd(&s_tris, ntri);
             atomicMin(&s_first, c.z);
             atomicMax(&s_end, c.z + ntri);

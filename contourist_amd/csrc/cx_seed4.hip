@@ -339,9 +339,20 @@ __global__ void cxs4_k_keep_sum(uint32_t* out) {
     __syncthreads();
     if (threadIdx.x == 0) out[3] += s;
 }
-__global__ void cxs4_k_count_groups(const uint32_t* parent, uint32_t ncells, const uint8_t* flag, uint32_t* out) {
+// out[2] = groups kept: the in-range groups reached (flags are only ever set on roots of in-range hyper-voxels), with all_in_range every
+// in-range group; a seed voxel outside the box is kept but is no group
+__global__ void cxs4_k_count_groups(const uint4* cells, const uint32_t* parent, uint32_t ncells, const uint8_t* flag, uint32_t* out, cxs4_grid G,
+                                    int all_in_range) {
     const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < ncells && parent[r] == r && flag[r]) atomicAdd(&out[2], 1u);
+    if (r >= ncells || parent[r] != r) return;
+    bool counts = flag[r] != 0;
+    if (!counts && all_in_range) {
+        const uint4 c = cells[r];
+        int p[4];
+        cxs4_unravel(G, c.x, p);
+        counts = cxs4_is_voxel_record(G, c) && cxs4_in_range(G, p);
+    }
+    if (counts) atomicAdd(&out[2], 1u);
 }
 
 extern "C" int cx_select_seeded4d(cx_ctx* ctx, const int32_t* endpoints_ijkl, int64_t n, int64_t* out_counts) {
@@ -413,7 +424,7 @@ extern "C" int cx_select_seeded4d_ex(cx_ctx* ctx, const int32_t* endpoints_ijkl,
             hipLaunchKernelGGL(cxs4_k_keep, dim3((nt + 255u) / 256u), dim3(256), 0, st, S4->cells, ncells, vmap, parent, flag, flag + ncells + 64, S4->tets, S4->vkeys, nt,
                                S4->tet_keep, out, G, all_in_range);
             hipLaunchKernelGGL(cxs4_k_keep_sum, dim3(1), dim3(CXS4_PARTIALS), 0, st, out);
-            hipLaunchKernelGGL(cxs4_k_count_groups, dim3(blocks), dim3(256), 0, st, parent, ncells, flag, out);
+            hipLaunchKernelGGL(cxs4_k_count_groups, dim3(blocks), dim3(256), 0, st, S4->cells, parent, ncells, flag, out, G, all_in_range);
         }
         CXS4_TRY(hipGetLastError());
         CXS4_TRY(hipMemcpyAsync(host_out, out, sizeof(host_out), hipMemcpyDeviceToHost, st));

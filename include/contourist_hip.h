@@ -209,6 +209,15 @@ int cx_rccl_comm_share(cx_ctx* ctx, cx_ctx* owner);
  * context's stream with the context's own communicator, enqueue cx_extract3d_async behind it.  (A 64-plane slab of a 512^3
  * volume is ~50 us of GPU time: the host side of a step has to be cheaper than that.) */
 int cx_slab_step(cx_ctx* ctx, float* local_planes, int64_t n_own, int64_t n1, int64_t n2, int rank, int world, double value, uint32_t flags);
+/* Seeded selection (tetrahedral.py:396-463): restricts the post-passes, until the next extraction, to the triangles of the voxel
+ * groups reached from the end points.  endpoints_ijk: n x 6 int32 lattice points (i0,j0,k0, i1,j1,k1) whose samples straddle the
+ * isovalue; range_lo_hi: lo[3], hi[3] of the in_range box, lo <= voxel < hi, clamped to the array (NULL: the whole array).
+ * out_counts (4 x int64): [0] seed voxels (slots looked at, with one thread per pair), [1] groups kept, [2] triangles kept,
+ * [3] rejected pairs (CX_ERR_INVALID: the context is then without a selection).
+ * Groups kept, here and in cx_select_seeded4d*: the number of connected groups (26 neighbours, 80 in 4-D) of surface voxels
+ * INSIDE the box, connected inside the box, that the selection keeps.  A seed voxel outside the box is kept and lets the groups it
+ * touches grow, but is itself no group.  With CX_SEED_ALL_IN_RANGE every group inside the box is kept, so that is their number,
+ * whatever the end points. */
 int cx_select_seeded3d(cx_ctx* ctx, const int32_t* endpoints_ijk, int64_t n, const int32_t* range_lo_hi, int64_t* out_counts);
 /* flags CX_SEED_ALL_IN_RANGE: every voxel inside range_lo_hi is kept (the exhaustive search_for_endpoints() of the
  * reference, tetrahedral.py:74-81) and the end points only add the seed voxels OUTSIDE it: the reference does not
@@ -543,7 +552,7 @@ int cx_counts4d_get(cx_ctx* ctx, cx_counts* out);
  * neighbours of pentatopes.py:32-39.  endpoints_ijkl: n x 8 int32 lattice points (i0,j0,k0,l0, i1,j1,k1,l1) whose
  * samples straddle the isovalue.  Call between cx_extract4d and cx_postprocess4d; restricts the post-pass (until the
  * next extraction) to the tetrahedra of the hyper-voxel groups reached.  out_counts (4 x int64): [0] seed voxels,
- * [1] groups kept, [2] tetrahedra kept, [3] rejected pairs (CX_ERR_INVALID). */
+ * [1] groups kept (as defined at cx_select_seeded3d), [2] tetrahedra kept, [3] rejected pairs (CX_ERR_INVALID). */
 int cx_select_seeded4d(cx_ctx* ctx, const int32_t* endpoints_ijkl, int64_t n, int64_t* out_counts);
 /* The same with the reference's in_range box (tetrahedral.py:465-469) given explicitly: range_lo_hi = lo[4], hi[4] in array
  * coordinates, lo <= hyper-voxel < hi (NULL: the whole array).  For an array that carries a rim of samples around the reference's

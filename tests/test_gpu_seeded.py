@@ -152,3 +152,302 @@ def test_many_seeds_take_the_parallel_path():
         assert got["triangles_kept"] == int(mask0.sum())
     finally:
         ctx.close()
+
+
+# ---- the selection against the restated search, boxes and all (fields, cases and the comparison: tests/seeded_cases.py) ----------
+# Every comparison is exact: kept triangles as sets of sorted edge-key triples, triangles_kept, the vertex mask == used by a kept
+# triangle, groups_kept and the seed kernel that ran (seeded_cases.run_case).
+
+def _field3():
+    import seeded_cases as sc
+    A, v = sc.field3d()
+    sc.assert_preconditions(A, v)            # no sample on the isovalue, >= 3 components, >= 2 of them across record blocks
+    return sc, A, v, sc.oracle_mesh(A, v)
+
+
+def _kept_sizes(r):
+    return sorted(n for n, k in r["groups"] if k)
+
+
+CUT6 = ((0, 0, 0), (6, 38, 41))              # the seed voxels of COLLIDING3 lie just outside: kept one by one, growing into one cap
+FULL3 = ((-3, -1, -9), (99, 41, 50))        # beyond the array on both sides: clamped, equals the default
+SHAPE3 = (40, 38, 41)
+
+
+@pytest.mark.parametrize("which", [(1306,), (1416,), (1036,), (194,), (1306, 194), (1416, 1036)])
+def test_components_from_far_end_points(which):
+    """far-apart end points (device bisection), some as (high, low), one pair twice: each component on its own and two together"""
+    sc, A, v, M = _field3()
+    eps = [sc.PAIRS3[n] if i % 2 == 0 else sc.flipped(sc.PAIRS3[n]) for i, n in enumerate(which)]
+    if which[0] in (1416, 194):
+        eps[0] = sc.flipped(eps[0])
+    eps.append(eps[0])
+    D = sc.DeviceMesh(A, v)
+    try:
+        r = sc.run_case(D, M, sc.case(eps))
+        assert _kept_sizes(r) == sorted(which) and len(r["surf"]) == sum(which)            # (the oracle: what the case is about)
+        assert not r["mismatches"], r["mismatches"]
+        assert r["got"]["groups_kept"] == len(which)
+    finally:
+        D.close()
+
+
+BOXES3 = {
+    "lo>0": dict(box=((6, 5, 7), SHAPE3), seeds=(1306, 1416), kept=2, fewer=True),
+    "hi<corner": dict(box=((0, 0, 0), (30, 38, 41)), seeds=(1416,), kept=1, fewer=True),      # through the 1416 sphere
+    "upper face": dict(box=((0, 0, 0), (36, 33, 19)), seeds=(1416,), kept=1, fewer=True),      # hi on the sphere's last voxels
+    "rod": dict(box=((0, 9, 9), (40, 14, 14)), eps=[[(11, 11, 11), (0, 11, 11)]], kept=1, groups=[(34, 0), (25, 25)]),
+    "beyond": dict(box=FULL3, seeds=(1306, 194), kept=2, same_as_default=True),
+    "empty": dict(box=((5, 5, 20), (30, 30, 20)), seeds=(1306, 1036), kept=0, only_seeds=True),
+    "rim": dict(box=((1, 1, 1), (38, 36, 39)), seeds=(1416, 1036, 194), kept=3),
+}
+
+
+@pytest.mark.parametrize("name", sorted(BOXES3))
+def test_in_range_boxes(name):
+    """voxel_range: lo > 0 on every axis, hi below the corner through a big sphere, a box that splits one sphere into two in-box
+    pieces of which one is seeded, a box beyond the array, an empty box (only the seed voxels), the one-voxel-rim box"""
+    from oracle import seeds
+    sc, A, v, M = _field3()
+    B = BOXES3[name]
+    eps = B.get("eps") or [sc.PAIRS3[n] for n in B["seeds"]]
+    c = sc.case(eps, B["box"])
+    D = sc.DeviceMesh(A, v)
+    try:
+        r = sc.run_case(D, M, c)
+        # what the case is about, from the oracle
+        free = seeds.reached(A, v, eps)
+        assert sum(1 for n, k in r["groups"] if k) == B["kept"]
+        if B.get("fewer"):
+            assert r["surf"] < free and len(r["surf"]) > 100
+        if B.get("groups"):
+            assert r["groups"] == B["groups"]
+        if B.get("same_as_default"):
+            assert r["surf"] == free
+        if B.get("only_seeds"):
+            assert r["surf"] == seeds.initial_voxels(A, v, eps) and 0 < int(r["want"].sum()) < 60
+        if name == "upper face":
+            hi = np.array(B["box"][1])
+            vox = np.array(sorted(r["surf"]))
+            assert all((vox[:, a] == hi[a] - 1).any() for a in range(3))      # kept voxels on every upper face: hi - 1 is in
+            assert all((np.array(sorted(free))[:, a] == hi[a]).any() for a in range(3))      # ... and hi itself is surface, left out
+        assert not r["mismatches"], r["mismatches"]
+    finally:
+        D.close()
+
+
+@pytest.mark.parametrize("all_in_range", (False, True))
+@pytest.mark.parametrize("side", ("hi", "lo"))
+def test_seed_voxels_outside_the_box(side, all_in_range):
+    """the seed voxels lie one step outside the box: kept, and they grow one step into it.  With ALL_IN_RANGE every surface voxel
+    of the box is kept as well, whatever its group."""
+    from oracle import seeds
+    sc, A, v, M = _field3()
+    eps = [[(28, 27, 12), (39, 27, 12)]] if side == "hi" else [[(28, 27, 12), (0, 27, 12)]]
+    start = np.array(sorted(seeds.initial_voxels(A, v, eps)))
+    if side == "hi":
+        box = ((0, 0, 0), (int(start[:, 0].min()), 38, 41))
+    else:
+        box = ((int(start[:, 0].max()) + 1, 0, 0), SHAPE3)
+    c = sc.case(eps, box, all_in_range=all_in_range)
+    D = sc.DeviceMesh(A, v)
+    try:
+        r = sc.run_case(D, M, c)
+        inside = seeds.in_box_surface(A, v, *box)
+        assert len(start) == 2 and not (set(map(tuple, start.tolist())) & inside)       # both seed voxels outside the box
+        assert set(map(tuple, start.tolist())) <= r["surf"]                              # kept all the same
+        grown = r["surf"] & inside
+        if all_in_range:
+            assert grown == inside and len(r["groups"]) >= 2 and all(k == n for n, k in r["groups"])
+            assert r["got"]["groups_kept"] == len(r["groups"])
+        else:
+            assert 100 < len(grown) < len(inside) and _kept_sizes(r) == [len(grown)]    # one in-box group, reached in one step
+            assert r["got"]["groups_kept"] == 1
+        assert not r["mismatches"], r["mismatches"]
+    finally:
+        D.close()
+
+
+def test_parallel_seed_kernel_where_the_choice_matters():
+    """CX_SEED_PARALLEL against the oracle without the shared visited set, on pairs that collide (the sequential oracle picks
+    another voxel there): with an empty box the kept triangles are exactly those of the seed voxels"""
+    sc, A, v, M = _field3()
+    empty = ((0, 0, 0), (0, 0, 0))
+    for box in (empty, CUT6):
+        ws, wp = M.select(sc.case(sc.COLLIDING3, box))[0], M.select(sc.case(sc.COLLIDING3, box, parallel=True))[0]
+        assert int(wp.sum()) < int(ws.sum()) and not (wp & ~ws).any()                    # the two oracles differ here
+    D = sc.DeviceMesh(A, v)
+    try:
+        for box in (empty, None, CUT6):
+            seq, par = sc.case(sc.COLLIDING3, box), sc.case(sc.COLLIDING3, box, parallel=True)
+            for c in (par, seq, par):
+                r = sc.run_case(D, M, c)
+                assert not r["mismatches"], (box, c["parallel"], r["mismatches"])
+        r = sc.run_case(D, M, sc.case(list(sc.PAIRS3.values()), None, parallel=True))       # far-apart pairs bisected per thread
+        assert _kept_sizes(r) == [194, 1036, 1306, 1416] and not r["mismatches"], r["mismatches"]
+    finally:
+        D.close()
+
+
+def test_more_than_65536_pairs_take_the_parallel_kernel_by_themselves():
+    sc, A, v, M = _field3()
+    short = sc.COLLIDING3 + [sc.PAIRS3[1036], sc.flipped(sc.PAIRS3[194])]
+    eps = (short * (65537 // len(short) + 1))[:65537]
+    c = sc.case(eps, CUT6)
+    ws, wp = M.select(dict(c, eps=short))[0], M.select(dict(c, eps=short, parallel=True))[0]
+    assert int(wp.sum()) < int(ws.sum())                                                 # the sequential kernel would keep more
+    D = sc.DeviceMesh(A, v)
+    try:
+        r = sc.run_case(D, M, dict(c, oracle=dict(shared_visited=False)))
+        assert D.ctx.seeded_mode() == "parallel" and len(eps) == 65537
+        assert np.array_equal(r["want"], wp) and not r["mismatches"], r["mismatches"]
+        r = sc.run_case(D, M, sc.case(eps[:65536], c["box"]))                            # one fewer: the reference's order
+        assert D.ctx.seeded_mode() == "sequential"
+        assert np.array_equal(r["want"], ws) and not r["mismatches"], r["mismatches"]
+    finally:
+        D.close()
+
+
+@pytest.mark.parametrize("name", ("uint8", "int16"))
+def test_typed_grids_against_the_oracle(name):
+    """8- and 16-bit samples read in their own type by the seed kernels: the mask equals the oracle's on the quantised values"""
+    sc, A, v, _ = _field3()
+    if name == "uint8":
+        q, value = np.clip(np.round(128 + 4 * A.astype(np.float64)), 0, 255).astype(np.uint8), 128.5
+    else:
+        q, value = np.round(100 * A.astype(np.float64)).astype(np.int16), 0.5
+    Q = q.astype(np.float64)
+    sizes = sc.assert_preconditions(Q, value)
+    M = sc.oracle_mesh(Q, value)
+    D = sc.DeviceMesh(q, value, native=True)
+    try:
+        assert D.ctx.grid_info()["dtype"] == name
+        eps = [sc.PAIRS3[1306], sc.flipped(sc.PAIRS3[194])]
+        cut = ((0, 0, 0), (40, 14, 41))                       # through the larger of the two
+        for c in (sc.case(eps), sc.case(eps, parallel=True), sc.case(eps, cut), sc.case(eps, cut, parallel=True)):
+            r = sc.run_case(D, M, c)
+            assert len(_kept_sizes(r)) == 2 and (c["box"] is None) == (_kept_sizes(r) == sorted([sizes[1], sizes[3]]))
+            assert not r["mismatches"], (c["parallel"], r["mismatches"])
+    finally:
+        D.close()
+
+
+def test_voxels_that_only_touch_the_isovalue_do_not_bridge_groups():
+    """DESIGN.md's deviation: one sample equal to the isovalue among higher ones, between two blobs.  The reference's border_voxel
+    bridges the groups (oracle, default rule: both blobs), the strict sign change does not (oracle, strict: one) -- the device
+    keeps the strict one's triangles"""
+    import seeded_cases as sc
+    A, v, pair = sc.bridge_field(3)
+    M = sc.oracle_mesh(A, v)
+    loose, strict = M.select(sc.case([pair])), M.select(sc.case([pair], strict=True))
+    assert int(loose[0].sum()) == 2 * int(strict[0].sum()) > 0 and strict[1] < loose[1]
+    D = sc.DeviceMesh(A, v)
+    try:
+        for parallel in (False, True):
+            r = sc.run_case(D, M, sc.case([pair], strict=True, parallel=parallel))
+            assert np.array_equal(r["want"], strict[0]) and r["groups"] == [(len(strict[1]), len(strict[1])), (len(strict[1]), 0)]
+            assert not r["mismatches"], r["mismatches"]
+    finally:
+        D.close()
+
+
+def test_no_end_points_and_an_empty_extraction():
+    from contourist_amd import _ffi
+    from oracle import seeds
+    sc, A, v, M = _field3()
+    D = sc.DeviceMesh(A, v)
+    try:
+        rod = BOXES3["rod"]["box"]
+        r = sc.run_case(D, M, sc.case([]))
+        assert not r["mismatches"] and r["got"] == dict(seed_voxels=0, groups_kept=0, triangles_kept=0, kept=0) and not r["mask"].any()
+        r = sc.run_case(D, M, sc.case([], rod))
+        assert not r["mismatches"] and r["got"]["triangles_kept"] == 0
+        r = sc.run_case(D, M, sc.case([], rod, all_in_range=True))                       # exactly the voxels of the box
+        assert r["surf"] == seeds.in_box_surface(A, v, *rod) and r["got"]["groups_kept"] == 2 and r["got"]["triangles_kept"] > 0
+        assert not r["mismatches"], r["mismatches"]
+        # an empty extraction: isovalue above every sample
+        counts = D.ctx.extract3d(float(A.max()) + 1.0, _ffi.CX_DIAG_CPYTHON310)
+        assert counts["n_triangles"] == 0 and counts["n_vertices"] == 0
+        for flags in (dict(), dict(all_in_range=True), dict(parallel=True), dict(voxel_range=rod)):
+            assert D.ctx.select_seeded([], **flags) == dict(seed_voxels=0, groups_kept=0, triangles_kept=0)
+            tk, vk = D.ctx.seeded_masks(counts)
+            assert len(tk) == 0 and len(vk) == 0
+    finally:
+        D.close()
+
+
+def test_a_rejected_call_leaves_the_context_without_a_selection():
+    from contourist_amd import _ffi
+    sc, A, v, M = _field3()
+    D = sc.DeviceMesh(A, v)
+    try:
+        good = sc.case([sc.PAIRS3[194]])
+        outside = [[(30, 10, 30), (30, 10, 41)]]             # k = 41 is not in the array
+        one_side = [[(0, 0, 0), (0, 37, 0)]]                 # both high
+        assert A[0, 0, 0] > v and A[0, 37, 0] > v
+        for bad in (outside, one_side, [sc.PAIRS3[1306]] + one_side, outside + [sc.PAIRS3[1306]]):
+            for parallel in (False, True):
+                r = sc.run_case(D, M, good)
+                assert not r["mismatches"] and not r["mask"].all()
+                with pytest.raises(_ffi.CxError) as e:
+                    D.ctx.select_seeded(bad, parallel=parallel)
+                assert e.value.code == -1
+                tk, vk = D.ctx.seeded_masks(D.counts)        # no selection: everything
+                assert tk.all() and vk.all() and len(tk) == D.counts["n_triangles"]
+        r = sc.run_case(D, M, sc.case([sc.PAIRS3[1036]], BOXES3["lo>0"]["box"]))
+        assert not r["mismatches"], r["mismatches"]
+    finally:
+        D.close()
+
+
+def test_one_context_sequential_parallel_boxes_and_a_4d_selection_in_between():
+    """the scratch buffers (seed_buf) are shared by all of these: every call gives the oracle's mask"""
+    sc, A, v, M = _field3()
+    A4, v4 = sc.field4d()
+    M4 = sc.oracle_mesh(A4, v4)
+    D = sc.DeviceMesh(A, v)
+    try:
+        far = list(sc.PAIRS3.values())
+        cases = [sc.case(far[:2]), sc.case(sc.COLLIDING3, BOXES3["empty"]["box"], parallel=True), sc.case(far[2:], BOXES3["rim"]["box"]),
+                 sc.case(far[1:3], BOXES3["hi<corner"]["box"], parallel=True), sc.case([far[3]], BOXES3["lo>0"]["box"], all_in_range=True),
+                 sc.case(far[:1])]
+        for c in cases[:3]:
+            r = sc.run_case(D, M, c)
+            assert not r["mismatches"], r["mismatches"]
+        D4 = sc.DeviceMesh(A4, v4, ctx=D.ctx)                # a 4-D extraction and selection on the same context
+        r4 = sc.run_case(D4, M4, sc.case([sc.PAIRS4[1238]], ((1, 1, 1, 1), (12, 13, 12, 6))))
+        assert not r4["mismatches"] and r4["got"]["tetrahedra_kept"] > 0, r4["mismatches"]
+        for c in cases[3:]:
+            r = sc.run_case(D, M, c)
+            assert not r["mismatches"], r["mismatches"]
+    finally:
+        D.close()
+
+
+def test_level1_after_a_boxed_selection_with_a_seed_outside_the_box():
+    """postprocess3d after a boxed selection == the oracle's Level 1 of the filtered Level-0 mesh (as
+    test_device_selection_equals_oracle does without a box)"""
+    from oracle import postpass, seeds
+    sc, A, v, M = _field3()
+    eps = [[(28, 27, 12), (39, 27, 12)], sc.PAIRS3[194]]
+    start = np.array(sorted(seeds.initial_voxels(A, v, eps[:1])))
+    box = ((0, 0, 0), (int(start[:, 0].min()), 38, 41))
+    D = sc.DeviceMesh(A, v)
+    try:
+        r = sc.run_case(D, M, sc.case(eps, box))
+        assert not r["mismatches"], r["mismatches"]
+        assert not (set(map(tuple, start.tolist())) & seeds.in_box_surface(A, v, *box)) and r["got"]["groups_kept"] == 2
+        want, O, ko = r["want"], M.O, M.keys
+        corner = np.array(A.shape) - 1
+        used = np.zeros(len(ko), dtype=bool)
+        used[O["tris"][want].ravel()] = True
+        renum = np.cumsum(used) - 1
+        L1 = postpass.level1_from_level0(ko[used], O["xyz"][used], renum[O["tris"][want]], corner)
+        post = D.ctx.postprocess3d(0)
+        pts, t1 = D.ctx.download_level1(post)
+        assert post["n_after_weld"] == L1["n_after_weld"] and post["n_after_tiny"] == L1["n_after_tiny"]
+        assert len(t1) == len(L1["triangles"]) > 0
+        cmp = postpass.compare_level1(L1, pts, t1, corner, reach=0)
+        assert not cmp["missing"] and not cmp["extra"] and not cmp["winding"]
+    finally:
+        D.close()

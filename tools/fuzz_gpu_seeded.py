@@ -1,53 +1,42 @@
 #!/usr/bin/env python3
-"""Randomised parity of the seeded selection (cx_select_seeded3d_ex: the two-step unions, the per-triangle keep kernel) on the GPU:
-random multi-component fields (several thousand surface voxels: many blocks of records, pairs across blocks), random seed segments
-taken from crossing edges, random in_range boxes -- the kept triangle mask against oracle/seeds.py.
-python tools/fuzz_gpu_seeded.py [seconds] [seed]"""
+"""Randomised parity of the seeded selections (cx_select_seeded3d_ex, cx_select_seeded4d_ex: the two-step unions, the keep kernels, both
+seed kernels) on the GPU: random multi-component fields of noisy spheres (several thousand surface voxels: many blocks of records, pairs
+across blocks), random far-apart end point pairs that the device has to bisect, random in_range boxes (now and then empty or beyond the
+array), now and then CX_SEED_ALL_IN_RANGE and the one-thread-per-pair seed kernel -- kept simplices, counts, vertex mask and groups_kept
+against oracle/seeds.py.  Fields, cases and the comparison are those of the test suite (tests/seeded_cases.py).
+python tools/fuzz_gpu_seeded.py [seconds] [seed] [3|4: dimension, default both in turn]"""
 import os, sys, time
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
-from contourist_amd import _ffi
-from oracle import level0, seeds
+import seeded_cases as sc
+from oracle import seeds
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = np.random.RandomState(int(sys.argv[2]) if len(sys.argv) > 2 else 17)
-t0 = time.time(); last_note = t0; ncase = 0; nbad = 0; ntri = 0
-ctx = _ffi.Context(0)
+dims = (int(sys.argv[3]),) if len(sys.argv) > 3 else (3, 4)
+t0 = time.time(); last_note = t0; ncase = 0; nbad = 0; nkept = 0; nfield = 0
 while time.time() - t0 < budget:
     if time.time() - last_note > 60.0:
         last_note = time.time()
         print("... %d cases, %d mismatches, %.0f s" % (ncase, nbad, time.time() - t0), flush=True)
-    shape = tuple(int(x) for x in rng.randint(18, 34, size=3))
-    A = rng.standard_normal(shape)
-    for _ in range(int(rng.randint(2, 5))):
-        for ax in range(3):
-            A = 0.25 * np.roll(A, 1, ax) + 0.5 * A + 0.25 * np.roll(A, -1, ax)
-    A = (A / max(A.std(), 1e-9)).astype(np.float32)
-    A += np.float32(1e-4) * rng.standard_normal(shape).astype(np.float32)      # (no sample equal to the isovalue)
-    v = float(np.float32(rng.uniform(-0.7, 0.7)))
-    ctx.upload_grid(A)
-    counts = ctx.extract3d(v, 1)
-    if counts["n_triangles"] < 50:
+    dim = dims[nfield % len(dims)]
+    A, v = sc.random_field(rng, dim)
+    sizes = [n for n, _ in seeds.groups(A, v, ())]
+    if np.any(A == v) or len(sizes) < 2 or not np.any(A < v):       # (no sample equal to the isovalue; more than one component)
         continue
-    xyz, keys, tris = ctx.download_level0(counts)
-    keys = keys.astype(np.int64)
-    lin, d = keys >> 3, keys & 7
-    q = np.stack([lin // (shape[1] * shape[2]), (lin // shape[2]) % shape[1], lin % shape[2]], axis=1)
-    dv = np.stack([(d >> 2) & 1, (d >> 1) & 1, d & 1], axis=1)
-    O = level0.march3d(A, v, diag_mode=1)
-    ko = level0.edge_keys_from_pairs(O["pairs"], A.shape)
-    order_o, order_d = np.argsort(ko), np.argsort(keys)
-    for trial in range(3):
-        pick = rng.choice(len(keys), size=int(rng.randint(1, 4)), replace=False)
-        eps = [[tuple(int(x) for x in q[p]), tuple(int(x) for x in q[p] + dv[p])] for p in pick]
-        want, _ = seeds.select(A, v, eps, ko, O["tris"])
-        got = ctx.select_seeded(eps)
-        tk, vk = ctx.seeded_masks(counts)
-        # compare as sets of key triples
-        kept_d = set(tuple(sorted(int(keys[i]) for i in t)) for t in np.asarray(tris)[tk])
-        kept_o = set(tuple(sorted(int(ko[i]) for i in t)) for t in np.asarray(O["tris"])[np.asarray(want, dtype=bool)])
-        ncase += 1; ntri += len(kept_o)
-        if got["triangles_kept"] != int(np.sum(want)) or kept_d != kept_o:
-            nbad += 1
-            print("MISMATCH shape", shape, "v", v, "eps", eps, got, int(np.sum(want)), flush=True)
-print("fuzz seeded selection: %d cases, %d triangles kept, %d mismatches, %.0f s" % (ncase, ntri, nbad, time.time() - t0))
+    nfield += 1
+    M = sc.OracleMesh(A, v)
+    D = sc.DeviceMesh(A, v)
+    try:
+        for trial in range(4):
+            c = sc.random_case(rng, A, v)
+            r = sc.run_case(D, M, c)
+            ncase += 1; nkept += int(r["want"].sum())
+            if r["mismatches"]:
+                nbad += 1
+                print("MISMATCH shape", A.shape, "components", sizes, "case", c, r["got"], r["mismatches"], flush=True)
+    finally:
+        D.close()
+print("fuzz seeded selection: %d cases on %d fields, %d simplices kept, %d mismatches, %.0f s" % (ncase, nfield, nkept, nbad, time.time() - t0))
 sys.exit(1 if nbad else 0)
