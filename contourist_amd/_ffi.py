@@ -66,6 +66,7 @@ SYMBOLS = [
     "cx_level1_components", "cx_level1_components_download", "cx_level1_component_labels", "cx_level1_component_labels_download", "cx_level1_keep_components",
     "cx_level1_topology", "cx_level1_topology_download", "cx_level1_boundary_loops", "cx_level1_boundary_loops_download",
     "cx_level1_simplify", "cx_level1_simplify_map", "cx_level1_simplify_map_download",
+    "cx_level1_clip_plane", "cx_level1_clip_scalars", "cx_level1_clip_map", "cx_level1_clip_map_download", "cx_level1_clip_info",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -117,6 +118,10 @@ CX_SIMPLIFY_ACROSS_COMPONENTS = 2
 CX_SIMPLIFY_COUNT_ONLY = 4
 CX_SIMPLIFY_NORMALS = 8
 SIMPLIFY_KEYS = ("n_vertices", "n_triangles", "n_components", "n_clusters", "cell", "clamped")
+CX_CLIP_NO_CLEAN = 1
+CX_CLIP_KEEP_BELOW = 2
+CX_CLIP_NORMALS = 4
+CLIP_KEYS = ("n_vertices", "n_triangles", "n_components", "n_cut_vertices", "n_cut_triangles", "n_nonfinite", "n_on_cut")
 CX2_ALL_CHAINS = 1
 CX2_NO_DEDUPE = 2
 CX2_SEARCH_SEEDS = 4
@@ -237,6 +242,11 @@ def load():
         "cx_level1_simplify": [vp, vp, ctypes.c_uint32, vp, vp],
         "cx_level1_simplify_map": [vp, ctypes.POINTER(vp)],
         "cx_level1_simplify_map_download": [vp, vp],
+        "cx_level1_clip_plane": [vp, vp, ctypes.c_uint32, vp],
+        "cx_level1_clip_scalars": [vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_uint32, vp],
+        "cx_level1_clip_map": [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)],
+        "cx_level1_clip_map_download": [vp, vp, vp],
+        "cx_level1_clip_info": [vp, vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -808,6 +818,74 @@ class Context(object):
         out = np.zeros(n_old, dtype=np.int32)
         self._check_attr(self.lib.cx_level1_simplify_map_download(self.handle, out.ctypes.data if n_old else None))
         return out
+
+    # ---- clipping of the Level-1 mesh by a plane or a per-vertex scalar (cx_clip.hip) --------------------------------------------
+    @staticmethod
+    def _clip_counts(out):
+        return dict(n_vertices=int(out[0]), n_triangles=int(out[1]), n_components=int(out[4]), n_cut_vertices=int(out[2]),
+                    n_cut_triangles=int(out[3]), n_nonfinite=int(out[5]), n_on_cut=int(out[6]), n_raw_triangles=int(out[7]))
+
+    def level1_clip_plane(self, normal, offset, flags=0):
+        """cx_level1_clip_plane: keep n.p >= offset (grid coordinates; n.p <= offset with CX_CLIP_KEEP_BELOW) -> dict(CLIP_KEYS
+        and n_raw_triangles, the triangles handed to the tail)"""
+        p4 = np.ascontiguousarray(np.concatenate([np.asarray(normal, dtype=np.float64).reshape(3), [float(offset)]]))
+        out = np.zeros(8, dtype=np.int64)
+        self._check_attr(self.lib.cx_level1_clip_plane(self.handle, p4.ctypes.data, int(flags), out.ctypes.data))
+        return self._clip_counts(out)
+
+    def level1_clip_scalars(self, scalars, threshold=0.0, flags=0):
+        """cx_level1_clip_scalars: `scalars` one value per Level-1 vertex, a numpy array (converted to float64) or a torch tensor
+        on the context's device; keeps scalars >= threshold -> the dict of level1_clip_plane"""
+        nv = self.level1_device_ptrs()[2]
+        out = np.zeros(8, dtype=np.int64)
+        if hasattr(scalars, "data_ptr"):
+            import torch
+            t = scalars.reshape(-1).to(torch.float64).contiguous()
+            if int(t.numel()) != nv:
+                raise ValueError("%d scalars for %d vertices" % (int(t.numel()), nv))
+            if t.is_cuda:
+                if t.device.index not in (None, self.device):
+                    t = t.to(torch.device("cuda", self.device))
+                torch.cuda.synchronize(t.device)
+                self._check_attr(self.lib.cx_level1_clip_scalars(self.handle, ctypes.c_void_p(t.data_ptr() if nv else 0), 1, float(threshold), int(flags),
+                                                                 out.ctypes.data))
+                return self._clip_counts(out)
+            scalars = t.numpy()
+        a = np.ascontiguousarray(np.asarray(scalars, dtype=np.float64).reshape(-1))
+        if len(a) != nv:
+            raise ValueError("%d scalars for %d vertices" % (len(a), nv))
+        self._check_attr(self.lib.cx_level1_clip_scalars(self.handle, ctypes.c_void_p(a.ctypes.data if nv else 0), 0, float(threshold), int(flags), out.ctypes.data))
+        return self._clip_counts(out)
+
+    def level1_clip_field(self, field, value=0.0, flags=0):
+        "clip by a second grid sampled at the vertices (cx_level1_sample_grid), the values staying on the device"
+        ptr, code, on_dev, keep = self._second_grid(field)
+        p = ctypes.c_void_p()
+        self._check_attr(self.lib.cx_level1_sample_grid(self.handle, ctypes.c_void_p(ptr), code, on_dev, ctypes.byref(p), None))
+        out = np.zeros(8, dtype=np.int64)
+        self._check_attr(self.lib.cx_level1_clip_scalars(self.handle, ctypes.c_void_p(p.value or 0), 1, float(value), int(flags), out.ctypes.data))
+        del keep
+        return self._clip_counts(out)
+
+    def level1_clip_map(self, device=False):
+        """(lo_hi (V',2) int32, t (V',) float64): per vertex of the clipped mesh the edge {lo, hi} of the mesh before the clip it lies
+        on and where (lo == hi, t == 0: a kept vertex); device=True: torch tensors on the GPU"""
+        lp, tp = ctypes.c_void_p(), ctypes.c_void_p()
+        self._check_attr(self.lib.cx_level1_clip_map(self.handle, ctypes.byref(lp), ctypes.byref(tp)))      # (none: the library's CX_ERR_STATE)
+        nv = self.level1_device_ptrs()[2]
+        if device:
+            import torch
+            return self._device_view(lp.value or 0, (nv, 2), "<i4", torch.int32), self._device_view(tp.value or 0, (nv,), "<f8", torch.float64)
+        lo_hi, t = np.zeros((nv, 2), dtype=np.int32), np.zeros(nv, dtype=np.float64)
+        self._check_attr(self.lib.cx_level1_clip_map_download(self.handle, lo_hi.ctypes.data if nv else None, t.ctypes.data if nv else None))
+        return lo_hi, t
+
+    def level1_clip_info(self):
+        "of the last clip: dict(kernels_ms, tail_ms, cut_corners, table_slots, n_vertices_before, n_triangles_before, n_raw_vertices, n_raw_triangles)"
+        info = np.zeros(8, dtype=np.float64)
+        self._check(self.lib.cx_level1_clip_info(self.handle, info.ctypes.data))
+        return dict(kernels_ms=float(info[0]), tail_ms=float(info[1]), cut_corners=int(info[2]), table_slots=int(info[3]), n_vertices_before=int(info[4]),
+                    n_triangles_before=int(info[5]), n_raw_vertices=int(info[6]), n_raw_triangles=int(info[7]))
 
     def surface_geometry(self, points, triangles, do_clean):
         pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3).copy()

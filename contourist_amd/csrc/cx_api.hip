@@ -52,6 +52,7 @@ extern "C" int cx_ctx_destroy(cx_ctx* ctx) {
     cx_comp_free(ctx);
     cx_topo_free(ctx);
     cx_simplify_free(ctx);
+    cx_clip_free(ctx);
     cx_state4_free(ctx);
     cx_state2_free(ctx);
     if (ctx->counters_host) (void)hipHostFree(ctx->counters_host);

@@ -169,6 +169,8 @@ struct cx_ctx {
     struct cx_simplify_state* simp = nullptr;
     // topology of the Level-1 mesh (cx_topo.hip): edge-use table, boundary loops and the table, kept between calls
     struct cx_topo_state* topo = nullptr;
+    // clipping of the Level-1 mesh (cx_clip.hip): bit masks, counts, the edge table of the cut band, the map, kept between calls
+    struct cx_clip_state* clip = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -304,6 +306,19 @@ int cx_level1_simplify_bufs(cx_ctx* ctx, bool normals, bool dry_run, cx_level1_s
 int cx_level1_simplify_tail(cx_ctx* ctx, uint32_t nv_old, uint32_t ncl, uint32_t nt, bool do_clean, bool normals, int64_t* counts);
 int cx_level1_carried_normals(cx_ctx* ctx, const double** nrm, uint32_t* nv);
 int cx_level1_simplify_map_get(cx_ctx* ctx, const int32_t** map, uint32_t* n);
+// what cx_clip.hip writes for the same tail: nv_raw points (the old vertices in their order, then the cut vertices), prio = the
+// vertex's place in that list, nt_raw triangles with tprio3 = {source triangle} x 3, all of them alive
+struct cx_level1_clip_io {
+    double* pts;
+    uint32_t* prio;
+    int32_t* tri;
+    uint32_t* tprio3;
+    uint8_t* alive;
+};
+int cx_level1_clip_bufs(cx_ctx* ctx, size_t nv_raw, size_t nt_raw, cx_level1_clip_io* out);
+int cx_level1_clip_tail(cx_ctx* ctx, uint32_t nv_raw, uint32_t nt_raw, bool do_clean, int64_t* counts);
+int cx_level1_clip_normals(cx_ctx* ctx, double** out);
+uint64_t cx_level1_generation(cx_ctx* ctx);
 // cx_comp.hip
 void cx_comp_free(cx_ctx* ctx);
 int cx_comp_labels_get(cx_ctx* ctx, const char* who, cx_level1_comp_view* V, const int32_t** tlab, const int32_t** vlab, uint32_t* nc);
@@ -311,6 +326,8 @@ int cx_comp_labels_get(cx_ctx* ctx, const char* who, cx_level1_comp_view* V, con
 void cx_topo_free(cx_ctx* ctx);
 // cx_simplify.hip
 void cx_simplify_free(cx_ctx* ctx);
+// cx_clip.hip
+void cx_clip_free(cx_ctx* ctx);
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);
 // cx_contour2d.hip

@@ -48,6 +48,7 @@ struct cx_post_state {
     cx_buf<uint8_t> nrm[2], nrm_tmp, smap;
     int nrm_cur = 0;
     bool simplified = false, carried = false, smap_valid = false;
+    bool clipped = false;             // the derived mesh came out of cx_level1_clip_* (cx_clip.hip): old vertices and cut vertices
     uint32_t smap_n = 0;
     struct {
         bool open = false;            // between cx_postprocess3d_shard_begin and _finish
@@ -1186,7 +1187,7 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
     S->keys_edge = false; S->orient_live = false; S->vflip_valid = false;
     S->shard_mesh = false; S->gen++; S->orient_nt = 0;
     S->shard.open = false;
-    S->simplified = false; S->carried = false; S->smap_valid = false;
+    S->simplified = false; S->carried = false; S->smap_valid = false; S->clipped = false;
     if (do_clean && nt) {
         u64* parent2 = S->parent2.as<u64>();
         hipLaunchKernelGGL(cxp_k_iota64, dim3(cx_blocks(nv)), dim3(256), 0, st, parent2, nv);
@@ -1920,7 +1921,8 @@ int cx_level1_attr_view(cx_ctx* ctx, const char* who, cx_level1_view* out) {
     if (!ctx->post || !ctx->post_valid || !ctx->post->keys_valid) { ctx->err = std::string(who) + ": no Level-1 mesh (run cx_postprocess3d first)"; return CX_ERR_INVALID; }
     cx_post_state* S = ctx->post;
     if (!S->keys_edge) {
-        ctx->err = std::string(who) + (S->simplified ? ": the vertices of a simplified mesh (cx_level1_simplify) are cluster means, not edge crossings of the resident array"
+        ctx->err = std::string(who) + (S->clipped ? ": the vertices of a clipped mesh (cx_level1_clip_*) are not all edge crossings of the resident array"
+                                       : S->simplified ? ": the vertices of a simplified mesh (cx_level1_simplify) are cluster means, not edge crossings of the resident array"
                                                      : ": the Level-1 vertices are not edge crossings of the resident array (a mesh handed to cx_postprocess3d_mesh, or a shard)");
         return CX_ERR_UNSUPPORTED;
     }
@@ -2117,6 +2119,53 @@ int cx_level1_simplify_map_get(cx_ctx* ctx, const int32_t** map, uint32_t* n) {
     }
     *map = S->smap.as<const int32_t>(); *n = S->smap_n;
     return CX_OK;
+}
+
+// ---- what the clip (cx_clip.hip) needs from the Level-1 state ---------------------------------------------------------------------------
+// Siblings of the two simplify calls for a mesh that GROWS: nv_raw = the old vertices and the cut vertices, nt_raw = the triangles the
+// clip emits (up to two per source triangle); every one of them is alive.  The buffers are the ones the post-pass starts from; the
+// resident mesh (pts_out, tri_out, keys_out and the tables of the orientation step) is not touched before the tail.
+int cx_level1_clip_bufs(cx_ctx* ctx, size_t nv_raw, size_t nt_raw, cx_level1_clip_io* out) {
+    cx_post_state* S = ctx->post;
+    int rc;
+    if ((rc = S->pts.grow(ctx, (nv_raw + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = S->prio.grow(ctx, (nv_raw + 1) * sizeof(uint32_t)))) return rc;
+    if ((rc = S->tri.grow(ctx, (nt_raw + 1) * 3 * sizeof(int32_t) * 2))) return rc;
+    if ((rc = S->alive.grow(ctx, nt_raw + 16))) return rc;
+    if ((rc = S->parent2.grow(ctx, (nv_raw + 1) * sizeof(u64)))) return rc;
+    out->pts = S->pts.as<double>();
+    out->prio = S->prio.as<uint32_t>();
+    out->tri = S->tri.as<int32_t>();
+    out->tprio3 = (uint32_t*)(out->tri + (nt_raw + 1) * 3);
+    out->alive = S->alive.as<uint8_t>();
+    return CX_OK;
+}
+// clean (optional), compaction, orientation with the windings taken as coherent: the kernels cxp_run3d ends with.  The result is a
+// derived mesh in the sense of the simplification (its keys are not edge ids); it carries no normals until cx_level1_clip_normals.
+int cx_level1_clip_tail(cx_ctx* ctx, uint32_t nv_raw, uint32_t nt_raw, bool do_clean, int64_t* counts) {
+    cx_post_state* S = ctx->post;
+    int rc;
+    uint32_t* tprio3 = (uint32_t*)(S->tri.as<int32_t>() + ((size_t)nt_raw + 1) * 3);
+    if ((rc = cxp_clean_orient(ctx, S, nv_raw, nt_raw, do_clean, true, tprio3, counts, true))) { ctx->post_valid = false; return rc; }
+    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    S->simplified = true; S->carried = false; S->clipped = true;
+    return CX_OK;
+}
+// room for the normals the clipped mesh carries (one per vertex of it, written by the caller on the context's stream)
+int cx_level1_clip_normals(cx_ctx* ctx, double** out) {
+    cx_post_state* S = ctx->post;
+    const int cur = S->nrm_cur;
+    const int rc = S->nrm[1 - cur].grow(ctx, ((size_t)S->nv_out + 1) * 3 * sizeof(double));
+    if (rc) return rc;
+    *out = S->nrm[1 - cur].as<double>();
+    S->nrm_cur = 1 - cur;
+    S->carried = true;
+    return CX_OK;
+}
+// the generation of the Level-1 mesh (0: there is none): what another translation unit caches belongs to one value of it
+uint64_t cx_level1_generation(cx_ctx* ctx) {
+    cx_post_state* S = ctx->post;
+    return (S && ctx->post_valid && S->keys_valid) ? S->gen : 0;
 }
 
 // ---- binary mesh files straight from the Level-1 device buffers (what every caller of the reference does next,

@@ -383,6 +383,41 @@ class GridContour3d(object):
         "(V_before,) int32: the new index of every vertex of the mesh before the last simplify(), -1 where it went away"
         return self.context().level1_simplify_map(getattr(self, "_simplify_n_old", 0), device)      # (none yet: the library's CX_ERR_STATE)
 
+    # -- clipping by a plane, a box or a scalar field on the device --------------------------------------------------------------
+    def clip(self, plane=None, box=None, field=None, scalars=None, value=0.0, keep="above", clean=True, normals="auto", mins=None, delta=None):
+        """cut the mesh open ON THE DEVICE (cx_level1_clip_*); exactly one of
+        plane=(normal3, offset): keeps n.p >= offset, in grid coordinates, or in world coordinates when mins / delta are given
+            (converted on the host: n_grid = n * delta, offset_grid = offset - n.mins);
+        box=(lo3, hi3): six plane clips in the fixed order -x, +x, -y, +y, -z, +z, stopping early when the mesh is empty; the counts
+            of cut vertices, cut triangles, non-finite and on-cut vertices are summed over them, and clip_map() then describes
+            the LAST of them only;
+        field=: a second grid of the samples' shape, scalars = vertex_values(field) kept on the device, keeps field >= value (not
+            available on a derived mesh -- after simplify() or clip());
+        scalars=: a (V,) array or device tensor, converted to float64, keeps scalars >= value.
+        keep="below" keeps the other side (not for a box).  Triangles the cut crosses are cut; a vertex exactly on the cut is not
+        duplicated.  normals: as for simplify().  Afterwards every reader gives the clipped mesh, whose boundary_loops() are the cut
+        curves; vertex_values() and vertex_curvature() raise NotImplementedError.
+        -> dict(n_vertices, n_triangles, n_components, n_cut_vertices, n_cut_triangles, n_nonfinite, n_on_cut)"""
+        spec = _clip_args(plane, box, field, scalars, keep, mins, delta)
+        ctx = self._ensure_post(clean)
+        if normals == "auto":
+            try:
+                self._attr_checks()
+                normals = bool(self._post.get("carried_normals", True))
+            except NotImplementedError:
+                normals = False
+        counts = _clip_on(ctx, spec, value, keep, clean, bool(normals))
+        self._post = dict(self._post, carried_normals=bool(normals), **{k: counts[k] for k in ("n_vertices", "n_triangles", "n_components")})
+        return counts
+
+    def clip_map(self, device=False):
+        "(lo_hi (V',2) int32, t (V',) float64) of the last clip(): output vertex i lies on the edge lo_hi[i] of the mesh before it, at t[i]"
+        return self.context().level1_clip_map(device)
+
+    def clip_values(self, values):
+        "a per-vertex array (numpy or torch) of the mesh before the last clip() carried across it: (1-t)*values[lo] + t*values[hi]"
+        return _clip_values(values, self.context())
+
     def write_mesh(self, path, fmt="ply", mins=None, delta=None, clean=True):
         """the welded, cleaned, oriented mesh as a binary file written STRAIGHT FROM THE DEVICE BUFFERS (cx_level1_write: no
         (points, triangles) arrays on the host) -- the step every caller of the reference takes next (html_demo.py:118-161).
@@ -501,6 +536,79 @@ def _simplify_on(ctx, cell, target_triangles, by_component, clean, normals, max_
     counts = ctx.level1_simplify(cell, flags | (_ffi.CX_SIMPLIFY_NORMALS if normals else 0))
     owner._simplify_n_old = int(n_old)
     return {k: counts[k] for k in _ffi.SIMPLIFY_KEYS}
+
+
+def _clip_args(plane, box, field, scalars, keep, mins=None, delta=None):
+    """the source of a clip() checked and brought into grid coordinates, before anything touches the device:
+    ("planes", [(normal3, offset), ...]) | ("field", field) | ("scalars", scalars)"""
+    given = [name for name, v in (("plane", plane), ("box", box), ("field", field), ("scalars", scalars)) if v is not None]
+    if len(given) != 1:
+        raise ValueError("exactly one of plane, box, field and scalars is needed (got %s)" % (", ".join(given) or "none"))
+    if keep not in ("above", "below"):
+        raise ValueError('keep must be "above" or "below"')
+    d = np.ones(3) if delta is None else np.asarray(delta, dtype=np.float64).reshape(3)
+    m = np.zeros(3) if mins is None else np.asarray(mins, dtype=np.float64).reshape(3)
+
+    def to_grid(n, offset):
+        n = np.asarray(n, dtype=np.float64).reshape(3)
+        offset = float(offset)
+        if not (np.all(np.isfinite(n)) and np.isfinite(offset)) or not np.any(n != 0.0):
+            raise ValueError("a plane needs a finite normal that is not zero and a finite offset")
+        return n * d, offset - float(np.dot(n, m))
+    if plane is not None:
+        normal, offset = plane
+        return "planes", [to_grid(normal, offset)]
+    if box is not None:
+        if keep != "above":
+            raise ValueError('a box keeps its inside: keep="below" is not available for it')
+        lo, hi = (np.asarray(x, dtype=np.float64).reshape(3) for x in box)
+        planes = []
+        for a in range(3):
+            e = np.zeros(3)
+            e[a] = 1.0
+            planes.append(to_grid(e, lo[a]))
+            planes.append(to_grid(-e, -hi[a]))
+        return "planes", planes
+    return ("field", field) if field is not None else ("scalars", scalars)
+
+
+def _clip_on(ctx, spec, value, keep, clean, normals):
+    "clip() of the three isosurface classes on the context that holds the mesh"
+    flags = (0 if clean else _ffi.CX_CLIP_NO_CLEAN) | (_ffi.CX_CLIP_KEEP_BELOW if keep == "below" else 0) | (_ffi.CX_CLIP_NORMALS if normals else 0)
+    kind, what = spec
+    if kind == "field":
+        counts = ctx.level1_clip_field(what, value, flags)
+    elif kind == "scalars":
+        counts = ctx.level1_clip_scalars(what, value, flags)
+    else:
+        counts = None
+        for n, offset in what:
+            c = ctx.level1_clip_plane(n, offset, flags)
+            if counts is not None:
+                for k in ("n_cut_vertices", "n_cut_triangles", "n_nonfinite", "n_on_cut"):
+                    c[k] += counts[k]
+            counts = c
+            if counts["n_triangles"] == 0:
+                break
+    return {k: counts[k] for k in _ffi.CLIP_KEYS}
+
+
+def _clip_values(values, ctx):
+    "(1 - t) * values[lo] + t * values[hi] over the map of the last clip; a torch tensor on the device stays there"
+    if hasattr(values, "data_ptr"):
+        lo_hi, t = ctx.level1_clip_map(device=values.is_cuda)
+        if not values.is_cuda:
+            import torch
+            lo_hi, t = torch.from_numpy(lo_hi), torch.from_numpy(t)
+        lo, hi = lo_hi[:, 0].long(), lo_hi[:, 1].long()
+        t = t.to(values.dtype) if values.dtype.is_floating_point else t
+    else:
+        values = np.asarray(values)
+        lo_hi, t = ctx.level1_clip_map()
+        lo, hi = lo_hi[:, 0], lo_hi[:, 1]
+    if values.ndim > 1:
+        t = t.reshape((-1,) + (1,) * (values.ndim - 1))
+    return (1.0 - t) * values[lo] + t * values[hi]
 
 
 def unpack_edge_ids(keys, shape):
@@ -702,6 +810,21 @@ class Delta3DContour(object):
     def simplify_map(self, device=False):
         "GridContour3d.simplify_map"
         return self.contour_maker.simplify_map(device)
+
+    def clip(self, plane=None, box=None, field=None, scalars=None, value=0.0, keep="above", clean=True, normals="auto", mins=None, delta=None):
+        """GridContour3d.clip of this isosurface; plane and box are in WORLD coordinates (the grid's mins and delta, unless mins /
+        delta are given), field an array of the grid's shape (grid_dimensions + 1)"""
+        mins = self.grid.mins if mins is None else mins
+        delta = self.grid.delta if delta is None else delta
+        return self.contour_maker.clip(plane, box, field, scalars, value, keep, clean, normals, mins, delta)
+
+    def clip_map(self, device=False):
+        "GridContour3d.clip_map"
+        return self.contour_maker.clip_map(device)
+
+    def clip_values(self, values):
+        "GridContour3d.clip_values"
+        return self.contour_maker.clip_values(values)
 
     def vertex_normals(self, clean=True, device=False):
         """(V,3) float64 unit normals in WORLD coordinates (the gradient per axis divided by delta, normalised); row i belongs
@@ -928,6 +1051,27 @@ class LevelResult(tuple):
     def simplify_map(self, device=False):
         "GridContour3d.simplify_map for the level's mesh"
         return self._ctx().level1_simplify_map(getattr(self, "_simplify_n_old", 0), device)
+
+    def clip(self, plane=None, box=None, field=None, scalars=None, value=0.0, keep="above", clean=True, normals="auto", mins=None, delta=None):
+        """GridContour3d.clip on the level's mesh; plane and box in WORLD coordinates (the level's mins and delta, unless mins / delta
+        are given).  The tuple's own points and triangles are the unclipped ones: mesh() downloads the clipped mesh"""
+        mins = self._mins if mins is None else mins
+        delta = self._delta if delta is None else delta
+        spec = _clip_args(plane, box, field, scalars, keep, mins, delta)
+        ctx = self._ctx()
+        if normals == "auto":
+            normals = bool(self._post.get("carried_normals", True))
+        counts = _clip_on(ctx, spec, value, keep, clean, bool(normals))
+        self._post = dict(self._post, carried_normals=bool(normals), **{k: counts[k] for k in ("n_vertices", "n_triangles", "n_components")})
+        return counts
+
+    def clip_map(self, device=False):
+        "GridContour3d.clip_map for the level's mesh"
+        return self._ctx().level1_clip_map(device)
+
+    def clip_values(self, values):
+        "GridContour3d.clip_values for the level's mesh"
+        return _clip_values(values, self._ctx())
 
     def mesh(self):
         "(world points, sorted triangle rows) of the level's mesh as it stands on the device (after keep_components or simplify: that one)"

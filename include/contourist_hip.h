@@ -520,6 +520,64 @@ int cx_level1_simplify(cx_ctx* ctx, const double* cell3, uint32_t flags, int64_t
 int cx_level1_simplify_map(cx_ctx* ctx, void** new_index_of_old_vertex_dev);
 int cx_level1_simplify_map_download(cx_ctx* ctx, int32_t* new_index_of_old_vertex);
 
+/* ---- clipping: cut the Level-1 mesh open by a plane or a per-vertex scalar, on the device ------------------------------------------
+ * What a viewer or a measurement script does most often with an isosurface: keep the half in front of a plane, a region of interest,
+ * or the part where a second volume is above a threshold.  cx_level1_keep_components only drops whole components; this cuts triangles.
+ * (No counterpart in the reference.)
+ * Input: the current unsharded Level-1 mesh (V vertices, T triangles in device order, every triangle with three distinct indices) and
+ * one float64 scalar s[v] per vertex.  d[v] = s[v] - threshold, or threshold - s[v] with CX_CLIP_KEEP_BELOW.  A vertex is INSIDE iff
+ * d[v] is finite and d[v] >= 0.
+ *   - A triangle with a vertex whose d is not finite is dropped whole and counted (n_nonfinite).
+ *   - Three vertices inside: the triangle is kept unchanged.  None inside: dropped.
+ *   - One inside.  Rotate the corners, keeping the cyclic order, so that corner i is inside and j, k follow: one triangle
+ *     (v_i, c(i,j), c(i,k)).
+ *   - Two inside.  Rotate so that i is the outside corner: two triangles, (c(j,i), v_j, v_k) and (c(j,i), v_k, c(k,i)).  The diagonal
+ *     is fixed by this rule and never looks at a neighbour.
+ *   - c(a,b), with a inside and b outside: if d[a] == 0 it IS vertex a and no new vertex is made.  Otherwise it is the cut vertex of the
+ *     undirected edge {lo, hi} = {min(a,b), max(a,b)}: one such vertex per mesh edge, shared by every triangle on that edge, at
+ *         t = d[lo] / (d[lo] - d[hi]),   p = p[lo] + t * (p[hi] - p[lo])   per coordinate,
+ *     every operation rounded once (no fused multiply-add), so numpy reproduces the bits.
+ *   - Triangles left with two equal indices are dropped.
+ * The vertex list handed to the tail is the V old vertices in their order, then the cut vertices, ordered by the smallest corner
+ * number 3t+k among the triangle edges (edge k joins corners k and (k+1)%3) that cut that mesh edge.  The key of an old vertex is its
+ * old index, the key of cut vertex r is V + r (cx_level1_download_keys).  Output triangles come in source-triangle order, the first of
+ * a pair before the second; their priority triple is {t, t, t} of the source triangle, as the simplifier's.
+ * Then comes the shared tail, exactly as after cx_level1_simplify: the reference's clean_triangles rule unless CX_CLIP_NO_CLEAN
+ * (bit 0), compaction of the vertices in use, orientation with the windings taken as coherent.
+ * CX_CLIP_NORMALS: an old vertex keeps its normal -- cx_level1_normals(delta3 == NULL) of the source, or its carried normals if the
+ * source is itself a derived mesh; a cut vertex gets normalize((1 - t) * n[lo] + t * n[hi]), (0,0,0) for a zero sum, each operation
+ * rounded once.  Allowed only where cx_level1_normals is served for the source (CX_ERR_UNSUPPORTED elsewhere, the mesh untouched).
+ * The map has one record {lo, hi, t} per OUTPUT vertex, holding indices of the mesh before the call: lo == hi and t == 0 for a kept
+ * vertex.  A caller carries any per-vertex attribute a of their own across the cut with it: (1 - t) * a[lo] + t * a[hi].
+ * cx_level1_clip_plane: s = n0*x + n1*y + n2*z in grid coordinates, evaluated left to right with every operation rounded once;
+ * plane4 = {n0, n1, n2, threshold}.  A zero or non-finite normal (or a non-finite threshold) gives CX_ERR_INVALID.
+ * cx_level1_clip_scalars: the general entry; V doubles on the host, or on the device when on_device != 0 (the buffer
+ * cx_level1_sample_grid returns may be handed over as it is).
+ * out_counts (8 x int64): [0] vertices, [1] triangles, [2] cut vertices, [3] source triangles that were cut, [4] components,
+ * [5] n_nonfinite (source triangles dropped for a non-finite d), [6] vertices with d == 0, [7] triangles handed to the tail (an upper
+ * bound on [1]).
+ * After a clip the mesh is a derived one in the sense of the simplification: cx_level1_normals serves the carried normals
+ * (CX_ERR_UNSUPPORTED when the clip ran without CX_CLIP_NORMALS), cx_level1_sample_grid and cx_level1_curvature answer
+ * CX_ERR_UNSUPPORTED, the simplify map is invalid.  The clip map is valid until the next post-pass, filter, simplification or clip
+ * (CX_ERR_STATE then); its device pointers are (V', 2) int32 and (V',) float64.  Components, topology and boundary loops are
+ * rebuilt on the next request; the boundary loops of a clipped closed surface are its cut curves.
+ * Errors: CX_ERR_INVALID without a Level-1 mesh, with unknown flags or a bad plane; CX_ERR_UNSUPPORTED after
+ * cx_postprocess3d_shard_*, for 2^30 triangles or more, and for CX_CLIP_NORMALS on a source without normals; CX_ERR_STATE when the
+ * tables of the orientation step are gone.  A call that fails before the tail starts leaves the mesh bit for bit as it was.  All
+ * buffers belong to the context (counted by cx_device_bytes) and are reused; the edge table is sized by the number of cut corners,
+ * not by the mesh.  Reproducible: every output array is the same bit for bit in every call and context.
+ * cx_level1_clip_info (measurement): of the last clip on this context, info8 = {ms of the clip kernels, ms of the tail with the
+ * map, cut corners, slots of the edge table, V, T, vertices handed to the tail, triangles handed to the tail}, the times between
+ * HIP events on the context's stream; CX_ERR_STATE when none has run. */
+#define CX_CLIP_NO_CLEAN    1u   /* bit 0, as cx_postprocess3d */
+#define CX_CLIP_KEEP_BELOW  2u
+#define CX_CLIP_NORMALS     4u
+int cx_level1_clip_plane(cx_ctx* ctx, const double* plane4, uint32_t flags, int64_t* out_counts8);
+int cx_level1_clip_scalars(cx_ctx* ctx, const double* scalars, int on_device, double threshold, uint32_t flags, int64_t* out_counts8);
+int cx_level1_clip_map(cx_ctx* ctx, void** lo_hi_dev, void** t_dev);
+int cx_level1_clip_map_download(cx_ctx* ctx, int32_t* lo_hi, double* t);
+int cx_level1_clip_info(cx_ctx* ctx, double* info8);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
