@@ -336,7 +336,13 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
         // the triangle stage walks the vertex stage's cell records.  The kernel that walks queue entries instead (no records: 80 MB
         // less HBM traffic per 512^3 extraction) is built and bit-identical, and measured no faster at 512^3 and slower on thin slabs
         // (DESIGN.md section 4): it runs on request (CX_DEBUG=1 CX_K2_ENTRIES=1)
-        P.write_records = (!fused && !tiled && !cx_debug_knob("CX_K2_ENTRIES", 0u)) ? 1u : 0u;
+        // Its records are the slim ones (8 bytes + {first triangle, first vertex} per 64 records: half the 128 MB round trip of
+        // the full ones at 512^3); whoever wants full records afterwards gets them from cx_ensure_cell_records.
+        P.write_records = (!fused && !tiled && !cx_debug_knob("CX_K2_ENTRIES", 0u)) ? (CX_SLIM_RECORDS ? CX_RECORDS_SLIM : CX_RECORDS_FULL) : CX_RECORDS_NONE;
+        if (P.write_records == CX_RECORDS_SLIM) {
+            if ((rc = ctx->cbase.grow(ctx, (size_t)ctx->ccap() / 64u + 1u))) return rc;
+            P.cbase = ctx->cbase;
+        }
         if (tiled) {
             P.qa = nullptr;       // nobody gathers the queue words: the stream kernel does not store them
             if ((rc = ctx->fj.grow(ctx, (size_t)P.n0 * (4u * T.njg) * P.n2 + 64u))) return rc;
@@ -358,15 +364,10 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
     ctx->last_task = T;
     ctx->last_flags = flags;
     ctx->path = staged ? (fused ? 2 : (tiled ? 3 : 1)) : 0;
-    ctx->records_valid = staged ? (P.write_records != 0u) : true;   // the generic path always writes them
+    ctx->records_valid = staged ? (P.write_records == CX_RECORDS_FULL) : true;   // the generic path always writes the full records
     cx_ctx::evset* ev = nullptr;
-    if (ctx->timing) {
-        if (ctx->nevents < (int)(sizeof(ctx->events) / sizeof(ctx->events[0]))) {
-            ev = &ctx->events[ctx->nevents++];
-            for (int n = 0; n < 5; n++)
-                if (!ev->e[n]) CX_HIP(ctx, hipEventCreate(&ev->e[n]));
-        }
-    }
+    if (ctx->timing && ctx->nevents < (int)(sizeof(ctx->events) / sizeof(ctx->events[0])) && ctx->events[ctx->nevents].e[4])
+        ev = &ctx->events[ctx->nevents++];     // (made by cx_timing_enable: no hipEventCreate here; extractions beyond the pool go untimed)
     // the generic kernel accumulates into the counters; the staged pipeline's scan kernel writes all of them
     if (!staged || (flags & CX_DBG_PHASE_A_ONLY))
         CX_HIP(ctx, hipMemsetAsync(ctx->counters, 0, CX_CNT_WORDS * sizeof(uint32_t), ctx->stream));
@@ -468,7 +469,7 @@ int cx_ensure_cell_records(cx_ctx* ctx) {
     if (ctx->records_valid) return CX_OK;
     cx_params P = ctx->last;
     P.flags |= CX_DBG_NO_VERTS | CX_DBG_NO_CELLTAB;
-    P.write_records = 1u;
+    P.write_records = CX_RECORDS_FULL;   // over the slim ones of the default path, which the triangle stage is done with (same stream)
     P.ccap = ctx->ccap(); P.cells = ctx->cells;
     cx_launch_emit_vertices(P, ctx->last_task, ctx->stream);
     CX_HIP(ctx, hipGetLastError());
@@ -619,8 +620,16 @@ extern "C" int cx_measure_read_bandwidth(cx_ctx* ctx, const void* device_ptr, in
 
 extern "C" int cx_timing_enable(cx_ctx* ctx, int on) {
     if (!ctx) return CX_ERR_INVALID;
-    ctx->timing = on != 0;
     ctx->nevents = 0;
+    ctx->timing = false;
+    if (!on) return CX_OK;
+    // every event the pool can hand out, once per context: none is created while extracting (the first timed steps of a context
+    // paid up to five hipEventCreate each).  They only measure time: no system-scope fence where one is recorded.
+    CX_HIP(ctx, hipSetDevice(ctx->device));
+    for (auto& ev : ctx->events)
+        for (int n = 0; n < 5; n++)
+            if (!ev.e[n]) CX_HIP(ctx, hipEventCreateWithFlags(&ev.e[n], hipEventDisableSystemFence));
+    ctx->timing = true;
     return CX_OK;
 }
 

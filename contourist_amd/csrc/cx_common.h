@@ -159,7 +159,9 @@ struct cx_params {
     uint32_t qlimit;          // queue entries a streaming wave may store (T.wcap; less when levels share a pool)
     uint32_t* kstart;         // [nkw] triangle stage: the batch in which wave m's share of the rounds starts (as rstart for the vertex stage)
     uint32_t nkw;             // waves of the triangle stage (4 x its grid)
-    uint32_t write_records;   // 1: the vertex stage also writes the 16-byte cell records (seeded selection, the record-walking triangle kernel)
+    uint32_t write_records;   // the vertex stage also writes cell records: CX_RECORDS_FULL the 16-byte ones (seeded selection, levels), CX_RECORDS_SLIM
+                              // the 8-byte ones {lin, sign|tetskip<<8|ntri<<16|emask<<24} of the record-walking triangle kernel, in the front half of `cells`
+    uint2* cbase;             // [ccap / 64 + 1] slim records: {first triangle, first vertex} of record 64 g (the others: + the prefixes of their 64-group)
     // the stream of interpolation fractions (round 4): the stream kernel, which has the samples, computes t = (v - f(q)) / (f(q+d) - f(q))
     // of every crossing and writes them per streaming wave in the order the vertex stage numbers the vertices; the vertex stage reads
     // them back in order instead of gathering samples from half of the grid's cache lines.  null: the vertex stage gathers (levels, fused).
@@ -174,6 +176,11 @@ struct cx_params {
     uint32_t* torder;         // [3][2 nblocks] half tiles by class of work (most queue entries first; empty ones in none), filled by the scan kernel
     uint32_t tile_cap;        // info words a workgroup of the tile kernel holds in LDS (queue entries of its tile + the next chunk's first plane)
 };
+enum { CX_RECORDS_NONE = 0, CX_RECORDS_FULL = 1, CX_RECORDS_SLIM = 2 };
+// the default staged path hands 8-byte cell records from the vertex to the triangle stage (host side, cx_api.hip; 0: the 16-byte ones, for A/B builds)
+#ifndef CX_SLIM_RECORDS
+#define CX_SLIM_RECORDS 1
+#endif
 #ifndef CX_SWP
 #define CX_SWP 16u            // plane slots per streaming wave: cell planes per task (ci) + 1, ci <= 15
 #endif

@@ -108,6 +108,7 @@ struct cx_ctx {
     cx_buf<float> tq;               // staged kernels: the stream kernel's interpolation fractions, one region per streaming wave (cx_params::tq)
     cx_buf<uint64_t> info64;        // staged kernels: per queue entry, (crossing mask << 32) | first vertex
     cx_buf<uint32_t> chunksum;      // totals of every 256 streaming waves (cx_params::chunksum)
+    cx_buf<uint2> cbase;           // slim cell records: {first triangle, first vertex} of every 64th record (cx_params::cbase)
     cx_buf<uint32_t> rstart;        // vertex stage: first batch of every wave's share of the rounds (cx_params::rstart)
     cx_buf<uint32_t> kstart;        // the same for the triangle stage (cx_params::kstart)
     cx_buf<uint64_t> fj;            // tile emit path: face words (cx_params::fj, fk), boundary records and their counts per tile
@@ -183,6 +184,7 @@ struct cx_ctx {
     void* xfer_stage[2] = {nullptr, nullptr};
     hipEvent_t xfer_ev[2] = {nullptr, nullptr};
     // timing
+    // one set of five markers per timed extraction, all made by cx_timing_enable (never while extracting)
     struct evset { hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; };
     bool timing = false;
     int nevents = 0;

@@ -56,6 +56,20 @@ __device__ __forceinline__ uint64_t cx_info_word(uint32_t vfirst, uint32_t emask
     return (uint64_t)vfirst | ((uint64_t)((emask & 0xFFu) | ((ntri & 0xFu) << 8) | ((tetskip & 0x3Fu) << 12)) << 32);
 }
 
+// the record of one cell, at place `at` of the record array.  Full: 16 bytes {lin, word, first triangle, first vertex}.  Slim
+// (P.write_records == CX_RECORDS_SLIM, the record-walking triangle kernel of the staged pipeline): 8 bytes {lin, word} in the front
+// half of the same allocation; the two running numbers of every 64th record go to P.cbase, and the triangle kernel -- whose waves
+// take 64 consecutive records from a multiple of 64 -- adds the prefixes of ntri and popc(emask) inside the group: records, vertices
+// and triangles are all numbered along the flat batch list.
+__device__ __forceinline__ void cx_store_cell_record(const cx_params& P, uint32_t at, uint32_t lin, uint32_t word, uint32_t tfirst, uint32_t vfirst) {
+    if (P.write_records == CX_RECORDS_SLIM) {   // uniform
+        reinterpret_cast<uint2*>(P.cells)[at] = make_uint2(lin, word);
+        if ((at & 63u) == 0u) P.cbase[at >> 6] = make_uint2(tfirst, vfirst);
+    } else {
+        P.cells[at] = make_uint4(lin, word, tfirst, vfirst);
+    }
+}
+
 // ---- per-cell path ------------------------------------------------------------------------------
 struct cx_run {
     uint32_t v, t, c, b;   // running vertex / triangle / cell-record / border-voxel counts
@@ -119,12 +133,7 @@ __device__ __forceinline__ void cx_process_queue(const cx_params& P, LinOf lin_o
                 else if (nv && !(P.flags & CX_DBG_NO_CELLTAB)) P.celltab[lin] = ((uint64_t)R.emask << 32) | (uint64_t)vfirst;
             }
             if (RECORDS && (P.write_records || !info) && rec && run.c + ctot <= P.ccap && !(P.flags & CX_DBG_NO_CELLS)) {
-                uint4 c4;
-                c4.x = lin;
-                c4.y = sm | (R.tetskip << 8) | (R.ntri << 16) | (R.emask << 24);
-                c4.z = run.t + tpre;
-                c4.w = vfirst;
-                P.cells[run.c + cx_mbcnt(recm)] = c4;
+                cx_store_cell_record(P, run.c + cx_mbcnt(recm), lin, sm | (R.tetskip << 8) | (R.ntri << 16) | (R.emask << 24), run.t + tpre, vfirst);
             }
         }
         run.v += vtot; run.t += ttot; run.c += ctot; run.b += btot;
@@ -366,12 +375,8 @@ __device__ __forceinline__ void cx_emit_queue_fast(const cx_params& P, const cx_
                 info[b0 + lane] = cx_info_word(Ra.base.v + Ra.vpre, Ra.emask, Ra.ntri, Ra.real_voxel ? 0u : 0x3Fu);
         }
         if (P.write_records && (Ra.emask | Ra.ntri) != 0u && Ra.base.c + Ra.ctot <= P.ccap && !(P.flags & CX_DBG_NO_CELLS)) {
-            uint4 c4;
-            c4.x = Ra.lin;
-            c4.y = Ra.sm | ((Ra.real_voxel ? 0u : 0x3Fu) << 8) | (Ra.ntri << 16) | (Ra.emask << 24);
-            c4.z = Ra.base.t + Ra.tpre;
-            c4.w = Ra.base.v + Ra.vpre;
-            P.cells[Ra.base.c + cx_mbcnt(Ra.recm)] = c4;
+            cx_store_cell_record(P, Ra.base.c + cx_mbcnt(Ra.recm), Ra.lin, Ra.sm | ((Ra.real_voxel ? 0u : 0x3Fu) << 8) | (Ra.ntri << 16) | (Ra.emask << 24),
+                                 Ra.base.t + Ra.tpre, Ra.base.v + Ra.vpre);
         }
         __builtin_amdgcn_wave_barrier();
 #if !CX_PIN_BEFORE_STORES
@@ -475,12 +480,8 @@ __device__ __forceinline__ void cx_emit_queue_t(const cx_params& P, const cx_fas
                 info[b0 + lane] = cx_info_word(Ra.base.v + Ra.vpre, Ra.emask, Ra.ntri, Ra.real_voxel ? 0u : 0x3Fu);
         }
         if (P.write_records && (Ra.emask | Ra.ntri) != 0u && Ra.base.c + Ra.ctot <= P.ccap && !(P.flags & CX_DBG_NO_CELLS)) {
-            uint4 c4;
-            c4.x = Ra.lin;
-            c4.y = Ra.sm | ((Ra.real_voxel ? 0u : 0x3Fu) << 8) | (Ra.ntri << 16) | (Ra.emask << 24);
-            c4.z = Ra.base.t + Ra.tpre;
-            c4.w = Ra.base.v + Ra.vpre;
-            P.cells[Ra.base.c + cx_mbcnt(Ra.recm)] = c4;
+            cx_store_cell_record(P, Ra.base.c + cx_mbcnt(Ra.recm), Ra.lin, Ra.sm | ((Ra.real_voxel ? 0u : 0x3Fu) << 8) | (Ra.ntri << 16) | (Ra.emask << 24),
+                                 Ra.base.t + Ra.tpre, Ra.base.v + Ra.vpre);
         }
         __builtin_amdgcn_wave_barrier();
         if (more) cx_tround_pin(Rb);   // the next round's fractions are waited for AFTER this round's stores went out
@@ -1680,10 +1681,20 @@ __device__ __forceinline__ void cx_tri_pin(cx_tri_in& I, uint4& nxt) {
 // predicated tetrahedra per cell lane: a voxel has 1.7 of them on average, so two rounds of 64 lanes replace six unrolled
 // hash comparisons per lane.  The corner hashes (low words) of a round's cells go through LDS (hs), overlaying the slot
 // words, which are written afterwards.
-template <bool NEG_ORIGIN, typename LDS>
+// SLIM: the wave's 64 lanes hold the slim records 64 g .. 64 g + 63 (cx_store_cell_record) and rec.z / rec.w the group's
+// {first triangle, first vertex}: a record's own two numbers are those plus the prefixes of ntri and popc(emask) inside the wave
+// (lanes behind the last record hold zeros, at the wave's end)
+template <bool NEG_ORIGIN, bool SLIM = false, typename LDS>
 __device__ __forceinline__ uint32_t cx_tri_phase1(const cx_params& P, LDS& L, uint32_t lane, uint32_t wave, const cx_tri_in& I) {
     const uint32_t sm = I.rec.y & 0xFFu, tetskip = (I.rec.y >> 8) & 0x3Fu, ntri = (I.rec.y >> 16) & 0xFFu;
-    if constexpr (LDS::packed) {     // rec.w and nb[].x carry the packed words as they are
+    if constexpr (SLIM) {
+        static_assert(!LDS::packed, "slim records: the record-walking kernel of the staged pipeline");
+        uint32_t vtot;
+        const uint32_t vpre = cx_wave_prefix_small<3>(__popc(I.rec.y >> 24), vtot);
+        L.ve[wave][0][lane] = make_uint2(I.rec.w + vpre, I.rec.y >> 24);
+#pragma unroll
+        for (uint32_t c = 1; c < 7; c++) L.ve[wave][c][lane] = I.nb[c - 1u];
+    } else if constexpr (LDS::packed) {     // rec.w and nb[].x carry the packed words as they are
         L.ve[wave][0][lane] = I.rec.w;
 #pragma unroll
         for (uint32_t c = 1; c < 7; c++) L.ve[wave][c][lane] = I.nb[c - 1u].x;
@@ -1791,7 +1802,7 @@ __device__ __forceinline__ uint32_t cx_tri_phase1(const cx_params& P, LDS& L, ui
     // slot words of this cell's triangles, in tetrahedron order
     uint32_t ttot;
     const uint32_t tpre = cx_wave_prefix_small<4>(ntri, ttot);
-    L.u[wave].a.tfirst[lane] = I.rec.z - tpre;   // triangle j of the wave goes to tfirst[cell] + j
+    L.u[wave].a.tfirst[lane] = SLIM ? I.rec.z : I.rec.z - tpre;   // triangle j of the wave goes to tfirst[cell] + j
     uint32_t pos = tpre;
     uint16_t* slot = L.u[wave].a.slot;
 #pragma unroll
@@ -1844,6 +1855,14 @@ __device__ __forceinline__ void cx_tri_phase2(const cx_params& P, LDS& L, uint32
 #ifndef CX_NT_RECS
 #define CX_NT_RECS 1     // the cell records are read once: nontemporal loads (A/B: ~1.5 %, within noise)
 #endif
+__device__ __forceinline__ uint2 cx_load_record2(const uint2* p) {   // a slim record
+#if CX_NT_RECS
+    const cx_v2u v = __builtin_nontemporal_load(reinterpret_cast<const cx_v2u*>(p));
+    return make_uint2(v.x, v.y);
+#else
+    return *p;
+#endif
+}
 __device__ __forceinline__ uint4 cx_load_record(const uint4* p) {
 #if CX_NT_RECS
     typedef uint32_t cx_v4u __attribute__((ext_vector_type(4)));
@@ -2041,7 +2060,7 @@ __device__ __forceinline__ void cx_triq_pin2(cx_tri_in& I) {
 #ifndef CX_K2Q_MIN_WAVES
 #define CX_K2Q_MIN_WAVES 5   // 96 registers: one more wave per SIMD than the allocator takes on its own (98)
 #endif
-template <bool NEG_ORIGIN>
+template <bool NEG_ORIGIN, bool SLIM>   // SLIM: 8-byte records + P.cbase (cx_store_cell_record); else the 16-byte records (cx_extract3d_levels)
 __global__ __launch_bounds__(256, CX_K2Q_MIN_WAVES) void cx_k_emit_triangles_q(const cx_params P, const cx_task T, const uint64_t* __restrict__ hash_xy) {
 #ifdef CX_OCC_PAD   // experiment: fewer workgroups per CU (what does the time do with the occupancy?)
     __shared__ uint32_t s_pad[CX_OCC_PAD / 4];
@@ -2050,6 +2069,7 @@ __global__ __launch_bounds__(256, CX_K2Q_MIN_WAVES) void cx_k_emit_triangles_q(c
     __shared__ cx_tri_lds L;
     const uint32_t ncells = min(P.counters[CX_CNT_CELLS], P.ccap);
     if (P.counters[CX_CNT_TRIS] > P.tcap || P.counters[CX_CNT_VERTS] > P.vcap) return;  // host re-runs with more room
+    if (SLIM && P.counters[CX_CNT_CELLS] > P.ccap) return;   // ... here too: the last 64-group's records and its P.cbase slot may not all be there
     // (Records are taken in launch order.  Measured and dropped, third session of round 4: every XCD taking ONE contiguous eighth of each
     // stride -- workgroup b -> block (b % 8) * (grid / 8) + b / 8 --, so that the queue / info words of neighbour cells come from the XCD's
     // own L2 more often: 0.126 -> 0.136 ms, 0.330 -> 0.340-0.345 ms per step.)
@@ -2065,7 +2085,18 @@ __global__ __launch_bounds__(256, CX_K2Q_MIN_WAVES) void cx_k_emit_triangles_q(c
     // result: written as `(at < ncells) ? load : zero`, the load sat in a branch whose result the compiler copied into other
     // registers right behind it, i.e. every iteration began by waiting for the record it had just asked for.  Whether the record
     // exists is decided when it is used (`valid`).
-    auto record = [&](uint32_t at) { return cx_load_record(P.cells + min(at, ncells - 1u)); };
+    // Slim: the 8-byte record and, in its z / w, the {first triangle, first vertex} of its group of 64 -- one wave-uniform 8-byte load
+    // per iteration (a wave's 64 records are one group: idx - lane is a multiple of 64), requested with the record
+    auto record = [&](uint32_t at) {
+        const uint32_t c = min(at, ncells - 1u);
+        if constexpr (SLIM) {
+            const uint2 r = cx_load_record2(reinterpret_cast<const uint2*>(P.cells) + c);
+            const uint2 b = P.cbase[__builtin_amdgcn_readfirstlane(c >> 6)];
+            return make_uint4(r.x, r.y, b.x, b.y);
+        } else {
+            return cx_load_record(P.cells + c);
+        }
+    };
     auto valid = [&](const uint4& r, uint32_t at) { return (at < ncells) ? r : zero; };
     // prologue: record idx through both stages, record idx + stride through the first, record idx + 2 stride loaded
     cx_tri_qa Ab, Ac;
@@ -2086,7 +2117,7 @@ __global__ __launch_bounds__(256, CX_K2Q_MIN_WAVES) void cx_k_emit_triangles_q(c
         uint4 rec_d = record(nidx + 2u * stride);          // the record three steps ahead
         cx_triq_stage1(P, T, L, valid(rec_c, nidx + stride), Ac);   // queue words of the record two steps ahead
         cx_triq_stage2(P, T, hash_xy, Ab, Ib);              // info words (and hash prefixes) of the next record
-        const uint32_t ttot = cx_tri_phase1<NEG_ORIGIN>(P, L, lane, wave, Ia);
+        const uint32_t ttot = cx_tri_phase1<NEG_ORIGIN, SLIM>(P, L, lane, wave, Ia);
 #if CX_PIN_BEFORE_STORES
         cx_triq_pin1(Ac, rec_d);                            // ... all back before the stores go out
         cx_triq_pin2(Ib);
@@ -2808,8 +2839,15 @@ void cx_launch_emit_triangles_q(const cx_params& P, const cx_task& T, const uint
     uint32_t g = cx_debug_knob("CX_TGRID", 256u * 8u);
     const uint32_t most = (P.ccap + 255u) / 256u;
     if (g > most) g = most;
-    if ((int32_t)P.org2 < 0) hipLaunchKernelGGL(cx_k_emit_triangles_q<true>, dim3(g ? g : 1u), dim3(256), 0, s, P, T, hash_xy);
-    else hipLaunchKernelGGL(cx_k_emit_triangles_q<false>, dim3(g ? g : 1u), dim3(256), 0, s, P, T, hash_xy);
+    const dim3 grid(g ? g : 1u);
+    const bool neg = (int32_t)P.org2 < 0;
+    if (P.write_records == CX_RECORDS_SLIM) {
+        if (neg) hipLaunchKernelGGL((cx_k_emit_triangles_q<true, true>), grid, dim3(256), 0, s, P, T, hash_xy);
+        else hipLaunchKernelGGL((cx_k_emit_triangles_q<false, true>), grid, dim3(256), 0, s, P, T, hash_xy);
+    } else {
+        if (neg) hipLaunchKernelGGL((cx_k_emit_triangles_q<true, false>), grid, dim3(256), 0, s, P, T, hash_xy);
+        else hipLaunchKernelGGL((cx_k_emit_triangles_q<false, false>), grid, dim3(256), 0, s, P, T, hash_xy);
+    }
 }
 
 // ---- fp32 grid coordinates of the vertex records, on request (cx_level0_download, cx_level0_device_ptrs): {x, y, z, bits(edge id)}

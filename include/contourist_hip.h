@@ -721,7 +721,8 @@ int cx_contour2d_extract(cx_ctx* ctx, const float* samples, int on_device, int64
 int cx_contour2d_download(cx_ctx* ctx, double* points_xy, int64_t* keys, cx_chain2d* chains);
 
 /* ---- measurement ----------------------------------------------------------------------------------
- * When enabled, every extract records HIP events around its kernels on the context's stream.
+ * When enabled, every extract records HIP events around its kernels on the context's stream (cx_timing_enable(ctx, 1)
+ * creates the events of the next 256 extracts once per context; extracts beyond that go untimed until the next read).
  * cx_timing_read synchronises and returns the summed milliseconds since the last reset:
  * ms[0] classify + vertex stage (all of its kernels), ms[1] triangle emit kernel, ms[2] whole extract,
  * ms[3] stream kernel, ms[4] scan kernel, ms[5] cell / vertex emit kernel (staged pipeline; the generic
