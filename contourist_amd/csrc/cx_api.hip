@@ -235,9 +235,8 @@ void cx_fill_value_params(cx_params& P, double value) {
 static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
     if (!ctx->grid.p) return fail(ctx, CX_ERR_STATE, "no grid: call cx_grid_upload or cx_grid_adopt_device first");
     if (!(value == value)) return fail(ctx, CX_ERR_INVALID, "isovalue is NaN");
-    // the public flags are the documented ones; the ablation bits (CX_DBG_*) give partial meshes and are only honoured
-    // in a process started with CX_DEBUG=1 (tools/)
-    if ((flags & ~(uint32_t)(CX_DIAG_CPYTHON310 | CX_KERNEL_GENERIC | CX_KERNEL_STAGED | CX_KERNEL_FUSED | CX_KERNEL_TILED)) != 0u && !cx_debug_enabled())
+    // the flags are the five documented ones, in every process
+    if ((flags & ~(uint32_t)(CX_DIAG_CPYTHON310 | CX_KERNEL_GENERIC | CX_KERNEL_STAGED | CX_KERNEL_FUSED | CX_KERNEL_TILED)) != 0u)
         return fail(ctx, CX_ERR_INVALID, "unknown flag bits in cx_extract3d");
     const int64_t N = ctx->n0 * ctx->n1 * ctx->n2;
     if (!ctx->cells || !ctx->verts || !ctx->tris) {
@@ -338,7 +337,7 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
         // (DESIGN.md section 4): it runs on request (CX_DEBUG=1 CX_K2_ENTRIES=1)
         // Its records are the slim ones (8 bytes + {first triangle, first vertex} per 64 records: half the 128 MB round trip of
         // the full ones at 512^3); whoever wants full records afterwards gets them from cx_ensure_cell_records.
-        P.write_records = (!fused && !tiled && !cx_debug_knob("CX_K2_ENTRIES", 0u)) ? (CX_SLIM_RECORDS ? CX_RECORDS_SLIM : CX_RECORDS_FULL) : CX_RECORDS_NONE;
+        P.write_records = (!fused && !tiled && !cx_debug_knob("CX_K2_ENTRIES", 0u)) ? CX_RECORDS_SLIM : CX_RECORDS_NONE;
         if (P.write_records == CX_RECORDS_SLIM) {
             if ((rc = ctx->cbase.grow(ctx, (size_t)ctx->ccap() / 64u + 1u))) return rc;
             P.cbase = ctx->cbase;
@@ -369,24 +368,24 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
     if (ctx->timing && ctx->nevents < (int)(sizeof(ctx->events) / sizeof(ctx->events[0])) && ctx->events[ctx->nevents].e[4])
         ev = &ctx->events[ctx->nevents++];     // (made by cx_timing_enable: no hipEventCreate here; extractions beyond the pool go untimed)
     // the generic kernel accumulates into the counters; the staged pipeline's scan kernel writes all of them
-    if (!staged || (flags & CX_DBG_PHASE_A_ONLY))
+    if (!staged)
         CX_HIP(ctx, hipMemsetAsync(ctx->counters, 0, CX_CNT_WORDS * sizeof(uint32_t), ctx->stream));
     if (ev) CX_HIP(ctx, hipEventRecord(ev->e[0], ctx->stream));
     if (staged) {
         cx_launch_stream(P, T, ctx->stream);
         if (ev) CX_HIP(ctx, hipEventRecord(ev->e[1], ctx->stream));
-        if (!(flags & CX_DBG_PHASE_A_ONLY)) cx_launch_scan_waves(P, T, ctx->stream);
+        cx_launch_scan_waves(P, T, ctx->stream);
         if (ev) CX_HIP(ctx, hipEventRecord(ev->e[2], ctx->stream));
         if (fused) cx_launch_emit_mesh(P, T, ctx->stream);
-        else if (tiled) { if (!(flags & (CX_DBG_PHASE_A_ONLY | CX_DBG_COUNT_ONLY))) cx_launch_tile_emit(P, T, ctx->hash_xy, ctx->stream); }
-        else if (!(flags & (CX_DBG_PHASE_A_ONLY | CX_DBG_COUNT_ONLY))) cx_launch_emit_vertices(P, T, ctx->stream);
+        else if (tiled) cx_launch_tile_emit(P, T, ctx->hash_xy, ctx->stream);
+        else cx_launch_emit_vertices(P, T, ctx->stream);
     } else {
         cx_launch_classify_generic(P, ctx->stream);
         if (ev) CX_HIP(ctx, hipEventRecord(ev->e[1], ctx->stream));
         if (ev) CX_HIP(ctx, hipEventRecord(ev->e[2], ctx->stream));
     }
     if (ev) CX_HIP(ctx, hipEventRecord(ev->e[3], ctx->stream));
-    if (!fused && !tiled && !(flags & (CX_DBG_NO_EMIT | CX_DBG_PHASE_A_ONLY | CX_DBG_COUNT_ONLY))) {
+    if (!fused && !tiled) {
         if (staged && P.write_records) cx_launch_emit_triangles_q(P, T, ctx->hash_xy, ctx->stream);
         else if (staged) cx_launch_emit_triangles_e(P, T, ctx->hash_xy, ctx->stream);   // (A/B: CX_K2_ENTRIES)
         else cx_launch_emit_triangles(P, ctx->hash_xy, ctx->stream);
@@ -461,14 +460,14 @@ extern "C" int cx_extract3d(cx_ctx* ctx, double value, uint32_t flags, cx_counts
     return fail(ctx, CX_ERR_CAPACITY, "output buffers still too small after growing");
 }
 
-// cell records {lin, sign|tetskip<<8|ntri<<16|emask<<24, first triangle, first vertex} of the last extraction: the fused emit
-// kernel does not write them; callers that walk the surface voxels (seeded selection) get them from the vertex stage of the
-// staged kernels run over the same queues with its other stores switched off
+// cell records {lin, sign|tetskip<<8|ntri<<16|emask<<24, first triangle, first vertex} of the last extraction: the default path
+// leaves the slim ones, the fused and tile emit kernels none; callers that walk the surface voxels (seeded selection) get the full
+// ones from a records-only pass -- the vertex stage of the staged kernels over the same queues, storing cell records and nothing else
 int cx_ensure_cell_records(cx_ctx* ctx) {
     if (!ctx->extracted) return fail(ctx, CX_ERR_STATE, "no valid extraction");
     if (ctx->records_valid) return CX_OK;
     cx_params P = ctx->last;
-    P.flags |= CX_DBG_NO_VERTS | CX_DBG_NO_CELLTAB;
+    P.records_only = 1u;                 // no vertex records (they are in place) and no info words (the fused path has no buffer for them)
     P.write_records = CX_RECORDS_FULL;   // over the slim ones of the default path, which the triangle stage is done with (same stream)
     P.ccap = ctx->ccap(); P.cells = ctx->cells;
     cx_launch_emit_vertices(P, ctx->last_task, ctx->stream);

@@ -8,7 +8,7 @@
 #include "../../include/contourist_hip.h"
 #include "cx_tables.h"
 
-// debug / tuning switches are honoured only in a process started with CX_DEBUG=1 (tools/, never the product path)
+// debug / tuning knobs (cx_debug_knob) are honoured only in a process started with CX_DEBUG=1 (tools/ and tests, never the product path)
 #include <cstdlib>
 #include <cstring>
 static inline bool cx_debug_enabled() {
@@ -57,13 +57,12 @@ struct cx_grid_ref {
     int32_t dtype;
 };
 template <int DT> struct cx_dt;
-// cvt: the loaded value (narrow types: its bits, zero-extended) as fp32.  raw / placeholder: what a kernel that converts later
-// (cx_vround_front -> cx_vround_pin) keeps in an fp32 register meanwhile -- the bits, and the bits of the small integer n (debug ablations)
+// cvt: the loaded value (narrow types: its bits, zero-extended) as fp32.  raw: what a kernel that converts later
+// (cx_vround_front -> cx_vround_pin) keeps in an fp32 register meanwhile -- the bits
 template <> struct cx_dt<CX_DTYPE_F32> {
     typedef float T; typedef float bits;
     static __device__ __forceinline__ float cvt(float v) { return v; }
     static __device__ __forceinline__ float raw(float v) { return v; }
-    static __device__ __forceinline__ float placeholder(uint32_t n) { return (float)n; }
 };
 template <int DT, typename TT, typename B>
 struct cx_dt_narrow {
@@ -75,7 +74,6 @@ struct cx_dt_int : cx_dt_narrow<DT, TT, typename std::make_unsigned<TT>::type> {
     static __device__ __forceinline__ float cvt(uint32_t v) {
         return (float)(TT)(typename std::make_unsigned<TT>::type)v;   // zero- or sign-extended, then v_cvt_f32_{u,i}32
     }
-    static __device__ __forceinline__ float placeholder(uint32_t n) { return __uint_as_float(n); }
 };
 template <> struct cx_dt<CX_DTYPE_U8> : cx_dt_int<CX_DTYPE_U8, uint8_t> {};
 template <> struct cx_dt<CX_DTYPE_I8> : cx_dt_int<CX_DTYPE_I8, int8_t> {};
@@ -83,11 +81,9 @@ template <> struct cx_dt<CX_DTYPE_U16> : cx_dt_int<CX_DTYPE_U16, uint16_t> {};
 template <> struct cx_dt<CX_DTYPE_I16> : cx_dt_int<CX_DTYPE_I16, int16_t> {};
 template <> struct cx_dt<CX_DTYPE_F16> : cx_dt_narrow<CX_DTYPE_F16, uint16_t, uint16_t> {
     static __device__ __forceinline__ float cvt(uint32_t v) { return (float)__builtin_bit_cast(_Float16, (uint16_t)v); }
-    static __device__ __forceinline__ float placeholder(uint32_t n) { return __uint_as_float(__builtin_bit_cast(uint16_t, (_Float16)n)); }
 };
 template <> struct cx_dt<CX_DTYPE_BF16> : cx_dt_narrow<CX_DTYPE_BF16, uint16_t, uint16_t> {
     static __device__ __forceinline__ float cvt(uint32_t v) { return __uint_as_float(v << 16); }
-    static __device__ __forceinline__ float placeholder(uint32_t n) { return __uint_as_float(__float_as_uint((float)n) >> 16); }
 };
 template <int DT>
 __device__ __forceinline__ const typename cx_dt<DT>::T* cx_grid_data(const cx_grid_ref& g) {
@@ -161,6 +157,8 @@ struct cx_params {
     uint32_t nkw;             // waves of the triangle stage (4 x its grid)
     uint32_t write_records;   // the vertex stage also writes cell records: CX_RECORDS_FULL the 16-byte ones (seeded selection, levels), CX_RECORDS_SLIM
                               // the 8-byte ones {lin, sign|tetskip<<8|ntri<<16|emask<<24} of the record-walking triangle kernel, in the front half of `cells`
+    uint32_t records_only;    // wave-uniform, 1: the vertex stage run again for its cell records alone (cx_ensure_cell_records) -- it walks the queues as
+                              // before and stores neither vertex records nor (first vertex, crossing mask) words (after the fused kernel there is no buffer for those)
     uint2* cbase;             // [ccap / 64 + 1] slim records: {first triangle, first vertex} of record 64 g (the others: + the prefixes of their 64-group)
     // the stream of interpolation fractions (round 4): the stream kernel, which has the samples, computes t = (v - f(q)) / (f(q+d) - f(q))
     // of every crossing and writes them per streaming wave in the order the vertex stage numbers the vertices; the vertex stage reads
@@ -177,10 +175,7 @@ struct cx_params {
     uint32_t tile_cap;        // info words a workgroup of the tile kernel holds in LDS (queue entries of its tile + the next chunk's first plane)
 };
 enum { CX_RECORDS_NONE = 0, CX_RECORDS_FULL = 1, CX_RECORDS_SLIM = 2 };
-// the default staged path hands 8-byte cell records from the vertex to the triangle stage (host side, cx_api.hip; 0: the 16-byte ones, for A/B builds)
-#ifndef CX_SLIM_RECORDS
-#define CX_SLIM_RECORDS 1
-#endif
+// (the default staged path hands the 8-byte cell records from the vertex to the triangle stage: host side, cx_api.hip)
 #ifndef CX_SWP
 #define CX_SWP 16u            // plane slots per streaming wave: cell planes per task (ci) + 1, ci <= 15
 #endif
@@ -220,19 +215,6 @@ struct cx_task {
     uint32_t bndcap;       // boundary records per half tile (tile emit path): the voxels of its last row and last sample column
     cx_fdiv div_nks, div_njg;   // / nks, / njg: a streaming wave's tile from its number (triangle stage)
 };
-
-// debug / ablation flags (timing experiments only; results are wrong when set)
-#define CX_DBG_PHASE_A_ONLY 0x10000u   // classify kernel: stream + queue, skip phase B
-#define CX_DBG_COUNT_ONLY 0x20000u     // phase B: count pass only
-#define CX_DBG_NO_CELLTAB 0x40000u     // phase B: skip the per-cell table store
-#define CX_DBG_NO_VERTS 0x80000u       // phase B: skip vertex record stores
-#define CX_DBG_NO_CELLS 0x100000u      // phase B: skip cell record stores
-#define CX_DBG_NO_LOOKUP 0x200000u     // emit kernel: skip neighbour table lookups
-#define CX_DBG_NO_TRIS 0x400000u       // emit kernel: skip triangle stores
-#define CX_DBG_NO_EMIT 0x800000u       // skip the emit kernel
-#define CX_DBG_NO_NEAR 0x2000000u      // stream kernel: ignore the tolerance screen (never take the per-cell path)
-#define CX_DBG_HASH64 0x4000000u       // triangle kernels: corner hashes in full 64-bit arithmetic (no table, no 32-bit fast form)
-#define CX_DBG_NO_VLOADS 0x1000000u    // phase B (packed entries): no sample loads for the vertices
 
 enum { CX_CNT_CELLS = 0, CX_CNT_VERTS = 1, CX_CNT_TRIS = 2, CX_CNT_BORDER = 3, CX_CNT_BATCHES = 4,
        CX_CNT_NEAR = 5,   // streaming waves that met a sample inside the tolerance screen (their cells take the per-cell path)

@@ -178,10 +178,6 @@ __global__ __launch_bounds__(256) void cxc_k_measure(const int32_t* __restrict__
         }
     }
     if (active && over) atomicOr(&acc[(size_t)label * CXC_WORDS + CXC_W_OVER], 1ULL);       // (never, for a mesh inside its grid box)
-#ifdef CXC_ABL_NOWAVE
-    // ablation (tools/bench_components.py): every lane on its own, to show what the reduction within the wave buys
-    if (active) cxc_lane_atomics(acc + (size_t)label * CXC_WORDS, ia, iv, im0, im1, im2, ex, lo0, lo1, lo2, hi0, hi1, hi2);
-#else
     const uint32_t lane = threadIdx.x & 63u;
     uint64_t rem = __ballot(active);
     while (rem != 0ULL) {                                   // wave-uniform
@@ -210,7 +206,6 @@ __global__ __launch_bounds__(256) void cxc_k_measure(const int32_t* __restrict__
             cxd_max64(&w[CXC_W_HI], h0); cxd_max64(&w[CXC_W_HI + 1], h1); cxd_max64(&w[CXC_W_HI + 2], h2);
         }
     }
-#endif
 }
 // vertices per component by vertex label, counted within the wave first
 __global__ __launch_bounds__(256) void cxc_k_vertex_count(const int32_t* __restrict__ vlab, uint32_t nv, uint32_t nc, u64* __restrict__ acc) {

@@ -4,19 +4,26 @@
 // A cell OWNS the 7 lattice edges q -> q+d, d = 4di+2dj+dk in 1..7, and (when all 8 corners are
 // inside the array) the 6 Kuhn tetrahedra of its voxel.  Vertex id of an edge = (lin(q) << 3) | d.
 //
-// Staged pipeline (any grid with n2 >= 4) -- no atomics, no barriers:
+// Staged pipeline (any grid with n2 >= 4) -- no atomics, no barriers between waves:
 //   S1  cx_k_stream            one pass over the samples: sign bits packed per lane, active cells (sign
 //                              change among the 8 corners) appended to a per-wave queue in global memory
 //                              as packed entries; the queue is cut into batches of >= CX_BATCH_MIN cells
 //                              with the vertex / triangle counts that precede them (from the packed words).
-//   S2  cx_k_scan_waves        exclusive scan of the per-wave totals -> output offsets, counters, and a
-//                              flat list of all batches.
-//   S3  cx_k_emit_vertices     one wave per batch: vertex records (one lane per vertex), per-cell table,
-//                              cell records.
-//   K2  cx_k_emit_triangles    one lane per cell record: expands the tetrahedra into index triples, looking
-//                              vertex indices up in the per-cell table.
-// Rows shorter than 4 samples, or on request (CX_KERNEL_GENERIC): cx_k_classify_generic (one lane per cell, LDS queue, one reservation atomic per
-// workgroup and counter -- same-address atomics saturate near 88/us on MI355X) followed by K2.
+//   S2  cx_k_scan_list         exclusive scan of the per-wave totals -> output offsets, counters, a flat
+//                              list of all batches and the batch each later wave's share of rounds starts in.
+//   S3  cx_k_emit_vertices     the rounds of 64 queued cells dealt evenly to the waves: vertex records (one
+//                              lane per vertex), one (first vertex, crossing mask) word per queue entry,
+//                              8-byte cell records.  With P.records_only: 16-byte cell records and nothing else.
+//   K2  cx_k_emit_triangles_q  one lane per cell record: expands the tetrahedra into index triples; the vertex
+//                              indices of neighbour cells come from their queue entries' words.
+// Every kernel has ONE body: the timing experiments that once lived here behind -D switches and flag bits are gone, their
+// results are in the comments at the places they decided and in DESIGN.md section 4.  What can still be selected is whole,
+// tested paths: on request (public flags) the fused kernel cx_k_emit_mesh (S3 + K2 in one pass) and the tile kernels of
+// cx_tile3d.h; in a process started with CX_DEBUG=1, the fraction stream (CX_TQ: S1 hands the interpolation fractions to S3)
+// and the entry-walking triangle kernel cx_k_emit_triangles_e (CX_K2_ENTRIES).  Macros behind #ifndef only give numbers.
+// Rows shorter than 4 samples, or on request (CX_KERNEL_GENERIC): cx_k_classify_generic (one lane per cell, LDS queue, one
+// reservation atomic per workgroup and counter -- same-address atomics saturate near 88/us on MI355X) followed by
+// cx_k_emit_triangles, which walks 16-byte cell records and looks neighbours up in a table of one entry per sample.
 #include <cstdlib>
 
 #include "cx_cell.h"
@@ -32,14 +39,8 @@ __device__ __constant__ uint8_t cx_d_voxel_ntri[256] = CX_VOXEL_NTRI_INIT;
 #ifndef CX_K1_MIN_WAVES
 #define CX_K1_MIN_WAVES 3   // stream kernel: two sample planes in flight per wave
 #endif
-#ifndef CX_S1_DEPTH
-#define CX_S1_DEPTH 1        // sample planes in flight ahead of the one the stream kernel works on (1 or 2; 2 measured slower: 0.131 vs 0.125 ms, 168 registers)
-#endif
 #ifndef CX_RJ
 #define CX_RJ 4             // cell rows per wave in the stream kernel (a workgroup covers 4*CX_RJ rows)
-#endif
-#ifndef CX_S1_LAZY
-#define CX_S1_LAZY 1         // stream kernel: queued cells are counted in full rounds of 64 when the stage is flushed or a batch closes (0: one round per plane step)
 #endif
 #ifndef CX_S3_MIN_SHARE
 #define CX_S3_MIN_SHARE 4u   // rounds a vertex-stage wave takes at least (small surfaces: fewer waves rather than waves that only start up)
@@ -122,17 +123,17 @@ __device__ __forceinline__ void cx_process_queue(const cx_params& P, LinOf lin_o
                     // the wave's vertices of this batch are one contiguous run of the vertex array:
                     // stage them in LDS, then write full 16-byte-per-lane rows
                     if (nv) cx_emit_vertices(P, f, R.emask, lin, i, j, k, [&](uint32_t r2, const cx_vrec& rec4) { vstage[vpre + r2] = rec4; });
-                    if (!(P.flags & CX_DBG_NO_VERTS))
+                    if (!P.records_only)
                         for (uint32_t o = lane; o < vtot; o += 64u) P.verts[run.v + o] = vstage[o];
-                } else if (nv && !(P.flags & CX_DBG_NO_VERTS)) {
+                } else if (nv && !P.records_only) {
                     cx_emit_vertices(P, f, R.emask, lin, i, j, k, [&](uint32_t r2, const cx_vrec& rec4) { P.verts[vfirst + r2] = rec4; });
                 }
                 // (first vertex, crossing mask) of the cell for the triangle stage: per queue entry (staged pipeline), or in
                 // the table of one entry per sample (generic classify kernel)
-                if (info) { if (have && !(P.flags & CX_DBG_NO_CELLTAB)) info[idx] = cx_info_word(vfirst, R.emask, R.ntri, R.tetskip); }
-                else if (nv && !(P.flags & CX_DBG_NO_CELLTAB)) P.celltab[lin] = ((uint64_t)R.emask << 32) | (uint64_t)vfirst;
+                if (info) { if (have && !P.records_only) info[idx] = cx_info_word(vfirst, R.emask, R.ntri, R.tetskip); }
+                else if (nv && !P.records_only) P.celltab[lin] = ((uint64_t)R.emask << 32) | (uint64_t)vfirst;
             }
-            if (RECORDS && (P.write_records || !info) && rec && run.c + ctot <= P.ccap && !(P.flags & CX_DBG_NO_CELLS)) {
+            if (RECORDS && (P.write_records || !info) && rec && run.c + ctot <= P.ccap) {
                 cx_store_cell_record(P, run.c + cx_mbcnt(recm), lin, sm | (R.tetskip << 8) | (R.ntri << 16) | (R.emask << 24), run.t + tpre, vfirst);
             }
         }
@@ -146,14 +147,11 @@ __device__ __forceinline__ void cx_process_queue(const cx_params& P, LinOf lin_o
 //   bits 10-14  position of the cell inside its lane's packed word (6*row + m)
 //   bits 15-20  streaming lane (k = k0 + 4*lane + m)
 //   bits 21-27  plane offset inside the task
-// Where a wave waits for the loads it issued at the top of an iteration: before the iteration's stores (1: rounds 1 and 2 --
-// a wait issued behind stores retires them too, `s_waitcnt vmcnt` counts loads and stores in issue order) or after them (0).
+// A wave waits for the loads it issued at the top of an iteration AFTER the iteration's stores, not before them (as rounds 1 and 2
+// did -- a wait issued behind stores retires them too, `s_waitcnt vmcnt` counts loads and stores in issue order).
 // tools/micro/mix_rate.hip settles it: 4 scattered gathers + 6 coalesced stores per iteration cost 1011 cycles per CU when the
 // wave waits for the gathers before it stores and 662 when it stores first -- the stores of one iteration and the gathers of
 // the next then travel together instead of one after the other.
-#ifndef CX_PIN_BEFORE_STORES
-#define CX_PIN_BEFORE_STORES 0
-#endif
 #ifndef CX_VR
 #define CX_VR 4u          // rounds of 64 vertices whose loads are issued together
 #endif
@@ -191,26 +189,10 @@ __device__ __forceinline__ uint32_t cx_corner_valid(const cx_params& P, uint32_t
 // Vertex records and triangles are not read again by the pipeline: nontemporal stores keep them from sitting dirty
 // in L2 / Infinity Cache until the NEXT extraction's stream kernel has to push them out (measured: stream kernel
 // 0.148 -> 0.129 ms inside the pipeline, whole extraction -5 %).  Table entries and cell records are read by the
-// triangle kernel right away and stay ordinary stores.  -DCX_NT_VERTS=0 / -DCX_NT_TRIS=0 for A/B.
-#ifndef CX_NT_VERTS
-#define CX_NT_VERTS 1
-#endif
-#ifndef CX_NT_TRIS
-#define CX_NT_TRIS 1
-#endif
-#ifndef CX_S1_SHIFT_OR
-#define CX_S1_SHIFT_OR 0
-#endif
-#ifndef CX_NT_GRID
-#define CX_NT_GRID 0
-#endif
+// triangle kernel right away and stay ordinary stores.
 typedef float cx_v4f __attribute__((ext_vector_type(4)));
 typedef uint32_t cx_v2u __attribute__((ext_vector_type(2)));
-#if CX_NT_VERTS
 #define CX_STORE_VERT(ptr, val) __builtin_nontemporal_store(cx_v2u{(val).x, (val).y}, reinterpret_cast<cx_v2u*>(ptr))
-#else
-#define CX_STORE_VERT(ptr, val) (*(ptr) = (val))
-#endif
 // one round of 64 queued cells, as the vertex stage carries it from its front half (decode, prefix
 // sums, slot table, corner loads issued) to its back half (interpolation, stores)
 struct cx_vround {
@@ -245,25 +227,19 @@ __device__ __forceinline__ void cx_vround_front(const cx_params& P, const cx_fas
     // interpolating the previous round's vertices meanwhile.
     uint32_t vm = cx_corner_valid(P, i, j, k);
     R.vk = (vm >> 1) & 1u;
-    if (P.flags & CX_DBG_NO_VLOADS) {
-#pragma unroll
-        for (int c = 0; c < 8; c++) R.f[c] = cx_dt<DT>::placeholder(c + 1);   // (cx_vround_pin converts them to c + 1)
-        R.vk = 1u;
-    } else {
-        const uint32_t lin = have ? R.lin : 0u;
-        const uint32_t oi = (have && (vm & 0x10u)) ? P.n1 * P.n2 : 0u, oj = (have && (vm & 4u)) ? P.n2 : 0u;
-        // at the array edge in k read the pair (k-1, k) instead and repeat k (as cx_load_corners does)
-        const uint32_t base = (R.vk || !have) ? lin : lin - 1u;
-        typedef typename cx_dt<DT>::bits B;
-        const B* __restrict__ A = reinterpret_cast<const B*>(cx_grid_data<DT>(P.grid));
-        const cx_pair<DT> p0 = *reinterpret_cast<const cx_pair<DT>*>(A + base);
-        const cx_pair<DT> p1 = *reinterpret_cast<const cx_pair<DT>*>(A + base + oj);
-        const cx_pair<DT> p2 = *reinterpret_cast<const cx_pair<DT>*>(A + base + oi);
-        const cx_pair<DT> p3 = *reinterpret_cast<const cx_pair<DT>*>(A + base + oi + oj);
-        R.f[0] = cx_dt<DT>::raw(p0.x); R.f[1] = cx_dt<DT>::raw(p0.y); R.f[2] = cx_dt<DT>::raw(p1.x); R.f[3] = cx_dt<DT>::raw(p1.y);
-        R.f[4] = cx_dt<DT>::raw(p2.x); R.f[5] = cx_dt<DT>::raw(p2.y); R.f[6] = cx_dt<DT>::raw(p3.x); R.f[7] = cx_dt<DT>::raw(p3.y);
-        if (!have) { vm = 0; R.vk = 1u; }
-    }
+    const uint32_t lin0 = have ? R.lin : 0u;
+    const uint32_t oi = (have && (vm & 0x10u)) ? P.n1 * P.n2 : 0u, oj = (have && (vm & 4u)) ? P.n2 : 0u;
+    // at the array edge in k read the pair (k-1, k) instead and repeat k (as cx_load_corners does)
+    const uint32_t at = (R.vk || !have) ? lin0 : lin0 - 1u;
+    typedef typename cx_dt<DT>::bits B;
+    const B* __restrict__ A = reinterpret_cast<const B*>(cx_grid_data<DT>(P.grid));
+    const cx_pair<DT> p0 = *reinterpret_cast<const cx_pair<DT>*>(A + at);
+    const cx_pair<DT> p1 = *reinterpret_cast<const cx_pair<DT>*>(A + at + oj);
+    const cx_pair<DT> p2 = *reinterpret_cast<const cx_pair<DT>*>(A + at + oi);
+    const cx_pair<DT> p3 = *reinterpret_cast<const cx_pair<DT>*>(A + at + oi + oj);
+    R.f[0] = cx_dt<DT>::raw(p0.x); R.f[1] = cx_dt<DT>::raw(p0.y); R.f[2] = cx_dt<DT>::raw(p1.x); R.f[3] = cx_dt<DT>::raw(p1.y);
+    R.f[4] = cx_dt<DT>::raw(p2.x); R.f[5] = cx_dt<DT>::raw(p2.y); R.f[6] = cx_dt<DT>::raw(p3.x); R.f[7] = cx_dt<DT>::raw(p3.y);
+    if (!have) { vm = 0; R.vk = 1u; }
     R.real_voxel = (have && vm == 0xFFu) ? 1u : 0u;
     const uint32_t s0 = (R.sm & 1u) ? 0xFFu : 0u;
     R.emask = have ? (((R.sm ^ s0) & vm) & 0xFEu) : 0u;
@@ -309,7 +285,7 @@ __device__ __forceinline__ cx_vrec cx_vertex_record(const cx_params& P, const cx
 // range of a batch's rounds (cx_k_emit_vertices)
 template <int DT>
 __device__ __forceinline__ void cx_emit_queue_fast(const cx_params& P, const cx_fast_geom& G, const uint32_t* q, uint32_t first, uint32_t n,
-                                                   uint32_t lane, cx_run run, uint32_t* slot2, const uint8_t* ntri_lut, uint64_t* info, unsigned long long* tacc = nullptr) {
+                                                   uint32_t lane, cx_run run, uint32_t* slot2, const uint8_t* ntri_lut, uint64_t* info) {
     float* corners = reinterpret_cast<float*>(slot2 + 2u * 448u);
     cx_vround Ra, Rb;
     uint32_t e0 = (first + lane < n) ? q[first + lane] : 0u;
@@ -317,12 +293,6 @@ __device__ __forceinline__ void cx_emit_queue_fast(const cx_params& P, const cx_
     cx_vround_front<DT>(P, G, q, n, first, lane, e0, run, slot2, ntri_lut, Ra);
     cx_vround_pin<DT>(Ra);
     uint32_t par = 0;
-#ifdef CX_S3_STAMPS
-#define CX_S3_T(k) { const unsigned long long tn = __builtin_amdgcn_s_memrealtime(); tacc[k] += tn - tprev; tprev = tn; }
-    unsigned long long tprev = __builtin_amdgcn_s_memrealtime();
-#else
-#define CX_S3_T(k)
-#endif
     for (uint32_t b0 = first; b0 < n; b0 += 64u) {
         const bool more = b0 + 64u < n;   // wave-uniform
         if (more) {
@@ -330,7 +300,6 @@ __device__ __forceinline__ void cx_emit_queue_fast(const cx_params& P, const cx_
             nb.v += Ra.vtot; nb.t += Ra.ttot; nb.c += Ra.ctot;
             cx_vround_front<DT>(P, G, q, n, b0 + 64u, lane, Ra.e_next, nb, slot2 + (par ^ 1u) * 448u, ntri_lut, Rb);
         }
-        CX_S3_T(0)
         // back half of round b0: the corner samples of the 64 cells go to LDS ...
 #pragma unroll
         for (uint32_t c = 0; c < 8; c++) corners[lane * CX_CORNER_ROW + c] = ((c & 1u) || Ra.vk) ? Ra.f[c] : Ra.f[c + 1u];   // no k+1: the pair is (k-1, k)
@@ -349,17 +318,12 @@ __device__ __forceinline__ void cx_emit_queue_fast(const cx_params& P, const cx_
             const uint32_t e2 = (uint32_t)__shfl((int)Ra.e, (int)cell);
             rec4[r] = cx_vertex_record(P, G, e2, d, corners[cell * CX_CORNER_ROW], corners[cell * CX_CORNER_ROW + d]);
         }
-        CX_S3_T(1)
-#if CX_PIN_BEFORE_STORES
-        if (more) cx_vround_pin<DT>(Rb);
-#endif
-        CX_S3_T(2)
         // ... then the stores
         if (vroom) {
 #pragma unroll
             for (uint32_t r = 0; r < CX_VR; r++) {
                 const uint32_t o = 64u * r + lane;
-                if (o < Ra.vtot && !(P.flags & CX_DBG_NO_VERTS)) CX_STORE_VERT(&P.verts[Ra.base.v + o], rec4[r]);
+                if (o < Ra.vtot && !P.records_only) CX_STORE_VERT(&P.verts[Ra.base.v + o], rec4[r]);
             }
             for (uint32_t o0 = 64u * CX_VR; o0 < Ra.vtot; o0 += 64u) {   // more than CX_VR x 64 vertices: the rest one round at a time
                 const uint32_t o = o0 + lane;
@@ -367,22 +331,19 @@ __device__ __forceinline__ void cx_emit_queue_fast(const cx_params& P, const cx_
                 const uint32_t cell = sl >> 3, d = sl & 7u;
                 const uint32_t e2 = (uint32_t)__shfl((int)Ra.e, (int)cell);
                 const cx_vrec r4 = cx_vertex_record(P, G, e2, d, corners[cell * CX_CORNER_ROW], corners[cell * CX_CORNER_ROW + d]);
-                if (o < Ra.vtot && !(P.flags & CX_DBG_NO_VERTS)) CX_STORE_VERT(&P.verts[Ra.base.v + o], r4);
+                if (o < Ra.vtot && !P.records_only) CX_STORE_VERT(&P.verts[Ra.base.v + o], r4);
             }
             // (first vertex, crossing mask) of every queued cell, one 8-byte word per queue entry: 512 contiguous bytes per round
             // (was: scattered into a table of one entry per sample -- a cache line per cell, written and later gathered)
-            if (b0 + lane < n && !(P.flags & CX_DBG_NO_CELLTAB))
+            if (b0 + lane < n && !P.records_only)
                 info[b0 + lane] = cx_info_word(Ra.base.v + Ra.vpre, Ra.emask, Ra.ntri, Ra.real_voxel ? 0u : 0x3Fu);
         }
-        if (P.write_records && (Ra.emask | Ra.ntri) != 0u && Ra.base.c + Ra.ctot <= P.ccap && !(P.flags & CX_DBG_NO_CELLS)) {
+        if (P.write_records && (Ra.emask | Ra.ntri) != 0u && Ra.base.c + Ra.ctot <= P.ccap) {
             cx_store_cell_record(P, Ra.base.c + cx_mbcnt(Ra.recm), Ra.lin, Ra.sm | ((Ra.real_voxel ? 0u : 0x3Fu) << 8) | (Ra.ntri << 16) | (Ra.emask << 24),
                                  Ra.base.t + Ra.tpre, Ra.base.v + Ra.vpre);
         }
         __builtin_amdgcn_wave_barrier();
-#if !CX_PIN_BEFORE_STORES
-        if (more) cx_vround_pin<DT>(Rb);   // the next round's samples are waited for AFTER this round's stores went out (see CX_PIN_BEFORE_STORES)
-#endif
-        CX_S3_T(3)
+        if (more) cx_vround_pin<DT>(Rb);   // the next round's samples are waited for AFTER this round's stores went out (the note above CX_VR)
         if (more) Ra = Rb;
         par ^= 1u;
     }
@@ -426,7 +387,7 @@ __device__ __forceinline__ void cx_tround_front(const cx_params& P, const cx_fas
     for (uint32_t r = 0; r < CX_VR; r++) {
         const uint32_t o = 64u * r + lane;
         R.tv[r] = 0u;
-        if (o < R.vtot && !(P.flags & CX_DBG_NO_VLOADS)) R.tv[r] = __builtin_nontemporal_load(tq_wave + base.v + o);
+        if (o < R.vtot) R.tv[r] = __builtin_nontemporal_load(tq_wave + base.v + o);
     }
 #pragma unroll
     for (uint32_t d = 1; d < 8; d++)
@@ -465,7 +426,7 @@ __device__ __forceinline__ void cx_emit_queue_t(const cx_params& P, const cx_fas
                 const uint32_t cell = sl >> 3, d = sl & 7u;
                 const uint32_t e2 = (uint32_t)__shfl((int)Ra.e, (int)cell);
                 const cx_vrec rec = make_uint2((cx_entry_lin(P, G, e2) << 3) | d, Ra.tv[r]);
-                if (o < Ra.vtot && !(P.flags & CX_DBG_NO_VERTS)) CX_STORE_VERT(&P.verts[Ra.base.v + o], rec);
+                if (o < Ra.vtot && !P.records_only) CX_STORE_VERT(&P.verts[Ra.base.v + o], rec);
             }
             for (uint32_t o0 = 64u * CX_VR; o0 < Ra.vtot; o0 += 64u) {   // more than CX_VR x 64 vertices: the rest one round at a time
                 const uint32_t o = o0 + lane;
@@ -474,12 +435,12 @@ __device__ __forceinline__ void cx_emit_queue_t(const cx_params& P, const cx_fas
                 const uint32_t e2 = (uint32_t)__shfl((int)Ra.e, (int)cell);
                 const uint32_t tb = (o < Ra.vtot) ? tq_wave[Ra.base.v + o] : 0u;
                 const cx_vrec rec = make_uint2((cx_entry_lin(P, G, e2) << 3) | d, tb);
-                if (o < Ra.vtot && !(P.flags & CX_DBG_NO_VERTS)) CX_STORE_VERT(&P.verts[Ra.base.v + o], rec);
+                if (o < Ra.vtot && !P.records_only) CX_STORE_VERT(&P.verts[Ra.base.v + o], rec);
             }
-            if (b0 + lane < n && !(P.flags & CX_DBG_NO_CELLTAB))
+            if (b0 + lane < n && !P.records_only)
                 info[b0 + lane] = cx_info_word(Ra.base.v + Ra.vpre, Ra.emask, Ra.ntri, Ra.real_voxel ? 0u : 0x3Fu);
         }
-        if (P.write_records && (Ra.emask | Ra.ntri) != 0u && Ra.base.c + Ra.ctot <= P.ccap && !(P.flags & CX_DBG_NO_CELLS)) {
+        if (P.write_records && (Ra.emask | Ra.ntri) != 0u && Ra.base.c + Ra.ctot <= P.ccap) {
             cx_store_cell_record(P, Ra.base.c + cx_mbcnt(Ra.recm), Ra.lin, Ra.sm | ((Ra.real_voxel ? 0u : 0x3Fu) << 8) | (Ra.ntri << 16) | (Ra.emask << 24),
                                  Ra.base.t + Ra.tpre, Ra.base.v + Ra.vpre);
         }
@@ -574,8 +535,11 @@ __device__ __forceinline__ void cx_cross_words(uint32_t A, uint32_t B, const cx_
 // generic classify kernel (any shape / alignment): one lane per cell, wave-private LDS queue, the
 // workgroup reserves output space with ONE atomic per counter, then emits (per-cell path).
 // =================================================================================================
+#ifndef CX_GEN_MIN_WAVES
+#define CX_GEN_MIN_WAVES 6   // what its LDS admits; on its own the allocator takes 87 registers and five waves
+#endif
 template <int DT>
-__global__ __launch_bounds__(256) void cx_k_classify_generic(const cx_params P, const uint32_t cells_per_block) {
+__global__ __launch_bounds__(256, CX_GEN_MIN_WAVES) void cx_k_classify_generic(const cx_params P, const uint32_t cells_per_block) {
     __shared__ uint32_t s_queue[4][CX_QCAP];
     __shared__ cx_vrec s_vstage[4][CX_VSTAGE];
     __shared__ uint32_t s_tot[4][4];
@@ -619,11 +583,6 @@ __global__ __launch_bounds__(256) void cx_k_classify_generic(const cx_params P, 
         // ---- phase B: count, reserve, emit.  The last round of a workgroup reserves once for all
         // four waves; a wave whose queue filled up early reserves for itself (dense surfaces only).
         const bool final_round = !streaming;
-        if (P.flags & CX_DBG_PHASE_A_ONLY) {
-            if (final_round) break;
-            qn = 0;
-            continue;
-        }
         cx_run run = {0, 0, 0, 0};
         auto lin_of = [&](uint32_t x) { return q[x]; };
         if (__ballot(dnear <= P.near_abs) != 0ULL) {   // wave-uniform: a sample inside the tolerance screen, count exactly
@@ -634,11 +593,6 @@ __global__ __launch_bounds__(256) void cx_k_classify_generic(const cx_params P, 
         }
         acc.v = acc.t = acc.c = acc.b = 0;
         dnear = 3.0e38f;
-        if (P.flags & CX_DBG_COUNT_ONLY) {
-            if (final_round) break;
-            qn = 0;
-            continue;
-        }
         if (final_round) {
             if (lane == 0) {
                 s_tot[wave][0] = run.v; s_tot[wave][1] = run.t; s_tot[wave][2] = run.c; s_tot[wave][3] = run.b;
@@ -753,10 +707,6 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
     extern __shared__ __attribute__((aligned(16))) float s_pl_dyn[];
     __shared__ uint32_t s_tot[4][8];
     __shared__ uint8_t s_ntri[256];      // triangles of a voxel by its corner sign mask
-#ifdef CX_S1_OCC_PAD   // experiment: fewer workgroups per CU (what does the stream kernel lose with less occupancy?)
-    __shared__ uint32_t s_pad[CX_S1_OCC_PAD / 4];
-    if (P.n0 == 0xFFFFFFFFu) reinterpret_cast<volatile uint32_t*>(s_pad)[threadIdx.x] = 1u;
-#endif
     if (b >= T.nblocks) return;
     s_ntri[threadIdx.x] = cx_d_voxel_ntri[threadIdx.x];
     if (b == 0u && threadIdx.x < 3u && P.torder) P.counters[CX_CNT_TCLS + threadIdx.x] = 0u;   // the scan kernel counts the tile kernel's work classes into these
@@ -768,9 +718,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
     uint32_t nbl = 0, nbflushed = 0;    // the same for batch records
     const uint32_t w = b * 4u + wave;
     unsigned long long* stamp = P.stamps ? P.stamps + (size_t)w * 4u : nullptr;
-#ifndef CX_S3_STAMPS
     if (stamp && lane == 0) stamp[0] = __builtin_amdgcn_s_memtime();
-#endif
     const cx_tile tile = cx_tile_of(P, T, b, wave);
     const uint32_t k0 = tile.k0, j0 = tile.j0, ib = tile.ib, nrows = tile.nrows;
     uint32_t p = tile.p;
@@ -793,7 +741,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
     // The counts of the queued cells (vertices, triangles, records, border voxels: what the batch records and the scan need) are only
     // ever used as sums over a batch, so they need not be taken step by step -- with ~30 cells per step half of the lanes of a
     // counting round stood idle.  Staged entries are counted in FULL rounds of 64 right before they leave the stage or a batch is
-    // closed (CX_S1_LAZY; the fraction stream P.tq works step by step and keeps the old form).
+    // closed (the fraction stream P.tq works step by step and keeps the old form: one counting round per plane step).
     uint32_t qc = 0;                 // wave-uniform: staged entries already counted
     // all eight corners of every cell of this wave's tile inside the array: the validity mask is 0xFF (wave-uniform)
     const bool interior = (tile.ib < P.n0) && (j0 + (uint32_t)CX_RJ < P.n1) && (k0 + 256u < P.n2);
@@ -822,9 +770,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
         qc = ql;
     };
     auto flush_queue = [&]() {
-#if CX_S1_LAZY
         if (!P.tq) count_pending();
-#endif
         __builtin_amdgcn_wave_barrier();
         if (qflushed + ql <= P.qlimit) {
             for (uint32_t o = lane; o < ql; o += 64u) gq[qflushed + o] = q[o];
@@ -848,9 +794,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
         nbl = 0;
     };
     auto close_batch = [&]() {
-#if CX_S1_LAZY
         if (!P.tq) count_pending();
-#endif
         const uint32_t bv = cxd_wave_add(acc.v), bt = cxd_wave_add(acc.t), bc = cxd_wave_add(acc.c);
         if (lane == 0) {
             s_br[wave][nbl][0] = qstart; s_br[wave][nbl][1] = qn - qstart; s_br[wave][nbl][2] = rv;
@@ -891,14 +835,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
                     R.v[r] = reinterpret_cast<const cx_row4_ua<V, ALIGNED ? sizeof(V) : sizeof(*A)>*>(A + rowofs + kofs_c)->v;
                     R.hv[r] = A[rowofs + (halo_in ? k0 + 256u : 0u)];                // raw bits, wave-uniform address
                 } else {
-#if CX_NT_GRID   // A/B: streaming loads of the grid (do not keep it in L2 / Infinity Cache)
-                {
-                    const cx_v4f t4 = __builtin_nontemporal_load(reinterpret_cast<const cx_v4f*>(A + rowofs + kofs_c));
-                    R.v[r] = make_float4(t4.x, t4.y, t4.z, t4.w);
-                }
-#else
                 R.v[r] = *reinterpret_cast<const float4*>(A + rowofs + kofs_c);      // lanes right of the array re-read its last 4 samples
-#endif
                 R.hv[r] = A[rowofs + (halo_in ? k0 + 256u : 0u)];                    // wave-uniform address
                 }
             }
@@ -908,11 +845,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
         // tolerance screen (smallest |f - vcmp| seen)
         float (*ring)[CX_RJ + 1][CX_PLW] = reinterpret_cast<float (*)[CX_RJ + 1][CX_PLW]>(s_pl_dyn + (size_t)wave * (2u * (CX_RJ + 1u) * CX_PLW));
         const bool stage_t = P.tq != nullptr;      // wave-uniform: this extraction hands fractions on (else the vertex stage gathers samples)
-#ifdef CX_FORCE_RING      // experiment: what the staging of the planes costs by itself
-        const bool stage_ring = true;
-#else
         const bool stage_ring = stage_t;
-#endif
         auto plane_bits = [&](const plane_raw& R, const uint32_t slot) -> uint32_t {
             // The sign bits are shifted in from the right, last row first: one v_alignbit_b32 per sample ({word, difference} >> 31 = the
             // word moved up by one with the sign bit of the difference behind it) instead of a shift and a shift-or; rows are
@@ -939,13 +872,6 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
                 }
                 const float dx = vx - P.vcmp, dy = vy - P.vcmp, dz = vz - P.vcmp, dw = vw - P.vcmp;
                 const float dh = hv - P.vcmp;
-#if CX_S1_SHIFT_OR      // A/B: a shift and a shift-or per sample
-                own |= (__float_as_uint(dx) >> 31) << (CX_ROWBITS * r + 0);
-                own |= (__float_as_uint(dy) >> 31) << (CX_ROWBITS * r + 1);
-                own |= (__float_as_uint(dz) >> 31) << (CX_ROWBITS * r + 2);
-                own |= (__float_as_uint(dw) >> 31) << (CX_ROWBITS * r + 3);
-                halo |= (__float_as_uint(dh) >> 31) << (CX_ROWBITS * r);
-#else
                 own <<= (CX_ROWBITS - 4u);                                     // the two unused places of the row above
                 own = __builtin_amdgcn_alignbit(own, __float_as_uint(dw), 31);   // bit 3 of the row
                 own = __builtin_amdgcn_alignbit(own, __float_as_uint(dz), 31);
@@ -953,7 +879,6 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
                 own = __builtin_amdgcn_alignbit(own, __float_as_uint(dx), 31);   // bit 0
                 halo <<= (CX_ROWBITS - 1u);
                 halo = __builtin_amdgcn_alignbit(halo, __float_as_uint(dh), 31);
-#endif
                 dnear = fminf(dnear, fminf(fminf(fabsf(dx), fabsf(dy)), fminf(fabsf(dz), fminf(fabsf(dw), fabsf(dh)))));
             }
             // k+1 neighbour of m=3: m=0 of the next lane; the last valid lane takes the halo sample or,
@@ -968,30 +893,8 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
         // issued all the same -- a branch around them makes the compiler wait for ALL outstanding loads at the next use, which undoes
         // the prefetch (measured: 0.126 -> 0.138 ms) -- but re-read plane ib, a cache hit, instead of the neighbour task's plane ib + 1
         // (rounds 1 and 2: one plane in ci + 2, 6 % of the kernel's HBM reads).
-        // CX_S1_DEPTH planes are in flight ahead of the one being worked on (a second one was tried in round 3: no gain, the kernel
-        // is not starved for samples).
-#if CX_S1_DEPTH == 2
-        plane_raw rawA, rawB, rawC;
-        load_plane(p, rawB);
-        load_plane(p + 1u, rawA);
-        load_plane(p + 2u, rawC);
-        uint32_t wprev = plane_bits(rawB, 0u);
-        // one step: plane p+1 is in `cur`, plane p+2 is on its way, plane p+3 is requested into `nxt` (whose plane is used up)
-        auto step = [&](const plane_raw& cur, plane_raw& nxt) {
-            load_plane(p + 3u, nxt);
-#elif CX_S1_DEPTH == 3
-        // TWO planes in flight with two buffers: a buffer is requested again right after its sign bits are taken (its samples are
-        // dead from then on), so while a step's active cells are worked on both the next plane and the one after are on their way
-        plane_raw rawA, rawB;
-        load_plane(p, rawB);
-        load_plane(p + 1u, rawA);
-        uint32_t wprev = plane_bits(rawB, 0u);
-        load_plane(p + 2u, rawB);
-        auto step = [&](plane_raw& cur, plane_raw& unused_) {
-            (void)unused_;
-            const uint32_t wcur = plane_bits(cur, (p + 1u - G.pstart) & 1u);
-            load_plane(p + 3u, cur);
-#else
+        // One plane is in flight ahead of the one being worked on.  Two planes in flight ahead: 0.131 against 0.125 ms, 168 registers;
+        // taken out (the kernel is not starved for samples).
         plane_raw rawA, rawB;
         load_plane(p, rawB);
         load_plane(p + 1u, rawA);
@@ -999,48 +902,29 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
         // one step: plane p+1 is in `cur` (loaded one step ago), plane p+2 is requested into `nxt`
         auto step = [&](const plane_raw& cur, plane_raw& nxt) {
             load_plane(p + 2u, nxt);
-#endif
-#if CX_S1_DEPTH != 3
             const uint32_t wcur = plane_bits(cur, (p + 1u - G.pstart) & 1u);
-#endif
             // per sample row: OR / AND over (k, k+1); then over rows (r, r+1); then over both planes
             const uint32_t op = wprev | (wprev >> 1), ap = wprev & (wprev >> 1);
             const uint32_t oc = wcur | (wcur >> 1), ac = wcur & (wcur >> 1);
             const uint32_t o = op | (op >> CX_ROWBITS) | oc | (oc >> CX_ROWBITS);
             const uint32_t a = ap & (ap >> CX_ROWBITS) & ac & (ac >> CX_ROWBITS);
             const uint32_t act0 = o & ~a & mr;
-#ifdef CX_S1_ABL
-            if (CX_S1_ABL == 2) { wprev = wcur; p++; return; }
-#endif
             if (__ballot(act0 != 0u) != 0ULL) {    // wave-uniform: some cell of this step has a sign change
-#if CX_S1_LAZY
                 // exclusive prefix of the lanes' cell counts by DPP row shifts (9 instructions; five ballots with their mbcnt pairs: 35)
                 const uint32_t cnt0 = __popc(act0);
                 const uint32_t incl0 = cx_wave_incl_scan(cnt0, lane);
                 const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl0, 63);
                 const uint32_t pre = incl0 - cnt0;
-#else
-                uint32_t tot;
-                const uint32_t pre = cx_wave_prefix_small<5>(__popc(act0), tot);
-#endif
                 const uint32_t sidx = p - G.pstart;
                 const uint32_t ebase = (lane << 15) | (sidx << 21);
                 // where the lane's cells of this step sit in the wave's queue, and which they are (bit 4r+m): lets the triangle stage
                 // find the queue entry of ANY active cell of the volume without a table per sample.  Straight to global memory, one
                 // coalesced 256-byte store per step that queued cells (round 3 staged all steps' words in 17 KB of LDS and wrote them
                 // out at the end, active or not; measured: the direct store is 3 % FASTER, and the LDS goes to the sample planes)
-#ifdef CX_S1_ABL
-                if (P.qa && CX_S1_ABL != 3) (P.qa + (size_t)w * (CX_SWP * 64u))[sidx * 64u + lane] =
-#else
                 if (P.qa) (P.qa + (size_t)w * (CX_SWP * 64u))[sidx * 64u + lane] =
-#endif
                     ((qn + pre) << 16) | (act0 & 0xFu) | ((act0 >> 2) & 0xF0u) | ((act0 >> 4) & 0xF00u) | ((act0 >> 6) & 0xF000u);
                 // The step's cells go through the entry stage in the order of the lanes; more than the stage holds (CX_SQ; up to 1024
                 // on white noise) go in two halves of the lanes -- the order in the queue is the same either way.
-#ifdef CX_S1_ABL      // timing experiments (tools/variants.sh + tools/stream_ab.py; the queues are garbage): 1 = the cells are counted but not
-                      // written to the stage, 2 = nothing of the active block at all, 3 = everything but the per-step queue word store
-                if (CX_S1_ABL == 1) { qn += tot; wprev = wcur; p++; return; }
-#endif
                 const uint32_t nhalf = (tot > CX_SQ) ? 2u : 1u;            // wave-uniform
                 const uint32_t mid = (uint32_t)__builtin_amdgcn_readlane((int)pre, 32);   // cells of lanes 0..31
                 const float* __restrict__ plo = &ring[sidx & 1u][0][0];          // sample plane p   (the cells' lower corners)
@@ -1063,7 +947,7 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
                     // of every crossing the cell owns, written to the wave's stream of fractions in the order the vertex stage numbers
                     // the vertices (cell after cell, direction after direction).
                     __builtin_amdgcn_wave_barrier();
-                    for (uint32_t o0 = 0; o0 < ((CX_S1_LAZY && !stage_t) ? 0u : ctot); o0 += 64u) {      // wave-uniform
+                    for (uint32_t o0 = 0; o0 < (stage_t ? ctot : 0u); o0 += 64u) {      // wave-uniform: without the fraction stream the cells are counted by count_pending
                         const uint32_t o = o0 + lane;
                         const bool have = o < ctot;
                         const uint32_t e = have ? q[ql + o] : 0u;
@@ -1121,31 +1005,19 @@ __device__ __forceinline__ void cx_stream_tile(const cx_params& P, const cx_task
             wprev = wcur;
             p++;
         };
-#if CX_S1_DEPTH == 2
-        while (p < ib) {
-            step(rawA, rawB);
-            if (p >= ib) break;
-            step(rawC, rawA);
-            if (p >= ib) break;
-            step(rawB, rawC);
-        }
-#else
         while (p < ib) {
             step(rawA, rawB);
             if (p >= ib) break;
             step(rawB, rawA);
         }
-#endif
     }
     if (qn > qstart) close_batch();
     flush_queue();
     flush_brec();
-#ifndef CX_S3_STAMPS
     if (stamp && lane == 0) stamp[1] = __builtin_amdgcn_s_memtime();
-#endif
     cx_run run;
     run.v = rv; run.t = rt; run.c = rc; run.b = cxd_wave_add(acc.b);
-    const bool near = __ballot(dnear <= P.near_abs) != 0ULL && !(P.flags & CX_DBG_NO_NEAR);   // wave-uniform
+    const bool near = __ballot(dnear <= P.near_abs) != 0ULL;   // wave-uniform
     bool really_near = false;
     if (near && qn != 0u && !overflow) {
         // a sample inside the screen: the reference's tolerance rules may drop tetrahedra or vertices.
@@ -1367,10 +1239,6 @@ __device__ __forceinline__ void cx_skip_rounds(const cx_params& P, const cx_fast
 #endif
 template <bool TQ, int DT>     // TQ: the interpolation fractions come from the stream kernel's stream (P.tq); else the samples are gathered here
 __global__ __launch_bounds__(256, CX_S3_MIN_WAVES) void cx_k_emit_vertices(const cx_params P, const cx_task T) {
-#ifdef CX_OCC_PAD   // experiment: fewer workgroups per CU (what does the time do with the occupancy?)
-    __shared__ uint32_t s_pad[CX_OCC_PAD / 4];
-    if (P.n0 == 0xFFFFFFFFu) reinterpret_cast<volatile uint32_t*>(s_pad)[threadIdx.x] = 1u;
-#endif
     __shared__ float4 s_vstage[4][CX_VSTAGE_LDS];
     __shared__ uint8_t s_ntri[256];
     s_ntri[threadIdx.x] = cx_d_voxel_ntri[threadIdx.x];
@@ -1387,10 +1255,6 @@ __global__ __launch_bounds__(256, CX_S3_MIN_WAVES) void cx_k_emit_vertices(const
     uint32_t f = P.rstart[blockIdx.x * 4u + wave];
     if (f >= nbatches) return;
     cx_bdesc D = P.flat[f];
-#ifdef CX_S3_STAMPS
-    unsigned long long tacc[4] = {0, 0, 0, 0}, nrounds = 0;
-    const unsigned long long tstart = __builtin_amdgcn_s_memrealtime();
-#endif
     for (;;) {   // waves are independent
         const uint32_t fn = f + 1u;
         cx_bdesc Dn = D;
@@ -1405,16 +1269,11 @@ __global__ __launch_bounds__(256, CX_S3_MIN_WAVES) void cx_k_emit_vertices(const
         uint64_t* __restrict__ info = P.info64 + D.qofs;
         if (!D.near) {
             if (r0) cx_skip_rounds(P, G, q, r0, lane, s_ntri, run);
-#ifdef CX_S3_STAMPS
-            nrounds += r1 - r0;
-            cx_emit_queue_fast<DT>(P, G, q, r0 * 64u, min(D.n, r1 * 64u), lane, run, reinterpret_cast<uint32_t*>(s_vstage[wave]), s_ntri, info, tacc);
-#else
             if (TQ)        // the fractions come from the stream kernel (the pointer is the wave's region minus its first vertex: indexed by GLOBAL vertex)
                 cx_emit_queue_t(P, G, q, r0 * 64u, min(D.n, r1 * 64u), lane, run, reinterpret_cast<uint32_t*>(s_vstage[wave]), s_ntri, info,
                                 reinterpret_cast<const uint32_t*>(P.tq) + ((size_t)D.w * T.wcap) - __builtin_amdgcn_readfirstlane(P.wbase[D.w].v));
             else
                 cx_emit_queue_fast<DT>(P, G, q, r0 * 64u, min(D.n, r1 * 64u), lane, run, reinterpret_cast<uint32_t*>(s_vstage[wave]), s_ntri, info);
-#endif
         } else if (r0 == 0u) {
             cx_process_queue<true, DT>(P, [&](uint32_t x) { return cx_entry_lin(P, G, q[x]); }, D.n, lane, true, run, reinterpret_cast<cx_vrec*>(s_vstage[wave]), info);
         }
@@ -1422,13 +1281,6 @@ __global__ __launch_bounds__(256, CX_S3_MIN_WAVES) void cx_k_emit_vertices(const
         f = fn;
         D = Dn;
     }
-#ifdef CX_S3_STAMPS
-    if (P.stamps && lane == 0) {   // per wave: start, end, time in the 4 parts of a round, rounds
-        unsigned long long* st = P.stamps + (size_t)(blockIdx.x * 4u + wave) * 8u;
-        st[0] = tstart; st[1] = __builtin_amdgcn_s_memrealtime();
-        st[2] = tacc[0]; st[3] = tacc[1]; st[4] = tacc[2]; st[5] = tacc[3]; st[6] = nrounds;
-    }
-#endif
 }
 
 // ---- CPython 3.10 tuple hash + 8-slot set order, used only with
@@ -1633,7 +1485,7 @@ __device__ __forceinline__ void cx_tri_fetch(const cx_params& P, const uint64_t*
 #pragma unroll
         for (uint32_t c2 = 0; c2 < 8; c2++) sup |= ((c2 & c) == c && c2 != c) ? (1u << c2) : 0u;
         uint2 pr = make_uint2(0u, 0u);
-        if (ntri && ((sm ^ sc) & sup) != 0u && !(P.flags & CX_DBG_NO_LOOKUP)) {
+        if (ntri && ((sm ^ sc) & sup) != 0u) {
             const uint32_t lc = lin + ((c & 4u) ? plane : 0u) + ((c & 2u) ? P.n2 : 0u) + (c & 1u);
             const uint64_t e = P.celltab[lc];
             pr = make_uint2((uint32_t)e, (uint32_t)(e >> 32));
@@ -1736,8 +1588,8 @@ __device__ __forceinline__ uint32_t cx_tri_phase1(const cx_params& P, LDS& L, ui
             kp0 = ((v0 == -1) ? ~1ULL : (uint64_t)(int64_t)v0) * CX_PY_P2;
             kp1 = ((v1 == -1) ? ~1ULL : (uint64_t)(int64_t)v1) * CX_PY_P2;
         }
-        bool exact = (P.flags & CX_DBG_HASH64) != 0u;
-        if (!exact) {
+        bool exact;
+        {
             // Fast form: only the LOW 32 bits of the corner hashes -- a probe step of the set order reads three bits five places
             // further up, so five steps fit.  A pair still on one slot after five steps, or a hash word of all ones (possibly
             // the hash CPython replaces by a constant), sends the whole wave through the 64-bit form below.
@@ -1837,40 +1689,26 @@ __device__ __forceinline__ void cx_tri_phase2(const cx_params& P, LDS& L, uint32
                 vi[sidx] = (int32_t)(pr.x + __popc(pr.y & ((1u << (cd >> 3)) - 1u)));
             }
         }
-        if (ok && !(P.flags & CX_DBG_NO_TRIS)) {
+        if (ok) {
             // 32-bit wrap-around on purpose: tfirst = first - rank may be "negative" when the wave's cells come from
             // different reservations (generic path); the sum is the triangle index again
             int32_t* out = P.tris + (size_t)(uint32_t)(L.u[wave].a.tfirst[cell] + j) * 3u;
-#if CX_NT_TRIS
             typedef int32_t cx_v3i __attribute__((ext_vector_type(3)));
             __builtin_nontemporal_store(cx_v3i{vi[0], vi[1], vi[2]}, reinterpret_cast<cx_v3i*>(out));
-#else
-            out[0] = vi[0]; out[1] = vi[1]; out[2] = vi[2];
-#endif
         }
     }
     __builtin_amdgcn_wave_barrier();
 }
 
-#ifndef CX_NT_RECS
-#define CX_NT_RECS 1     // the cell records are read once: nontemporal loads (A/B: ~1.5 %, within noise)
-#endif
+// the cell records are read once: nontemporal loads (against plain loads: ~1.5 %, within noise)
 __device__ __forceinline__ uint2 cx_load_record2(const uint2* p) {   // a slim record
-#if CX_NT_RECS
     const cx_v2u v = __builtin_nontemporal_load(reinterpret_cast<const cx_v2u*>(p));
     return make_uint2(v.x, v.y);
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ uint4 cx_load_record(const uint4* p) {
-#if CX_NT_RECS
     typedef uint32_t cx_v4u __attribute__((ext_vector_type(4)));
     const cx_v4u v = __builtin_nontemporal_load(reinterpret_cast<const cx_v4u*>(p));
     return make_uint4(v.x, v.y, v.z, v.w);
-#else
-    return *p;
-#endif
 }
 // one lane per cell record; waves walk the record array grid-stride (the record count lives on the device)
 #ifndef CX_K2_MIN_WAVES
@@ -1947,7 +1785,7 @@ __device__ __forceinline__ void cx_triq_issue(const cx_params& P, const cx_task&
     const bool m3 = (mm == 3u), r3 = (rr == 3u), pl = (ps + 1u == nsteps);
     const bool kfl = m3 && ls == 63u;
     // neighbour cells that own a crossing edge of this voxel (bit c), from the table
-    const uint32_t want = (ntri && !(P.flags & CX_DBG_NO_LOOKUP)) ? ((L.pats[sm].y >> 9) & 0x3Fu) : 0u;
+    const uint32_t want = ntri ? ((L.pats[sm].y >> 9) & 0x3Fu) : 0u;
     A.geo = want | (kfl ? 64u : 0u) | (r3 ? 128u : 0u) | (pl ? 256u : 0u) | (rr << 9) | (mm << 11);
     A.ij = ci * P.n1 + cj; A.ck = ck;
     // word index of the queue word of X + c in P.qa = [wave][plane step][lane]: a sum of one term per axis.  The neighbour
@@ -1963,11 +1801,7 @@ __device__ __forceinline__ void cx_triq_issue(const cx_params& P, const cx_task&
 #pragma unroll
     for (uint32_t c = 0; c < 6; c++) {
         A.qa[c] = 0;
-#ifdef CX_ABL_QA     // timing experiment: no queue-word gathers
-        if ((want >> c) & 1u) A.qa[c] = (idx[c] * 977u) & 0x00FFFFFFu;
-#else
         if ((want >> c) & 1u) A.qa[c] = cx_ld_u32_at(P.qa, idx[c] << 2);
-#endif
     }
 }
 // ... of a cell record (the record-walking kernel): the lattice point from its linear index
@@ -2030,11 +1864,7 @@ __device__ __forceinline__ void cx_triq_stage2(const cx_params& P, const cx_task
             const uint32_t qa = A.qa[c];
             const uint32_t below = qa & ((1u << bit[c]) - 1u);     // bit[c] <= 15: only bits of the 16-bit set
             const uint32_t at = qb[c] + (qa >> 16) + __popc(below);
-#ifdef CX_ABL_INFO   // timing experiment: no info-word gathers
-            const uint64_t e = ((uint64_t)0xFE << 32) | (uint64_t)at;
-#else
             const uint64_t e = P.info64[at];
-#endif
             pr = make_uint2((uint32_t)e, (uint32_t)(e >> 32));   // (bits above the crossing mask ride along: phase 2 only looks below bit 8.  No arithmetic on the loaded word here -- it would put a wait behind every gather)
         }
         I.nb[c] = pr;
@@ -2062,10 +1892,6 @@ __device__ __forceinline__ void cx_triq_pin2(cx_tri_in& I) {
 #endif
 template <bool NEG_ORIGIN, bool SLIM>   // SLIM: 8-byte records + P.cbase (cx_store_cell_record); else the 16-byte records (cx_extract3d_levels)
 __global__ __launch_bounds__(256, CX_K2Q_MIN_WAVES) void cx_k_emit_triangles_q(const cx_params P, const cx_task T, const uint64_t* __restrict__ hash_xy) {
-#ifdef CX_OCC_PAD   // experiment: fewer workgroups per CU (what does the time do with the occupancy?)
-    __shared__ uint32_t s_pad[CX_OCC_PAD / 4];
-    if (P.n0 == 0xFFFFFFFFu) reinterpret_cast<volatile uint32_t*>(s_pad)[threadIdx.x] = 1u;
-#endif
     __shared__ cx_tri_lds L;
     const uint32_t ncells = min(P.counters[CX_CNT_CELLS], P.ccap);
     if (P.counters[CX_CNT_TRIS] > P.tcap || P.counters[CX_CNT_VERTS] > P.vcap) return;  // host re-runs with more room
@@ -2118,15 +1944,9 @@ __global__ __launch_bounds__(256, CX_K2Q_MIN_WAVES) void cx_k_emit_triangles_q(c
         cx_triq_stage1(P, T, L, valid(rec_c, nidx + stride), Ac);   // queue words of the record two steps ahead
         cx_triq_stage2(P, T, hash_xy, Ab, Ib);              // info words (and hash prefixes) of the next record
         const uint32_t ttot = cx_tri_phase1<NEG_ORIGIN, SLIM>(P, L, lane, wave, Ia);
-#if CX_PIN_BEFORE_STORES
-        cx_triq_pin1(Ac, rec_d);                            // ... all back before the stores go out
-        cx_triq_pin2(Ib);
-        cx_tri_phase2(P, L, lane, wave, ttot);
-#else
         cx_tri_phase2(P, L, lane, wave, ttot);
         cx_triq_pin1(Ac, rec_d);                            // ... waited for after the stores went out
         cx_triq_pin2(Ib);
-#endif
         Ia = Ib;
         Ab = Ac;
         rec_c = rec_d;
@@ -2297,13 +2117,8 @@ __global__ __launch_bounds__(256, CX_K2E_MIN_WAVES) void cx_k_emit_triangles_e(c
         stage1(Rc, Ac);                                      // queue words of the round two steps ahead
         cx_triq_stage2(P, T, hash_xy, Ab, Ib);               // info words (and hash prefixes) of the next round
         const uint32_t ttot = cx_tri_phase1<NEG_ORIGIN>(P, L, lane, wave, Ia);
-#if CX_PIN_BEFORE_STORES
-        cx_triq_pin1(Ac, dummy); cx_triq_pin2(Ib); cx_eraw_pin(Rd);
-        cx_tri_phase2(P, L, lane, wave, ttot);
-#else
         cx_tri_phase2(P, L, lane, wave, ttot);
         cx_triq_pin1(Ac, dummy); cx_triq_pin2(Ib); cx_eraw_pin(Rd);
-#endif
         Ia = Ib;
         Ab = Ac;
         Rc = Rd;
@@ -2468,7 +2283,7 @@ __device__ __forceinline__ void cx_mesh_stage1(const cx_params& P, const cx_task
 #pragma unroll
         for (uint32_t c2 = 0; c2 < 8; c2++) sup |= ((c2 & c) == c && c2 != c) ? (1u << c2) : 0u;
         S.nb[c - 1u] = 0;
-        if (voxel && ((sm ^ sc) & sup) != 0u && !(P.flags & CX_DBG_NO_LOOKUP)) {
+        if (voxel && ((sm ^ sc) & sup) != 0u) {
             const uint32_t wsel = (dk ? kfl : 0u) | ((dj ? r3 : 0u) << 1) | ((di ? pl : 0u) << 2);
             const uint32_t qa = P.qa[qab[wsel] + pofs[di] + lane_k[dk]];
             // low 16 bits: the active cells below Y in its lane (their count completes the queue position)
@@ -2527,7 +2342,6 @@ __device__ __forceinline__ void cx_mesh_stage2(const cx_params& P, const cx_task
         R.e2[r] = (uint32_t)__shfl((int)e, (int)(R.sl[r] >> 3));
         const uint32_t d = R.sl[r] & 7u;
         const uint32_t lin2 = cx_entry_lin(P, G, R.e2[r]);
-        if (P.flags & CX_DBG_NO_VLOADS) { R.f0[r] = -1.0f; R.f1[r] = (float)lin2; continue; }
         R.f0[r] = A[lin2];
         R.f1[r] = A[lin2 + ((d & 4u) ? plane : 0u) + ((d & 2u) ? P.n2 : 0u) + (d & 1u)];
     }
@@ -2666,7 +2480,7 @@ __global__ __launch_bounds__(256, CX_EM_MIN_WAVES) void cx_k_emit_mesh(const cx_
 #pragma unroll
                 for (uint32_t r = 0; r < CX_VR; r++) {
                     const uint32_t o = 64u * r + lane;
-                    if (o < Ra.vtot && !(P.flags & CX_DBG_NO_VERTS)) CX_STORE_VERT(&P.verts[Ra.vbase + o], rec4[r]);
+                    if (o < Ra.vtot) CX_STORE_VERT(&P.verts[Ra.vbase + o], rec4[r]);
                 }
                 const uint32_t* slot = L.vslot[wave][par];
                 for (uint32_t o0 = 64u * CX_VR; o0 < Ra.vtot; o0 += 64u) {   // more than CX_VR x 64 vertices: the rest one round at a time

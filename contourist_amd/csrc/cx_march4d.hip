@@ -659,9 +659,6 @@ __device__ __forceinline__ void cx_tets_group(const cx_params4& P, cx_tet_lds& L
     }
     __builtin_amdgcn_wave_barrier();
     // ---- phase 2: one lane per tetrahedron
-#ifdef CX4_ABL_P2   // timing experiments (tools/variants.sh + tools/ab4d.py): no phase 2 / CX4_ABL_STORE 1 no stores, 2 plain stores
-    if (P.tcap != 12345u) return;
-#endif
     for (uint32_t j0 = 0; j0 < ttot; j0 += 64u) {   // wave-uniform
         const uint32_t j = j0 + lane;
         const bool ok = j < ttot;
@@ -687,14 +684,11 @@ __device__ __forceinline__ void cx_tets_group(const cx_params4& P, cx_tet_lds& L
             const uint32_t vf = L.vf[wave][cell][c1], em = L.em[wave][cell][c1];
             tv[s_] = (int32_t)(vf + __popc(em & ((1u << d) - 1u)));
         }
-#ifndef CX4_ABL_STORE
-#define CX4_ABL_STORE 0
-#endif
-        if (ok && (CX4_ABL_STORE != 1 || tv[0] == 0x7FFFFFF)) {   // not read again by the pipeline: nontemporal (see cx_march3d.hip)
+        if (ok) {   // not read again by the pipeline: nontemporal (see cx_march3d.hip)
             typedef int32_t cx_v4i __attribute__((ext_vector_type(4)));
             cx_v4i* dst = reinterpret_cast<cx_v4i*>(P.tets + (size_t)(tnext + j) * 4u);   // the round's tetrahedra, group after group
             const cx_v4i val = cx_v4i{tv[0], tv[1], flip ? tv[3] : tv[2], flip ? tv[2] : tv[3]};
-            if (CX4_ABL_STORE == 2) *dst = val; else __builtin_nontemporal_store(val, dst);
+            __builtin_nontemporal_store(val, dst);
         }
     }
     tnext += ttot;

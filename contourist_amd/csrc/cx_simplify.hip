@@ -185,10 +185,6 @@ __global__ __launch_bounds__(256) void cxs_k_accumulate(const double* __restrict
     if (__ballot(nclamp != 0u) != 0ULL) {                   // (never, for a mesh inside its grid box)
         if (nclamp) atomicAdd(clamped, nclamp);
     }
-#ifdef CXS_ABL_NOWAVE
-    // ablation (tools/bench_simplify.py): every lane on its own, to show what the reduction within the wave buys
-    if (active) cxs_lane_atomics(acc + (size_t)id * CXS_WORDS, 1ULL, X[0], X[1], X[2], nrm != nullptr, N[0], N[1], N[2]);
-#else
     const uint32_t lane = threadIdx.x & 63u;
     uint64_t rem = __ballot(active);
     while (rem != 0ULL) {                                   // wave-uniform
@@ -206,7 +202,6 @@ __global__ __launch_bounds__(256) void cxs_k_accumulate(const double* __restrict
         if (nrm) { m0 = cxd_wave_add(mine ? N[0] : 0LL); m1 = cxd_wave_add(mine ? N[1] : 0LL); m2 = cxd_wave_add(mine ? N[2] : 0LL); }   // (nrm: uniform)
         if ((int)lane == leader) cxs_lane_atomics(acc + (size_t)k * CXS_WORDS, (u64)__popcll(grp), s0, s1, s2, nrm != nullptr, m0, m1, m2);
     }
-#endif
 }
 // one lane per cluster: double(sum) rounded once, / double(n), * 2^-q; the normal sum normalised in float64 ((0,0,0) for a zero sum)
 __global__ void cxs_k_finish(const u64* __restrict__ acc, uint32_t ncl, cxs_params P, double* __restrict__ pts2, double* __restrict__ nrm2) {

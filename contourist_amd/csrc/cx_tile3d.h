@@ -79,7 +79,7 @@ __device__ __forceinline__ void cx_tile_front(const cx_params& P, const cx_fast_
     }
     brank += (uint32_t)__popcll(bm);
     const uint32_t ntri_e = bnd ? 0u : ntri;
-    const uint32_t want = (ntri_e && !(P.flags & CX_DBG_NO_LOOKUP)) ? ((pats[sm].y >> 9) & 0x3Fu) : 0u;
+    const uint32_t want = ntri_e ? ((pats[sm].y >> 9) & 0x3Fu) : 0u;
 #pragma unroll
     for (uint32_t c = 1; c < 7; c++) {
         const uint32_t dk = c & 1u, dj = (c >> 1) & 1u, di = c >> 2;
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256, CX_TILE_MIN_WAVES) void cx_k_tile_emit(const c
 #pragma unroll
             for (uint32_t r = 0; r < CX_VR; r++) {
                 const uint32_t o = 64u * r + lane;
-                if (o < Ra.vtot && !(P.flags & CX_DBG_NO_VERTS)) CX_STORE_VERT(&P.verts[Ra.base.v + o], rec4[r]);
+                if (o < Ra.vtot) CX_STORE_VERT(&P.verts[Ra.base.v + o], rec4[r]);
             }
             for (uint32_t o0 = 64u * CX_VR; o0 < Ra.vtot; o0 += 64u) {   // more than CX_VR x 64 vertices: the rest one round at a time
                 const uint32_t o = o0 + lane;
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256, CX_TILE_MIN_WAVES) void cx_k_tile_emit(const c
                 const uint32_t cell = sl >> 3, d = sl & 7u;
                 const uint32_t e2 = (uint32_t)__shfl((int)Ra.e, (int)cell);
                 const cx_vrec r4 = cx_vertex_record(P, G, e2, d, corners[cell * CX_CORNER_ROW], corners[cell * CX_CORNER_ROW + d]);
-                if (o < Ra.vtot && !(P.flags & CX_DBG_NO_VERTS)) CX_STORE_VERT(&P.verts[Ra.base.v + o], r4);
+                if (o < Ra.vtot) CX_STORE_VERT(&P.verts[Ra.base.v + o], r4);
             }
             // what pass B (and the boundary kernel) look up: the cell's word per queue entry, the word per (plane step, lane)
             {
@@ -349,7 +349,7 @@ __device__ __forceinline__ void cx_tile_fetch_faces(const cx_params& P, const cx
     const uint32_t cj = cx_div(r, P.div_row);
     const uint32_t ck = r - cj * P.n2;
     const bool jface = (cj & 7u) == 7u;     // on the high j face of its half tile: every neighbour is in a face row (else: in a face column)
-    const uint32_t want = (ntri && !(P.flags & CX_DBG_NO_LOOKUP)) ? ((pats[sm].y >> 9) & 0x3Fu) : 0u;
+    const uint32_t want = ntri ? ((pats[sm].y >> 9) & 0x3Fu) : 0u;
 #pragma unroll
     for (uint32_t c = 1; c < 7; c++) {
         uint2 pr = make_uint2(0u, 0u);

@@ -85,6 +85,42 @@ def test_unknown_flag_bits_are_rejected():
         ctx.close()
 
 
+_FLAG_BITS_CHILD = """
+import sys
+sys.path.insert(0, {root!r})
+import numpy as np
+from contourist_amd import _ffi
+from oracle import level0
+A = np.random.RandomState(17).standard_normal((8, 8, 8)).astype(np.float32)
+O = level0.march3d(A, 0.1, diag_mode=0)
+ctx = _ffi.Context(0)
+ctx.upload_grid(A)
+for bad in (0x10000, 0x20000, 0x40000, 0x80000, 0x100000, 0x200000, 0x400000, 0x800000, 0x1000000, 0x2000000, 0x4000000):
+    try:
+        ctx.extract3d(0.1, bad)
+    except _ffi.CxError as e:
+        assert e.code == -1, (hex(bad), e.code)      # CX_ERR_INVALID
+    else:
+        raise AssertionError("flag bit %#x was accepted" % bad)
+c = ctx.extract3d(0.1, 0)
+assert c["n_vertices"] == len(O["pairs"]) and c["n_triangles"] == len(O["tris"]) and c["n_triangles"] > 0, c
+ctx.close()
+print("FLAG_BITS_OK", c["n_vertices"], c["n_triangles"])
+"""
+
+
+def test_former_ablation_bits_are_rejected_with_debug_on():
+    """the eleven bits that once switched parts of the kernels off are unknown flags in EVERY process, one started with
+    CX_DEBUG=1 included (hence the child process): CX_ERR_INVALID for each, and the context extracts the oracle's counts afterwards"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _FLAG_BITS_CHILD.format(root=root)], env=dict(os.environ, CX_DEBUG="1"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert any(ln.startswith("FLAG_BITS_OK") for ln in r.stdout.splitlines()), r.stdout[-2000:]
+
+
 @pytest.mark.parametrize("shape,generic", [((37, 41, 52), False), ((37, 41, 52), True), ((29, 23, 67), False), ((64, 64, 64), False)])
 def test_exact_capacities(shape, generic):
     """cx_reserve with exactly the counts of the surface (ccap == n_cells, vcap == n_vertices, tcap == n_triangles) on

@@ -3,21 +3,15 @@
 call and cached) and `keep largest 1`, next to cx_postprocess3d and cx_level1_normals of the same mesh in the same process.  Warm
 context, 3 warm + `reps` timed calls between HIP events on the context's stream.  The measure kernel reads 12 + 72 bytes per
 triangle: the rate of the whole call (accumulator reset, measure kernel, vertex count, finish: the measure kernel is all but a few
-microseconds of it) is printed next to the streaming-read figure of cx_measure_read_bandwidth on the same device.  With
-CX_COMP_ABLATION_LIB=<library built with -DCXC_ABL_NOWAVE> the measures are timed once more in a child process that loads it (every
-lane issues its own atomics), to show what the reduction within the wave buys.  Such a library is made next to the normal one by
-    CX_EXTRA_FLAGS=-DCXC_ABL_NOWAVE python -m contourist_amd.build
-    cp contourist_amd/lib/libcontourist_hip.so contourist_amd/lib/libcontourist_hip_nowave.so
-    python -m contourist_amd.build          # the normal library again (objects built with extra flags are never reused)
+microseconds of it) is printed next to the streaming-read figure of cx_measure_read_bandwidth on the same device.
 Prints one JSON line and writes it to profiles/bench_components_<size>.json."""
-import ctypes, json, os, statistics, subprocess, sys
+import ctypes, json, os, statistics, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
 import torch
 from contourist_amd import _ffi, synthetic
 size = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-only_measure = len(sys.argv) > 3 and sys.argv[3] == "measure"
 dev = torch.device("cuda", 0)
 A = synthetic.smooth_noise_torch((size,) * 3, 1235, 1400, dev)
 ctx = _ffi.Context(0, stream=torch.cuda.current_stream().cuda_stream)
@@ -51,12 +45,9 @@ def measures(k):
 
 ctx._check_attr(ctx.lib.cx_level1_component_labels(ctx.handle, ctypes.byref(lab), None))
 nt, nv = int(post["n_triangles"]), int(post["n_vertices"])
-first = timed(measures, n=3 if only_measure else reps)
+first = timed(measures)
 out = {"size": size, "reps": reps, "device": torch.cuda.get_device_name(0), "level1": post, "measures_first_call": first,
        "measure_bytes_per_triangle": 84, "measures_call_GB_per_s": round(nt * 84 / first["median_ms"] / 1e6, 1)}
-if only_measure:
-    print(json.dumps({"measures_first_call": first}))
-    sys.exit(0)
 out["measures_cached"] = timed(lambda k: ctx.lib.cx_level1_components(ctx.handle, md[0].ctypes.data, ctypes.byref(nc), ctypes.byref(tab), None))
 out["components"] = int(nc.value)
 out["normals"] = timed(lambda k: ctx.lib.cx_level1_normals(ctx.handle, None, ctypes.byref(tab)))
@@ -74,13 +65,6 @@ out["largest"] = {"triangles": int(table["triangles"].max()), "kept_vertices": i
 out["read_bandwidth_GB_per_s"] = round(float(ctx.measure_read_bandwidth(A.data_ptr(), A.numel() * 4, 5)), 1)     # the grid, 512 MB
 out["measures_fraction_of_read_bandwidth"] = round(out["measures_call_GB_per_s"] / out["read_bandwidth_GB_per_s"], 3)
 ctx.close()
-abl = os.environ.get("CX_COMP_ABLATION_LIB")
-if abl and os.path.exists(abl):
-    env = dict(os.environ, CX_DEBUG="1", CX_LIB_PATH=abl)
-    env.pop("CX_COMP_ABLATION_LIB")
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), str(size), "3", "measure"], env=env, capture_output=True, text=True, timeout=600)
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-    out["measures_without_wave_reduction"] = json.loads(line[-1])["measures_first_call"] if line else {"error": r.stderr[-300:]}
 line = json.dumps(out)
 print(line)
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bench_components_%d.json" % size), "w") as f:

@@ -3,22 +3,15 @@
 and 8 with and without carried normals, the dry run, and a `target_triangles` search for 1 M triangles, next to cx_postprocess3d and
 cx_level1_normals of the same mesh in the same process.  Warm context, 3 warm + `reps` timed calls between HIP events on the
 context's stream.  A simplification consumes its input, so every timed call is preceded by an untimed cx_postprocess3d (and, with
-normals, cx_level1_normals and the component labels, which the call would otherwise make itself: they are timed on their own).  With
-CX_SIMPLIFY_ABLATION_LIB=<library built with -DCXS_ABL_NOWAVE> the cell-4 calls are timed once more in a child process that loads it
-(every lane of the accumulate kernel issues its own atomics), to show what the reduction within the wave buys.  Such a library is
-made next to the normal one by
-    CX_EXTRA_FLAGS=-DCXS_ABL_NOWAVE python -m contourist_amd.build
-    cp contourist_amd/lib/libcontourist_hip.so contourist_amd/lib/libcontourist_hip_nowave.so
-    python -m contourist_amd.build          # the normal library again (objects built with extra flags are never reused)
+normals, cx_level1_normals and the component labels, which the call would otherwise make itself: they are timed on their own).
 Prints one JSON line and writes it to profiles/bench_simplify_<size>.json."""
-import ctypes, json, os, statistics, subprocess, sys
+import ctypes, json, os, statistics, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
 import torch
 from contourist_amd import _ffi, synthetic
 size = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
-only_cell4 = len(sys.argv) > 3 and sys.argv[3] == "cell4"
 dev = torch.device("cuda", 0)
 A = synthetic.smooth_noise_torch((size,) * 3, 1235, 1400, dev)
 ctx = _ffi.Context(0, stream=torch.cuda.current_stream().cuda_stream)
@@ -63,14 +56,11 @@ def simplify(cell, flags):
 
 few = max(3, reps // 4)
 out = {"size": size, "reps": reps, "device": torch.cuda.get_device_name(0), "level1": post}
-for cell in ([4.0] if only_cell4 else [2.0, 4.0, 8.0]):
+for cell in (2.0, 4.0, 8.0):
     for normals in (False, True):
         name = "cell_%g%s" % (cell, "_normals" if normals else "")
         out[name] = timed(simplify(cell, _ffi.CX_SIMPLIFY_NORMALS if normals else 0), n=few, before=restore(normals))
         out[name].update(vertices=int(sc[0]), triangles=int(sc[1]), clusters=int(sc[6]), distinct=int(sc[7]))
-if only_cell4:
-    print(json.dumps({k: out[k] for k in ("cell_4", "cell_4_normals")}))
-    sys.exit(0)
 restore(False)(0)
 out["dry_run_cell_4"] = timed(simplify(4.0, _ffi.CX_SIMPLIFY_COUNT_ONLY))
 out["postprocess3d"] = timed(lambda k: ctx.lib.cx_postprocess3d_ex(ctx.handle, 0, 0.0, counts.ctypes.data), n=few)
@@ -98,13 +88,6 @@ out["target_triangles_1M"] = timed(search, n=few, before=restore(False))
 out["target_triangles_1M"].update(cell=found["cell"][0], triangles=found["n_triangles"], dry_runs=len(owner._simplify_search))
 out["cell_4_over_postprocess3d"] = round(out["cell_4"]["median_ms"] / out["postprocess3d"]["median_ms"], 3)
 ctx.close()
-abl = os.environ.get("CX_SIMPLIFY_ABLATION_LIB")
-if abl and os.path.exists(abl):
-    env = dict(os.environ, CX_DEBUG="1", CX_LIB_PATH=abl)
-    env.pop("CX_SIMPLIFY_ABLATION_LIB")
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), str(size), str(reps), "cell4"], env=env, capture_output=True, text=True, timeout=600)
-    line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-    out["without_wave_reduction"] = json.loads(line[-1]) if line else {"error": r.stderr[-300:]}
 line = json.dumps(out)
 print(line)
 with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "bench_simplify_%d.json" % size), "w") as f:

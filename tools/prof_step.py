@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """a few Level-0 extractions of the bench field, for rocprofv3 counter passes"""
 import os, sys
-os.environ.setdefault("CX_DEBUG", "1")   # ablation flags and tuning knobs are refused otherwise
+os.environ.setdefault("CX_DEBUG", "1")   # tuning knobs and CX_LIB_PATH are ignored otherwise
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
 from contourist_amd import _ffi, synthetic

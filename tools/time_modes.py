@@ -2,7 +2,7 @@
 """per-kernel timing (median of rounds, interleaved in one process) of the Level-0 paths: fused / staged emit,
 CPython-order / canonical diagonals"""
 import os, sys
-os.environ.setdefault("CX_DEBUG", "1")   # ablation flags and tuning knobs are refused otherwise
+os.environ.setdefault("CX_DEBUG", "1")   # tuning knobs and CX_LIB_PATH are ignored otherwise
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import torch
 from contourist_amd import _ffi, synthetic
@@ -18,26 +18,10 @@ if len(sys.argv) > 2 and sys.argv[2] == "quick":
     modes = [(1 | 0x400, "fused"), (0x400, "fused canon"), (1, "staged"), (0, "staged canon")]
 if len(sys.argv) > 2 and sys.argv[2] == "tiled":
     modes = [(1 | 0x800, "tiled"), (1 | 0x200, "staged"), (0x800, "tiled canon"), (0x200, "staged canon")]
-if len(sys.argv) > 2 and sys.argv[2] == "tiled_ablate":
-    F = 0x800
-    modes = [(F | 1, "tiled"), (F, "tiled canon"), (F | 0x1000000, "canon no_vloads"), (F | 0x400000, "canon no_tris"), (F | 0x80000, "canon no_verts"),
-             (F | 0x200000, "canon no_lookup"), (F | 0x1000000 | 0x80000, "canon no_vloads no_verts"), (F | 0x1000000 | 0x80000 | 0x400000, "canon alu+lds only")]
 if len(sys.argv) > 2 and sys.argv[2] == "staged":
     modes = [(1, "staged"), (0, "staged canon")]
-if len(sys.argv) > 2 and sys.argv[2] == "hash":
-    modes = [(1, "staged"), (0, "staged canon"), (1 | 0x200000, "cpython no_lookup"), (0x200000, "canon no_lookup")]
 if len(sys.argv) > 2 and sys.argv[2] == "fused":
     modes = [(1 | 0x400, "fused"), (0x400, "fused canon")]
-if len(sys.argv) > 2 and sys.argv[2] == "ablate_staged":
-    S = 0x200
-    modes = [(S | 1, "staged"), (S, "staged canon"), (S | 0x40000, "canon no_celltab"), (S | 0x40000 | 0x100000, "canon no_celltab no_cells"),
-             (S | 0x200000, "canon no_lookup"), (S | 0x400000, "canon no_tris"), (S | 0x200000 | 0x400000, "canon no_lookup no_tris"),
-             (S | 0x80000, "canon no_verts"), (S | 0x1000000, "canon no_vloads")]
-if len(sys.argv) > 2 and sys.argv[2] == "ablate":
-    F = 0x400
-    modes = [(F | 1, "fused"), (F, "fused canon"), (F | 0x200000, "canon no_lookup"), (F | 0x1000000, "canon no_vloads"),
-             (F | 0x80000, "canon no_verts"), (F | 0x400000, "canon no_tris"), (F | 0x80000 | 0x400000, "canon no_stores"),
-             (F | 0x200000 | 0x1000000, "canon no_loads"), (F | 0x200000 | 0x1000000 | 0x80000 | 0x400000, "canon alu only")]
 res = {name: [] for _, name in modes}
 for rnd in range(7):
     for fl, name in modes:
