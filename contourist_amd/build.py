@@ -53,9 +53,14 @@ def build(force=False, verbose=False):
             os.remove(stamp)
         cmds.append(cmd)
     if cmds:
-        # translation units are independent: compile them side by side (8 cores here, 16 on a GPU box)
+        # translation units are independent: compile them side by side, MAX_JOBS at a time when that is set, else one per CPU and at
+        # most 16 (a machine may grant a build fewer CPUs than it counts)
         from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=min(len(cmds), os.cpu_count() or 4)) as pool:
+        try:
+            jobs = max(1, int(os.environ["MAX_JOBS"]))
+        except (KeyError, ValueError):
+            jobs = min(os.cpu_count() or 4, 16)
+        with ThreadPoolExecutor(max_workers=min(len(cmds), jobs)) as pool:
             list(pool.map(subprocess.check_call, cmds))
     subprocess.check_call([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", OUT] + objs)
     return OUT

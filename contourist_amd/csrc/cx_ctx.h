@@ -29,7 +29,7 @@ static inline unsigned long long cx_table_size(size_t n) {
     return s;
 }
 
-struct cx_post_state;  // Level-1 buffers (cx_post.hip)
+struct cx_post_state;  // Level-1 buffers (cx_post.h)
 struct cx_state4;       // 4-D march state (cx_api4d.hip)
 struct cx_state2;       // 2-D contour lines (cx_contour2d.hip)
 struct cx_levels_state; // several isovalues of one grid (cx_levels.hip)

@@ -99,7 +99,7 @@ __device__ __forceinline__ double cxd_to_double128(u64 lo, u64 hi, int q) {
 
 // ---- lock-free union-find -------------------------------------------------------------------------------------------------------------
 // The rule for EVERY union-find in global memory here, whatever the width of its parent words (uint32_t below; the u64 words of
-// cxp_find / cxp_union and cxp_find0 / cxp_union0 in cx_post.hip; cxt_root / cxt_union in cx_topo.hip): every access to a parent word
+// cxp_find / cxp_union and cxp_find0 / cxp_union0 further down; cxt_root / cxt_union in cx_topo.hip): every access to a parent word
 // inside the kernel that unites is a device-scope atomic, loads and path-shortening writes included.  The L2s of the 8 XCDs are not
 // coherent with each other inside a kernel, and a version with plain loads and plain path-halving stores showed a rare wrong winding
 // of one component (stale lines mixing with memory-side compare-and-swaps).
@@ -134,4 +134,95 @@ __device__ __forceinline__ uint32_t cxd_uf_find_lds(uint32_t* lp, uint32_t x) {
         if (g != p) atomicCAS(&lp[x], p, g);
         x = p;
     }
+}
+
+// ---- the post-pass files' primitives (cx_post.hip, cx_post4d.hip, cx_morph.hip): a wave-wide maximum, union-find over u64 parent words,
+// the slot of an edge in the edge tables.  They keep the prefix they had in cx_post.hip ----------------------------------------------
+// monotonic maximum (cxd_max64) for a whole wave: when all its lanes share one key (component) they reduce among themselves and issue
+// ONE atomic; a wave that straddles components falls back to one call per lane.  (With values that grow along
+// the array -- vertices ordered by x -- the plain read alone does not help: every caller raises the maximum.)
+// All lanes of the wave must call it; `active` masks the idle ones.
+__device__ __forceinline__ void cxp_wave_max64(u64* table, uint32_t key, u64 v, bool active) {
+    const uint64_t act = __ballot(active);
+    if (act == 0ULL) return;
+    const uint32_t k = (uint32_t)__shfl((int)key, __ffsll((long long)act) - 1);
+    if (__ballot(active && key != k) != 0ULL) {   // wave-uniform
+        if (active) cxd_max64(&table[key], v);
+        return;
+    }
+    u64 m = active ? v : 0ULL;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)m, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(m >> 32), o);
+        const u64 other = ((u64)hi << 32) | lo;
+        m = other > m ? other : m;
+    }
+    if ((threadIdx.x & 63u) == 0u) cxd_max64(&table[k], m);
+}
+
+// union-find over 32-bit ids; parent word = (parity << 32) | parent id.  Root = smallest priority.
+__device__ __forceinline__ uint32_t cxp_find(const u64* parent, uint32_t x, uint32_t& parity) {
+    uint32_t par = 0;
+    for (;;) {
+        const u64 w = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t p = (uint32_t)w;
+        if (p == x) break;
+        par ^= (uint32_t)(w >> 32) & 1u;
+        x = p;
+    }
+    parity = par;
+    return x;
+}
+// link the sets of a and b; rel = parity between a and b (0: same winding class).
+// Every access to the parent words is a device-scope atomic, loads included (why: cx_dev.h, above cxd_uf_find).
+__device__ __forceinline__ void cxp_union(u64* parent, const uint32_t* prio, uint32_t a, uint32_t b, uint32_t rel) {
+    for (;;) {
+        uint32_t pa, pb;
+        uint32_t ra = cxp_find(parent, a, pa), rb = cxp_find(parent, b, pb);
+        if (ra == rb) return;
+        const uint32_t ka = prio ? prio[ra] : ra, kb = prio ? prio[rb] : rb;
+        const bool a_wins = (ka < kb) || (ka == kb && ra < rb);
+        const uint32_t win = a_wins ? ra : rb, lose = a_wins ? rb : ra;
+        const u64 expect = (u64)lose;                                  // still a root, parity 0
+        const u64 desired = ((u64)((pa ^ pb ^ rel) & 1u) << 32) | (u64)win;
+        if (atomicCAS(&parent[lose], expect, desired) == expect) return;
+    }
+}
+
+// The same for forests without parities and priorities (connectivity only: the march's own meshes), with path HALVING: on the way
+// up every node is pointed at its grandparent -- with a device-scope store, which is executed where the compare-and-swaps are, so
+// the two cannot disagree (cx_dev.h, above cxd_uf_find) -- and only ever at an ancestor.  Most unions of a large component find both sides in one
+// tree already; without the halving each of them walks the whole chain again (roots are the smallest ids, not the flattest trees).
+__device__ __forceinline__ uint32_t cxp_find0(u64* parent, uint32_t x) {
+    for (;;) {
+        const uint32_t p = (uint32_t)__hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (p == x) return x;
+        const uint32_t g = (uint32_t)__hip_atomic_load(&parent[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (g == p) return p;
+        __hip_atomic_store(&parent[x], (u64)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = g;
+    }
+}
+__device__ __forceinline__ void cxp_union0(u64* parent, uint32_t a, uint32_t b) {
+    for (;;) {
+        const uint32_t ra = cxp_find0(parent, a), rb = cxp_find0(parent, b);
+        if (ra == rb) return;
+        const uint32_t win = min(ra, rb), lose = max(ra, rb);
+        if (atomicCAS(&parent[lose], (u64)lose, (u64)win) == (u64)lose) return;
+        a = ra; b = rb;       // somebody else moved the loser: go on from the roots seen so far
+    }
+}
+
+// edge table: slot s = (key at tab[2s], first triangle at tab[2s+1]) -- one cache line per probe.
+// Slots are placed by the SMALLER vertex id (lo * mult + a few bits of the larger one): vertex ids follow the
+// order of the march, so the triangles of a wave probe neighbouring lines instead of random ones.
+// Device-scope atomics are executed at the memory side of the fabric (64 bytes of write traffic each, ~21 G/s for
+// the whole chip: PMC TCC_ATOMIC / WRITE_SIZE), so they are what this stage is bound by: ONE read-modify-write per
+// edge visit claims the key, the claimant publishes its triangle with a plain store (kernel 1); after the kernel
+// boundary every other visitor finds the slot again with plain loads and links itself to the claimant (kernel 2).
+// (mult == 0: plain hashing -- the small first table of cxp_k_edges_block, where the edges that arrive are the ones around merged
+// vertices, clustered in space: rows per vertex ran into each other there, chains of hundreds of probes)
+__device__ __forceinline__ u64 cxp_edge_slot(uint32_t lo, uint32_t hi, u64 mask, u64 mult) {
+    if (mult == 0) return cxd_mix(((u64)lo << 32) | (u64)hi) & mask;
+    return ((u64)lo * mult + (cxd_mix((u64)hi) % mult)) & mask;
 }

@@ -12,7 +12,7 @@
 //      dropped -- an edge that only a hyper-voxel below the slab uses, samples EQUAL to the isovalue -- is taken from the halo list itself),
 //   4. appends the slab's tetrahedra with assembly indices; a reference to one of its own halo vertices stays pending, -(1 + h).
 // The march's table emits every tetrahedron oriented (tools/gen_tables.py orient_tet), and the append keeps the order of its four
-// indices: the assembly is oriented as the single extraction is.  cx_slab4d_finish (cx_post.hip) runs the 4-D post-steps on it.
+// indices: the assembly is oriented as the single extraction is.  cx_slab4d_finish (cx_post4d.hip) runs the 4-D post-steps on it.
 #include <algorithm>
 #include <cstring>
 #include <new>

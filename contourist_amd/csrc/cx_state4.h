@@ -41,7 +41,7 @@ void cx_launch_emit_tets(const cx_params4& P, hipStream_t s);
 void cx_launch_hash_xyz(uint64_t* table, uint32_t n0, uint32_t n1, uint32_t n2, const uint32_t org[4], hipStream_t s);
 const uint64_t* cx_pent_lut_device();
 
-// Assembly of a volume marched slab by slab along axis 0 (cx_slab4d_begin / _append / _finish; cx_slab4d.hip, cx_post.hip).  Slab
+// Assembly of a volume marched slab by slab along axis 0 (cx_slab4d_begin / _append / _finish; cx_slab4d.hip, cx_post4d.hip).  Slab
 // i0 .. i1 is marched with origin (i0,0,0,0) and, unless it is the last, with plane i1 as a halo.  Its OWNED vertices (lower lattice
 // point below the halo) are appended in ascending edge id, so the whole assembly is in ascending GLOBAL edge id; tetrahedra are
 // appended with assembly indices, a reference to a halo vertex is held as -(1 + h) until the next append resolves entry h of `pend`.

@@ -113,7 +113,7 @@ def test_morph_triangles_device(name):
     ot, label, flags = postpass4d.orient_morph_triangles(M)
     common, agree = postpass4d.winding_agreement(kh, MT.segment_point_indices, MT.triangle_segment_indices, M["keys"], M["segments"], ot)
     # the march's table emits every tetrahedron wound low -> high (tools/gen_tables.py orient_tet, exact for any sample values
-    # of a sign pattern) and every slice is wound from that (cx_post.hip cxp_morph_slices): the same windings as the
+    # of a sign pattern) and every slice is wound from that (cx_morph.hip cxp_morph_slices): the same windings as the
     # reference's flood fill, also on the fixture with samples EQUAL to the isovalue (test0_style: zero-length edges)
     assert common == len(ot) and agree == common, (common, agree)
     # and against the real reference

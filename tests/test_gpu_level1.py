@@ -198,7 +198,7 @@ def test_random_fields_level1_equals_oracle():
 
 def test_open_mesh_of_separate_triangles():
     """17 000 triangles without a common edge: three distinct edges per triangle, the worst case of the orientation stage's edge
-    table (cx_post.hip, cxp_edge_table_size) -- every triangle its own component, nothing lost"""
+    table (cx_post.h, cxp_edge_table_size) -- every triangle its own component, nothing lost"""
     from contourist_amd import _ffi
     nt = 17000
     rng = np.random.RandomState(2)
