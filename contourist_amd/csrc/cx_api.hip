@@ -232,6 +232,24 @@ void cx_fill_value_params(cx_params& P, double value) {
     P.tol_value = 1e-8 + 1e-5 * std::fabs(value);
 }
 
+// what every extraction of the context's grid at `value` starts from; buffers, capacities and what depends on the task (div_ci) are the caller's
+void cx_base_params(const cx_ctx* ctx, double value, uint32_t flags, cx_params& P) {
+    memset(&P, 0, sizeof(P));
+    P.grid = ctx->grid;
+    P.n0 = (uint32_t)ctx->n0; P.n1 = (uint32_t)ctx->n1; P.n2 = (uint32_t)ctx->n2;
+    P.nsamples = (uint32_t)(ctx->n0 * ctx->n1 * ctx->n2);
+    P.div_plane = cx_fdiv_make(P.n1 * P.n2);
+    P.div_row = cx_fdiv_make(P.n2);
+    cx_fill_value_params(P, value);
+    P.flags = flags;
+    P.org0 = (uint32_t)ctx->origin[0]; P.org1 = (uint32_t)ctx->origin[1]; P.org2 = (uint32_t)ctx->origin[2];
+}
+
+cx_staged_sizes cx_staged_sizes_of(const cx_ctx* ctx, const cx_task& T) {
+    const size_t nw = (size_t)T.nblocks * 4u;   // {nw, need, qa, chunk_words, boundary}
+    return {nw, nw * T.wcap, nw * CX_SWP * 64u + 64u, ((nw + 255u) / 256u) * 8u, (size_t)(ctx->n0 * ctx->n1 + ctx->n0 * ctx->n2 + ctx->n1 * ctx->n2)};
+}
+
 static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
     if (!ctx->grid.p) return fail(ctx, CX_ERR_STATE, "no grid: call cx_grid_upload or cx_grid_adopt_device first");
     if (!(value == value)) return fail(ctx, CX_ERR_INVALID, "isovalue is NaN");
@@ -244,14 +262,7 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
         if (rc) return rc;
     }
     cx_params P;
-    memset(&P, 0, sizeof(P));
-    P.grid = ctx->grid;
-    P.n0 = (uint32_t)ctx->n0; P.n1 = (uint32_t)ctx->n1; P.n2 = (uint32_t)ctx->n2;
-    P.nsamples = (uint32_t)N;
-    P.div_plane = cx_fdiv_make(P.n1 * P.n2);
-    P.div_row = cx_fdiv_make(P.n2);
-    cx_fill_value_params(P, value);
-    P.flags = flags;
+    cx_base_params(ctx, value, flags, P);
     const bool staged = !(flags & CX_KERNEL_GENERIC) && cx_fast_classify_supported_dims(ctx->n2, ctx->grid);
     // fused emit kernel (no per-cell table, no cell records) only on request: measured slower than the staged kernels
     // (DESIGN.md section 4); an extraction that meets the tolerance path is sent through the staged kernels by cx_counts_get
@@ -275,8 +286,6 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
     P.counters = ctx->counters;
     P.stamps = ctx->stamps;
     ctx->last = P;
-    P.org0 = (uint32_t)ctx->origin[0]; P.org1 = (uint32_t)ctx->origin[1]; P.org2 = (uint32_t)ctx->origin[2];
-    ctx->last = P;
     {
         const int rch = cx_ensure_hash_xy(ctx, flags);
         if (rch) return rch;
@@ -298,24 +307,22 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
     memset(&T, 0, sizeof(T));
     if (staged) {
         T = cx_fast_task(P.n0, P.n1, P.n2);
-        const size_t nw = (size_t)T.nblocks * 4u, need = nw * T.wcap;
+        const cx_staged_sizes Z = cx_staged_sizes_of(ctx, T);
         int rc;
-        if ((rc = ctx->queue.grow(ctx, need))) return rc;
-        if ((rc = ctx->wsum.grow(ctx, nw))) return rc;
-        if ((rc = ctx->wbase.grow(ctx, nw))) return rc;
-        if ((rc = ctx->brec.grow(ctx, nw * T.bcap))) return rc;
+        if ((rc = ctx->queue.grow(ctx, Z.need))) return rc;
+        if ((rc = ctx->wsum.grow(ctx, Z.nw))) return rc;
+        if ((rc = ctx->wbase.grow(ctx, Z.nw))) return rc;
+        if ((rc = ctx->brec.grow(ctx, Z.nw * T.bcap))) return rc;
         // batches: at most one short batch per streaming wave plus one per CX_BATCH_MIN (>= 128) queued cells; queued
         // cells = cell records + array-boundary cells without vertices.  Sized from the cell capacity, so a
         // surface that fits the cell capacity fits here (cx_counts_get reports CX_ERR_CAPACITY otherwise).
-        const size_t boundary = (size_t)(ctx->n0 * ctx->n1 + ctx->n0 * ctx->n2 + ctx->n1 * ctx->n2);
-        const size_t nflat = nw + (size_t)ctx->ccap() / 64u + boundary / 128u + 4096u;
+        const size_t nflat = Z.nw + (size_t)ctx->ccap() / 64u + Z.boundary / 128u + 4096u;
         if ((rc = ctx->flat.grow(ctx, nflat))) return rc;
-        if ((rc = ctx->qa.grow(ctx, nw * CX_SWP * 64u + 64u))) return rc;
-        const size_t nchunk_words = ((nw + 255u) / 256u) * 8u;
-        if ((rc = ctx->chunksum.grow(ctx, nchunk_words))) return rc;
-        CX_HIP(ctx, hipMemsetAsync(ctx->chunksum, 0, nchunk_words * sizeof(uint32_t), ctx->stream));
-        if (!fused && (rc = ctx->info64.grow(ctx, need))) return rc;   // staged kernels: (first vertex, crossing mask) per queue entry
-        if (fused && (rc = ctx->info.grow(ctx, need))) return rc;        // fused kernel: one word per queue entry
+        if ((rc = ctx->qa.grow(ctx, Z.qa))) return rc;
+        if ((rc = ctx->chunksum.grow(ctx, Z.chunk_words))) return rc;
+        CX_HIP(ctx, hipMemsetAsync(ctx->chunksum, 0, Z.chunk_words * sizeof(uint32_t), ctx->stream));
+        if (!fused && (rc = ctx->info64.grow(ctx, Z.need))) return rc;   // staged kernels: (first vertex, crossing mask) per queue entry
+        if (fused && (rc = ctx->info.grow(ctx, Z.need))) return rc;        // fused kernel: one word per queue entry
         P.queue = ctx->queue; P.wsum = ctx->wsum; P.wbase = ctx->wbase; P.brec = ctx->brec;
         P.flat = ctx->flat; P.fcap = (uint32_t)nflat;
         P.qa = ctx->qa; P.info = ctx->info; P.info64 = ctx->info64; P.chunksum = ctx->chunksum;
@@ -329,7 +336,7 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
         // built, tested (tests/test_gpu_level0.py::test_fraction_stream) and OFF; CX_DEBUG=1 CX_TQ=1 turns it on.
         P.tq = nullptr; P.tlimit = 0;
         if (!fused && !typed && cx_debug_knob("CX_TQ", 0u)) {   // (an fp32 A/B switch: not instantiated for narrow types)
-            if ((rc = ctx->tq.grow(ctx, need))) return rc;
+            if ((rc = ctx->tq.grow(ctx, Z.need))) return rc;
             P.tq = ctx->tq; P.tlimit = T.wcap;
         }
         // the triangle stage walks the vertex stage's cell records.  The kernel that walks queue entries instead (no records: 80 MB

@@ -241,6 +241,15 @@ int cx_ensure_cell_records(cx_ctx* ctx);
 int cx_ensure_hash_xy(cx_ctx* ctx, uint32_t flags);
 int cx_level0_expanded(cx_ctx* ctx, float4** out);   // the records of the current extraction as float4 {x,y,z,id} (device, enqueued on the stream)
 void cx_fill_value_params(cx_params& P, double value);
+void cx_base_params(const cx_ctx* ctx, double value, uint32_t flags, cx_params& P);   // P zeroed, then the grid, its shape and origin, the value fields, the flags
+struct cx_staged_sizes {      // what the staged pipeline's side tables hold for one extraction (elements, not bytes)
+    size_t nw;                // streaming waves
+    size_t need;              // queue entries: every wave's region of T.wcap
+    size_t qa;                // queue words per (wave, plane step, lane)
+    size_t chunk_words;       // totals of the scan's chunks of 256 waves
+    size_t boundary;          // samples on three faces of the array
+};
+cx_staged_sizes cx_staged_sizes_of(const cx_ctx* ctx, const cx_task& T);
 // cx_halo.hip
 void cx_rccl_comm_free(cx_ctx* ctx);
 // cx_xfer.hip

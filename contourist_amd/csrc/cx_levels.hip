@@ -149,11 +149,11 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
     const cx_task T = cx_fast_task((uint32_t)ctx->n0, (uint32_t)ctx->n1, (uint32_t)ctx->n2);
     L->T = T;
     L->flags = flags;
-    const size_t nw = (size_t)T.nblocks * 4u, need = nw * T.wcap;
-    const size_t boundary = (size_t)(ctx->n0 * ctx->n1 + ctx->n0 * ctx->n2 + ctx->n1 * ctx->n2);
+    const cx_staged_sizes Z = cx_staged_sizes_of(ctx, T);
+    const size_t nw = Z.nw, need = Z.need;
     // batches: one short batch per streaming wave + one per CX_BATCH_MIN queued cells; the cell count is not known yet, so
     // room for a surface through a quarter of all cells (more: CX_ERR_CAPACITY, extract such levels one by one)
-    const size_t nflat = nw + (size_t)N / 4u / 512u + boundary / 128u + 4096u;
+    const size_t nflat = nw + (size_t)N / 4u / 512u + Z.boundary / 128u + 4096u;
     // Queue entries: worst case one per sample and level.  Pooled (the default): the levels share ONE region of `need` entries,
     // level l owning entries [l sub, l sub + sub) of every streaming wave's stretch of T.wcap -- 0.54 GB + 1.07 GB of info words at
     // 512^3 whatever the number of levels (round 2: 0.6 GB per level + 2 x 1.07 GB).  A wave whose cells do not fit its slice
@@ -172,7 +172,7 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
     } else {
         L->qpool.release();
     }
-    const size_t chunk_words = (((nw + 255u) / 256u) * 8u + 63u) & ~(size_t)63u;      // per level, a multiple of 256 bytes
+    const size_t chunk_words = (Z.chunk_words + 63u) & ~(size_t)63u;     // per level, a multiple of 256 bytes
     if ((rc = L->counters_all.grow(ctx, (size_t)nlevels * CX_CNT_WORDS))) return rc;
     if ((rc = L->chunk_all.grow(ctx, (size_t)nlevels * chunk_words))) return rc;
     CX_HIP(ctx, hipMemsetAsync(L->chunk_all, 0, (size_t)nlevels * chunk_words * sizeof(uint32_t), ctx->stream));
@@ -184,20 +184,12 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
         if ((rc = S.wbase.grow(ctx, nw))) return rc;
         if ((rc = S.brec.grow(ctx, nw * T.bcap))) return rc;
         if ((rc = S.flat.grow(ctx, nflat))) return rc;
-        if ((rc = S.qa.grow(ctx, nw * CX_SWP * 64u + 64u))) return rc;
+        if ((rc = S.qa.grow(ctx, Z.qa))) return rc;
         S.counters = L->counters_all + (size_t)l * CX_CNT_WORDS;
         S.chunksum = L->chunk_all + (size_t)l * chunk_words;
         cx_params& P = S.P;
-        memset(&P, 0, sizeof(P));
-        P.grid = ctx->grid;
-        P.n0 = (uint32_t)ctx->n0; P.n1 = (uint32_t)ctx->n1; P.n2 = (uint32_t)ctx->n2;
-        P.nsamples = (uint32_t)N;
-        P.div_plane = cx_fdiv_make(P.n1 * P.n2);
-        P.div_row = cx_fdiv_make(P.n2);
+        cx_base_params(ctx, values[l], flags, P);
         P.div_ci = cx_fdiv_make(T.ci);
-        cx_fill_value_params(P, values[l]);
-        P.flags = flags;
-        P.org0 = (uint32_t)ctx->origin[0]; P.org1 = (uint32_t)ctx->origin[1]; P.org2 = (uint32_t)ctx->origin[2];
         P.counters = S.counters;
         P.queue = pooled ? L->qpool + (size_t)l * sub : S.queue;
         P.qlimit = pooled ? sub : T.wcap;

@@ -684,7 +684,7 @@ __device__ __forceinline__ void cx_tets_group(const cx_params4& P, cx_tet_lds& L
             const uint32_t vf = L.vf[wave][cell][c1], em = L.em[wave][cell][c1];
             tv[s_] = (int32_t)(vf + __popc(em & ((1u << d) - 1u)));
         }
-        if (ok) {   // not read again by the pipeline: nontemporal (see cx_march3d.hip)
+        if (ok) {   // not read again by the pipeline: nontemporal (see cx_emit3d.h)
             typedef int32_t cx_v4i __attribute__((ext_vector_type(4)));
             cx_v4i* dst = reinterpret_cast<cx_v4i*>(P.tets + (size_t)(tnext + j) * 4u);   // the round's tetrahedra, group after group
             const cx_v4i val = cx_v4i{tv[0], tv[1], flip ? tv[3] : tv[2], flip ? tv[2] : tv[3]};

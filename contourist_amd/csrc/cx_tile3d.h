@@ -1,5 +1,5 @@
-// cx_tile3d.h -- the TILE EMIT path of the 3-D march (round 4).  Included by cx_march3d.hip behind the triangle-stage device
-// functions it reuses (cx_vround_front, cx_tri_phase1 / cx_tri_phase2, ...).
+// cx_tile3d.h -- the TILE EMIT path of the 3-D march (round 4).  The last section of the cx_march3d.hip translation unit: included
+// only there, behind the device functions it reuses (cx_emit3d.h: cx_vround_front, cx_tri3d.h: cx_tri_phase1 / cx_tri_phase2, ...).
 //
 // Why.  The staged pipeline hands vertex indices from its vertex stage to its triangle stage through HBM: an 8-byte info word per
 // queue entry and a 16-byte record per cell written by one kernel and gathered by the next, plus the stream kernel's queue words
