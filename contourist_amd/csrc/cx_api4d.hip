@@ -103,6 +103,9 @@ static int enqueue4(cx_ctx* ctx, cx_state4* S, double value, uint32_t flags) {
     P.lut = cx_pent_lut_device();
     if (!P.lut) { ctx->err = "pentatope table symbol not found"; return CX_ERR_HIP; }
     if (flags & CX_DIAG_CPYTHON310) {
+        // the kernels hash lattice coordinates as 32-bit ints (py_round4): beyond that the set order would silently be another one
+        for (int d = 0; d < 4; d++)
+            if (S->origin[d] + S->n[d] - 1 > 0x7FFFFFFFLL) { ctx->err = "4-D origin: lattice coordinates beyond 2^31 - 1 (CPython set order)"; return CX_ERR_UNSUPPORTED; }
         const int64_t key[7] = {S->n[0], S->n[1], S->n[2], S->origin[0], S->origin[1], S->origin[2], 1};
         if (memcmp(key, S->hash_key, sizeof(key)) != 0) {
             const size_t need = (size_t)(S->n[0] * S->n[1] * S->n[2]);

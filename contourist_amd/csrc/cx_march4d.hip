@@ -810,12 +810,19 @@ const uint64_t* cx_pent_lut_device() {
     return (const uint64_t*)p;
 }
 
+// Numeric knobs of the launchers below (cx_debug_knob: a process started with CX_DEBUG=1 only; tests).  They shrink the grids so
+// that small fields reach the branches only large ones reach otherwise: CX4_SB_BLOCKS caps the workgroups of both sign-bitmap
+// kernels as given (grid-stride trips), CX4_IPB sets the items per workgroup of the queue kernel (several steps per wave: the
+// flush of its LDS queue), CX4_CELLS_WGS / CX4_TETS_WGS cap the cells and the tetrahedra kernel (grid-stride trips; whole rounds
+// next to half rounds).  Unset, every launch is what it was.
 void cx_launch_signbits4d(const cx_params4& P, hipStream_t s) {
+    const uint32_t sb_blocks = cx_debug_knob("CX4_SB_BLOCKS", 0u);
     if (P.n3 % 32u == 0u && ((uintptr_t)P.grid & 15u) == 0u && !cx_debug_knob("CX4_SB_ROWS", 0)) {
         const uint32_t nquads = P.nsamples / 4u;
         uint32_t blocks = (nquads + 256u * CX4_SB_UNROLL - 1u) / (256u * CX4_SB_UNROLL);
         const uint32_t most = 256u * cx_debug_knob("CX4_SB_WGS", 16u);
         if (blocks > most) blocks = most;
+        if (sb_blocks && blocks > sb_blocks) blocks = sb_blocks;
         hipLaunchKernelGGL(cx_k_signbits4_flat, dim3(blocks), dim3(256), 0, s, P, nquads);
         return;
     }
@@ -824,22 +831,25 @@ void cx_launch_signbits4d(const cx_params4& P, hipStream_t s) {
     const uint32_t waves = (total + 7u) / 8u;
     uint32_t blocks = (waves + 3u) / 4u;
     if (blocks > 256u * 64u) blocks = 256u * 64u;   // grid-stride
+    if (sb_blocks && blocks > sb_blocks) blocks = sb_blocks;
     hipLaunchKernelGGL(cx_k_signbits4, dim3(blocks), dim3(256), 0, s, P, nchunk, cx_fdiv_make(nchunk), total);
 }
 void cx_launch_classify4d(const cx_params4& P, hipStream_t s) {
     const uint32_t nitems = P.nrows * P.nw3;
-    uint32_t ipb = (nitems + 3071u) / 3072u;
+    uint32_t ipb = cx_debug_knob("CX4_IPB", (nitems + 3071u) / 3072u);
     ipb = (ipb + 255u) & ~255u;
     if (ipb < 256u) ipb = 256u;
     const uint32_t blocks = (nitems + ipb - 1u) / ipb;
     hipLaunchKernelGGL(cx_k_queue4, dim3(blocks), dim3(256), 0, s, P, ipb);
     uint32_t cblocks = (P.qcap + CX4_CELLS_WAVES * 64u - 1u) / (CX4_CELLS_WAVES * 64u);
-    if (cblocks > 1024u) cblocks = 1024u;         // grid-stride: four workgroups per CU
+    const uint32_t cmost = cx_debug_knob("CX4_CELLS_WGS", 1024u);   // grid-stride: four workgroups per CU
+    if (cblocks > cmost) cblocks = cmost;
     hipLaunchKernelGGL(cx_k_cells4, dim3(cblocks ? cblocks : 1u), dim3(CX4_CELLS_WAVES * 64u), 0, s, P);
 }
 void cx_launch_emit_tets(const cx_params4& P, hipStream_t s) {
     uint32_t blocks = (P.qcap + 255u) / 256u;
-    if (blocks > 256u * 4u) blocks = 256u * 4u;   // grid-stride: a few workgroups per CU
+    const uint32_t most = cx_debug_knob("CX4_TETS_WGS", 256u * 4u);   // grid-stride: a few workgroups per CU
+    if (blocks > most) blocks = most;
     hipLaunchKernelGGL(cx_k_emit_tets, dim3(blocks ? blocks : 1u), dim3(256), 0, s, P);
 }
 void cx_launch_hash_xyz(uint64_t* table, uint32_t n0, uint32_t n1, uint32_t n2, const uint32_t org[4], hipStream_t s) {

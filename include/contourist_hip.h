@@ -595,7 +595,10 @@ int cx_surface_geometry(cx_ctx* ctx, double* points_xyz, int64_t* nv, int32_t* t
  * Result: vertex records float4 {x,y,z,t} in grid coordinates, edge ids
  * (linear index of the lower lattice point << 4) | direction (1..15 = 8di+4dj+2dk+dl), and
  * tetrahedra as 4 int32 vertex indices (cx_counts.n_triangles counts tetrahedra here).
- * CX_DIAG_CPYTHON310 reproduces the reference's 2-3 split (set order of 4-tuples, pentatopes.py:255-256). */
+ * CX_DIAG_CPYTHON310 reproduces the reference's 2-3 split (set order of 4-tuples, pentatopes.py:255-256).
+ * cx_set_origin4d: lattice coordinates of sample [0,0,0,0] (>= -1024 per axis; they enter the set order only).  The kernels hash
+ * lattice coordinates as 32-bit ints: with CX_DIAG_CPYTHON310 an origin that puts the array's last lattice point beyond 2^31 - 1
+ * on some axis is refused by cx_extract4d (CX_ERR_UNSUPPORTED). */
 int cx_grid4d_upload(cx_ctx* ctx, const float* host, int64_t n0, int64_t n1, int64_t n2, int64_t n3);
 int cx_grid4d_adopt_device(cx_ctx* ctx, const void* device_ptr, int64_t n0, int64_t n1, int64_t n2, int64_t n3);
 int cx_set_origin4d(cx_ctx* ctx, int64_t o0, int64_t o1, int64_t o2, int64_t o3);
