@@ -67,6 +67,7 @@ SYMBOLS = [
     "cx_level1_topology", "cx_level1_topology_download", "cx_level1_boundary_loops", "cx_level1_boundary_loops_download",
     "cx_level1_simplify", "cx_level1_simplify_map", "cx_level1_simplify_map_download",
     "cx_level1_clip_plane", "cx_level1_clip_scalars", "cx_level1_clip_map", "cx_level1_clip_map_download", "cx_level1_clip_info",
+    "cx_cap3d", "cx_cap3d_download", "cx_cap3d_info", "cx_postprocess3d_capped",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -122,6 +123,34 @@ CX_CLIP_NO_CLEAN = 1
 CX_CLIP_KEEP_BELOW = 2
 CX_CLIP_NORMALS = 4
 CLIP_KEYS = ("n_vertices", "n_triangles", "n_components", "n_cut_vertices", "n_cut_triangles", "n_nonfinite", "n_on_cut")
+CX_CAP_BELOW = 1
+CX_CAP_ALL_FACES = 63
+CAP_FACES = ("-x", "+x", "-y", "+y", "-z", "+z")      # bit 0: i = 0, bit 1: i = n0-1, bit 2: j = 0, ...
+CAP_KEYS = ("n_lattice_vertices", "n_cap_triangles", "n_missing_crossings", "n_rim_crossings")
+
+
+def cap_faces_mask(faces):
+    """'all', a 6-bit mask, or a list of the names "-x", "+x", "-y", "+y", "-z", "+z" -> the mask of cx_cap3d"""
+    if isinstance(faces, str):
+        if faces == "all":
+            return CX_CAP_ALL_FACES
+        faces = [faces]
+    if isinstance(faces, (int, np.integer)) and not isinstance(faces, bool):
+        if int(faces) < 0 or int(faces) > CX_CAP_ALL_FACES:
+            raise ValueError("a face mask has six bits, not %r" % (faces,))
+        return int(faces)
+    mask = 0
+    for name in faces:
+        if name not in CAP_FACES:
+            raise ValueError("faces are named %s, not %r" % (", ".join(CAP_FACES), name))
+        mask |= 1 << CAP_FACES.index(name)
+    return mask
+
+
+def cap_side_flags(side):
+    if side not in ("above", "below"):
+        raise ValueError("side is 'above' (cap where f >= value) or 'below' (where f < value), not %r" % (side,))
+    return CX_CAP_BELOW if side == "below" else 0
 CX2_ALL_CHAINS = 1
 CX2_NO_DEDUPE = 2
 CX2_SEARCH_SEEDS = 4
@@ -247,6 +276,10 @@ def load():
         "cx_level1_clip_map": [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)],
         "cx_level1_clip_map_download": [vp, vp, vp],
         "cx_level1_clip_info": [vp, vp],
+        "cx_cap3d": [vp, u32, u32, vp],
+        "cx_cap3d_download": [vp, vp, vp],
+        "cx_cap3d_info": [vp, vp],
+        "cx_postprocess3d_capped": [vp, u32, vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -475,6 +508,33 @@ class Context(object):
     def postprocess3d(self, flags=0, smooth=0.0):
         out = np.zeros(8, dtype=np.int64)
         self._check(self.lib.cx_postprocess3d_ex(self.handle, int(flags), float(smooth or 0.0), out.ctypes.data))
+        return dict(n_vertices=int(out[0]), n_triangles=int(out[1]), n_after_weld=int(out[2]),
+                    n_after_tiny=int(out[3]), n_components=int(out[4]))
+
+    def cap3d(self, faces="all", side="above"):
+        """build the rim cap of the current extraction (cx_cap3d) -> dict of CAP_KEYS; faces: 'all', a mask or names of CAP_FACES"""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.cx_cap3d(self.handle, cap_faces_mask(faces), cap_side_flags(side), out.ctypes.data))
+        return dict(zip(CAP_KEYS, (int(x) for x in out)))
+
+    def download_cap(self, counts):
+        """the raw cap -> (keys (C,) uint32 in ascending order: lattice points carry direction 0, triangles (K,3) int32 into the Level-0
+        vertices followed by the cap vertices); counts: what cap3d returned"""
+        keys = np.empty(int(counts["n_lattice_vertices"]) + int(counts["n_missing_crossings"]), dtype=np.uint32)
+        tris = np.empty((int(counts["n_cap_triangles"]), 3), dtype=np.int32)
+        self._check(self.lib.cx_cap3d_download(self.handle, keys.ctypes.data, tris.ctypes.data))
+        return keys, tris
+
+    def cap_info(self):
+        "of the current cap: dict(ms, n_rim_records, table_slots, n_rim_points)"
+        out = np.zeros(4, dtype=np.float64)
+        self._check(self.lib.cx_cap3d_info(self.handle, out.ctypes.data))
+        return dict(ms=float(out[0]), n_rim_records=int(out[1]), table_slots=int(out[2]), n_rim_points=int(out[3]))
+
+    def postprocess3d_capped(self, flags=0):
+        "Level 1 of the Level-0 mesh followed by the current cap (cap3d first) -> the same dict as postprocess3d"
+        out = np.zeros(8, dtype=np.int64)
+        self._check(self.lib.cx_postprocess3d_capped(self.handle, int(flags), out.ctypes.data))
         return dict(n_vertices=int(out[0]), n_triangles=int(out[1]), n_after_weld=int(out[2]),
                     n_after_tiny=int(out[3]), n_components=int(out[4]))
 

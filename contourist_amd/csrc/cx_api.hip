@@ -53,6 +53,7 @@ extern "C" int cx_ctx_destroy(cx_ctx* ctx) {
     cx_topo_free(ctx);
     cx_simplify_free(ctx);
     cx_clip_free(ctx);
+    cx_cap_free(ctx);
     cx_state4_free(ctx);
     cx_state2_free(ctx);
     if (ctx->counters_host) (void)hipHostFree(ctx->counters_host);
@@ -95,6 +96,7 @@ static int set_grid_dims(cx_ctx* ctx, int64_t n0, int64_t n1, int64_t n2) {
     cx_levels_invalidate(ctx);
     ctx->extracted = false;
     ctx->post_valid = false;
+    ctx->cap_valid = false;
     return CX_OK;
 }
 
@@ -189,6 +191,7 @@ extern "C" int cx_reserve(cx_ctx* ctx, int64_t max_cells, int64_t max_vertices, 
     if ((rc = ctx->tris.grow(ctx, (size_t)max_triangles * 3u))) return rc;
     ctx->extracted = false;
     ctx->post_valid = false;
+    ctx->cap_valid = false;
     return CX_OK;
 }
 
@@ -403,6 +406,7 @@ static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
     ctx->counts_fetched = false;
     ctx->post_valid = false;
     ctx->keep_valid = false;
+    ctx->cap_valid = false;
     cx_levels_invalidate(ctx); // the context's output buffers hold this extraction now, not a level of cx_extract3d_levels
     return CX_OK;
 }

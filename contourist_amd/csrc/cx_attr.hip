@@ -526,6 +526,7 @@ extern "C" int cx_level1_normals(cx_ctx* ctx, const double* delta3, void** norma
     if (!cxa_delta_ok(delta3)) return cxa_fail(ctx, CX_ERR_INVALID, "cx_level1_normals: the spacing must be positive and finite");
     int rcc = CX_OK;
     if (cxa_carried(ctx, delta3, normals_dev, nullptr, &rcc)) return rcc;
+    if (cx_level1_capped(ctx)) return cxa_fail(ctx, CX_ERR_UNSUPPORTED, "cx_level1_normals: a capped mesh (cx_postprocess3d_capped) has a crease along the rim and no single normal there");
     cx_level1_view V;
     int rc = cxa_level1(ctx, "cx_level1_normals", &V);
     if (rc) return rc;
@@ -620,6 +621,7 @@ extern "C" int cx_level0_curvature_download(cx_ctx* ctx, const double* delta3, f
 extern "C" int cx_level1_curvature(cx_ctx* ctx, const double* delta3, void** curv_dev) {
     if (!ctx) return CX_ERR_INVALID;
     if (!cxa_delta_ok(delta3)) return cxa_fail(ctx, CX_ERR_INVALID, "cx_level1_curvature: the spacing must be positive and finite");
+    if (cx_level1_capped(ctx)) return cxa_fail(ctx, CX_ERR_UNSUPPORTED, "cx_level1_curvature: a capped mesh (cx_postprocess3d_capped) has a crease along the rim and flat caps: no curvature of the field there");
     cx_level1_view V;
     int rc = cxa_level1(ctx, "cx_level1_curvature", &V);
     if (rc) return rc;

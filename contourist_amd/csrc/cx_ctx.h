@@ -172,6 +172,10 @@ struct cx_ctx {
     struct cx_topo_state* topo = nullptr;
     // clipping of the Level-1 mesh (cx_clip.hip): bit masks, counts, the edge table of the cut band, the map, kept between calls
     struct cx_clip_state* clip = nullptr;
+    // rim caps of the current extraction (cx_cap.hip): sign words, the table of the rim's crossings, the cap itself, kept between calls.
+    // cap_valid: they hold the cap of what the context's Level-0 buffers hold now (cleared wherever those change hands)
+    struct cx_cap_state* cap = nullptr;
+    bool cap_valid = false;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -339,6 +343,17 @@ void cx_topo_free(cx_ctx* ctx);
 void cx_simplify_free(cx_ctx* ctx);
 // cx_clip.hip
 void cx_clip_free(cx_ctx* ctx);
+// cx_cap.hip: the cap of the current extraction for the post-pass (cx_postprocess3d_capped): ncv vertex records {key, 0} in ascending
+// key and nct index triples into the Level-0 vertices followed by them.  CX_ERR_STATE without a valid cap, CX_ERR_UNSUPPORTED on the
+// routes no cap is built for.
+void cx_cap_free(cx_ctx* ctx);
+struct cx_cap_view {
+    const cx_vrec* vrec;
+    const int32_t* tris;
+    uint32_t ncv, nct;
+};
+int cx_cap_view_get(cx_ctx* ctx, const char* who, cx_cap_view* out);
+bool cx_level1_capped(cx_ctx* ctx);   // cx_post.hip: the Level-1 mesh came out of cx_postprocess3d_capped (or is a filtered copy of one)
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);
 // cx_contour2d.hip

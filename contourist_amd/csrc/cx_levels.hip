@@ -120,6 +120,7 @@ extern "C" int cx_levels_select(cx_ctx* ctx, int32_t index) {
     ctx->counts_fetched = true;
     ctx->post_valid = false;
     ctx->keep_valid = false;
+    ctx->cap_valid = false;
     ctx->records_valid = true;
     ctx->path = 1;
     return CX_OK;
@@ -141,7 +142,7 @@ extern "C" int cx_extract3d_levels(cx_ctx* ctx, const double* values, int32_t nl
     cx_levels_unselect(ctx);
     L->nvalid = 0;
     // nothing is selected from here on: an error return below must not leave the context describing a level that is gone
-    ctx->extracted = false; ctx->counts_fetched = false; ctx->post_valid = false; ctx->keep_valid = false;
+    ctx->extracted = false; ctx->counts_fetched = false; ctx->post_valid = false; ctx->keep_valid = false; ctx->cap_valid = false;
     if ((int)L->slots.size() < nlevels) L->slots.resize(nlevels);
     const int64_t N = ctx->n0 * ctx->n1 * ctx->n2;
     int rc = cx_ensure_hash_xy(ctx, flags);

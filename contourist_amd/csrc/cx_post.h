@@ -33,6 +33,10 @@ struct cx_post_state {
     bool simplified = false, carried = false, smap_valid = false;
     bool clipped = false;             // the derived mesh came out of cx_level1_clip_* (cx_clip.hip): old vertices and cut vertices
     uint32_t smap_n = 0;
+    // rim caps (cx_cap.hip): the mesh of generation capped_gen came out of cx_postprocess3d_capped, or is a filtered copy of one: its keys
+    // are edge ids AND lattice points (direction 0), a crease runs along its rim and no normal or curvature is served for it
+    uint64_t capped_gen = 0;
+    bool capped() const { return capped_gen != 0 && capped_gen == gen; }
     struct {
         bool open = false;            // between cx_postprocess3d_shard_begin and _finish
         uint32_t nv2 = 0, nt2 = 0;    // mesh of own + first-halo-layer triangles the labels refer to

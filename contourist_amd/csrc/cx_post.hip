@@ -1589,6 +1589,54 @@ extern "C" int cx_postprocess3d_ex(cx_ctx* ctx, uint32_t flags, double smooth, i
     return CX_OK;
 }
 
+// ---- the capped mesh (cx_cap.hip, include/contourist_hip.h "rim caps"): the Level-0 mesh followed by the cap of cx_cap3d ---------------
+// The input is filled as cx_postprocess3d_ex fills it, then the cap's vertices (the same float64 formula on their records {key, 0}: a
+// lattice point, direction 0, interpolates between itself and itself) and triangles follow, and cxp_run3d runs on nv + cap, nt + cap.
+// edge_crossings = true stands, for two reasons:
+//   - cxp_weld_alone must treat a lattice-point vertex as NOT alone (a crossing within 1/ex of it shares its bucket).  It does: the
+//     coordinate it looks at is an integer for a direction-0 key (every coordinate of a lattice point is), u = x - floor(x) = 0, and
+//     u > thr fails for every thr > 0.  A crossing the cap made itself (the march had skipped it) is a crossing like the march's own.
+//   - the block linking's premise, an edge on at most two triangles before anything is merged: a rim edge of the march's mesh lay on one
+//     triangle and gets the one cap triangle of its face-triangle; an edge inside a face lies on the two cap triangles beside it; an edge
+//     of the array's box lies on one cap triangle of each of its two faces; nothing else is added.
+// The windings are coherent by construction (the cap is wound with the march), so coherent = true stands as well.
+extern "C" int cx_postprocess3d_capped(cx_ctx* ctx, uint32_t flags, int64_t* out_counts) {
+    if (!ctx) return CX_ERR_INVALID;
+    if (!ctx->extracted) { ctx->err = "cx_postprocess3d_capped: no valid extraction"; return CX_ERR_STATE; }
+    if (flags & ~1u) { ctx->err = "cx_postprocess3d_capped: unknown flag bits (only bit 0, no clean-up, is defined)"; return CX_ERR_INVALID; }
+    CX_HIP(ctx, hipSetDevice(ctx->device));
+    cx_cap_view K;
+    int rc = cx_cap_view_get(ctx, "cx_postprocess3d_capped", &K);      // (refuses the routes no cap is built for; nothing is written before)
+    if (rc) return rc;
+    cx_post_state* S;
+    if ((rc = cxp_state(ctx, &S))) return rc;
+    const uint32_t nv0 = (uint32_t)ctx->counts.n_vertices, nt0 = (uint32_t)ctx->counts.n_triangles;
+    const uint32_t nv = nv0 + K.ncv, nt = nt0 + K.nct;
+    hipStream_t st = ctx->stream;
+    int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if ((rc = cxp_reserve3d(ctx, S, nv, nt))) return rc;
+    const cx_params& P = ctx->last;
+    const cxp_origin3 org{{0.0, 0.0, 0.0}};
+    if (nv && nt) {
+        const double* A64 = ctx->grid64_valid ? ctx->grid64.get() : nullptr;
+        if (nv0) cxp_launch_vertices_f64(dim3(cx_blocks(nv0)), st, P.grid, A64, P.n1, P.n2, P.div_plane, P.div_row, P.value, (const cx_vrec*)ctx->verts.get(), nv0,
+                                         S->pts.as<double>(), S->prio.as<uint32_t>(), org);
+        if (K.ncv) cxp_launch_vertices_f64(dim3(cx_blocks(K.ncv)), st, P.grid, A64, P.n1, P.n2, P.div_plane, P.div_row, P.value, K.vrec, K.ncv,
+                                           S->pts.as<double>() + (size_t)nv0 * 3, S->prio.as<uint32_t>() + nv0, org);
+        if (nt0) CX_HIP(ctx, hipMemcpyAsync(S->tri.get(), ctx->tris, (size_t)nt0 * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        if (K.nct) CX_HIP(ctx, hipMemcpyAsync(S->tri.as<int32_t>() + (size_t)nt0 * 3, K.tris, (size_t)K.nct * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        CX_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
+    }
+    const double corner[3] = {(double)(P.n0 - 1), (double)(P.n1 - 1), (double)(P.n2 - 1)};
+    if ((rc = cxp_run3d(ctx, S, nv, nt, corner, nullptr, !(flags & 1u), 0.0, true, counts, true))) return rc;
+    ctx->post_valid = true;
+    S->keys_edge = true;
+    S->capped_gen = S->gen;
+    if (out_counts) memcpy(out_counts, counts, sizeof(counts));
+    return CX_OK;
+}
+bool cx_level1_capped(cx_ctx* ctx) { return ctx->post && ctx->post_valid && ctx->post->capped(); }
+
 // ---- sharded Level 1 (the reference is one process: tetrahedral.py:190-215, 353-375, surface_geometry.py:14-140) ----
 // The context holds the extraction of a slab that was marched TOGETHER with two layers of cells of each neighbour slab
 // (cx_set_origin = where the local array starts in the whole volume, cx_set_reference_corner = the whole volume's corner).
@@ -1921,7 +1969,9 @@ int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new, const u
     S->nv_out = nv_new; S->nt_out = nt_new;
     S->orient_nt = nt_new;
     S->vflip_valid = false;      // (written again from the tables on the next request)
+    const bool capped = S->capped();     // (a filtered copy of a capped mesh is a capped mesh)
     S->gen++;
+    if (capped) S->capped_gen = S->gen;
     return CX_OK;
 }
 

@@ -395,6 +395,7 @@ extern "C" int cx_select_seeded3d_ex(cx_ctx* ctx, const int32_t* endpoints_ijk, 
     uint8_t* tri_keep = ctx->tri_keep;
     uint8_t* vkeep = ctx->tri_keep + nt;
     ctx->keep_valid = false;
+    ctx->cap_valid = false;     // (a cap closes the whole surface, not a selection of it)
     // scratch
     uint32_t *vmap = nullptr, *parent = nullptr, *seeds = nullptr, *out = nullptr, *abits = nullptr;
     uint8_t* flag = nullptr;

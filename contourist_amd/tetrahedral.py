@@ -89,6 +89,8 @@ class GridContour3d(object):
         self._ctx = context
         self._counts = None
         self._post = None
+        self._cap = None              # (face mask, side) of cap_rim(), or None
+        self.cap_counts = None
 
     # -- device plumbing ----------------------------------------------------------------------------
     def context(self):
@@ -226,7 +228,9 @@ class GridContour3d(object):
                 ctx.set_reference_corner([int(h) - int(l) for l, h in zip(lo, hi)])
             else:
                 ctx.set_reference_corner((0, 0, 0))
-            if self.linear_interpolate:
+            if self._cap is not None:
+                self._post = self._postprocess_capped(ctx, clean)
+            elif self.linear_interpolate:
                 self._post = ctx.postprocess3d(0 if clean else 1, self.smooth or 0.0)
             else:
                 self._post = self._postprocess_refined(ctx, clean)
@@ -252,8 +256,52 @@ class GridContour3d(object):
                 ctx.set_reference_corner([int(h) - int(l) for l, h in zip(lo, hi)])
             else:
                 ctx.set_reference_corner((0, 0, 0))
-            self._post = ctx.postprocess3d(0 if clean else 1, self.smooth or 0.0) if self.linear_interpolate else self._postprocess_refined(ctx, clean)
+            if self._cap is not None:
+                self._post = self._postprocess_capped(ctx, clean)
+            else:
+                self._post = ctx.postprocess3d(0 if clean else 1, self.smooth or 0.0) if self.linear_interpolate else self._postprocess_refined(ctx, clean)
         return ctx
+
+    # -- rim caps: close the surface where the rim of the array cuts it open --------------------------------------
+    def _cap_refusal(self):
+        "why this maker takes no cap, or None"
+        if self._in_slabs():
+            return "a volume marched in slabs has no single extraction whose rim could be capped"
+        if self.end_points is not None and len(self.end_points):
+            return "end points select components of the surface: a cap closes the whole surface, not a selection of it"
+        if self.voxel_range is not None or self.grid_shift or tuple(self.origin) != (0, 0, 0):
+            return "a voxel_range (an array carrying a margin) has its rim outside the grid"
+        if not self.linear_interpolate:
+            return "linear_interpolate=False moves the crossings off the march's piecewise-linear surface: the flat caps would not meet them"
+        if self.smooth:
+            return "smooth moves the rim's vertices out of the faces of the array"
+        return None
+
+    def cap_rim(self, faces="all", side="above"):
+        """Close the surface where the rim of the sampled array cuts it open (include/contourist_hip.h, "rim caps"): every later
+        get_points_and_triangles(), components(), topology(), write_mesh(), simplify() and clip() serves march + cap, a closed mesh
+        whose components() volume is that of {f >= value} (side="above") or {f < value} ("below") under the march's interpolant.
+        faces: "all", a 6-bit mask, or a list of "-x", "+x", "-y", "+y", "-z", "+z".  Returns the cap's counts (_ffi.CAP_KEYS).
+        cap_rim(None) undoes it.  Normals and curvature are not served for a capped mesh (a crease runs along the rim)."""
+        if faces is None:
+            self._cap, self.cap_counts, self._post = None, None, None
+            return None
+        mask, flags = _ffi.cap_faces_mask(faces), _ffi.cap_side_flags(side)
+        why = self._cap_refusal()
+        if why:
+            raise NotImplementedError("cap_rim: " + why)
+        self.march()
+        self.cap_counts = self.context().cap3d(mask, side)
+        self._cap = (mask, "below" if flags else "above")
+        self._post = None
+        return dict(self.cap_counts)
+
+    def _postprocess_capped(self, ctx, clean):
+        why = self._cap_refusal()
+        if why:
+            raise NotImplementedError("cap_rim: " + why)
+        self.cap_counts = ctx.cap3d(*self._cap)        # (idempotent: built again only after a new extraction)
+        return dict(ctx.postprocess3d_capped(0 if clean else 1), capped=True, carried_normals=False)
 
     # -- vertex attributes: normals from the field's gradient, a second grid sampled at the vertices -------------
     def _attr_checks(self):
@@ -612,7 +660,7 @@ def _clip_values(values, ctx):
 
 
 def unpack_edge_ids(keys, shape):
-    "edge id (lin << 3 | d) -> (lower lattice point (V,3), upper lattice point (V,3))"
+    "edge id (lin << 3 | d) -> (lower lattice point (V,3), upper lattice point (V,3)); d == 0 (a lattice-point vertex of a rim cap): both are the point"
     keys = np.asarray(keys).astype(np.int64)
     lin, d = keys >> 3, keys & 7
     i, r = np.divmod(lin, shape[1] * shape[2])
@@ -777,6 +825,10 @@ class Delta3DContour(object):
             from . import mesh_io
             return mesh_io.write_gltf_device(self, path, normals=fmt == "gltf_normals")
         return self.contour_maker.write_mesh(path, fmt, self.grid.mins, self.grid.delta)
+
+    def cap_rim(self, faces="all", side="above"):
+        "GridContour3d.cap_rim of this isosurface (refused, with the reason, when the maker carries a rim of samples around the grid)"
+        return self.contour_maker.cap_rim(faces, side)
 
     def components(self, clean=True, device=False):
         "GridContour3d.components in WORLD coordinates (areas, volumes, centroids and boxes of the grid's mins and delta)"
@@ -1100,7 +1152,10 @@ class MultiLevelIsosurfaces(object):
         self.counts = None
         self._current = None
 
-    def levels(self, clean=True):
+    def levels(self, clean=True, cap=None):
+        """cap: None, or the faces of GridContour3d.cap_rim ("all", a mask, names) -- every level is then capped (side "above") after it is
+        selected, exactly as a single capped extraction of that value"""
+        cap_mask = None if cap is None else _ffi.cap_faces_mask(cap)
         samples = self.grid.dense_samples()
         corner = tuple(int(n) for n in self.grid.grid_dimensions)
         shape = tuple(int(n) for n in samples.shape)
@@ -1108,6 +1163,8 @@ class MultiLevelIsosurfaces(object):
         if shape[2] < 4:          # rows shorter than 4 samples take the shape-agnostic kernel: one level at a time
             for n, v in enumerate(self.values):
                 maker = GridContour3d(corner, samples, v, None, context=ctx)
+                if cap_mask is not None:
+                    maker.cap_rim(cap_mask)
                 grid_points, triangles = maker.get_points_and_triangles(clean)
                 self._current = n
                 yield LevelResult((v, self.grid.from_grid_coordinates(grid_points) if len(grid_points) else np.zeros((0, 3)),
@@ -1125,7 +1182,11 @@ class MultiLevelIsosurfaces(object):
         self.counts = ctx.extract3d_levels(self.values, self.flags)
         for n, v in enumerate(self.values):
             ctx.select_level(n)
-            post = ctx.postprocess3d(0 if clean else 1)
+            if cap_mask is not None:
+                ctx.cap3d(cap_mask, "above")
+                post = dict(ctx.postprocess3d_capped(0 if clean else 1), capped=True, carried_normals=False)
+            else:
+                post = ctx.postprocess3d(0 if clean else 1)
             grid_points, triangles = ctx.download_level1(post)
             geometry = surface_geometry.SurfaceGeometry._from_device(grid_points, triangles, ctx)   # sorted rows, as the reference returns them
             points = self.grid.from_grid_coordinates(geometry.vertices) if len(grid_points) else np.zeros((0, 3))

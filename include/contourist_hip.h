@@ -578,6 +578,63 @@ int cx_level1_clip_map(cx_ctx* ctx, void** lo_hi_dev, void** t_dev);
 int cx_level1_clip_map_download(cx_ctx* ctx, int32_t* lo_hi, double* t);
 int cx_level1_clip_info(cx_ctx* ctx, double* info8);
 
+/* ---- rim caps: close the isosurface where the rim of the array cuts it open, on the device ------------------------------------------
+ * A surface that runs into the edge of the sampled array ends there in boundary loops: its components are not closed, their signed
+ * volume is no volume.  The cap is the cross-section of the solid with the selected faces of the array; march plus cap is a closed
+ * mesh whose enclosed volume is that of {f >= value} (or {f < value}) under the march's own piecewise-linear interpolant.
+ * (No counterpart in the reference.)
+ * Input: the current extraction (resident grid of any CX_DTYPE_*, n0 x n1 x n2, isovalue v, nv Level-0 vertices {edge id, t}, nt
+ * triangles), a 6-bit mask `faces` (bit 0: i = 0, bit 1: i = n0-1, bit 2: j = 0, bit 3: j = n1-1, bit 4: k = 0, bit 5: k = n2-1) and a
+ * side: ABOVE caps where f >= v, BELOW (CX_CAP_BELOW) where f < v.
+ *   - A lattice point is INSIDE iff !(f < v) for ABOVE and iff f < v for BELOW: the bit the march classifies with, read from the grid
+ *     in its own type.
+ *   - Face-triangles.  A face of axis a has the in-plane axes (u, w), u < w in the order i, j, k.  The Kuhn tetrahedra cut every unit
+ *     square of it, lower corner (a, b) in (u, w), along the diagonal (a, b)-(a+1, b+1) (lattice direction 3 on an i-face, 5 on a j-face,
+ *     6 on a k-face) into triangle 0 = {(a, b), (a+1, b), (a+1, b+1)} and triangle 1 = {(a, b), (a+1, b+1), (a, b+1)}, corners 0, 1, 2
+ *     in that order.  The square's linear index in the face is a * (n_w - 1) + b.
+ *   - Per face-triangle with m inside corners.  m = 0: nothing.  m = 3: one triangle (p_0, p_1, p_2) of lattice-point vertices.
+ *     m = 1: rotate the corners, keeping the cyclic order, so that i is the inside one and j, k follow: (p_i, c(i,j), c(i,k)).
+ *     m = 2: rotate so that i is the OUTSIDE one: (c(i,j), p_j, p_k) and (c(i,j), p_k, c(k,i)).  The quad's diagonal runs from the
+ *     crossing behind the outside corner to the corner before it: a rule of the triangle's own corner numbers that never looks at a
+ *     neighbour.
+ *   - c(a,b) is the crossing of the lattice edge between corners a and b (their inside bits differ): the Level-0 vertex with that edge
+ *     id, found by id, never made again.  Where the march has emitted none (it may skip a crossing under the reference's tolerance
+ *     rules) the cap makes the vertex itself: key = the edge id, position by the float64 formula of the post-pass.  It is counted; the
+ *     surface is already open there and the cap does not promise to close it.
+ *   - A lattice-point vertex has key (linear index << 3) | 0 -- the direction field of an edge id takes 1..7, 0 is the lattice point
+ *     itself --, position (i, j, k) exactly and t = 0.  A lattice point on two or three selected faces is ONE vertex.
+ *   - Order.  The cap vertices follow the nv Level-0 vertices in ascending key.  The cap triangles follow the nt Level-0 triangles in
+ *     the order (face number, square's linear index in the face, triangle 0 / 1, piece 0 / 1).
+ *   - Winding.  The corners of a face-triangle run counter-clockwise in (u, w), around e_u x e_w = +i on an i-face, -j on a j-face, +k on
+ *     a k-face.  The march's normals point from f < v to f >= v: into the solid of ABOVE, out of the solid of BELOW.  The cap is wound
+ *     with it: ABOVE wants the normal that points into the array (+axis on the low face of an axis, -axis on the high one), BELOW the
+ *     opposite; where that is not the counter-clockwise one the last two corners of every emitted triangle are exchanged (ABOVE:
+ *     faces 1, 2, 5; BELOW: faces 0, 3, 4).  Every edge shared by a march triangle and a cap triangle, or by two cap triangles, is
+ *     then traversed in opposite directions by the two.
+ * cx_cap3d builds the cap of the current extraction.  counts4: [0] lattice-point vertices, [1] cap triangles, [2] crossings the march
+ * had not emitted, [3] rim edges with a crossing.  Idempotent per (extraction, faces, side); the cap is gone with the next extraction,
+ * grid call, cx_reserve, cx_levels_select or seeded selection (CX_ERR_STATE from the calls below then).
+ * cx_cap3d_download: the raw cap: keys = [0] + [2] uint32, tris = [1] x 3 int32 indices into the Level-0 vertices followed by the
+ * cap vertices.  Either pointer may be NULL.
+ * cx_postprocess3d_capped: cx_postprocess3d (flags bit 0: no clean-up) on the Level-0 mesh followed by the current cap; out_counts as
+ * cx_postprocess3d.  The result is a Level-1 mesh like any other for the downloads, components, topology, boundary loops, the
+ * filter, the simplifier, the clip and the plain writers; cx_level1_download_keys returns edge ids and lattice-point keys, and
+ * cx_level1_sample_grid samples a lattice-point vertex at its lattice point.  cx_level1_normals and cx_level1_curvature (and the
+ * writers' formats with normals) answer CX_ERR_UNSUPPORTED: a crease runs along the rim and has no single normal.
+ * Refused with CX_ERR_UNSUPPORTED and a message, before anything is written: a seeded selection in force, a negative origin or a
+ * reference corner (arrays carrying a margin), a positive origin (a slab of a larger volume).  Smoothing, the sharded post-pass and
+ * cx_postprocess3d_mesh take no cap.  CX_ERR_INVALID for unknown face or flag bits, CX_ERR_STATE without an extraction.
+ * All buffers belong to the context (counted by cx_device_bytes) and are reused; the table of the rim's crossings is sized by their
+ * number, not by the mesh.  Integer atomics only: every output is the same bit for bit in every call and context.
+ * cx_cap3d_info (measurement): of the current cap, info4 = {ms of cx_cap3d between HIP events on the context's stream, Level-0
+ * vertices on the selected faces, slots of the table, rim points}. */
+#define CX_CAP_BELOW        1u
+#define CX_CAP_ALL_FACES    63u
+int cx_cap3d(cx_ctx* ctx, uint32_t faces, uint32_t flags, int64_t* counts4);
+int cx_cap3d_download(cx_ctx* ctx, uint32_t* keys, int32_t* tris);
+int cx_cap3d_info(cx_ctx* ctx, double* info4);
+int cx_postprocess3d_capped(cx_ctx* ctx, uint32_t flags, int64_t* out_counts);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
