@@ -68,6 +68,7 @@ SYMBOLS = [
     "cx_level1_simplify", "cx_level1_simplify_map", "cx_level1_simplify_map_download",
     "cx_level1_clip_plane", "cx_level1_clip_scalars", "cx_level1_clip_map", "cx_level1_clip_map_download", "cx_level1_clip_info",
     "cx_cap3d", "cx_cap3d_download", "cx_cap3d_info", "cx_postprocess3d_capped",
+    "cx_samples_select", "cx_level_spectrum3d",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -127,6 +128,7 @@ CX_CAP_BELOW = 1
 CX_CAP_ALL_FACES = 63
 CAP_FACES = ("-x", "+x", "-y", "+y", "-z", "+z")      # bit 0: i = 0, bit 1: i = n0-1, bit 2: j = 0, ...
 CAP_KEYS = ("n_lattice_vertices", "n_cap_triangles", "n_missing_crossings", "n_rim_crossings")
+SPECTRUM_KEYS = ("n_cells", "n_vertices", "n_triangles", "n_near")
 
 
 def cap_faces_mask(faces):
@@ -279,6 +281,8 @@ def load():
         "cx_cap3d": [vp, u32, u32, vp],
         "cx_cap3d_download": [vp, vp, vp],
         "cx_cap3d_info": [vp, vp],
+        "cx_samples_select": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, vp, ctypes.c_int32, vp, ctypes.POINTER(i64)],
+        "cx_level_spectrum3d": [vp, vp, ctypes.c_int32, vp, vp, vp, vp],
         "cx_postprocess3d_capped": [vp, u32, vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
@@ -537,6 +541,31 @@ class Context(object):
         self._check(self.lib.cx_postprocess3d_capped(self.handle, int(flags), out.ctypes.data))
         return dict(n_vertices=int(out[0]), n_triangles=int(out[1]), n_after_weld=int(out[2]),
                     n_after_tiny=int(out[3]), n_components=int(out[4]))
+
+    def samples_select(self, ranks, samples=None, dtype=None, n=None):
+        """exact order statistics (cx_samples_select) -> (values float64 in the order of `ranks`, number of NaN samples).
+        samples: None = the bound 3-D grid; a numpy array of a type of DTYPE_CODES (copied to the device); or a device pointer (int)
+        with `dtype` and `n`"""
+        rk = np.ascontiguousarray(ranks, dtype=np.int64).reshape(-1)
+        out = np.empty(len(rk), dtype=np.float64)
+        n_nan = ctypes.c_int64()
+        if samples is None:
+            ptr, code, on_device, count, keep = None, 0, 1, 0, None
+        elif isinstance(samples, (int, np.integer)):
+            ptr, code, on_device, count, keep = ctypes.c_void_p(int(samples)), dtype_code(dtype), 1, int(n), None
+        else:
+            keep = native_array(samples)
+            ptr, code, on_device, count = ctypes.c_void_p(keep.ctypes.data), dtype_code(keep.dtype), 0, int(keep.size)
+        self._check(self.lib.cx_samples_select(self.handle, ptr, code, on_device, count, rk.ctypes.data, len(rk), out.ctypes.data, ctypes.byref(n_nan)))
+        return out, int(n_nan.value)
+
+    def level_spectrum3d(self, values):
+        """the size of the bound grid's isosurface at every one of `values` (cx_level_spectrum3d) -> dict of four int64 arrays in the
+        order of `values`: n_cells, n_vertices, n_triangles, n_near"""
+        vals = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        out = {k: np.zeros(len(vals), dtype=np.int64) for k in SPECTRUM_KEYS}
+        self._check(self.lib.cx_level_spectrum3d(self.handle, vals.ctypes.data, len(vals), *[out[k].ctypes.data for k in SPECTRUM_KEYS]))
+        return out
 
     def level0_points_f64(self, counts):
         "float64 coordinates of the Level-0 vertices as the reference interpolates them, in download_level0 order"

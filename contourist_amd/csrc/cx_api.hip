@@ -54,6 +54,7 @@ extern "C" int cx_ctx_destroy(cx_ctx* ctx) {
     cx_simplify_free(ctx);
     cx_clip_free(ctx);
     cx_cap_free(ctx);
+    cx_pick_free(ctx);
     cx_state4_free(ctx);
     cx_state2_free(ctx);
     if (ctx->counters_host) (void)hipHostFree(ctx->counters_host);

@@ -176,6 +176,9 @@ struct cx_ctx {
     // cap_valid: they hold the cap of what the context's Level-0 buffers hold now (cleared wherever those change hands)
     struct cx_cap_state* cap = nullptr;
     bool cap_valid = false;
+    // choosing isovalues (cx_pick.hip): histograms of the select, difference arrays and tables of the spectrum, the device copy of host
+    // samples, kept between calls.  Scratch only: nothing here describes the current extraction
+    struct cx_pick_state* pick = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -353,6 +356,8 @@ struct cx_cap_view {
     uint32_t ncv, nct;
 };
 int cx_cap_view_get(cx_ctx* ctx, const char* who, cx_cap_view* out);
+// cx_pick.hip
+void cx_pick_free(cx_ctx* ctx);
 bool cx_level1_capped(cx_ctx* ctx);   // cx_post.hip: the Level-1 mesh came out of cx_postprocess3d_capped (or is a filtered copy of one)
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);

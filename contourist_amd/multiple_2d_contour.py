@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _ffi
 from . import field2d
+from . import levels
 from . import triangulated
 
 
@@ -93,8 +94,9 @@ class Multiple2DContour(Multiple2DContourGrid):
 class Percentile2DContour(Multiple2DContourGrid):
     "levels = every (N / breakpoints)-th sample of the sorted lattice samples (multiple_2d_contour.py:84-98)"
 
-    def __init__(self, xmin, ymin, xmax, ymax, dx, dy, function, breakpoints=10, segment_endpoints=()):
+    def __init__(self, xmin, ymin, xmax, ymax, dx, dy, function, breakpoints=10, segment_endpoints=(), levels_on_device=False):
         self.function_grid = _grid2d(xmin, ymin, xmax, ymax, dx, dy, function)
+        self.levels_on_device = levels_on_device   # the levels by exact selection on the device (levels.py): the same values, no host sort
         self.values = self.get_values(breakpoints)
         Multiple2DContourGrid.__init__(self, self.function_grid, self.values, segment_endpoints)
 
@@ -102,7 +104,13 @@ class Percentile2DContour(Multiple2DContourGrid):
         "the lattice samples the device contours (float64 view of the fp32 array)"
         return np.asarray(triangulated.grid_lattice(self.function_grid)[2], dtype=np.float64)
 
+    def _lattice(self):
+        "the fp32 lattice samples themselves (their float64 view has the same order and the same values)"
+        return triangulated.grid_lattice(self.function_grid)[2]
+
     def get_values(self, breakpoints):
+        if self.levels_on_device:
+            return levels.percentile_values(self._lattice(), breakpoints, triangulated._DEFAULT_DEVICE[0])
         ordered = np.sort(self._samples(), axis=None)
         stride = int(ordered.size / breakpoints)
         return list(ordered[stride::stride])
@@ -112,6 +120,8 @@ class Linear2DContour(Percentile2DContour):
     "levels = multiples of (max - min) / breakpoints, as the reference computes them (multiple_2d_contour.py:100-108)"
 
     def get_values(self, breakpoints):
+        if self.levels_on_device:
+            return levels.linear_values(self._lattice(), breakpoints, triangulated._DEFAULT_DEVICE[0])
         samples = self._samples()
         step = (samples.max() - samples.min()) * (1.0 / breakpoints)
         return [step * k for k in range(1, breakpoints)]

@@ -1151,6 +1151,39 @@ class MultiLevelIsosurfaces(object):
         self._ctx = _ffi.Context(self.device)
         self.counts = None
         self._current = None
+        self._bound = False           # the context holds this object's samples (levels() binds them anew; spectrum() only if needed)
+
+    @classmethod
+    def at_quantiles(cls, mins, maxes, delta, function, q, **kw):
+        """the levels at the q-quantiles (q in [0, 1]) of the field's own samples, NaN samples left out: exact order statistics
+        taken on the device (levels.quantiles), no sort and no sample of the samples"""
+        from . import levels as _levels
+        made = cls(mins, maxes, delta, function, (), **kw)
+        made.values = sorted(float(v) for v in _levels.quantiles(made.grid.dense_samples(), q, made.device))
+        return made
+
+    def _bind_grid(self, samples):
+        shape = tuple(int(n) for n in samples.shape)
+        ctx = self._ctx
+        if grid_field._is_torch(samples):
+            assert samples.is_cuda and samples.is_contiguous() and _ffi.native_dtype(samples.dtype), \
+                "device samples must be a contiguous tensor on the GPU of a supported dtype (%s)" % ", ".join(_ffi.DTYPE_CODES)
+            ctx.adopt_device_grid(samples.data_ptr(), shape, keepalive=samples, dtype=samples.dtype)
+        else:
+            ctx.upload_grid_native(samples)
+        ctx.set_origin(0, 0, 0)
+        ctx.set_reference_corner((0, 0, 0))
+        self._bound = True
+
+    def spectrum(self, values=None):
+        """the size of the surface at every one of `values` (default: the object's own), without marching any: dict of four int64
+        arrays in the order of `values` -- n_cells (whole cells the surface passes through), n_vertices, n_triangles (the march's
+        n_border_voxels, n_vertices and n_triangles at that value wherever n_near is 0) and n_near.  One pass over the samples for
+        all values; levels already marched stay as they are."""
+        from . import levels as _levels
+        if not self._bound:
+            self._bind_grid(self.grid.dense_samples())
+        return _levels.spectrum_of_context(self._ctx, self.values if values is None else values)
 
     def levels(self, clean=True, cap=None):
         """cap: None, or the faces of GridContour3d.cap_rim ("all", a mask, names) -- every level is then capped (side "above") after it is
@@ -1161,6 +1194,7 @@ class MultiLevelIsosurfaces(object):
         shape = tuple(int(n) for n in samples.shape)
         ctx = self._ctx
         if shape[2] < 4:          # rows shorter than 4 samples take the shape-agnostic kernel: one level at a time
+            self._bound = False
             for n, v in enumerate(self.values):
                 maker = GridContour3d(corner, samples, v, None, context=ctx)
                 if cap_mask is not None:
@@ -1171,14 +1205,7 @@ class MultiLevelIsosurfaces(object):
                                    triangles))._bind(self, n, maker._post, self.grid.delta, self.grid.mins)
             self._current = None
             return
-        if grid_field._is_torch(samples):
-            assert samples.is_cuda and samples.is_contiguous() and _ffi.native_dtype(samples.dtype), \
-                "device samples must be a contiguous tensor on the GPU of a supported dtype (%s)" % ", ".join(_ffi.DTYPE_CODES)
-            ctx.adopt_device_grid(samples.data_ptr(), shape, keepalive=samples, dtype=samples.dtype)
-        else:
-            ctx.upload_grid_native(samples)
-        ctx.set_origin(0, 0, 0)
-        ctx.set_reference_corner((0, 0, 0))
+        self._bind_grid(samples)
         self.counts = ctx.extract3d_levels(self.values, self.flags)
         for n, v in enumerate(self.values):
             ctx.select_level(n)

@@ -635,6 +635,48 @@ int cx_cap3d_download(cx_ctx* ctx, uint32_t* keys, int32_t* tris);
 int cx_cap3d_info(cx_ctx* ctx, double* info4);
 int cx_postprocess3d_capped(cx_ctx* ctx, uint32_t flags, int64_t* out_counts);
 
+/* ---- choosing isovalues: exact order statistics of the samples, and the size of the surface at many candidate values ----------------
+ * Replaces the host sort behind the reference's level pickers (Percentile2DContour / Linear2DContour, multiple_2d_contour.py:84-108:
+ * np.sort of all samples, every (N / breakpoints)-th of them; min and max) and answers what the reference has no call for: how large
+ * the isosurface is at each of a few hundred candidate values, without marching any of them.
+ *
+ * cx_samples_select: exact order statistics.
+ *   samples  NULL: the bound 3-D grid in its own CX_DTYPE_* (dtype, on_device and n are ignored; CX_ERR_STATE without a grid).  Else n
+ *            samples (1 <= n <= 2^31) of type `dtype`, on the device (on_device != 0: any pointer aligned to its own type, e.g. a slice
+ *            of a larger array, a 2-D or 4-D array) or on the host (copied into scratch of the context).
+ *   ranks    nranks (1..1024) zero-based ranks in any order, repeats allowed; a rank >= n is CX_ERR_INVALID.
+ *   out_values[k] = the sample of rank ranks[k] in numpy's sort order of the samples as fp32 (every type converts to fp32 exactly):
+ *            -inf < finite < +inf < NaN, NaN of either sign last, -0.0 and +0.0 equal (either may be returned).  That is
+ *            np.sort(x.astype(np.float32), axis=None)[ranks[k]], NaN for NaN.  Exact: no sampling, no bins.
+ *   out_n_nan  the number of NaN samples (may be NULL).  Minimum and maximum are ranks 0 and n - 1 - n_nan.
+ *   Method: most-significant-digit radix select on order-preserving keys of the type's own width (8-bit types one pass over the
+ *   samples, 16-bit types two, fp32 three of 12 / 10 / 10 bits); ranks that fall under different key prefixes are refined together, 12
+ *   prefixes to a pass.  Counts are integers, summed in 64 bits.
+ *
+ * cx_level_spectrum3d: the per-level size curve of the bound grid (any CX_DTYPE_*, at least 2 samples per axis), one pass over the
+ * samples for all levels.
+ *   values   nlevels (1..4096) finite values of fp32 magnitude, any order, duplicates allowed; the outputs are in the order of `values`
+ *            and any of them may be NULL.
+ *   For a value v let vcmp and near_abs be what the march compares with (vcmp = the smallest fp32 >= v, -0.0 for 0; near_abs = the fp32
+ *   above 2.2e-5 |v| + 4e-8).  A sample f is LOW iff f < vcmp; a NaN is never low.
+ *   n_cells      lattice cells (all 8 corners inside the array) with a low and a non-low corner
+ *   n_vertices   lattice edges with one low and one non-low end, an edge running from a lattice point to one of its 7 forward
+ *                neighbours (di, dj, dk) != 0 inside the array: the edges of the 6 Kuhn tetrahedra
+ *   n_triangles  over the 6 tetrahedra of every cell: 1 for a tetrahedron with 1 or 3 low corners, 2 for one with 2
+ *   n_near       samples inside the march's tolerance screen: fabsf(f - vcmp) <= near_abs, evaluated in fp32
+ *   Where n_near[l] == 0 they are the counts of cx_extract3d(values[l]): n_vertices and n_triangles are its n_vertices and
+ *   n_triangles, n_cells is its n_border_voxels (the reference's len(surface_voxels)) -- and its n_cells wherever the surface stays
+ *   off the upper faces of the array: the march also keeps a cell record for a lattice point of those faces that owns a crossing
+ *   edge but no whole cell, so its n_cells lies between n_cells and n_cells + n_vertices here.  Enough to size cx_reserve, or to plot
+ *   the curve and trust it.  Where n_near[l] > 0 the reference's np.allclose skips may make the march emit fewer.
+ *   CX_ERR_STATE without a grid, CX_ERR_INVALID for a count outside 1..4096 or a value that is NaN, infinite or beyond fp32.
+ * Both calls keep their own scratch in the context (counted by cx_device_bytes) and leave the current extraction, the selected level of
+ * cx_extract3d_levels and the Level-1 state as they are.  Integer atomics only: every result is the same in every call. */
+int cx_samples_select(cx_ctx* ctx, const void* samples, int32_t dtype, int on_device, int64_t n, const int64_t* ranks, int32_t nranks,
+                      double* out_values, int64_t* out_n_nan);
+int cx_level_spectrum3d(cx_ctx* ctx, const double* values, int32_t nlevels, int64_t* n_cells, int64_t* n_vertices, int64_t* n_triangles,
+                        int64_t* n_near);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
