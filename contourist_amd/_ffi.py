@@ -51,6 +51,12 @@ class cx_loop(ctypes.Structure):
     _fields_ = [("component", ctypes.c_int32), ("simple", ctypes.c_int32), ("first", ctypes.c_uint32), ("count", ctypes.c_uint32)]
 
 
+class cx_filter_axis(ctypes.Structure):
+    "one axis of cx_grid_filter3d: 24 bytes"
+    _fields_ = [("weights", ctypes.c_void_p), ("n_weights", ctypes.c_int32), ("origin", ctypes.c_int32), ("stride", ctypes.c_int32)]
+
+
+FILTER_MODES = {"nearest": 0, "reflect": 1, "constant": 2}
 TOPOLOGY_DTYPE = np.dtype([("triangles", "<i8"), ("vertices", "<i8"), ("edges", "<i8"), ("boundary_edges", "<i8"), ("nonmanifold_edges", "<i8"),
                            ("euler", "<i8"), ("boundary_loops", "<i4"), ("genus", "<i4"), ("nonsimple_loops", "<i4"), ("reserved", "<i4")])
 LOOP_DTYPE = np.dtype([("component", "<i4"), ("simple", "<i4"), ("first", "<u4"), ("count", "<u4")])
@@ -69,6 +75,7 @@ SYMBOLS = [
     "cx_level1_clip_plane", "cx_level1_clip_scalars", "cx_level1_clip_map", "cx_level1_clip_map_download", "cx_level1_clip_info",
     "cx_cap3d", "cx_cap3d_download", "cx_cap3d_info", "cx_postprocess3d_capped",
     "cx_samples_select", "cx_level_spectrum3d",
+    "cx_grid_filter3d", "cx_grid_filter3d_result", "cx_grid_filter3d_bind",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -284,6 +291,9 @@ def load():
         "cx_samples_select": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, vp, ctypes.c_int32, vp, ctypes.POINTER(i64)],
         "cx_level_spectrum3d": [vp, vp, ctypes.c_int32, vp, vp, vp, vp],
         "cx_postprocess3d_capped": [vp, u32, vp],
+        "cx_grid_filter3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, vp, ctypes.c_int32, dbl, vp, vp, vp],
+        "cx_grid_filter3d_result": [vp, ctypes.POINTER(vp), vp],
+        "cx_grid_filter3d_bind": [vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -566,6 +576,64 @@ class Context(object):
         out = {k: np.zeros(len(vals), dtype=np.int64) for k in SPECTRUM_KEYS}
         self._check(self.lib.cx_level_spectrum3d(self.handle, vals.ctypes.data, len(vals), *[out[k].ctypes.data for k in SPECTRUM_KEYS]))
         return out
+
+    def filter_grid(self, axes, mode="nearest", cval=0.0, samples=None, out=None, download=False):
+        """separable filter with a stride per axis (cx_grid_filter3d) -> (shape of the result, the result).
+        axes: three of (weights or None, origin, stride), for axis 0, 1, 2.  mode: a name of FILTER_MODES.
+        samples: None = the bound 3-D grid; a 3-D numpy array of a type of DTYPE_CODES (copied to the device);
+        (device pointer, dtype, shape) of contiguous samples on the device; or (numpy array, dtype, shape): host samples whose
+        type is `dtype` whatever numpy calls their bytes.
+        out: None = the result stays in the context (filter_result, bind_filtered); or a device pointer to room for the result.
+        The result: a numpy array with download=True, else its device pointer (an int; the context's own buffer is valid until the
+        next filter_grid or bind_filtered)."""
+        assert len(axes) == 3
+        recs, keep = (cx_filter_axis * 3)(), []
+        for a, (weights, origin, stride) in enumerate(axes):
+            w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+            keep.append(w)
+            recs[a].weights = None if w is None or not len(w) else w.ctypes.data
+            recs[a].n_weights = 0 if w is None else len(w)
+            recs[a].origin, recs[a].stride = int(origin), int(stride)
+        if samples is None:
+            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
+        elif isinstance(samples, tuple) and isinstance(samples[0], np.ndarray):      # host bytes of a type numpy has no name for (bfloat16 as uint16)
+            host = np.ascontiguousarray(samples[0])
+            keep.append(host)
+            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(samples[1]), 0, tuple(int(n) for n in samples[2])
+        elif isinstance(samples, tuple):
+            ptr, code, on_device, shape = ctypes.c_void_p(int(samples[0])), dtype_code(samples[1]), 1, tuple(int(n) for n in samples[2])
+        else:
+            host = native_array(samples)
+            keep.append(host)
+            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
+        assert len(shape) == 3, "3-D sample array expected"
+        m = np.zeros(3, dtype=np.int64)
+        if download:      # the shape first: it follows from the shape and the strides alone
+            n = self.shape if samples is None else shape
+            if n is None:
+                raise CxError(CX_ERR_STATE, "filter_grid: no samples given and no grid bound")
+            host_out = np.empty([-(-int(n[a]) // max(1, int(axes[a][2]))) for a in range(3)], dtype=np.float32)
+        self._check(self.lib.cx_grid_filter3d(self.handle, ptr, code, on_device, shape[0], shape[1], shape[2], ctypes.cast(recs, ctypes.c_void_p),
+                                              FILTER_MODES[mode], float(cval), ctypes.c_void_p(int(out)) if out else None,
+                                              host_out.ctypes.data if download else None, m.ctypes.data))
+        shape_out = tuple(int(x) for x in m)
+        if download:
+            assert host_out.shape == shape_out
+            return shape_out, host_out
+        return shape_out, (int(out) if out else self.filter_result()[1])
+
+    def filter_result(self):
+        "(shape, device pointer) of the result the last filter_grid left in the context (cx_grid_filter3d_result)"
+        p, m = ctypes.c_void_p(), np.zeros(3, dtype=np.int64)
+        self._check(self.lib.cx_grid_filter3d_result(self.handle, ctypes.byref(p), m.ctypes.data))
+        return tuple(int(x) for x in m), int(p.value or 0)
+
+    def bind_filtered(self):
+        "the result the last filter_grid left in the context becomes the bound grid (float32, owned by the context): cx_grid_filter3d_bind"
+        shape = self.filter_result()[0]
+        self._check(self.lib.cx_grid_filter3d_bind(self.handle))
+        self.shape = shape
+        self._keep = None
 
     def level0_points_f64(self, counts):
         "float64 coordinates of the Level-0 vertices as the reference interpolates them, in download_level0 order"

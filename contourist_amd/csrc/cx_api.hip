@@ -55,6 +55,7 @@ extern "C" int cx_ctx_destroy(cx_ctx* ctx) {
     cx_clip_free(ctx);
     cx_cap_free(ctx);
     cx_pick_free(ctx);
+    cx_filter_free(ctx);
     cx_state4_free(ctx);
     cx_state2_free(ctx);
     if (ctx->counters_host) (void)hipHostFree(ctx->counters_host);
@@ -101,6 +102,18 @@ static int set_grid_dims(cx_ctx* ctx, int64_t n0, int64_t n1, int64_t n2) {
     return CX_OK;
 }
 
+int cx_grid_bind_owned(cx_ctx* ctx, cx_buf<uint8_t>& buf, int32_t dtype, int64_t n0, int64_t n1, int64_t n2) {
+    const int rc = set_grid_dims(ctx, n0, n1, n2);
+    if (rc) return rc;
+    ctx->grid = {nullptr, CX_DTYPE_F32};
+    if (&buf != &ctx->grid_owned) {
+        ctx->grid_owned = std::move(buf);   // (releases the grid owned before)
+        buf = cx_buf<uint8_t>();
+    }
+    ctx->grid = {ctx->grid_owned, dtype};
+    return CX_OK;
+}
+
 extern "C" int cx_grid_upload_typed(cx_ctx* ctx, const void* host, int32_t dtype, int64_t n0, int64_t n1, int64_t n2) {
     if (!ctx || !host) return CX_ERR_INVALID;
     if (!cx_dtype_valid(dtype)) return fail(ctx, CX_ERR_INVALID, ("cx_grid_upload_typed: unknown sample type " + std::to_string(dtype)).c_str());
@@ -113,8 +126,7 @@ extern "C" int cx_grid_upload_typed(cx_ctx* ctx, const void* host, int32_t dtype
     if (rc) return rc;
     CX_HIP(ctx, hipMemcpyAsync(ctx->grid_owned, host, bytes, hipMemcpyHostToDevice, ctx->stream));
     CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->grid = {ctx->grid_owned, dtype};
-    return CX_OK;
+    return cx_grid_bind_owned(ctx, ctx->grid_owned, dtype, n0, n1, n2);
 }
 
 extern "C" int cx_grid_upload(cx_ctx* ctx, const float* host, int64_t n0, int64_t n1, int64_t n2) {

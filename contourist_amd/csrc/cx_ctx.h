@@ -179,6 +179,9 @@ struct cx_ctx {
     // choosing isovalues (cx_pick.hip): histograms of the select, difference arrays and tables of the spectrum, the device copy of host
     // samples, kept between calls.  Scratch only: nothing here describes the current extraction
     struct cx_pick_state* pick = nullptr;
+    // preparing the volume (cx_filter.hip): the device copy of host samples, the result of the first kernel, and the context's own result
+    // until cx_grid_filter3d_bind makes it the bound grid.  Nothing here describes the current extraction
+    struct cx_filter_state* filt = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -244,6 +247,10 @@ int cx_buf<T>::grow_keep(cx_ctx* ctx, size_t used, size_t need) {
 }
 
 // cx_api.hip
+// `buf` (n0 n1 n2 samples of `dtype`) becomes the bound grid, owned by the context: what cx_grid_upload_typed does once its samples are
+// in place.  Everything that described the previous grid is reset, the previous owned grid is released; `buf` is left empty.  On a
+// shape the march does not take nothing changes.
+int cx_grid_bind_owned(cx_ctx* ctx, cx_buf<uint8_t>& buf, int32_t dtype, int64_t n0, int64_t n1, int64_t n2);
 int cx_ensure_cell_records(cx_ctx* ctx);
 int cx_ensure_hash_xy(cx_ctx* ctx, uint32_t flags);
 int cx_level0_expanded(cx_ctx* ctx, float4** out);   // the records of the current extraction as float4 {x,y,z,id} (device, enqueued on the stream)
@@ -358,6 +365,8 @@ struct cx_cap_view {
 int cx_cap_view_get(cx_ctx* ctx, const char* who, cx_cap_view* out);
 // cx_pick.hip
 void cx_pick_free(cx_ctx* ctx);
+// cx_filter.hip
+void cx_filter_free(cx_ctx* ctx);
 bool cx_level1_capped(cx_ctx* ctx);   // cx_post.hip: the Level-1 mesh came out of cx_postprocess3d_capped (or is a filtered copy of one)
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);

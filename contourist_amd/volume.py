@@ -1,0 +1,181 @@
+"""Preparing the volume on the device: smoothing, binning and level-of-detail pyramids of a sample array before it is marched
+(`cx_grid_filter3d`, csrc/cx_filter.hip).
+
+Everything here is one operation: per axis a row of fp32 weights, an origin and a stride,
+
+    out[i] = (float32) sum_k float64(weights[k]) * float64(in[src(i * stride + k - origin)])
+
+summed in float64 with k ascending and rounded to float32 once per axis; the axes are filtered last axis first, float32 between
+them.  `src` is the boundary rule: "nearest", "reflect" or "constant" (`cval`), as scipy.ndimage names them.  tests/filter_ref.py
+restates it in numpy and the device result equals it bit for bit.
+
+Samples are a numpy array or a contiguous tensor already on the GPU, of 1 to 3 dimensions (missing leading axes count as axes of
+length 1 that are not filtered).  Types the kernels read (float32, uint8, int8, uint16, int16, float16, bfloat16) are loaded as
+they are and converted in registers; any other type is converted to float32 first.  The result is float32: a numpy array for numpy
+samples, a device tensor for a tensor.
+
+`lattice_of` gives the `(mins, delta)` of the result's lattice, so that a result goes straight into
+`FunctionGrid.from_array(result, mins, delta)` or `MultiLevelIsosurfaces` and lands where the data is.
+"""
+import numpy as np
+
+from . import _ffi
+from . import grid_field
+
+MAX_WEIGHTS = 129      # per axis of cx_grid_filter3d
+PYRAMID_WEIGHTS = (1.0 / 16.0, 4.0 / 16.0, 6.0 / 16.0, 4.0 / 16.0, 1.0 / 16.0)
+
+_contexts = {}
+
+
+def _context(device=None):
+    "one context per device for the calls of this module (its scratch is kept between calls)"
+    if device is None:
+        from . import triangulated
+        device = triangulated._DEFAULT_DEVICE[0]
+    device = int(device)
+    if device not in _contexts:
+        _contexts[device] = _ffi.Context(device)
+    return _contexts[device]
+
+
+def _per_axis(value, ndim, neutral, name):
+    "a scalar for all axes of the array, or one value per axis of the array -> three values, `neutral` on the padded leading axes"
+    if np.ndim(value) == 0:
+        vals = [value] * ndim
+    else:
+        vals = list(value)
+        assert len(vals) == ndim, "%s: one value or one per axis of the samples (%d)" % (name, ndim)
+    return [neutral] * (3 - ndim) + vals
+
+
+def _weights_per_axis(weights, ndim):
+    "one 1-D row of weights for all axes of the array, or a list with a row or None per axis -> three rows (float32) or None"
+    per_axis = isinstance(weights, (list, tuple)) and len(weights) == ndim and all(w is None or np.ndim(w) == 1 for w in weights)
+    rows = list(weights) if per_axis else [weights] * ndim
+    out = [None] * (3 - ndim)
+    for w in rows:
+        if w is None:
+            out.append(None)
+            continue
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        assert w.ndim == 1 and 1 <= len(w) <= MAX_WEIGHTS, "1 to %d weights per axis" % MAX_WEIGHTS
+        out.append(w)
+    return out
+
+
+def default_origin(n_weights):
+    "the tap that sits on the output sample when no origin is given: the middle one, n_weights // 2 (scipy.ndimage's centre)"
+    return int(n_weights) // 2
+
+
+def gaussian_weights(sigma, truncate=4.0):
+    """scipy.ndimage's Gaussian kernel: exp(-k^2 / (2 sigma^2)) for k = -r .. r, r = int(truncate * sigma + 0.5), computed and
+    normalised in float64, then rounded to float32.  None for sigma == 0 (the axis is not filtered)."""
+    sigma = float(sigma)
+    assert sigma >= 0.0 and np.isfinite(sigma), "sigma is a finite number >= 0"
+    if sigma == 0.0:
+        return None
+    radius = int(float(truncate) * sigma + 0.5)
+    assert 2 * radius + 1 <= MAX_WEIGHTS, "truncate * sigma is at most %d samples" % ((MAX_WEIGHTS - 1) // 2)
+    k = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * k ** 2)
+    return (phi / phi.sum()).astype(np.float32)
+
+
+def block_mean_weights(factor):
+    "`factor` taps of 1 / factor (the float32 nearest to it); None for factor 1"
+    factor = int(factor)
+    assert 1 <= factor <= MAX_WEIGHTS, "a factor of 1 to %d" % MAX_WEIGHTS
+    if factor == 1:
+        return None
+    return np.full(factor, np.float64(1.0) / np.float64(factor)).astype(np.float32)
+
+
+def convolve_separable(samples, weights, strides=1, origins=None, mode="nearest", cval=0.0, device=None):
+    """the operation of this module.  weights: one 1-D row for all axes, or a list with one row or None (axis not filtered) per axis
+    of `samples`; strides, origins: one value or one per axis; origins None: the middle tap (`default_origin`).  An axis keeps every
+    stride-th output: ceil(n / stride) samples."""
+    on_device = grid_field._is_torch(samples)
+    if on_device:
+        t = samples
+        assert t.is_cuda, "a tensor of samples must be on the GPU (pass host samples as a numpy array)"
+        if not _ffi.native_dtype(t.dtype):
+            t = t.float()
+        assert t.is_contiguous(), "a tensor of samples must be contiguous"
+        shape = tuple(int(n) for n in t.shape)
+    else:
+        a = np.asarray(samples)
+        if not _ffi.native_dtype(a.dtype):
+            a = a.astype(np.float32)
+        a = _ffi.native_array(a)
+        shape = tuple(int(n) for n in a.shape)
+    ndim = len(shape)
+    assert 1 <= ndim <= 3, "samples of 1 to 3 dimensions"
+    rows = _weights_per_axis(weights, ndim)
+    st = [int(s) for s in _per_axis(strides, ndim, 1, "strides")]
+    if origins is None:
+        og = [0 if w is None else default_origin(len(w)) for w in rows]
+    else:
+        og = [int(o) for o in _per_axis(origins, ndim, 0, "origins")]
+    axes = [(rows[k], og[k] if rows[k] is not None else 0, st[k]) for k in range(3)]
+    shape3 = (1,) * (3 - ndim) + shape
+    if on_device:
+        import torch
+        context = _context(t.device.index if device is None else device)
+        out = torch.empty([-(-shape3[k] // max(1, st[k])) for k in range(3)], dtype=torch.float32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()      # the samples are there; the context has a stream of its own
+        got, _ = context.filter_grid(axes, mode, cval, samples=(t.data_ptr(), t.dtype, shape3), out=out.data_ptr())
+        context.synchronize()
+        assert got == tuple(out.shape)
+        return out.reshape(got[3 - ndim:])
+    context = _context(device)
+    got, result = context.filter_grid(axes, mode, cval, samples=a.reshape(shape3), download=True)
+    return result.reshape(got[3 - ndim:])
+
+
+def gaussian(samples, sigma, truncate=4.0, stride=1, mode="nearest", cval=0.0, device=None):
+    """scipy.ndimage.gaussian_filter of the float32 samples, every stride-th sample kept.  sigma, stride: one value or one per axis;
+    sigma == 0 leaves an axis unfiltered."""
+    ndim = len(samples.shape)
+    sig = _per_axis(sigma, ndim, 0.0, "sigma")[3 - ndim:]
+    return convolve_separable(samples, [gaussian_weights(s, truncate) for s in sig], stride, None, mode, cval, device)
+
+
+def block_mean(samples, factor, mode="nearest", cval=0.0, device=None):
+    """the mean over blocks of `factor` samples (one value or one per axis): `factor` taps of 1 / factor from the block's first sample,
+    stride `factor`.  A partial last block is completed by the boundary rule."""
+    ndim = len(samples.shape)
+    fac = [int(f) for f in _per_axis(factor, ndim, 1, "factor")[3 - ndim:]]
+    return convolve_separable(samples, [block_mean_weights(f) for f in fac], fac, 0, mode, cval, device)
+
+
+def pyramid(samples, levels, mode="nearest", cval=0.0, device=None):
+    "[samples, half, quarter, ...] (`levels` arrays): each the one before filtered with [1, 4, 6, 4, 1] / 16 at stride 2"
+    out = [samples]
+    for _ in range(int(levels) - 1):
+        prev = out[-1]
+        strides = [2 if int(n) >= 2 else 1 for n in prev.shape]
+        rows = [np.asarray(PYRAMID_WEIGHTS, dtype=np.float32) if int(n) >= 2 else None for n in prev.shape]
+        out.append(convolve_separable(prev, rows, strides, None, mode, cval, device))
+    return out
+
+
+def lattice_of(mins, delta, strides=1, origins=None, weights=None):
+    """(mins, delta) of the lattice of a result, given those of the samples: delta times the stride, mins shifted by
+    (n_weights - 1) / 2 - origin samples -- the centre of the taps of output 0.  Zero for a centred kernel of odd length,
+    (factor - 1) / 2 for `block_mean`.  weights: as in `convolve_separable`; None: nothing is shifted."""
+    mins = np.asarray(mins, dtype=np.float64).reshape(-1)
+    ndim = len(mins)
+    delta = np.asarray(_per_axis(delta, ndim, 1.0, "delta")[3 - ndim:] if np.ndim(delta) else [delta] * ndim, dtype=np.float64)
+    st = np.asarray(_per_axis(strides, ndim, 1, "strides")[3 - ndim:], dtype=np.float64)
+    if weights is None:
+        taps = [0] * ndim
+    else:
+        taps = [0 if w is None else len(w) for w in _weights_per_axis(weights, ndim)[3 - ndim:]]
+    if origins is None:
+        og = [default_origin(n) for n in taps]
+    else:
+        og = [int(o) for o in _per_axis(origins, ndim, 0, "origins")[3 - ndim:]]
+    shift = np.asarray([(n - 1) / 2.0 - o if n else 0.0 for n, o in zip(taps, og)], dtype=np.float64)
+    return mins + shift * delta, delta * st

@@ -677,6 +677,47 @@ int cx_samples_select(cx_ctx* ctx, const void* samples, int32_t dtype, int on_de
 int cx_level_spectrum3d(cx_ctx* ctx, const double* values, int32_t nlevels, int64_t* n_cells, int64_t* n_vertices, int64_t* n_triangles,
                         int64_t* n_near);
 
+/* ---- preparing the volume: a separable filter with a stride per axis, on the device ----------------------------------------------
+ * Smoothing (a Gaussian), binning (a block mean) and one step of a pyramid are all one operation: per axis a row of weights, an origin
+ * and a stride.  The reference has no call for it; a caller ran scipy.ndimage on the host and uploaded again.
+ *
+ * cx_grid_filter3d
+ *   samples  NULL: the bound 3-D grid in its own CX_DTYPE_* (dtype, on_device and the shape are ignored; CX_ERR_STATE without a grid).
+ *            Else n0 n1 n2 samples of type `dtype` (every axis >= 1: a 2-D array goes in as 1 x n x m; at most 2^31 samples), on the
+ *            device (any pointer aligned to its own type) or on the host (copied into scratch of the context).
+ *   axes[a]  for axis a: n_weights fp32 weights (1..129), origin (0 .. n_weights-1) and stride (1 .. n_a).  weights == NULL or
+ *            n_weights == 0: the axis is not filtered, only the stride applies (out[i] = in[i stride] as fp32, origin ignored).
+ *   The passes run axis 2, then axis 1, then axis 0, each on the fp32 result of the one before.  Per axis, with n the length of the
+ *   axis going in, the length coming out is m = ceil(n / stride) and
+ *       out[i] = (float) sum over k = 0 .. n_weights-1 of (double)weights[k] * (double)in[src(i stride + k - origin)]
+ *   summed in double with k ascending from +0.0 and rounded to fp32 once per pass.  (The product of two fp32 numbers is exact in double,
+ *   so a fused multiply-add gives the same double as a multiply and an add: the bits do not depend on how the sum is compiled.)
+ *   src is the boundary rule of `mode`: CX_FILTER_NEAREST clamps the index to [0, n-1]; CX_FILTER_REFLECT takes p = j mod 2n
+ *   (non-negative) and reads p < n ? p : 2n-1-p, so a radius beyond the axis is legal; CX_FILTER_CONSTANT reads (float)cval outside.
+ *   These are scipy.ndimage's 'nearest', 'reflect' and 'constant'.
+ *   out_device  not NULL: m0 m1 m2 fp32 values are written there (device memory of the caller; CX_ERR_INVALID if it overlaps the
+ *            input), and the context keeps no result.  NULL: the result goes into a buffer the context owns (counted by
+ *            cx_device_bytes, reused by the next call) and stays pending until the next call or cx_grid_filter3d_bind.
+ *   out_host    not NULL: also receives a copy.  out_shape (may be NULL) receives {m0, m1, m2}.
+ *   CX_ERR_INVALID: an unknown mode or sample type, a NaN or infinite cval, n_weights, origin or stride outside their ranges, a shape
+ *   outside its range.
+ * cx_grid_filter3d_result: the pending result, device pointer and shape; CX_ERR_STATE when none is pending.
+ * cx_grid_filter3d_bind: the pending result becomes the bound grid -- CX_DTYPE_F32, owned by the context, of the result's shape -- as
+ *   if it had been uploaded: the float64 originals, the current extraction, the levels and the Level-1 state of the grid before are
+ *   gone and the grid the context owned before is released.  No host copy of the filtered samples ever exists.  Afterwards nothing is
+ *   pending (a second bind or a _result answers CX_ERR_STATE).  A result the march does not take (an axis shorter than 2, more than
+ *   2^29 samples) is refused as an upload of that shape is, and stays pending.
+ * Filtering without binding leaves the bound grid, the current extraction, the selected level of cx_extract3d_levels and the Level-1
+ * state as they are.  No atomics: every call gives the same bits. */
+#define CX_FILTER_NEAREST  0
+#define CX_FILTER_REFLECT  1
+#define CX_FILTER_CONSTANT 2
+typedef struct cx_filter_axis { const float* weights; int32_t n_weights; int32_t origin; int32_t stride; } cx_filter_axis;
+int cx_grid_filter3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                     const cx_filter_axis axes[3], int32_t mode, double cval, void* out_device, float* out_host, int64_t out_shape[3]);
+int cx_grid_filter3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3]);
+int cx_grid_filter3d_bind(cx_ctx* ctx);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
