@@ -57,6 +57,9 @@ class cx_filter_axis(ctypes.Structure):
 
 
 FILTER_MODES = {"nearest": 0, "reflect": 1, "constant": 2}
+DIST_SIDES = {"below": 0, "above": 1, "signed": 2}                  # CX_DIST_*
+DIST_KINDS = {"squared": 0, "float32": 1, "mask": 2}                # CX_DIST_OUT_*
+DIST_KIND_DTYPES = {0: np.float64, 1: np.float32, 2: np.uint8}
 TOPOLOGY_DTYPE = np.dtype([("triangles", "<i8"), ("vertices", "<i8"), ("edges", "<i8"), ("boundary_edges", "<i8"), ("nonmanifold_edges", "<i8"),
                            ("euler", "<i8"), ("boundary_loops", "<i4"), ("genus", "<i4"), ("nonsimple_loops", "<i4"), ("reserved", "<i4")])
 LOOP_DTYPE = np.dtype([("component", "<i4"), ("simple", "<i4"), ("first", "<u4"), ("count", "<u4")])
@@ -76,6 +79,7 @@ SYMBOLS = [
     "cx_cap3d", "cx_cap3d_download", "cx_cap3d_info", "cx_postprocess3d_capped",
     "cx_samples_select", "cx_level_spectrum3d",
     "cx_grid_filter3d", "cx_grid_filter3d_result", "cx_grid_filter3d_bind",
+    "cx_grid_distance3d", "cx_grid_distance3d_result", "cx_grid_distance3d_bind",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -294,6 +298,9 @@ def load():
         "cx_grid_filter3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, vp, ctypes.c_int32, dbl, vp, vp, vp],
         "cx_grid_filter3d_result": [vp, ctypes.POINTER(vp), vp],
         "cx_grid_filter3d_bind": [vp],
+        "cx_grid_distance3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, dbl, vp, ctypes.c_int32, ctypes.c_int32, dbl, vp, vp, vp],
+        "cx_grid_distance3d_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)],
+        "cx_grid_distance3d_bind": [vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -632,6 +639,58 @@ class Context(object):
         "the result the last filter_grid left in the context becomes the bound grid (float32, owned by the context): cx_grid_filter3d_bind"
         shape = self.filter_result()[0]
         self._check(self.lib.cx_grid_filter3d_bind(self.handle))
+        self.shape = shape
+        self._keep = None
+
+    def distance_grid(self, value, side="below", kind="float32", sampling=None, radius2=0.0, samples=None, out=None, download=False):
+        """exact Euclidean distance transform of the samples thresholded at `value` (cx_grid_distance3d) -> (n_sites, the result).
+        side: a name of DIST_SIDES; kind: a name of DIST_KINDS ("squared": float64 squared distances, "float32": distances, "mask":
+        uint8, 1 where the squared distance is <= radius2); sampling: None or the three steps of the lattice.
+        samples: as in filter_grid (None = the bound grid, a 3-D numpy array, (device pointer, dtype, shape), (numpy array, dtype, shape)).
+        out: None = the result stays in the context (distance_result, bind_distance); or a device pointer to room for the result.
+        The result: a numpy array of the kind's type with download=True, else its device pointer."""
+        keep = []
+        if samples is None:
+            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
+        elif isinstance(samples, tuple) and isinstance(samples[0], np.ndarray):
+            host = np.ascontiguousarray(samples[0])
+            keep.append(host)
+            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(samples[1]), 0, tuple(int(n) for n in samples[2])
+        elif isinstance(samples, tuple):
+            ptr, code, on_device, shape = ctypes.c_void_p(int(samples[0])), dtype_code(samples[1]), 1, tuple(int(n) for n in samples[2])
+        else:
+            host = native_array(samples)
+            keep.append(host)
+            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
+        assert len(shape) == 3, "3-D sample array expected"
+        steps = None if sampling is None else np.ascontiguousarray(sampling, dtype=np.float64).reshape(3)
+        kind_code = DIST_KINDS[kind]
+        if download:
+            n = self.shape if samples is None else shape
+            if n is None:
+                raise CxError(CX_ERR_STATE, "distance_grid: no samples given and no grid bound")
+            host_out = np.empty(n, dtype=DIST_KIND_DTYPES.get(kind_code, np.uint8))
+        n_sites = ctypes.c_int64()
+        self._check(self.lib.cx_grid_distance3d(self.handle, ptr, code, on_device, shape[0], shape[1], shape[2], float(value),
+                                                None if steps is None else steps.ctypes.data, DIST_SIDES[side], kind_code, float(radius2),
+                                                ctypes.c_void_p(int(out)) if out else None, host_out.ctypes.data if download else None,
+                                                ctypes.addressof(n_sites)))
+        if download:
+            return int(n_sites.value), host_out
+        return int(n_sites.value), (int(out) if out else self.distance_result()[1])
+
+    def distance_result(self):
+        "(shape, device pointer, kind name, n_sites) of the result the last distance_grid left in the context (cx_grid_distance3d_result)"
+        p, m, kind, n_sites = ctypes.c_void_p(), np.zeros(3, dtype=np.int64), ctypes.c_int32(), ctypes.c_int64()
+        self._check(self.lib.cx_grid_distance3d_result(self.handle, ctypes.byref(p), m.ctypes.data, ctypes.byref(kind), ctypes.byref(n_sites)))
+        names = {v: k for k, v in DIST_KINDS.items()}
+        return tuple(int(x) for x in m), int(p.value or 0), names[int(kind.value)], int(n_sites.value)
+
+    def bind_distance(self):
+        """the float32 or mask result the last distance_grid left in the context becomes the bound grid (float32 / uint8, owned by the
+        context): cx_grid_distance3d_bind"""
+        shape = self.distance_result()[0]
+        self._check(self.lib.cx_grid_distance3d_bind(self.handle))
         self.shape = shape
         self._keep = None
 

@@ -182,6 +182,9 @@ struct cx_ctx {
     // preparing the volume (cx_filter.hip): the device copy of host samples, the result of the first kernel, and the context's own result
     // until cx_grid_filter3d_bind makes it the bound grid.  Nothing here describes the current extraction
     struct cx_filter_state* filt = nullptr;
+    // distance fields (cx_dist.hip): the device copy of host samples, the signed squared distances between the passes, and the context's
+    // own result until cx_grid_distance3d_bind makes it the bound grid: a slot of its own, beside the filter's
+    struct cx_dist_state* dist = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -367,6 +370,8 @@ int cx_cap_view_get(cx_ctx* ctx, const char* who, cx_cap_view* out);
 void cx_pick_free(cx_ctx* ctx);
 // cx_filter.hip
 void cx_filter_free(cx_ctx* ctx);
+// cx_dist.hip
+void cx_dist_free(cx_ctx* ctx);
 bool cx_level1_capped(cx_ctx* ctx);   // cx_post.hip: the Level-1 mesh came out of cx_postprocess3d_capped (or is a filtered copy of one)
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);

@@ -179,3 +179,116 @@ def lattice_of(mins, delta, strides=1, origins=None, weights=None):
         og = [int(o) for o in _per_axis(origins, ndim, 0, "origins")[3 - ndim:]]
     shift = np.asarray([(n - 1) / 2.0 - o if n else 0.0 for n, o in zip(taps, og)], dtype=np.float64)
     return mins + shift * delta, delta * st
+
+
+# ---- distance fields (cx_grid_distance3d, csrc/cx_dist.hip) ---------------------------------------------------------------------------
+# A sample f is LOW iff float64(f) < value (a NaN is never low): the march's own classification.  The squared distance is a minimum per
+# axis, last axis first, in float64 (include/contourist_hip.h, "distance fields"; tests/distance_ref.py restates it and the device result
+# equals it bit for bit).  With unit sampling it is the exact squared Euclidean distance.
+
+def _distance_samples(samples):
+    "-> (on_device, the samples in a type the kernels read, their shape)"
+    if grid_field._is_torch(samples):
+        import torch
+        t = samples
+        assert t.is_cuda, "a tensor of samples must be on the GPU (pass host samples as a numpy array)"
+        if t.dtype == torch.bool:
+            t = t.to(torch.uint8)
+        elif not _ffi.native_dtype(t.dtype):
+            t = t.float()
+        assert t.is_contiguous(), "a tensor of samples must be contiguous"
+        return True, t, tuple(int(n) for n in t.shape)
+    a = np.asarray(samples)
+    if a.dtype == np.bool_:
+        a = a.view(np.uint8)
+    elif not _ffi.native_dtype(a.dtype):
+        a = a.astype(np.float32)
+    a = _ffi.native_array(a)
+    return False, a, tuple(int(n) for n in a.shape)
+
+
+def _distance_steps(steps, device, samples):
+    """runs the transforms `steps` = [(value, side, kind, radius2), ...], each on the result of the one before (which stays on the
+    device), on `samples` -> the last result: a numpy array for numpy samples, a device tensor for a tensor"""
+    on_device, s, shape = samples
+    ndim = len(shape)
+    assert 1 <= ndim <= 3, "samples of 1 to 3 dimensions"
+    shape3 = (1,) * (3 - ndim) + shape
+    sampling = steps[0][4]
+    if sampling is not None:
+        sampling = [float(x) for x in _per_axis(sampling, ndim, 1.0, "sampling")]
+    if on_device:
+        import torch
+        torch_types = {"squared": torch.float64, "float32": torch.float32, "mask": torch.uint8}
+        context = _context(s.device.index if device is None else device)
+        torch.cuda.current_stream(s.device).synchronize()      # the samples are there; the context has a stream of its own
+        src, result = (s.data_ptr(), s.dtype, shape3), None
+        for value, side, kind, radius2, _ in steps:
+            out = torch.empty(shape3, dtype=torch_types[kind], device=s.device)
+            context.distance_grid(value, side, kind, sampling, radius2, samples=src, out=out.data_ptr())
+            src, result = (out.data_ptr(), out.dtype, shape3), out
+        return result.reshape(shape)
+    context = _context(device)
+    src = s.reshape(shape3)
+    for n, (value, side, kind, radius2, _) in enumerate(steps):
+        if n + 1 < len(steps):      # stays in the context; the next step reads it there
+            _, ptr = context.distance_grid(value, side, kind, sampling, radius2, samples=src)
+            src = (ptr, "uint8", shape3)
+        else:
+            _, result = context.distance_grid(value, side, kind, sampling, radius2, samples=src, download=True)
+    return result.reshape(shape)
+
+
+def distance(samples, value, side="below", sampling=None, squared=False, device=None):
+    """the Euclidean distance from every sample to the nearest site, float32 (squared=True: the squared distance, float64).
+    side "below": the sites are the samples with f >= value, the result is 0 there and positive where f < value
+    (scipy.ndimage.distance_transform_edt(f < value)); "above": the sites are the samples with f < value (edt(f >= value)); "signed":
+    above minus below, which has the sign of f - value.  Without a site the result is +inf.
+    sampling: None (1 per axis), one step or one per axis of the samples; `sampling=delta` gives world units.  The result lives on
+    the samples' own lattice: the same (mins, delta), `lattice_of(mins, delta)` with no weights.
+    Samples: a numpy array (a numpy array comes back) or a contiguous GPU tensor (a tensor comes back) of 1 to 3 dimensions."""
+    return _distance_steps([(value, side, "squared" if squared else "float32", 0.0, sampling)], device, _distance_samples(samples))
+
+
+def signed_distance(samples, value, sampling=None, device=None):
+    """distance(..., side="signed"): negative where f < value, positive where f >= value, never 0.  Marching it at 0 gives the surface
+    of f at `value` without the staircase of a mask, wound the same way; marching it at d gives the offset surface at distance d.
+    `sampling=delta` gives world units; the result's lattice is the samples' (`lattice_of(mins, delta)` with no weights)."""
+    return distance(samples, value, "signed", sampling, False, device)
+
+
+def _radius2(radius):
+    radius = float(radius)
+    assert radius >= 0.0 and np.isfinite(radius), "radius is a finite number >= 0"
+    return radius * radius
+
+
+def _inverted(mask):
+    return mask.bitwise_xor_(1) if grid_field._is_torch(mask) else mask ^ np.uint8(1)
+
+
+def dilate(samples, value, radius, sampling=None, device=None):
+    """the set {f >= value} grown by a ball: uint8, 1 where a sample of the set lies within `radius` (squared distance <= radius^2).
+    `sampling=delta` gives the radius world units; the mask's lattice is the samples' (`lattice_of(mins, delta)` with no weights)."""
+    return _distance_steps([(value, "below", "mask", _radius2(radius), sampling)], device, _distance_samples(samples))
+
+
+def erode(samples, value, radius, sampling=None, device=None):
+    """the set {f >= value} shrunk by a ball: uint8, 1 where no sample outside the set lies within `radius`.  The array's rim does not
+    erode: there is nothing outside the array.  Sampling and lattice as in `dilate`."""
+    return _inverted(_distance_steps([(value, "above", "mask", _radius2(radius), sampling)], device, _distance_samples(samples)))
+
+
+def opened(samples, value, radius, sampling=None, device=None):
+    """erode, then dilate: removes what a ball of `radius` does not fit into (specks, thin bridges).  The second transform runs on the
+    first one's mask where it lies on the device, thresholded at 0.5.  Sampling and lattice as in `dilate`."""
+    r2 = _radius2(radius)
+    # the first mask is 1 where the set is eroded away: the eroded set is its zeros, the sites of "above" at 0.5
+    return _distance_steps([(value, "above", "mask", r2, sampling), (0.5, "above", "mask", r2, sampling)], device, _distance_samples(samples))
+
+
+def closed(samples, value, radius, sampling=None, device=None):
+    """dilate, then erode: fills what a ball of `radius` does not fit into (pinholes, thin gaps).  The second transform runs on the
+    first one's mask where it lies on the device, thresholded at 0.5.  Sampling and lattice as in `dilate`."""
+    r2 = _radius2(radius)
+    return _inverted(_distance_steps([(value, "below", "mask", r2, sampling), (0.5, "above", "mask", r2, sampling)], device, _distance_samples(samples)))

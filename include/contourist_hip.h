@@ -718,6 +718,62 @@ int cx_grid_filter3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_dev
 int cx_grid_filter3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3]);
 int cx_grid_filter3d_bind(cx_ctx* ctx);
 
+/* ---- distance fields: the exact Euclidean distance transform of a thresholded volume, on the device ---------------------------------
+ * What a caller with a segmented volume ran scipy.ndimage.distance_transform_edt for: a smooth field from a mask, offset surfaces,
+ * dilation and erosion by a ball, thickness maps.  The reference has no call for it.
+ *
+ * cx_grid_distance3d
+ *   samples  NULL: the bound 3-D grid in its own CX_DTYPE_* (dtype, on_device and the shape are ignored; CX_ERR_STATE without a grid).
+ *            Else n0 n1 n2 samples of type `dtype` (every axis >= 1, at most 2^29 samples), on the device (any pointer aligned to its
+ *            own type) or on the host (copied into scratch of the context).  The pointer cx_grid_distance3d_result handed out is a
+ *            legal input (the second step of an opening or closing): that result is consumed, the new one takes its place.
+ *   value    a sample f is LOW iff (double)f < value; a NaN is never low.  This is the march's own classification.
+ *   sampling three doubles s0, s1, s2, each finite and > 0; NULL: 1, 1, 1.  w_a = s_a * s_a, rounded once, must be a normal double.
+ *   side     CX_DIST_BELOW: the sites are the samples that are not low; the result is 0 there and the distance to the nearest site at
+ *            the low samples (scipy's edt(f < value)).  CX_DIST_ABOVE: the sites are the low samples (edt(f >= value)).
+ *            CX_DIST_SIGNED: above minus below; it has the sign of f - value, so marching it at 0 winds the surface as marching f at
+ *            `value` does.
+ *   The squared distance is a minimum per axis, last axis first, all in double, (a - b)^2 the exact integer converted to double (exact
+ *   below 2^53), fl one IEEE rounding:
+ *       g2[i,j,k] = min over the sites (i,j,k') of the row of fl(w2 (k-k')^2), +inf for a row without a site
+ *       g1[i,j,k] = min over j' of fl(g2[i,j',k] + fl(w1 (j-j')^2))
+ *       g0[i,j,k] = min over i' of fl(g1[i',j,k] + fl(w0 (i-i')^2))
+ *   With unit sampling every value is an exact integer and g0 is the squared Euclidean distance to the nearest site.  With another
+ *   sampling it is one well-defined double per sample: a minimum does not depend on the order of its candidates, and the kernels skip
+ *   a candidate only where fl(w d^2) alone is not below the best so far.  A volume without a site gives +inf everywhere.
+ *   out_kind CX_DIST_OUT_SQUARED_F64: g0 as doubles; with CX_DIST_SIGNED g0 of ABOVE minus g0 of BELOW (one of them is 0 everywhere).
+ *            CX_DIST_OUT_F32: (float)sqrt(g0), the double square root correctly rounded, then rounded to fp32; with CX_DIST_SIGNED
+ *            (float)(sqrt(gA) - sqrt(gB)).
+ *            CX_DIST_OUT_MASK_U8: g0 <= radius2 ? 1 : 0 as uint8 (radius2 finite and >= 0; refused with CX_DIST_SIGNED).  The mask of
+ *            BELOW is the dilation of {f >= value} by the ball of squared radius radius2, 1 minus the mask of ABOVE its erosion.
+ *   out_device  not NULL: n0 n1 n2 values of the kind are written there (device memory of the caller, aligned to the kind's type;
+ *            CX_ERR_INVALID if it overlaps the input), and the context keeps no result.  NULL: the result goes into a buffer the
+ *            context owns (counted by cx_device_bytes, reused by the next call) and stays pending until the next cx_grid_distance3d
+ *            or cx_grid_distance3d_bind.  The slot is the distance transform's own: cx_grid_filter3d and this call do not disturb
+ *            each other's pending result.
+ *   out_host    not NULL: also receives a copy.
+ *   n_sites     (may be NULL) the number of sites, an exact count: samples that are not low (BELOW), low samples (ABOVE), the smaller
+ *            of the two (SIGNED).  0 iff the distances are infinite.  The call returns after the stream has run it.
+ *   CX_ERR_INVALID: a NaN or infinite value, a bad sampling, side, kind or radius2, an unknown sample type, a shape outside its range.
+ * cx_grid_distance3d_result: the pending result: device pointer, shape, kind and n_sites; CX_ERR_STATE when none is pending.
+ * cx_grid_distance3d_bind: the pending CX_DIST_OUT_F32 or CX_DIST_OUT_MASK_U8 result becomes the bound grid (CX_DTYPE_F32 / CX_DTYPE_U8),
+ *   owned by the context, with every reset of an upload, as cx_grid_filter3d_bind does it.  Refused with CX_ERR_INVALID, the result
+ *   left pending: a CX_DIST_OUT_SQUARED_F64 result, a result that holds an infinity (n_sites == 0), an axis shorter than 2.
+ *   CX_ERR_STATE when nothing is pending.
+ * A call without bind leaves the bound grid, the current extraction, the selected level, the Level-1 state and the cap as they are.
+ * No atomics on floating-point values: every call gives the same bits.  tests/distance_ref.py restates all of it in numpy. */
+#define CX_DIST_BELOW  0
+#define CX_DIST_ABOVE  1
+#define CX_DIST_SIGNED 2
+#define CX_DIST_OUT_SQUARED_F64 0
+#define CX_DIST_OUT_F32         1
+#define CX_DIST_OUT_MASK_U8     2
+int cx_grid_distance3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                       double value, const double sampling[3], int32_t side, int32_t out_kind, double radius2,
+                       void* out_device, void* out_host, int64_t* n_sites);
+int cx_grid_distance3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_kind, int64_t* n_sites);
+int cx_grid_distance3d_bind(cx_ctx* ctx);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
