@@ -462,7 +462,7 @@ static int cxp_morph_sort_by_start(cx_ctx* ctx, cx_post_state* S, uint32_t nseg,
 extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
     if (!ctx) return CX_ERR_INVALID;
     cx_state4* G = ctx->s4;
-    if (!G || !G->post_valid || !ctx->post) { ctx->err = "cx_morph_triangles: run cx_postprocess4d first"; return CX_ERR_STATE; }
+    if (!cxp_tets4d(ctx)) { ctx->err = "cx_morph_triangles: run cx_postprocess4d first"; return CX_ERR_STATE; }
     CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     hipStream_t st = ctx->stream;
@@ -471,7 +471,7 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
     const uint32_t* prio = S->prio.as<const uint32_t>();
     const int32_t* tets = S->tri_out.as<const int32_t>();
     uint32_t* misc = S->misc.as<uint32_t>();
-    u64* mm = (u64*)(misc + 16);
+    u64* mm = (u64*)(misc + CXP_M_MINMAX_T);
     int rc;
     int64_t counts[8] = {nv, 0, 0, 0, 0, 0, 0, 0};
     u64 h_mm[2] = {0, 0};      // min / max t of all points (MorphTriangles.min_value / max_value), orderable encodings
@@ -494,10 +494,10 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
         if (!G->post_assembled && cx_debug_knob("CX_TETS_ORIENT", 0))
             hipLaunchKernelGGL(cxp_k_tets_orient, dim3(cx_blocks(nt)), dim3(256), 0, st, S->tri_out.as<int32_t>(), nt, prio, G4);
         hipLaunchKernelGGL(cxp_k_morph_count, dim3(cx_blocks(nt)), dim3(256), 0, st, tets, nt, pts, prio, mm, cnt);
-        if ((rc = cxp_scan(ctx, S, cnt, off, nt, misc + 1))) return rc;
+        if ((rc = cxp_scan(ctx, S, cnt, off, nt, misc + CXP_M_TOTAL0))) return rc;
         uint32_t ntri = 0;
         u64* h = h_mm;
-        CX_HIP(ctx, hipMemcpyAsync(&ntri, misc + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipMemcpyAsync(&ntri, misc + CXP_M_TOTAL0, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         CX_HIP(ctx, hipMemcpyAsync(h, mm, sizeof(h_mm), hipMemcpyDeviceToHost, st));
         CX_HIP(ctx, hipStreamSynchronize(st));
         S->me_off.clear();
@@ -521,9 +521,9 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             const u64 smult = std::max<u64>(1, ssz / std::max<u64>(1, (u64)nv));
             hipLaunchKernelGGL(cxp_k_seg_insert, dim3(cx_blocks(np, CXP_SEG_KEYS)), dim3(256), 0, st, pairs, np, skeys, ssz - 1, smult);
             hipLaunchKernelGGL(cxp_k_occ_count, dim3(nob), dim3(256), 0, st, (const u64*)skeys, (size_t)ssz, boff);
-            cxp_scan_sums(st, boff, nob, misc + 2);
+            cxp_scan_sums(st, boff, nob, misc + CXP_M_TOTAL1);
             uint32_t nseg = 0;
-            CX_HIP(ctx, hipMemcpyAsync(&nseg, misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            CX_HIP(ctx, hipMemcpyAsync(&nseg, misc + CXP_M_TOTAL1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             CX_HIP(ctx, hipStreamSynchronize(st));
             if ((rc = S->msegs.grow(ctx, (size_t)(nseg + 1) * 2 * sizeof(int32_t)))) return rc;
             if ((rc = S->mmid.grow(ctx, (size_t)(nseg + 1) * 3 * sizeof(double)))) return rc;
@@ -534,7 +534,7 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             double* stime = S->mtime.as<double>();
             double* ttime = stime + (size_t)(nseg + 1) * 2;
             int32_t* tris = S->mtris.as<int32_t>();
-            hipLaunchKernelGGL(cxp_k_seg_write4, dim3(nob), dim3(256), 0, st, (const u64*)skeys, (size_t)ssz, (const uint32_t*)boff, (const uint32_t*)(misc + 2), nob,
+            hipLaunchKernelGGL(cxp_k_seg_write4, dim3(nob), dim3(256), 0, st, (const u64*)skeys, (size_t)ssz, (const uint32_t*)boff, (const uint32_t*)(misc + CXP_M_TOTAL1), nob,
                                pts, sid, segs, mid, stime);
             hipLaunchKernelGGL(cxp_k_tri_segments, dim3(cx_blocks(ntri)), dim3(256), 0, st, pairs, ntri, skeys, sid, ssz - 1, smult, stime, mm, tris, ttime);
             CX_HIP(ctx, hipStreamSynchronize(st));   // the segment table is reused below
@@ -545,13 +545,13 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             if ((rc = S->tvals.grow(ctx, esz * sizeof(u64)))) return rc;
             if ((rc = S->parent.grow(ctx, (size_t)ntri * sizeof(u64)))) return rc;
             if ((rc = S->mnext.grow(ctx, (size_t)ntri * 3 * sizeof(uint32_t)))) return rc;
-            if ((rc = S->comp.grow(ctx, (size_t)ntri * (3 * sizeof(u64) + sizeof(uint32_t))))) return rc;
+            if ((rc = S->comp.grow(ctx, cxp_comp_bytes(ntri)))) return rc;
             u64* ekeys = S->tkeys.as<u64>();
             u64* eheads = S->tvals.as<u64>();
             u64* parent = S->parent.as<u64>();
-            S->orient_live = false; S->gen++;   // (the 3-D orientation's tables lived here: what cx_comp.hip cached of them is stale)
+            cxp_tables_taken(S);    // (the 3-D orientation's tables lived in S->parent and S->comp)
             uint32_t* next = S->mnext.as<uint32_t>();
-            u64* cmaxx = S->comp.as<u64>();   // the component tables (cxp_orient_pick)
+            u64* comp = S->comp.as<u64>();    // the component tables (cxp_comp_view: laid out by cxp_orient_pick)
             cxp_fill64(st, ekeys, (size_t)esz, CXD_EMPTY);
             cxp_fill64(st, eheads, (size_t)esz, CXD_EMPTY);
             cxp_iota64(st, parent, ntri);
@@ -560,8 +560,8 @@ extern "C" int cx_morph_triangles(cx_ctx* ctx, int64_t* out_counts) {
             // segment midpoints, no keys: the largest index breaks the tie.  (The list of possible start triangles sits where the edge lists'
             // `next` words were: free by now)
             uint32_t ncomp = 0;
-            if ((rc = cxp_orient_pick(ctx, tris, ntri, mid, parent, cmaxx, nullptr, nullptr, next, misc))) return rc;
-            if ((rc = cxp_orient_decide(ctx, tris, ntri, mid, parent, cmaxx, next, misc, true, &ncomp))) return rc;
+            if ((rc = cxp_orient_pick(ctx, tris, ntri, mid, parent, comp, nullptr, nullptr, next, misc))) return rc;
+            if ((rc = cxp_orient_decide(ctx, tris, ntri, mid, parent, comp, next, misc, true, &ncomp))) return rc;
             CX_HIP(ctx, hipStreamSynchronize(st));
             CX_HIP(ctx, hipGetLastError());
             S->ms_out = nseg; S->mt_out = ntri;
@@ -734,7 +734,7 @@ static inline double cxp_host_from_orderable(u64 o) {
     return d;
 }
 // ranks of n elements by the bin of range[2 q]; bin starts (CXP_SB_BINS + 1) and the longest range[2 q + 1] - range[2 q] to the host.
-// Scratch: S->mnext (bins), S->flags (count matrix), S->scan (its scan), S->misc + 32.. (starts), S->misc + 20 (longest life).
+// Scratch: S->mnext (bins), S->flags (count matrix), S->scan (its scan), S->misc words CXP_M_SB_STARTS.. (starts), CXP_M_MAXDUR (longest life).
 static int cxp_sb_ranks(cx_ctx* ctx, cx_post_state* S, const double* range, uint32_t n, double lo, double inv_width, uint32_t* rank,
                         uint32_t* starts_host, double* maxdur_host) {
     int rc;
@@ -749,23 +749,23 @@ static int cxp_sb_ranks(cx_ctx* ctx, cx_post_state* S, const double* range, uint
     uint32_t* counts = S->flags.as<uint32_t>();
     uint32_t* offs = S->scan.as<uint32_t>();
     uint32_t* misc = S->misc.as<uint32_t>();
-    u64* maxdur = (u64*)(misc + 20);
+    u64* maxdur = (u64*)(misc + CXP_M_MAXDUR);
     CX_HIP(ctx, hipMemsetAsync(counts, 0, cells * sizeof(uint32_t), st));
     CX_HIP(ctx, hipMemsetAsync(maxdur, 0, sizeof(u64), st));
     const uint32_t nblocks = cx_blocks(nunits, 4);
     hipLaunchKernelGGL(cxp_k_sb_hist, dim3(nblocks), dim3(256), 0, st, range, n, lo, inv_width, bins, counts, nunits, maxdur);
-    if ((rc = cxp_scan(ctx, S, counts, offs, (uint32_t)cells, misc + 22))) return rc;
+    if ((rc = cxp_scan(ctx, S, counts, offs, (uint32_t)cells, misc + CXP_M_SB_TOTAL))) return rc;
     hipLaunchKernelGGL(cxp_k_sb_rank, dim3(nblocks), dim3(256), 0, st, (const uint8_t*)bins, n, (const uint32_t*)offs, nunits, rank);
-    hipLaunchKernelGGL(cxp_k_sb_starts, dim3(1), dim3(512), 0, st, (const uint32_t*)offs, nunits, n, misc + 32);
+    hipLaunchKernelGGL(cxp_k_sb_starts, dim3(1), dim3(512), 0, st, (const uint32_t*)offs, nunits, n, misc + CXP_M_SB_STARTS);
     u64 md = 0;
-    CX_HIP(ctx, hipMemcpyAsync(starts_host, misc + 32, (CXP_SB_BINS + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipMemcpyAsync(starts_host, misc + CXP_M_SB_STARTS, (CXP_SB_BINS + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     CX_HIP(ctx, hipMemcpyAsync(&md, maxdur, sizeof(md), hipMemcpyDeviceToHost, st));
     CX_HIP(ctx, hipStreamSynchronize(st));
     CX_HIP(ctx, hipGetLastError());
     *maxdur_host = md ? cxp_host_from_orderable(md) : 0.0;
     return CX_OK;
 }
-// mm_host = orderable min / max of the time of all points (S->misc + 16, read by the caller)
+// mm_host = orderable min / max of the time of all points (misc words CXP_M_MINMAX_T, read by the caller)
 static int cxp_morph_sort_by_start(cx_ctx* ctx, cx_post_state* S, uint32_t nseg, uint32_t ntri, const u64* mm_host) {
     int rc;
     hipStream_t st = ctx->stream;
@@ -778,7 +778,7 @@ static int cxp_morph_sort_by_start(cx_ctx* ctx, cx_post_state* S, uint32_t nseg,
     if ((rc = S->mtime2.grow(ctx, ((size_t)(nseg + 1) * 2 + (size_t)(ntri + 1) * 2) * sizeof(double)))) return rc;
     if ((rc = S->parent.grow(ctx, ((size_t)nseg + ntri + 64) * sizeof(uint32_t)))) return rc;
     uint32_t* rank_s = S->parent.as<uint32_t>();
-    S->orient_live = false; S->gen++;   // (the 3-D orientation's tables lived here: what cx_comp.hip cached of them is stale)
+    cxp_tables_taken(S);    // (the 3-D orientation's tables lived in S->parent)
     uint32_t* rank_t = rank_s + nseg + 16;
     const int32_t* segs = S->msegs.as<const int32_t>();
     const int32_t* tris = S->mtris.as<const int32_t>();

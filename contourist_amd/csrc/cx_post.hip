@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "cx_post.h"
+#include "cx_state4.h"
 
 void cx_post_free(cx_ctx* ctx) {
     if (!ctx->post) return;
@@ -1048,58 +1049,144 @@ int cxp_orient_pick(cx_ctx* ctx, const int32_t* tri, uint32_t nt, const double* 
                     const uint8_t* cls, uint32_t* clist, uint32_t* misc) {
     int rc;
     hipStream_t st = ctx->stream;
-    u64* cmaxx = comp;
-    u64* cbest = cmaxx + nt;
-    u64* cmaxv = cbest + nt;
-    uint32_t* cstart = (uint32_t*)(cmaxv + nt);
-    if ((rc = cxp_flatten(ctx, parent, nt, misc))) return rc;
-    CX_HIP(ctx, hipMemsetAsync(cmaxx, 0, (size_t)nt * (3 * sizeof(u64) + sizeof(uint32_t)), st));
-    CX_HIP(ctx, hipMemsetAsync(misc + 3, 0, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(cxp_k_comp_maxx, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, nt, pts, parent, cmaxx, cls);
+    const cxp_comp_tables C = cxp_comp_view(comp, nt);
+    if ((rc = cxp_flatten(ctx, parent, nt, misc + CXP_M_CHANGED))) return rc;
+    CX_HIP(ctx, hipMemsetAsync(comp, 0, cxp_comp_bytes(nt), st));
+    CX_HIP(ctx, hipMemsetAsync(misc + CXP_M_NCOMP, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(cxp_k_comp_maxx, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, nt, pts, parent, C.cmaxx, cls);
     // the four kernels that pick a component's start triangle visit the list of triangles AT the component's largest x (cxp_k_comp_list)
-    const uint32_t* cn = misc + 11;
+    const uint32_t* cn = misc + CXP_M_CLIST;
     const dim3 lgrid(std::min(cx_blocks(nt), 1024u));
-    CX_HIP(ctx, hipMemsetAsync(misc + 11, 0, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(cxp_k_comp_list, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, nt, pts, parent, cmaxx, cls, clist, misc + 11);
-    hipLaunchKernelGGL(cxp_k_comp_maxv, lgrid, dim3(256), 0, st, tri, nt, pts, parent, cmaxx, cmaxv, keys, cls, (const uint32_t*)clist, cn);
-    hipLaunchKernelGGL(cxp_k_comp_start, lgrid, dim3(256), 0, st, tri, nt, pts, parent, cmaxv, cbest, cls, (const uint32_t*)clist, cn);
-    hipLaunchKernelGGL(cxp_k_comp_pick, lgrid, dim3(256), 0, st, tri, nt, pts, parent, cmaxv, cbest, cstart, cls, (const uint32_t*)clist, cn);
+    CX_HIP(ctx, hipMemsetAsync(misc + CXP_M_CLIST, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(cxp_k_comp_list, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, nt, pts, parent, C.cmaxx, cls, clist, misc + CXP_M_CLIST);
+    hipLaunchKernelGGL(cxp_k_comp_maxv, lgrid, dim3(256), 0, st, tri, nt, pts, parent, C.cmaxx, C.cmaxv, keys, cls, (const uint32_t*)clist, cn);
+    hipLaunchKernelGGL(cxp_k_comp_start, lgrid, dim3(256), 0, st, tri, nt, pts, parent, C.cmaxv, C.cflip, cls, (const uint32_t*)clist, cn);
+    hipLaunchKernelGGL(cxp_k_comp_pick, lgrid, dim3(256), 0, st, tri, nt, pts, parent, C.cmaxv, C.cflip, C.cstart, cls, (const uint32_t*)clist, cn);
     return CX_OK;
 }
 int cxp_orient_decide(cx_ctx* ctx, int32_t* tri, uint32_t nt, const double* pts, const u64* parent, u64* comp, const uint32_t* clist,
                       uint32_t* misc, bool wind, uint32_t* ncomp) {
     hipStream_t st = ctx->stream;
-    u64* cbest = comp + nt;
-    const uint32_t* cstart = (const uint32_t*)(comp + 3 * (size_t)nt);
-    const uint32_t* cn = misc + 11;
+    const cxp_comp_tables C = cxp_comp_view(comp, nt);
+    const uint32_t* cn = misc + CXP_M_CLIST;
     const dim3 lgrid(std::min(cx_blocks(nt), 1024u));
-    hipLaunchKernelGGL(cxp_k_comp_decide, lgrid, dim3(256), 0, st, tri, nt, pts, parent, cstart, cbest, clist, cn);
+    hipLaunchKernelGGL(cxp_k_comp_decide, lgrid, dim3(256), 0, st, tri, nt, pts, parent, (const uint32_t*)C.cstart, C.cflip, clist, cn);
     if (wind) {
-        hipLaunchKernelGGL(cxp_k_orient, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, nt, parent, cbest, misc + 3);
-        CX_HIP(ctx, hipMemcpyAsync(ncomp, misc + 3, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(cxp_k_orient, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, nt, parent, C.cflip, misc + CXP_M_NCOMP);
+        CX_HIP(ctx, hipMemcpyAsync(ncomp, misc + CXP_M_NCOMP, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     }
     return CX_OK;
 }
 
-// Shared tail: clean (optional) + compaction + orientation (optional) on S->pts (nv x 3 doubles),
-// S->tri (nt x 3), S->alive.  prio = vertex priorities.  Results in S->pts_out / S->tri_out.
-static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, bool do_clean, bool do_orient,
-                            uint32_t* tprio3, int64_t* out_counts, bool coherent, uint8_t* involved = nullptr, const cxp_shard* shard = nullptr,
+// ---- the record of what the buffers hold (cx_post.h) ----------------------------------------------------------------------------------
+void cxp_begin(cx_ctx* ctx, cx_post_state* S) {
+    const uint64_t gen = S->rec.gen + 1;
+    S->rec = cxp_record();
+    S->rec.gen = gen;
+    ctx->post_valid = false;
+    if (ctx->s4) ctx->s4->post_valid = false;
+}
+int cxp_publish(cx_ctx* ctx, cx_post_state* S, cxp_record::holds_t holds, cxp_record::origin_t origin, const int64_t* counts, int64_t* out_counts) {
+    S->rec.holds = holds;
+    S->rec.origin = origin;
+    if (holds == cxp_record::MESH3D) ctx->post_valid = true;
+    if (holds == cxp_record::TETS4D) ctx->s4->post_valid = true;
+    if (out_counts) memcpy(out_counts, counts, 8 * sizeof(int64_t));
+    return CX_OK;
+}
+bool cxp_mesh3d(const cx_ctx* ctx) { return ctx->post && ctx->post_valid && ctx->post->rec.holds == cxp_record::MESH3D; }
+bool cxp_tets4d(const cx_ctx* ctx) { return ctx->post && ctx->s4 && ctx->s4->post_valid && ctx->post->rec.holds == cxp_record::TETS4D; }
+
+// the five buffers of the raw input mesh for nv vertices and nt triangles (S->raw).  weld: the whole post-pass follows (cxp_run3d): also
+// the weld's representatives (rep) and the tiny collapse's union-find (parent), each at the place in the order it was always grown at
+static int cxp_reserve_raw(cx_ctx* ctx, cx_post_state* S, size_t nv, size_t nt, bool weld = false) {
+    int rc;
+    if ((rc = S->pts.grow(ctx, (nv + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = S->prio.grow(ctx, (nv + 1) * sizeof(uint32_t)))) return rc;
+    if (weld && (rc = S->rep.grow(ctx, (nv + 1) * (sizeof(uint32_t) + 1)))) return rc;
+    if ((rc = S->tri.grow(ctx, (nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;   // triangles + priority triples
+    if ((rc = S->alive.grow(ctx, nt + 16))) return rc;
+    if (weld && (rc = S->parent.grow(ctx, (nv + 1) * sizeof(u64)))) return rc;
+    if ((rc = S->parent2.grow(ctx, (nv + 1) * sizeof(u64)))) return rc;
+    S->raw = {S->pts.as<double>(), S->prio.as<uint32_t>(), S->tri.as<int32_t>(), S->tri.as<uint32_t>() + (nt + 1) * 3, S->alive.as<uint8_t>(),
+              S->parent2.as<u64>()};
+    return CX_OK;
+}
+
+// triangles that became the same vertex set: the one with the smallest sorted priority triple survives (tsz slots of S->tkeys)
+static void cxp_dedupe(cx_ctx* ctx, cx_post_state* S, const int32_t* tri, const uint32_t* tprio3, uint8_t* alive, uint32_t nt, u64 tsz, const uint8_t* involved) {
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXD_EMPTY);
+    hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, involved);
+    hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, involved);
+}
+
+// Ordered compaction of the used vertices and living triangles of (pts, keys, tri, alive) into the buffers P / T / K, grown to the
+// totals (byte flags in S->flags, per-block counts, the scan redone inside the two consumers; vnew in S->scan).  The totals come back
+// in ONE copy of nwords words from CXP_M_TOTAL0 on: h[0] vertices, h[1] triangles, and h[2] = CXP_M_NCOMP for the caller that asks.
+static int cxp_compact(cx_ctx* ctx, cx_post_state* S, const double* pts, const uint32_t* keys, const int32_t* tri, const uint8_t* alive, uint32_t nv,
+                       uint32_t nt, cx_buf<uint8_t>& P, cx_buf<uint8_t>& T, cx_buf<uint8_t>& K, uint8_t* ever, uint32_t* told, int nwords,
+                       uint32_t* h) {
+    int rc;
+    hipStream_t st = ctx->stream;
+    uint32_t* misc = S->misc.as<uint32_t>();
+    const uint32_t nbv = cx_blocks(nv, CXP_SCAN_BLOCK), nbt = cx_blocks(nt, CXP_SCAN_BLOCK);
+    if ((rc = S->blocksums.grow(ctx, (size_t)(nbv + nbt + 16) * sizeof(uint32_t)))) return rc;
+    uint8_t* used = S->flags.as<uint8_t>();
+    uint32_t* vnew = S->scan.as<uint32_t>();
+    uint32_t* voff = S->blocksums.as<uint32_t>();
+    uint32_t* toff = voff + nbv + 8;
+    for (int k = 0; k < nwords; k++) h[k] = 0;
+    if (nt) {
+        CX_HIP(ctx, hipMemsetAsync(used, 0, (size_t)nv, st));
+        hipLaunchKernelGGL(cxp_k_mark_used8, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, used);
+        hipLaunchKernelGGL(cxp_k_me_count, dim3(nbv), dim3(256), 0, st, (const uint8_t*)used, nv, voff);
+        hipLaunchKernelGGL(cxp_k_me_count, dim3(nbt), dim3(256), 0, st, alive, nt, toff);
+        hipLaunchKernelGGL(cxp_k_scan_sums2, dim3(2), dim3(1024), 0, st, voff, nbv, misc + CXP_M_TOTAL0, toff, nbt, misc + CXP_M_TOTAL1);
+        CX_HIP(ctx, hipMemcpyAsync(h, misc + CXP_M_TOTAL0, nwords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipStreamSynchronize(st));
+    }
+    if ((rc = P.grow(ctx, (size_t)(h[0] + 1) * 3 * sizeof(double)))) return rc;
+    if ((rc = T.grow(ctx, (size_t)(h[1] + 1) * 3 * sizeof(int32_t)))) return rc;
+    if ((rc = K.grow(ctx, (size_t)(h[0] + 1) * sizeof(uint32_t)))) return rc;
+    if (h[1]) {
+        hipLaunchKernelGGL(cxp_k_compact_pts_fused, dim3(nbv), dim3(256), 0, st, pts, (const uint8_t*)used, (const uint32_t*)voff, nv, vnew, P.as<double>(), keys,
+                           K.as<uint32_t>(), (const uint8_t*)ever, ever ? ever + nv : nullptr);
+        hipLaunchKernelGGL(cxp_k_compact_tri_fused, dim3(nbt), dim3(256), 0, st, tri, alive, (const uint32_t*)toff, (const uint32_t*)vnew, nt, T.as<int32_t>(), told);
+    }
+    return CX_OK;
+}
+
+// the boundary block of an open shard in S->bnd: hash1 u64[n1] | hash4 u64[n4] | candidates cxp_cand[n1 + n4] | label1 u32[n1] | label4 u32[n4]
+struct cxp_bnd {
+    u64 *hash1, *hash4;
+    cxp_cand* cand;
+    uint32_t *label1, *label4;
+};
+static size_t cxp_bnd_bytes(size_t n1, size_t n4) { return (n1 + n4 + 2) * (sizeof(u64) + sizeof(cxp_cand) + sizeof(uint32_t)) + 64; }
+static cxp_bnd cxp_bnd_view(cx_post_state* S, size_t n1, size_t n4) {
+    u64* hash1 = S->bnd.as<u64>();
+    cxp_cand* cand = (cxp_cand*)(hash1 + n1 + n4);
+    uint32_t* label1 = (uint32_t*)(cand + n1 + n4);
+    return {hash1, hash1 + n1, cand, label1, label1 + n1};
+}
+
+// Shared tail: clean (optional) + compaction + orientation (optional) on the raw mesh S->raw (nv x 3 doubles, nt x 3 indices, alive
+// bytes; prio = vertex priorities).  Results in S->pts_out / S->tri_out / S->keys_out, S->nv_out / S->nt_out.  The caller has called
+// cxp_begin and publishes what comes out.
+static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, bool do_clean, bool do_orient, int64_t* out_counts, bool coherent,
+                            uint8_t* involved = nullptr, const cxp_shard* shard = nullptr,
                             uint8_t* ever = nullptr) {   // ever != nullptr: the march's own mesh (cxp_k_edges_block); u8[nv] flags, room for nv more behind them
     int rc;
-    double* pts = S->pts.as<double>();
-    uint32_t* prio = S->prio.as<uint32_t>();
-    int32_t* tri = S->tri.as<int32_t>();
-    uint8_t* alive = S->alive.as<uint8_t>();
-    uint32_t* misc = S->misc.as<uint32_t>();   // [0] changed flag, [1..] counters
+    double* pts = S->raw.pts;
+    uint32_t* prio = S->raw.prio;
+    int32_t* tri = S->raw.tri;
+    uint32_t* tprio3 = S->raw.tprio3;
+    uint8_t* alive = S->raw.alive;
+    uint32_t* misc = S->misc.as<uint32_t>();
     hipStream_t st = ctx->stream;
-    S->keys_valid = false;
-    S->keys_edge = false; S->orient_live = false; S->vflip_valid = false;
-    S->shard_mesh = false; S->gen++; S->orient_nt = 0;
-    S->shard.open = false;
-    S->simplified = false; S->carried = false; S->smap_valid = false; S->clipped = false;
     if (do_clean && nt) {
-        u64* parent2 = S->parent2.as<u64>();
+        u64* parent2 = S->raw.parent2;
         hipLaunchKernelGGL(cxp_k_iota64, dim3(cx_blocks(nv)), dim3(256), 0, st, parent2, nv);
         hipLaunchKernelGGL(cxp_k_degenerate, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, pts, parent2, prio);
         if (involved) CX_HIP(ctx, hipMemsetAsync(involved, 0, nv, st));
@@ -1107,9 +1194,7 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
         // (with the filter only triangles next to a merge enter the table: 5/4 of the bound is plenty and half as much to clear)
         const u64 tsz = involved ? cxp_edge_table_size(nt) : cx_table_size(nt);
         if ((rc = S->tkeys.grow(ctx, tsz * sizeof(u64)))) return rc;
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXD_EMPTY);
-        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
-        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
+        cxp_dedupe(ctx, S, tri, tprio3, alive, nt, tsz, involved);
     }
     // ---- sharded: the second layer of the neighbours' cells has done its work (weld, tiny collapse and clean-up above saw it)
     uint8_t* cls = nullptr;
@@ -1119,44 +1204,19 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
         if ((rc = S->told.grow(ctx, ((size_t)nt + 16) * sizeof(uint32_t)))) return rc;
         cls = S->cls.as<uint8_t>();
         told = S->told.as<uint32_t>();
-        CX_HIP(ctx, hipMemsetAsync(misc + 6, 0, 2 * sizeof(uint32_t), st));
-        if (nt) hipLaunchKernelGGL(cxp_k_shard_classify, dim3(cx_blocks(nt)), dim3(256), 0, st, tprio3, alive, nt, *shard, cx_fdiv_make(shard->plane), cls, misc + 6);
+        CX_HIP(ctx, hipMemsetAsync(misc + CXP_M_SHARD_N, 0, 2 * sizeof(uint32_t), st));
+        if (nt) hipLaunchKernelGGL(cxp_k_shard_classify, dim3(cx_blocks(nt)), dim3(256), 0, st, tprio3, alive, nt, *shard, cx_fdiv_make(shard->plane), cls, misc + CXP_M_SHARD_N);
     }
-    // ---- compaction of used vertices and living triangles (byte flags, per-block counts, the scan redone inside the two consumers)
+    // ---- compaction of used vertices and living triangles
     if ((rc = S->flags.grow(ctx, (size_t)(nv + nt + 16) * sizeof(uint32_t)))) return rc;      // (also: the list of possible start triangles below)
     if ((rc = S->scan.grow(ctx, (size_t)(nv + 16) * sizeof(uint32_t)))) return rc;
-    const uint32_t nbv = cx_blocks(nv, CXP_SCAN_BLOCK), nbt = cx_blocks(nt, CXP_SCAN_BLOCK);
-    if ((rc = S->blocksums.grow(ctx, (size_t)(nbv + nbt + 16) * sizeof(uint32_t)))) return rc;
-    uint8_t* used = S->flags.as<uint8_t>();
-    uint32_t* vnew = S->scan.as<uint32_t>();
-    uint32_t* voff = S->blocksums.as<uint32_t>();
-    uint32_t* toff = voff + nbv + 8;
-    uint32_t nv2 = 0, nt2 = 0;
-    if (nt) {
-        CX_HIP(ctx, hipMemsetAsync(used, 0, (size_t)nv, st));
-        hipLaunchKernelGGL(cxp_k_mark_used8, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, used);
-        hipLaunchKernelGGL(cxp_k_me_count, dim3(nbv), dim3(256), 0, st, (const uint8_t*)used, nv, voff);
-        hipLaunchKernelGGL(cxp_k_me_count, dim3(nbt), dim3(256), 0, st, (const uint8_t*)alive, nt, toff);
-        hipLaunchKernelGGL(cxp_k_scan_sums2, dim3(2), dim3(1024), 0, st, voff, nbv, misc + 1, toff, nbt, misc + 2);
-        uint32_t h[2];
-        CX_HIP(ctx, hipMemcpyAsync(h, misc + 1, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CX_HIP(ctx, hipStreamSynchronize(st));
-        nv2 = h[0]; nt2 = h[1];
-    }
-    if ((rc = S->pts_out.grow(ctx, (size_t)(nv2 + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = S->tri_out.grow(ctx, (size_t)(nt2 + 1) * 3 * sizeof(int32_t)))) return rc;
-    if ((rc = S->keys_out.grow(ctx, (size_t)(nv2 + 1) * sizeof(uint32_t)))) return rc;
+    uint32_t h[2];
+    if ((rc = cxp_compact(ctx, S, pts, prio, tri, alive, nv, nt, S->pts_out, S->tri_out, S->keys_out, ever, told, 2, h))) return rc;
+    const uint32_t nv2 = h[0], nt2 = h[1];
     double* pts2 = S->pts_out.as<double>();
     int32_t* tri2 = S->tri_out.as<int32_t>();
     uint32_t* keys2 = S->keys_out.as<uint32_t>();
-    if (nt2) {
-        hipLaunchKernelGGL(cxp_k_compact_pts_fused, dim3(nbv), dim3(256), 0, st, (const double*)pts, (const uint8_t*)used, (const uint32_t*)voff, nv, vnew, pts2,
-                           (const uint32_t*)prio, keys2, (const uint8_t*)ever, ever ? ever + nv : nullptr);
-        hipLaunchKernelGGL(cxp_k_compact_tri_fused, dim3(nbt), dim3(256), 0, st, (const int32_t*)tri, (const uint8_t*)alive, (const uint32_t*)toff,
-                           (const uint32_t*)vnew, nt, tri2, told);
-    }
     S->nv_out = nv2; S->nt_out = nt2;
-    S->keys_valid = true;
     uint8_t* cls2 = nullptr;
     if (shard) {
         cls2 = cls + nt;
@@ -1180,12 +1240,9 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
             if (esz > esz_full) esz = esz_full;
         }
         if ((rc = S->parent.grow(ctx, (size_t)nt2 * sizeof(u64)))) return rc;
-        if ((rc = S->comp.grow(ctx, (size_t)nt2 * (3 * sizeof(u64) + sizeof(uint32_t))))) return rc;
+        if ((rc = S->comp.grow(ctx, cxp_comp_bytes(nt2)))) return rc;
         u64* parent = S->parent.as<u64>();
-        u64* cmaxx = S->comp.as<u64>();
-        u64* cbest = cmaxx + nt2;
-        u64* cmaxv = cbest + nt2;
-        uint32_t* cstart = (uint32_t*)(cmaxv + nt2);
+        const cxp_comp_tables C = cxp_comp_view(S->comp.as<u64>(), nt2);
         uint32_t* others = S->comp.as<uint32_t>();   // 12 of the 28 bytes per triangle that the component tables take below
         for (;;) {
             if ((rc = S->tkeys.grow(ctx, 2 * esz * sizeof(u64)))) return rc;
@@ -1196,12 +1253,12 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
             hipLaunchKernelGGL(cxp_k_iota64, dim3(cx_blocks(nt2)), dim3(256), 0, st, parent, nt2);
             const u64 emult = (blocks && esz != esz_full) ? 0 : std::max<u64>(1, esz / std::max<u64>(1, (u64)nv2));
             if (blocks) {
-                CX_HIP(ctx, hipMemsetAsync(misc + 12, 0, sizeof(uint32_t), st));
+                CX_HIP(ctx, hipMemsetAsync(misc + CXP_M_OVER, 0, sizeof(uint32_t), st));
                 hipLaunchKernelGGL(cxp_k_edges_block, dim3((nt2 + CXP_EB - 1u) / CXP_EB), dim3(256), 0, st, tri2, nt2, (const uint8_t*)(ever + nv), etab, esz - 1,
-                                   emult, parent, (uint8_t*)others, esz == esz_full ? 0xFFFFFFFFu : 256u, misc + 12);
+                                   emult, parent, (uint8_t*)others, esz == esz_full ? 0xFFFFFFFFu : 256u, misc + CXP_M_OVER);
                 if (esz != esz_full) {
                     uint32_t over = 0;
-                    CX_HIP(ctx, hipMemcpyAsync(&over, misc + 12, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+                    CX_HIP(ctx, hipMemcpyAsync(&over, misc + CXP_M_OVER, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
                     CX_HIP(ctx, hipStreamSynchronize(st));
                     if (over) { esz = esz_full; continue; }
                 }
@@ -1219,44 +1276,39 @@ static int cxp_clean_orient(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t
         }
         // (the scan / flag arrays of the compaction are free by now: the list of possible start triangles goes there)
         uint32_t* clist = S->flags.as<uint32_t>();
-        if ((rc = cxp_orient_pick(ctx, tri2, nt2, pts2, parent, cmaxx, keys2, cls2, clist, misc))) return rc;
+        if ((rc = cxp_orient_pick(ctx, tri2, nt2, pts2, parent, C.cmaxx, keys2, cls2, clist, misc))) return rc;
         if (shard) {
             // what the neighbours need: the triangles at the slab boundaries with their labels (they stay on the device), and the
             // start-triangle candidate of every component that reaches a neighbour.  Sizes follow the slab boundary, not the slab.
             uint32_t hb[2] = {0, 0};
-            CX_HIP(ctx, hipMemcpyAsync(hb, misc + 6, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            CX_HIP(ctx, hipMemcpyAsync(hb, misc + CXP_M_SHARD_N, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             CX_HIP(ctx, hipStreamSynchronize(st));
             const size_t n1 = hb[0], n4 = hb[1], nb = n1 + n4;
-            // layout of S->bnd: hash1 u64[n1] | hash4 u64[n4] | candidates cxp_cand[nb] | label1 u32[n1] | label4 u32[n4]
-            if ((rc = S->bnd.grow(ctx, (nb + 2) * (sizeof(u64) + sizeof(cxp_cand) + sizeof(uint32_t)) + 64))) return rc;
-            u64* hash1 = S->bnd.as<u64>();
-            u64* hash4 = hash1 + n1;
-            cxp_cand* cand = (cxp_cand*)(hash4 + n4);
-            uint32_t* label1 = (uint32_t*)(cand + nb);
-            uint32_t* label4 = label1 + n1;
+            if ((rc = S->bnd.grow(ctx, cxp_bnd_bytes(n1, n4)))) return rc;
+            const cxp_bnd B = cxp_bnd_view(S, n1, n4);
             uint8_t* open = cls + 2 * (size_t)nt;
             CX_HIP(ctx, hipMemsetAsync(open, 0, nt2, st));
-            CX_HIP(ctx, hipMemsetAsync(misc + 8, 0, 3 * sizeof(uint32_t), st));
+            CX_HIP(ctx, hipMemsetAsync(misc + CXP_M_BND_N, 0, 3 * sizeof(uint32_t), st));
             if (nb) {
                 const u64 key_offset = ((u64)ctx->origin[0] * (u64)shard->plane) << 3;
-                hipLaunchKernelGGL(cxp_k_shard_boundary, dim3(cx_blocks(nt2)), dim3(256), 0, st, cls2, told, tprio3, parent, nt2, key_offset, misc + 8,
-                                   (uint32_t)n1, (uint32_t)n4, hash1, label1, hash4, label4, open);
-                hipLaunchKernelGGL(cxp_k_shard_candidates, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, pts2, keys2, parent, open, nt2, cmaxx, cmaxv,
-                                   cstart, misc + 10, (uint32_t)nb, cand);
+                hipLaunchKernelGGL(cxp_k_shard_boundary, dim3(cx_blocks(nt2)), dim3(256), 0, st, cls2, told, tprio3, parent, nt2, key_offset, misc + CXP_M_BND_N,
+                                   (uint32_t)n1, (uint32_t)n4, B.hash1, B.label1, B.hash4, B.label4, open);
+                hipLaunchKernelGGL(cxp_k_shard_candidates, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, pts2, keys2, parent, open, nt2, C.cmaxx, C.cmaxv,
+                                   C.cstart, misc + CXP_M_BND_NCAND, (uint32_t)nb, B.cand);
             }
             uint32_t h2[3] = {0, 0, 0};
-            CX_HIP(ctx, hipMemcpyAsync(h2, misc + 8, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            CX_HIP(ctx, hipMemcpyAsync(h2, misc + CXP_M_BND_N, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             CX_HIP(ctx, hipStreamSynchronize(st));
             if (h2[0] != n1 || h2[1] != n4 || h2[2] > nb) { ctx->err = "sharded Level 1: boundary lists do not add up"; return CX_ERR_HIP; }
             S->shard.n1 = (uint32_t)n1; S->shard.n4 = (uint32_t)n4; S->shard.ncand = h2[2];
         }
-        if ((rc = cxp_orient_decide(ctx, tri2, nt2, pts2, parent, cmaxx, clist, misc, !shard, &ncomp))) return rc;
-        if (!shard) { S->orient_live = true; S->orient_nt = nt2; }
+        if ((rc = cxp_orient_decide(ctx, tri2, nt2, pts2, parent, C.cmaxx, clist, misc, !shard, &ncomp))) return rc;
+        if (!shard) { S->rec.tables_live = true; S->rec.tables_nt = nt2; }
         CX_HIP(ctx, hipStreamSynchronize(st));
     } else if (shard) {
         S->shard.n1 = 0; S->shard.n4 = 0; S->shard.ncand = 0;
     }
-    if (shard) { S->shard.open = true; S->shard.nv2 = nv2; S->shard.nt2 = nt2; S->shard.nt_in = nt; }
+    if (shard) { S->shard.nv2 = nv2; S->shard.nt2 = nt2; S->shard.nt_in = nt; }
     CX_HIP(ctx, hipGetLastError());
     if (out_counts) {
         out_counts[0] = nv2; out_counts[1] = nt2; out_counts[4] = ncomp;
@@ -1271,11 +1323,11 @@ static int cxp_shard_finish(cx_ctx* ctx, cx_post_state* S, const uint32_t* label
     hipStream_t st = ctx->stream;
     uint32_t* misc = S->misc.as<uint32_t>();
     const uint32_t nv2 = S->shard.nv2, nt2 = S->shard.nt2;
-    S->shard.open = false;
-    uint32_t ncomp = 0, nv3 = 0, nt3 = 0;
+    cxp_begin(ctx, S);      // (the open shard is over, however this ends)
+    uint32_t h[3] = {0, 0, 0};       // vertices, triangles, components
     if (nt2) {
         u64* parent = S->parent.as<u64>();
-        u64* cflip = S->comp.as<u64>() + nt2;
+        u64* cflip = cxp_comp_view(S->comp.as<u64>(), nt2).cflip;
         int32_t* tri2 = S->tri_out.as<int32_t>();
         const uint8_t* cls2 = S->cls.as<const uint8_t>() + S->shard.nt_in;
         if (n) {
@@ -1286,50 +1338,26 @@ static int cxp_shard_finish(cx_ctx* ctx, cx_post_state* S, const uint32_t* label
             CX_HIP(ctx, hipMemcpyAsync(df, flips, (size_t)n, hipMemcpyHostToDevice, st));
             hipLaunchKernelGGL(cxp_k_shard_set_flips, dim3(cx_blocks(n)), dim3(256), 0, st, dl, df, n, nt2, cflip);
         }
-        CX_HIP(ctx, hipMemsetAsync(misc + 3, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(cxp_k_orient, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, nt2, parent, cflip, misc + 3);
-        // own triangles and the vertices they use (the same ordered compaction as in cxp_clean_orient)
+        CX_HIP(ctx, hipMemsetAsync(misc + CXP_M_NCOMP, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(cxp_k_orient, dim3(cx_blocks(nt2)), dim3(256), 0, st, tri2, nt2, parent, cflip, misc + CXP_M_NCOMP);
+        // own triangles and the vertices they use.  The march's own buffers are free by now: they take the final mesh on its way back
+        // into the output buffers
         uint8_t* alive = S->alive.as<uint8_t>();
-        uint8_t* used = S->flags.as<uint8_t>();
-        uint32_t* vnew = S->scan.as<uint32_t>();
-        const uint32_t nbv = cx_blocks(nv2, CXP_SCAN_BLOCK), nbt = cx_blocks(nt2, CXP_SCAN_BLOCK);
-        if ((rc = S->blocksums.grow(ctx, (size_t)(nbv + nbt + 16) * sizeof(uint32_t)))) return rc;
-        uint32_t* voff = S->blocksums.as<uint32_t>();
-        uint32_t* toff = voff + nbv + 8;
         hipLaunchKernelGGL(cxp_k_shard_own_alive, dim3(cx_blocks(nt2)), dim3(256), 0, st, cls2, nt2, alive);
-        CX_HIP(ctx, hipMemsetAsync(used, 0, (size_t)nv2, st));
-        hipLaunchKernelGGL(cxp_k_mark_used8, dim3(cx_blocks(nt2)), dim3(256), 0, st, (const int32_t*)tri2, (const uint8_t*)alive, nt2, used);
-        hipLaunchKernelGGL(cxp_k_me_count, dim3(nbv), dim3(256), 0, st, (const uint8_t*)used, nv2, voff);
-        hipLaunchKernelGGL(cxp_k_me_count, dim3(nbt), dim3(256), 0, st, (const uint8_t*)alive, nt2, toff);
-        hipLaunchKernelGGL(cxp_k_scan_sums2, dim3(2), dim3(1024), 0, st, voff, nbv, misc + 1, toff, nbt, misc + 2);
-        uint32_t h[3];
-        CX_HIP(ctx, hipMemcpyAsync(h, misc + 1, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        CX_HIP(ctx, hipStreamSynchronize(st));
-        nv3 = h[0]; nt3 = h[1]; ncomp = h[2];
-        // the march's own buffers are free by now: they take the final mesh on its way back into the output buffers
-        if ((rc = S->pts.grow(ctx, (size_t)(nv3 + 1) * 3 * sizeof(double)))) return rc;
-        if ((rc = S->tri.grow(ctx, (size_t)(nt3 + 1) * 3 * sizeof(int32_t)))) return rc;
-        if ((rc = S->keys_tmp.grow(ctx, (size_t)(nv3 + 1) * sizeof(uint32_t)))) return rc;
-        if (nt3) {
-            hipLaunchKernelGGL(cxp_k_compact_pts_fused, dim3(nbv), dim3(256), 0, st, S->pts_out.as<const double>(), (const uint8_t*)used, (const uint32_t*)voff, nv2, vnew,
-                               S->pts.as<double>(), S->keys_out.as<const uint32_t>(), S->keys_tmp.as<uint32_t>(), (const uint8_t*)nullptr, (uint8_t*)nullptr);
-            hipLaunchKernelGGL(cxp_k_compact_tri_fused, dim3(nbt), dim3(256), 0, st, (const int32_t*)tri2, (const uint8_t*)alive, (const uint32_t*)toff,
-                               (const uint32_t*)vnew, nt2, S->tri.as<int32_t>(), (uint32_t*)nullptr);
-        }
+        if ((rc = cxp_compact(ctx, S, S->pts_out.as<const double>(), S->keys_out.as<const uint32_t>(), tri2, alive, nv2, nt2, S->pts, S->tri, S->keys_tmp,
+                              nullptr, nullptr, 3, h))) return rc;
         // back into the output buffers (every buffer keeps its size from call to call: nothing is reallocated for the next volume)
-        if (nt3) {
-            CX_HIP(ctx, hipMemcpyAsync(S->pts_out.get(), S->pts.get(), (size_t)nv3 * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
-            CX_HIP(ctx, hipMemcpyAsync(S->tri_out.get(), S->tri.get(), (size_t)nt3 * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-            CX_HIP(ctx, hipMemcpyAsync(S->keys_out.get(), S->keys_tmp.get(), (size_t)nv3 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        if (h[1]) {
+            CX_HIP(ctx, hipMemcpyAsync(S->pts_out.get(), S->pts.get(), (size_t)h[0] * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
+            CX_HIP(ctx, hipMemcpyAsync(S->tri_out.get(), S->tri.get(), (size_t)h[1] * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+            CX_HIP(ctx, hipMemcpyAsync(S->keys_out.get(), S->keys_tmp.get(), (size_t)h[0] * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         }
         CX_HIP(ctx, hipStreamSynchronize(st));
     }
-    S->nv_out = nv3; S->nt_out = nt3;
-    S->keys_valid = true;
-    S->shard_mesh = true; S->gen++;
+    S->nv_out = h[0]; S->nt_out = h[1];
     CX_HIP(ctx, hipGetLastError());
-    if (out_counts) { out_counts[0] = nv3; out_counts[1] = nt3; out_counts[4] = ncomp; }
-    return CX_OK;
+    const int64_t counts[8] = {h[0], h[1], 0, 0, h[2], 0, 0, 0};
+    return cxp_publish(ctx, S, cxp_record::MESH3D, cxp_record::SHARD, counts, out_counts);
 }
 
 int cxp_state(cx_ctx* ctx, cx_post_state** out) {
@@ -1339,7 +1367,7 @@ int cxp_state(cx_ctx* ctx, cx_post_state** out) {
     // every post-pass rewrites the points the morph triangles of an earlier cx_morph_triangles index: those are gone (their segments would
     // point into the new points: cx_morph_eval on them read out of bounds)
     ctx->post->ms_out = 0; ctx->post->mt_out = 0; ctx->post->msorted = false; ctx->post->me_off.clear();
-    return ctx->post->misc.grow(ctx, 512 * sizeof(uint32_t));      // (words 32..288: bin starts of the start-time sort)
+    return ctx->post->misc.grow(ctx, CXP_M_WORDS * sizeof(uint32_t));
 }
 
 // ---- smooth_interpolations(factor) (tetrahedral.py:329-351): every vertex that is part of a triangle moves by
@@ -1443,17 +1471,30 @@ extern "C" int cx_postprocess3d(cx_ctx* ctx, uint32_t flags, int64_t* out_counts
     return cx_postprocess3d_ex(ctx, flags, 0.0, out_counts);
 }
 
-// buffers of the 3-D post-pass for nv vertices and nt triangles
-static int cxp_reserve3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt) {
-    int rc;
-    if ((rc = S->pts.grow(ctx, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = S->prio.grow(ctx, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
-    if ((rc = S->rep.grow(ctx, (size_t)(nv + 1) * (sizeof(uint32_t) + 1)))) return rc;
-    if ((rc = S->tri.grow(ctx, (size_t)(nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;   // triangles + priority triples
-    if ((rc = S->alive.grow(ctx, (size_t)nt + 16))) return rc;
-    if ((rc = S->parent.grow(ctx, (size_t)(nv + 1) * sizeof(u64)))) return rc;
-    if ((rc = S->parent2.grow(ctx, (size_t)(nv + 1) * sizeof(u64)))) return rc;
+// The raw mesh from the current extraction: its vertices in float64 about the lattice origin org (priority = edge id), its triangles,
+// and alive bytes for nt_alive triangles (a caller that appends triangles of its own asks for more than the extraction has).  The
+// seeded selection's mask, where there is one, becomes the alive bytes and *vkeep the vertices' half of it.
+static int cxp_raw_from_extraction(cx_ctx* ctx, cx_post_state* S, const cxp_origin3& org, uint32_t nt_alive, const uint8_t** vkeep) {
+    const cx_params& P = ctx->last;
+    const uint32_t nv = (uint32_t)ctx->counts.n_vertices, nt = (uint32_t)ctx->counts.n_triangles;
+    hipStream_t st = ctx->stream;
+    if (nv) cxp_launch_vertices_f64(dim3(cx_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2, P.div_plane, P.div_row, P.value,
+                                    (const cx_vrec*)ctx->verts.get(), nv, S->raw.pts, S->raw.prio, org);
+    if (nt) CX_HIP(ctx, hipMemcpyAsync(S->raw.tri, ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    if (ctx->keep_valid && vkeep) {   // cx_select_seeded3d: only the triangles (and vertices) of the selected components exist
+        CX_HIP(ctx, hipMemcpyAsync(S->raw.alive, ctx->tri_keep, nt, hipMemcpyDeviceToDevice, st));
+        *vkeep = ctx->tri_keep + nt;
+    } else {
+        CX_HIP(ctx, hipMemsetAsync(S->raw.alive, 1, nt_alive, st));
+    }
     return CX_OK;
+}
+// the reference's `corner` (voxels per axis) of the resident array; an array with a margin around the reference's grid carries the
+// reference's own corner in ctx->corner_ref (cx_set_reference_corner)
+static void cxp_corner_of(const cx_ctx* ctx, double corner[3]) {
+    const cx_params& P = ctx->last;
+    const uint32_t n[3] = {P.n0, P.n1, P.n2};
+    for (int a = 0; a < 3; a++) corner[a] = ctx->corner_ref[a] > 0 ? (double)ctx->corner_ref[a] : (double)(n[a] - 1);
 }
 // weld -> (smooth) -> tiny collapse -> clean -> orient on S->pts / S->prio / S->tri / S->alive (A6..A10)
 // edge_crossings: the vertices are the march's own crossings with their edge ids as priorities (cx_postprocess3d*), not points
@@ -1462,13 +1503,13 @@ static int cxp_run3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, co
                      double smooth, bool coherent, int64_t* counts, bool edge_crossings = false, const cxp_shard* shard = nullptr, bool march_mesh = false) {
     int rc;
     hipStream_t st = ctx->stream;
-    double* pts = S->pts.as<double>();
-    uint32_t* prio = S->prio.as<uint32_t>();
+    double* pts = S->raw.pts;
+    uint32_t* prio = S->raw.prio;
     uint32_t* rep = S->rep.as<uint32_t>();
     uint8_t* moved = (uint8_t*)(rep + nv + 1);
-    int32_t* tri = S->tri.as<int32_t>();
-    uint32_t* tprio3 = (uint32_t*)(tri + (size_t)(nt + 1) * 3);
-    uint8_t* alive = S->alive.as<uint8_t>();
+    int32_t* tri = S->raw.tri;
+    uint32_t* tprio3 = S->raw.tprio3;
+    uint8_t* alive = S->raw.alive;
     uint32_t* misc = S->misc.as<uint32_t>();
     uint8_t* ever = nullptr;      // the march's own crossings: which vertices weld or clean-up merge something into
     for (int a = 0; a < 3; a++) S->corner[a] = corner[a];
@@ -1504,11 +1545,9 @@ static int cxp_run3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, co
         if (involved) CX_HIP(ctx, hipMemsetAsync(involved, 0, nv, st));
         hipLaunchKernelGGL(cxp_k_remap, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, rep, (const u64*)nullptr, involved, ever);
         const u64 tsz = involved ? cxp_edge_table_size(nt) : cx_table_size(nt);
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXD_EMPTY);
-        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
-        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)involved);
-        CX_HIP(ctx, hipMemsetAsync(misc + 4, 0, 2 * sizeof(uint32_t), st));
-        hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cx_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 4);
+        cxp_dedupe(ctx, S, tri, tprio3, alive, nt, tsz, involved);
+        CX_HIP(ctx, hipMemsetAsync(misc + CXP_M_WELD, 0, 2 * sizeof(uint32_t), st));
+        hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cx_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + CXP_M_WELD);
         if (smooth > 0.0) {
             // ---- smooth_interpolations (tetrahedral.py:547-550), between the weld and the tiny collapse
             const u64 esz = cx_table_size((size_t)nt * 3);
@@ -1536,14 +1575,14 @@ static int cxp_run3d(cx_ctx* ctx, cx_post_state* S, uint32_t nv, uint32_t nt, co
                            1.0 / corner[2], 1e-4, parent, prio, moved);
         // roots keep their own coordinates, so moving members in place is race free
         hipLaunchKernelGGL(cxp_k_move, dim3(cx_blocks(nv)), dim3(256), 0, st, pts, pts, parent, moved, nv);
-        hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cx_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + 5);
+        hipLaunchKernelGGL(cxp_k_count_alive, dim3(std::min(cx_blocks(nt), 1024u)), dim3(256), 0, st, alive, nt, misc + CXP_M_TINY);
         uint32_t h[2];
-        CX_HIP(ctx, hipMemcpyAsync(h, misc + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        CX_HIP(ctx, hipMemcpyAsync(h, misc + CXP_M_WELD, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         CX_HIP(ctx, hipStreamSynchronize(st));
         counts[2] = h[0]; counts[3] = h[1];
     }
     // (`moved` is free again after cxp_k_move)
-    return cxp_clean_orient(ctx, S, nv, nt, do_clean, true, tprio3, counts, coherent,
+    return cxp_clean_orient(ctx, S, nv, nt, do_clean, true, counts, coherent,
                             (coherent && nv && nt && !cx_debug_knob("CX_DEDUPE_ALL", 0)) ? moved : nullptr, shard, ever);
 }
 
@@ -1555,10 +1594,9 @@ extern "C" int cx_postprocess3d_ex(cx_ctx* ctx, uint32_t flags, double smooth, i
     int rc = cxp_state(ctx, &S);
     if (rc) return rc;
     const uint32_t nv = (uint32_t)ctx->counts.n_vertices, nt = (uint32_t)ctx->counts.n_triangles;
-    hipStream_t st = ctx->stream;
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if ((rc = cxp_reserve3d(ctx, S, nv, nt))) return rc;
-    const cx_params& P = ctx->last;
+    cxp_begin(ctx, S);
+    if ((rc = cxp_reserve_raw(ctx, S, nv, nt, true))) return rc;
     const uint8_t* vkeep = nullptr;
     // an array with a rim of samples around the reference's grid starts at a NEGATIVE lattice point (cx_set_origin):
     // the post-pass then works in the reference's own lattice coordinates, so that the weld buckets truncate as the
@@ -1566,27 +1604,11 @@ extern "C" int cx_postprocess3d_ex(cx_ctx* ctx, uint32_t flags, double smooth, i
     cxp_origin3 org{{0.0, 0.0, 0.0}};
     if (ctx->origin[0] < 0 || ctx->origin[1] < 0 || ctx->origin[2] < 0)
         for (int a = 0; a < 3; a++) org.o[a] = (double)ctx->origin[a];
-    if (nv && nt) {
-        cxp_launch_vertices_f64(dim3(cx_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
-                           P.div_plane, P.div_row, P.value, ctx->verts.get(), nv, S->pts.as<double>(), S->prio.as<uint32_t>(), org);
-        CX_HIP(ctx, hipMemcpyAsync(S->tri.get(), ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        if (ctx->keep_valid) {   // cx_select_seeded3d: only the triangles (and vertices) of the selected components exist
-            CX_HIP(ctx, hipMemcpyAsync(S->alive.get(), ctx->tri_keep, nt, hipMemcpyDeviceToDevice, st));
-            vkeep = ctx->tri_keep + nt;
-        } else {
-            CX_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
-        }
-    }
-    // the reference's `corner` (voxels per axis); a sample array with a margin around the reference's grid
-    // carries the reference's own corner in ctx->corner_ref (cx_set_reference_corner)
-    double corner[3] = {(double)(P.n0 - 1), (double)(P.n1 - 1), (double)(P.n2 - 1)};
-    for (int a = 0; a < 3; a++)
-        if (ctx->corner_ref[a] > 0) corner[a] = (double)ctx->corner_ref[a];
+    if (nv && nt && (rc = cxp_raw_from_extraction(ctx, S, org, nt, &vkeep))) return rc;
+    double corner[3];
+    cxp_corner_of(ctx, corner);
     if ((rc = cxp_run3d(ctx, S, nv, nt, corner, vkeep, !(flags & 1u), smooth, true, counts, true))) return rc;   // the march winds every triangle low -> high
-    ctx->post_valid = true;
-    S->keys_edge = true;
-    if (out_counts) memcpy(out_counts, counts, sizeof(counts));
-    return CX_OK;
+    return cxp_publish(ctx, S, cxp_record::MESH3D, cxp_record::GRID, counts, out_counts);
 }
 
 // ---- the capped mesh (cx_cap.hip, include/contourist_hip.h "rim caps"): the Level-0 mesh followed by the cap of cx_cap3d ---------------
@@ -1614,29 +1636,26 @@ extern "C" int cx_postprocess3d_capped(cx_ctx* ctx, uint32_t flags, int64_t* out
     const uint32_t nv = nv0 + K.ncv, nt = nt0 + K.nct;
     hipStream_t st = ctx->stream;
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if ((rc = cxp_reserve3d(ctx, S, nv, nt))) return rc;
+    cxp_begin(ctx, S);
+    if ((rc = cxp_reserve_raw(ctx, S, nv, nt, true))) return rc;
     const cx_params& P = ctx->last;
+    // ON PURPOSE: the origin is zero and cx_set_reference_corner is ignored (unlike cx_postprocess3d_ex): the cap's lattice points are
+    // those of the array that was marched, and the corner that of that array
     const cxp_origin3 org{{0.0, 0.0, 0.0}};
     if (nv && nt) {
-        const double* A64 = ctx->grid64_valid ? ctx->grid64.get() : nullptr;
-        if (nv0) cxp_launch_vertices_f64(dim3(cx_blocks(nv0)), st, P.grid, A64, P.n1, P.n2, P.div_plane, P.div_row, P.value, (const cx_vrec*)ctx->verts.get(), nv0,
-                                         S->pts.as<double>(), S->prio.as<uint32_t>(), org);
-        if (K.ncv) cxp_launch_vertices_f64(dim3(cx_blocks(K.ncv)), st, P.grid, A64, P.n1, P.n2, P.div_plane, P.div_row, P.value, K.vrec, K.ncv,
-                                           S->pts.as<double>() + (size_t)nv0 * 3, S->prio.as<uint32_t>() + nv0, org);
-        if (nt0) CX_HIP(ctx, hipMemcpyAsync(S->tri.get(), ctx->tris, (size_t)nt0 * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        if (K.nct) CX_HIP(ctx, hipMemcpyAsync(S->tri.as<int32_t>() + (size_t)nt0 * 3, K.tris, (size_t)K.nct * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        CX_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
+        if ((rc = cxp_raw_from_extraction(ctx, S, org, nt, nullptr))) return rc;      // (alive bytes for the cap's triangles too)
+        if (K.ncv) cxp_launch_vertices_f64(dim3(cx_blocks(K.ncv)), st, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2, P.div_plane, P.div_row,
+                                           P.value, K.vrec, K.ncv, S->raw.pts + (size_t)nv0 * 3, S->raw.prio + nv0, org);
+        if (K.nct) CX_HIP(ctx, hipMemcpyAsync(S->raw.tri + (size_t)nt0 * 3, K.tris, (size_t)K.nct * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     }
     const double corner[3] = {(double)(P.n0 - 1), (double)(P.n1 - 1), (double)(P.n2 - 1)};
     if ((rc = cxp_run3d(ctx, S, nv, nt, corner, nullptr, !(flags & 1u), 0.0, true, counts, true))) return rc;
-    ctx->post_valid = true;
-    S->keys_edge = true;
-    S->capped_gen = S->gen;
-    if (out_counts) memcpy(out_counts, counts, sizeof(counts));
-    return CX_OK;
+    S->rec.capped = true;
+    return cxp_publish(ctx, S, cxp_record::MESH3D, cxp_record::GRID, counts, out_counts);
 }
-bool cx_level1_capped(cx_ctx* ctx) { return ctx->post && ctx->post_valid && ctx->post->capped(); }
+bool cx_level1_capped(cx_ctx* ctx) { return cxp_mesh3d(ctx) && ctx->post->rec.capped; }
 
+static bool cxp_shard_open(const cx_ctx* ctx) { return ctx->post && ctx->post->rec.holds == cxp_record::SHARD_OPEN; }
 // ---- sharded Level 1 (the reference is one process: tetrahedral.py:190-215, 353-375, surface_geometry.py:14-140) ----
 // The context holds the extraction of a slab that was marched TOGETHER with two layers of cells of each neighbour slab
 // (cx_set_origin = where the local array starts in the whole volume, cx_set_reference_corner = the whole volume's corner).
@@ -1659,25 +1678,18 @@ extern "C" int cx_postprocess3d_shard_begin(cx_ctx* ctx, uint32_t flags, int64_t
     int rc = cxp_state(ctx, &S);
     if (rc) return rc;
     const uint32_t nv = (uint32_t)ctx->counts.n_vertices, nt = (uint32_t)ctx->counts.n_triangles;
-    hipStream_t st = ctx->stream;
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if ((rc = cxp_reserve3d(ctx, S, nv, nt))) return rc;
+    cxp_begin(ctx, S);
+    if ((rc = cxp_reserve_raw(ctx, S, nv, nt, true))) return rc;
     // coordinates of the WHOLE volume, added to the lattice points before the interpolation: bit for bit what the undivided
     // volume computes, so that the weld buckets truncate identically
     const cxp_origin3 org{{(double)ctx->origin[0], (double)ctx->origin[1], (double)ctx->origin[2]}};
-    if (nv && nt) {
-        cxp_launch_vertices_f64(dim3(cx_blocks(nv)), st, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
-                           P.div_plane, P.div_row, P.value, ctx->verts.get(), nv, S->pts.as<double>(), S->prio.as<uint32_t>(), org);
-        CX_HIP(ctx, hipMemcpyAsync(S->tri.get(), ctx->tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        CX_HIP(ctx, hipMemsetAsync(S->alive.get(), 1, nt, st));
-    }
-    double corner[3] = {(double)(P.n0 - 1), (double)(P.n1 - 1), (double)(P.n2 - 1)};
-    for (int a = 0; a < 3; a++)
-        if (ctx->corner_ref[a] > 0) corner[a] = (double)ctx->corner_ref[a];
+    if (nv && nt && (rc = cxp_raw_from_extraction(ctx, S, org, nt, nullptr))) return rc;
+    double corner[3];
+    cxp_corner_of(ctx, corner);
     const cxp_shard sh{P.n1 * P.n2, (uint32_t)own_lo, (uint32_t)own_hi, P.n0 - 1};
-    ctx->post_valid = false;
     if ((rc = cxp_run3d(ctx, S, nv, nt, corner, nullptr, !(flags & 1u), 0.0, true, counts, true, &sh))) return rc;
-    if (out_counts) memcpy(out_counts, counts, sizeof(counts));
+    cxp_publish(ctx, S, cxp_record::SHARD_OPEN, cxp_record::SHARD, counts, out_counts);
     *n_own_lower = S->shard.n1;
     *n_upper_copies = S->shard.n4;
     *n_candidates = S->shard.ncand;
@@ -1691,18 +1703,16 @@ extern "C" int cx_postprocess3d_shard_begin(cx_ctx* ctx, uint32_t flags, int64_t
 // are meant to stay on the device: a torch tensor sorts and sends them).
 extern "C" int cx_postprocess3d_shard_boundary(cx_ctx* ctx, int which, uint64_t* hash, uint32_t* label) {
     if (!ctx || (which != 1 && which != 4)) return CX_ERR_INVALID;
-    if (!ctx->post || !ctx->post->shard.open) { ctx->err = "cx_postprocess3d_shard_boundary: call cx_postprocess3d_shard_begin first"; return CX_ERR_STATE; }
+    if (!cxp_shard_open(ctx)) { ctx->err = "cx_postprocess3d_shard_boundary: call cx_postprocess3d_shard_begin first"; return CX_ERR_STATE; }
     CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
-    const size_t n1 = S->shard.n1, n4 = S->shard.n4, nb = n1 + n4;
+    const size_t n1 = S->shard.n1, n4 = S->shard.n4;
     const size_t n = which == 1 ? n1 : n4;
     if (!n) return CX_OK;
     if (!hash || !label) return CX_ERR_INVALID;
-    const u64* hash1 = S->bnd.as<const u64>();
-    const cxp_cand* cand = (const cxp_cand*)(hash1 + nb);
-    const uint32_t* label1 = (const uint32_t*)(cand + nb);
-    CX_HIP(ctx, hipMemcpyAsync(hash, which == 1 ? hash1 : hash1 + n1, n * sizeof(u64), hipMemcpyDefault, ctx->stream));
-    CX_HIP(ctx, hipMemcpyAsync(label, which == 1 ? label1 : label1 + n1, n * sizeof(uint32_t), hipMemcpyDefault, ctx->stream));
+    const cxp_bnd B = cxp_bnd_view(S, n1, n4);
+    CX_HIP(ctx, hipMemcpyAsync(hash, which == 1 ? B.hash1 : B.hash4, n * sizeof(u64), hipMemcpyDefault, ctx->stream));
+    CX_HIP(ctx, hipMemcpyAsync(label, which == 1 ? B.label1 : B.label4, n * sizeof(uint32_t), hipMemcpyDefault, ctx->stream));
     CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CX_OK;
 }
@@ -1714,13 +1724,13 @@ extern "C" int cx_postprocess3d_shard_boundary(cx_ctx* ctx, int which, uint64_t*
 extern "C" int cx_postprocess3d_shard_candidates(cx_ctx* ctx, uint32_t* cand_label, double* cand_x, uint32_t* cand_vertex_key, double* cand_nx,
                                                  uint8_t* cand_negative, uint8_t* cand_has) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!ctx->post || !ctx->post->shard.open) { ctx->err = "cx_postprocess3d_shard_candidates: call cx_postprocess3d_shard_begin first"; return CX_ERR_STATE; }
+    if (!cxp_shard_open(ctx)) { ctx->err = "cx_postprocess3d_shard_candidates: call cx_postprocess3d_shard_begin first"; return CX_ERR_STATE; }
     CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
-    const size_t nb = (size_t)S->shard.n1 + S->shard.n4, nc = S->shard.ncand;
+    const size_t nc = S->shard.ncand;
     if (!nc) return CX_OK;
     if (!cand_label || !cand_x || !cand_vertex_key || !cand_nx || !cand_negative || !cand_has) return CX_ERR_INVALID;
-    const cxp_cand* cand = (const cxp_cand*)(S->bnd.as<const u64>() + nb);
+    const cxp_cand* cand = cxp_bnd_view(S, S->shard.n1, S->shard.n4).cand;
     std::vector<cxp_cand> h(nc);
     CX_HIP(ctx, hipMemcpyAsync(h.data(), cand, nc * sizeof(cxp_cand), hipMemcpyDeviceToHost, ctx->stream));
     CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1737,15 +1747,10 @@ extern "C" int cx_postprocess3d_shard_candidates(cx_ctx* ctx, uint32_t* cand_lab
 // of the whole volume.  out_counts as cx_postprocess3d ([0] vertices, [1] triangles, [4] components seen locally).
 extern "C" int cx_postprocess3d_shard_finish(cx_ctx* ctx, const uint32_t* labels, const uint8_t* flips, int64_t n, int64_t* out_counts) {
     if (!ctx || n < 0 || (n && (!labels || !flips))) return CX_ERR_INVALID;
-    if (!ctx->post || !ctx->post->shard.open) { ctx->err = "cx_postprocess3d_shard_finish: call cx_postprocess3d_shard_begin first"; return CX_ERR_STATE; }
+    if (!cxp_shard_open(ctx)) { ctx->err = "cx_postprocess3d_shard_finish: call cx_postprocess3d_shard_begin first"; return CX_ERR_STATE; }
     if (n > (int64_t)ctx->post->shard.nt2) { ctx->err = "cx_postprocess3d_shard_finish: more labels than triangles"; return CX_ERR_INVALID; }
     CX_HIP(ctx, hipSetDevice(ctx->device));
-    int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int rc = cxp_shard_finish(ctx, ctx->post, labels, flips, (uint32_t)n, counts);
-    if (rc) return rc;
-    ctx->post_valid = true;
-    if (out_counts) memcpy(out_counts, counts, sizeof(counts));
-    return CX_OK;
+    return cxp_shard_finish(ctx, ctx->post, labels, flips, (uint32_t)n, out_counts);
 }
 
 // edge id ((linear index of the lower lattice point << 3) | direction, local to the array that was marched) of every vertex of
@@ -1753,7 +1758,7 @@ extern "C" int cx_postprocess3d_shard_finish(cx_ctx* ctx, const uint32_t* labels
 // weld, tiny collapse and clean-up)
 extern "C" int cx_level1_download_keys(cx_ctx* ctx, uint32_t* keys) {
     if (!ctx || !keys) return CX_ERR_INVALID;
-    if (!ctx->post || !ctx->post_valid || !ctx->post->keys_valid) { ctx->err = "cx_level1_download_keys: run cx_postprocess3d first"; return CX_ERR_STATE; }
+    if (!cxp_mesh3d(ctx)) { ctx->err = "cx_level1_download_keys: run cx_postprocess3d first"; return CX_ERR_STATE; }
     CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     if (!S->nv_out) return CX_OK;
@@ -1772,15 +1777,14 @@ extern "C" int cx_level0_points_f64(cx_ctx* ctx, double* points_xyz) {
     if (rc) return rc;
     const uint32_t nv = (uint32_t)ctx->counts.n_vertices;
     if (!nv) return CX_OK;
+    cxp_begin(ctx, S);         // (the points go where the post-pass starts from: the buffers no longer hold a Level-1 mesh)
     if ((rc = S->pts.grow(ctx, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
     if ((rc = S->prio.grow(ctx, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
     const cx_params& P = ctx->last;
     const cxp_origin3 org{{(double)ctx->origin[0], (double)ctx->origin[1], (double)ctx->origin[2]}};
     cxp_launch_vertices_f64(dim3(cx_blocks(nv)), ctx->stream, P.grid, ctx->grid64_valid ? ctx->grid64.get() : nullptr, P.n1, P.n2,
                        P.div_plane, P.div_row, P.value, ctx->verts.get(), nv, S->pts.as<double>(), S->prio.as<uint32_t>(), org);
-    if ((rc = cx_copy_to_host1(ctx, points_xyz, S->pts.get(), (size_t)nv * 3 * sizeof(double)))) return rc;
-    ctx->post_valid = false;   // the post-pass buffers no longer hold a Level-1 mesh
-    return CX_OK;
+    return cx_copy_to_host1(ctx, points_xyz, S->pts.get(), (size_t)nv * 3 * sizeof(double));
 }
 
 // Level 1 of a Level-0 mesh handed over by the caller, e.g. assembled from the slabs of several GPUs: vertices in
@@ -1806,7 +1810,8 @@ extern "C" int cx_postprocess3d_mesh(cx_ctx* ctx, const double* points_xyz, int6
     }
     hipStream_t st = ctx->stream;
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if ((rc = cxp_reserve3d(ctx, S, nv, nt))) return rc;
+    cxp_begin(ctx, S);         // (the input is good: from here on the resident mesh is gone)
+    if ((rc = cxp_reserve_raw(ctx, S, nv, nt, true))) return rc;
     if (nv && nt) {
         CX_HIP(ctx, hipMemcpyAsync(S->pts.get(), points_xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, st));
         CX_HIP(ctx, hipMemcpyAsync(S->tri.get(), tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -1815,14 +1820,12 @@ extern "C" int cx_postprocess3d_mesh(cx_ctx* ctx, const double* points_xyz, int6
     }
     const double corner[3] = {(double)corner3[0], (double)corner3[1], (double)corner3[2]};
     if ((rc = cxp_run3d(ctx, S, nv, nt, corner, nullptr, !(flags & 1u), smooth, !(flags & 4u), counts, false, nullptr, (flags & 8u) != 0u))) return rc;
-    ctx->post_valid = true;
-    if (out_counts) memcpy(out_counts, counts, sizeof(counts));
-    return CX_OK;
+    return cxp_publish(ctx, S, cxp_record::MESH3D, cxp_record::CALLER_MESH, counts, out_counts);
 }
 
 extern "C" int cx_level1_download(cx_ctx* ctx, double* points_xyz, int32_t* tris) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!ctx->post || !ctx->post_valid) { ctx->err = "cx_level1_download: run cx_postprocess3d first"; return CX_ERR_STATE; }
+    if (!cxp_mesh3d(ctx)) { ctx->err = "cx_level1_download: run cx_postprocess3d first"; return CX_ERR_STATE; }
     CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     void* d[2] = {(points_xyz && S->nv_out) ? (void*)points_xyz : nullptr, (tris && S->nt_out) ? (void*)tris : nullptr};
@@ -1836,7 +1839,7 @@ extern "C" int cx_level1_download(cx_ctx* ctx, double* points_xyz, int32_t* tris
 // is complete when this returns.
 extern "C" int cx_level1_device_ptrs(cx_ctx* ctx, void** points_xyz, void** tris, int64_t* n_vertices, int64_t* n_triangles) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!ctx->post || !ctx->post_valid) { ctx->err = "cx_level1_device_ptrs: run cx_postprocess3d first"; return CX_ERR_STATE; }
+    if (!cxp_mesh3d(ctx)) { ctx->err = "cx_level1_device_ptrs: run cx_postprocess3d first"; return CX_ERR_STATE; }
     CX_HIP(ctx, hipSetDevice(ctx->device));
     CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     cx_post_state* S = ctx->post;
@@ -1860,28 +1863,37 @@ __global__ void cxp_k_vertex_flip(const int32_t* __restrict__ tri, uint32_t nt, 
 #pragma unroll
     for (int k = 0; k < 3; k++) vflip[(uint32_t)tri[(size_t)t * 3 + k]] = 1;
 }
+// what the two views answer without a 3-D mesh: CX_ERR_INVALID; where the 4-D post-pass's result lies in the buffers instead, CX_ERR_STATE
+// with the view's text for tables that are gone (that pass took their memory)
+static int cxp_no_mesh3d(cx_ctx* ctx, const char* who, const char* gone) {
+    const bool tets = cxp_tets4d(ctx);
+    ctx->err = std::string(who) + (tets ? gone : ": no Level-1 mesh (run cx_postprocess3d first)");
+    return tets ? CX_ERR_STATE : CX_ERR_INVALID;
+}
+static const char CXP_ATTR_GONE[] = ": the orientation tables of the post-pass are gone (run cx_postprocess3d again)";
+static const char CXP_COMP_GONE[] = ": the orientation tables of the post-pass are gone (a 4-D pass used their memory, or the post-pass ran without the orientation step): run cx_postprocess3d again";
 int cx_level1_attr_view(cx_ctx* ctx, const char* who, cx_level1_view* out) {
-    if (!ctx->post || !ctx->post_valid || !ctx->post->keys_valid) { ctx->err = std::string(who) + ": no Level-1 mesh (run cx_postprocess3d first)"; return CX_ERR_INVALID; }
+    if (!cxp_mesh3d(ctx)) return cxp_no_mesh3d(ctx, who, CXP_ATTR_GONE);
     cx_post_state* S = ctx->post;
-    if (!S->keys_edge) {
-        ctx->err = std::string(who) + (S->clipped ? ": the vertices of a clipped mesh (cx_level1_clip_*) are not all edge crossings of the resident array"
-                                       : S->simplified ? ": the vertices of a simplified mesh (cx_level1_simplify) are cluster means, not edge crossings of the resident array"
+    if (S->rec.origin != cxp_record::GRID) {
+        ctx->err = std::string(who) + (S->rec.origin == cxp_record::CLIPPED ? ": the vertices of a clipped mesh (cx_level1_clip_*) are not all edge crossings of the resident array"
+                                       : S->rec.origin == cxp_record::SIMPLIFIED ? ": the vertices of a simplified mesh (cx_level1_simplify) are cluster means, not edge crossings of the resident array"
                                                      : ": the Level-1 vertices are not edge crossings of the resident array (a mesh handed to cx_postprocess3d_mesh, or a shard)");
         return CX_ERR_UNSUPPORTED;
     }
     const uint32_t nv = (uint32_t)S->nv_out, nt = (uint32_t)S->nt_out;
-    if (nv && !S->vflip_valid) {
-        if (nt && (!S->orient_live || S->orient_nt != nt)) { ctx->err = std::string(who) + ": the orientation tables of the post-pass are gone (run cx_postprocess3d again)"; return CX_ERR_STATE; }
+    if (nv && !S->rec.vflip_cached) {
+        if (nt && !S->rec.tables_for(nt)) { ctx->err = std::string(who) + CXP_ATTR_GONE; return CX_ERR_STATE; }
         int rc;
         if ((rc = S->vflip.grow(ctx, (size_t)nv + 16))) return rc;
         CX_HIP(ctx, hipMemsetAsync(S->vflip.get(), 0, nv, ctx->stream));
         if (nt) {
             const u64* parent = S->parent.as<const u64>();
-            const u64* cflip = S->comp.as<const u64>() + nt;    // (cbest of cxp_clean_orient)
+            const u64* cflip = cxp_comp_view(S->comp.as<u64>(), nt).cflip;
             hipLaunchKernelGGL(cxp_k_vertex_flip, dim3(cx_blocks(nt)), dim3(256), 0, ctx->stream, S->tri_out.as<const int32_t>(), nt, parent, cflip, S->vflip.as<uint8_t>());
             CX_HIP(ctx, hipGetLastError());
         }
-        S->vflip_valid = true;
+        S->rec.vflip_cached = true;
     }
     out->keys = S->keys_out.as<const uint32_t>();
     out->vflip = S->vflip.as<const uint8_t>();
@@ -1904,25 +1916,25 @@ __global__ void cxp_k_carry_normals(const double* __restrict__ in, const uint32_
     for (int a = 0; a < 3; a++) out[(size_t)j * 3 + a] = in[(size_t)v * 3 + a];
 }
 int cx_level1_comp_view_get(cx_ctx* ctx, const char* who, cx_level1_comp_view* out) {
-    if (!ctx->post || !ctx->post_valid || !ctx->post->keys_valid) { ctx->err = std::string(who) + ": no Level-1 mesh (run cx_postprocess3d first)"; return CX_ERR_INVALID; }
+    if (!cxp_mesh3d(ctx)) return cxp_no_mesh3d(ctx, who, CXP_COMP_GONE);
     cx_post_state* S = ctx->post;
-    if (S->shard_mesh || S->shard.open) {
+    if (S->rec.origin == cxp_record::SHARD) {
         ctx->err = std::string(who) + ": the components of a sharded Level-1 mesh reach other ranks (cx_postprocess3d_shard_*): not available";
         return CX_ERR_UNSUPPORTED;
     }
     const uint32_t nv = (uint32_t)S->nv_out, nt = (uint32_t)S->nt_out;
-    if ((nt && (!S->orient_live || S->orient_nt != nt)) || (!nt && S->orient_nt && !S->orient_live)) {
-        ctx->err = std::string(who) + ": the orientation tables of the post-pass are gone (a 4-D pass used their memory, or the post-pass ran without the orientation step): run cx_postprocess3d again";
+    if (nt && !S->rec.tables_for(nt)) {
+        ctx->err = std::string(who) + CXP_COMP_GONE;
         return CX_ERR_STATE;
     }
     out->parent = S->parent.as<const u64>();
-    out->cflip = nt ? S->comp.as<const u64>() + nt : nullptr;    // (cbest of cxp_clean_orient)
+    out->cflip = nt ? cxp_comp_view(S->comp.as<u64>(), nt).cflip : nullptr;
     out->tri = S->tri_out.as<const int32_t>();
     out->pts = S->pts_out.as<const double>();
     out->keys = S->keys_out.as<const uint32_t>();
     out->nv = nv; out->nt = nt;
     for (int a = 0; a < 3; a++) out->corner[a] = S->corner[a];
-    out->gen = S->gen;
+    out->gen = S->rec.gen;
     return CX_OK;
 }
 // room for a filtered copy of the mesh and its tables in buffers the post-pass is done with (the march's points and triangles, the key
@@ -1946,8 +1958,9 @@ int cx_level1_comp_scratch_get(cx_ctx* ctx, cx_level1_comp_scratch* out) {
 int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new, const uint32_t* vuse, const uint32_t* vnew) {
     cx_post_state* S = ctx->post;
     hipStream_t st = ctx->stream;
-    S->smap_valid = false;
-    if (S->carried && nv_new && S->nv_out) {       // the carried normals of a simplified mesh follow their vertices
+    const cxp_record before = S->rec;
+    cxp_begin(ctx, S);
+    if (before.normals_carried && nv_new && S->nv_out) {       // the carried normals of a simplified mesh follow their vertices
         const int rcn = S->nrm[1 - S->nrm_cur].grow(ctx, ((size_t)nv_new + 1) * 3 * sizeof(double));
         if (rcn) return rcn;
         hipLaunchKernelGGL(cxp_k_carry_normals, dim3(cx_blocks((size_t)S->nv_out)), dim3(256), 0, st, S->nrm[S->nrm_cur].as<const double>(), vuse, vnew,
@@ -1963,16 +1976,15 @@ int cx_level1_comp_commit(cx_ctx* ctx, uint32_t nv_new, uint32_t nt_new, const u
     if (nt_new) {
         CX_HIP(ctx, hipMemcpyAsync(S->tri_out.get(), S->tri.get(), (size_t)nt_new * 3 * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
         CX_HIP(ctx, hipMemcpyAsync(S->parent.get(), parent_new, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
-        CX_HIP(ctx, hipMemcpyAsync(S->comp.as<u64>() + nt_new, parent_new + nt_old + 1, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
+        CX_HIP(ctx, hipMemcpyAsync(cxp_comp_view(S->comp.as<u64>(), nt_new).cflip, parent_new + nt_old + 1, (size_t)nt_new * sizeof(u64), hipMemcpyDeviceToDevice, st));
     }
     CX_HIP(ctx, hipStreamSynchronize(st));
     S->nv_out = nv_new; S->nt_out = nt_new;
-    S->orient_nt = nt_new;
-    S->vflip_valid = false;      // (written again from the tables on the next request)
-    const bool capped = S->capped();     // (a filtered copy of a capped mesh is a capped mesh)
-    S->gen++;
-    if (capped) S->capped_gen = S->gen;
-    return CX_OK;
+    // a filtered copy keeps where the mesh came from, its cap and its normals; its tables are the filtered ones; the vertex flips are
+    // written again from them on the next request, and the map of an earlier simplification no longer fits
+    S->rec.capped = before.capped; S->rec.normals_carried = before.normals_carried;
+    S->rec.tables_live = before.tables_live; S->rec.tables_nt = nt_new;
+    return cxp_publish(ctx, S, cxp_record::MESH3D, before.origin, nullptr, nullptr);
 }
 
 // ---- what the simplification (cx_simplify.hip) needs from the Level-1 state ------------------------------------------------------------
@@ -1984,25 +1996,18 @@ int cx_level1_simplify_bufs(cx_ctx* ctx, bool normals, bool dry_run, cx_level1_s
     cx_post_state* S = ctx->post;
     const size_t nv = (size_t)S->nv_out, nt = (size_t)S->nt_out;
     int rc;
-    // (as cxp_reserve3d, without S->parent: it holds the tables of the orientation step the mesh still needs if the call fails)
-    if ((rc = S->pts.grow(ctx, (nv + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = S->prio.grow(ctx, (nv + 1) * sizeof(uint32_t)))) return rc;
-    if ((rc = S->tri.grow(ctx, (nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;
-    if ((rc = S->alive.grow(ctx, nt + 16))) return rc;
-    if ((rc = S->parent2.grow(ctx, (nv + 1) * sizeof(u64)))) return rc;
+    // (without S->parent: it holds the tables of the orientation step the mesh still needs if the call fails, and
+    // without S->rep, which a dry run takes for the map below)
+    if ((rc = cxp_reserve_raw(ctx, S, nv, nt))) return rc;
     // (a dry run leaves the map of the last simplification alone: its cluster ids go into the weld's scratch)
     if ((rc = (dry_run ? S->rep : S->smap).grow(ctx, (nv + 16) * sizeof(int32_t)))) return rc;
     if (normals && (rc = S->nrm_tmp.grow(ctx, (nv + 1) * 3 * sizeof(double)))) return rc;
-    out->pts = S->pts.as<double>();
-    out->prio = S->prio.as<uint32_t>();
-    out->tri = S->tri.as<int32_t>();
-    out->tprio3 = (uint32_t*)(out->tri + (nt + 1) * 3);
-    out->alive = S->alive.as<uint8_t>();
+    out->pts = S->raw.pts; out->prio = S->raw.prio; out->tri = S->raw.tri; out->tprio3 = S->raw.tprio3; out->alive = S->raw.alive;
     out->map = (dry_run ? S->rep : S->smap).as<int32_t>();
     out->nrm_new = normals ? S->nrm_tmp.as<double>() : nullptr;
-    out->nrm_src = S->carried ? S->nrm[S->nrm_cur].as<const double>() : nullptr;
-    out->simplified = S->simplified;
-    if (!dry_run) S->smap_valid = false;
+    out->nrm_src = S->rec.normals_carried ? S->nrm[S->nrm_cur].as<const double>() : nullptr;
+    out->simplified = S->rec.derived();
+    if (!dry_run) S->rec.map_live = false;
     return CX_OK;
 }
 // new index of every OLD vertex: through the cluster, the vertex the clean-up merged the cluster into (if any), the compaction
@@ -2018,22 +2023,18 @@ int cx_level1_simplify_tail(cx_ctx* ctx, uint32_t nv_old, uint32_t ncl, uint32_t
     cx_post_state* S = ctx->post;
     hipStream_t st = ctx->stream;
     int rc;
-    int32_t* tri = S->tri.as<int32_t>();
-    uint32_t* tprio3 = (uint32_t*)(tri + ((size_t)S->nt_out + 1) * 3);
-    uint8_t* alive = S->alive.as<uint8_t>();
     const int cur = S->nrm_cur;
+    cxp_begin(ctx, S);      // (the raw mesh is written; from here on the outputs are: a failure leaves no mesh)
     if (nt && ncl) {
         const u64 tsz = cx_table_size(nt);
         if ((rc = S->tkeys.grow(ctx, tsz * sizeof(u64)))) return rc;
-        hipLaunchKernelGGL(cxp_k_fill64, dim3(2048), dim3(256), 0, st, S->tkeys.as<u64>(), (size_t)tsz, CXD_EMPTY);
-        hipLaunchKernelGGL(cxp_k_dedupe_insert, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, tprio3, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)nullptr);
-        hipLaunchKernelGGL(cxp_k_dedupe_resolve, dim3(cx_blocks(nt)), dim3(256), 0, st, tri, alive, nt, S->tkeys.as<u64>(), tsz - 1, (const uint8_t*)nullptr);
+        cxp_dedupe(ctx, S, S->raw.tri, S->raw.tprio3, S->raw.alive, nt, tsz, nullptr);
     }
     // (the compaction writes the new id of every vertex in use: the others keep -1)
     if ((rc = S->scan.grow(ctx, ((size_t)ncl + 16) * sizeof(uint32_t)))) return rc;
     if (ncl) CX_HIP(ctx, hipMemsetAsync(S->scan.get(), 0xFF, (size_t)ncl * sizeof(uint32_t), st));
     if (normals && (rc = S->nrm[1 - cur].grow(ctx, ((size_t)ncl + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = cxp_clean_orient(ctx, S, ncl, nt, do_clean, true, tprio3, counts, true))) { ctx->post_valid = false; return rc; }
+    if ((rc = cxp_clean_orient(ctx, S, ncl, nt, do_clean, true, counts, true))) return rc;
     const uint32_t* vnew = S->scan.as<const uint32_t>();
     if (nv_old) hipLaunchKernelGGL(cxp_k_simplify_map, dim3(cx_blocks(nv_old)), dim3(256), 0, st, S->smap.as<int32_t>(), nv_old, ncl,
                                    (do_clean && nt) ? S->parent2.as<const u64>() : (const u64*)nullptr, vnew);
@@ -2044,25 +2045,25 @@ int cx_level1_simplify_tail(cx_ctx* ctx, uint32_t nv_old, uint32_t ncl, uint32_t
     }
     CX_HIP(ctx, hipGetLastError());
     CX_HIP(ctx, hipStreamSynchronize(st));
-    S->simplified = true; S->carried = normals;
-    S->smap_valid = true; S->smap_n = nv_old;
-    return CX_OK;
+    S->rec.normals_carried = normals;
+    S->rec.map_live = true; S->rec.map_n = nv_old;
+    return cxp_publish(ctx, S, cxp_record::MESH3D, cxp_record::SIMPLIFIED, nullptr, nullptr);
 }
 // 0: the mesh is not a simplified one; 1: simplified, *nrm = its carried normals; 2: simplified without normals
 int cx_level1_carried_normals(cx_ctx* ctx, const double** nrm, uint32_t* nv) {
     cx_post_state* S = ctx->post;
-    if (!S || !ctx->post_valid || !S->keys_valid || !S->simplified) return 0;
+    if (!cxp_mesh3d(ctx) || !S->rec.derived()) return 0;
     *nv = (uint32_t)S->nv_out;
-    *nrm = S->carried ? S->nrm[S->nrm_cur].as<const double>() : nullptr;
-    return S->carried ? 1 : 2;
+    *nrm = S->rec.normals_carried ? S->nrm[S->nrm_cur].as<const double>() : nullptr;
+    return S->rec.normals_carried ? 1 : 2;
 }
 int cx_level1_simplify_map_get(cx_ctx* ctx, const int32_t** map, uint32_t* n) {
     cx_post_state* S = ctx->post;
-    if (!S || !ctx->post_valid || !S->simplified || !S->smap_valid) {
+    if (!cxp_mesh3d(ctx) || !S->rec.map_live) {
         ctx->err = "cx_level1_simplify_map: no simplification since the last post-pass or filter";
         return CX_ERR_STATE;
     }
-    *map = S->smap.as<const int32_t>(); *n = S->smap_n;
+    *map = S->smap.as<const int32_t>(); *n = S->rec.map_n;
     return CX_OK;
 }
 
@@ -2073,16 +2074,8 @@ int cx_level1_simplify_map_get(cx_ctx* ctx, const int32_t** map, uint32_t* n) {
 int cx_level1_clip_bufs(cx_ctx* ctx, size_t nv_raw, size_t nt_raw, cx_level1_clip_io* out) {
     cx_post_state* S = ctx->post;
     int rc;
-    if ((rc = S->pts.grow(ctx, (nv_raw + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = S->prio.grow(ctx, (nv_raw + 1) * sizeof(uint32_t)))) return rc;
-    if ((rc = S->tri.grow(ctx, (nt_raw + 1) * 3 * sizeof(int32_t) * 2))) return rc;
-    if ((rc = S->alive.grow(ctx, nt_raw + 16))) return rc;
-    if ((rc = S->parent2.grow(ctx, (nv_raw + 1) * sizeof(u64)))) return rc;
-    out->pts = S->pts.as<double>();
-    out->prio = S->prio.as<uint32_t>();
-    out->tri = S->tri.as<int32_t>();
-    out->tprio3 = (uint32_t*)(out->tri + (nt_raw + 1) * 3);
-    out->alive = S->alive.as<uint8_t>();
+    if ((rc = cxp_reserve_raw(ctx, S, nv_raw, nt_raw))) return rc;
+    out->pts = S->raw.pts; out->prio = S->raw.prio; out->tri = S->raw.tri; out->tprio3 = S->raw.tprio3; out->alive = S->raw.alive;
     return CX_OK;
 }
 // clean (optional), compaction, orientation with the windings taken as coherent: the kernels cxp_run3d ends with.  The result is a
@@ -2090,11 +2083,10 @@ int cx_level1_clip_bufs(cx_ctx* ctx, size_t nv_raw, size_t nt_raw, cx_level1_cli
 int cx_level1_clip_tail(cx_ctx* ctx, uint32_t nv_raw, uint32_t nt_raw, bool do_clean, int64_t* counts) {
     cx_post_state* S = ctx->post;
     int rc;
-    uint32_t* tprio3 = (uint32_t*)(S->tri.as<int32_t>() + ((size_t)nt_raw + 1) * 3);
-    if ((rc = cxp_clean_orient(ctx, S, nv_raw, nt_raw, do_clean, true, tprio3, counts, true))) { ctx->post_valid = false; return rc; }
+    cxp_begin(ctx, S);
+    if ((rc = cxp_clean_orient(ctx, S, nv_raw, nt_raw, do_clean, true, counts, true))) return rc;
     CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    S->simplified = true; S->carried = false; S->clipped = true;
-    return CX_OK;
+    return cxp_publish(ctx, S, cxp_record::MESH3D, cxp_record::CLIPPED, nullptr, nullptr);
 }
 // room for the normals the clipped mesh carries (one per vertex of it, written by the caller on the context's stream)
 int cx_level1_clip_normals(cx_ctx* ctx, double** out) {
@@ -2104,13 +2096,13 @@ int cx_level1_clip_normals(cx_ctx* ctx, double** out) {
     if (rc) return rc;
     *out = S->nrm[1 - cur].as<double>();
     S->nrm_cur = 1 - cur;
-    S->carried = true;
+    S->rec.normals_carried = true;
     return CX_OK;
 }
 // the generation of the Level-1 mesh (0: there is none): what another translation unit caches belongs to one value of it
 uint64_t cx_level1_generation(cx_ctx* ctx) {
     cx_post_state* S = ctx->post;
-    return (S && ctx->post_valid && S->keys_valid) ? S->gen : 0;
+    return cxp_mesh3d(ctx) ? S->rec.gen : 0;
 }
 
 // SurfaceGeometry(vertices, triangles) on a caller's mesh.  mode: 0 = orient only, 1 = clean + orient, 2 = clean only.
@@ -2125,13 +2117,10 @@ extern "C" int cx_surface_geometry(cx_ctx* ctx, double* points_xyz, int64_t* nv_
     for (int64_t n = 0; n < (int64_t)nt * 3; n++)
         if (tris[n] < 0 || tris[n] >= (int64_t)nv) { ctx->err = "cx_surface_geometry: triangle index out of range"; return CX_ERR_INVALID; }
     hipStream_t st = ctx->stream;
-    if ((rc = S->pts.grow(ctx, (size_t)(nv + 1) * 3 * sizeof(double)))) return rc;
-    if ((rc = S->prio.grow(ctx, (size_t)(nv + 1) * sizeof(uint32_t)))) return rc;
-    if ((rc = S->tri.grow(ctx, (size_t)(nt + 1) * 3 * sizeof(int32_t) * 2))) return rc;
-    if ((rc = S->alive.grow(ctx, (size_t)nt + 16))) return rc;
-    if ((rc = S->parent2.grow(ctx, (size_t)(nv + 1) * sizeof(u64)))) return rc;
-    int32_t* tri = S->tri.as<int32_t>();
-    uint32_t* tprio3 = (uint32_t*)(tri + (size_t)(nt + 1) * 3);
+    cxp_begin(ctx, S);         // (nothing is published: the result goes back to the caller, the buffers hold no Level-1 mesh afterwards)
+    if ((rc = cxp_reserve_raw(ctx, S, nv, nt))) return rc;
+    int32_t* tri = S->raw.tri;
+    uint32_t* tprio3 = S->raw.tprio3;
     if (nv) CX_HIP(ctx, hipMemcpyAsync(S->pts.get(), points_xyz, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, st));
     if (nt) CX_HIP(ctx, hipMemcpyAsync(tri, tris, (size_t)nt * 3 * sizeof(int32_t), hipMemcpyHostToDevice, st));
     if (nv) hipLaunchKernelGGL(cxp_k_iota_prio, dim3(cx_blocks(nv)), dim3(256), 0, st, S->prio.as<uint32_t>(), nv);
@@ -2143,11 +2132,10 @@ extern "C" int cx_surface_geometry(cx_ctx* ctx, double* points_xyz, int64_t* nv_
                            (const u64*)nullptr);
     }
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if ((rc = cxp_clean_orient(ctx, S, nv, nt, mode != 0, mode != 2, tprio3, counts, false))) return rc;   // caller's windings: arbitrary
+    if ((rc = cxp_clean_orient(ctx, S, nv, nt, mode != 0, mode != 2, counts, false))) return rc;   // caller's windings: arbitrary
     if (S->nv_out) CX_HIP(ctx, hipMemcpyAsync(points_xyz, S->pts_out.get(), (size_t)S->nv_out * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     if (S->nt_out) CX_HIP(ctx, hipMemcpyAsync(tris, S->tri_out.get(), (size_t)S->nt_out * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     CX_HIP(ctx, hipStreamSynchronize(st));
     *nv_io = S->nv_out; *nt_io = S->nt_out;
-    ctx->post_valid = false;
     return CX_OK;
 }

@@ -135,26 +135,26 @@ static int cxp_post4_tets(cx_ctx* ctx, cx_post_state* S, const int32_t* tets, ui
     uint8_t* moved = S->rep.as<uint8_t>();
     uint8_t* alive = S->alive.as<uint8_t>();
     u64* parent = S->parent.as<u64>();
-    S->orient_live = false; S->gen++;   // (the 3-D orientation's tables lived here: what cx_comp.hip cached of them is stale)
+    cxp_tables_taken(S);    // (the 3-D orientation's tables lived in S->parent)
     uint32_t* misc = S->misc.as<uint32_t>();
     hipLaunchKernelGGL(cxp_k_drop_instant, dim3(cx_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1e-7);
     // cx_select_seeded4d: only the tetrahedra of the selected components exist
     if (keep) hipLaunchKernelGGL(cxp_k_and_mask, dim3(cx_blocks(nt)), dim3(256), 0, st, alive, keep, nt);
-    CX_HIP(ctx, hipMemsetAsync(misc + 4, 0, 2 * sizeof(uint32_t), st));
-    cxp_count_alive(st, alive, nt, misc + 4);
+    CX_HIP(ctx, hipMemsetAsync(misc + CXP_M_WELD, 0, 2 * sizeof(uint32_t), st));
+    cxp_count_alive(st, alive, nt, misc + CXP_M_WELD);
     cxp_iota64(st, parent, nv);
     CX_HIP(ctx, hipMemsetAsync(moved, 0, nv, st));
     hipLaunchKernelGGL(cxp_k_tiny4, dim3(cx_blocks(nt)), dim3(256), 0, st, tets, alive, nt, pts, 1.0 / corner[0], 1.0 / corner[1],
                        1.0 / corner[2], 1.0 / corner[3], 1e-3, parent, prio, moved);
     hipLaunchKernelGGL(cxp_k_move4, dim3(cx_blocks(nv)), dim3(256), 0, st, pts, parent, moved, nv);
-    cxp_count_alive(st, alive, nt, misc + 5);
+    cxp_count_alive(st, alive, nt, misc + CXP_M_TINY);
     uint32_t* tflag = S->flags.as<uint32_t>();
     uint32_t* tnew = S->scan.as<uint32_t>();
     cxp_alive_u32(st, alive, nt, tflag);
-    if ((rc = cxp_scan(ctx, S, tflag, tnew, nt, misc + 2))) return rc;
+    if ((rc = cxp_scan(ctx, S, tflag, tnew, nt, misc + CXP_M_TOTAL1))) return rc;
     uint32_t h[3];
-    CX_HIP(ctx, hipMemcpyAsync(h, misc + 4, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    CX_HIP(ctx, hipMemcpyAsync(h + 2, misc + 2, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipMemcpyAsync(h, misc + CXP_M_WELD, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    CX_HIP(ctx, hipMemcpyAsync(h + 2, misc + CXP_M_TOTAL1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     CX_HIP(ctx, hipStreamSynchronize(st));
     counts[2] = h[0]; counts[3] = h[1];
     const uint32_t nt2 = h[2];
@@ -186,6 +186,7 @@ extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double*
     if (rc) return rc;
     const uint32_t nv = (uint32_t)G->counts.n_vertices, nt = (uint32_t)G->counts.n_triangles;
     hipStream_t st = ctx->stream;
+    cxp_begin(ctx, S);
     if ((rc = cxp_reserve4(ctx, S, nv, nt))) return rc;
     double* pts = S->pts.as<double>();
     uint32_t* prio = S->prio.as<uint32_t>();
@@ -213,9 +214,7 @@ extern "C" int cx_postprocess4d_points(cx_ctx* ctx, int32_t nbins, const double*
     }
     S->nv_out = nv; S->nt_out = nt2;
     counts[0] = nv; counts[1] = nt2;
-    G->post_valid = true;
-    if (out_counts) memcpy(out_counts, counts, sizeof(counts));
-    return CX_OK;
+    return cxp_publish(ctx, S, cxp_record::TETS4D, cxp_record::GRID, counts, out_counts);
 }
 
 // ---- the same post-steps on a slab assembly (cx_slab4d.hip): the points were interpolated per slab in the whole volume's lattice, the
@@ -240,6 +239,7 @@ extern "C" int cx_slab4d_finish(cx_ctx* ctx, int32_t nbins, int64_t* out_counts)
     if ((rc = cxp_state(ctx, &S))) return rc;
     const uint32_t nv = A->nv, nt = A->nt;
     hipStream_t st = ctx->stream;
+    cxp_begin(ctx, S);
     if ((rc = cxp_reserve4(ctx, S, nv, nt))) return rc;
     int64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t nt2 = 0;
@@ -254,16 +254,13 @@ extern "C" int cx_slab4d_finish(cx_ctx* ctx, int32_t nbins, int64_t* out_counts)
     S->nv_out = nv; S->nt_out = nt2;
     counts[0] = nv; counts[1] = nt2;
     A->open = false;
-    G->post_valid = true;
     G->post_assembled = true;
-    if (out_counts) memcpy(out_counts, counts, sizeof(counts));
-    return CX_OK;
+    return cxp_publish(ctx, S, cxp_record::TETS4D, cxp_record::GRID, counts, out_counts);
 }
 
 extern "C" int cx_level1_4d_download(cx_ctx* ctx, double* points_xyzt, int32_t* tets) {
     if (!ctx) return CX_ERR_INVALID;
-    cx_state4* G = ctx->s4;
-    if (!G || !G->post_valid || !ctx->post) { ctx->err = "cx_level1_4d_download: run cx_postprocess4d first"; return CX_ERR_STATE; }
+    if (!cxp_tets4d(ctx)) { ctx->err = "cx_level1_4d_download: run cx_postprocess4d first"; return CX_ERR_STATE; }
     CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     void* d[2] = {(points_xyzt && S->nv_out) ? (void*)points_xyzt : nullptr, (tets && S->nt_out) ? (void*)tets : nullptr};

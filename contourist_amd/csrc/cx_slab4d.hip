@@ -20,6 +20,7 @@
 
 #include "cx_ctx.h"
 
+#include "cx_post.h"
 #include "cx_state4.h"
 
 #define CXS_BINS 256u
@@ -350,7 +351,7 @@ int cx_slab4_check(cx_ctx* ctx, cx_slab4* A) {
 extern "C" int cx_slab4d_download_keys(cx_ctx* ctx, int64_t* keys) {
     if (!ctx || !keys) return CX_ERR_INVALID;
     cx_state4* G = ctx->s4;
-    if (!G || !G->post_valid || !G->post_assembled || !G->slab) { ctx->err = "cx_slab4d_download_keys: run cx_slab4d_finish first"; return CX_ERR_STATE; }
+    if (!cxp_tets4d(ctx) || !G->post_assembled || !G->slab) { ctx->err = "cx_slab4d_download_keys: run cx_slab4d_finish first"; return CX_ERR_STATE; }
     CX_HIP(ctx, hipSetDevice(ctx->device));
     if (!G->slab->nv) return CX_OK;
     return cx_copy_to_host1(ctx, keys, G->slab->keys, (size_t)G->slab->nv * sizeof(uint64_t));

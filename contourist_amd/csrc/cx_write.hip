@@ -60,7 +60,7 @@ __global__ void cxw_k_faces13(const int32_t* __restrict__ tri, uint32_t first, u
 }
 extern "C" int cx_level1_write(cx_ctx* ctx, int format, const char* path, const double* mins_delta, double* out_info) {
     if (!ctx || !path || (format != CX_FILE_PLY && format != CX_FILE_GLTF_BIN && format != CX_FILE_PLY_NORMALS && format != CX_FILE_GLTF_BIN_NORMALS)) return CX_ERR_INVALID;
-    if (!ctx->post || !ctx->post_valid) { ctx->err = "cx_level1_write: run cx_postprocess3d first"; return CX_ERR_STATE; }
+    if (!cxp_mesh3d(ctx)) { ctx->err = "cx_level1_write: run cx_postprocess3d first"; return CX_ERR_STATE; }
     CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_post_state* S = ctx->post;
     // the formats with normals: the unit normals of cx_level1_normals (world normals when a spacing is handed over), laid out like the positions
