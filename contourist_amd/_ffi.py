@@ -63,6 +63,11 @@ DIST_KIND_DTYPES = {0: np.float64, 1: np.float32, 2: np.uint8}
 TOPOLOGY_DTYPE = np.dtype([("triangles", "<i8"), ("vertices", "<i8"), ("edges", "<i8"), ("boundary_edges", "<i8"), ("nonmanifold_edges", "<i8"),
                            ("euler", "<i8"), ("boundary_loops", "<i4"), ("genus", "<i4"), ("nonsimple_loops", "<i4"), ("reserved", "<i4")])
 LOOP_DTYPE = np.dtype([("component", "<i4"), ("simple", "<i4"), ("first", "<u4"), ("count", "<u4")])
+LABEL_SIDES = {"high": 0, "low": 1}                                 # CX_LABEL_*
+# one record of cx_grid_label3d_measures (cx_label_component): 72 bytes
+LABEL_COMPONENT_DTYPE = np.dtype([("voxels", "<i8"), ("first", "<i8"), ("sum", "<i8", (3,)), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)),
+                                  ("rim", "<u4"), ("reserved", "<u4")])
+assert LABEL_COMPONENT_DTYPE.itemsize == 72
 
 # every symbol include/contourist_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -80,6 +85,7 @@ SYMBOLS = [
     "cx_samples_select", "cx_level_spectrum3d",
     "cx_grid_filter3d", "cx_grid_filter3d_result", "cx_grid_filter3d_bind",
     "cx_grid_distance3d", "cx_grid_distance3d_result", "cx_grid_distance3d_bind",
+    "cx_grid_label3d", "cx_grid_label3d_result", "cx_grid_label3d_measures", "cx_grid_label3d_select", "cx_grid_label3d_select_result", "cx_grid_label3d_bind",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -301,6 +307,12 @@ def load():
         "cx_grid_distance3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, dbl, vp, ctypes.c_int32, ctypes.c_int32, dbl, vp, vp, vp],
         "cx_grid_distance3d_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)],
         "cx_grid_distance3d_bind": [vp],
+        "cx_grid_label3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, dbl, ctypes.c_int32, ctypes.c_int32, vp, vp, vp],
+        "cx_grid_label3d_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)],
+        "cx_grid_label3d_measures": [vp, vp, i64],
+        "cx_grid_label3d_select": [vp, vp, i64, vp, vp, vp],
+        "cx_grid_label3d_select_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int64)],
+        "cx_grid_label3d_bind": [vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -691,6 +703,81 @@ class Context(object):
         context): cx_grid_distance3d_bind"""
         shape = self.distance_result()[0]
         self._check(self.lib.cx_grid_distance3d_bind(self.handle))
+        self.shape = shape
+        self._keep = None
+
+    def label_grid(self, value, side="high", connectivity=1, samples=None, out=None, download=False):
+        """connected components of the samples thresholded at `value` (cx_grid_label3d) -> (K, the labels).
+        side: a name of LABEL_SIDES ("high": the samples with f >= value and the NaNs are labelled, "low": those with f < value);
+        connectivity: 1, 2 or 3 (6, 18 or 26 neighbours).
+        samples: as in filter_grid (None = the bound grid, a 3-D numpy array, (device pointer, dtype, shape), (numpy array, dtype, shape)).
+        out: None = the labels stay in the context (label_result, label_measures, label_select); or a device pointer to room for them.
+        The labels: an int32 numpy array with download=True, else their device pointer."""
+        keep = []
+        if samples is None:
+            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
+        elif isinstance(samples, tuple) and isinstance(samples[0], np.ndarray):
+            host = np.ascontiguousarray(samples[0])
+            keep.append(host)
+            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(samples[1]), 0, tuple(int(n) for n in samples[2])
+        elif isinstance(samples, tuple):
+            ptr, code, on_device, shape = ctypes.c_void_p(int(samples[0])), dtype_code(samples[1]), 1, tuple(int(n) for n in samples[2])
+        else:
+            host = native_array(samples)
+            keep.append(host)
+            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
+        assert len(shape) == 3, "3-D sample array expected"
+        if download:
+            n = self.shape if samples is None else shape
+            if n is None:
+                raise CxError(CX_ERR_STATE, "label_grid: no samples given and no grid bound")
+            host_out = np.empty(n, dtype=np.int32)
+        k = ctypes.c_int64()
+        self._check(self.lib.cx_grid_label3d(self.handle, ptr, code, on_device, shape[0], shape[1], shape[2], float(value),
+                                             LABEL_SIDES[side], int(connectivity), ctypes.c_void_p(int(out)) if out else None,
+                                             host_out.ctypes.data if download else None, ctypes.addressof(k)))
+        if download:
+            return int(k.value), host_out
+        return int(k.value), (int(out) if out else self.label_result()[1])
+
+    def label_result(self):
+        "(shape, device pointer, side name, connectivity, K) of the labels the last label_grid left in the context (cx_grid_label3d_result)"
+        p, m, side, conn, k = ctypes.c_void_p(), np.zeros(3, dtype=np.int64), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64()
+        self._check(self.lib.cx_grid_label3d_result(self.handle, ctypes.byref(p), m.ctypes.data, ctypes.byref(side), ctypes.byref(conn), ctypes.byref(k)))
+        names = {v: n for n, v in LABEL_SIDES.items()}
+        return tuple(int(x) for x in m), int(p.value or 0), names[int(side.value)], int(conn.value), int(k.value)
+
+    def label_measures(self):
+        "one record (LABEL_COMPONENT_DTYPE) per component of the labels in the context, record c - 1 for label c (cx_grid_label3d_measures)"
+        k = self.label_result()[4]
+        out = np.zeros(k, dtype=LABEL_COMPONENT_DTYPE)
+        self._check(self.lib.cx_grid_label3d_measures(self.handle, out.ctypes.data if k else None, k))
+        return out
+
+    def label_select(self, keep, out=None, download=False):
+        """uint8 mask, 1 where keep[label] is set (cx_grid_label3d_select) -> (number of ones, the mask).  keep: K + 1 flags indexed by
+        label, keep[0] for the samples without one.  out: None = the mask stays in the context (label_mask_result, bind_label_mask); or
+        a device pointer to room for it.  The mask: a numpy array with download=True, else its device pointer."""
+        flags = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8).reshape(-1)
+        if download:
+            host_out = np.empty(self.label_result()[0], dtype=np.uint8)
+        n = ctypes.c_int64()
+        self._check(self.lib.cx_grid_label3d_select(self.handle, flags.ctypes.data, len(flags), ctypes.c_void_p(int(out)) if out else None,
+                                                    host_out.ctypes.data if download else None, ctypes.addressof(n)))
+        if download:
+            return int(n.value), host_out
+        return int(n.value), (int(out) if out else self.label_mask_result()[1])
+
+    def label_mask_result(self):
+        "(shape, device pointer, number of ones) of the mask the last label_select left in the context (cx_grid_label3d_select_result)"
+        p, m, n = ctypes.c_void_p(), np.zeros(3, dtype=np.int64), ctypes.c_int64()
+        self._check(self.lib.cx_grid_label3d_select_result(self.handle, ctypes.byref(p), m.ctypes.data, ctypes.byref(n)))
+        return tuple(int(x) for x in m), int(p.value or 0), int(n.value)
+
+    def bind_label_mask(self):
+        "the mask the last label_select left in the context becomes the bound grid (uint8, owned by the context): cx_grid_label3d_bind"
+        shape = self.label_mask_result()[0]
+        self._check(self.lib.cx_grid_label3d_bind(self.handle))
         self.shape = shape
         self._keep = None
 

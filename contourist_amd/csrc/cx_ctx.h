@@ -185,6 +185,10 @@ struct cx_ctx {
     // distance fields (cx_dist.hip): the device copy of host samples, the signed squared distances between the passes, and the context's
     // own result until cx_grid_distance3d_bind makes it the bound grid: a slot of its own, beside the filter's
     struct cx_dist_state* dist = nullptr;
+    // connected components of a thresholded volume (cx_label.hip): the device copy of host samples, the labels (pending until the next
+    // cx_grid_label3d), their records, and the mask of cx_grid_label3d_select until cx_grid_label3d_bind makes it the bound grid: a slot
+    // of its own, beside the filter's and the distance transform's
+    struct cx_label_state* label = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -372,6 +376,8 @@ void cx_pick_free(cx_ctx* ctx);
 void cx_filter_free(cx_ctx* ctx);
 // cx_dist.hip
 void cx_dist_free(cx_ctx* ctx);
+// cx_label.hip
+void cx_label_free(cx_ctx* ctx);
 bool cx_level1_capped(cx_ctx* ctx);   // cx_post.hip: the Level-1 mesh came out of cx_postprocess3d_capped (or is a filtered copy of one)
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);

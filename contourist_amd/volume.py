@@ -292,3 +292,125 @@ def closed(samples, value, radius, sampling=None, device=None):
     first one's mask where it lies on the device, thresholded at 0.5.  Sampling and lattice as in `dilate`."""
     r2 = _radius2(radius)
     return _inverted(_distance_steps([(value, "below", "mask", r2, sampling), (0.5, "above", "mask", r2, sampling)], device, _distance_samples(samples)))
+
+
+
+# ---- connected components (cx_grid_label3d, csrc/cx_label.hip) -----------------------------------------------------------------------
+# The objects of the thresholded volume: labels numbered by the linear index of each component's first sample (scipy.ndimage.label's
+# own numbering), one record of exact integers per component, and masks chosen by label.  tests/label_ref.py restates it in numpy and
+# the device result equals it exactly.  A result's lattice is the samples' own: the same (mins, delta), `lattice_of(mins, delta)` with
+# no weights.
+
+def _label_samples(samples):
+    "-> (on_device, the samples in a type the kernels read, their shape, the shape padded to three axes, the argument of label_grid)"
+    on_device, s, shape = _distance_samples(samples)
+    ndim = len(shape)
+    assert 1 <= ndim <= 3, "samples of 1 to 3 dimensions"
+    shape3 = (1,) * (3 - ndim) + shape
+    if on_device:
+        import torch
+        torch.cuda.current_stream(s.device).synchronize()      # the samples are there; the context has a stream of its own
+        return True, s, shape, shape3, (s.data_ptr(), s.dtype, shape3)
+    return False, s, shape, shape3, s.reshape(shape3)
+
+
+def _device_view(ptr, shape, typestr, device):
+    "a tensor over device memory of the context's (no copy): valid as long as that buffer is"
+    import torch
+
+    class _View(object):
+        def __init__(self):
+            self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
+    return torch.as_tensor(_View(), device=device)
+
+
+def label(samples, value, side="high", connectivity=1, measures=False, device=None):
+    """scipy.ndimage.label of the thresholded samples -> (labels int32, K), with measures=True (labels, K, records).
+    side "high": the samples with f >= value (and the NaNs) are labelled; "low": those with f < value.  connectivity 1, 2, 3: 6, 18 or
+    26 neighbours in three dimensions (offsets that differ on at most `connectivity` axes).  Labels are 1..K in the order of each
+    component's first sample in C order, 0 elsewhere.  records: one `_ffi.LABEL_COMPONENT_DTYPE` per component, record c - 1 for label
+    c: voxels, first, sum, lo, hi, rim over the three axes of the padded shape (missing leading axes have length 1).
+    Samples: a numpy array (a numpy array comes back) or a contiguous GPU tensor (a tensor comes back) of 1 to 3 dimensions; bool
+    samples count as 0 and 1."""
+    on_device, s, shape, shape3, arg = _label_samples(samples)
+    if not on_device:
+        context = _context(device)
+        k, labels = context.label_grid(value, side, connectivity, samples=arg, download=True)
+        labels = labels.reshape(shape)
+    else:
+        import torch
+        context = _context(s.device.index if device is None else device)
+        if measures:      # the records describe labels the context holds: those are copied once on the device
+            k, ptr = context.label_grid(value, side, connectivity, samples=arg)
+            labels = _device_view(ptr, shape, "<i4", s.device).clone()
+            torch.cuda.current_stream(s.device).synchronize()      # (the context's buffer is free for its next call)
+        else:
+            labels = torch.empty(shape3, dtype=torch.int32, device=s.device)
+            k, _ = context.label_grid(value, side, connectivity, samples=arg, out=labels.data_ptr())
+            labels = labels.reshape(shape)
+    return (labels, k, context.label_measures()) if measures else (labels, k)
+
+
+def _selected(context, on_device, s, shape, shape3, keep):
+    "the mask of the labels the context holds: a tensor beside the samples `s`, or a numpy array"
+    if on_device:
+        import torch
+        out = torch.empty(shape3, dtype=torch.uint8, device=s.device)
+        context.label_select(keep, out=out.data_ptr())
+        return out.reshape(shape)
+    return context.label_select(keep, download=True)[1].reshape(shape)
+
+
+def keep_components(samples, value, side="high", connectivity=1, largest=None, min_voxels=None, rim=None, keep=None, device=None):
+    """uint8 mask of the components of `label(samples, value, side, connectivity)` that pass every criterion given:
+    min_voxels=n: at least n voxels; rim=True / False: only components that touch / do not touch the array's rim (on an axis of the
+    samples; padded leading axes do not count); keep: a bool array over the labels 1..K, or a callable that gets the records and
+    returns one; largest=k, applied last: of what is left, the k components with the most voxels, ties going to the smaller label.
+    The criteria are evaluated on the host from the records (K of them); the labels and the mask never leave the device for a tensor."""
+    on_device, s, shape, shape3, arg = _label_samples(samples)
+    context = _context((s.device.index if on_device else None) if device is None else device)
+    k, _ = context.label_grid(value, side, connectivity, samples=arg)
+    records = context.label_measures()
+    ok = np.ones(k, dtype=bool)
+    if min_voxels is not None:
+        ok &= records["voxels"] >= int(min_voxels)
+    if rim is not None:
+        real = 0
+        for axis in range(3 - len(shape), 3):
+            real |= 3 << (2 * axis)
+        touches = (records["rim"] & np.uint32(real)) != 0
+        ok &= touches if rim else ~touches
+    if keep is not None:
+        flags = np.asarray(keep(records) if callable(keep) else keep).astype(bool).reshape(-1)
+        assert len(flags) == k, "keep: one flag per component (%d)" % k
+        ok &= flags
+    if largest is not None:
+        cand = np.flatnonzero(ok)
+        order = cand[np.argsort(-records["voxels"][cand], kind="stable")]      # stable: the smaller label first among equals
+        ok = np.zeros(k, dtype=bool)
+        ok[order[:max(0, int(largest))]] = True
+    return _selected(context, on_device, s, shape, shape3, np.concatenate([[False], ok]))
+
+
+def remove_small(samples, value, min_voxels, connectivity=1, device=None):
+    "the set {f >= value} without its components of fewer than `min_voxels` voxels: uint8"
+    return keep_components(samples, value, "high", connectivity, min_voxels=min_voxels, device=device)
+
+
+def clear_border(samples, value, connectivity=1, device=None):
+    "the set {f >= value} without the components that touch the array's rim (skimage.segmentation.clear_border): uint8"
+    return keep_components(samples, value, "high", connectivity, rim=False, device=device)
+
+
+def fill_holes(samples, value, connectivity=1, device=None):
+    """the set {f >= value} united with the components of {f < value}, labelled with `connectivity`, that do not touch the array's rim:
+    uint8.  scipy.ndimage.binary_fill_holes(f >= value, generate_binary_structure(3, connectivity))."""
+    on_device, s, shape, shape3, arg = _label_samples(samples)
+    context = _context((s.device.index if on_device else None) if device is None else device)
+    k, _ = context.label_grid(value, "low", connectivity, samples=arg)
+    records = context.label_measures()
+    real = 0
+    for axis in range(3 - len(shape), 3):
+        real |= 3 << (2 * axis)
+    enclosed = (records["rim"] & np.uint32(real)) == 0
+    return _selected(context, on_device, s, shape, shape3, np.concatenate([[True], enclosed]))

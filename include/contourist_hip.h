@@ -774,6 +774,71 @@ int cx_grid_distance3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_d
 int cx_grid_distance3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_kind, int64_t* n_sites);
 int cx_grid_distance3d_bind(cx_ctx* ctx);
 
+/* ---- labels: the connected components of a thresholded volume, on the device -----------------------------------------------------------
+ * What a caller with a segmented volume ran scipy.ndimage.label for, and what follows from it: voxel counts, boxes and centroids per
+ * component, "keep the largest object", "remove the specks", "fill the enclosed holes", "drop what touches the rim".  The reference has
+ * no call for it.  (The components of the Level-1 MESH are another matter: a solid with a cavity is one voxel object and two surfaces.)
+ *
+ * cx_grid_label3d
+ *   samples, dtype, on_device, n0 n1 n2: as in cx_grid_distance3d.  NULL: the bound 3-D grid in its own type (CX_ERR_STATE without one);
+ *            else a host or device pointer of any CX_DTYPE_*, every axis >= 1, at most 2^29 samples.  The pointer
+ *            cx_grid_label3d_select_result handed out is a legal input (CX_DTYPE_U8, on the device).
+ *   value    a sample f is LOW iff (double)f < value; a NaN is never low.  This is the march's own classification.
+ *   side     CX_LABEL_HIGH: the samples that are not low are labelled.  CX_LABEL_LOW: the low ones are.
+ *   connectivity  1, 2 or 3: two labelled samples are neighbours when their index offsets are each in {-1, 0, 1} and differ from 0 on
+ *            at most `connectivity` axes: 6, 18 or 26 neighbours, scipy's generate_binary_structure(3, connectivity).  Neighbours
+ *            never wrap: the last sample of a row and the first of the next row are not neighbours, nor are those of two planes.
+ *   The result: n0 n1 n2 int32 labels, 0 on the samples that are not labelled, else 1 .. K.  Components are numbered by the linear
+ *   index (C order) of their first sample: component 1 holds the labelled sample with the smallest linear index, component c + 1 the
+ *   smallest one that is in none of 1 .. c.  This is scipy.ndimage.label's own numbering, and it makes the labels a pure function of
+ *   the inputs: no order of unions can show in them.
+ *   out_device  not NULL: the labels are written there (device memory of the caller, aligned to 4; CX_ERR_INVALID if it overlaps the
+ *            input), and the context keeps no result.  NULL: they go into a buffer the context owns (counted by cx_device_bytes, reused
+ *            by the next call) and stay pending until the next cx_grid_label3d.  The slot is the labels' own: cx_grid_filter3d,
+ *            cx_grid_distance3d and this call do not disturb each other's pending results.
+ *   out_host    not NULL: also receives a copy.   n_components (may be NULL): K.  The call returns after the stream has run it.
+ *   CX_ERR_INVALID: a NaN or infinite value, an unknown side, connectivity or sample type, a shape outside its range.
+ * cx_grid_label3d_result: the pending labels: device pointer, shape, side, connectivity and K; CX_ERR_STATE when none are pending.
+ * cx_grid_label3d_measures: one cx_label_component per component of the pending labels, record c - 1 for label c, computed on the
+ *   first request.  Every field is an exact integer:
+ *     voxels   the number of samples of the component          first    its smallest linear index
+ *     sum[a]   the sum of its samples' indices along axis a (the centroid is sum / voxels)
+ *     lo[a], hi[a]  the smallest and largest index along axis a (its box, both ends included)
+ *     rim      bit 2a set: the component has a sample at index 0 of axis a; bit 2a + 1: one at index n_a - 1
+ *     reserved 0
+ *   CX_ERR_STATE when no labels are pending, CX_ERR_INVALID when capacity < K; K == 0 is served with any capacity.  Integer atomics
+ *   only: two calls give the same bytes.
+ * cx_grid_label3d_select: keep is n_keep == K + 1 host bytes indexed by label, keep[0] for the samples without one; the result is a
+ *   uint8 mask, 1 where keep[label] != 0, written to out_device (memory of the caller; CX_ERR_INVALID if it overlaps the labels) or,
+ *   out_device NULL, into a second buffer of the label state, where it stays pending until the next select or cx_grid_label3d_bind.
+ *   out_host also receives a copy; n_voxels (may be NULL) the exact count of ones.  CX_ERR_STATE without pending labels,
+ *   CX_ERR_INVALID for another n_keep.
+ * cx_grid_label3d_select_result: the pending mask: device pointer, shape and count; CX_ERR_STATE when none is pending.  The pointer is a
+ *   legal `samples` of cx_grid_distance3d and of cx_grid_label3d (CX_DTYPE_U8, on the device).
+ * cx_grid_label3d_bind: the pending mask becomes the bound grid (CX_DTYPE_U8, owned by the context) with every reset of an upload, as
+ *   cx_grid_distance3d_bind does it.  CX_ERR_INVALID, the mask left pending, for an axis shorter than 2; CX_ERR_STATE without a pending
+ *   mask.  The labels stay pending: only a later cx_grid_label3d replaces them.
+ * A call without bind leaves the bound grid, the current extraction, the selected level, the Level-1 state, the cap and the filter's
+ * and the distance transform's pending results as they are.  tests/label_ref.py restates all of it in numpy. */
+#define CX_LABEL_HIGH 0
+#define CX_LABEL_LOW  1
+typedef struct cx_label_component {
+    int64_t voxels;
+    int64_t first;
+    int64_t sum[3];
+    int32_t lo[3];
+    int32_t hi[3];
+    uint32_t rim;
+    uint32_t reserved;
+} cx_label_component;      /* 72 bytes */
+int cx_grid_label3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                    double value, int32_t side, int32_t connectivity, int32_t* out_device, int32_t* out_host, int64_t* n_components);
+int cx_grid_label3d_result(cx_ctx* ctx, int32_t** labels_device, int64_t shape[3], int32_t* side, int32_t* connectivity, int64_t* n_components);
+int cx_grid_label3d_measures(cx_ctx* ctx, cx_label_component* out_host, int64_t capacity);
+int cx_grid_label3d_select(cx_ctx* ctx, const uint8_t* keep, int64_t n_keep, uint8_t* out_device, uint8_t* out_host, int64_t* n_voxels);
+int cx_grid_label3d_select_result(cx_ctx* ctx, uint8_t** mask_device, int64_t shape[3], int64_t* n_voxels);
+int cx_grid_label3d_bind(cx_ctx* ctx);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
