@@ -86,6 +86,7 @@ SYMBOLS = [
     "cx_grid_filter3d", "cx_grid_filter3d_result", "cx_grid_filter3d_bind",
     "cx_grid_distance3d", "cx_grid_distance3d_result", "cx_grid_distance3d_bind",
     "cx_grid_label3d", "cx_grid_label3d_result", "cx_grid_label3d_measures", "cx_grid_label3d_select", "cx_grid_label3d_select_result", "cx_grid_label3d_bind",
+    "cx_grid_resample3d", "cx_grid_resample3d_result", "cx_grid_resample3d_bind",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -313,6 +314,9 @@ def load():
         "cx_grid_label3d_select": [vp, vp, i64, vp, vp, vp],
         "cx_grid_label3d_select_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int64)],
         "cx_grid_label3d_bind": [vp],
+        "cx_grid_resample3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, dbl, vp, vp, vp],
+        "cx_grid_resample3d_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)],
+        "cx_grid_resample3d_bind": [vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -778,6 +782,60 @@ class Context(object):
         "the mask the last label_select left in the context becomes the bound grid (uint8, owned by the context): cx_grid_label3d_bind"
         shape = self.label_mask_result()[0]
         self._check(self.lib.cx_grid_label3d_bind(self.handle))
+        self.shape = shape
+        self._keep = None
+
+    def resample_grid(self, matrix, offset, out_shape, order=1, mode="nearest", cval=0.0, samples=None, out=None, download=False):
+        """the samples read through the affine index map c = offset + matrix @ i (cx_grid_resample3d) -> (n_outside, the result).
+        matrix: 3 x 3, output index to input index (scipy.ndimage.affine_transform's convention); offset: 3; out_shape: 3.
+        order 0: the nearest sample in the input's own type; order 1: trilinear, float32.  mode: a name of FILTER_MODES.
+        samples: as in filter_grid (None = the bound grid, a 3-D numpy array, (device pointer, dtype, shape), (numpy array, dtype, shape)).
+        out: None = the result stays in the context (resample_result, bind_resampled); or a device pointer to room for the result.
+        The result: a numpy array with download=True (bfloat16 samples at order 0 come back as their uint16 bit patterns), else its
+        device pointer.  n_outside: the output samples whose source coordinate lies off the array on some axis."""
+        keep = []
+        if samples is None:
+            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
+        elif isinstance(samples, tuple) and isinstance(samples[0], np.ndarray):
+            host = np.ascontiguousarray(samples[0])
+            keep.append(host)
+            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(samples[1]), 0, tuple(int(n) for n in samples[2])
+        elif isinstance(samples, tuple):
+            ptr, code, on_device, shape = ctypes.c_void_p(int(samples[0])), dtype_code(samples[1]), 1, tuple(int(n) for n in samples[2])
+        else:
+            host = native_array(samples)
+            keep.append(host)
+            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
+        assert len(shape) == 3, "3-D sample array expected"
+        mat = np.ascontiguousarray(matrix, dtype=np.float64).reshape(3, 3)
+        off = np.ascontiguousarray(offset, dtype=np.float64).reshape(3)
+        m = np.ascontiguousarray(out_shape, dtype=np.int64).reshape(3)
+        if download:
+            if samples is None:
+                if self.shape is None:
+                    raise CxError(CX_ERR_STATE, "resample_grid: no samples given and no grid bound")
+                code = DTYPE_CODES[self.grid_info()["dtype"]]
+            name = DTYPE_NAMES.get(code, "float32") if int(order) == 0 else "float32"
+            host_out = np.empty([max(0, int(x)) for x in m], dtype=np.uint16 if name == "bfloat16" else np.dtype(name))
+        n_outside = ctypes.c_int64()
+        self._check(self.lib.cx_grid_resample3d(self.handle, ptr, code, on_device, shape[0], shape[1], shape[2], mat.ctypes.data, off.ctypes.data,
+                                                m.ctypes.data, int(order), FILTER_MODES[mode], float(cval), ctypes.c_void_p(int(out)) if out else None,
+                                                host_out.ctypes.data if download else None, ctypes.addressof(n_outside)))
+        if download:
+            return int(n_outside.value), host_out
+        return int(n_outside.value), (int(out) if out else self.resample_result()[1])
+
+    def resample_result(self):
+        "(shape, device pointer, dtype name, n_outside) of the result the last resample_grid left in the context (cx_grid_resample3d_result)"
+        p, m, code, n_outside = ctypes.c_void_p(), np.zeros(3, dtype=np.int64), ctypes.c_int32(), ctypes.c_int64()
+        self._check(self.lib.cx_grid_resample3d_result(self.handle, ctypes.byref(p), m.ctypes.data, ctypes.byref(code), ctypes.byref(n_outside)))
+        return tuple(int(x) for x in m), int(p.value or 0), DTYPE_NAMES[int(code.value)], int(n_outside.value)
+
+    def bind_resampled(self):
+        """the result the last resample_grid left in the context becomes the bound grid (float32 for order 1, the input's type for order 0,
+        owned by the context): cx_grid_resample3d_bind"""
+        shape = self.resample_result()[0]
+        self._check(self.lib.cx_grid_resample3d_bind(self.handle))
         self.shape = shape
         self._keep = None
 

@@ -189,6 +189,9 @@ struct cx_ctx {
     // cx_grid_label3d), their records, and the mask of cx_grid_label3d_select until cx_grid_label3d_bind makes it the bound grid: a slot
     // of its own, beside the filter's and the distance transform's
     struct cx_label_state* label = nullptr;
+    // resampling through an affine map (cx_resample.hip): the device copy of host samples, the table of the axis-aligned kernel, and the
+    // context's own result until cx_grid_resample3d_bind makes it the bound grid: a slot of its own, beside the other three
+    struct cx_resample_state* resample = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -378,6 +381,8 @@ void cx_filter_free(cx_ctx* ctx);
 void cx_dist_free(cx_ctx* ctx);
 // cx_label.hip
 void cx_label_free(cx_ctx* ctx);
+// cx_resample.hip
+void cx_resample_free(cx_ctx* ctx);
 bool cx_level1_capped(cx_ctx* ctx);   // cx_post.hip: the Level-1 mesh came out of cx_postprocess3d_capped (or is a filtered copy of one)
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);

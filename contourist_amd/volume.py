@@ -414,3 +414,172 @@ def fill_holes(samples, value, connectivity=1, device=None):
         real |= 3 << (2 * axis)
     enclosed = (records["rim"] & np.uint32(real)) == 0
     return _selected(context, on_device, s, shape, shape3, np.concatenate([[True], enclosed]))
+
+
+# ---- resampling through an affine map (cx_grid_resample3d, csrc/cx_resample.hip) ------------------------------------------------------
+# out[i] = f(offset + matrix @ i): the matrix maps the OUTPUT index to the INPUT index, scipy.ndimage.affine_transform's convention,
+# computed in float64 with every product and sum rounded on its own.  order 0 reads the nearest sample, floor(c + 0.5), in the samples'
+# own type; order 1 blends the eight corners around floor(c) in float64 (input axis 2 first, then 1, then 0) and rounds to float32 once.
+# Modes "nearest", "reflect" and "constant" are scipy's 'nearest', 'reflect' and 'grid-constant'.  tests/resample_ref.py restates it in
+# numpy and the device result equals it bit for bit.
+
+def _map3(matrix, offset, ndim):
+    "(matrix, offset) of an array of `ndim` axes -> the 3 x 3 matrix and 3-vector of the array padded with leading axes of length 1"
+    M = np.asarray(matrix, dtype=np.float64)
+    if M.ndim == 0:
+        M = np.full(ndim, float(M))
+    if M.ndim == 1:
+        assert len(M) in (ndim, 3), "matrix: a vector of one factor per axis of the samples (%d)" % ndim
+        M = np.diag(M)
+    assert M.shape in ((ndim, ndim), (3, 3)), "matrix: %d x %d or 3 x 3" % (ndim, ndim)
+    off = np.asarray(offset, dtype=np.float64)
+    if off.ndim == 0:
+        off = np.full(M.shape[0], float(off))
+    off = off.reshape(-1)
+    assert len(off) == M.shape[0], "offset: one value or one per row of the matrix"
+    M3, off3 = np.eye(3), np.zeros(3)
+    k = 3 - M.shape[0]
+    M3[k:, k:] = M
+    off3[k:] = off
+    return M3, off3
+
+
+def resample(samples, matrix, offset=0, output_shape=None, order=1, mode="nearest", cval=0.0, device=None, return_outside=False):
+    """scipy.ndimage.affine_transform(samples, matrix, offset, output_shape, order=order) for order 0 and 1.
+    matrix: 3 x 3 (ndim x ndim for samples of fewer dimensions), or a vector, which means a diagonal; offset: one value or one per
+    axis; output_shape None: the samples' shape.  order 0 returns the samples' own type, order 1 float32.
+    return_outside=True: (result, n_outside), the number of output samples whose source coordinate lies off the array on some axis.
+    Samples: a numpy array (a numpy array comes back) or a contiguous GPU tensor (a tensor comes back) of 1 to 3 dimensions."""
+    on_device, s, shape = _distance_samples(samples)
+    ndim = len(shape)
+    assert 1 <= ndim <= 3, "samples of 1 to 3 dimensions"
+    assert int(order) in (0, 1), "order 0 or 1"
+    M3, off3 = _map3(matrix, offset, ndim)
+    out_shape = shape if output_shape is None else tuple(int(n) for n in output_shape)
+    assert len(out_shape) == ndim, "output_shape: one length per axis of the samples (%d)" % ndim
+    shape3, out3 = (1,) * (3 - ndim) + shape, (1,) * (3 - ndim) + out_shape
+    if on_device:
+        import torch
+        context = _context(s.device.index if device is None else device)
+        out = torch.empty(out3, dtype=s.dtype if int(order) == 0 else torch.float32, device=s.device)
+        torch.cuda.current_stream(s.device).synchronize()      # the samples are there; the context has a stream of its own
+        n_outside, _ = context.resample_grid(M3, off3, out3, order, mode, cval, samples=(s.data_ptr(), s.dtype, shape3), out=out.data_ptr())
+        result = out.reshape(out_shape)
+    else:
+        context = _context(device)
+        n_outside, result = context.resample_grid(M3, off3, out3, order, mode, cval, samples=s.reshape(shape3), download=True)
+        result = result.reshape(out_shape)
+    return (result, n_outside) if return_outside else result
+
+
+def _corner_scale(n, m):
+    """the step d of `zoom`'s "corners": (n - 1) / (m - 1), moved by a few units in its last place where that makes the last
+    coordinate (m - 1) d, rounded as the kernel rounds it, exactly n - 1; where no such neighbour exists, the nearest step that does not
+    fall short of n - 1 (the last output then reads the last sample under "nearest" and "reflect", and counts as outside)"""
+    if m <= 1 or n <= 1:
+        return 0.0
+    last, steps = np.float64(n - 1), np.float64(m - 1)
+    d = last / steps
+    lo = hi = d
+    near = [d]
+    for _ in range(4):
+        lo, hi = np.nextafter(lo, -np.inf), np.nextafter(hi, np.inf)
+        near += [lo, hi]
+    for x in near:
+        if steps * x == last:
+            return float(x)
+    while steps * d < last:
+        d = np.nextafter(d, np.inf)
+    return float(d)
+
+
+def zoom_map(shape, factor, align="centers"):
+    "(matrix diagonal, offset, output shape) of `zoom` for samples of `shape`"
+    ndim = len(shape)
+    fac = [float(f) for f in _per_axis(factor, ndim, 1.0, "factor")[3 - ndim:]]
+    assert all(f > 0.0 and np.isfinite(f) for f in fac), "factor is a finite number > 0"
+    out = tuple(max(1, int(round(int(n) * f))) for n, f in zip(shape, fac))
+    if align == "centers":
+        diag = np.asarray([1.0 / f for f in fac], dtype=np.float64)
+        return diag, 0.5 * diag - 0.5, out
+    assert align == "corners", "align: 'centers' or 'corners'"
+    return np.asarray([_corner_scale(int(n), m) for n, m in zip(shape, out)], dtype=np.float64), np.zeros(ndim), out
+
+
+def zoom(samples, factor, order=1, mode="nearest", align="centers", cval=0.0, device=None):
+    """the samples at `factor` times the resolution (one factor or one per axis): round(n * factor) samples per axis, at least 1.
+    align "centers": samples are cell centres and the array keeps its extent, c = (i + 0.5) / factor - 0.5 -- what
+    scipy.ndimage.zoom(samples, factor, order=order, mode=..., grid_mode=True) reads wherever n * factor is an integer (scipy divides
+    by the ratio of the lengths, which is the factor then), with scipy's mode 'grid-constant' for "constant".
+    align "corners": the first and last sample keep their place, c = i (n - 1) / (m - 1) -- scipy.ndimage.zoom's default
+    (grid_mode=False), the step adjusted in its last place so that the last output lands on the last sample (`_corner_scale`): the
+    corner samples are reproduced exactly under "nearest" and "reflect"."""
+    shape = tuple(int(n) for n in samples.shape)
+    diag, off, out = zoom_map(shape, factor, align)
+    return resample(samples, diag, off, out, order, mode, cval, device)
+
+
+def regrid_map(mins, delta, like_shape, like_mins, like_delta, rotation=None):
+    """(matrix, offset) in float64 that take an index of the lattice (like_mins, like_delta) of `like_shape` to the index of the same
+    world point on the lattice (mins, delta); rotation: the world point is first turned by this matrix about the target lattice's centre"""
+    ndim = len(like_shape)
+    mins = np.asarray(mins, dtype=np.float64).reshape(ndim)
+    like_mins = np.asarray(like_mins, dtype=np.float64).reshape(ndim)
+    delta = np.asarray(delta, dtype=np.float64) * np.ones(ndim)
+    like_delta = np.asarray(like_delta, dtype=np.float64) * np.ones(ndim)
+    assert np.all(delta != 0.0) and np.all(like_delta != 0.0), "a lattice step of 0"
+    R = np.eye(ndim) if rotation is None else np.asarray(rotation, dtype=np.float64).reshape(ndim, ndim)
+    centre = like_mins + like_delta * (np.asarray(like_shape, dtype=np.float64) - 1.0) / 2.0
+    # world x = like_mins + like_delta i;  turned: centre + R (x - centre);  source index: (that - mins) / delta
+    matrix = (R * like_delta[None, :]) / delta[:, None]
+    offset = (centre + R @ (like_mins - centre) - mins) / delta
+    return matrix, offset
+
+
+def regrid(samples, mins, delta, like_shape, like_mins, like_delta, rotation=None, order=1, mode="constant", cval=0.0, device=None,
+           return_map=False, return_outside=False):
+    """the samples of the lattice (mins, delta) on the lattice (like_mins, like_delta) of `like_shape`: what makes a second volume a
+    legal `field` of vertex_values and clip beside a marched volume of that shape.  rotation: an optional world rotation (ndim x ndim)
+    about the target lattice's centre.  Matrix and offset are computed in float64 on the host (`regrid_map`).
+    -> the result; with return_outside (result, n_outside); with return_map the matrix and the offset follow."""
+    matrix, offset = regrid_map(mins, delta, like_shape, like_mins, like_delta, rotation)
+    result, n_outside = resample(samples, matrix, offset, tuple(int(n) for n in like_shape), order, mode, cval, device, return_outside=True)
+    out = (result, n_outside) if return_outside else (result,)
+    if return_map:
+        out = out + (matrix, offset)
+    return out[0] if len(out) == 1 else out
+
+
+def reslice(samples, origin, u, v, shape, order=1, mode="constant", cval=0.0, device=None, return_outside=False):
+    """one oblique plane of a 3-D volume: the image out[i, j] = f(origin + i u + j v), origin, u and v in index coordinates of the
+    samples, `shape` the image's (rows, columns)."""
+    assert len(samples.shape) == 3, "reslice: a 3-D volume"
+    matrix = np.zeros((3, 3))
+    matrix[:, 1] = np.asarray(u, dtype=np.float64).reshape(3)
+    matrix[:, 2] = np.asarray(v, dtype=np.float64).reshape(3)
+    out = resample(samples, matrix, np.asarray(origin, dtype=np.float64).reshape(3), (1, int(shape[0]), int(shape[1])), order, mode, cval,
+                   device, return_outside=True)
+    image = out[0].reshape(int(shape[0]), int(shape[1]))
+    return (image, out[1]) if return_outside else image
+
+
+def lattice_after(mins, delta, matrix, offset):
+    """world (mins, delta) of the result of `resample`, per axis of the RESULT, when the map is a scaled permutation (zoom, crop,
+    regrid without rotation, flip, transpose): result axis k runs along the samples' axis a with M[a][k] != 0, from
+    mins[a] + delta[a] offset[a] in steps of delta[a] M[a][k] (negative after a flip).  Asserts for any other matrix."""
+    mins = np.asarray(mins, dtype=np.float64).reshape(-1)
+    ndim = len(mins)
+    delta = np.asarray(delta, dtype=np.float64) * np.ones(ndim)
+    M = np.asarray(matrix, dtype=np.float64)
+    if M.ndim < 2:
+        M = np.diag(M * np.ones(ndim))
+    off = np.asarray(offset, dtype=np.float64) * np.ones(ndim)
+    assert M.shape == (ndim, ndim), "matrix: %d x %d" % (ndim, ndim)
+    nz = M != 0.0
+    assert np.all(nz.sum(axis=0) == 1) and np.all(nz.sum(axis=1) == 1), "lattice_after: the matrix is not a scaled permutation"
+    new_mins, new_delta = np.zeros(ndim), np.zeros(ndim)
+    for a in range(ndim):
+        k = int(np.flatnonzero(nz[a])[0])
+        new_mins[k] = mins[a] + delta[a] * off[a]
+        new_delta[k] = delta[a] * M[a, k]
+    return new_mins, new_delta

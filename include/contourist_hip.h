@@ -839,6 +839,54 @@ int cx_grid_label3d_select(cx_ctx* ctx, const uint8_t* keep, int64_t n_keep, uin
 int cx_grid_label3d_select_result(cx_ctx* ctx, uint8_t** mask_device, int64_t shape[3], int64_t* n_voxels);
 int cx_grid_label3d_bind(cx_ctx* ctx);
 
+/* ---- resampling through an affine map: regrid, zoom, reslice, on the device ----------------------------------------------------------
+ * What a caller ran scipy.ndimage.affine_transform or zoom for: a second volume on the marched volume's lattice, anisotropic voxels made
+ * isotropic, a scan rotated into a registered frame, one oblique plane of samples.  The reference has no call for it.
+ *
+ * cx_grid_resample3d
+ *   samples, dtype, on_device, n0 n1 n2: as in cx_grid_filter3d.  NULL: the bound 3-D grid in its own type (CX_ERR_STATE without one);
+ *            else a host or device pointer of any CX_DTYPE_*, every axis >= 1, at most 2^31 samples.  The pointer
+ *            cx_grid_resample3d_result handed out is a legal input: that result is consumed, the new one takes its place.
+ *   matrix   9 doubles M[a][k] = matrix[3 a + k], offset 3 doubles, each finite and at most 2^20 in magnitude.  The matrix maps the
+ *            OUTPUT index to the INPUT index (scipy.ndimage.affine_transform's convention).
+ *   out_shape  m0 m1 m2, each >= 1, at most 2^31 samples in all.
+ *   For the output index i0 i1 i2 the source coordinate on input axis a is
+ *       c_a = ((offset[a] + M[a][0] i0) + M[a][1] i1) + M[a][2] i2
+ *   in double, every product and every sum rounded on its own: no fused multiply-add (a product of two doubles is not exact, so
+ *   contraction would change bits).  With the bound on the entries every floor of c fits an int64 and c - floor c is exact.
+ *   src is the boundary rule of `mode` per index, as in cx_grid_filter3d: CX_FILTER_NEAREST clamps, CX_FILTER_REFLECT takes p = j mod 2n
+ *   and reads p < n ? p : 2n-1-p, CX_FILTER_CONSTANT reads cval when any of the three indices is outside.  These are scipy's 'nearest',
+ *   'reflect' and 'grid-constant' (scipy's plain 'constant' is another rule and is not offered).
+ *   order 0  j_a = floor(c_a + 0.5); the output is the sample at src of j in the input's own type, its bytes copied (a mask or a label
+ *            volume stays what it is).  cval must be a value of that type (CX_ERR_INVALID otherwise).
+ *   order 1  trilinear: lo_a = floor(c_a), t_a = c_a - lo_a; the corner samples s[d0][d1][d2] at src of lo_a + d_a are widened to double
+ *            (under CX_FILTER_CONSTANT the fill is (double)(float)cval); lerp(a, b, t) = (t == 0) ? a : a + t * (b - a), each operation
+ *            rounded on its own; input axis 2 is reduced first (four lerps with t_2), then axis 1 (two), then axis 0 (one); the result
+ *            is rounded to fp32 once.  The output is CX_DTYPE_F32.  With t == 0 the high corner does not enter, so an identity map
+ *            reproduces infinite samples.
+ *   n_outside  (may be NULL) the number of output samples with some c_a < 0 or c_a > n_a - 1: how much of the result is boundary rule
+ *            and not data.  An exact integer, the same in every call.  The call returns after the stream has run it.
+ *   out_device  not NULL: the m0 m1 m2 values are written there (device memory of the caller, aligned to the output type;
+ *            CX_ERR_INVALID if it overlaps the input), and the context keeps no result.  NULL: the result goes into a buffer the context
+ *            owns (counted by cx_device_bytes, reused by the next call) and stays pending until the next cx_grid_resample3d or
+ *            cx_grid_resample3d_bind.  The slot is this call's own: cx_grid_filter3d, cx_grid_distance3d, cx_grid_label3d and this call
+ *            do not disturb each other's pending results, and the pending pointer is a legal `samples` of all four.
+ *   out_host    not NULL: also receives a copy.
+ *   CX_ERR_INVALID: an unknown order, mode or sample type, a NaN or infinite cval, a matrix or offset entry that is not finite or
+ *   exceeds 2^20 in magnitude, a shape outside its range.
+ * cx_grid_resample3d_result: the pending result: device pointer, shape, its CX_DTYPE_* and n_outside; CX_ERR_STATE when none is pending.
+ * cx_grid_resample3d_bind: the pending result becomes the bound grid -- CX_DTYPE_F32 for order 1, the input's own type for order 0, owned
+ *   by the context -- with every reset of an upload, as cx_grid_filter3d_bind does it.  A result the march does not take (an axis
+ *   shorter than 2, more than 2^29 samples) is refused as an upload of that shape is, and stays pending.  CX_ERR_STATE when nothing is
+ *   pending.
+ * A call without bind leaves the bound grid, the current extraction, the selected level and the Level-1 state as they are.  The only
+ * atomic is the integer add of n_outside: every call gives the same bits.  tests/resample_ref.py restates all of it in numpy. */
+int cx_grid_resample3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                       const double matrix[9], const double offset[3], const int64_t out_shape[3],
+                       int32_t order, int32_t mode, double cval, void* out_device, void* out_host, int64_t* n_outside);
+int cx_grid_resample3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_dtype, int64_t* n_outside);
+int cx_grid_resample3d_bind(cx_ctx* ctx);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
