@@ -87,6 +87,7 @@ SYMBOLS = [
     "cx_grid_distance3d", "cx_grid_distance3d_result", "cx_grid_distance3d_bind",
     "cx_grid_label3d", "cx_grid_label3d_result", "cx_grid_label3d_measures", "cx_grid_label3d_select", "cx_grid_label3d_select_result", "cx_grid_label3d_bind",
     "cx_grid_resample3d", "cx_grid_resample3d_result", "cx_grid_resample3d_bind",
+    "cx_grid_rank3d", "cx_grid_rank3d_result", "cx_grid_rank3d_bind",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -317,6 +318,9 @@ def load():
         "cx_grid_resample3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, dbl, vp, vp, vp],
         "cx_grid_resample3d_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)],
         "cx_grid_resample3d_bind": [vp],
+        "cx_grid_rank3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, dbl, vp, vp],
+        "cx_grid_rank3d_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int32)],
+        "cx_grid_rank3d_bind": [vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -836,6 +840,64 @@ class Context(object):
         owned by the context): cx_grid_resample3d_bind"""
         shape = self.resample_result()[0]
         self._check(self.lib.cx_grid_resample3d_bind(self.handle))
+        self.shape = shape
+        self._keep = None
+
+    def rank_grid(self, size, rank, footprint=None, origin=None, mode="nearest", cval=0, samples=None, out=None, download=False):
+        """the element at position `rank` of the sorted window around every sample (cx_grid_rank3d) -> (shape, the result).
+        size: the three sides of the footprint's box (or one for all), 1..7; footprint: None = the whole box, or an array of that shape, non-zero = the
+        offset belongs to it; rank: 0 .. W - 1, W the number of offsets; origin: None = size // 2 per axis (scipy's centre), or three
+        values 0 .. size - 1.  mode: a name of FILTER_MODES; cval: a value of the sample type.
+        samples: as in filter_grid (None = the bound grid, a 3-D numpy array, (device pointer, dtype, shape), (numpy array, dtype, shape)).
+        out: None = the result stays in the context (rank_result, bind_ranked); or a device pointer to room for the result.
+        The result has the samples' type: a numpy array with download=True (bfloat16 samples come back as their uint16 bit patterns),
+        else its device pointer."""
+        keep = []
+        if samples is None:
+            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
+        elif isinstance(samples, tuple) and isinstance(samples[0], np.ndarray):
+            host = np.ascontiguousarray(samples[0])
+            keep.append(host)
+            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(samples[1]), 0, tuple(int(n) for n in samples[2])
+        elif isinstance(samples, tuple):
+            ptr, code, on_device, shape = ctypes.c_void_p(int(samples[0])), dtype_code(samples[1]), 1, tuple(int(n) for n in samples[2])
+        else:
+            host = native_array(samples)
+            keep.append(host)
+            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
+        assert len(shape) == 3, "3-D sample array expected"
+        box = np.ascontiguousarray(np.broadcast_to(np.asarray(size, dtype=np.int32), (3,)))
+        og = box // 2 if origin is None else np.ascontiguousarray(origin, dtype=np.int32).reshape(3)
+        fp = None
+        if footprint is not None:
+            fp = np.ascontiguousarray(np.asarray(footprint) != 0, dtype=np.uint8)
+            assert fp.shape == tuple(int(s) for s in box), "footprint: an array of the shape `size`"
+        if samples is None:
+            if self.shape is None:
+                raise CxError(CX_ERR_STATE, "rank_grid: no samples given and no grid bound")
+            shape_out, code_out = tuple(self.shape), DTYPE_CODES[self.grid_info()["dtype"]]
+        else:
+            shape_out, code_out = shape, code
+        if download:
+            name = DTYPE_NAMES.get(code_out, "float32")
+            host_out = np.empty([max(0, int(n)) for n in shape_out], dtype=np.uint16 if name == "bfloat16" else np.dtype(name))
+        self._check(self.lib.cx_grid_rank3d(self.handle, ptr, code, on_device, shape[0], shape[1], shape[2], box.ctypes.data, og.ctypes.data,
+                                            None if fp is None else fp.ctypes.data, int(rank), FILTER_MODES[mode], float(cval),
+                                            ctypes.c_void_p(int(out)) if out else None, host_out.ctypes.data if download else None))
+        if download:
+            return shape_out, host_out
+        return shape_out, (int(out) if out else self.rank_result()[1])
+
+    def rank_result(self):
+        "(shape, device pointer, dtype name) of the result the last rank_grid left in the context (cx_grid_rank3d_result)"
+        p, m, code = ctypes.c_void_p(), np.zeros(3, dtype=np.int64), ctypes.c_int32()
+        self._check(self.lib.cx_grid_rank3d_result(self.handle, ctypes.byref(p), m.ctypes.data, ctypes.byref(code)))
+        return tuple(int(x) for x in m), int(p.value or 0), DTYPE_NAMES[int(code.value)]
+
+    def bind_ranked(self):
+        "the result the last rank_grid left in the context becomes the bound grid (the samples' own type, owned by the context): cx_grid_rank3d_bind"
+        shape = self.rank_result()[0]
+        self._check(self.lib.cx_grid_rank3d_bind(self.handle))
         self.shape = shape
         self._keep = None
 

@@ -29,6 +29,29 @@ static inline unsigned long long cx_table_size(size_t n) {
     return s;
 }
 
+// cval in the sample type, if it is a value of that type (cx_grid_resample3d at order 0, cx_grid_rank3d): its bits, zero-extended
+static inline bool cx_dtype_value_bits(int32_t dtype, double cval, uint32_t& bits) {
+    const float f = (float)cval;
+    uint32_t fb;
+    memcpy(&fb, &f, 4);
+    switch (dtype) {
+        case CX_DTYPE_U8: bits = (uint32_t)(uint8_t)cval; return cval >= 0.0 && cval <= 255.0 && (double)(uint8_t)cval == cval;
+        case CX_DTYPE_I8: bits = (uint32_t)(uint8_t)(int8_t)cval; return cval >= -128.0 && cval <= 127.0 && (double)(int8_t)cval == cval;
+        case CX_DTYPE_U16: bits = (uint32_t)(uint16_t)cval; return cval >= 0.0 && cval <= 65535.0 && (double)(uint16_t)cval == cval;
+        case CX_DTYPE_I16: bits = (uint32_t)(uint16_t)(int16_t)cval; return cval >= -32768.0 && cval <= 32767.0 && (double)(int16_t)cval == cval;
+        case CX_DTYPE_F16: {
+            if (!(cval >= -65504.0 && cval <= 65504.0)) return false;
+            const _Float16 h = (_Float16)cval;
+            uint16_t hb;
+            memcpy(&hb, &h, 2);
+            bits = hb;
+            return (double)h == cval;
+        }
+        case CX_DTYPE_BF16: bits = fb >> 16; return (double)f == cval && (fb & 0xFFFFu) == 0u;
+        default: bits = fb; return (double)f == cval;
+    }
+}
+
 struct cx_post_state;  // Level-1 buffers (cx_post.h)
 struct cx_state4;       // 4-D march state (cx_api4d.hip)
 struct cx_state2;       // 2-D contour lines (cx_contour2d.hip)
@@ -192,6 +215,9 @@ struct cx_ctx {
     // resampling through an affine map (cx_resample.hip): the device copy of host samples, the table of the axis-aligned kernel, and the
     // context's own result until cx_grid_resample3d_bind makes it the bound grid: a slot of its own, beside the other three
     struct cx_resample_state* resample = nullptr;
+    // rank filters (cx_rank.hip): the device copy of host samples and the context's own result until cx_grid_rank3d_bind makes it the
+    // bound grid: a slot of its own, beside the other four
+    struct cx_rank_state* rank = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -383,6 +409,8 @@ void cx_dist_free(cx_ctx* ctx);
 void cx_label_free(cx_ctx* ctx);
 // cx_resample.hip
 void cx_resample_free(cx_ctx* ctx);
+// cx_rank.hip
+void cx_rank_free(cx_ctx* ctx);
 bool cx_level1_capped(cx_ctx* ctx);   // cx_post.hip: the Level-1 mesh came out of cx_postprocess3d_capped (or is a filtered copy of one)
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);

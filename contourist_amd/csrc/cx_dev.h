@@ -25,6 +25,36 @@ __device__ __forceinline__ double cxd_from_orderable(u64 o) {
     return __longlong_as_double((long long)b);
 }
 
+// The same for the floats of 32 and 16 bits, NaN included: -inf < negative < -0.0 < +0.0 < positive < +inf < every NaN (one key, all
+// ones).  Unlike the keys of cx_pick.hip, which fold -0.0 onto +0.0, these have an inverse: a rank filter hands a sample back.
+// `inf`: the bits of +infinity (0x7C00 half, 0x7F80 bfloat16); `qnan`: the canonical quiet NaN the NaN key stands for
+__device__ __forceinline__ uint32_t cxd_orderable32(uint32_t u) {
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ uint32_t cxd_from_orderable32(uint32_t k) {
+    if (k == 0xFFFFFFFFu) return 0x7FC00000u;
+    return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
+}
+__device__ __forceinline__ uint32_t cxd_orderable16(uint32_t u, uint32_t inf) {
+    if ((u & 0x7FFFu) > inf) return 0xFFFFu;
+    return (u & 0x8000u) ? (~u & 0xFFFFu) : (u | 0x8000u);
+}
+__device__ __forceinline__ uint32_t cxd_from_orderable16(uint32_t k, uint32_t qnan) {
+    if (k == 0xFFFFu) return qnan;
+    return (k & 0x8000u) ? (k ^ 0x8000u) : (~k & 0xFFFFu);
+}
+
+// the boundary rule of the grid calls (cx_grid_resample3d, cx_grid_rank3d): the index read for j on an axis of n samples, -1 for cval
+__device__ __forceinline__ int32_t cxd_boundary_src(int64_t j, int64_t n, int32_t mode) {
+    if (j >= 0 && j < n) return (int32_t)j;
+    if (mode == CX_FILTER_CONSTANT) return -1;
+    if (mode == CX_FILTER_NEAREST) return j < 0 ? 0 : (int32_t)(n - 1);
+    int64_t p = j % (2 * n);
+    if (p < 0) p += 2 * n;
+    return (int32_t)(p < n ? p : 2 * n - 1 - p);
+}
+
 // monotonic maximum / minimum with a plain read first: once the running extreme is established almost every caller
 // sees that its value cannot move it and skips the atomic (same-address atomics serialise at ~88/us)
 __device__ __forceinline__ void cxd_max64(u64* addr, u64 v) {

@@ -79,16 +79,6 @@ struct cxr_args {
     unsigned long long bricks;
 };
 
-// the filter's boundary rule: the index read, -1 for cval
-__device__ __forceinline__ int32_t cxr_src(int64_t j, int64_t n, int32_t mode) {
-    if (j >= 0 && j < n) return (int32_t)j;
-    if (mode == CX_FILTER_CONSTANT) return -1;
-    if (mode == CX_FILTER_NEAREST) return j < 0 ? 0 : (int32_t)(n - 1);
-    int64_t p = j % (2 * n);
-    if (p < 0) p += 2 * n;
-    return (int32_t)(p < n ? p : 2 * n - 1 - p);
-}
-
 __device__ __forceinline__ double cxr_coord(const double (&r)[4], int64_t i0, int64_t i1, int64_t i2) {
     return ((r[0] + r[1] * (double)i0) + r[2] * (double)i1) + r[3] * (double)i2;
 }
@@ -99,14 +89,14 @@ __device__ __forceinline__ cxr_ent cxr_entry(double c, int64_t n, int32_t mode, 
     e.outside = (c < 0.0 || c > (double)(n - 1)) ? 1u : 0u;
     e.pad = 0u;
     if (order == 0) {
-        e.lo = e.hi = cxr_src((int64_t)floor(c + 0.5), n, mode);
+        e.lo = e.hi = cxd_boundary_src((int64_t)floor(c + 0.5), n, mode);
         e.t = 0.0;
     } else {
         const double f = floor(c);
         const int64_t j = (int64_t)f;
         e.t = c - f;
-        e.lo = cxr_src(j, n, mode);
-        e.hi = cxr_src(j + 1, n, mode);
+        e.lo = cxd_boundary_src(j, n, mode);
+        e.hi = cxd_boundary_src(j + 1, n, mode);
     }
     return e;
 }
@@ -215,29 +205,6 @@ static int cxr_state(cx_ctx* ctx, const char* msg) {
     return CX_ERR_STATE;
 }
 
-// cval in the sample type, if it is a value of that type
-static bool cxr_fill_bits(int32_t dtype, double cval, uint32_t& bits) {
-    const float f = (float)cval;
-    uint32_t fb;
-    memcpy(&fb, &f, 4);
-    switch (dtype) {
-        case CX_DTYPE_U8: bits = (uint32_t)(uint8_t)cval; return cval >= 0.0 && cval <= 255.0 && (double)(uint8_t)cval == cval;
-        case CX_DTYPE_I8: bits = (uint32_t)(uint8_t)(int8_t)cval; return cval >= -128.0 && cval <= 127.0 && (double)(int8_t)cval == cval;
-        case CX_DTYPE_U16: bits = (uint32_t)(uint16_t)cval; return cval >= 0.0 && cval <= 65535.0 && (double)(uint16_t)cval == cval;
-        case CX_DTYPE_I16: bits = (uint32_t)(uint16_t)(int16_t)cval; return cval >= -32768.0 && cval <= 32767.0 && (double)(int16_t)cval == cval;
-        case CX_DTYPE_F16: {
-            if (std::fabs(cval) > 65504.0) return false;
-            const _Float16 h = (_Float16)cval;
-            uint16_t hb;
-            memcpy(&hb, &h, 2);
-            bits = hb;
-            return (double)h == cval;
-        }
-        case CX_DTYPE_BF16: bits = fb >> 16; return (double)f == cval && (fb & 0xFFFFu) == 0u;
-        default: bits = fb; return (double)f == cval;
-    }
-}
-
 static int32_t cxr_ceil_log2(int64_t m) {
     int32_t l = 0;
     while ((1LL << l) < m) l++;
@@ -284,7 +251,7 @@ extern "C" int cx_grid_resample3d(cx_ctx* ctx, const void* samples, int32_t dtyp
     }
     cxr_args A;
     memset(&A, 0, sizeof(A));
-    if (order == 0 && !cxr_fill_bits(dtype, cval, A.fill_bits)) return cxr_invalid(ctx, "cx_grid_resample3d: cval is not a value of the sample type (order 0)");
+    if (order == 0 && !cx_dtype_value_bits(dtype, cval, A.fill_bits)) return cxr_invalid(ctx, "cx_grid_resample3d: cval is not a value of the sample type (order 0)");
     const int32_t out_dtype = order == 0 ? dtype : CX_DTYPE_F32;
     const size_t in_bytes = (size_t)(n0 * n1 * n2) * cx_dtype_size(dtype), out_bytes = (size_t)(m0 * m1 * m2) * cx_dtype_size(out_dtype);
     const void* dev = samples ? samples : ctx->grid.p;

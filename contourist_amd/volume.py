@@ -583,3 +583,112 @@ def lattice_after(mins, delta, matrix, offset):
         new_mins[k] = mins[a] + delta[a] * off[a]
         new_delta[k] = delta[a] * M[a, k]
     return new_mins, new_delta
+
+
+# ---- rank filters (cx_grid_rank3d, csrc/cx_rank.hip) ---------------------------------------------------------------------------------
+# out[i] = the element at position `rank` of the sorted window {samples[src(i + d - origin)] : d in the footprint}, in the samples' own
+# type: scipy.ndimage.rank_filter.  Nothing is computed, a sample is selected, so the result equals scipy's in value and a numpy
+# restatement (tests/rank_ref.py) bit for bit.  Floats are ordered -inf < ... < -0.0 < +0.0 < ... < +inf < NaN; a selected NaN comes out
+# as the canonical quiet NaN.  Modes "nearest", "reflect" and "constant" are scipy's 'nearest', 'reflect' and 'constant'.  `origin` is
+# the offset of the footprint's box that sits on the output sample, 0 .. size - 1, None for the middle one (`default_origin`); scipy's
+# `origin` argument is this one minus size // 2.  The result's lattice is the samples' own: the same (mins, delta),
+# `lattice_of(mins, delta)` with no weights.
+
+MAX_RANK_SIZE = 7      # per axis of cx_grid_rank3d
+
+
+def ball(radius):
+    "the boolean footprint {d : |d - c|^2 <= radius^2} in a box of side 2 int(radius) + 1 with centre c, for radius < 4"
+    radius = float(radius)
+    assert 0.0 <= radius < 4.0, "a radius of 0 to less than 4 (a box of at most %d per axis)" % MAX_RANK_SIZE
+    r = int(radius)
+    d = np.arange(-r, r + 1, dtype=np.float64) ** 2
+    return d[:, None, None] + d[None, :, None] + d[None, None, :] <= radius * radius
+
+
+def percentile_rank(percentile, n_window):
+    "scipy.ndimage.percentile_filter's rank: a negative percentile has 100 added; 100 is the last element; else int(W p / 100.0)"
+    p = percentile
+    if p < 0.0:
+        p += 100.0
+    assert 0.0 <= p <= 100.0, "a percentile of -100 to 100"
+    return int(n_window) - 1 if p == 100.0 else int(float(n_window) * p / 100.0)
+
+
+def _rank_footprint(size, footprint, ndim):
+    "(size, footprint) of an array of `ndim` axes -> (the box's three sides, the footprint as a 3-D bool array or None, W)"
+    if footprint is None:
+        box = [int(s) for s in _per_axis(size, ndim, 1, "size")]
+        assert all(1 <= s <= MAX_RANK_SIZE for s in box), "a size of 1 to %d per axis" % MAX_RANK_SIZE
+        return box, None, box[0] * box[1] * box[2]
+    fp = np.asarray(footprint) != 0
+    assert fp.ndim == ndim, "footprint: one axis per axis of the samples (%d)" % ndim
+    fp = np.ascontiguousarray(fp.reshape((1,) * (3 - ndim) + fp.shape))
+    assert all(1 <= s <= MAX_RANK_SIZE for s in fp.shape), "a footprint of 1 to %d per axis" % MAX_RANK_SIZE
+    return [int(s) for s in fp.shape], fp, int(fp.sum())
+
+
+def _rank_cval(cval, dtype):
+    "cval as a value of the sample type: rounded to it for a float type, an integer in range for an integer type"
+    name = str(dtype).replace("torch.", "")
+    if name == "bfloat16":
+        import torch
+        return float(torch.tensor(float(cval), dtype=torch.float32).to(torch.bfloat16).float().item())
+    dt = np.dtype(name)
+    if dt.kind == "f":
+        return float(np.asarray(cval, dtype=np.float64).astype(dt))
+    info = np.iinfo(dt)
+    assert float(cval) == int(cval) and info.min <= int(cval) <= info.max, "cval: an integer of the sample type (%s)" % dt.name
+    return int(cval)
+
+
+def rank_filter(samples, rank, size=3, footprint=None, origin=None, mode="nearest", cval=0, device=None):
+    """scipy.ndimage.rank_filter(samples, rank, size or footprint, mode=mode, cval=cval, origin=origin - size // 2) in the samples' own
+    type.  size: one side or one per axis, 1..7, ignored when a footprint (an array of the samples' dimensions, non-zero = in the
+    window) is given; rank: 0 .. W - 1 among the W elements of the window, a negative one counts from the end.
+    Samples: a numpy array (a numpy array comes back) or a contiguous GPU tensor (a tensor comes back) of 1 to 3 dimensions; bool
+    samples count as uint8 0 and 1; types the kernels do not read are converted to float32 first.  The result lives on the samples' own
+    lattice (`lattice_of(mins, delta)` with no weights)."""
+    on_device, s, shape = _distance_samples(samples)
+    ndim = len(shape)
+    assert 1 <= ndim <= 3, "samples of 1 to 3 dimensions"
+    box, fp, n_window = _rank_footprint(size, footprint, ndim)
+    rank = int(rank)
+    if rank < 0:
+        rank += n_window
+    og = [b // 2 for b in box] if origin is None else [int(o) for o in _per_axis(origin, ndim, 0, "origin")]
+    fill = _rank_cval(cval, s.dtype)
+    shape3 = (1,) * (3 - ndim) + shape
+    if on_device:
+        import torch
+        context = _context(s.device.index if device is None else device)
+        out = torch.empty(shape3, dtype=s.dtype, device=s.device)
+        torch.cuda.current_stream(s.device).synchronize()      # the samples are there; the context has a stream of its own
+        context.rank_grid(box, rank, fp, og, mode, fill, samples=(s.data_ptr(), s.dtype, shape3), out=out.data_ptr())
+        return out.reshape(shape)
+    context = _context(device)
+    return context.rank_grid(box, rank, fp, og, mode, fill, samples=s.reshape(shape3), download=True)[1].reshape(shape)
+
+
+def _n_window(samples, size, footprint):
+    return _rank_footprint(size, footprint, len(samples.shape))[2]
+
+
+def median(samples, size=3, footprint=None, origin=None, mode="nearest", cval=0, device=None):
+    "scipy.ndimage.median_filter: rank W // 2 of `rank_filter`.  On a uint8 mask with an odd W: the majority filter"
+    return rank_filter(samples, _n_window(samples, size, footprint) // 2, size, footprint, origin, mode, cval, device)
+
+
+def minimum(samples, size=3, footprint=None, origin=None, mode="nearest", cval=0, device=None):
+    "scipy.ndimage.minimum_filter (grey erosion by a flat footprint): rank 0 of `rank_filter`; separable, and computed so, for a whole box"
+    return rank_filter(samples, 0, size, footprint, origin, mode, cval, device)
+
+
+def maximum(samples, size=3, footprint=None, origin=None, mode="nearest", cval=0, device=None):
+    "scipy.ndimage.maximum_filter (grey dilation by a flat footprint): rank W - 1 of `rank_filter`; separable, and computed so, for a whole box"
+    return rank_filter(samples, -1, size, footprint, origin, mode, cval, device)
+
+
+def percentile(samples, percentile, size=3, footprint=None, origin=None, mode="nearest", cval=0, device=None):
+    "scipy.ndimage.percentile_filter: rank `percentile_rank(percentile, W)` of `rank_filter`"
+    return rank_filter(samples, percentile_rank(percentile, _n_window(samples, size, footprint)), size, footprint, origin, mode, cval, device)

@@ -887,6 +887,54 @@ int cx_grid_resample3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_d
 int cx_grid_resample3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_dtype, int64_t* n_outside);
 int cx_grid_resample3d_bind(cx_ctx* ctx);
 
+/* ---- rank filters: median, percentile, grey minimum and maximum of a volume, on the device ------------------------------------------
+ * What a caller ran scipy.ndimage.median_filter, rank_filter, percentile_filter, minimum_filter or maximum_filter for: noise removed
+ * with the edges kept before the threshold, the labelling and the distance transform see them; on a uint8 mask, the majority filter.
+ * The reference has no call for it.
+ *
+ * cx_grid_rank3d
+ *   samples, dtype, on_device, n0 n1 n2: as in cx_grid_resample3d.  NULL: the bound 3-D grid in its own type (CX_ERR_STATE without one);
+ *            else a host or device pointer of any CX_DTYPE_*, aligned to its own type, every axis >= 1, at most 2^31 samples.  The
+ *            pointer cx_grid_rank3d_result handed out is a legal input: that result is consumed, the new one takes its place.
+ *   size     the footprint's box s0 s1 s2, each 1..7; origin o0 o1 o2, each 0 .. s_a - 1 (scipy's centre is s_a / 2; scipy's `origin`
+ *            argument is o_a - s_a / 2).
+ *   footprint  NULL: the whole box.  Else s0 s1 s2 bytes in C order on the host, non-zero = the offset belongs to the footprint.
+ *            W = the number of offsets that belong to it (>= 1).
+ *   rank     0 .. W - 1.
+ *       window(i) = { in[src0(i0 + d0 - o0), src1(i1 + d1 - o1), src2(i2 + d2 - o2)] : d in the footprint }
+ *       out[i]    = the element of window(i) at position `rank` in ascending order
+ *   in the input's own type and shape.  The order is a total order on the samples' bits: integers by value; floats as
+ *   -inf < negative finite < -0.0 < +0.0 < positive finite < +inf < NaN, every NaN, whatever its sign and payload, one largest element.
+ *   A selected NaN comes out as the canonical quiet NaN of the type (0x7FC00000, 0x7E00 half, 0x7FC0 bfloat16); every other output is
+ *   the bits of a sample (or of cval).  Equal elements have equal bits, so no tie rule is needed.  (The keys of cx_samples_select fold
+ *   -0.0 onto +0.0 and have no inverse; these do not.)
+ *   src is the boundary rule of `mode` per index, as in cx_grid_filter3d: CX_FILTER_NEAREST clamps, CX_FILTER_REFLECT takes p = j mod 2n
+ *   and reads p < n ? p : 2n-1-p (a window wider than the axis is legal), under CX_FILTER_CONSTANT an element whose index is off the
+ *   array on any axis is cval.  cval must be finite and a value of the sample type (CX_ERR_INVALID otherwise), in every mode.
+ *   With origin = o - s / 2 this is scipy.ndimage.rank_filter(in, rank, footprint=..., mode='nearest' | 'reflect' | 'constant', cval=...,
+ *   origin=...); rank W / 2 is median_filter, 0 and W - 1 are minimum_filter and maximum_filter.
+ *   out_device  not NULL: the n0 n1 n2 values are written there (device memory of the caller, aligned to the sample type;
+ *            CX_ERR_INVALID if it overlaps the input), and the context keeps no result.  NULL: the result goes into a buffer the context
+ *            owns (counted by cx_device_bytes, reused by the next call) and stays pending until the next cx_grid_rank3d or
+ *            cx_grid_rank3d_bind.  The slot is this call's own: cx_grid_filter3d, cx_grid_distance3d, cx_grid_label3d,
+ *            cx_grid_resample3d and this call do not disturb each other's pending results, and the pending pointer is a legal `samples`
+ *            of all five.
+ *   out_host    not NULL: also receives a copy.  The call returns after the stream has run it.
+ *   CX_ERR_INVALID: an unknown mode or sample type, a size outside 1..7, an origin outside 0 .. s - 1, an empty footprint, a rank
+ *   outside 0 .. W - 1, a cval that is not finite or not a value of the sample type, a shape outside its range, an output that overlaps
+ *   the input.
+ * cx_grid_rank3d_result: the pending result: device pointer, shape and its CX_DTYPE_*; CX_ERR_STATE when none is pending.
+ * cx_grid_rank3d_bind: the pending result becomes the bound grid in the input's own type, owned by the context, with every reset of an
+ *   upload, as cx_grid_filter3d_bind does it.  A result the march does not take (an axis shorter than 2, more than 2^29 samples) is
+ *   refused as an upload of that shape is, and stays pending.  Afterwards nothing is pending.  CX_ERR_STATE when nothing is pending.
+ * A call without bind leaves the bound grid, the current extraction, the selected level and the Level-1 state as they are.  No
+ * floating-point arithmetic and no atomics: every call gives the same bits.  tests/rank_ref.py restates all of it in numpy. */
+int cx_grid_rank3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                   const int32_t size[3], const int32_t origin[3], const uint8_t* footprint /* size[0]*size[1]*size[2] bytes, C order, host; NULL = full box */,
+                   int32_t rank, int32_t mode, double cval, void* out_device, void* out_host);
+int cx_grid_rank3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_dtype);
+int cx_grid_rank3d_bind(cx_ctx* ctx);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
