@@ -64,6 +64,11 @@ TOPOLOGY_DTYPE = np.dtype([("triangles", "<i8"), ("vertices", "<i8"), ("edges", 
                            ("euler", "<i8"), ("boundary_loops", "<i4"), ("genus", "<i4"), ("nonsimple_loops", "<i4"), ("reserved", "<i4")])
 LOOP_DTYPE = np.dtype([("component", "<i4"), ("simple", "<i4"), ("first", "<u4"), ("count", "<u4")])
 LABEL_SIDES = {"high": 0, "low": 1}                                 # CX_LABEL_*
+RECON_METHODS = {"dilation": 0, "erosion": 1}                       # CX_RECON_DILATION / _EROSION
+RECON_MARKERS = {"array": 0, "shift": 1, "step": 2, "rim": 3}       # CX_RECON_MARKER_*
+RECON_OUTS = {"values": 0, "changed": 1}                            # CX_RECON_OUT_*
+RECON_ALL_FACES = 63                                                # bit 0: i = 0, 1: i = n0-1, 2: j = 0, 3: j = n1-1, 4: k = 0, 5: k = n2-1
+RECON_STATS = ("n_changed", "n_clamped", "rounds", "tile_visits")   # cx_recon_stats, four int64
 # one record of cx_grid_label3d_measures (cx_label_component): 72 bytes
 LABEL_COMPONENT_DTYPE = np.dtype([("voxels", "<i8"), ("first", "<i8"), ("sum", "<i8", (3,)), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)),
                                   ("rim", "<u4"), ("reserved", "<u4")])
@@ -88,6 +93,7 @@ SYMBOLS = [
     "cx_grid_label3d", "cx_grid_label3d_result", "cx_grid_label3d_measures", "cx_grid_label3d_select", "cx_grid_label3d_select_result", "cx_grid_label3d_bind",
     "cx_grid_resample3d", "cx_grid_resample3d_result", "cx_grid_resample3d_bind",
     "cx_grid_rank3d", "cx_grid_rank3d_result", "cx_grid_rank3d_bind",
+    "cx_grid_reconstruct3d", "cx_grid_reconstruct3d_result", "cx_grid_reconstruct3d_bind",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -321,6 +327,10 @@ def load():
         "cx_grid_rank3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, dbl, vp, vp],
         "cx_grid_rank3d_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int32)],
         "cx_grid_rank3d_bind": [vp],
+        "cx_grid_reconstruct3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, vp, ctypes.c_int32, dbl, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                  ctypes.c_int32, vp, vp, vp],
+        "cx_grid_reconstruct3d_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)],
+        "cx_grid_reconstruct3d_bind": [vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -898,6 +908,80 @@ class Context(object):
         "the result the last rank_grid left in the context becomes the bound grid (the samples' own type, owned by the context): cx_grid_rank3d_bind"
         shape = self.rank_result()[0]
         self._check(self.lib.cx_grid_rank3d_bind(self.handle))
+        self.shape = shape
+        self._keep = None
+
+    def reconstruct_grid(self, marker="step", h=0.0, faces=RECON_ALL_FACES, method="dilation", connectivity=1, out_kind="values", samples=None,
+                         out=None, download=False):
+        """grey morphological reconstruction under the mask `samples` (cx_grid_reconstruct3d) -> (stats, the result).
+        marker: a name of RECON_MARKERS other than "array" ("shift": mask -+ h, "step": the predecessor / successor, "rim": the mask on
+        the faces `faces`), or a marker array given the way `samples` is; method: a name of RECON_METHODS; connectivity: 1, 2 or 3;
+        out_kind: a name of RECON_OUTS ("values": the samples' type, "changed": uint8, 1 where the result differs from the mask).
+        samples: as in filter_grid (None = the bound grid, a 3-D numpy array, (device pointer, dtype, shape), (numpy array, dtype, shape));
+        a marker array has the same form (a device pointer when samples is None) and the mask's shape and type.
+        out: None = the result stays in the context (reconstruct_result, bind_reconstructed); or a device pointer to room for the result.
+        stats: a dict of RECON_STATS (n_changed and n_clamped exact; rounds and tile_visits informational).  The result: a numpy array
+        with download=True (bfloat16 samples come back as their uint16 bit patterns), else its device pointer."""
+        keep = []
+
+        def located(a):
+            "-> (pointer, dtype code, on_device, shape)"
+            if isinstance(a, tuple) and isinstance(a[0], np.ndarray):
+                host = np.ascontiguousarray(a[0])
+                keep.append(host)
+                return ctypes.c_void_p(host.ctypes.data), dtype_code(a[1]), 0, tuple(int(n) for n in a[2])
+            if isinstance(a, tuple):
+                return ctypes.c_void_p(int(a[0])), dtype_code(a[1]), 1, tuple(int(n) for n in a[2])
+            host = native_array(a)
+            keep.append(host)
+            return ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
+
+        if samples is None:
+            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
+        else:
+            ptr, code, on_device, shape = located(samples)
+        assert len(shape) == 3, "3-D sample array expected"
+        if samples is None:
+            if self.shape is None:
+                raise CxError(CX_ERR_STATE, "reconstruct_grid: no samples given and no grid bound")
+            shape_out, code_out = tuple(self.shape), DTYPE_CODES[self.grid_info()["dtype"]]
+        else:
+            shape_out, code_out = shape, code
+        mptr = None
+        if isinstance(marker, str):
+            kind = RECON_MARKERS[marker]
+            assert marker != "array", "marker: the array itself, or the name of another marker kind"
+        elif marker is None:
+            kind = RECON_MARKERS["array"]      # (refused by the library)
+        else:
+            kind = RECON_MARKERS["array"]
+            mptr, mcode, m_on_device, mshape = located(marker)
+            assert mcode == code_out and tuple(mshape) == tuple(shape_out) and m_on_device == on_device, "marker: the mask's shape, type and residency"
+        if download:
+            name = DTYPE_NAMES.get(code_out, "float32") if RECON_OUTS[out_kind] == 0 else "uint8"
+            host_out = np.empty([max(0, int(n)) for n in shape_out], dtype=np.uint16 if name == "bfloat16" else np.dtype(name))
+        st = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.cx_grid_reconstruct3d(self.handle, ptr, code, on_device, shape[0], shape[1], shape[2], mptr, kind, float(h), int(faces),
+                                                   RECON_METHODS[method], int(connectivity), RECON_OUTS[out_kind],
+                                                   ctypes.c_void_p(int(out)) if out else None, host_out.ctypes.data if download else None,
+                                                   st.ctypes.data))
+        stats = dict(zip(RECON_STATS, (int(x) for x in st)))
+        if download:
+            return stats, host_out
+        return stats, (int(out) if out else self.reconstruct_result()[1])
+
+    def reconstruct_result(self):
+        "(shape, device pointer, dtype name, out kind name) of the result the last reconstruct_grid left in the context (cx_grid_reconstruct3d_result)"
+        p, m, code, kind = ctypes.c_void_p(), np.zeros(3, dtype=np.int64), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self.lib.cx_grid_reconstruct3d_result(self.handle, ctypes.byref(p), m.ctypes.data, ctypes.byref(code), ctypes.byref(kind)))
+        names = {v: k for k, v in RECON_OUTS.items()}
+        return tuple(int(x) for x in m), int(p.value or 0), DTYPE_NAMES[int(code.value)], names[int(kind.value)]
+
+    def bind_reconstructed(self):
+        """the result the last reconstruct_grid left in the context becomes the bound grid (the samples' own type, uint8 for "changed", owned
+        by the context): cx_grid_reconstruct3d_bind"""
+        shape = self.reconstruct_result()[0]
+        self._check(self.lib.cx_grid_reconstruct3d_bind(self.handle))
         self.shape = shape
         self._keep = None
 

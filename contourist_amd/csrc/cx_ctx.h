@@ -218,6 +218,9 @@ struct cx_ctx {
     // rank filters (cx_rank.hip): the device copy of host samples and the context's own result until cx_grid_rank3d_bind makes it the
     // bound grid: a slot of its own, beside the other four
     struct cx_rank_state* rank = nullptr;
+    // morphological reconstruction (cx_recon.hip): the device copies of a host mask and marker, the working keys, the tile lists, and
+    // the context's own result until cx_grid_reconstruct3d_bind makes it the bound grid: a slot of its own, beside the other five
+    struct cx_recon_state* recon = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -411,6 +414,8 @@ void cx_label_free(cx_ctx* ctx);
 void cx_resample_free(cx_ctx* ctx);
 // cx_rank.hip
 void cx_rank_free(cx_ctx* ctx);
+// cx_recon.hip
+void cx_recon_free(cx_ctx* ctx);
 bool cx_level1_capped(cx_ctx* ctx);   // cx_post.hip: the Level-1 mesh came out of cx_postprocess3d_capped (or is a filtered copy of one)
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);

@@ -45,6 +45,29 @@ __device__ __forceinline__ uint32_t cxd_from_orderable16(uint32_t k, uint32_t qn
     return (k & 0x8000u) ? (k ^ 0x8000u) : (~k & 0xFFFFu);
 }
 
+// the key of a sample of any CX_DTYPE_* (its bits, zero-extended) in the key's own width, and back (cx_rank.hip, cx_recon.hip):
+// integers by value with the sign bit flipped, floats by the functions above
+__device__ __forceinline__ uint32_t cxd_sample_key(int32_t dtype, uint32_t raw) {
+    switch (dtype) {
+        case CX_DTYPE_U8: case CX_DTYPE_U16: return raw;
+        case CX_DTYPE_I8: return raw ^ 0x80u;
+        case CX_DTYPE_I16: return raw ^ 0x8000u;
+        case CX_DTYPE_F16: return cxd_orderable16(raw, 0x7C00u);
+        case CX_DTYPE_BF16: return cxd_orderable16(raw, 0x7F80u);
+        default: return cxd_orderable32(raw);
+    }
+}
+__device__ __forceinline__ uint32_t cxd_sample_unkey(int32_t dtype, uint32_t key) {
+    switch (dtype) {
+        case CX_DTYPE_U8: case CX_DTYPE_U16: return key;
+        case CX_DTYPE_I8: return key ^ 0x80u;
+        case CX_DTYPE_I16: return key ^ 0x8000u;
+        case CX_DTYPE_F16: return cxd_from_orderable16(key, 0x7E00u);
+        case CX_DTYPE_BF16: return cxd_from_orderable16(key, 0x7FC0u);
+        default: return cxd_from_orderable32(key);
+    }
+}
+
 // the boundary rule of the grid calls (cx_grid_resample3d, cx_grid_rank3d): the index read for j on an axis of n samples, -1 for cval
 __device__ __forceinline__ int32_t cxd_boundary_src(int64_t j, int64_t n, int32_t mode) {
     if (j >= 0 && j < n) return (int32_t)j;

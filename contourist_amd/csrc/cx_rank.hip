@@ -63,26 +63,8 @@ struct cxq_args {
     unsigned long long tiles;
 };
 
-__device__ __forceinline__ uint32_t cxq_key(int32_t dtype, uint32_t raw) {
-    switch (dtype) {
-        case CX_DTYPE_U8: case CX_DTYPE_U16: return raw;
-        case CX_DTYPE_I8: return raw ^ 0x80u;
-        case CX_DTYPE_I16: return raw ^ 0x8000u;
-        case CX_DTYPE_F16: return cxd_orderable16(raw, 0x7C00u);
-        case CX_DTYPE_BF16: return cxd_orderable16(raw, 0x7F80u);
-        default: return cxd_orderable32(raw);
-    }
-}
-__device__ __forceinline__ uint32_t cxq_unkey(int32_t dtype, uint32_t key) {
-    switch (dtype) {
-        case CX_DTYPE_U8: case CX_DTYPE_U16: return key;
-        case CX_DTYPE_I8: return key ^ 0x80u;
-        case CX_DTYPE_I16: return key ^ 0x8000u;
-        case CX_DTYPE_F16: return cxd_from_orderable16(key, 0x7E00u);
-        case CX_DTYPE_BF16: return cxd_from_orderable16(key, 0x7FC0u);
-        default: return cxd_from_orderable32(key);
-    }
-}
+__device__ __forceinline__ uint32_t cxq_key(int32_t dtype, uint32_t raw) { return cxd_sample_key(dtype, raw); }
+__device__ __forceinline__ uint32_t cxq_unkey(int32_t dtype, uint32_t key) { return cxd_sample_unkey(dtype, key); }
 
 // the first output of this workgroup's tile
 __device__ __forceinline__ void cxq_place(const cxq_args& A, int64_t& b0, int64_t& b1, int64_t& b2) {

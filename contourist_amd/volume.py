@@ -692,3 +692,133 @@ def maximum(samples, size=3, footprint=None, origin=None, mode="nearest", cval=0
 def percentile(samples, percentile, size=3, footprint=None, origin=None, mode="nearest", cval=0, device=None):
     "scipy.ndimage.percentile_filter: rank `percentile_rank(percentile, W)` of `rank_filter`"
     return rank_filter(samples, percentile_rank(percentile, _n_window(samples, size, footprint)), size, footprint, origin, mode, cval, device)
+
+
+# ---- morphological reconstruction (cx_grid_reconstruct3d, csrc/cx_recon.hip) ----------------------------------------------------------
+# Reconstruction by dilation of a marker g under a mask f: the largest R <= f above min(g, f) in which every sample is reached from it
+# by a path of neighbours along which R does not increase; by erosion: the dual.  The result is made of minima and maxima of the
+# samples only, in their own type, in the order of the rank filters (-inf < ... < -0.0 < +0.0 < ... < +inf < NaN), and equals a numpy
+# restatement (tests/recon_ref.py) bit for bit.  connectivity 1, 2, 3: 6, 18 or 26 neighbours in three dimensions, as `label` counts
+# them.  The result's lattice is the samples' own.
+
+def _recon_faces(faces, ndim):
+    "'all' or a mask of the bits 2 a (the low face of axis a of the samples) and 2 a + 1 (its high face) -> the bits of the padded shape"
+    full = (1 << (2 * ndim)) - 1
+    if isinstance(faces, str):
+        assert faces == "all", "faces: 'all' or a mask of the bits 2 * axis (low face) and 2 * axis + 1 (high face)"
+        faces = full
+    faces = int(faces)
+    assert 1 <= faces <= full, "faces: at least one face, bits 0 .. %d for samples of %d dimensions" % (2 * ndim - 1, ndim)
+    return faces << (2 * (3 - ndim))
+
+
+def _recon_h(h, dtype):
+    "h as cx_grid_reconstruct3d takes it: finite and above 0, an integer for an integer type"
+    h = float(h)
+    assert np.isfinite(h) and h > 0.0, "h: finite and above 0"
+    try:
+        name = np.dtype(dtype).name
+    except TypeError:      # a torch type, or its name
+        name = str(dtype).replace("torch.", "")
+    assert "float" in name or h == int(h), "h: an integer for samples of an integer type (%s)" % name
+    return h
+
+
+def _reconstruct(samples, marker, h, faces, method, connectivity, out_kind, device):
+    "marker: the name of a marker kind, or the marker array -> the result beside the samples: a tensor for a tensor, else a numpy array"
+    assert method in _ffi.RECON_METHODS, "method: 'dilation' or 'erosion'"
+    assert connectivity in (1, 2, 3), "connectivity: 1, 2 or 3"
+    on_device, s, shape = _distance_samples(samples)
+    ndim = len(shape)
+    assert 1 <= ndim <= 3, "samples of 1 to 3 dimensions"
+    shape3 = (1,) * (3 - ndim) + shape
+    m = None
+    if not isinstance(marker, str):
+        m_on_device, m, m_shape = _distance_samples(marker)
+        assert m_on_device == on_device, "marker and mask: two numpy arrays or two GPU tensors"
+        assert m_shape == shape, "marker: the shape of the mask"
+        assert m.dtype == s.dtype, "marker: the type of the mask (%s)" % s.dtype
+    elif marker == "shift":
+        h = _recon_h(h, s.dtype)
+    elif marker == "rim":
+        faces = _recon_faces(faces, ndim)
+    if on_device:
+        import torch
+        context = _context(s.device.index if device is None else device)
+        out = torch.empty(shape3, dtype=s.dtype if out_kind == "values" else torch.uint8, device=s.device)
+        torch.cuda.current_stream(s.device).synchronize()      # the samples are there; the context has a stream of its own
+        context.reconstruct_grid(marker if m is None else (m.data_ptr(), m.dtype, shape3), h, faces, method, connectivity, out_kind,
+                                 samples=(s.data_ptr(), s.dtype, shape3), out=out.data_ptr())
+        return out.reshape(shape)
+    context = _context(device)
+    return context.reconstruct_grid(marker if m is None else m.reshape(shape3), h, faces, method, connectivity, out_kind,
+                                    samples=s.reshape(shape3), download=True)[1].reshape(shape)
+
+
+def reconstruct(marker, mask, method="dilation", connectivity=1, device=None):
+    """skimage.morphology.reconstruction(marker, mask, method) in the mask's type.  The marker is clamped into the mask first: min(marker,
+    mask) for "dilation", max(marker, mask) for "erosion".  marker and mask: two numpy arrays (a numpy array comes back) or two contiguous
+    GPU tensors (a tensor comes back) of one shape of 1 to 3 dimensions and one type; bool counts as uint8, types the kernels do not
+    read are converted to float32 first."""
+    assert not isinstance(marker, str), "marker: an array of the mask's shape"
+    return _reconstruct(mask, marker, 0.0, 0, method, connectivity, "values", device)
+
+
+def h_maxima(samples, h, connectivity=1, device=None):
+    """the samples with every bump shallower than h cut off: the reconstruction by dilation of samples - h under the samples.  Integer
+    samples: h an integer, samples - h saturates; float samples: samples - h computed in float64 and rounded to the type once."""
+    return _reconstruct(samples, "shift", h, 0, "dilation", connectivity, "values", device)
+
+
+def h_minima(samples, h, connectivity=1, device=None):
+    "the samples with every pit shallower than h filled: the reconstruction by erosion of samples + h above the samples"
+    return _reconstruct(samples, "shift", h, 0, "erosion", connectivity, "values", device)
+
+
+def h_domes(samples, h, connectivity=1, device=None):
+    "uint8, 1 where `h_maxima` lowered a sample: the support of the domes"
+    return _reconstruct(samples, "shift", h, 0, "dilation", connectivity, "changed", device)
+
+
+def h_basins(samples, h, connectivity=1, device=None):
+    "uint8, 1 where `h_minima` raised a sample: the support of the basins"
+    return _reconstruct(samples, "shift", h, 0, "erosion", connectivity, "changed", device)
+
+
+def regional_maxima(samples, connectivity=1, device=None):
+    """uint8, 1 on the plateaus no neighbour of which is higher (skimage.morphology.local_maxima): the markers to put on a `distance`
+    field before touching grains are split.  Every type, floats included: the marker is the sample's predecessor in the order.  A
+    constant array is one maximum (all ones), the smallest value of an integer type included; only -inf everywhere gives zeros."""
+    return _reconstruct(samples, "step", 0.0, 0, "dilation", connectivity, "changed", device)
+
+
+def regional_minima(samples, connectivity=1, device=None):
+    "uint8, 1 on the plateaus no neighbour of which is lower (skimage.morphology.local_minima)"
+    return _reconstruct(samples, "step", 0.0, 0, "erosion", connectivity, "changed", device)
+
+
+def fill_holes_grey(samples, connectivity=1, device=None):
+    """every pit that is not connected to the array's rim filled to its brim: the reconstruction by erosion from the rim, in the samples'
+    type.  On a mask of 0 and 1: scipy.ndimage.binary_fill_holes with generate_binary_structure(ndim, connectivity)."""
+    return _reconstruct(samples, "rim", 0.0, "all", "erosion", connectivity, "values", device)
+
+
+def clear_border_grey(samples, faces="all", connectivity=1, mask=False, device=None):
+    """the reconstruction by dilation from the rim: what of the samples is connected to the faces `faces` ('all', or a mask of the bits
+    2 * axis for the low and 2 * axis + 1 for the high face of an axis of the samples), in the samples' type; mask=True: uint8, 1 where
+    a sample is NOT reached at its own height.  Grey clear-border is samples - result: that subtraction is arithmetic in the caller's
+    type and is left to the caller."""
+    return _reconstruct(samples, "rim", 0.0, faces, "dilation", connectivity, "changed" if mask else "values", device)
+
+
+def propagate(seeds, mask, connectivity=1, device=None):
+    "scipy.ndimage.binary_propagation(seeds, generate_binary_structure(ndim, connectivity), mask=mask) of bool or uint8 arrays: uint8 0 and 1"
+    def binary(a):
+        if grid_field._is_torch(a):
+            import torch
+            assert a.dtype in (torch.bool, torch.uint8), "seeds and mask: bool or uint8"
+            return (a != 0).to(torch.uint8)
+        a = np.asarray(a)
+        assert a.dtype in (np.bool_, np.uint8), "seeds and mask: bool or uint8"
+        return (a != 0).astype(np.uint8)
+    return _reconstruct(binary(mask), binary(seeds), 0.0, 0, "dilation", connectivity, "values", device)

@@ -935,6 +935,77 @@ int cx_grid_rank3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_devic
 int cx_grid_rank3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_dtype);
 int cx_grid_rank3d_bind(cx_ctx* ctx);
 
+/* ---- reconstruction: grey morphological reconstruction of a volume, on the device ------------------------------------------------------
+ * Reconstruction by dilation of a marker g under a mask f: the largest array R <= f that dominates min(g, f) and in which every sample
+ * is reached from it by a path of neighbours along which R does not increase.  What a caller ran skimage.morphology.reconstruction,
+ * h_maxima, local_maxima or scipy.ndimage.binary_propagation for: bumps shallower than h removed with the edges kept, the regional
+ * maxima of a distance field as markers, grey fill-holes and grey clear-border.  The reference has no call for it.
+ *
+ * cx_grid_reconstruct3d
+ *   mask, dtype, on_device, n0 n1 n2: as the samples of cx_grid_rank3d.  NULL: the bound 3-D grid in its own type (CX_ERR_STATE without
+ *            one; the marker array is then on the device); else a host or device pointer of any CX_DTYPE_*, aligned to its own type,
+ *            every axis >= 1, at most 2^31 samples (CX_ERR_UNSUPPORTED beyond).  The pointer cx_grid_reconstruct3d_result handed out
+ *            is a legal input.
+ *   Every comparison is made on the keys of the rank filters: integers by value; floats as -inf < negative finite < -0.0 < +0.0 <
+ *   positive finite < +inf < NaN, every NaN one largest element that comes out as the canonical quiet NaN of the type.  The result is a
+ *   minimum or maximum of values of the mask and the marker, in the samples' own type.
+ *   method   CX_RECON_DILATION: the marker grows upward under the mask.  CX_RECON_EROSION: the dual: the smallest R >= f below
+ *            max(g, f) in which every sample is reached by a path along which R does not decrease (the same on the complemented keys).
+ *   connectivity  1, 2 or 3: 6, 18 or 26 neighbours, as in cx_grid_label3d.
+ *   marker_kind
+ *     CX_RECON_MARKER_ARRAY  `marker` is a second array of the mask's shape, type and residency (CX_ERR_INVALID when NULL), clamped into
+ *            the mask: min(g, f) for dilation, max(g, f) for erosion.  stats->n_clamped counts the samples the clamp changed.
+ *     CX_RECON_MARKER_SHIFT  marker = mask - h (dilation) or mask + h (erosion), h finite and > 0: h-maxima and h-minima.  Integer types:
+ *            h an integer, the arithmetic saturates in the type.  Float types: (double)sample -+ h in float64, rounded once to the
+ *            sample type (to nearest even); a NaN stays one.  No second array.
+ *     CX_RECON_MARKER_STEP   marker = the sample's predecessor (dilation) or successor (erosion) in the order of the keys: integers
+ *            v - 1 or v + 1, saturating; floats the next value of the type, -0.0 and +0.0 being neighbours, saturating at -inf (dilation)
+ *            or +inf (erosion); the predecessor of NaN is +inf, its successor NaN.  With CX_RECON_OUT_CHANGED: the regional extrema.
+ *     CX_RECON_MARKER_RIM    marker = mask on the faces of the array named by the 6 bits of `faces` (bit 0: i = 0, 1: i = n0-1, 2: j = 0,
+ *            3: j = n1-1, 4: k = 0, 5: k = n2-1; 1..63), elsewhere the bottom (dilation) or the top (erosion) of the order of the
+ *            keys, which does not survive: every sample is connected to the rim.  Grey clear-border and grey fill-holes.
+ *   out_kind CX_RECON_OUT_VALUES: the reconstruction in the samples' own type.  CX_RECON_OUT_CHANGED: uint8, 1 where the key of the
+ *            result differs from the key of the mask: the regional extrema, the support of the h-domes, what was filled or cleared.
+ *            One case is defined apart: an integer array that is everywhere the extreme value of its type (the minimum for dilation,
+ *            the maximum for erosion) has no predecessor to step to; under CX_RECON_MARKER_STEP it is one regional extremum and the
+ *            CHANGED mask is all ones (n_changed stays the count of result != mask, 0).
+ *   out_device, out_host  as in cx_grid_rank3d: a caller's device buffer (n0 n1 n2 samples, or bytes for CHANGED) may not overlap the
+ *            mask or the marker (CX_ERR_INVALID) and leaves the context without a result; NULL: the result goes into a buffer the
+ *            context owns and stays pending until the next cx_grid_reconstruct3d or cx_grid_reconstruct3d_bind, in a sixth slot:
+ *            the pending results of cx_grid_filter3d, cx_grid_distance3d, cx_grid_label3d, cx_grid_resample3d and cx_grid_rank3d
+ *            are not disturbed, and the pending pointer (CX_DTYPE_U8 for CHANGED) is a legal input of all of them.  out_host not
+ *            NULL: also receives a copy.  The call returns after the stream has run it.
+ *   stats    may be NULL.  n_changed: the samples where result != mask; n_clamped: see CX_RECON_MARKER_ARRAY.  Both exact and the same
+ *            in every call.  rounds (kernel launches that visited a tile) and tile_visits are informational and may differ from call
+ *            to call: tiles of one launch read each other's samples while they are written, which changes how soon a value arrives,
+ *            never the result.
+ *   CX_ERR_INVALID: an unknown method, marker kind, output kind, connectivity or sample type, faces outside 1..63 with
+ *   CX_RECON_MARKER_RIM, an h that is not finite, not above 0 or (integer types) not an integer, a NULL marker with
+ *   CX_RECON_MARKER_ARRAY, an axis below 1, an output that overlaps an input.  CX_ERR_UNSUPPORTED: more than 2^31 samples.
+ *   CX_ERR_HIP with a message if tiles were still active after as many rounds as the array has samples (no correct run gets there).
+ * cx_grid_reconstruct3d_result: the pending result: device pointer, shape, its CX_DTYPE_* and CX_RECON_OUT_*; CX_ERR_STATE when none is
+ *   pending.
+ * cx_grid_reconstruct3d_bind: the pending result becomes the bound grid (the samples' type, or CX_DTYPE_U8 for CHANGED), owned by the
+ *   context, with every reset of an upload, as cx_grid_rank3d_bind does it.  A result the march does not take (an axis shorter than 2,
+ *   more than 2^29 samples) is refused as an upload of that shape is, and stays pending.  CX_ERR_STATE when nothing is pending.
+ * A call without bind leaves the bound grid, the current extraction, the selected level and the Level-1 state as they are.  The
+ * result is the unique fixed point of v = min(f, max(v, neighbours of v)) above the clamped marker, so every call gives the same bits
+ * whatever order the device works in.  tests/recon_ref.py restates all of it in numpy. */
+#define CX_RECON_DILATION 0
+#define CX_RECON_EROSION  1
+#define CX_RECON_MARKER_ARRAY 0
+#define CX_RECON_MARKER_SHIFT 1
+#define CX_RECON_MARKER_STEP  2
+#define CX_RECON_MARKER_RIM   3
+#define CX_RECON_OUT_VALUES  0
+#define CX_RECON_OUT_CHANGED 1
+typedef struct cx_recon_stats { int64_t n_changed, n_clamped, rounds, tile_visits; } cx_recon_stats;
+int cx_grid_reconstruct3d(cx_ctx* ctx, const void* mask, int32_t dtype, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                          const void* marker, int32_t marker_kind, double h, int32_t faces, int32_t method, int32_t connectivity,
+                          int32_t out_kind, void* out_device, void* out_host, cx_recon_stats* stats);
+int cx_grid_reconstruct3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_dtype, int32_t* out_kind);
+int cx_grid_reconstruct3d_bind(cx_ctx* ctx);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
