@@ -139,7 +139,33 @@ def native_dtype(dtype):
         return False
 
 
-CX_MESH_OF_THE_MARCH = 8      # cx_postprocess3d_mesh flags bit 3: the triangles are ones the march emitted (at most two per edge before merges)
+def locate_samples(samples, keep):
+    """where the samples of a whole-volume operation are -> (pointer, CX_DTYPE_* code, on_device, shape).  samples: None = the bound
+    grid; a 3-D numpy array of a type of DTYPE_CODES; (device pointer, dtype, shape) of contiguous samples on the device; or
+    (numpy array, dtype, shape): host samples whose type is `dtype` whatever numpy calls their bytes (bfloat16 as uint16).  A host
+    array is made contiguous and appended to the list `keep`, which has to outlive the call that reads the pointer."""
+    if samples is None:
+        return None, 0, 1, (0, 0, 0)
+    if isinstance(samples, tuple):
+        first, dtype, shape = samples
+        host = np.ascontiguousarray(first) if isinstance(first, np.ndarray) else None
+    else:
+        host = native_array(samples)
+        dtype, shape = host.dtype, host.shape
+    if host is not None:
+        keep.append(host)
+    shape = tuple(int(n) for n in shape)
+    assert len(shape) == 3, "3-D sample array expected"
+    return ctypes.c_void_p(int(first) if host is None else host.ctypes.data), dtype_code(dtype), int(host is None), shape
+
+
+def _download_array(shape, code):
+    "an empty host array for a result of CX_DTYPE_* `code`: bfloat16, a type numpy has no name for, comes back as its uint16 bit patterns"
+    name = DTYPE_NAMES.get(code, "float32")
+    return np.empty([max(0, int(n)) for n in shape], dtype=np.uint16 if name == "bfloat16" else np.dtype(name))
+
+
+CX_MESH_OF_THE_MARCH = 8     # cx_postprocess3d_mesh flags bit 3: the triangles are ones the march emitted (at most two per edge before merges)
 CX_SIMPLIFY_NO_CLEAN = 1
 CX_SIMPLIFY_ACROSS_COMPONENTS = 2
 CX_SIMPLIFY_COUNT_ONLY = 4
@@ -614,6 +640,13 @@ class Context(object):
         self._check(self.lib.cx_level_spectrum3d(self.handle, vals.ctypes.data, len(vals), *[out[k].ctypes.data for k in SPECTRUM_KEYS]))
         return out
 
+    def _bind_pending(self, result_fn, bind_fn):
+        "the result that result_fn describes becomes the bound grid through bind_fn, an operation's cx_grid_*_bind"
+        shape = result_fn()[0]
+        self._check(bind_fn(self.handle))
+        self.shape = shape
+        self._keep = None
+
     def filter_grid(self, axes, mode="nearest", cval=0.0, samples=None, out=None, download=False):
         """separable filter with a stride per axis (cx_grid_filter3d) -> (shape of the result, the result).
         axes: three of (weights or None, origin, stride), for axis 0, 1, 2.  mode: a name of FILTER_MODES.
@@ -631,19 +664,7 @@ class Context(object):
             recs[a].weights = None if w is None or not len(w) else w.ctypes.data
             recs[a].n_weights = 0 if w is None else len(w)
             recs[a].origin, recs[a].stride = int(origin), int(stride)
-        if samples is None:
-            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
-        elif isinstance(samples, tuple) and isinstance(samples[0], np.ndarray):      # host bytes of a type numpy has no name for (bfloat16 as uint16)
-            host = np.ascontiguousarray(samples[0])
-            keep.append(host)
-            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(samples[1]), 0, tuple(int(n) for n in samples[2])
-        elif isinstance(samples, tuple):
-            ptr, code, on_device, shape = ctypes.c_void_p(int(samples[0])), dtype_code(samples[1]), 1, tuple(int(n) for n in samples[2])
-        else:
-            host = native_array(samples)
-            keep.append(host)
-            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
-        assert len(shape) == 3, "3-D sample array expected"
+        ptr, code, on_device, shape = locate_samples(samples, keep)
         m = np.zeros(3, dtype=np.int64)
         if download:      # the shape first: it follows from the shape and the strides alone
             n = self.shape if samples is None else shape
@@ -667,10 +688,7 @@ class Context(object):
 
     def bind_filtered(self):
         "the result the last filter_grid left in the context becomes the bound grid (float32, owned by the context): cx_grid_filter3d_bind"
-        shape = self.filter_result()[0]
-        self._check(self.lib.cx_grid_filter3d_bind(self.handle))
-        self.shape = shape
-        self._keep = None
+        self._bind_pending(self.filter_result, self.lib.cx_grid_filter3d_bind)
 
     def distance_grid(self, value, side="below", kind="float32", sampling=None, radius2=0.0, samples=None, out=None, download=False):
         """exact Euclidean distance transform of the samples thresholded at `value` (cx_grid_distance3d) -> (n_sites, the result).
@@ -680,19 +698,7 @@ class Context(object):
         out: None = the result stays in the context (distance_result, bind_distance); or a device pointer to room for the result.
         The result: a numpy array of the kind's type with download=True, else its device pointer."""
         keep = []
-        if samples is None:
-            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
-        elif isinstance(samples, tuple) and isinstance(samples[0], np.ndarray):
-            host = np.ascontiguousarray(samples[0])
-            keep.append(host)
-            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(samples[1]), 0, tuple(int(n) for n in samples[2])
-        elif isinstance(samples, tuple):
-            ptr, code, on_device, shape = ctypes.c_void_p(int(samples[0])), dtype_code(samples[1]), 1, tuple(int(n) for n in samples[2])
-        else:
-            host = native_array(samples)
-            keep.append(host)
-            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
-        assert len(shape) == 3, "3-D sample array expected"
+        ptr, code, on_device, shape = locate_samples(samples, keep)
         steps = None if sampling is None else np.ascontiguousarray(sampling, dtype=np.float64).reshape(3)
         kind_code = DIST_KINDS[kind]
         if download:
@@ -719,10 +725,7 @@ class Context(object):
     def bind_distance(self):
         """the float32 or mask result the last distance_grid left in the context becomes the bound grid (float32 / uint8, owned by the
         context): cx_grid_distance3d_bind"""
-        shape = self.distance_result()[0]
-        self._check(self.lib.cx_grid_distance3d_bind(self.handle))
-        self.shape = shape
-        self._keep = None
+        self._bind_pending(self.distance_result, self.lib.cx_grid_distance3d_bind)
 
     def label_grid(self, value, side="high", connectivity=1, samples=None, out=None, download=False):
         """connected components of the samples thresholded at `value` (cx_grid_label3d) -> (K, the labels).
@@ -732,19 +735,7 @@ class Context(object):
         out: None = the labels stay in the context (label_result, label_measures, label_select); or a device pointer to room for them.
         The labels: an int32 numpy array with download=True, else their device pointer."""
         keep = []
-        if samples is None:
-            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
-        elif isinstance(samples, tuple) and isinstance(samples[0], np.ndarray):
-            host = np.ascontiguousarray(samples[0])
-            keep.append(host)
-            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(samples[1]), 0, tuple(int(n) for n in samples[2])
-        elif isinstance(samples, tuple):
-            ptr, code, on_device, shape = ctypes.c_void_p(int(samples[0])), dtype_code(samples[1]), 1, tuple(int(n) for n in samples[2])
-        else:
-            host = native_array(samples)
-            keep.append(host)
-            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
-        assert len(shape) == 3, "3-D sample array expected"
+        ptr, code, on_device, shape = locate_samples(samples, keep)
         if download:
             n = self.shape if samples is None else shape
             if n is None:
@@ -794,10 +785,7 @@ class Context(object):
 
     def bind_label_mask(self):
         "the mask the last label_select left in the context becomes the bound grid (uint8, owned by the context): cx_grid_label3d_bind"
-        shape = self.label_mask_result()[0]
-        self._check(self.lib.cx_grid_label3d_bind(self.handle))
-        self.shape = shape
-        self._keep = None
+        self._bind_pending(self.label_mask_result, self.lib.cx_grid_label3d_bind)
 
     def resample_grid(self, matrix, offset, out_shape, order=1, mode="nearest", cval=0.0, samples=None, out=None, download=False):
         """the samples read through the affine index map c = offset + matrix @ i (cx_grid_resample3d) -> (n_outside, the result).
@@ -808,19 +796,7 @@ class Context(object):
         The result: a numpy array with download=True (bfloat16 samples at order 0 come back as their uint16 bit patterns), else its
         device pointer.  n_outside: the output samples whose source coordinate lies off the array on some axis."""
         keep = []
-        if samples is None:
-            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
-        elif isinstance(samples, tuple) and isinstance(samples[0], np.ndarray):
-            host = np.ascontiguousarray(samples[0])
-            keep.append(host)
-            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(samples[1]), 0, tuple(int(n) for n in samples[2])
-        elif isinstance(samples, tuple):
-            ptr, code, on_device, shape = ctypes.c_void_p(int(samples[0])), dtype_code(samples[1]), 1, tuple(int(n) for n in samples[2])
-        else:
-            host = native_array(samples)
-            keep.append(host)
-            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
-        assert len(shape) == 3, "3-D sample array expected"
+        ptr, code, on_device, shape = locate_samples(samples, keep)
         mat = np.ascontiguousarray(matrix, dtype=np.float64).reshape(3, 3)
         off = np.ascontiguousarray(offset, dtype=np.float64).reshape(3)
         m = np.ascontiguousarray(out_shape, dtype=np.int64).reshape(3)
@@ -829,8 +805,7 @@ class Context(object):
                 if self.shape is None:
                     raise CxError(CX_ERR_STATE, "resample_grid: no samples given and no grid bound")
                 code = DTYPE_CODES[self.grid_info()["dtype"]]
-            name = DTYPE_NAMES.get(code, "float32") if int(order) == 0 else "float32"
-            host_out = np.empty([max(0, int(x)) for x in m], dtype=np.uint16 if name == "bfloat16" else np.dtype(name))
+            host_out = _download_array(m, code if int(order) == 0 else DTYPE_CODES["float32"])
         n_outside = ctypes.c_int64()
         self._check(self.lib.cx_grid_resample3d(self.handle, ptr, code, on_device, shape[0], shape[1], shape[2], mat.ctypes.data, off.ctypes.data,
                                                 m.ctypes.data, int(order), FILTER_MODES[mode], float(cval), ctypes.c_void_p(int(out)) if out else None,
@@ -848,10 +823,7 @@ class Context(object):
     def bind_resampled(self):
         """the result the last resample_grid left in the context becomes the bound grid (float32 for order 1, the input's type for order 0,
         owned by the context): cx_grid_resample3d_bind"""
-        shape = self.resample_result()[0]
-        self._check(self.lib.cx_grid_resample3d_bind(self.handle))
-        self.shape = shape
-        self._keep = None
+        self._bind_pending(self.resample_result, self.lib.cx_grid_resample3d_bind)
 
     def rank_grid(self, size, rank, footprint=None, origin=None, mode="nearest", cval=0, samples=None, out=None, download=False):
         """the element at position `rank` of the sorted window around every sample (cx_grid_rank3d) -> (shape, the result).
@@ -863,19 +835,7 @@ class Context(object):
         The result has the samples' type: a numpy array with download=True (bfloat16 samples come back as their uint16 bit patterns),
         else its device pointer."""
         keep = []
-        if samples is None:
-            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
-        elif isinstance(samples, tuple) and isinstance(samples[0], np.ndarray):
-            host = np.ascontiguousarray(samples[0])
-            keep.append(host)
-            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(samples[1]), 0, tuple(int(n) for n in samples[2])
-        elif isinstance(samples, tuple):
-            ptr, code, on_device, shape = ctypes.c_void_p(int(samples[0])), dtype_code(samples[1]), 1, tuple(int(n) for n in samples[2])
-        else:
-            host = native_array(samples)
-            keep.append(host)
-            ptr, code, on_device, shape = ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
-        assert len(shape) == 3, "3-D sample array expected"
+        ptr, code, on_device, shape = locate_samples(samples, keep)
         box = np.ascontiguousarray(np.broadcast_to(np.asarray(size, dtype=np.int32), (3,)))
         og = box // 2 if origin is None else np.ascontiguousarray(origin, dtype=np.int32).reshape(3)
         fp = None
@@ -889,8 +849,7 @@ class Context(object):
         else:
             shape_out, code_out = shape, code
         if download:
-            name = DTYPE_NAMES.get(code_out, "float32")
-            host_out = np.empty([max(0, int(n)) for n in shape_out], dtype=np.uint16 if name == "bfloat16" else np.dtype(name))
+            host_out = _download_array(shape_out, code_out)
         self._check(self.lib.cx_grid_rank3d(self.handle, ptr, code, on_device, shape[0], shape[1], shape[2], box.ctypes.data, og.ctypes.data,
                                             None if fp is None else fp.ctypes.data, int(rank), FILTER_MODES[mode], float(cval),
                                             ctypes.c_void_p(int(out)) if out else None, host_out.ctypes.data if download else None))
@@ -906,10 +865,7 @@ class Context(object):
 
     def bind_ranked(self):
         "the result the last rank_grid left in the context becomes the bound grid (the samples' own type, owned by the context): cx_grid_rank3d_bind"
-        shape = self.rank_result()[0]
-        self._check(self.lib.cx_grid_rank3d_bind(self.handle))
-        self.shape = shape
-        self._keep = None
+        self._bind_pending(self.rank_result, self.lib.cx_grid_rank3d_bind)
 
     def reconstruct_grid(self, marker="step", h=0.0, faces=RECON_ALL_FACES, method="dilation", connectivity=1, out_kind="values", samples=None,
                          out=None, download=False):
@@ -923,24 +879,7 @@ class Context(object):
         stats: a dict of RECON_STATS (n_changed and n_clamped exact; rounds and tile_visits informational).  The result: a numpy array
         with download=True (bfloat16 samples come back as their uint16 bit patterns), else its device pointer."""
         keep = []
-
-        def located(a):
-            "-> (pointer, dtype code, on_device, shape)"
-            if isinstance(a, tuple) and isinstance(a[0], np.ndarray):
-                host = np.ascontiguousarray(a[0])
-                keep.append(host)
-                return ctypes.c_void_p(host.ctypes.data), dtype_code(a[1]), 0, tuple(int(n) for n in a[2])
-            if isinstance(a, tuple):
-                return ctypes.c_void_p(int(a[0])), dtype_code(a[1]), 1, tuple(int(n) for n in a[2])
-            host = native_array(a)
-            keep.append(host)
-            return ctypes.c_void_p(host.ctypes.data), dtype_code(host.dtype), 0, tuple(int(n) for n in host.shape)
-
-        if samples is None:
-            ptr, code, on_device, shape = None, 0, 1, (0, 0, 0)
-        else:
-            ptr, code, on_device, shape = located(samples)
-        assert len(shape) == 3, "3-D sample array expected"
+        ptr, code, on_device, shape = locate_samples(samples, keep)
         if samples is None:
             if self.shape is None:
                 raise CxError(CX_ERR_STATE, "reconstruct_grid: no samples given and no grid bound")
@@ -955,11 +894,10 @@ class Context(object):
             kind = RECON_MARKERS["array"]      # (refused by the library)
         else:
             kind = RECON_MARKERS["array"]
-            mptr, mcode, m_on_device, mshape = located(marker)
+            mptr, mcode, m_on_device, mshape = locate_samples(marker, keep)
             assert mcode == code_out and tuple(mshape) == tuple(shape_out) and m_on_device == on_device, "marker: the mask's shape, type and residency"
         if download:
-            name = DTYPE_NAMES.get(code_out, "float32") if RECON_OUTS[out_kind] == 0 else "uint8"
-            host_out = np.empty([max(0, int(n)) for n in shape_out], dtype=np.uint16 if name == "bfloat16" else np.dtype(name))
+            host_out = _download_array(shape_out, code_out if RECON_OUTS[out_kind] == 0 else DTYPE_CODES["uint8"])
         st = np.zeros(4, dtype=np.int64)
         self._check(self.lib.cx_grid_reconstruct3d(self.handle, ptr, code, on_device, shape[0], shape[1], shape[2], mptr, kind, float(h), int(faces),
                                                    RECON_METHODS[method], int(connectivity), RECON_OUTS[out_kind],
@@ -980,10 +918,7 @@ class Context(object):
     def bind_reconstructed(self):
         """the result the last reconstruct_grid left in the context becomes the bound grid (the samples' own type, uint8 for "changed", owned
         by the context): cx_grid_reconstruct3d_bind"""
-        shape = self.reconstruct_result()[0]
-        self._check(self.lib.cx_grid_reconstruct3d_bind(self.handle))
-        self.shape = shape
-        self._keep = None
+        self._bind_pending(self.reconstruct_result, self.lib.cx_grid_reconstruct3d_bind)
 
     def level0_points_f64(self, counts):
         "float64 coordinates of the Level-0 vertices as the reference interpolates them, in download_level0 order"

@@ -8,11 +8,6 @@
 
 #include "cx_ctx.h"
 
-static int fail(cx_ctx* ctx, int code, const char* msg) {
-    if (ctx) ctx->err = msg;
-    return code;
-}
-
 extern "C" const char* cx_version(void) { return "contourist_hip gfx950 " __DATE__; }
 
 extern "C" int cx_ctx_create(int device_id, cx_ctx** out) {
@@ -94,9 +89,9 @@ extern "C" int cx_synchronize(cx_ctx* ctx) {
 }
 
 static int set_grid_dims(cx_ctx* ctx, int64_t n0, int64_t n1, int64_t n2) {
-    if (n0 < 2 || n1 < 2 || n2 < 2) return fail(ctx, CX_ERR_INVALID, "grid must have at least 2 samples per axis");
+    if (n0 < 2 || n1 < 2 || n2 < 2) return cx_fail(ctx, CX_ERR_INVALID, "grid must have at least 2 samples per axis");
     const int64_t N = n0 * n1 * n2;
-    if (N > (1LL << 29)) return fail(ctx, CX_ERR_UNSUPPORTED, "more than 2^29 samples in one grid: partition into slabs");
+    if (N > (1LL << 29)) return cx_fail(ctx, CX_ERR_UNSUPPORTED, "more than 2^29 samples in one grid: partition into slabs");
     ctx->n0 = n0; ctx->n1 = n1; ctx->n2 = n2;
     ctx->grid64_valid = false;   // the float64 originals belonged to the previous grid
     cx_levels_unselect(ctx);     // a level selected on the previous grid gets its output buffers back: its slot would allocate new ones otherwise
@@ -121,7 +116,7 @@ int cx_grid_bind_owned(cx_ctx* ctx, cx_buf<uint8_t>& buf, int32_t dtype, int64_t
 
 extern "C" int cx_grid_upload_typed(cx_ctx* ctx, const void* host, int32_t dtype, int64_t n0, int64_t n1, int64_t n2) {
     if (!ctx || !host) return CX_ERR_INVALID;
-    if (!cx_dtype_valid(dtype)) return fail(ctx, CX_ERR_INVALID, ("cx_grid_upload_typed: unknown sample type " + std::to_string(dtype)).c_str());
+    if (!cx_dtype_valid(dtype)) return cx_fail(ctx, CX_ERR_INVALID, ("cx_grid_upload_typed: unknown sample type " + std::to_string(dtype)).c_str());
     CX_HIP(ctx, hipSetDevice(ctx->device));
     int rc = set_grid_dims(ctx, n0, n1, n2);
     if (rc) return rc;
@@ -140,7 +135,7 @@ extern "C" int cx_grid_upload(cx_ctx* ctx, const float* host, int64_t n0, int64_
 
 extern "C" int cx_grid_adopt_device_typed(cx_ctx* ctx, const void* device_ptr, int32_t dtype, int64_t n0, int64_t n1, int64_t n2) {
     if (!ctx || !device_ptr) return CX_ERR_INVALID;
-    if (!cx_dtype_valid(dtype)) return fail(ctx, CX_ERR_INVALID, ("cx_grid_adopt_device_typed: unknown sample type " + std::to_string(dtype)).c_str());
+    if (!cx_dtype_valid(dtype)) return cx_fail(ctx, CX_ERR_INVALID, ("cx_grid_adopt_device_typed: unknown sample type " + std::to_string(dtype)).c_str());
     CX_HIP(ctx, hipSetDevice(ctx->device));
     int rc = set_grid_dims(ctx, n0, n1, n2);
     if (rc) return rc;
@@ -154,7 +149,7 @@ extern "C" int cx_grid_adopt_device(cx_ctx* ctx, const void* device_ptr, int64_t
 
 extern "C" int cx_grid_info(cx_ctx* ctx, int32_t* dtype, int64_t* device_bytes) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!ctx->grid.p) return fail(ctx, CX_ERR_STATE, "no grid: call cx_grid_upload or cx_grid_adopt_device first");
+    if (!ctx->grid.p) return cx_fail(ctx, CX_ERR_STATE, "no grid: call cx_grid_upload or cx_grid_adopt_device first");
     if (dtype) *dtype = ctx->grid.dtype;
     if (device_bytes)
         *device_bytes = ctx->grid.p == ctx->grid_owned ? ctx->n0 * ctx->n1 * ctx->n2 * (int64_t)cx_dtype_size(ctx->grid.dtype) : 0;
@@ -171,7 +166,7 @@ extern "C" int cx_grid_shadow_f64(cx_ctx* ctx, const double* host, int64_t n0, i
     ctx->post_valid = false;
     if (!host) return CX_OK;
     if (!ctx->grid.p || n0 != ctx->n0 || n1 != ctx->n1 || n2 != ctx->n2)   // of any sample type
-        return fail(ctx, CX_ERR_STATE, "cx_grid_shadow_f64: bind the fp32 grid of the same dimensions first");
+        return cx_fail(ctx, CX_ERR_STATE, "cx_grid_shadow_f64: bind the fp32 grid of the same dimensions first");
     CX_HIP(ctx, hipSetDevice(ctx->device));
     const size_t N = (size_t)(n0 * n1 * n2);
     int rc = ctx->grid64.grow(ctx, N);
@@ -201,7 +196,7 @@ extern "C" int cx_set_reference_corner(cx_ctx* ctx, int64_t c0, int64_t c1, int6
 extern "C" int cx_reserve(cx_ctx* ctx, int64_t max_cells, int64_t max_vertices, int64_t max_triangles) {
     if (!ctx || max_cells < 0 || max_vertices < 0 || max_triangles < 0) return CX_ERR_INVALID;
     if (max_cells > 0xFFFFFFF0LL || max_vertices > 0xFFFFFFF0LL || max_triangles > 0x7FFFFFF0LL)
-        return fail(ctx, CX_ERR_UNSUPPORTED, "capacity beyond 32-bit indices");
+        return cx_fail(ctx, CX_ERR_UNSUPPORTED, "capacity beyond 32-bit indices");
     CX_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
     if ((rc = ctx->cells.grow(ctx, (size_t)max_cells))) return rc;
@@ -272,11 +267,11 @@ cx_staged_sizes cx_staged_sizes_of(const cx_ctx* ctx, const cx_task& T) {
 }
 
 static int enqueue_extract(cx_ctx* ctx, double value, uint32_t flags) {
-    if (!ctx->grid.p) return fail(ctx, CX_ERR_STATE, "no grid: call cx_grid_upload or cx_grid_adopt_device first");
-    if (!(value == value)) return fail(ctx, CX_ERR_INVALID, "isovalue is NaN");
+    if (!ctx->grid.p) return cx_fail(ctx, CX_ERR_STATE, "no grid: call cx_grid_upload or cx_grid_adopt_device first");
+    if (!(value == value)) return cx_fail(ctx, CX_ERR_INVALID, "isovalue is NaN");
     // the flags are the five documented ones, in every process
     if ((flags & ~(uint32_t)(CX_DIAG_CPYTHON310 | CX_KERNEL_GENERIC | CX_KERNEL_STAGED | CX_KERNEL_FUSED | CX_KERNEL_TILED)) != 0u)
-        return fail(ctx, CX_ERR_INVALID, "unknown flag bits in cx_extract3d");
+        return cx_fail(ctx, CX_ERR_INVALID, "unknown flag bits in cx_extract3d");
     const int64_t N = ctx->n0 * ctx->n1 * ctx->n2;
     if (!ctx->cells || !ctx->verts || !ctx->tris) {
         int rc = cx_reserve(ctx, N / 16 + 4096, N / 8 + 4096, N / 4 + 4096);
@@ -437,7 +432,7 @@ extern "C" int cx_extract3d_async(cx_ctx* ctx, double value, uint32_t flags) {
 
 extern "C" int cx_counts_get(cx_ctx* ctx, cx_counts* out) {
     if (!ctx || !out) return CX_ERR_INVALID;
-    if (!ctx->extracted) return fail(ctx, CX_ERR_STATE, "no extraction enqueued");
+    if (!ctx->extracted) return cx_fail(ctx, CX_ERR_STATE, "no extraction enqueued");
     if (ctx->counts_fetched) { *out = ctx->counts; return CX_OK; }   // the device counters may belong to a later 4-D march
     CX_HIP(ctx, hipSetDevice(ctx->device));
     CX_HIP(ctx, hipMemcpyAsync(ctx->counters_host, ctx->counters, CX_CNT_WORDS * sizeof(uint32_t),
@@ -451,7 +446,7 @@ extern "C" int cx_counts_get(cx_ctx* ctx, cx_counts* out) {
     if (out->n_cells > ctx->ccap() || out->n_vertices > ctx->vcap() || out->n_triangles > ctx->tcap() ||
         (ctx->last.flat && ctx->counters_host[CX_CNT_BATCHES] > ctx->last.fcap)) {
         ctx->extracted = false;
-        return fail(ctx, CX_ERR_CAPACITY, "output buffers too small for this isosurface");
+        return cx_fail(ctx, CX_ERR_CAPACITY, "output buffers too small for this isosurface");
     }
     if (ctx->path == 3 && (ctx->counters_host[CX_CNT_NEAR] != 0u || ctx->counters_host[CX_CNT_TILEOVF] != 0u)) {
         // a wave on the tolerance path, or a tile with more surface cells than a workgroup's LDS words: the tile kernels have
@@ -486,14 +481,14 @@ extern "C" int cx_extract3d(cx_ctx* ctx, double value, uint32_t flags, cx_counts
                         c.n_triangles + c.n_triangles / 20 + 1024);
         if (rc) return rc;
     }
-    return fail(ctx, CX_ERR_CAPACITY, "output buffers still too small after growing");
+    return cx_fail(ctx, CX_ERR_CAPACITY, "output buffers still too small after growing");
 }
 
 // cell records {lin, sign|tetskip<<8|ntri<<16|emask<<24, first triangle, first vertex} of the last extraction: the default path
 // leaves the slim ones, the fused and tile emit kernels none; callers that walk the surface voxels (seeded selection) get the full
 // ones from a records-only pass -- the vertex stage of the staged kernels over the same queues, storing cell records and nothing else
 int cx_ensure_cell_records(cx_ctx* ctx) {
-    if (!ctx->extracted) return fail(ctx, CX_ERR_STATE, "no valid extraction");
+    if (!ctx->extracted) return cx_fail(ctx, CX_ERR_STATE, "no valid extraction");
     if (ctx->records_valid) return CX_OK;
     cx_params P = ctx->last;
     P.records_only = 1u;                 // no vertex records (they are in place) and no info words (the fused path has no buffer for them)
@@ -526,7 +521,7 @@ int cx_level0_expanded(cx_ctx* ctx, float4** out) {
 
 extern "C" int cx_level0_download(cx_ctx* ctx, float* verts_xyzk, int32_t* tris) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!ctx->extracted) return fail(ctx, CX_ERR_STATE, "no valid extraction");
+    if (!ctx->extracted) return cx_fail(ctx, CX_ERR_STATE, "no valid extraction");
     CX_HIP(ctx, hipSetDevice(ctx->device));
     float4* xyz = nullptr;
     if (verts_xyzk && ctx->counts.n_vertices) {
@@ -541,7 +536,7 @@ extern "C" int cx_level0_download(cx_ctx* ctx, float* verts_xyzk, int32_t* tris)
 
 extern "C" int cx_level0_device_ptrs(cx_ctx* ctx, void** verts_xyzk, void** tris) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!ctx->extracted) return fail(ctx, CX_ERR_STATE, "no valid extraction");
+    if (!ctx->extracted) return cx_fail(ctx, CX_ERR_STATE, "no valid extraction");
     CX_HIP(ctx, hipSetDevice(ctx->device));
     if (verts_xyzk) {
         cx_counts c;
@@ -557,7 +552,7 @@ extern "C" int cx_level0_device_ptrs(cx_ctx* ctx, void** verts_xyzk, void** tris
 
 extern "C" int cx_level0_download_records(cx_ctx* ctx, uint32_t* vertex_records, int32_t* tris) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!ctx->extracted) return fail(ctx, CX_ERR_STATE, "no valid extraction");
+    if (!ctx->extracted) return cx_fail(ctx, CX_ERR_STATE, "no valid extraction");
     CX_HIP(ctx, hipSetDevice(ctx->device));
     cx_counts c;
     const int rc = cx_counts_get(ctx, &c);
@@ -570,7 +565,7 @@ extern "C" int cx_level0_download_records(cx_ctx* ctx, uint32_t* vertex_records,
 
 extern "C" int cx_level0_device_records(cx_ctx* ctx, void** vertex_records, void** tris) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!ctx->extracted) return fail(ctx, CX_ERR_STATE, "no valid extraction");
+    if (!ctx->extracted) return cx_fail(ctx, CX_ERR_STATE, "no valid extraction");
     if (vertex_records) *vertex_records = ctx->verts;
     if (tris) *tris = ctx->tris;
     return CX_OK;
@@ -631,14 +626,14 @@ static int read_bandwidth(cx_ctx* ctx, const void* device_ptr, size_t n16, int r
     return CX_OK;
 }
 extern "C" int cx_measure_read_bandwidth(cx_ctx* ctx, const void* device_ptr, int64_t bytes, int reps, double* out_GBps) {
-    if (!ctx || !device_ptr || bytes < (1 << 20) || reps < 1 || !out_GBps) return ctx ? fail(ctx, CX_ERR_INVALID, "cx_measure_read_bandwidth: bad argument") : CX_ERR_INVALID;
+    if (!ctx || !device_ptr || bytes < (1 << 20) || reps < 1 || !out_GBps) return ctx ? cx_fail(ctx, CX_ERR_INVALID, "cx_measure_read_bandwidth: bad argument") : CX_ERR_INVALID;
     CX_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->counters) return fail(ctx, CX_ERR_STATE, "context has no scratch words yet (extract once first)");
+    if (!ctx->counters) return cx_fail(ctx, CX_ERR_STATE, "context has no scratch words yet (extract once first)");
     // one way out for the sink and the two events, whatever fails in between
     cx_buf<uint32_t> sink;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int rc = sink.grow(ctx, 256);
-    if (!rc && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = fail(ctx, CX_ERR_HIP, "cx_measure_read_bandwidth: hipEventCreate failed");
+    if (!rc && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) rc = cx_fail(ctx, CX_ERR_HIP, "cx_measure_read_bandwidth: hipEventCreate failed");
     if (!rc) rc = read_bandwidth(ctx, device_ptr, (size_t)bytes / 16u, reps, e0, e1, sink, out_GBps);
     if (rc) (void)hipStreamSynchronize(ctx->stream);   // nothing enqueued here outlives the sink
     if (e0) (void)hipEventDestroy(e0);

@@ -376,10 +376,6 @@ __global__ void cx_k_level1_sample(const cx_grid_ref B, const cxa_edge1* __restr
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------
-static int cxa_fail(cx_ctx* ctx, int code, const char* msg) {
-    ctx->err = msg;
-    return code;
-}
 static cxa_dims cxa_dims_of(const cx_ctx* ctx) {
     cxa_dims D;
     D.n0 = (uint32_t)ctx->n0; D.n1 = (uint32_t)ctx->n1; D.n2 = (uint32_t)ctx->n2;
@@ -421,7 +417,7 @@ static int cxa_level0(cx_ctx* ctx, const char* who, uint32_t* nv) {
 
 extern "C" int cx_level0_normals(cx_ctx* ctx, const double* delta3, void** normals_dev) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!cxa_delta_ok(delta3)) return cxa_fail(ctx, CX_ERR_INVALID, "cx_level0_normals: the spacing must be positive and finite");
+    if (!cxa_delta_ok(delta3)) return cx_fail(ctx, CX_ERR_INVALID, "cx_level0_normals: the spacing must be positive and finite");
     uint32_t nv = 0;
     int rc = cxa_level0(ctx, "cx_level0_normals", &nv);
     if (rc) return rc;
@@ -508,25 +504,25 @@ static int cxa_carried(cx_ctx* ctx, const double* delta3, void** normals_dev, ui
     const int mode = cx_level1_carried_normals(ctx, &N, &nv);
     if (!mode) return 0;
     *rc = CX_OK;
-    if (mode == 2) { *rc = cxa_fail(ctx, CX_ERR_UNSUPPORTED, "cx_level1_normals: the mesh was simplified without CX_SIMPLIFY_NORMALS: it carries no normals"); return 1; }
+    if (mode == 2) { *rc = cx_fail(ctx, CX_ERR_UNSUPPORTED, "cx_level1_normals: the mesh was simplified without CX_SIMPLIFY_NORMALS: it carries no normals"); return 1; }
     if (normals_dev) *normals_dev = nullptr;
     if (nv_out) *nv_out = nv;
     if (!nv) return 1;
-    if (hipSetDevice(ctx->device) != hipSuccess) { *rc = cxa_fail(ctx, CX_ERR_HIP, "cx_level1_normals: hipSetDevice"); return 1; }
+    if (hipSetDevice(ctx->device) != hipSuccess) { *rc = cx_fail(ctx, CX_ERR_HIP, "cx_level1_normals: hipSetDevice"); return 1; }
     if (ctx->attr_n1.cap() < (size_t)nv * 3u && (*rc = ctx->attr_n1.grow(ctx, ((size_t)nv + nv / 16u + 64u) * 3u))) return 1;
     hipLaunchKernelGGL(cx_k_carried_normals, dim3(cx_blocks(nv)), dim3(256), 0, ctx->stream, N, nv, delta3 ? 1 : 0, delta3 ? delta3[0] : 1.0, delta3 ? delta3[1] : 1.0,
                        delta3 ? delta3[2] : 1.0, ctx->attr_n1);
-    if (hipGetLastError() != hipSuccess) { *rc = cxa_fail(ctx, CX_ERR_HIP, "cx_level1_normals: launch of the carried normals failed"); return 1; }
+    if (hipGetLastError() != hipSuccess) { *rc = cx_fail(ctx, CX_ERR_HIP, "cx_level1_normals: launch of the carried normals failed"); return 1; }
     if (normals_dev) *normals_dev = ctx->attr_n1;
     return 1;
 }
 
 extern "C" int cx_level1_normals(cx_ctx* ctx, const double* delta3, void** normals_dev) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!cxa_delta_ok(delta3)) return cxa_fail(ctx, CX_ERR_INVALID, "cx_level1_normals: the spacing must be positive and finite");
+    if (!cxa_delta_ok(delta3)) return cx_fail(ctx, CX_ERR_INVALID, "cx_level1_normals: the spacing must be positive and finite");
     int rcc = CX_OK;
     if (cxa_carried(ctx, delta3, normals_dev, nullptr, &rcc)) return rcc;
-    if (cx_level1_capped(ctx)) return cxa_fail(ctx, CX_ERR_UNSUPPORTED, "cx_level1_normals: a capped mesh (cx_postprocess3d_capped) has a crease along the rim and no single normal there");
+    if (cx_level1_capped(ctx)) return cx_fail(ctx, CX_ERR_UNSUPPORTED, "cx_level1_normals: a capped mesh (cx_postprocess3d_capped) has a crease along the rim and no single normal there");
     cx_level1_view V;
     int rc = cxa_level1(ctx, "cx_level1_normals", &V);
     if (rc) return rc;
@@ -588,7 +584,7 @@ static int cxa_curvature_axes(cx_ctx* ctx, const char* who) {
 
 extern "C" int cx_level0_curvature(cx_ctx* ctx, const double* delta3, void** curv_dev) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!cxa_delta_ok(delta3)) return cxa_fail(ctx, CX_ERR_INVALID, "cx_level0_curvature: the spacing must be positive and finite");
+    if (!cxa_delta_ok(delta3)) return cx_fail(ctx, CX_ERR_INVALID, "cx_level0_curvature: the spacing must be positive and finite");
     uint32_t nv = 0;
     int rc = cxa_level0(ctx, "cx_level0_curvature", &nv);
     if (rc) return rc;
@@ -620,8 +616,8 @@ extern "C" int cx_level0_curvature_download(cx_ctx* ctx, const double* delta3, f
 // (a simplified mesh is refused by cx_level1_attr_view: its vertices are cluster means, and no curvature is carried over)
 extern "C" int cx_level1_curvature(cx_ctx* ctx, const double* delta3, void** curv_dev) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!cxa_delta_ok(delta3)) return cxa_fail(ctx, CX_ERR_INVALID, "cx_level1_curvature: the spacing must be positive and finite");
-    if (cx_level1_capped(ctx)) return cxa_fail(ctx, CX_ERR_UNSUPPORTED, "cx_level1_curvature: a capped mesh (cx_postprocess3d_capped) has a crease along the rim and flat caps: no curvature of the field there");
+    if (!cxa_delta_ok(delta3)) return cx_fail(ctx, CX_ERR_INVALID, "cx_level1_curvature: the spacing must be positive and finite");
+    if (cx_level1_capped(ctx)) return cx_fail(ctx, CX_ERR_UNSUPPORTED, "cx_level1_curvature: a capped mesh (cx_postprocess3d_capped) has a crease along the rim and flat caps: no curvature of the field there");
     cx_level1_view V;
     int rc = cxa_level1(ctx, "cx_level1_curvature", &V);
     if (rc) return rc;

@@ -202,24 +202,15 @@ struct cx_ctx {
     // choosing isovalues (cx_pick.hip): histograms of the select, difference arrays and tables of the spectrum, the device copy of host
     // samples, kept between calls.  Scratch only: nothing here describes the current extraction
     struct cx_pick_state* pick = nullptr;
-    // preparing the volume (cx_filter.hip): the device copy of host samples, the result of the first kernel, and the context's own result
-    // until cx_grid_filter3d_bind makes it the bound grid.  Nothing here describes the current extraction
+    // the whole-volume operations: filter, distance transform, components (the mask of cx_grid_label3d_select), resampling, rank filters,
+    // reconstruction.  Each keeps a cx_slot of its own (cx_gridop.h: the device copy of host samples and the context's own result until
+    // the operation's _bind makes it the bound grid) beside its scratch, so that none disturbs another's pending result.  Nothing here
+    // describes the current extraction
     struct cx_filter_state* filt = nullptr;
-    // distance fields (cx_dist.hip): the device copy of host samples, the signed squared distances between the passes, and the context's
-    // own result until cx_grid_distance3d_bind makes it the bound grid: a slot of its own, beside the filter's
     struct cx_dist_state* dist = nullptr;
-    // connected components of a thresholded volume (cx_label.hip): the device copy of host samples, the labels (pending until the next
-    // cx_grid_label3d), their records, and the mask of cx_grid_label3d_select until cx_grid_label3d_bind makes it the bound grid: a slot
-    // of its own, beside the filter's and the distance transform's
     struct cx_label_state* label = nullptr;
-    // resampling through an affine map (cx_resample.hip): the device copy of host samples, the table of the axis-aligned kernel, and the
-    // context's own result until cx_grid_resample3d_bind makes it the bound grid: a slot of its own, beside the other three
     struct cx_resample_state* resample = nullptr;
-    // rank filters (cx_rank.hip): the device copy of host samples and the context's own result until cx_grid_rank3d_bind makes it the
-    // bound grid: a slot of its own, beside the other four
     struct cx_rank_state* rank = nullptr;
-    // morphological reconstruction (cx_recon.hip): the device copies of a host mask and marker, the working keys, the tile lists, and
-    // the context's own result until cx_grid_reconstruct3d_bind makes it the bound grid: a slot of its own, beside the other five
     struct cx_recon_state* recon = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
@@ -239,6 +230,12 @@ struct cx_ctx {
     int nevents = 0;
     evset events[256];
 };
+
+// a refusal: the text into the context (where there is one), the code back to the caller
+static inline int cx_fail(cx_ctx* ctx, int code, const char* msg) {
+    if (ctx) ctx->err = msg;
+    return code;
+}
 
 template <typename T>
 int cx_buf<T>::fail(cx_ctx* ctx, size_t bytes, hipError_t e) {

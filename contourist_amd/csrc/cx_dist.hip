@@ -24,23 +24,19 @@
 #include <new>
 #include <string>
 
-#include "cx_ctx.h"
 #include "cx_dev.h"
+#include "cx_gridop.h"
 
 #pragma clang fp contract(off)
 
 #define CXD_WAVES 4u
 #define CXD_BATCH 4      // distances per round of the outward scan: 2 CXD_BATCH loads in flight
 
-struct cx_dist_state {
-    cx_buf<uint8_t> in;        // host samples
+struct cx_dist_state : cx_slot {      // (the result is bytes of `kind`)
     cx_buf<double> a, b;       // the signed squared distances after axis 2 / axis 1
     cx_buf<unsigned long long> nlow;
-    cx_buf<uint8_t> result;    // the context's own result (bytes of the kind: cx_grid_distance3d_bind moves it into ctx->grid_owned)
-    int64_t shape[3] = {0, 0, 0};
     int32_t kind = 0;
     int64_t n_sites = 0;
-    bool pending = false;      // `result` holds the result of the last call and has not been bound
 };
 
 void cx_dist_free(cx_ctx* ctx) {
@@ -175,14 +171,6 @@ __global__ __launch_bounds__(256) void cxd_k_walk(const cxd_walk_args A) {
     }
 }
 
-static int cxd_invalid(cx_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return CX_ERR_INVALID;
-}
-static int cxd_state(cx_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return CX_ERR_STATE;
-}
 static size_t cxd_kind_size(int32_t kind) { return kind == CX_DIST_OUT_SQUARED_F64 ? 8u : kind == CX_DIST_OUT_F32 ? 4u : 1u; }
 static uint32_t cxd_grid(unsigned long long items) {
     const unsigned long long blocks = (items + CXD_WAVES - 1u) / CXD_WAVES;
@@ -193,57 +181,36 @@ extern "C" int cx_grid_distance3d(cx_ctx* ctx, const void* samples, int32_t dtyp
                                   double value, const double sampling[3], int32_t side, int32_t out_kind, double radius2,
                                   void* out_device, void* out_host, int64_t* n_sites) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!std::isfinite(value)) return cxd_invalid(ctx, "cx_grid_distance3d: value is NaN or infinite");
-    if (side != CX_DIST_BELOW && side != CX_DIST_ABOVE && side != CX_DIST_SIGNED) return cxd_invalid(ctx, "cx_grid_distance3d: unknown side");
+    if (!std::isfinite(value)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_distance3d: value is NaN or infinite");
+    if (side != CX_DIST_BELOW && side != CX_DIST_ABOVE && side != CX_DIST_SIGNED) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_distance3d: unknown side");
     if (out_kind != CX_DIST_OUT_SQUARED_F64 && out_kind != CX_DIST_OUT_F32 && out_kind != CX_DIST_OUT_MASK_U8)
-        return cxd_invalid(ctx, "cx_grid_distance3d: unknown output kind");
+        return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_distance3d: unknown output kind");
     if (out_kind == CX_DIST_OUT_MASK_U8) {
-        if (side == CX_DIST_SIGNED) return cxd_invalid(ctx, "cx_grid_distance3d: a mask of a signed distance");
-        if (!std::isfinite(radius2) || radius2 < 0.0) return cxd_invalid(ctx, "cx_grid_distance3d: radius2 is a finite number >= 0");
+        if (side == CX_DIST_SIGNED) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_distance3d: a mask of a signed distance");
+        if (!std::isfinite(radius2) || radius2 < 0.0) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_distance3d: radius2 is a finite number >= 0");
     }
     double w[3] = {1.0, 1.0, 1.0};
     if (sampling)
         for (int a = 0; a < 3; a++) {
-            if (!std::isfinite(sampling[a]) || !(sampling[a] > 0.0)) return cxd_invalid(ctx, "cx_grid_distance3d: sampling is finite and > 0 on every axis");
+            if (!std::isfinite(sampling[a]) || !(sampling[a] > 0.0)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_distance3d: sampling is finite and > 0 on every axis");
             w[a] = sampling[a] * sampling[a];
-            if (!std::isnormal(w[a])) return cxd_invalid(ctx, "cx_grid_distance3d: the square of a sampling step is not a normal double");
+            if (!std::isnormal(w[a])) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_distance3d: the square of a sampling step is not a normal double");
         }
-    if (!samples) {
-        if (!ctx->grid.p) return cxd_state(ctx, "cx_grid_distance3d: no samples given and no grid bound");
-        dtype = ctx->grid.dtype; n0 = ctx->n0; n1 = ctx->n1; n2 = ctx->n2; on_device = 1;
-    } else {
-        if (!cx_dtype_valid(dtype)) return cxd_invalid(ctx, "cx_grid_distance3d: unknown sample type");
-        if (n0 < 1 || n1 < 1 || n2 < 1 || n0 > (1LL << 29) || n1 > (1LL << 29) || n2 > (1LL << 29) || n0 * n1 > (1LL << 29) || n0 * n1 * n2 > (1LL << 29))
-            return cxd_invalid(ctx, "cx_grid_distance3d: at least 1 sample per axis, at most 2^29 in all");
-    }
-    const size_t count = (size_t)(n0 * n1 * n2), in_bytes = count * cx_dtype_size(dtype), out_bytes = count * cxd_kind_size(out_kind);
-    const void* dev = samples ? samples : ctx->grid.p;
-    if (out_device && on_device) {
-        const uintptr_t a0 = (uintptr_t)dev, a1 = a0 + in_bytes, b0 = (uintptr_t)out_device, b1 = b0 + out_bytes;
-        if (a0 < b1 && b0 < a1) return cxd_invalid(ctx, "cx_grid_distance3d: the output overlaps the input");
-    }
+    cx_source S;
+    int rc = cx_source_resolve(ctx, "cx_grid_distance3d", samples, dtype, on_device, n0, n1, n2, 29, &S);
+    if (rc) return rc;
+    n0 = S.n[0]; n1 = S.n[1]; n2 = S.n[2];
+    const size_t count = S.count, out_bytes = count * cxd_kind_size(out_kind);
+    if (out_device && S.on_device && cx_overlap(S.p, S.bytes, out_device, out_bytes))
+        return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_distance3d: the output overlaps the input");
     CX_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->dist) ctx->dist = new (std::nothrow) cx_dist_state();
-    cx_dist_state* D = ctx->dist;
+    cx_dist_state* D = cx_state_of(ctx->dist);
     if (!D) return CX_ERR_NOMEM;
     hipStream_t st = ctx->stream;
-    int rc;
-    if (samples && on_device && D->result.get() && samples == D->result.get()) {
-        // the result of the call before is the input of this one (the second step of an opening or closing): it changes places with
-        // the scratch for host samples, so that this call's own result cannot land on it
-        std::swap(D->in, D->result);
-        dev = D->in.get();
-    } else if (samples && !on_device) {
-        if ((rc = D->in.grow(ctx, in_bytes))) return rc;
-        CX_HIP(ctx, hipMemcpyAsync(D->in, samples, in_bytes, hipMemcpyHostToDevice, st));
-        dev = D->in.get();
-    }
-    D->pending = false;      // the result of this call, or none: a caller's output leaves nothing to hand out or bind
-    void* final_out = out_device;
-    if (!out_device) {
-        if ((rc = D->result.grow(ctx, out_bytes))) return rc;
-        final_out = D->result.get();
-    }
+    const void* dev;
+    void* final_out;
+    // (the result of the call before may be the input of this one: the second step of an opening or closing)
+    if ((rc = D->stage(ctx, S, &dev)) || (rc = D->open(ctx, out_device, out_bytes, &final_out))) return rc;
     if ((rc = D->a.grow(ctx, count)) || (rc = D->b.grow(ctx, count)) || (rc = D->nlow.grow(ctx, 1))) return rc;
     CX_HIP(ctx, hipMemsetAsync(D->nlow, 0, sizeof(unsigned long long), st));
     cxd_rows_args R;
@@ -251,7 +218,7 @@ extern "C" int cx_grid_distance3d(cx_ctx* ctx, const void* samples, int32_t dtyp
     R.in = dev; R.out = D->a.get(); R.nlow = D->nlow.get();
     R.rows = n0 * n1; R.n2 = n2; R.value = value; R.w2 = w[2];
 #define CX_LAUNCH(DT) hipLaunchKernelGGL((cxd_k_rows<DT>), dim3(cxd_grid((unsigned long long)R.rows)), dim3(256), 0, st, R);
-    CX_DISPATCH_DTYPE(dtype, CX_LAUNCH)
+    CX_DISPATCH_DTYPE(S.dtype, CX_LAUNCH)
 #undef CX_LAUNCH
     CX_HIP(ctx, hipGetLastError());
     cxd_walk_args W;
@@ -276,17 +243,16 @@ extern "C" int cx_grid_distance3d(cx_ctx* ctx, const void* samples, int32_t dtyp
     CX_HIP(ctx, hipStreamSynchronize(st));      // the count is the caller's, and its host memory is its own again
     const int64_t low = (int64_t)nlow, high = (int64_t)count - low;
     const int64_t sites = side == CX_DIST_BELOW ? high : side == CX_DIST_ABOVE ? low : (low < high ? low : high);
-    if (!out_device) { D->shape[0] = n0; D->shape[1] = n1; D->shape[2] = n2; D->kind = out_kind; D->n_sites = sites; D->pending = true; }
+    if (!out_device) { D->publish(n0, n1, n2); D->kind = out_kind; D->n_sites = sites; }
     if (n_sites) *n_sites = sites;
     return CX_OK;
 }
 
 extern "C" int cx_grid_distance3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_kind, int64_t* n_sites) {
     if (!ctx) return CX_ERR_INVALID;
-    cx_dist_state* D = ctx->dist;
-    if (!D || !D->pending) return cxd_state(ctx, "cx_grid_distance3d_result: no result of cx_grid_distance3d in the context");
-    if (out_device) *out_device = D->result.get();
-    if (out_shape) { out_shape[0] = D->shape[0]; out_shape[1] = D->shape[1]; out_shape[2] = D->shape[2]; }
+    const cx_dist_state* D = ctx->dist;
+    const int rc = cx_slot_result(ctx, D, "cx_grid_distance3d_result: no result of cx_grid_distance3d in the context", out_device, out_shape);
+    if (rc) return rc;
     if (out_kind) *out_kind = D->kind;
     if (n_sites) *n_sites = D->n_sites;
     return CX_OK;
@@ -295,13 +261,9 @@ extern "C" int cx_grid_distance3d_result(cx_ctx* ctx, void** out_device, int64_t
 extern "C" int cx_grid_distance3d_bind(cx_ctx* ctx) {
     if (!ctx) return CX_ERR_INVALID;
     cx_dist_state* D = ctx->dist;
-    if (!D || !D->pending) return cxd_state(ctx, "cx_grid_distance3d_bind: no result of cx_grid_distance3d in the context");
-    if (D->kind == CX_DIST_OUT_SQUARED_F64) return cxd_invalid(ctx, "cx_grid_distance3d_bind: squared distances in double are not a grid the march reads");
-    if (D->kind == CX_DIST_OUT_F32 && D->n_sites == 0) return cxd_invalid(ctx, "cx_grid_distance3d_bind: the result is infinite (a side without a site)");
-    CX_HIP(ctx, hipSetDevice(ctx->device));
-    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int rc = cx_grid_bind_owned(ctx, D->result, D->kind == CX_DIST_OUT_F32 ? CX_DTYPE_F32 : CX_DTYPE_U8, D->shape[0], D->shape[1], D->shape[2]);
-    if (rc) return rc;
-    D->pending = false;
-    return CX_OK;
+    if (D && D->pending) {
+        if (D->kind == CX_DIST_OUT_SQUARED_F64) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_distance3d_bind: squared distances in double are not a grid the march reads");
+        if (D->kind == CX_DIST_OUT_F32 && D->n_sites == 0) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_distance3d_bind: the result is infinite (a side without a site)");
+    }
+    return cx_slot_bind(ctx, D, "cx_grid_distance3d_bind: no result of cx_grid_distance3d in the context", D && D->kind == CX_DIST_OUT_F32 ? CX_DTYPE_F32 : CX_DTYPE_U8);
 }

@@ -23,8 +23,8 @@
 #include <new>
 #include <string>
 
-#include "cx_ctx.h"
 #include "cx_dev.h"
+#include "cx_gridop.h"
 
 #define CXF_MAXW 129
 #define CXF_R 16          // outputs along the walked axis per wave: (CXF_R - 1) stride + taps input rows for CXF_R output rows
@@ -32,12 +32,8 @@
 #define CXF_WAVES 4u
 #define CXF_WROWS 32u     // rows of the wave's window of walked samples (fp32, 64 lanes each): 8 KB per wave
 
-struct cx_filter_state {
-    cx_buf<uint8_t> in;        // host samples
+struct cx_filter_state : cx_slot {      // (the result is fp32)
     cx_buf<float> mid;         // the result of cxf_k_rows where cxf_k_planes follows
-    cx_buf<uint8_t> result;    // the context's own result (fp32, kept as bytes: cx_grid_filter3d_bind moves it into ctx->grid_owned)
-    int64_t shape[3] = {0, 0, 0};
-    bool pending = false;      // `result` holds the result of the last call and has not been bound
 };
 
 void cx_filter_free(cx_ctx* ctx) {
@@ -362,15 +358,6 @@ __global__ __launch_bounds__(256) void cxf_k_planes(const cxf_args A) {
     }
 }
 
-static int cxf_invalid(cx_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return CX_ERR_INVALID;
-}
-static int cxf_state(cx_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return CX_ERR_STATE;
-}
-
 static void cxf_axis_fill(cxf_axis& X, const cx_filter_axis& a, int64_t n) {
     memset(&X, 0, sizeof(X));
     const bool filtered = a.weights && a.n_weights > 0;
@@ -398,23 +385,18 @@ static uint32_t cxf_grid(unsigned long long items) {
 extern "C" int cx_grid_filter3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_device, int64_t n0, int64_t n1, int64_t n2,
                                 const cx_filter_axis axes[3], int32_t mode, double cval, void* out_device, float* out_host, int64_t out_shape[3]) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!axes) return cxf_invalid(ctx, "cx_grid_filter3d: no axes");
-    if (mode != CX_FILTER_NEAREST && mode != CX_FILTER_REFLECT && mode != CX_FILTER_CONSTANT) return cxf_invalid(ctx, "cx_grid_filter3d: unknown mode");
-    if (!std::isfinite(cval)) return cxf_invalid(ctx, "cx_grid_filter3d: cval is NaN or infinite");
-    if (!samples) {
-        if (!ctx->grid.p) return cxf_state(ctx, "cx_grid_filter3d: no samples given and no grid bound");
-        dtype = ctx->grid.dtype; n0 = ctx->n0; n1 = ctx->n1; n2 = ctx->n2; on_device = 1;
-    } else {
-        if (!cx_dtype_valid(dtype)) return cxf_invalid(ctx, "cx_grid_filter3d: unknown sample type");
-        if (n0 < 1 || n1 < 1 || n2 < 1 || n0 > (1LL << 31) || n1 > (1LL << 31) || n2 > (1LL << 31) || n0 * n1 > (1LL << 31) || n0 * n1 * n2 > (1LL << 31))
-            return cxf_invalid(ctx, "cx_grid_filter3d: at least 1 sample per axis, at most 2^31 in all");
-    }
-    const int64_t n[3] = {n0, n1, n2};
+    if (!axes) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_filter3d: no axes");
+    if (mode != CX_FILTER_NEAREST && mode != CX_FILTER_REFLECT && mode != CX_FILTER_CONSTANT) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_filter3d: unknown mode");
+    if (!std::isfinite(cval)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_filter3d: cval is NaN or infinite");
+    cx_source S;
+    int rc = cx_source_resolve(ctx, "cx_grid_filter3d", samples, dtype, on_device, n0, n1, n2, 31, &S);
+    if (rc) return rc;
+    n0 = S.n[0]; n1 = S.n[1]; n2 = S.n[2];
     for (int a = 0; a < 3; a++) {
-        if (axes[a].stride < 1 || (int64_t)axes[a].stride > n[a]) return cxf_invalid(ctx, "cx_grid_filter3d: a stride outside 1..n");
+        if (axes[a].stride < 1 || (int64_t)axes[a].stride > S.n[a]) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_filter3d: a stride outside 1..n");
         if (axes[a].weights && axes[a].n_weights != 0) {
-            if (axes[a].n_weights < 1 || axes[a].n_weights > CXF_MAXW) return cxf_invalid(ctx, "cx_grid_filter3d: 1..129 weights per axis");
-            if (axes[a].origin < 0 || axes[a].origin >= axes[a].n_weights) return cxf_invalid(ctx, "cx_grid_filter3d: an origin outside 0..n_weights-1");
+            if (axes[a].n_weights < 1 || axes[a].n_weights > CXF_MAXW) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_filter3d: 1..129 weights per axis");
+            if (axes[a].origin < 0 || axes[a].origin >= axes[a].n_weights) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_filter3d: an origin outside 0..n_weights-1");
         }
     }
     cxf_args R, P;      // the two kernels
@@ -424,29 +406,17 @@ extern "C" int cx_grid_filter3d(cx_ctx* ctx, const void* samples, int32_t dtype,
     cxf_axis_fill(P.walk, axes[0], n0);
     const int64_t m0 = P.walk.m, m1 = R.walk.m, m2 = R.inner.m;
     const bool two = P.walk.nw != 0;      // axis 0 filtered: cxf_k_planes follows; else cxf_k_rows visits the kept planes only
-    const size_t in_bytes = (size_t)(n0 * n1 * n2) * cx_dtype_size(dtype), out_count = (size_t)(m0 * m1 * m2);
-    const void* dev = samples ? samples : ctx->grid.p;
-    if (out_device && on_device) {
-        const uintptr_t a0 = (uintptr_t)dev, a1 = a0 + in_bytes, b0 = (uintptr_t)out_device, b1 = b0 + out_count * sizeof(float);
-        if (a0 < b1 && b0 < a1) return cxf_invalid(ctx, "cx_grid_filter3d: the output overlaps the input");
-    }
+    const size_t out_count = (size_t)(m0 * m1 * m2);
+    if (out_device && S.on_device && cx_overlap(S.p, S.bytes, out_device, out_count * sizeof(float)))
+        return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_filter3d: the output overlaps the input");
     CX_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->filt) ctx->filt = new (std::nothrow) cx_filter_state();
-    cx_filter_state* F = ctx->filt;
+    cx_filter_state* F = cx_state_of(ctx->filt);
     if (!F) return CX_ERR_NOMEM;
     hipStream_t st = ctx->stream;
-    int rc;
-    if (samples && !on_device) {
-        if ((rc = F->in.grow(ctx, in_bytes))) return rc;
-        CX_HIP(ctx, hipMemcpyAsync(F->in, samples, in_bytes, hipMemcpyHostToDevice, st));
-        dev = F->in.get();
-    }
-    float* final_out = static_cast<float*>(out_device);
-    F->pending = false;      // the result of this call, or none: a caller's output leaves nothing to hand out or bind
-    if (!out_device) {
-        if ((rc = F->result.grow(ctx, out_count * sizeof(float)))) return rc;
-        final_out = F->result.as<float>();
-    }
+    const void* dev;
+    void* out;
+    if ((rc = F->stage(ctx, S, &dev)) || (rc = F->open(ctx, out_device, out_count * sizeof(float), &out))) return rc;
+    float* final_out = static_cast<float*>(out);
     if (two && (rc = F->mid.grow(ctx, (size_t)(n0 * m1 * m2)))) return rc;
     R.in = dev; R.out = two ? F->mid.get() : final_out;
     R.planes = two ? n0 : m0; R.plane_step = two ? 1 : P.walk.stride;
@@ -458,7 +428,7 @@ extern "C" int cx_grid_filter3d(cx_ctx* ctx, const void* samples, int32_t dtype,
 #define CX_LAUNCH(DT)                                                                                          \
     if (big) hipLaunchKernelGGL((cxf_k_rows<DT, true>), dim3(cxf_grid(R.items)), dim3(256), 0, st, R);         \
     else hipLaunchKernelGGL((cxf_k_rows<DT, false>), dim3(cxf_grid(R.items)), dim3(256), 0, st, R);
-    CX_DISPATCH_DTYPE(dtype, CX_LAUNCH)
+    CX_DISPATCH_DTYPE(S.dtype, CX_LAUNCH)
 #undef CX_LAUNCH
     CX_HIP(ctx, hipGetLastError());
     if (two) {
@@ -473,30 +443,19 @@ extern "C" int cx_grid_filter3d(cx_ctx* ctx, const void* samples, int32_t dtype,
         else hipLaunchKernelGGL(cxf_k_planes<false>, dim3(cxf_grid(P.items)), dim3(256), 0, st, P);
         CX_HIP(ctx, hipGetLastError());
     }
-    if (!out_device) { F->shape[0] = m0; F->shape[1] = m1; F->shape[2] = m2; F->pending = true; }
+    if (!out_device) F->publish(m0, m1, m2);
     if (out_shape) { out_shape[0] = m0; out_shape[1] = m1; out_shape[2] = m2; }
     if (out_host) CX_HIP(ctx, hipMemcpyAsync(out_host, final_out, out_count * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (out_host || (samples && !on_device)) CX_HIP(ctx, hipStreamSynchronize(st));      // the caller's host memory is its own again
+    if (out_host || !S.on_device) CX_HIP(ctx, hipStreamSynchronize(st));      // the caller's host memory is its own again
     return CX_OK;
 }
 
 extern "C" int cx_grid_filter3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3]) {
     if (!ctx) return CX_ERR_INVALID;
-    cx_filter_state* F = ctx->filt;
-    if (!F || !F->pending) return cxf_state(ctx, "cx_grid_filter3d_result: no result of cx_grid_filter3d in the context");
-    if (out_device) *out_device = F->result.get();
-    if (out_shape) { out_shape[0] = F->shape[0]; out_shape[1] = F->shape[1]; out_shape[2] = F->shape[2]; }
-    return CX_OK;
+    return cx_slot_result(ctx, ctx->filt, "cx_grid_filter3d_result: no result of cx_grid_filter3d in the context", out_device, out_shape);
 }
 
 extern "C" int cx_grid_filter3d_bind(cx_ctx* ctx) {
     if (!ctx) return CX_ERR_INVALID;
-    cx_filter_state* F = ctx->filt;
-    if (!F || !F->pending) return cxf_state(ctx, "cx_grid_filter3d_bind: no result of cx_grid_filter3d in the context");
-    CX_HIP(ctx, hipSetDevice(ctx->device));
-    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the filter may still be reading the grid that goes
-    const int rc = cx_grid_bind_owned(ctx, F->result, CX_DTYPE_F32, F->shape[0], F->shape[1], F->shape[2]);
-    if (rc) return rc;
-    F->pending = false;
-    return CX_OK;
+    return cx_slot_bind(ctx, ctx->filt, "cx_grid_filter3d_bind: no result of cx_grid_filter3d in the context", CX_DTYPE_F32);
 }

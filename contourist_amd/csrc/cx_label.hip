@@ -29,15 +29,14 @@
 #include <new>
 #include <string>
 
-#include "cx_ctx.h"
 #include "cx_dev.h"
+#include "cx_gridop.h"
 
 #define CXL_WAVES 4u
 #define CXL_SELECT_BLOCKS 2048u       // a lane walks its groups of 16 samples with the grid's stride; one count per workgroup
 #define CXL_MEASURE_BLOCKS 1024u      // 4 blocks of 4 waves per compute unit: what every wave carries at its end goes to one record in the worst case
 
 struct cx_label_state {
-    cx_buf<uint8_t> in;          // host samples
     cx_buf<uint32_t> labels;     // the context's own labels (the parents until cxl_k_relabel)
     cx_buf<uint32_t> rank;       // root flags, then their exclusive scan
     cx_buf<u64> bits;            // one ballot per row and tile
@@ -45,15 +44,13 @@ struct cx_label_state {
     cx_buf<u64> misc;            // [0] K (low word), [1] ones of the last select
     cx_buf<cx_label_component> records;
     cx_buf<uint8_t> keep;        // the caller's keep bytes
-    cx_buf<uint8_t> mask;        // the context's own mask (cx_grid_label3d_bind moves it into ctx->grid_owned)
+    cx_slot mask;                // the host samples of cx_grid_label3d, and the context's own mask (the result of cx_grid_label3d_select)
     int64_t shape[3] = {0, 0, 0};
     int32_t side = 0, connectivity = 0;
     int64_t k = 0;
     bool pending = false;        // `labels` holds the result of the last call
     bool measured = false;       // `records` describes them
-    int64_t mask_shape[3] = {0, 0, 0};
     int64_t mask_voxels = 0;
-    bool mask_pending = false;   // `mask` holds the result of the last select and has not been bound
 };
 
 void cx_label_free(cx_ctx* ctx) {
@@ -357,14 +354,6 @@ __global__ __launch_bounds__(256) void cxl_k_select(const cxl_select_args A) {
     }
 }
 
-static int cxl_invalid(cx_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return CX_ERR_INVALID;
-}
-static int cxl_state(cx_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return CX_ERR_STATE;
-}
 static uint32_t cxl_grid_rows(int64_t rows) {
     const unsigned long long blocks = ((unsigned long long)rows + CXL_WAVES - 1u) / CXL_WAVES;
     return (uint32_t)(blocks < (1ull << 20) ? (blocks ? blocks : 1ull) : (1ull << 20));
@@ -373,39 +362,25 @@ static uint32_t cxl_grid_flat(size_t n) {
     const size_t blocks = (n + 255u) / 256u;
     return (uint32_t)(blocks < (1u << 20) ? (blocks ? blocks : 1u) : (1u << 20));
 }
-static bool cxl_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + a_bytes, b0 = (uintptr_t)b, b1 = b0 + b_bytes;
-    return a0 < b1 && b0 < a1;
-}
 
 extern "C" int cx_grid_label3d(cx_ctx* ctx, const void* samples, int32_t dtype, int on_device, int64_t n0, int64_t n1, int64_t n2,
                                double value, int32_t side, int32_t connectivity, int32_t* out_device, int32_t* out_host, int64_t* n_components) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!std::isfinite(value)) return cxl_invalid(ctx, "cx_grid_label3d: value is NaN or infinite");
-    if (side != CX_LABEL_HIGH && side != CX_LABEL_LOW) return cxl_invalid(ctx, "cx_grid_label3d: unknown side");
-    if (connectivity < 1 || connectivity > 3) return cxl_invalid(ctx, "cx_grid_label3d: connectivity is 1, 2 or 3");
-    if (!samples) {
-        if (!ctx->grid.p) return cxl_state(ctx, "cx_grid_label3d: no samples given and no grid bound");
-        dtype = ctx->grid.dtype; n0 = ctx->n0; n1 = ctx->n1; n2 = ctx->n2; on_device = 1;
-    } else {
-        if (!cx_dtype_valid(dtype)) return cxl_invalid(ctx, "cx_grid_label3d: unknown sample type");
-        if (n0 < 1 || n1 < 1 || n2 < 1 || n0 > (1LL << 29) || n1 > (1LL << 29) || n2 > (1LL << 29) || n0 * n1 > (1LL << 29) || n0 * n1 * n2 > (1LL << 29))
-            return cxl_invalid(ctx, "cx_grid_label3d: at least 1 sample per axis, at most 2^29 in all");
-    }
-    const size_t count = (size_t)(n0 * n1 * n2), in_bytes = count * cx_dtype_size(dtype), out_bytes = count * sizeof(int32_t);
-    const void* dev = samples ? samples : ctx->grid.p;
-    if (out_device && on_device && cxl_overlap(dev, in_bytes, out_device, out_bytes)) return cxl_invalid(ctx, "cx_grid_label3d: the output overlaps the input");
+    if (!std::isfinite(value)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_label3d: value is NaN or infinite");
+    if (side != CX_LABEL_HIGH && side != CX_LABEL_LOW) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_label3d: unknown side");
+    if (connectivity < 1 || connectivity > 3) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_label3d: connectivity is 1, 2 or 3");
+    cx_source S;
+    int rc = cx_source_resolve(ctx, "cx_grid_label3d", samples, dtype, on_device, n0, n1, n2, 29, &S);
+    if (rc) return rc;
+    n0 = S.n[0]; n1 = S.n[1]; n2 = S.n[2];
+    const size_t count = S.count, out_bytes = count * sizeof(int32_t);
+    if (out_device && S.on_device && cx_overlap(S.p, S.bytes, out_device, out_bytes)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_label3d: the output overlaps the input");
     CX_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->label) ctx->label = new (std::nothrow) cx_label_state();
-    cx_label_state* L = ctx->label;
+    cx_label_state* L = cx_state_of(ctx->label);
     if (!L) return CX_ERR_NOMEM;
     hipStream_t st = ctx->stream;
-    int rc;
-    if (samples && !on_device) {
-        if ((rc = L->in.grow(ctx, in_bytes))) return rc;
-        CX_HIP(ctx, hipMemcpyAsync(L->in, samples, in_bytes, hipMemcpyHostToDevice, st));
-        dev = L->in.get();
-    }
+    const void* dev = S.p;      // (the labels are no buffer a caller's samples can lie in: nothing steps aside)
+    if (!S.on_device && (rc = cx_upload(ctx, L->mask.in, S.p, S.bytes, &dev))) return rc;
     L->pending = false;      // the labels of this call, or none: a caller's output leaves nothing to hand out or measure
     L->measured = false;
     uint32_t* parent = reinterpret_cast<uint32_t*>(out_device);
@@ -422,7 +397,7 @@ extern "C" int cx_grid_label3d(cx_ctx* ctx, const void* samples, int32_t dtype, 
     R.in = dev; R.parent = parent; R.bits = L->bits.get();
     R.rows = rows; R.n2 = n2; R.tiles = tiles; R.value = value; R.side = side;
 #define CX_LAUNCH(DT) hipLaunchKernelGGL((cxl_k_rows<DT>), dim3(cxl_grid_rows(rows)), dim3(256), 0, st, R);
-    CX_DISPATCH_DTYPE(dtype, CX_LAUNCH)
+    CX_DISPATCH_DTYPE(S.dtype, CX_LAUNCH)
 #undef CX_LAUNCH
     CX_HIP(ctx, hipGetLastError());
     cxl_unite_args U;
@@ -452,7 +427,7 @@ extern "C" int cx_grid_label3d(cx_ctx* ctx, const void* samples, int32_t dtype, 
 extern "C" int cx_grid_label3d_result(cx_ctx* ctx, int32_t** labels_device, int64_t shape[3], int32_t* side, int32_t* connectivity, int64_t* n_components) {
     if (!ctx) return CX_ERR_INVALID;
     cx_label_state* L = ctx->label;
-    if (!L || !L->pending) return cxl_state(ctx, "cx_grid_label3d_result: no labels of cx_grid_label3d in the context");
+    if (!L || !L->pending) return cx_fail(ctx, CX_ERR_STATE, "cx_grid_label3d_result: no labels of cx_grid_label3d in the context");
     if (labels_device) *labels_device = reinterpret_cast<int32_t*>(L->labels.get());
     if (shape) { shape[0] = L->shape[0]; shape[1] = L->shape[1]; shape[2] = L->shape[2]; }
     if (side) *side = L->side;
@@ -464,9 +439,9 @@ extern "C" int cx_grid_label3d_result(cx_ctx* ctx, int32_t** labels_device, int6
 extern "C" int cx_grid_label3d_measures(cx_ctx* ctx, cx_label_component* out_host, int64_t capacity) {
     if (!ctx) return CX_ERR_INVALID;
     cx_label_state* L = ctx->label;
-    if (!L || !L->pending) return cxl_state(ctx, "cx_grid_label3d_measures: no labels of cx_grid_label3d in the context");
+    if (!L || !L->pending) return cx_fail(ctx, CX_ERR_STATE, "cx_grid_label3d_measures: no labels of cx_grid_label3d in the context");
     if (L->k == 0) return CX_OK;
-    if (capacity < L->k || !out_host) return cxl_invalid(ctx, "cx_grid_label3d_measures: room for fewer records than there are components");
+    if (capacity < L->k || !out_host) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_label3d_measures: room for fewer records than there are components");
     CX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     if (!L->measured) {
@@ -491,21 +466,18 @@ extern "C" int cx_grid_label3d_measures(cx_ctx* ctx, cx_label_component* out_hos
 extern "C" int cx_grid_label3d_select(cx_ctx* ctx, const uint8_t* keep, int64_t n_keep, uint8_t* out_device, uint8_t* out_host, int64_t* n_voxels) {
     if (!ctx) return CX_ERR_INVALID;
     cx_label_state* L = ctx->label;
-    if (!L || !L->pending) return cxl_state(ctx, "cx_grid_label3d_select: no labels of cx_grid_label3d in the context");
-    if (!keep || n_keep != L->k + 1) return cxl_invalid(ctx, "cx_grid_label3d_select: one keep byte per label, 0 included");
+    if (!L || !L->pending) return cx_fail(ctx, CX_ERR_STATE, "cx_grid_label3d_select: no labels of cx_grid_label3d in the context");
+    if (!keep || n_keep != L->k + 1) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_label3d_select: one keep byte per label, 0 included");
     const size_t count = (size_t)(L->shape[0] * L->shape[1] * L->shape[2]);
-    if (out_device && cxl_overlap(L->labels.get(), count * sizeof(uint32_t), out_device, count)) return cxl_invalid(ctx, "cx_grid_label3d_select: the output overlaps the labels");
+    if (out_device && cx_overlap(L->labels.get(), count * sizeof(uint32_t), out_device, count)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_label3d_select: the output overlaps the labels");
     CX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     int rc;
     if ((rc = L->keep.grow(ctx, (size_t)n_keep))) return rc;
     CX_HIP(ctx, hipMemcpyAsync(L->keep, keep, (size_t)n_keep, hipMemcpyHostToDevice, st));
-    L->mask_pending = false;      // the mask of this call, or none
-    uint8_t* out = out_device;
-    if (!out_device) {
-        if ((rc = L->mask.grow(ctx, count))) return rc;
-        out = L->mask.get();
-    }
+    void* opened;
+    if ((rc = L->mask.open(ctx, out_device, count, &opened))) return rc;
+    uint8_t* out = static_cast<uint8_t*>(opened);
     CX_HIP(ctx, hipMemsetAsync(L->misc.get() + 1, 0, sizeof(u64), st));
     cxl_select_args S;
     memset(&S, 0, sizeof(S));
@@ -521,32 +493,23 @@ extern "C" int cx_grid_label3d_select(cx_ctx* ctx, const uint8_t* keep, int64_t 
     CX_HIP(ctx, hipMemcpyAsync(&ones, L->misc.get() + 1, sizeof(ones), hipMemcpyDeviceToHost, st));
     if (out_host) CX_HIP(ctx, hipMemcpyAsync(out_host, out, count, hipMemcpyDeviceToHost, st));
     CX_HIP(ctx, hipStreamSynchronize(st));
-    if (!out_device) {
-        L->mask_shape[0] = L->shape[0]; L->mask_shape[1] = L->shape[1]; L->mask_shape[2] = L->shape[2];
-        L->mask_voxels = (int64_t)ones; L->mask_pending = true;
-    }
+    if (!out_device) { L->mask.publish(L->shape[0], L->shape[1], L->shape[2]); L->mask_voxels = (int64_t)ones; }
     if (n_voxels) *n_voxels = (int64_t)ones;
     return CX_OK;
 }
 
 extern "C" int cx_grid_label3d_select_result(cx_ctx* ctx, uint8_t** mask_device, int64_t shape[3], int64_t* n_voxels) {
     if (!ctx) return CX_ERR_INVALID;
-    cx_label_state* L = ctx->label;
-    if (!L || !L->mask_pending) return cxl_state(ctx, "cx_grid_label3d_select_result: no mask of cx_grid_label3d_select in the context");
-    if (mask_device) *mask_device = L->mask.get();
-    if (shape) { shape[0] = L->mask_shape[0]; shape[1] = L->mask_shape[1]; shape[2] = L->mask_shape[2]; }
+    const cx_label_state* L = ctx->label;
+    void* mask = nullptr;
+    const int rc = cx_slot_result(ctx, L ? &L->mask : nullptr, "cx_grid_label3d_select_result: no mask of cx_grid_label3d_select in the context", &mask, shape);
+    if (rc) return rc;
+    if (mask_device) *mask_device = static_cast<uint8_t*>(mask);
     if (n_voxels) *n_voxels = L->mask_voxels;
     return CX_OK;
 }
 
 extern "C" int cx_grid_label3d_bind(cx_ctx* ctx) {
     if (!ctx) return CX_ERR_INVALID;
-    cx_label_state* L = ctx->label;
-    if (!L || !L->mask_pending) return cxl_state(ctx, "cx_grid_label3d_bind: no mask of cx_grid_label3d_select in the context");
-    CX_HIP(ctx, hipSetDevice(ctx->device));
-    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int rc = cx_grid_bind_owned(ctx, L->mask, CX_DTYPE_U8, L->mask_shape[0], L->mask_shape[1], L->mask_shape[2]);
-    if (rc) return rc;
-    L->mask_pending = false;
-    return CX_OK;
+    return cx_slot_bind(ctx, ctx->label ? &ctx->label->mask : nullptr, "cx_grid_label3d_bind: no mask of cx_grid_label3d_select in the context", CX_DTYPE_U8);
 }

@@ -26,8 +26,8 @@
 #include <string>
 #include <vector>
 
-#include "cx_ctx.h"
 #include "cx_dev.h"
+#include "cx_gridop.h"
 
 #define CXK_ROUND 12u           // prefixes per refinement pass: 12 histograms of 1024 bins are 48 KB of LDS
 #define CXK_HIST 12288u         // histogram words of one pass (the first fp32 pass has 4096 bins and no prefix)
@@ -226,7 +226,7 @@ extern "C" int cx_samples_select(cx_ctx* ctx, const void* samples, int32_t dtype
     if (!ctx) return CX_ERR_INVALID;
     if (!ranks || nranks < 1 || nranks > CXK_MAX_RANKS) return cxk_invalid(ctx, "cx_samples_select: 1..1024 ranks");
     if (!samples) {
-        if (!ctx->grid.p) { ctx->err = "cx_samples_select: no samples given and no grid bound"; return CX_ERR_STATE; }
+        if (!ctx->grid.p) return cx_no_grid(ctx, "cx_samples_select");
         dtype = ctx->grid.dtype; n = ctx->n0 * ctx->n1 * ctx->n2; on_device = 1;
     } else {
         if (!cx_dtype_valid(dtype)) return cxk_invalid(ctx, "cx_samples_select: unknown sample type");

@@ -26,8 +26,8 @@
 #include <new>
 #include <utility>
 
-#include "cx_ctx.h"
 #include "cx_dev.h"
+#include "cx_gridop.h"
 
 #define CXQ_T0 4
 #define CXQ_T1 4
@@ -36,12 +36,8 @@
 #define CXQ_MASK_WORDS 11                                  // 343 bits
 #define CXQ_TAB_BYTES 1376u                                // 343 words, rounded up to 16 bytes
 
-struct cx_rank_state {
-    cx_buf<uint8_t> in;        // host samples; the result of the call before where that is this call's input
-    cx_buf<uint8_t> result;    // the context's own result (bytes: cx_grid_rank3d_bind moves it into ctx->grid_owned)
-    int64_t shape[3] = {0, 0, 0};
-    int32_t dtype = CX_DTYPE_F32;
-    bool pending = false;      // `result` holds the result of the last call and has not been bound
+struct cx_rank_state : cx_slot {
+    int32_t dtype = CX_DTYPE_F32;      // of the result
 };
 
 void cx_rank_free(cx_ctx* ctx) {
@@ -193,15 +189,6 @@ static_assert(CXQ_T1 == 4 && CXQ_T2 == 64 && CXQ_T1 * CXQ_T2 == 256, "a wave per
 static_assert(CXQ_MAX_SIZE * CXQ_MAX_SIZE * CXQ_MAX_SIZE <= 32 * CXQ_MASK_WORDS, "a mask bit per offset of the largest box");
 static_assert(4u * CXQ_MAX_SIZE * CXQ_MAX_SIZE * CXQ_MAX_SIZE <= CXQ_TAB_BYTES && CXQ_TAB_BYTES % 16u == 0u, "a table word per offset of the largest box");
 
-static int cxq_invalid(cx_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return CX_ERR_INVALID;
-}
-static int cxq_state(cx_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return CX_ERR_STATE;
-}
-
 // the key of a sample's bits, as cxq_key makes it (cval is finite: no NaN)
 static uint32_t cxq_host_key(int32_t dtype, uint32_t raw) {
     switch (dtype) {
@@ -217,60 +204,37 @@ extern "C" int cx_grid_rank3d(cx_ctx* ctx, const void* samples, int32_t dtype, i
                               const int32_t size[3], const int32_t origin[3], const uint8_t* footprint, int32_t rank, int32_t mode, double cval,
                               void* out_device, void* out_host) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!size || !origin) return cxq_invalid(ctx, "cx_grid_rank3d: no size or origin");
-    if (mode != CX_FILTER_NEAREST && mode != CX_FILTER_REFLECT && mode != CX_FILTER_CONSTANT) return cxq_invalid(ctx, "cx_grid_rank3d: unknown mode");
-    if (!std::isfinite(cval)) return cxq_invalid(ctx, "cx_grid_rank3d: cval is NaN or infinite");
+    if (!size || !origin) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_rank3d: no size or origin");
+    if (mode != CX_FILTER_NEAREST && mode != CX_FILTER_REFLECT && mode != CX_FILTER_CONSTANT) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_rank3d: unknown mode");
+    if (!std::isfinite(cval)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_rank3d: cval is NaN or infinite");
     cxq_args A;
     memset(&A, 0, sizeof(A));
     for (int a = 0; a < 3; a++) {
-        if (size[a] < 1 || size[a] > CXQ_MAX_SIZE) return cxq_invalid(ctx, "cx_grid_rank3d: a size of 1 to 7 per axis");
-        if (origin[a] < 0 || origin[a] >= size[a]) return cxq_invalid(ctx, "cx_grid_rank3d: an origin of 0 to size - 1 per axis");
+        if (size[a] < 1 || size[a] > CXQ_MAX_SIZE) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_rank3d: a size of 1 to 7 per axis");
+        if (origin[a] < 0 || origin[a] >= size[a]) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_rank3d: an origin of 0 to size - 1 per axis");
         A.s[a] = size[a]; A.o[a] = origin[a];
     }
     const int32_t box = size[0] * size[1] * size[2];
     int32_t W = 0;
     for (int32_t e = 0; e < box; e++)
         if (!footprint || footprint[e]) { A.mask[e >> 5] |= 1u << (e & 31); W++; }
-    if (W == 0) return cxq_invalid(ctx, "cx_grid_rank3d: the footprint is empty");
-    if (rank < 0 || rank >= W) return cxq_invalid(ctx, "cx_grid_rank3d: a rank of 0 to W - 1, W the number of offsets in the footprint");
-    if (!samples) {
-        if (!ctx->grid.p) return cxq_state(ctx, "cx_grid_rank3d: no samples given and no grid bound");
-        dtype = ctx->grid.dtype; n0 = ctx->n0; n1 = ctx->n1; n2 = ctx->n2; on_device = 1;
-    } else {
-        if (!cx_dtype_valid(dtype)) return cxq_invalid(ctx, "cx_grid_rank3d: unknown sample type");
-        if (n0 < 1 || n1 < 1 || n2 < 1 || n0 > (1LL << 31) || n1 > (1LL << 31) || n2 > (1LL << 31) || n0 * n1 > (1LL << 31) || n0 * n1 * n2 > (1LL << 31))
-            return cxq_invalid(ctx, "cx_grid_rank3d: at least 1 sample per axis, at most 2^31 in all");
-    }
+    if (W == 0) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_rank3d: the footprint is empty");
+    if (rank < 0 || rank >= W) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_rank3d: a rank of 0 to W - 1, W the number of offsets in the footprint");
+    cx_source src;
+    int rc = cx_source_resolve(ctx, "cx_grid_rank3d", samples, dtype, on_device, n0, n1, n2, 31, &src);
+    if (rc) return rc;
+    dtype = src.dtype; n0 = src.n[0]; n1 = src.n[1]; n2 = src.n[2];
     uint32_t fill_bits;
-    if (!cx_dtype_value_bits(dtype, cval, fill_bits)) return cxq_invalid(ctx, "cx_grid_rank3d: cval is not a value of the sample type");
-    const size_t esize = cx_dtype_size(dtype), bytes = (size_t)(n0 * n1 * n2) * esize;
-    const void* dev = samples ? samples : ctx->grid.p;
-    if (out_device && on_device) {
-        const uintptr_t a0 = (uintptr_t)dev, a1 = a0 + bytes, b0 = (uintptr_t)out_device, b1 = b0 + bytes;
-        if (a0 < b1 && b0 < a1) return cxq_invalid(ctx, "cx_grid_rank3d: the output overlaps the input");
-    }
+    if (!cx_dtype_value_bits(dtype, cval, fill_bits)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_rank3d: cval is not a value of the sample type");
+    const size_t esize = cx_dtype_size(dtype), bytes = src.bytes;
+    if (out_device && src.on_device && cx_overlap(src.p, bytes, out_device, bytes)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_rank3d: the output overlaps the input");
     CX_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->rank) ctx->rank = new (std::nothrow) cx_rank_state();
-    cx_rank_state* S = ctx->rank;
+    cx_rank_state* S = cx_state_of(ctx->rank);
     if (!S) return CX_ERR_NOMEM;
     hipStream_t st = ctx->stream;
-    int rc;
-    if (samples && on_device && S->result.get() && samples == S->result.get()) {
-        // the result of the call before is the input of this one: it changes places with the scratch for host samples, so that this
-        // call's own result cannot land on it
-        std::swap(S->in, S->result);
-        dev = S->in.get();
-    } else if (samples && !on_device) {
-        if ((rc = S->in.grow(ctx, bytes))) return rc;
-        CX_HIP(ctx, hipMemcpyAsync(S->in, samples, bytes, hipMemcpyHostToDevice, st));
-        dev = S->in.get();
-    }
-    S->pending = false;      // the result of this call, or none: a caller's output leaves nothing to hand out or bind
-    void* final_out = out_device;
-    if (!out_device) {
-        if ((rc = S->result.grow(ctx, bytes))) return rc;
-        final_out = S->result.get();
-    }
+    const void* dev;
+    void* final_out;
+    if ((rc = S->stage(ctx, src, &dev)) || (rc = S->open(ctx, out_device, bytes, &final_out))) return rc;
     A.in = dev; A.out = final_out;
     A.n[0] = n0; A.n[1] = n1; A.n[2] = n2;
     A.rank = (uint32_t)rank; A.mode = mode; A.dtype = dtype;
@@ -299,31 +263,19 @@ extern "C" int cx_grid_rank3d(cx_ctx* ctx, const void* samples, int32_t dtype, i
     CX_HIP(ctx, hipGetLastError());
     if (out_host) CX_HIP(ctx, hipMemcpyAsync(out_host, final_out, bytes, hipMemcpyDeviceToHost, st));
     CX_HIP(ctx, hipStreamSynchronize(st));      // the caller's host memory is its own again
-    if (!out_device) {
-        S->shape[0] = n0; S->shape[1] = n1; S->shape[2] = n2;
-        S->dtype = dtype; S->pending = true;
-    }
+    if (!out_device) { S->publish(n0, n1, n2); S->dtype = dtype; }
     return CX_OK;
 }
 
 extern "C" int cx_grid_rank3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_dtype) {
     if (!ctx) return CX_ERR_INVALID;
-    cx_rank_state* S = ctx->rank;
-    if (!S || !S->pending) return cxq_state(ctx, "cx_grid_rank3d_result: no result of cx_grid_rank3d in the context");
-    if (out_device) *out_device = S->result.get();
-    if (out_shape) { out_shape[0] = S->shape[0]; out_shape[1] = S->shape[1]; out_shape[2] = S->shape[2]; }
-    if (out_dtype) *out_dtype = S->dtype;
-    return CX_OK;
+    const int rc = cx_slot_result(ctx, ctx->rank, "cx_grid_rank3d_result: no result of cx_grid_rank3d in the context", out_device, out_shape);
+    if (rc == CX_OK && out_dtype) *out_dtype = ctx->rank->dtype;
+    return rc;
 }
 
 extern "C" int cx_grid_rank3d_bind(cx_ctx* ctx) {
     if (!ctx) return CX_ERR_INVALID;
     cx_rank_state* S = ctx->rank;
-    if (!S || !S->pending) return cxq_state(ctx, "cx_grid_rank3d_bind: no result of cx_grid_rank3d in the context");
-    CX_HIP(ctx, hipSetDevice(ctx->device));
-    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int rc = cx_grid_bind_owned(ctx, S->result, S->dtype, S->shape[0], S->shape[1], S->shape[2]);
-    if (rc) return rc;
-    S->pending = false;
-    return CX_OK;
+    return cx_slot_bind(ctx, S, "cx_grid_rank3d_bind: no result of cx_grid_rank3d in the context", S ? S->dtype : 0);
 }

@@ -43,8 +43,8 @@
 #include <new>
 #include <utility>
 
-#include "cx_ctx.h"
 #include "cx_dev.h"
+#include "cx_gridop.h"
 
 #define CXR_T0 8
 #define CXR_T1 8
@@ -66,16 +66,13 @@ struct cxr_counters {          // 64 bytes, zeroed before every call
     u64 pad2;
 };
 
-struct cx_recon_state {
-    cx_buf<uint8_t> in, in2;   // host mask and host marker
+struct cx_recon_state : cx_slot {      // (`in`: a host mask)
+    cx_buf<uint8_t> in2;       // a host marker
     cx_buf<uint8_t> state;     // a working key per sample
     cx_buf<uint32_t> work;     // two lists and two flag arrays of one word per tile
     cx_buf<uint8_t> counters;  // cxr_counters
-    cx_buf<uint8_t> result;    // the context's own result (bytes: cx_grid_reconstruct3d_bind moves it into ctx->grid_owned)
     cx_buf<uint8_t> prev;      // the result of the call before, where that is an input of this call
-    int64_t shape[3] = {0, 0, 0};
-    int32_t dtype = CX_DTYPE_F32, out_kind = CX_RECON_OUT_VALUES;
-    bool pending = false;      // `result` holds the result of the last call and has not been bound
+    int32_t dtype = CX_DTYPE_F32, out_kind = CX_RECON_OUT_VALUES;      // of the result
 };
 
 void cx_recon_free(cx_ctx* ctx) {
@@ -361,15 +358,6 @@ __global__ __launch_bounds__(256) void cxr_k_final(const cxr_args A) {
 static_assert(CXR_T2 == 64 && CXR_T0 * CXR_T2 == 512 && CXR_T1 * CXR_T2 == 512, "a lane per sample of a row; two columns per thread");
 static_assert(16u + ((CXR_HALO * 4u + 15u) & ~15u) + CXR_TILE * 4u <= 65536u, "the LDS of a tile of 32-bit keys");
 
-static int cxr_fail(cx_ctx* ctx, int code, const char* msg) {
-    ctx->err = msg;
-    return code;
-}
-static bool cxr_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
 template <typename K>
 static void cxr_launch_init(const cxr_args& A, dim3 grid, hipStream_t st) { hipLaunchKernelGGL(cxr_k_init<K>, grid, dim3(256), 0, st, A); }
 template <typename K>
@@ -391,62 +379,39 @@ extern "C" int cx_grid_reconstruct3d(cx_ctx* ctx, const void* mask, int32_t dtyp
                                      const void* marker, int32_t marker_kind, double h, int32_t faces, int32_t method, int32_t connectivity,
                                      int32_t out_kind, void* out_device, void* out_host, cx_recon_stats* stats) {
     if (!ctx) return CX_ERR_INVALID;
-    if (method != CX_RECON_DILATION && method != CX_RECON_EROSION) return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: unknown method");
-    if (connectivity < 1 || connectivity > 3) return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: a connectivity of 1, 2 or 3");
-    if (out_kind != CX_RECON_OUT_VALUES && out_kind != CX_RECON_OUT_CHANGED) return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: unknown output kind");
-    if (marker_kind < CX_RECON_MARKER_ARRAY || marker_kind > CX_RECON_MARKER_RIM) return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: unknown marker kind");
-    if (marker_kind == CX_RECON_MARKER_ARRAY && !marker) return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: CX_RECON_MARKER_ARRAY without a marker");
-    if (marker_kind == CX_RECON_MARKER_RIM && (faces <= 0 || faces > 63)) return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: CX_RECON_MARKER_RIM takes 1 to 6 of the face bits");
-    if (marker_kind == CX_RECON_MARKER_SHIFT && !(std::isfinite(h) && h > 0.0)) return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: h must be finite and above 0");
-    if (!mask) {
-        if (!ctx->grid.p) return cxr_fail(ctx, CX_ERR_STATE, "cx_grid_reconstruct3d: no mask given and no grid bound");
-        dtype = ctx->grid.dtype; n0 = ctx->n0; n1 = ctx->n1; n2 = ctx->n2; on_device = 1;      // (a marker array lives where the mask does)
-    } else {
-        if (!cx_dtype_valid(dtype)) return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: unknown sample type");
-        if (n0 < 1 || n1 < 1 || n2 < 1) return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: at least 1 sample per axis");
-        if (n0 > (1LL << 31) || n1 > (1LL << 31) || n2 > (1LL << 31) || n0 * n1 > (1LL << 31) || n0 * n1 * n2 > (1LL << 31))
-            return cxr_fail(ctx, CX_ERR_UNSUPPORTED, "cx_grid_reconstruct3d: at most 2^31 samples");
-    }
+    if (method != CX_RECON_DILATION && method != CX_RECON_EROSION) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: unknown method");
+    if (connectivity < 1 || connectivity > 3) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: a connectivity of 1, 2 or 3");
+    if (out_kind != CX_RECON_OUT_VALUES && out_kind != CX_RECON_OUT_CHANGED) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: unknown output kind");
+    if (marker_kind < CX_RECON_MARKER_ARRAY || marker_kind > CX_RECON_MARKER_RIM) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: unknown marker kind");
+    if (marker_kind == CX_RECON_MARKER_ARRAY && !marker) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: CX_RECON_MARKER_ARRAY without a marker");
+    if (marker_kind == CX_RECON_MARKER_RIM && (faces <= 0 || faces > 63)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: CX_RECON_MARKER_RIM takes 1 to 6 of the face bits");
+    if (marker_kind == CX_RECON_MARKER_SHIFT && !(std::isfinite(h) && h > 0.0)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: h must be finite and above 0");
+    cx_source M;
+    int rc = cx_source_resolve(ctx, "cx_grid_reconstruct3d", mask, dtype, on_device, n0, n1, n2, 31, &M, true);
+    if (rc) return rc;
+    dtype = M.dtype; n0 = M.n[0]; n1 = M.n[1]; n2 = M.n[2]; on_device = M.on_device;      // (a marker array lives where the mask does)
     const bool is_float = dtype == CX_DTYPE_F32 || dtype == CX_DTYPE_F16 || dtype == CX_DTYPE_BF16;
-    if (marker_kind == CX_RECON_MARKER_SHIFT && !is_float && h != std::floor(h)) return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: h of an integer type must be an integer");
-    const size_t esize = cx_dtype_size(dtype), total = (size_t)(n0 * n1 * n2), bytes = total * esize;
+    if (marker_kind == CX_RECON_MARKER_SHIFT && !is_float && h != std::floor(h)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: h of an integer type must be an integer");
+    const size_t esize = cx_dtype_size(dtype), total = M.count, bytes = M.bytes;
     const size_t out_bytes = out_kind == CX_RECON_OUT_VALUES ? bytes : total;
-    const bool mask_dev = !mask || on_device, marker_dev = marker_kind == CX_RECON_MARKER_ARRAY && on_device;
-    if (out_device && ((mask_dev && cxr_overlap(mask ? mask : ctx->grid.p, bytes, out_device, out_bytes)) || (marker_dev && cxr_overlap(marker, bytes, out_device, out_bytes))))
-        return cxr_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: the output overlaps an input");
+    const bool marker_dev = marker_kind == CX_RECON_MARKER_ARRAY && on_device;
+    if ((on_device && cx_overlap(M.p, bytes, out_device, out_bytes)) || (marker_dev && cx_overlap(marker, bytes, out_device, out_bytes)))
+        return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_reconstruct3d: the output overlaps an input");
     CX_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->recon) ctx->recon = new (std::nothrow) cx_recon_state();
-    cx_recon_state* S = ctx->recon;
+    cx_recon_state* S = cx_state_of(ctx->recon);
     if (!S) return CX_ERR_NOMEM;
     hipStream_t st = ctx->stream;
-    int rc;
-    // an input that lies in the result of the call before: that buffer steps aside, so that this call's own result cannot land on it
-    if (S->result.get() && ((mask && mask_dev && cxr_overlap(mask, bytes, S->result.get(), S->result.bytes())) ||
-                            (marker_dev && cxr_overlap(marker, bytes, S->result.get(), S->result.bytes()))))
-        std::swap(S->result, S->prev);
-    S->pending = false;      // the result of this call, or none
-    const void* mask_d = mask ? mask : ctx->grid.p;
-    if (mask && !on_device) {
-        if ((rc = S->in.grow(ctx, bytes))) return rc;
-        CX_HIP(ctx, hipMemcpyAsync(S->in, mask, bytes, hipMemcpyHostToDevice, st));
-        mask_d = S->in.get();
-    }
-    const void* marker_d = nullptr;
-    if (marker_kind == CX_RECON_MARKER_ARRAY) {
-        marker_d = marker;
-        if (!on_device) {
-            if ((rc = S->in2.grow(ctx, bytes))) return rc;
-            CX_HIP(ctx, hipMemcpyAsync(S->in2, marker, bytes, hipMemcpyHostToDevice, st));
-            marker_d = S->in2.get();
-        }
-    }
+    // an input that lies in the result of the call before: that buffer steps aside into `prev`, the mask's scratch keeps its memory
+    const void* mask_d = M.p;
+    const void* marker_d = marker_kind == CX_RECON_MARKER_ARRAY ? marker : nullptr;
+    if (on_device) S->step_aside(M.p, bytes, S->prev);
+    else if ((rc = cx_upload(ctx, S->in, M.p, bytes, &mask_d))) return rc;
+    if (marker_dev) S->step_aside(marker, bytes, S->prev);
+    else if (marker_d && (rc = cx_upload(ctx, S->in2, marker, bytes, &marker_d))) return rc;
     const int64_t g0 = (n0 + CXR_T0 - 1) / CXR_T0, g1 = (n1 + CXR_T1 - 1) / CXR_T1, g2 = (n2 + CXR_T2 - 1) / CXR_T2;
     const size_t tiles = (size_t)g0 * (size_t)g1 * (size_t)g2;      // (<= 2^28: a tile holds eight samples at least, or the whole axis 0)
-    void* final_out = out_device;
-    if (!out_device) {
-        if ((rc = S->result.grow(ctx, out_bytes))) return rc;
-        final_out = S->result.get();
-    }
+    void* final_out;
+    if ((rc = S->open(ctx, out_device, out_bytes, &final_out))) return rc;
     if ((rc = S->state.grow(ctx, bytes))) return rc;
     if ((rc = S->work.grow(ctx, 4 * tiles))) return rc;
     if ((rc = S->counters.grow(ctx, sizeof(cxr_counters)))) return rc;
@@ -482,7 +447,7 @@ extern "C" int cx_grid_reconstruct3d(cx_ctx* ctx, const void* mask, int32_t dtyp
         CX_HIP(ctx, hipMemcpyAsync(&hc, S->counters, sizeof(hc), hipMemcpyDeviceToHost, st));
         CX_HIP(ctx, hipStreamSynchronize(st));
         if (hc.cnt[r % 3ull] == 0u) break;
-        if (r >= bound) return cxr_fail(ctx, CX_ERR_HIP, "cx_grid_reconstruct3d: tiles still active after as many rounds as the array has samples");
+        if (r >= bound) return cx_fail(ctx, CX_ERR_HIP, "cx_grid_reconstruct3d: tiles still active after as many rounds as the array has samples");
     }
     A.all_ones = (marker_kind == CX_RECON_MARKER_STEP && out_kind == CX_RECON_OUT_CHANGED && !is_float && hc.n_moved == 0ull) ? 1u : 0u;
     {
@@ -497,20 +462,15 @@ extern "C" int cx_grid_reconstruct3d(cx_ctx* ctx, const void* mask, int32_t dtyp
         stats->n_changed = (int64_t)hc.n_changed; stats->n_clamped = (int64_t)hc.n_clamped;
         stats->rounds = (int64_t)hc.rounds; stats->tile_visits = (int64_t)hc.visits;
     }
-    if (!out_device) {
-        S->shape[0] = n0; S->shape[1] = n1; S->shape[2] = n2;
-        S->dtype = out_kind == CX_RECON_OUT_VALUES ? dtype : CX_DTYPE_U8;
-        S->out_kind = out_kind; S->pending = true;
-    }
+    if (!out_device) { S->publish(n0, n1, n2); S->dtype = out_kind == CX_RECON_OUT_VALUES ? dtype : CX_DTYPE_U8; S->out_kind = out_kind; }
     return CX_OK;
 }
 
 extern "C" int cx_grid_reconstruct3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_dtype, int32_t* out_kind) {
     if (!ctx) return CX_ERR_INVALID;
-    cx_recon_state* S = ctx->recon;
-    if (!S || !S->pending) return cxr_fail(ctx, CX_ERR_STATE, "cx_grid_reconstruct3d_result: no result of cx_grid_reconstruct3d in the context");
-    if (out_device) *out_device = S->result.get();
-    if (out_shape) { out_shape[0] = S->shape[0]; out_shape[1] = S->shape[1]; out_shape[2] = S->shape[2]; }
+    const cx_recon_state* S = ctx->recon;
+    const int rc = cx_slot_result(ctx, S, "cx_grid_reconstruct3d_result: no result of cx_grid_reconstruct3d in the context", out_device, out_shape);
+    if (rc) return rc;
     if (out_dtype) *out_dtype = S->dtype;
     if (out_kind) *out_kind = S->out_kind;
     return CX_OK;
@@ -519,11 +479,5 @@ extern "C" int cx_grid_reconstruct3d_result(cx_ctx* ctx, void** out_device, int6
 extern "C" int cx_grid_reconstruct3d_bind(cx_ctx* ctx) {
     if (!ctx) return CX_ERR_INVALID;
     cx_recon_state* S = ctx->recon;
-    if (!S || !S->pending) return cxr_fail(ctx, CX_ERR_STATE, "cx_grid_reconstruct3d_bind: no result of cx_grid_reconstruct3d in the context");
-    CX_HIP(ctx, hipSetDevice(ctx->device));
-    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int rc = cx_grid_bind_owned(ctx, S->result, S->dtype, S->shape[0], S->shape[1], S->shape[2]);
-    if (rc) return rc;
-    S->pending = false;
-    return CX_OK;
+    return cx_slot_bind(ctx, S, "cx_grid_reconstruct3d_bind: no result of cx_grid_reconstruct3d in the context", S ? S->dtype : 0);
 }

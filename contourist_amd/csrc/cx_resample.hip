@@ -26,8 +26,8 @@
 #include <new>
 #include <utility>
 
-#include "cx_ctx.h"
 #include "cx_dev.h"
+#include "cx_gridop.h"
 
 #define CXR_LIMIT 1048576.0               // |matrix|, |offset| <= 2^20
 #define CXR_TABLE_MAX (1LL << 20)         // entries of the table kernel's table; a longer output takes the general kernel
@@ -44,16 +44,12 @@ struct cxr_ent {      // 24 bytes
     uint32_t pad;
 };
 
-struct cx_resample_state {
-    cx_buf<uint8_t> in;        // host samples; the result of the call before where that is this call's input
-    cx_buf<uint8_t> result;    // the context's own result (bytes: cx_grid_resample3d_bind moves it into ctx->grid_owned)
+struct cx_resample_state : cx_slot {
     cx_buf<cxr_ent> table;
     cx_buf<unsigned long long> count;     // the shards of n_outside
     unsigned long long shards[CXR_SHARDS * CXR_SHARD_WORDS];      // ... and where they land on the host
-    int64_t shape[3] = {0, 0, 0};
-    int32_t dtype = CX_DTYPE_F32;
+    int32_t dtype = CX_DTYPE_F32;      // of the result
     int64_t n_outside = 0;
-    bool pending = false;      // `result` holds the result of the last call and has not been bound
 };
 
 void cx_resample_free(cx_ctx* ctx) {
@@ -196,15 +192,6 @@ __global__ __launch_bounds__(256) void cxr_k_nearest(const cxr_args A) {
     cxr_count_outside(A, outside);
 }
 
-static int cxr_invalid(cx_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return CX_ERR_INVALID;
-}
-static int cxr_state(cx_ctx* ctx, const char* msg) {
-    ctx->err = msg;
-    return CX_ERR_STATE;
-}
-
 static int32_t cxr_ceil_log2(int64_t m) {
     int32_t l = 0;
     while ((1LL << l) < m) l++;
@@ -230,57 +217,35 @@ extern "C" int cx_grid_resample3d(cx_ctx* ctx, const void* samples, int32_t dtyp
                                   const double matrix[9], const double offset[3], const int64_t out_shape[3], int32_t order, int32_t mode,
                                   double cval, void* out_device, void* out_host, int64_t* n_outside) {
     if (!ctx) return CX_ERR_INVALID;
-    if (!matrix || !offset || !out_shape) return cxr_invalid(ctx, "cx_grid_resample3d: no matrix, offset or output shape");
-    if (order != 0 && order != 1) return cxr_invalid(ctx, "cx_grid_resample3d: order 0 or 1");
-    if (mode != CX_FILTER_NEAREST && mode != CX_FILTER_REFLECT && mode != CX_FILTER_CONSTANT) return cxr_invalid(ctx, "cx_grid_resample3d: unknown mode");
-    if (!std::isfinite(cval)) return cxr_invalid(ctx, "cx_grid_resample3d: cval is NaN or infinite");
+    if (!matrix || !offset || !out_shape) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_resample3d: no matrix, offset or output shape");
+    if (order != 0 && order != 1) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_resample3d: order 0 or 1");
+    if (mode != CX_FILTER_NEAREST && mode != CX_FILTER_REFLECT && mode != CX_FILTER_CONSTANT) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_resample3d: unknown mode");
+    if (!std::isfinite(cval)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_resample3d: cval is NaN or infinite");
     for (int e = 0; e < 12; e++) {
         const double x = e < 9 ? matrix[e] : offset[e - 9];
-        if (!std::isfinite(x) || std::fabs(x) > CXR_LIMIT) return cxr_invalid(ctx, "cx_grid_resample3d: matrix and offset are finite and at most 2^20 in magnitude");
+        if (!std::isfinite(x) || std::fabs(x) > CXR_LIMIT) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_resample3d: matrix and offset are finite and at most 2^20 in magnitude");
     }
     const int64_t m0 = out_shape[0], m1 = out_shape[1], m2 = out_shape[2];
     if (m0 < 1 || m1 < 1 || m2 < 1 || m0 > (1LL << 31) || m1 > (1LL << 31) || m2 > (1LL << 31) || m0 * m1 > (1LL << 31) || m0 * m1 * m2 > (1LL << 31))
-        return cxr_invalid(ctx, "cx_grid_resample3d: at least 1 output sample per axis, at most 2^31 in all");
-    if (!samples) {
-        if (!ctx->grid.p) return cxr_state(ctx, "cx_grid_resample3d: no samples given and no grid bound");
-        dtype = ctx->grid.dtype; n0 = ctx->n0; n1 = ctx->n1; n2 = ctx->n2; on_device = 1;
-    } else {
-        if (!cx_dtype_valid(dtype)) return cxr_invalid(ctx, "cx_grid_resample3d: unknown sample type");
-        if (n0 < 1 || n1 < 1 || n2 < 1 || n0 > (1LL << 31) || n1 > (1LL << 31) || n2 > (1LL << 31) || n0 * n1 > (1LL << 31) || n0 * n1 * n2 > (1LL << 31))
-            return cxr_invalid(ctx, "cx_grid_resample3d: at least 1 sample per axis, at most 2^31 in all");
-    }
+        return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_resample3d: at least 1 output sample per axis, at most 2^31 in all");
+    cx_source src;
+    int rc = cx_source_resolve(ctx, "cx_grid_resample3d", samples, dtype, on_device, n0, n1, n2, 31, &src);
+    if (rc) return rc;
+    dtype = src.dtype; n0 = src.n[0]; n1 = src.n[1]; n2 = src.n[2];
     cxr_args A;
     memset(&A, 0, sizeof(A));
-    if (order == 0 && !cx_dtype_value_bits(dtype, cval, A.fill_bits)) return cxr_invalid(ctx, "cx_grid_resample3d: cval is not a value of the sample type (order 0)");
+    if (order == 0 && !cx_dtype_value_bits(dtype, cval, A.fill_bits)) return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_resample3d: cval is not a value of the sample type (order 0)");
     const int32_t out_dtype = order == 0 ? dtype : CX_DTYPE_F32;
-    const size_t in_bytes = (size_t)(n0 * n1 * n2) * cx_dtype_size(dtype), out_bytes = (size_t)(m0 * m1 * m2) * cx_dtype_size(out_dtype);
-    const void* dev = samples ? samples : ctx->grid.p;
-    if (out_device && on_device) {
-        const uintptr_t a0 = (uintptr_t)dev, a1 = a0 + in_bytes, b0 = (uintptr_t)out_device, b1 = b0 + out_bytes;
-        if (a0 < b1 && b0 < a1) return cxr_invalid(ctx, "cx_grid_resample3d: the output overlaps the input");
-    }
+    const size_t out_bytes = (size_t)(m0 * m1 * m2) * cx_dtype_size(out_dtype);
+    if (out_device && src.on_device && cx_overlap(src.p, src.bytes, out_device, out_bytes))
+        return cx_fail(ctx, CX_ERR_INVALID, "cx_grid_resample3d: the output overlaps the input");
     CX_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->resample) ctx->resample = new (std::nothrow) cx_resample_state();
-    cx_resample_state* S = ctx->resample;
+    cx_resample_state* S = cx_state_of(ctx->resample);
     if (!S) return CX_ERR_NOMEM;
     hipStream_t st = ctx->stream;
-    int rc;
-    if (samples && on_device && S->result.get() && samples == S->result.get()) {
-        // the result of the call before is the input of this one: it changes places with the scratch for host samples, so that this
-        // call's own result cannot land on it
-        std::swap(S->in, S->result);
-        dev = S->in.get();
-    } else if (samples && !on_device) {
-        if ((rc = S->in.grow(ctx, in_bytes))) return rc;
-        CX_HIP(ctx, hipMemcpyAsync(S->in, samples, in_bytes, hipMemcpyHostToDevice, st));
-        dev = S->in.get();
-    }
-    S->pending = false;      // the result of this call, or none: a caller's output leaves nothing to hand out or bind
-    void* final_out = out_device;
-    if (!out_device) {
-        if ((rc = S->result.grow(ctx, out_bytes))) return rc;
-        final_out = S->result.get();
-    }
+    const void* dev;
+    void* final_out;
+    if ((rc = S->stage(ctx, src, &dev)) || (rc = S->open(ctx, out_device, out_bytes, &final_out))) return rc;
     const size_t count_words = (size_t)CXR_SHARDS * CXR_SHARD_WORDS;
     if ((rc = S->count.grow(ctx, count_words))) return rc;
     CX_HIP(ctx, hipMemsetAsync(S->count, 0, count_words * sizeof(unsigned long long), st));
@@ -355,20 +320,16 @@ extern "C" int cx_grid_resample3d(cx_ctx* ctx, const void* samples, int32_t dtyp
     CX_HIP(ctx, hipStreamSynchronize(st));      // the count is the caller's, and its host memory is its own again
     unsigned long long count = 0;
     for (uint32_t k = 0; k < CXR_SHARDS; k++) count += S->shards[k * CXR_SHARD_WORDS];
-    if (!out_device) {
-        S->shape[0] = m0; S->shape[1] = m1; S->shape[2] = m2;
-        S->dtype = out_dtype; S->n_outside = (int64_t)count; S->pending = true;
-    }
+    if (!out_device) { S->publish(m0, m1, m2); S->dtype = out_dtype; S->n_outside = (int64_t)count; }
     if (n_outside) *n_outside = (int64_t)count;
     return CX_OK;
 }
 
 extern "C" int cx_grid_resample3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_dtype, int64_t* n_outside) {
     if (!ctx) return CX_ERR_INVALID;
-    cx_resample_state* S = ctx->resample;
-    if (!S || !S->pending) return cxr_state(ctx, "cx_grid_resample3d_result: no result of cx_grid_resample3d in the context");
-    if (out_device) *out_device = S->result.get();
-    if (out_shape) { out_shape[0] = S->shape[0]; out_shape[1] = S->shape[1]; out_shape[2] = S->shape[2]; }
+    const cx_resample_state* S = ctx->resample;
+    const int rc = cx_slot_result(ctx, S, "cx_grid_resample3d_result: no result of cx_grid_resample3d in the context", out_device, out_shape);
+    if (rc) return rc;
     if (out_dtype) *out_dtype = S->dtype;
     if (n_outside) *n_outside = S->n_outside;
     return CX_OK;
@@ -377,11 +338,5 @@ extern "C" int cx_grid_resample3d_result(cx_ctx* ctx, void** out_device, int64_t
 extern "C" int cx_grid_resample3d_bind(cx_ctx* ctx) {
     if (!ctx) return CX_ERR_INVALID;
     cx_resample_state* S = ctx->resample;
-    if (!S || !S->pending) return cxr_state(ctx, "cx_grid_resample3d_bind: no result of cx_grid_resample3d in the context");
-    CX_HIP(ctx, hipSetDevice(ctx->device));
-    CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int rc = cx_grid_bind_owned(ctx, S->result, S->dtype, S->shape[0], S->shape[1], S->shape[2]);
-    if (rc) return rc;
-    S->pending = false;
-    return CX_OK;
+    return cx_slot_bind(ctx, S, "cx_grid_resample3d_bind: no result of cx_grid_resample3d in the context", S ? S->dtype : 0);
 }

@@ -684,7 +684,9 @@ int cx_level_spectrum3d(cx_ctx* ctx, const double* values, int32_t nlevels, int6
  * cx_grid_filter3d
  *   samples  NULL: the bound 3-D grid in its own CX_DTYPE_* (dtype, on_device and the shape are ignored; CX_ERR_STATE without a grid).
  *            Else n0 n1 n2 samples of type `dtype` (every axis >= 1: a 2-D array goes in as 1 x n x m; at most 2^31 samples), on the
- *            device (any pointer aligned to its own type) or on the host (copied into scratch of the context).
+ *            device (any pointer aligned to its own type) or on the host (copied into scratch of the context).  The pointer
+ *            cx_grid_filter3d_result handed out is a legal input (a pyramid on the device): that result is consumed, the new one
+ *            takes its place.
  *   axes[a]  for axis a: n_weights fp32 weights (1..129), origin (0 .. n_weights-1) and stride (1 .. n_a).  weights == NULL or
  *            n_weights == 0: the axis is not filtered, only the stride applies (out[i] = in[i stride] as fp32, origin ignored).
  *   The passes run axis 2, then axis 1, then axis 0, each on the fp32 result of the one before.  Per axis, with n the length of the

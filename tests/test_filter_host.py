@@ -79,3 +79,33 @@ def test_weight_builders_bit_for_bit():
     assert volume.block_mean_weights(1) is None
     assert np.array_equal(R.bits(np.asarray(volume.PYRAMID_WEIGHTS, dtype=np.float32)), R.bits(R.PYRAMID.astype(np.float32)))
     assert volume.default_origin(5) == R.centre(5) == 2 and volume.default_origin(4) == R.centre(4) == 2
+
+
+def test_locate_samples():
+    "the four forms of `samples` every whole-volume operation of _ffi.Context takes -> (pointer, CX_DTYPE_* code, on_device, shape)"
+    from contourist_amd import _ffi
+    keep = []
+    assert _ffi.locate_samples(None, keep) == (None, 0, 1, (0, 0, 0)) and keep == []
+    # a numpy array: made contiguous, kept alive, its own type
+    A = np.arange(4 * 5 * 6, dtype=np.int16).reshape(4, 5, 6)[:, :, ::2]
+    assert not A.flags.c_contiguous
+    ptr, code, on_device, shape = _ffi.locate_samples(A, keep)
+    assert (code, on_device, shape) == (_ffi.DTYPE_CODES["int16"], 0, (4, 5, 3))
+    assert len(keep) == 1 and keep[0].flags.c_contiguous and np.array_equal(keep[0], A) and ptr.value == keep[0].ctypes.data
+    # a big-endian array is byte-swapped on the way
+    ptr, code, on_device, shape = _ffi.locate_samples(np.arange(24, dtype=">u2").reshape(2, 3, 4), keep)
+    assert (code, on_device, shape) == (_ffi.DTYPE_CODES["uint16"], 0, (2, 3, 4))
+    assert len(keep) == 2 and keep[1].dtype.isnative and keep[1][1, 2, 3] == 23 and ptr.value == keep[1].ctypes.data
+    # (device pointer, dtype, shape): nothing to keep
+    ptr, code, on_device, shape = _ffi.locate_samples((0x7F0000001000, "uint8", [2, np.int64(3), 4]), keep)
+    assert (ptr.value, code, on_device, shape) == (0x7F0000001000, 1, 1, (2, 3, 4)) and all(type(n) is int for n in shape) and len(keep) == 2
+    # (numpy array, dtype, shape): host bytes of a type numpy has no name for
+    B = np.zeros((2, 3, 8), dtype=np.uint16)
+    ptr, code, on_device, shape = _ffi.locate_samples((B, "bfloat16", (2, 3, 8)), keep)
+    assert (ptr.value, code, on_device, shape) == (B.ctypes.data, 6, 0, (2, 3, 8)) and keep[2] is B
+    ptr, code, on_device, shape = _ffi.locate_samples((B[:, :, ::2], "bfloat16", (2, 3, 4)), keep)
+    assert (code, on_device, shape) == (6, 0, (2, 3, 4)) and keep[3].flags.c_contiguous and ptr.value == keep[3].ctypes.data != B.ctypes.data
+    with pytest.raises(ValueError):
+        _ffi.locate_samples(np.zeros((2, 2, 2), dtype=np.float64), keep)
+    with pytest.raises(AssertionError):
+        _ffi.locate_samples(np.zeros((2, 2), dtype=np.float32), keep)

@@ -434,3 +434,20 @@ def test_errors(ctx):
     # next to it is fine
     ctx.distance_grid(0.5, "signed", samples=(inner.data_ptr(), inner.dtype, A.shape), out=big.data_ptr())
     same(big[:A.size].cpu().numpy().reshape(A.shape), R.distance(A, 0.5, "signed"))
+
+
+def test_a_pointer_into_the_pending_result():
+    "planes 1 to 5 of a pending uint8 mask as the samples of the next call, whose result the context keeps again"
+    from contourist_amd import _ffi
+    A = uniform((6, 9, 70), 41)
+    first = R.mask(A, 0.97, "below", 2.0)
+    assert 0 < first[1:].sum() < first[1:].size
+    c = _ffi.Context()
+    try:
+        _, ptr = c.distance_grid(0.97, "below", "mask", radius2=2.0, samples=A)
+        n_sites, got = c.distance_grid(0.5, "below", "float32", samples=(ptr + 9 * 70, "uint8", (5, 9, 70)), download=True)
+        assert n_sites == int(first[1:].sum())
+        same(got, R.distance(first[1:], 0.5, "below"))
+        assert c.distance_result()[::2] == ((5, 9, 70), "float32")
+    finally:
+        c.close()

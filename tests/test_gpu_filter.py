@@ -409,3 +409,43 @@ def test_offsets_beyond_32_bits(ctx):
                 for t1 in range(2):
                     acc = acc + np.float64(w1[t1]) * np.float64(rows[t1])
                 assert np.float32(acc).view(np.uint32) == got[i, a, b].view(np.uint32), (i, a, b)
+
+
+def three_taps(seed):
+    return (weights(3, seed), 1, 1)
+
+
+# the pending result fed back as `samples`, the new result kept in the context again.  Axis 0 not filtered: one kernel, which before
+# the step-aside read and wrote the same buffer; all axes: two kernels; stride 2: the output is smaller than the input
+CHAIN_CASES = {
+    "one_kernel": [(None, 0, 1), three_taps(1), three_taps(2)],
+    "two_kernels": [three_taps(0), three_taps(1), three_taps(2)],
+    "one_kernel_stride_2": [(None, 0, 1), three_taps(1), (weights(3, 2), 1, 2)],
+    "two_kernels_stride_2": [three_taps(0), three_taps(1), (weights(3, 2), 1, 2)],
+}
+
+
+@pytest.mark.parametrize("case", sorted(CHAIN_CASES))
+def test_the_pending_result_is_the_next_input(case):
+    "axis 2 (70) is longer than one tile of 64 columns; every step == the restatement applied once more; steady state allocates nothing"
+    from contourist_amd import _ffi
+    axes = CHAIN_CASES[case]
+    A = field((5, 9, 70), 31)
+    c = _ffi.Context()
+    try:
+        shape, ptr = c.filter_grid(axes, "reflect", samples=A)
+        want = R.filter3d(A, axes, "reflect")
+        assert shape == want.shape
+        for step in range(2, 6):
+            if step >= 4:      # from the third chained call on (the fourth call in all)
+                before = _ffi.device_bytes(c.handle)
+            shape, got = c.filter_grid(axes, "reflect", samples=(ptr, "float32", shape), download=True)
+            want = R.filter3d(want, axes, "reflect")
+            assert shape == want.shape == got.shape, (step, shape, want.shape)
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (step, float(np.abs(got - want).max()))
+            described, ptr = c.filter_result()
+            assert described == shape and ptr
+            if step >= 4:
+                assert _ffi.device_bytes(c.handle) == before, step
+    finally:
+        c.close()

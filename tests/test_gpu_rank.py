@@ -491,3 +491,17 @@ def test_errors(ctx):
     ctx.synchronize()
     assert big[:A.size].cpu().numpy().reshape(A.shape).tobytes() == R.rank_filter(A, 13, 3).tobytes()
 
+
+def test_a_pointer_into_the_pending_result():
+    "planes 1 to 5 of the pending result as the samples of the next call, whose result the context keeps again"
+    from contourist_amd import _ffi
+    A = field((6, 9, 70), 41, np.uint8)
+    first = R.rank_filter(A, 13, 3)
+    c = _ffi.Context()
+    try:
+        _, ptr = c.rank_grid(3, 13, samples=A)
+        shape, got = c.rank_grid(3, 13, samples=(ptr + 9 * 70, "uint8", (5, 9, 70)), download=True)
+        assert shape == (5, 9, 70) and R.same_bytes(got, R.rank_filter(first[1:], 13, 3))
+        assert c.rank_result()[::2] == ((5, 9, 70), "uint8")
+    finally:
+        c.close()
