@@ -2088,14 +2088,16 @@ int cx_level1_clip_tail(cx_ctx* ctx, uint32_t nv_raw, uint32_t nt_raw, bool do_c
     CX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return cxp_publish(ctx, S, cxp_record::MESH3D, cxp_record::CLIPPED, nullptr, nullptr);
 }
-// room for the normals the clipped mesh carries (one per vertex of it, written by the caller on the context's stream)
+// room for the normals the clipped mesh carries (one per vertex of it, written by the caller on the context's stream).  The clip reads
+// its source's normals from the copy cx_level1_normals made (carried ones included), never from nrm[] itself, so the new ones take
+// the current buffer: changing over to the other one, as the simplification and the component filter must, gave the second buffer its
+// size only at the second clip, an allocation in the steady state of clip, post-pass, clip
 int cx_level1_clip_normals(cx_ctx* ctx, double** out) {
     cx_post_state* S = ctx->post;
     const int cur = S->nrm_cur;
-    const int rc = S->nrm[1 - cur].grow(ctx, ((size_t)S->nv_out + 1) * 3 * sizeof(double));
+    const int rc = S->nrm[cur].grow(ctx, ((size_t)S->nv_out + 1) * 3 * sizeof(double));
     if (rc) return rc;
-    *out = S->nrm[1 - cur].as<double>();
-    S->nrm_cur = 1 - cur;
+    *out = S->nrm[cur].as<double>();
     S->rec.normals_carried = true;
     return CX_OK;
 }

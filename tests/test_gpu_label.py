@@ -626,3 +626,29 @@ def test_errors(ctx):
             ctx.label_select(np.ones(k + 1), out=out)
         assert e.value.code == _ffi.CX_ERR_INVALID
     assert ctx.label_result() == (A.shape, lptr, "high", 1, k)      # the refused calls changed nothing
+
+
+def test_a_pointer_into_the_pending_result():
+    "planes 1 to 5 of the pending mask of a selection as the samples of the next call, whose selection writes the context's mask again"
+    from contourist_amd import _ffi
+    A = uniform((6, 9, 70), 41)
+    labels, k = R.label(A, 0.6, "high", 1)
+    keep = keep_pattern(k)
+    keep[0] = 0      # two components of three, and none of the unlabelled samples
+    first = R.select(labels, keep)[0]
+    assert k >= 2 and 0 < first[1:].sum() < first[1:].size
+    c = _ffi.Context()
+    try:
+        c.label_grid(0.6, "high", 1, samples=A)
+        _, mptr = c.label_select(keep)
+        k2, got = c.label_grid(0.5, "high", 2, samples=(mptr + 9 * 70, "uint8", (5, 9, 70)), download=True)
+        want, want_k = R.label(first[1:], 0.5, "high", 2)
+        assert k2 == want_k >= 2
+        same(got, want)
+        n, mask = c.label_select(keep_pattern(k2), download=True)
+        want_mask, want_n = R.select(want, keep_pattern(k2))
+        assert n == want_n
+        same(mask, want_mask)
+        assert c.label_result()[::2] == ((5, 9, 70), "high", k2) and c.label_mask_result()[::2] == ((5, 9, 70), n)
+    finally:
+        c.close()

@@ -485,3 +485,20 @@ def test_twice_the_same_bytes_and_counts(ctx):
         stats2, again = ctx.reconstruct_grid(marker, samples=A, download=True, **kw)
         assert R.same_bytes(got, want) and again.tobytes() == got.tobytes()
         assert (stats["n_changed"], stats["n_clamped"]) == (n_changed, n_clamped) == (stats2["n_changed"], stats2["n_clamped"])
+
+
+def test_a_pointer_into_the_pending_result():
+    "planes 1 to 5 of the pending result as the mask of the next call, whose result the context keeps again"
+    from contourist_amd import _ffi
+    A, G, _ = typed("uint8", (6, 9, 70), 41)
+    first = C.reconstruct(A, G)[0]
+    want, n_changed, n_clamped = C.reconstruct(np.ascontiguousarray(first[1:]), "step")
+    assert n_changed > 0
+    c = _ffi.Context()
+    try:
+        _, ptr = c.reconstruct_grid(G, samples=A)
+        stats, got = c.reconstruct_grid("step", samples=(ptr + 9 * 70, "uint8", (5, 9, 70)), download=True)
+        assert (stats["n_changed"], stats["n_clamped"]) == (n_changed, n_clamped) and R.same_bytes(got, want)
+        assert c.reconstruct_result()[::2] == ((5, 9, 70), "uint8")
+    finally:
+        c.close()

@@ -499,3 +499,22 @@ def test_errors(ctx):
     ctx.resample_grid(M, o, A.shape, samples=src, out=big.data_ptr())
     ctx.synchronize()
     assert big[:A.size].cpu().numpy().reshape(A.shape).tobytes() == R.resample(A, M, o, A.shape, 1)[0].tobytes()
+
+
+def test_a_pointer_into_the_pending_result():
+    "planes 1 to 5 of the pending result as the samples of the next call, whose result the context keeps again: both kernels"
+    from contourist_amd import _ffi
+    A = field((6, 9, 70), 41)
+    part = (5, 9, 70)
+    for M, off in TYPE_MAPS:
+        first = R.resample(A, M, off, A.shape, 1, "reflect", 0.0)[0]
+        want, want_outside = R.resample(first[1:], M, off, part, 1, "reflect", 0.0)
+        assert want_outside > 0
+        c = _ffi.Context()
+        try:
+            _, ptr = c.resample_grid(M, off, A.shape, 1, "reflect", 0.0, samples=A)
+            n_outside, got = c.resample_grid(M, off, part, 1, "reflect", 0.0, samples=(ptr + 9 * 70 * 4, "float32", part), download=True)
+            assert n_outside == want_outside and R.same_bytes(got, want)
+            assert c.resample_result()[::2] == (part, "float32")
+        finally:
+            c.close()
