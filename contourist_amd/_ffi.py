@@ -69,6 +69,8 @@ RECON_MARKERS = {"array": 0, "shift": 1, "step": 2, "rim": 3}       # CX_RECON_M
 RECON_OUTS = {"values": 0, "changed": 1}                            # CX_RECON_OUT_*
 RECON_ALL_FACES = 63                                                # bit 0: i = 0, 1: i = n0-1, 2: j = 0, 3: j = n1-1, 4: k = 0, 5: k = n2-1
 RECON_STATS = ("n_changed", "n_clamped", "rounds", "tile_visits")   # cx_recon_stats, four int64
+WATERSHED_DIRECTIONS = {"rising": 0, "falling": 1}                  # CX_WATERSHED_RISING / _FALLING
+WATERSHED_STATS = ("n_labelled", "n_unreached", "n_ignored", "n_markers", "rounds", "tile_visits", "jump_rounds")   # cx_watershed_stats, seven int64
 # one record of cx_grid_label3d_measures (cx_label_component): 72 bytes
 LABEL_COMPONENT_DTYPE = np.dtype([("voxels", "<i8"), ("first", "<i8"), ("sum", "<i8", (3,)), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)),
                                   ("rim", "<u4"), ("reserved", "<u4")])
@@ -94,6 +96,7 @@ SYMBOLS = [
     "cx_grid_resample3d", "cx_grid_resample3d_result", "cx_grid_resample3d_bind",
     "cx_grid_rank3d", "cx_grid_rank3d_result", "cx_grid_rank3d_bind",
     "cx_grid_reconstruct3d", "cx_grid_reconstruct3d_result", "cx_grid_reconstruct3d_bind",
+    "cx_grid_watershed3d", "cx_grid_watershed3d_result",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -357,6 +360,8 @@ def load():
                                   ctypes.c_int32, vp, vp, vp],
         "cx_grid_reconstruct3d_result": [vp, ctypes.POINTER(vp), vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)],
         "cx_grid_reconstruct3d_bind": [vp],
+        "cx_grid_watershed3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp],
+        "cx_grid_watershed3d_result": [vp, ctypes.POINTER(vp), vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -919,6 +924,59 @@ class Context(object):
         """the result the last reconstruct_grid left in the context becomes the bound grid (the samples' own type, uint8 for "changed", owned
         by the context): cx_grid_reconstruct3d_bind"""
         self._bind_pending(self.reconstruct_result, self.lib.cx_grid_reconstruct3d_bind)
+
+    def watershed_grid(self, markers, region=None, connectivity=1, direction="rising", samples=None, out=None, out_host=None):
+        """marker-based watershed of the relief `samples` (cx_grid_watershed3d) -> (stats, the labels).
+        samples: as in filter_grid (None = the bound grid, a 3-D numpy array, (device pointer, dtype, shape), (numpy array, dtype, shape)).
+        markers: int32 of the relief's shape, a value above 0 a label: a numpy array beside host samples, a device pointer beside
+        samples on the device (or the bound grid).  region: None = every sample, or uint8 given the way the markers are, non-zero =
+        inside.  connectivity: 1, 2 or 3; direction: a name of WATERSHED_DIRECTIONS ("falling" floods from the maxima down).
+        out: None = the labels stay in the context (watershed_result); or a device pointer to room for n int32.  out_host: None, True
+        (a new int32 array) or a contiguous int32 array of the relief's shape, which receives a copy.
+        stats: a dict of WATERSHED_STATS (the first four exact, the last three informational).  The labels: the host array with
+        out_host, else their device pointer."""
+        keep = []
+        ptr, code, on_device, shape = locate_samples(samples, keep)
+        if samples is None:
+            if self.shape is None:
+                raise CxError(CX_ERR_STATE, "watershed_grid: no samples given and no grid bound")
+            shape = tuple(self.shape)
+
+        def beside(a, dtype, name):
+            "the pointer of an array that lives where the samples do"
+            if a is None:
+                return None
+            if on_device:
+                assert not isinstance(a, np.ndarray), "%s: a device pointer beside samples on the device" % name
+                return ctypes.c_void_p(int(a))
+            h = np.ascontiguousarray(a, dtype=dtype)
+            assert h.shape == tuple(shape), "%s: the shape of the samples" % name
+            keep.append(h)
+            return ctypes.c_void_p(h.ctypes.data)
+        mptr = beside(markers, np.int32, "markers")
+        rptr = beside(region, np.uint8, "region")
+        host_out = None
+        if out_host is True:
+            host_out = np.empty(shape, dtype=np.int32)
+        elif out_host is not None:
+            host_out = out_host
+            assert isinstance(host_out, np.ndarray) and host_out.dtype == np.int32 and host_out.flags.c_contiguous and host_out.shape == tuple(shape), \
+                "out_host: a contiguous int32 array of the samples' shape"
+        st = np.zeros(len(WATERSHED_STATS), dtype=np.int64)
+        self._check(self.lib.cx_grid_watershed3d(self.handle, ptr, code, on_device, shape[0] if samples is not None else 0,
+                                                 shape[1] if samples is not None else 0, shape[2] if samples is not None else 0, mptr, rptr,
+                                                 int(connectivity), WATERSHED_DIRECTIONS[direction], ctypes.c_void_p(int(out)) if out else None,
+                                                 None if host_out is None else host_out.ctypes.data, st.ctypes.data))
+        stats = dict(zip(WATERSHED_STATS, (int(x) for x in st)))
+        if host_out is not None:
+            return stats, host_out
+        return stats, (int(out) if out else self.watershed_result()[1])
+
+    def watershed_result(self):
+        "(shape, device pointer) of the labels the last watershed_grid left in the context (cx_grid_watershed3d_result)"
+        p, m = ctypes.c_void_p(), np.zeros(3, dtype=np.int64)
+        self._check(self.lib.cx_grid_watershed3d_result(self.handle, ctypes.byref(p), m.ctypes.data))
+        return tuple(int(x) for x in m), int(p.value or 0)
 
     def level0_points_f64(self, counts):
         "float64 coordinates of the Level-0 vertices as the reference interpolates them, in download_level0 order"

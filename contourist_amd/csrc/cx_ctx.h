@@ -212,6 +212,8 @@ struct cx_ctx {
     struct cx_resample_state* resample = nullptr;
     struct cx_rank_state* rank = nullptr;
     struct cx_recon_state* recon = nullptr;
+    // the marker-based watershed (cx_watershed.hip): a seventh slot; its result is int32 labels, which are not a grid to bind
+    struct cx_watershed_state* watershed = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -413,6 +415,8 @@ void cx_resample_free(cx_ctx* ctx);
 void cx_rank_free(cx_ctx* ctx);
 // cx_recon.hip
 void cx_recon_free(cx_ctx* ctx);
+// cx_watershed.hip
+void cx_watershed_free(cx_ctx* ctx);
 bool cx_level1_capped(cx_ctx* ctx);   // cx_post.hip: the Level-1 mesh came out of cx_postprocess3d_capped (or is a filtered copy of one)
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);

@@ -822,3 +822,118 @@ def propagate(seeds, mask, connectivity=1, device=None):
         assert a.dtype in (np.bool_, np.uint8), "seeds and mask: bool or uint8"
         return (a != 0).astype(np.uint8)
     return _reconstruct(binary(mask), binary(seeds), 0.0, 0, "dilation", connectivity, "values", device)
+
+
+# ---- marker-based watershed (cx_grid_watershed3d, csrc/cx_watershed.hip) ------------------------------------------------------------
+# The labels of the markers flooded over a relief, low values first ("rising") or high values first ("falling": a distance field is
+# flooded from its maxima without being negated).  Every sample of the domain (inside the region, not NaN) takes the label of the
+# marker whose flood arrives first by the cost (level, steps since that level was entered); exact ties go to the neighbour with the
+# smaller linear index, a stated bias that makes the labels a pure function of the inputs (include/contourist_hip.h, "watershed").
+# They equal a numpy restatement (tests/watershed_ref.py) byte for byte; skimage.segmentation.watershed and
+# scipy.ndimage.watershed_ift break ties differently.  The labels' lattice is the samples' own.
+
+def _beside(a, on_device, shape, kind, name):
+    "markers (kind int32) or a region (kind uint8, non-zero = inside) that lives where the relief does, contiguous and of its shape"
+    if on_device:
+        import torch
+        assert grid_field._is_torch(a) and a.is_cuda, "%s: a GPU tensor beside a relief on the GPU" % name
+        assert tuple(int(n) for n in a.shape) == shape, "%s: the shape of the relief" % name
+        t = (a != 0).to(torch.uint8) if kind == "uint8" else a.to(torch.int32)
+        return t.contiguous()
+    assert not grid_field._is_torch(a), "%s: a numpy array beside a numpy relief" % name
+    a = np.asarray(a)
+    assert a.shape == shape, "%s: the shape of the relief" % name
+    if kind == "uint8":
+        return np.ascontiguousarray(a != 0, dtype=np.uint8)
+    assert a.dtype.kind in "iub", "%s: integer labels" % name
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _on_device(context, arrays):
+    "numpy arrays as byte tensors on the context's device (None stays None), there when this returns"
+    import torch
+    dev = torch.device("cuda", context.device)
+    out = [None if a is None else torch.from_numpy(np.ascontiguousarray(a).reshape(-1).view(np.uint8)).to(dev) for a in arrays]
+    torch.cuda.current_stream(dev).synchronize()      # the context has a stream of its own
+    return out
+
+
+def _flood(context, on_device, src, shape, shape3, markers_ptr, region_ptr, connectivity, direction, like):
+    "cx_grid_watershed3d on device inputs -> (labels beside the caller's relief: a tensor like `like`, or a numpy array; stats)"
+    if on_device:
+        import torch
+        out = torch.empty(shape3, dtype=torch.int32, device=like.device)
+        stats, _ = context.watershed_grid(markers_ptr, region_ptr, connectivity, direction, samples=src, out=out.data_ptr())
+        return out.reshape(shape), stats
+    stats, labels = context.watershed_grid(markers_ptr, region_ptr, connectivity, direction, samples=src, out_host=True)
+    return labels.reshape(shape), stats
+
+
+def watershed(relief, markers=None, region=None, connectivity=1, direction="rising", device=None, return_stats=False):
+    """the int32 labels of `markers` flooded over the relief (cx_grid_watershed3d); with return_stats=True (labels, stats).
+    markers: integers of the relief's shape, a value above 0 a label (one label may sit on many samples); None: the labelled regional
+    minima of the relief ("rising") or maxima ("falling"), found with `regional_minima` / `regional_maxima` and `label`'s kernels at
+    the same connectivity.  region: None, or an array of the relief's shape, non-zero = inside; samples outside it and NaN samples get
+    0 and stop the flood.  connectivity 1, 2, 3: 6, 18 or 26 neighbours.  direction "rising": the flood starts at low values;
+    "falling": at high ones.  Exact ties go to the neighbour with the smaller linear index.
+    Relief, markers and region: numpy arrays (a numpy array comes back) or contiguous GPU tensors (a tensor comes back) of 1 to 3
+    dimensions; a bool relief counts as uint8, types the kernels do not read are converted to float32 first.  Every step runs on the
+    device of one context: no volume crosses to the host between them."""
+    assert direction in _ffi.WATERSHED_DIRECTIONS, "direction: 'rising' or 'falling'"
+    assert connectivity in (1, 2, 3), "connectivity: 1, 2 or 3"
+    on_device, s, shape = _distance_samples(relief)
+    ndim = len(shape)
+    assert 1 <= ndim <= 3, "samples of 1 to 3 dimensions"
+    shape3 = (1,) * (3 - ndim) + shape
+    m = None if markers is None else _beside(markers, on_device, shape, "int32", "markers")
+    g = None if region is None else _beside(region, on_device, shape, "uint8", "region")
+    if on_device:
+        import torch
+        context = _context(s.device.index if device is None else device)
+        torch.cuda.current_stream(s.device).synchronize()      # the inputs are there; the context has a stream of its own
+        ds, dm, dg = s, m, g
+    else:
+        context = _context(device)
+        ds, dm, dg = _on_device(context, [s, m, g])
+    src = (ds.data_ptr(), s.dtype, shape3)
+    if dm is None:
+        _, extrema = context.reconstruct_grid("step", 0.0, 0, "erosion" if direction == "rising" else "dilation", connectivity, "changed", samples=src)
+        _, markers_ptr = context.label_grid(0.5, "high", connectivity, samples=(extrema, "uint8", shape3))
+    else:
+        markers_ptr = dm.data_ptr()
+    labels, stats = _flood(context, on_device, src, shape, shape3, markers_ptr, None if dg is None else dg.data_ptr(), connectivity, direction, s)
+    return (labels, stats) if return_stats else labels
+
+
+def split_touching(samples, value, h, side="high", connectivity=1, sampling=None, device=None):
+    """int32 labels that separate the touching grains, cells or pores of the object {f >= value} (side "high") or {f < value} ("low"):
+    the distance inside the object (`distance`), its `h_maxima` (bumps of the distance field shallower than h do not split an object;
+    h in the distance's units, finite and above 0), their regional maxima labelled as markers, and a falling `watershed` of the distance
+    field with the object as the region.  0 outside the object.  The whole chain runs on one context; nothing but the labels comes
+    back.  Samples: a numpy array (a numpy array comes back) or a contiguous GPU tensor (a tensor comes back) of 1 to 3 dimensions."""
+    assert side in _ffi.LABEL_SIDES, "side: 'high' or 'low'"
+    assert connectivity in (1, 2, 3), "connectivity: 1, 2 or 3"
+    h = _recon_h(h, np.float32)
+    on_device, s, shape = _distance_samples(samples)
+    ndim = len(shape)
+    assert 1 <= ndim <= 3, "samples of 1 to 3 dimensions"
+    shape3 = (1,) * (3 - ndim) + shape
+    if sampling is not None:
+        sampling = [float(x) for x in _per_axis(sampling, ndim, 1.0, "sampling")]
+    if on_device:
+        import torch
+        context = _context(s.device.index if device is None else device)
+        torch.cuda.current_stream(s.device).synchronize()      # the samples are there; the context has a stream of its own
+        ds = s
+    else:
+        context = _context(device)
+        ds, = _on_device(context, [s])
+    src = (ds.data_ptr(), s.dtype, shape3)
+    k, _ = context.label_grid(value, side, connectivity, samples=src)
+    _, region_ptr = context.label_select(np.concatenate([[False], np.ones(k, dtype=bool)]))      # the object, uint8
+    _, dist_ptr = context.distance_grid(value, "above" if side == "high" else "below", "float32", sampling, samples=src)
+    field = (dist_ptr, "float32", shape3)
+    _, flat_ptr = context.reconstruct_grid("shift", h, 0, "dilation", connectivity, "values", samples=field)
+    _, maxima_ptr = context.reconstruct_grid("step", 0.0, 0, "dilation", connectivity, "changed", samples=(flat_ptr, "float32", shape3))
+    _, markers_ptr = context.label_grid(0.5, "high", connectivity, samples=(maxima_ptr, "uint8", shape3))
+    return _flood(context, on_device, field, shape, shape3, markers_ptr, region_ptr, connectivity, "falling", s)[0]

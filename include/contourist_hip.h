@@ -1008,6 +1008,67 @@ int cx_grid_reconstruct3d(cx_ctx* ctx, const void* mask, int32_t dtype, int on_d
 int cx_grid_reconstruct3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3], int32_t* out_dtype, int32_t* out_kind);
 int cx_grid_reconstruct3d_bind(cx_ctx* ctx);
 
+/* ---- watershed: marker-based watershed of a volume, on the device ----------------------------------------------------------------------
+ * The labels of the markers flooded over a relief: Meyer's flooding with first-in first-out lakes, written as a path cost so that the
+ * ties have one answer.  The last step of the chain threshold, distance field, h-maxima, regional maxima, labels: it splits grains,
+ * cells or pores that touch.  What a caller ran skimage.segmentation.watershed or scipy.ndimage.watershed_ift for -- but their ties
+ * differ from each other and from these, so neither is an equality oracle.
+ *
+ * cx_grid_watershed3d
+ *   relief   the samples f: NULL = the bound grid (CX_ERR_STATE when none is bound); else n0 n1 n2 samples of CX_DTYPE_* `dtype` in device
+ *            memory (on_device != 0) or host memory, every axis >= 1, at most 2^31 samples (CX_ERR_UNSUPPORTED beyond).
+ *   markers  int32, the relief's shape, and where the relief is: device memory when the relief is on the device or the bound grid, host
+ *            memory with a host relief.  A value above 0 is a label; everything else means "no marker".  One label may sit on many
+ *            samples, connected or not.  CX_ERR_INVALID when NULL.
+ *   region   NULL = every sample is inside; else uint8 of the same shape and residency, non-zero = inside.
+ *   connectivity  1, 2 or 3: 6, 18 or 26 neighbours, as in cx_grid_label3d.
+ *   direction  CX_WATERSHED_RISING floods from low values up.  CX_WATERSHED_FALLING is the dual: the same kernels on complemented keys,
+ *            as CX_RECON_EROSION does it, so that a distance field is flooded from its maxima without being negated.
+ *   Domain.  The samples that are inside the region and are not NaN (NaN is tested on the sample, before any complement).  A sample
+ *            outside the domain always gets label 0.  A marker outside the domain is ignored and counted in n_ignored.
+ *   Comparisons.  All on keys: the sample's bits mapped to an unsigned integer whose order is -inf < ... < -0.0 < +0.0 < ... < +inf for
+ *            floats and the value's order for integers (the keys of cx_grid_rank3d); FALLING compares key ^ ones (of the key's width).
+ *            No arithmetic is done on samples.
+ *   Arrival cost.  A path is a sequence of neighbours inside the domain that starts on a marker sample s and passes through no other
+ *            marker sample.  Its cost is a pair (P, d), built step by step: at s it is (key(s), 0); a step onto v from cost (P, d)
+ *            gives (key(v), 0) if key(v) > P (a climb to a new level), else (P, d + 1) (staying in the lake at level P).  W(v) is the
+ *            lexicographically least cost over all such paths to v, "unreached" when there is none.  P is the level at which the flood
+ *            wets v, d the number of steps since that level was entered.  Equivalently W is the unique fixed point of
+ *            W(v) = min over neighbours u of step(W(u), v) with the marker samples held at (key, 0); unique because a step strictly
+ *            increases the pair.
+ *   Labels.  A marker sample keeps its label.  Every other reached sample takes the label of ONE neighbour: the one with the least W,
+ *            among neighbours of equal W the one with the smallest linear index in C order.  That neighbour's W is strictly below the
+ *            sample's own, so the rule is well founded.  Unreached samples and samples outside the domain get 0.  The labels are a pure
+ *            function of the inputs: the same bytes in every call, whatever order the device works in.  The index tie-break is a
+ *            stated BIAS towards low indices on exact ties (a plateau between two markers at equal distance goes to the side whose
+ *            samples come first in C order); it is what makes the answer unique, not a claim about the data.
+ *   out_device, out_host  int32 labels.  A caller's device buffer (n0 n1 n2 int32, aligned to 4, else CX_ERR_INVALID) may not overlap
+ *            a device input (CX_ERR_INVALID) and leaves the context without a result; NULL: the labels go into a buffer the context
+ *            owns and stay pending until the next cx_grid_watershed3d, in a seventh slot of its own: the pending results of
+ *            cx_grid_filter3d, cx_grid_distance3d, cx_grid_label3d (and its select), cx_grid_resample3d, cx_grid_rank3d and
+ *            cx_grid_reconstruct3d are not disturbed, and their pending pointers are legal inputs here (labels as markers, a
+ *            select mask as region, a distance field or reconstruction as relief).  This call's own pending result is a legal
+ *            `markers` of the next call.  out_host not NULL: also receives a copy.  The call returns after the stream has run it.
+ *   stats    may be NULL.  n_labelled: samples with a label above 0; n_unreached: samples INSIDE the domain that no path reaches;
+ *            n_ignored: marker samples outside the domain; n_markers: marker samples inside it.  These four are exact and the same in
+ *            every call.  rounds (kernel launches that visited a tile), tile_visits and jump_rounds (pointer-doubling passes that
+ *            resolved the labels) are informational and may differ from call to call.
+ *   No marker inside the domain is not an error: CX_OK, all labels 0.
+ *   CX_ERR_INVALID: an unknown sample type, an axis below 1, NULL markers, a connectivity outside 1..3, an unknown direction, an output
+ *   that overlaps an input, an out_device not aligned to 4.  CX_ERR_UNSUPPORTED: more than 2^31 samples.  CX_ERR_STATE: NULL relief
+ *   with no grid bound.  CX_ERR_HIP with a message if tiles were still active after as many rounds as the array has samples, or the
+ *   labels unresolved after 32 doubling passes (no correct run gets to either).
+ * cx_grid_watershed3d_result: the pending labels: device pointer and shape; CX_ERR_STATE when nothing is pending.
+ * There is no _bind: labels are not a grid to march.  A call leaves the bound grid, the current extraction, the selected level and the
+ * Level-1 state as they are.  tests/watershed_ref.py restates all of it in numpy. */
+#define CX_WATERSHED_RISING  0
+#define CX_WATERSHED_FALLING 1
+typedef struct cx_watershed_stats { int64_t n_labelled, n_unreached, n_ignored, n_markers, rounds, tile_visits, jump_rounds; } cx_watershed_stats;
+int cx_grid_watershed3d(cx_ctx* ctx, const void* relief, int32_t dtype, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                        const int32_t* markers, const uint8_t* region, int32_t connectivity, int32_t direction,
+                        void* out_device, void* out_host, cx_watershed_stats* stats);
+int cx_grid_watershed3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3]);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
