@@ -75,6 +75,13 @@ WATERSHED_STATS = ("n_labelled", "n_unreached", "n_ignored", "n_markers", "round
 LABEL_COMPONENT_DTYPE = np.dtype([("voxels", "<i8"), ("first", "<i8"), ("sum", "<i8", (3,)), ("lo", "<i4", (3,)), ("hi", "<i4", (3,)),
                                   ("rim", "<u4"), ("reserved", "<u4")])
 assert LABEL_COMPONENT_DTYPE.itemsize == 72
+# one record of cx_grid_regions3d (cx_region): the measures of cx_label_component, then the value fields; 128 bytes
+REGION_DTYPE = np.dtype(LABEL_COMPONENT_DTYPE.descr + [("n_nan", "<i8"), ("min_at", "<i8"), ("max_at", "<i8"), ("vmin", "<f8"), ("vmax", "<f8"),
+                                                       ("isum", "<i8"), ("vsum", "<f8")])
+# one record of cx_grid_regions3d_contacts (cx_region_contact): 32 bytes
+REGION_CONTACT_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("faces", "<i8", (3,))])
+assert REGION_DTYPE.itemsize == 128 and REGION_CONTACT_DTYPE.itemsize == 32
+CX_REGIONS_MAX_LABEL = 1 << 24
 
 # every symbol include/contourist_hip.h declares (tests check the library exports all of them)
 SYMBOLS = [
@@ -97,6 +104,7 @@ SYMBOLS = [
     "cx_grid_rank3d", "cx_grid_rank3d_result", "cx_grid_rank3d_bind",
     "cx_grid_reconstruct3d", "cx_grid_reconstruct3d_result", "cx_grid_reconstruct3d_bind",
     "cx_grid_watershed3d", "cx_grid_watershed3d_result",
+    "cx_grid_regions3d", "cx_grid_regions3d_select", "cx_grid_regions3d_select_result", "cx_grid_regions3d_bind", "cx_grid_regions3d_map", "cx_grid_regions3d_contacts",
     "cx_grid4d_upload", "cx_grid4d_adopt_device", "cx_set_origin4d", "cx_extract4d", "cx_extract4d_async", "cx_counts4d_get", "cx_select_seeded4d", "cx_select_seeded4d_ex", "cx_seeded_mode", "cx_halo_exchange", "cx_rccl_unique_id", "cx_rccl_comm_init", "cx_rccl_comm_destroy", "cx_rccl_available", "cx_rccl_comm_share", "cx_slab_step", "cx_seeded4d_mask_download", "cx_level0_4d_download", "cx_postprocess4d", "cx_postprocess4d_points", "cx_level1_4d_download", "cx_morph_triangles", "cx_morph_download", "cx_morph_eval", "cx_morph_eval_download", "cx_morph_eval_many", "cx_morph_eval_many_download", "cx_morph_eval_many_device_ptrs", "cx_morph_eval_many_download_all",
     "cx_slab4d_begin", "cx_slab4d_append", "cx_slab4d_finish", "cx_slab4d_download_keys",
     "cx_contour2d_extract", "cx_contour2d_download",
@@ -362,6 +370,12 @@ def load():
         "cx_grid_reconstruct3d_bind": [vp],
         "cx_grid_watershed3d": [vp, vp, ctypes.c_int32, ctypes.c_int, i64, i64, i64, vp, vp, ctypes.c_int32, ctypes.c_int32, vp, vp, vp],
         "cx_grid_watershed3d_result": [vp, ctypes.POINTER(vp), vp],
+        "cx_grid_regions3d": [vp, vp, ctypes.c_int, i64, i64, i64, vp, ctypes.c_int32, ctypes.c_int, vp, i64, vp, vp],
+        "cx_grid_regions3d_select": [vp, vp, ctypes.c_int, i64, i64, i64, vp, i64, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp],
+        "cx_grid_regions3d_select_result": [vp, ctypes.POINTER(vp), vp, vp, ctypes.POINTER(ctypes.c_int64)],
+        "cx_grid_regions3d_bind": [vp],
+        "cx_grid_regions3d_map": [vp, vp, ctypes.c_int, i64, i64, i64, vp, i64, vp, vp],
+        "cx_grid_regions3d_contacts": [vp, vp, ctypes.c_int, i64, i64, i64, vp, i64, vp],
         "cx_debug_stamps": [vp, i64, vp],
         "cx_grid4d_upload": [vp, vp, i64, i64, i64, i64],
         "cx_grid4d_adopt_device": [vp, vp, i64, i64, i64, i64],
@@ -977,6 +991,110 @@ class Context(object):
         p, m = ctypes.c_void_p(), np.zeros(3, dtype=np.int64)
         self._check(self.lib.cx_grid_watershed3d_result(self.handle, ctypes.byref(p), m.ctypes.data))
         return tuple(int(x) for x in m), int(p.value or 0)
+
+    @staticmethod
+    def _locate_labels(labels, keep):
+        """the labels of a regions call -> (pointer, on_device, shape): a 3-D numpy array (made int32 and contiguous, appended to `keep`)
+        or (device pointer, shape) of contiguous int32 labels on the device"""
+        if isinstance(labels, tuple):
+            ptr, shape = labels
+            shape = tuple(int(n) for n in shape)
+            assert len(shape) == 3, "3-D label array expected"
+            return ctypes.c_void_p(int(ptr)), 1, shape
+        host = np.ascontiguousarray(labels, dtype=np.int32)
+        assert host.ndim == 3, "3-D label array expected"
+        keep.append(host)
+        return ctypes.c_void_p(host.ctypes.data), 0, tuple(int(n) for n in host.shape)
+
+    def regions_grid(self, labels, values=None, count_only=False):
+        """one record (REGION_DTYPE) per label 1 .. K of an int32 label volume, K its largest label (cx_grid_regions3d); record c - 1
+        belongs to label c.  labels: a 3-D numpy array or (device pointer, shape).  values: None, or a second array of the labels' shape
+        given as `samples` is elsewhere (a numpy array of a type of DTYPE_CODES, (device pointer, dtype, shape), (numpy array, dtype,
+        shape)): the records then carry its extremes, their places and its sums per label.  count_only: -> (K, number of negative
+        labels) and no records."""
+        keep = []
+        lptr, on_device, shape = self._locate_labels(labels, keep)
+        vptr, vcode, v_on_device = None, 0, 0
+        if values is not None:
+            vptr, vcode, v_on_device, vshape = locate_samples(values, keep)
+            assert vshape == shape, "values: the shape of the labels"
+        k, neg = ctypes.c_int64(), ctypes.c_int64()
+        head = (self.handle, lptr, on_device, shape[0], shape[1], shape[2], vptr, vcode, v_on_device)
+        self._check(self.lib.cx_grid_regions3d(*head, None, 0, ctypes.addressof(k), ctypes.addressof(neg)))
+        if count_only:
+            return int(k.value), int(neg.value)
+        out = np.zeros(int(k.value), dtype=REGION_DTYPE)
+        if len(out):
+            self._check(self.lib.cx_grid_regions3d(*head, out.ctypes.data, len(out), None, None))
+        return out
+
+    def regions_select(self, labels, keep, box=None, pad=0, out=None, download=False):
+        """uint8 mask of the labels whose keep flag is set, cropped to a box grown by `pad` (cx_grid_regions3d_select) ->
+        (number of ones, shape, origin, the mask).  keep: flags indexed by label, keep[0] for the background; labels beyond it are not
+        kept.  box: None = the whole array, or (lo, hi), index triples, both ends included; pad: 0 .. 8, the rim of zeros where it
+        leaves the array.  origin = lo - pad, the place of the mask's first sample in the labels' indices (may be negative).
+        out: None = the mask stays in the context (regions_mask_result, bind_region_mask); or a device pointer to room for it.
+        The mask: a numpy array with download=True, else its device pointer."""
+        held = []
+        lptr, on_device, shape = self._locate_labels(labels, held)
+        flags = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8).reshape(-1)
+        lo = hi = None
+        if box is not None:
+            lo = np.ascontiguousarray(box[0], dtype=np.int64).reshape(3)
+            hi = np.ascontiguousarray(box[1], dtype=np.int64).reshape(3)
+        host_out = None
+        if download:
+            ext = [(int(hi[a] - lo[a]) + 1 if box is not None else shape[a]) + 2 * int(pad) for a in range(3)]
+            host_out = np.empty([max(0, e) for e in ext], dtype=np.uint8)
+        m, org, n = np.zeros(3, dtype=np.int64), np.zeros(3, dtype=np.int64), ctypes.c_int64()
+        self._check(self.lib.cx_grid_regions3d_select(self.handle, lptr, on_device, shape[0], shape[1], shape[2], flags.ctypes.data if len(flags) else None,
+                                                      len(flags), None if lo is None else lo.ctypes.data, None if hi is None else hi.ctypes.data, int(pad),
+                                                      ctypes.c_void_p(int(out)) if out else None, None if host_out is None else host_out.ctypes.data,
+                                                      m.ctypes.data, org.ctypes.data, ctypes.addressof(n)))
+        shape_out, origin = tuple(int(x) for x in m), tuple(int(x) for x in org)
+        if download:
+            assert host_out.shape == shape_out
+            return int(n.value), shape_out, origin, host_out
+        return int(n.value), shape_out, origin, (int(out) if out else self.regions_mask_result()[1])
+
+    def regions_mask_result(self):
+        "(shape, device pointer, origin, number of ones) of the mask the last regions_select left in the context (cx_grid_regions3d_select_result)"
+        p, m, org, n = ctypes.c_void_p(), np.zeros(3, dtype=np.int64), np.zeros(3, dtype=np.int64), ctypes.c_int64()
+        self._check(self.lib.cx_grid_regions3d_select_result(self.handle, ctypes.byref(p), m.ctypes.data, org.ctypes.data, ctypes.byref(n)))
+        return tuple(int(x) for x in m), int(p.value or 0), tuple(int(x) for x in org), int(n.value)
+
+    def bind_region_mask(self):
+        """the mask the last regions_select left in the context becomes the bound grid (uint8, owned by the context): cx_grid_regions3d_bind.
+        The origin stays what set_origin made it, as across uploads: set_origin(*origin) of the mask makes the march of the crop the
+        march of the whole mask."""
+        self._bind_pending(self.regions_mask_result, self.lib.cx_grid_regions3d_bind)
+
+    def regions_map(self, labels, table, out=None, download=False):
+        """out = table[label], 0 for labels beyond the table (cx_grid_regions3d_map) -> the mapped labels: a numpy array with
+        download=True, else the device pointer `out`, which may be the labels' own pointer (in place).  table: int32 indexed by label."""
+        held = []
+        lptr, on_device, shape = self._locate_labels(labels, held)
+        tab = np.ascontiguousarray(table, dtype=np.int32).reshape(-1)
+        assert out or download, "regions_map: a device pointer to write to, or download=True"
+        host_out = np.empty(shape, dtype=np.int32) if download else None
+        self._check(self.lib.cx_grid_regions3d_map(self.handle, lptr, on_device, shape[0], shape[1], shape[2], tab.ctypes.data if len(tab) else None, len(tab),
+                                                   ctypes.c_void_p(int(out)) if out else None, None if host_out is None else host_out.ctypes.data))
+        return host_out if download else int(out)
+
+    def regions_contacts(self, labels):
+        """the pairs of labels that share a face (cx_grid_regions3d_contacts) -> records of REGION_CONTACT_DTYPE sorted by (a, b), a < b,
+        0 (the background) included as a partner; faces[x]: the sample pairs adjacent along axis x that carry the two labels"""
+        held = []
+        lptr, on_device, shape = self._locate_labels(labels, held)
+        n = ctypes.c_int64()
+        head = (self.handle, lptr, on_device, shape[0], shape[1], shape[2])
+        out = np.zeros(4096, dtype=REGION_CONTACT_DTYPE)      # most volumes have fewer pairs: one pass; else the count, then a second pass
+        rc = self.lib.cx_grid_regions3d_contacts(*head, out.ctypes.data, len(out), ctypes.addressof(n))
+        if rc == CX_ERR_INVALID and n.value > len(out):
+            out = np.zeros(int(n.value), dtype=REGION_CONTACT_DTYPE)
+            rc = self.lib.cx_grid_regions3d_contacts(*head, out.ctypes.data, len(out), ctypes.addressof(n))
+        self._check(rc)
+        return out[:int(n.value)].copy()
 
     def level0_points_f64(self, counts):
         "float64 coordinates of the Level-0 vertices as the reference interpolates them, in download_level0 order"

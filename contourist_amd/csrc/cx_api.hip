@@ -57,6 +57,7 @@ extern "C" int cx_ctx_destroy(cx_ctx* ctx) {
     cx_rank_free(ctx);
     cx_recon_free(ctx);
     cx_watershed_free(ctx);
+    cx_regions_free(ctx);
     cx_state4_free(ctx);
     cx_state2_free(ctx);
     if (ctx->counters_host) (void)hipHostFree(ctx->counters_host);

@@ -214,6 +214,9 @@ struct cx_ctx {
     struct cx_recon_state* recon = nullptr;
     // the marker-based watershed (cx_watershed.hip): a seventh slot; its result is int32 labels, which are not a grid to bind
     struct cx_watershed_state* watershed = nullptr;
+    // the regions of a labelled volume (cx_regions.hip): scratch, the device records and an eighth slot, the cropped mask of
+    // cx_grid_regions3d_select.  The labels are an argument of every call: nothing here refers to them between calls
+    struct cx_regions_state* regions = nullptr;
     // Level-1
     cx_post_state* post = nullptr;
     bool post_valid = false;
@@ -417,6 +420,8 @@ void cx_rank_free(cx_ctx* ctx);
 void cx_recon_free(cx_ctx* ctx);
 // cx_watershed.hip
 void cx_watershed_free(cx_ctx* ctx);
+// cx_regions.hip
+void cx_regions_free(cx_ctx* ctx);
 bool cx_level1_capped(cx_ctx* ctx);   // cx_post.hip: the Level-1 mesh came out of cx_postprocess3d_capped (or is a filtered copy of one)
 // cx_api4d.hip
 void cx_state4_free(cx_ctx* ctx);

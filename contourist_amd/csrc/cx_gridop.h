@@ -1,4 +1,4 @@
-// cx_gridop.h -- the host-side frame of the whole-volume operations (cx_filter, cx_dist, cx_label, cx_resample, cx_rank, cx_recon, cx_watershed):
+// cx_gridop.h -- the host-side frame of the whole-volume operations (cx_filter, cx_dist, cx_label, cx_resample, cx_rank, cx_recon, cx_watershed, cx_regions):
 // where an operation's samples come from, and the slot that keeps its result in the context until it is bound.
 #pragma once
 #include <new>

@@ -937,3 +937,189 @@ def split_touching(samples, value, h, side="high", connectivity=1, sampling=None
     _, maxima_ptr = context.reconstruct_grid("step", 0.0, 0, "dilation", connectivity, "changed", samples=(flat_ptr, "float32", shape3))
     _, markers_ptr = context.label_grid(0.5, "high", connectivity, samples=(maxima_ptr, "uint8", shape3))
     return _flood(context, on_device, field, shape, shape3, markers_ptr, region_ptr, connectivity, "falling", s)[0]
+
+
+# ---- regions of a labelled volume (cx_grid_regions3d*, csrc/cx_regions.hip) ----------------------------------------------------------
+# What reads the labels `split_touching`, `watershed` or `label` made, or any other int32 label array: one record per label (size, box,
+# centroid sums, the extremes and sums of a second array), masks of chosen labels cropped to a box, relabelling through a table, the
+# pairs of labels that share a face, and one surface per label at the cost of its box.  A label <= 0 is background.  Everything is
+# exact and equals a numpy restatement (tests/regions_ref.py) except `vsum` of a float array, whose bound the header states.
+
+def _region_labels(labels):
+    "-> (on_device, the labels int32 and contiguous, their shape, the shape padded to three axes, the `labels` argument of the regions calls)"
+    if grid_field._is_torch(labels):
+        import torch
+        assert labels.is_cuda, "labels: a numpy array or a GPU tensor"
+        t = labels.to(torch.int32).contiguous()
+        shape = tuple(int(n) for n in t.shape)
+        assert 1 <= len(shape) <= 3, "labels of 1 to 3 dimensions"
+        shape3 = (1,) * (3 - len(shape)) + shape
+        torch.cuda.current_stream(t.device).synchronize()      # the labels are there; the context has a stream of its own
+        return True, t, shape, shape3, (t.data_ptr(), shape3)
+    a = np.asarray(labels)
+    assert a.dtype.kind in "iub", "labels: integers"
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    assert 1 <= a.ndim <= 3, "labels of 1 to 3 dimensions"
+    shape3 = (1,) * (3 - a.ndim) + a.shape
+    return False, a, a.shape, shape3, a.reshape(shape3)
+
+
+def _region_context(on_device, t, device):
+    return _context((t.device.index if on_device else None) if device is None else device)
+
+
+def regions(labels, values=None, device=None):
+    """one record (`_ffi.REGION_DTYPE`) per label 1 .. K of an integer label array, K its largest label; record c - 1 belongs to label c:
+    voxels, first, sum, lo, hi, rim as `label(..., measures=True)` gives them (over the three axes of the padded shape) and, with
+    `values` (an array of the labels' shape), n_nan, min_at / max_at (linear indices; ties: the smallest), vmin / vmax, isum, vsum.
+    What scipy.ndimage.find_objects, sum, minimum_position and maximum_position give, in one pass.  A label nobody carries has
+    voxels 0.  Labels and values: numpy arrays or contiguous GPU tensors of 1 to 3 dimensions; the records are a numpy array."""
+    on_device, t, shape, shape3, arg = _region_labels(labels)
+    context = _region_context(on_device, t, device)
+    varg = None
+    if values is not None:
+        v_on_device, v, vshape = _distance_samples(values)
+        assert vshape == shape, "values: the shape of the labels"
+        if v_on_device:
+            import torch
+            torch.cuda.current_stream(v.device).synchronize()
+            varg = (v.data_ptr(), v.dtype, shape3)
+        else:
+            varg = v.reshape(shape3)
+    return context.regions_grid(arg, varg)
+
+
+def _keep_flags(ids):
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    assert len(ids) == 0 or ids.min() >= 0, "ids: labels, 0 for the background"
+    flags = np.zeros(int(ids.max()) + 1 if len(ids) else 1, dtype=np.uint8)
+    flags[ids] = 1
+    return flags
+
+
+def region_mask(labels, ids, box=None, pad=0, device=None):
+    """(uint8 mask, origin): 1 where the label is one of `ids` (0 names the background), cropped to the index box `box` = (lo, hi), both
+    ends included (None: the whole array), grown by `pad` samples (0 .. 8) on every side of every axis; where that leaves the array the
+    mask is 0.  origin = lo - pad: the index of the mask's first sample in the labels' array (negative where the pad leaves it).  A
+    numpy array for numpy labels, a tensor for a tensor."""
+    on_device, t, shape, shape3, arg = _region_labels(labels)
+    context = _region_context(on_device, t, device)
+    ndim, lead = len(shape), 3 - len(shape)
+    lo3, hi3 = [0] * 3, [n - 1 for n in shape3]
+    if box is not None:
+        lo, hi = [list(np.asarray(b, dtype=np.int64).reshape(ndim)) for b in box]
+        lo3[lead:], hi3[lead:] = [int(x) for x in lo], [int(x) for x in hi]
+    pad = int(pad)
+    ext = tuple(hi3[a] - lo3[a] + 1 + 2 * pad for a in range(3))
+    if on_device:
+        import torch
+        out = torch.empty([max(0, e) for e in ext], dtype=torch.uint8, device=t.device)
+        _, shape_out, origin, _ = context.regions_select(arg, _keep_flags(ids), (lo3, hi3), pad, out=out.data_ptr())
+    else:
+        _, shape_out, origin, out = context.regions_select(arg, _keep_flags(ids), (lo3, hi3), pad, download=True)
+    assert tuple(out.shape) == shape_out
+    for _ in range(lead):      # a padded leading axis has one real plane, at index pad
+        out = out[pad]
+    return out, tuple(origin[lead:])
+
+
+def _mapped(context, on_device, t, shape, arg, table):
+    "the labels through the table: a new tensor beside the labels, or a numpy array"
+    if on_device:
+        import torch
+        out = torch.empty_like(t)
+        context.regions_map(arg, table, out=out.data_ptr())
+        return out
+    return context.regions_map(arg, table, download=True).reshape(shape)
+
+
+def relabel(labels, device=None):
+    """(labels, forward_map): the labels renumbered 1 .. M in the order of their values, as skimage.segmentation.relabel_sequential
+    does; forward_map[old] = new (int32, K + 1 entries, 0 for labels nobody carries and for the background)."""
+    on_device, t, shape, shape3, arg = _region_labels(labels)
+    context = _region_context(on_device, t, device)
+    records = context.regions_grid(arg)
+    forward = np.zeros(len(records) + 1, dtype=np.int32)
+    present = records["voxels"] > 0
+    forward[1:][present] = np.arange(1, int(present.sum()) + 1, dtype=np.int32)
+    return _mapped(context, on_device, t, shape, arg, forward), forward
+
+
+def keep_regions(labels, min_voxels=None, rim=None, keep=None, device=None):
+    """the labels with the regions that fail a criterion set to 0; the others keep their ids.  min_voxels=n: at least n voxels;
+    rim=True / False: only regions that touch / do not touch the array's rim (on an axis of the labels; padded leading axes do not
+    count); keep: a bool array over the labels 1 .. K, or a callable that gets the records and returns one."""
+    on_device, t, shape, shape3, arg = _region_labels(labels)
+    context = _region_context(on_device, t, device)
+    records = context.regions_grid(arg)
+    k = len(records)
+    ok = records["voxels"] > 0
+    if min_voxels is not None:
+        ok &= records["voxels"] >= int(min_voxels)
+    if rim is not None:
+        real = 0
+        for axis in range(3 - len(shape), 3):
+            real |= 3 << (2 * axis)
+        touches = (records["rim"] & np.uint32(real)) != 0
+        ok &= touches if rim else ~touches
+    if keep is not None:
+        flags = np.asarray(keep(records) if callable(keep) else keep).astype(bool).reshape(-1)
+        assert len(flags) == k, "keep: one flag per label (%d)" % k
+        ok &= flags
+    table = np.zeros(k + 1, dtype=np.int32)
+    table[1:][ok] = np.flatnonzero(ok) + 1
+    return _mapped(context, on_device, t, shape, arg, table)
+
+
+def contacts(labels, sampling=None, device=None):
+    """the pairs of labels a < b that share a face somewhere (0, the background, included as a partner): records of
+    `_ffi.REGION_CONTACT_DTYPE` sorted by (a, b), faces[x] = the sample pairs adjacent along axis x of the padded shape.  With
+    `sampling` (the lattice steps, one or one per axis) the records get a column `area` = sum over x of faces[x] times the product of
+    the two other steps (a missing leading axis has step 1)."""
+    on_device, t, shape, shape3, arg = _region_labels(labels)
+    context = _region_context(on_device, t, device)
+    found = context.regions_contacts(arg)
+    if sampling is None:
+        return found
+    steps = [1.0] * (3 - len(shape)) + [float(x) for x in _per_axis(sampling, len(shape), 1.0, "sampling")]
+    out = np.zeros(len(found), dtype=np.dtype(_ffi.REGION_CONTACT_DTYPE.descr + [("area", "<f8")]))
+    for name in ("a", "b", "faces"):
+        out[name] = found[name]
+    out["area"] = sum(found["faces"][:, x].astype(np.float64) * (steps[(x + 1) % 3] * steps[(x + 2) % 3]) for x in range(3))
+    return out
+
+
+def region_surfaces(labels, ids=None, mins=None, delta=None, pad=1, device=None):
+    """a generator of (id, points float64 (V, 3), triangles int32 (T, 3)): the surface of every region of `ids` (None: every label some
+    sample carries), each from its own box: the region's mask cropped to the record's box grown by `pad` (>= 1 closes the surface;
+    the rim of the array counts as outside), bound, marched at 0.5 and post-processed.  Points are in the whole volume's coordinates:
+    indices of the labels' array, or index * delta + mins when either is given.  The cost follows the boxes, not the number of
+    labels times the volume.  Labels: a 3-D numpy array or GPU tensor.  The context's bound grid and extraction are replaced."""
+    on_device, t, shape, shape3, arg = _region_labels(labels)
+    assert len(shape) == 3, "3-D labels"
+    context = _region_context(on_device, t, device)
+    records = context.regions_grid(arg)
+    if ids is None:
+        ids = np.flatnonzero(records["voxels"] > 0) + 1
+    scale = np.ones(3) if delta is None else np.asarray(delta, dtype=np.float64).reshape(3)
+    shift = np.zeros(3) if mins is None else np.asarray(mins, dtype=np.float64).reshape(3)
+    try:
+        for c in [int(x) for x in np.asarray(ids).reshape(-1)]:
+            if c < 1 or c > len(records) or records["voxels"][c - 1] == 0:
+                yield c, np.zeros((0, 3), dtype=np.float64), np.zeros((0, 3), dtype=np.int32)
+                continue
+            flags = np.zeros(c + 1, dtype=np.uint8)
+            flags[c] = 1
+            _, _, origin, _ = context.regions_select(arg, flags, (records["lo"][c - 1], records["hi"][c - 1]), pad)
+            context.bind_region_mask()
+            context.set_origin(*origin)      # (the march's tie-breaks hash the volume's own lattice points)
+            context.extract3d(0.5)
+            post = context.postprocess3d()
+            points, triangles = context.download_level1(post)
+            if min(origin) >= 0:      # the post-pass works in the array's own coordinates unless the array starts before the volume
+                points = points + np.asarray(origin, dtype=np.float64)
+            if mins is not None or delta is not None:
+                points = points * scale + shift
+            yield c, points, triangles
+    finally:
+        context.set_origin(0, 0, 0)      # the module's context goes back to an array that starts at the volume's first sample

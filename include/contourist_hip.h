@@ -1069,6 +1069,91 @@ int cx_grid_watershed3d(cx_ctx* ctx, const void* relief, int32_t dtype, int on_d
                         void* out_device, void* out_host, cx_watershed_stats* stats);
 int cx_grid_watershed3d_result(cx_ctx* ctx, void** out_device, int64_t out_shape[3]);
 
+/* ---- regions: measures, cropped masks, contacts and relabelling of a labelled volume, on the device --------------------------------------
+ * What follows a segmentation: per label its size, box, centroid and the extremes and sum of a second array (scipy.ndimage.find_objects,
+ * sum, minimum_position, maximum_position), a mask of chosen labels cropped to a box that binds and marches (one surface per object at
+ * the cost of its box, not of the volume), the pairs of labels that share a face, and a relabelling through a table
+ * (skimage.segmentation.relabel_sequential, dropping, merging).  The reference has no call for it.
+ *
+ * Common to the four calls
+ *   labels, on_device, n0 n1 n2: int32, aligned to 4, in device memory (on_device != 0) or host memory, every axis >= 1, at most 2^29
+ *            samples (CX_ERR_INVALID otherwise, and for NULL).  Any label volume, whichever call made it: the pointers handed out by
+ *            cx_grid_watershed3d_result and cx_grid_label3d_result are legal.  Device labels are read where they lie; host labels go
+ *            up into a buffer of the state.  The context keeps no reference to the labels between calls.
+ *   A label <= 0 is background; a negative label counts as 0 everywhere.
+ *   Every count is an exact integer and every result a pure function of the inputs: two calls give the same bytes, with ONE stated
+ *   exception, vsum of a float array (below).
+ *
+ * cx_grid_regions3d
+ *   K = the largest label, found by a reduction; *k_max receives it, *n_negative the number of negative samples (either may be NULL).
+ *   CX_ERR_UNSUPPORTED when K > CX_REGIONS_MAX_LABEL: the record table is K x 128 bytes on the device and on the host (2 GiB at the
+ *   limit), and labels beyond it are no numbering of regions.  out_host NULL: K only.  Else CX_ERR_INVALID when capacity < K; K == 0 is
+ *   served with any capacity.  Record c - 1 belongs to label c:
+ *     shape    voxels, first, sum, lo, hi, rim as cx_grid_label3d_measures defines them
+ *     n_nan    the samples of the label whose value is NaN
+ *     min_at, max_at  the linear index of the smallest / largest value that is not NaN; among equal values the smallest index; -1: none
+ *     vmin, vmax      those values, exactly (every sample type converts to double exactly); 0 when there is none
+ *     isum     integer sample types: the exact sum of the values; float types: 0
+ *     vsum     integer types: (double)isum; float types: the sum of the values that are not NaN, added up in double
+ *   A label no sample carries has voxels 0, first -1, lo {0,0,0}, hi {-1,-1,-1}, min_at = max_at = -1 and everything else 0.
+ *   values   NULL (the value fields are then those of a label without samples), or an array of the labels' shape of any CX_DTYPE_*
+ *            values_dtype, in host or device memory (values_on_device) independently of the labels.
+ *   Floats are ordered as cx_grid_rank3d orders them: -inf < ... < -0.0 < +0.0 < ... < +inf, NaN excluded and counted.  So vmin of
+ *   {-0.0, +0.0} is -0.0.
+ *   vsum of a float array is built with floating-point atomics, whose order differs from call to call: it is the ONLY field that may
+ *   differ between two calls, and it satisfies |vsum - exact| <= (voxels - 1) * 2^-53 * sum |v|, the bound of a sum of doubles in any
+ *   order (each sample converts to double exactly).
+ * cx_grid_regions3d_select
+ *   keep     n_keep host bytes indexed by label, keep[0] for the background; a label >= n_keep is not kept.
+ *   box_lo, box_hi  an index box, both ends included; both NULL: the whole array.  pad: 0 .. 8.
+ *   The result is the uint8 mask of the array extended by zeros, cropped to [box_lo - pad, box_hi + pad] and contiguous: shape
+ *   box_hi - box_lo + 1 + 2 pad; inside the array keep[label] != 0, outside it 0.  out_shape, out_origin (= box_lo - pad, may be
+ *   negative) and n_voxels (the exact count of ones) may be NULL.
+ *   out_device  not NULL: the mask is written there (any alignment; CX_ERR_INVALID if it overlaps device labels), and the context keeps
+ *            no result.  NULL: it goes into a buffer the context owns and stays pending until the next select or the bind, in an eighth
+ *            slot of its own: the pending results of the seven other volume operations are not disturbed, and the pending pointer is a
+ *            legal `samples` of them (CX_DTYPE_U8, on the device).  out_host not NULL: also receives a copy.
+ *   CX_ERR_INVALID: a box that leaves the array, lo > hi, one end of the box without the other, a pad outside 0 .. 8.
+ * cx_grid_regions3d_select_result: the pending mask: device pointer, shape, origin and count; CX_ERR_STATE when none is pending.
+ * cx_grid_regions3d_bind: the pending mask becomes the bound grid (CX_DTYPE_U8, owned by the context) with every reset of an upload, as
+ *   cx_grid_label3d_bind does it.  The origin is the caller's, as it is across uploads: passing the mask's origin to cx_set_origin,
+ *   which takes negative origins, makes the march of the crop the march of the whole mask.  CX_ERR_INVALID, the mask left pending, for
+ *   an axis shorter than 2; CX_ERR_STATE without a pending mask.
+ * cx_grid_regions3d_map
+ *   out[i] = map[label] for a label in [0, n_map), the negative ones counting as 0, and 0 for a label >= n_map.  map: n_map int32 on the
+ *   host.  Relabelling, dropping small regions and merging regions are all this call.  out_device (aligned to 4) may BE the device
+ *   labels (in place); any other overlap is CX_ERR_INVALID.  out_host also receives a copy; one of the two must be given.  Nothing stays
+ *   pending.
+ * cx_grid_regions3d_contacts
+ *   One record per unordered pair a < b of distinct labels, 0 included as a partner, that are face neighbours somewhere; faces[x] = the
+ *   number of sample pairs adjacent along axis x that carry {a, b}.  Neighbours never wrap across rows or planes.  Records are sorted by
+ *   (a, b).  *n receives their number; out_host NULL: the number only; CX_ERR_INVALID when capacity < n.  Face contacts only.
+ *   CX_ERR_UNSUPPORTED beyond 2^26 pairs.
+ * A call without bind leaves the bound grid, the current extraction, the selected level, the Level-1 state and the seven other pending
+ * results as they are.  tests/regions_ref.py restates all of it in numpy. */
+#define CX_REGIONS_MAX_LABEL (1 << 24)
+typedef struct cx_region {
+    cx_label_component shape;
+    int64_t n_nan;
+    int64_t min_at, max_at;
+    double  vmin, vmax;
+    int64_t isum;
+    double  vsum;
+} cx_region;               /* 128 bytes */
+typedef struct cx_region_contact { int32_t a, b; int64_t faces[3]; } cx_region_contact;      /* 32 bytes */
+int cx_grid_regions3d(cx_ctx* ctx, const int32_t* labels, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                      const void* values, int32_t values_dtype, int values_on_device, cx_region* out_host, int64_t capacity,
+                      int64_t* k_max, int64_t* n_negative);
+int cx_grid_regions3d_select(cx_ctx* ctx, const int32_t* labels, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                             const uint8_t* keep, int64_t n_keep, const int64_t box_lo[3], const int64_t box_hi[3], int32_t pad,
+                             uint8_t* out_device, uint8_t* out_host, int64_t out_shape[3], int64_t out_origin[3], int64_t* n_voxels);
+int cx_grid_regions3d_select_result(cx_ctx* ctx, uint8_t** mask_device, int64_t shape[3], int64_t origin[3], int64_t* n_voxels);
+int cx_grid_regions3d_bind(cx_ctx* ctx);
+int cx_grid_regions3d_map(cx_ctx* ctx, const int32_t* labels, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                          const int32_t* map, int64_t n_map, int32_t* out_device, int32_t* out_host);
+int cx_grid_regions3d_contacts(cx_ctx* ctx, const int32_t* labels, int on_device, int64_t n0, int64_t n1, int64_t n2,
+                               cx_region_contact* out_host, int64_t capacity, int64_t* n);
+
 /* ---- standalone SurfaceGeometry operator ---------------------------------------------------------
  * SurfaceGeometry(vertices, triangles).clean_triangles() / .orient_triangles()
  * (surface_geometry.py:6-12, 14-50, 52-140) on caller-supplied host arrays.
